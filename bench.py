@@ -16,7 +16,12 @@ kernels of the next.
 The capture is resident in HBM before the timed region (the first 5 s are the reference's
 seed-42 generator, tiled to 60 s in HBM -- SURVEY.md section 8(d)).
 
-The one JSON line also carries (rank 0, N = 1; all bounded so the default run stays within minutes):
+A plain run does only what the headline needs: set-up, warm-up, the timed steps, the result line (with `roofline` from
+the HIP events of those same steps) and, with --dump-outputs DIR, the outputs of the last timed step as DIR/<name>.npy.
+
+With --full the one JSON line also carries (rank 0, N = 1; all bounded so the run stays within minutes):
+  cpu_baseline, parity -- the CPU oracle on a bounded sample of the same capture, timed, and the benchmarked audio
+                         compared with it (--no-cpu-baseline drops both).
   value_host_resident -- the same step with the 2.4 GB capture starting in PINNED HOST memory every time (H2D inside
                          the timed region, double-buffered): the PCIe-inclusive rate.  Never `value`.
   configs             -- BASELINE config 1 (the reference's own --benchmark capture, 5 s @ 2.5 MS/s), config 3
@@ -74,22 +79,68 @@ def parse_args():
     # Defaults long enough to time the SUSTAINED rate: after an idle->load edge the part runs ~8 captures at boost
     # clocks, overshoots its 1400 W package limit, is clamped for ~25 captures (channelizer 0.84 ms instead of 0.57)
     # and settles by capture ~40 (profiles/power_trace.sh); 100 + 1000 captures take 0.8 s.
-    ap.add_argument("--steps", type=int, default=1000)
-    ap.add_argument("--warmup", type=int, default=100)
+    # (--axis channels: 5 and 2 when not given; its steps are 300 times as long)
+    ap.add_argument("--steps", type=int, default=None, help="timed steps (default 1000)")
+    ap.add_argument("--warmup", type=int, default=None, help="untimed steps in front of them (default 100)")
     ap.add_argument("--settle", type=int, default=60,
                     help="the untimed phase is at least this many captures long: max(0, settle - warmup) extra untimed "
                          "captures run in front of the warm-up steps (the power-management transient above)")
     ap.add_argument("--seconds", type=float, default=60.0, help="capture length (config 2: 60 s)")
     ap.add_argument("--sample-rate", type=float, default=10e6)
     ap.add_argument("--unique-seconds", type=float, default=5.0, help="seed-42 prefix generated on the host, then tiled")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure cpu_baseline + parity, value_host_resident, the configs array and file_to_wav")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step to DIR/<name>.npy (float32 / float64, at most 64 MB in all; e.g. bench_outputs/)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip cpu_baseline and parity")
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="target CPU time of the cpu_baseline sample")
-    ap.add_argument("--no-extras", action="store_true", help="skip value_host_resident, the configs array and file_to_wav")
+    ap.add_argument("--no-extras", action="store_true", help="--full: skip value_host_resident, the configs array and file_to_wav")
     ap.add_argument("--axis", choices=("captures", "channels"), default="captures",
                     help="captures (default): one independent capture per GPU (BASELINE configs 2 / 4); channels: BASELINE "
                          "config 5 -- one 50 MS/s capture broadcast to every GPU, its 40 channels sharded")
     ap.add_argument("--channels", type=int, default=40, help="--axis channels: NFM channels of the capture (config 5: 40)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    channels = args.axis == "channels"
+    if args.steps is None:
+        args.steps = 5 if channels else 1000
+    if args.warmup is None:
+        args.warmup = 2 if channels else 100
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
+
+
+DUMP_BUDGET = 64_000_000  # bytes of .npy data --dump-outputs may write in all
+DUMP_WINDOW = 4096  # elements per window of a sampled output
+
+
+def dump_outputs(out_dir: str, arrays: dict) -> None:
+    """Write each output as ``out_dir/<name>.npy``: integer and float32 data as float32, float64 as float64, complex as
+    (..., 2) of its real type (re, im).  ``arrays`` maps a name to ``(array, cap_bytes)``; an output larger than its cap is written
+    as a fixed sample instead: whole windows of ``DUMP_WINDOW`` consecutive elements of the flattened array, at window
+    positions drawn with a fixed seed (``<name>.npy`` is then (windows, DUMP_WINDOW[, 2]) and ``<name>_window_starts.npy``
+    holds each window's first flat index).  The same arguments give the same sample."""
+    assert sum(cap for _, cap in arrays.values()) <= DUMP_BUDGET
+    out = Path(out_dir)
+    out.mkdir(parents=True, exist_ok=True)
+    for name, (a, cap) in arrays.items():
+        a = np.asarray(a)
+        pair = np.iscomplexobj(a)
+        kind = np.float64 if a.dtype in (np.float64, np.complex128) else np.float32
+        flat = a.reshape(-1)
+        elem = (2 if pair else 1) * np.dtype(kind).itemsize
+
+        def as_float(x):  # (float copies of the selected elements only)
+            return np.stack([x.real, x.imag], axis=-1).astype(kind) if pair else x.astype(kind)
+
+        if flat.size * elem <= cap:
+            np.save(out / f"{name}.npy", as_float(a))
+            continue
+        n_win = flat.size // DUMP_WINDOW
+        k = min(n_win, cap // (DUMP_WINDOW * elem))
+        starts = np.sort(np.random.default_rng(20261015).choice(n_win, size=k, replace=False)) * DUMP_WINDOW
+        np.save(out / f"{name}.npy", as_float(np.stack([flat[s: s + DUMP_WINDOW] for s in starts])))
+        np.save(out / f"{name}_window_starts.npy", starts.astype(np.float64))
 
 
 class quiet_gc:
@@ -596,8 +647,7 @@ def main_channel_axis(args, json_fd: int) -> None:
         res = runner.collect(runner.submit(raw, enclosing=buf, lead_frames=0))
         return [(r["pcm"], r["demod"].peak) for r in res]  # (device PCM16, valid until this slot's next capture: gathered right away)
 
-    steps = args.steps if args.steps != 1000 else 5  # (the defaults of the capture axis are sized for 0.7 ms steps)
-    warm = args.warmup if args.warmup != 100 else 2
+    steps, warm = args.steps, args.warmup
     for _ in range(warm):
         job.step(stage)
     with quiet_gc():
@@ -629,8 +679,12 @@ def main_channel_axis(args, json_fd: int) -> None:
         "roofline": {"bound": "hbm", "kernel": "k_channelize_mfma_s16_ring_rows_multi", "achieved": round(algo / (elapsed / steps) / 1e9, 2),
                      "peak": HBM_PEAK_GBPS * world, "unit": "GB/s", "frac": round(algo / (elapsed / steps) / 1e9 / (HBM_PEAK_GBPS * world), 5),
                      "traffic": None, "note": "whole step (all launches, demodulators, resamplers, gather) against N x 8 TB/s on the algorithmic "
-                                              "bytes 4 B/frame + 4 B x 48 kHz per channel; the per-kernel figure of this shape is configs[3] of the default run"},
+                                              "bytes 4 B/frame + 4 B x 48 kHz per channel; the per-kernel figure of this shape is configs[3] of --full"},
     }
+    if args.dump_outputs and rank == 0:
+        # what rank 0 receives from the last step: every channel's 48 kHz PCM16, in channel order, and the peak
+        dump_outputs(args.dump_outputs, {"pcm_48k": (np.stack([got[u] for u in sorted(got)]), 56_000_000),
+                                         "audio_peak": (np.array([peak], dtype=np.float64), 64)})
     if distributed:
         import torch.distributed as dist
 
@@ -814,7 +868,7 @@ def main() -> None:
             "audio_samples_48k": int(n48),
             "mix_sign": int(sign),
             "settle_steps": settle,
-            "residency": "capture resident in HBM before the timed region (value); see value_host_resident for the PCIe-inclusive rate",
+            "residency": "capture resident in HBM before the timed region (value); --full adds value_host_resident, the PCIe-inclusive rate",
         },
         "roofline": {
             "bound": "hbm",
@@ -832,8 +886,16 @@ def main() -> None:
     }
     if gather is not None:
         out["config"]["gathers"] = gather.count
+    if args.dump_outputs and rank == 0:
+        # what a caller of the runner receives for the last timed capture: its 48 kHz PCM16 (on the host), the channel-rate
+        # audio, the decimated channel (a fixed sample of it: all three at config 2's size are 81 MB), mixer sign and peak
+        dump_outputs(args.dump_outputs, {"pcm_48k": (res["pcm_host"].numpy(), 16_000_000),
+                                         "audio": (audio.cpu().numpy(), 24_000_000),
+                                         "z": (res["z"].cpu().numpy(), 16_000_000),
+                                         "mix_sign": (np.array([sign], dtype=np.float64), 64),
+                                         "audio_peak": (np.array([res["demod"].peak], dtype=np.float64), 64)})
 
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         from oracle import cpu_ref as O
 
         # bounded sample: ~cpu_seconds of CPU work at the ~19 MS/s this port runs at, in whole reference chunks,
@@ -859,7 +921,7 @@ def main() -> None:
         }
         out["parity"] = {"rms_err_vs_oracle_fs_channel": rms_err(got, ref.audio), "samples_compared": int(ref.audio.size), "bar": 1e-4}
 
-    if rank == 0 and world == 1 and not args.no_extras and not distributed:
+    if args.full and rank == 0 and world == 1 and not args.no_extras and not distributed:
         # -- the same step from pinned host memory (PCIe-inclusive; never `value`) --------------------------------
         try:
             host_pinned = torch.from_numpy(np.tile(host, -(-2 * n_total // host.size))[: 2 * n_total]).pin_memory()
