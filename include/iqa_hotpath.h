@@ -412,6 +412,66 @@ int iqa_psd_frames(int32_t fmt, int32_t iq_order, const void *samples_dev, int64
  * an odd last row is copied; out_dev (ceil(n_rows/2) rows) must not alias rows_dev. */
 int iqa_pair_average_rows(const void *rows_dev, int32_t n_rows, int32_t n_cols, void *out_dev, void *stream);
 
+/* ------------------------------------------------------------------------- *
+ * Audio post-processing: automatic squelch (the reference's --audio-post)    *
+ * ------------------------------------------------------------------------- */
+
+/* ref: squelch.py apply_squelch :186-231 and its helpers :20-118, 164-183.  One call squelches a batch of files
+ * ("segments"): every per-sample array of segment s lives in the workspace at samples [base, base + n), base a
+ * multiple of IQA_SQ_TILE and ascending, so no workgroup straddles two files.  in_dev: float32 frames, segment s
+ * interleaved [n][channels] at float offset in_off.  out_dev: same element offsets, float32 or (out_pcm16) int16 =
+ * rint(y * 32767) saturated; segment s's result is the first (stop - start) * channels elements of its slot.
+ * result_dev: iqa_squelch_result[n_segs].  segs (host) and segs_dev (device copy) hold the same table.
+ * Percentiles (np.percentile, linear): the host gives each query's neighbouring order-statistic indices and the
+ * float32 weight numpy computes (q_index[0..1] / q_gamma[0]: the noise floor; [2..3] / [1]: the 5th and [4..5] / [2]:
+ * the 95th percentile of the adaptive score); the device selects those order statistics exactly and interpolates with
+ * numpy's float32 _lerp.  Dilation reproduces the reference's int8 accumulation: a window count c sets a sample only
+ * where (int8)(c mod 256) > 0.  Enqueues ~30 launches, no synchronisation. */
+#define IQA_SQ_TILE 2048
+typedef enum { IQA_SQ_ADAPTIVE = 0, IQA_SQ_STATIC = 1, IQA_SQ_TRANSIENT = 2 } iqa_sq_method;
+typedef enum {
+    IQA_SQ_STAGE_ENVELOPE_DB = 0, /* float32: _dbfs(_envelope(samples, window)) */
+    IQA_SQ_STAGE_LEVEL = 1,       /* float32: adaptive: envelope - minimum.accumulate(envelope); transient: the dB
+                                     difference of the short and long envelopes; static: unused */
+    IQA_SQ_STAGE_THRESHOLD = 2,   /* float32: the per-sample threshold the mask compared against */
+    IQA_SQ_STAGE_MASK = 3,        /* uint8: the mask before dilation */
+    IQA_SQ_STAGE_DILATED = 4,     /* uint8: _dilate_mask */
+    IQA_SQ_STAGE_GAIN = 5         /* float32: _smooth_gain */
+} iqa_sq_stage;
+typedef struct {
+    int32_t method;      /* iqa_sq_method */
+    int32_t auto_floor;  /* 0: segs[s].manual_floor_db */
+    int32_t trim;        /* trim_silence */
+    int32_t out_pcm16;
+    double margin_db;           /* threshold_margin_db */
+    double transient_margin_db;
+} iqa_squelch_params;
+typedef struct {
+    int64_t n;        /* frames (>= the envelope window, >= the long window for "transient") */
+    int64_t in_off;   /* float offset of the segment's frame 0 in in_dev / out_dev */
+    int64_t base;     /* first workspace sample (multiple of IQA_SQ_TILE) */
+    int32_t channels;
+    int32_t window, short_window, long_window;  /* envelope windows in samples (>= 1) */
+    int32_t hold;     /* dilation head = tail (<= 0: none) */
+    int32_t fade;     /* gain fade (0: the dilated mask itself) */
+    int32_t lead, trail;  /* trim margins in samples */
+    double manual_floor_db;
+    int64_t q_index[6];
+    float q_gamma[3];
+    int32_t reserved;
+} iqa_squelch_seg;
+typedef struct {
+    double noise_floor_db, threshold_db;
+    int64_t start, stop; /* the output is frames [start, stop) of samples * gain */
+} iqa_squelch_result;
+
+/* Workspace of iqa_squelch for `padded_samples` (= last base + n rounded up to IQA_SQ_TILE) and n_segs; -1 if invalid. */
+int64_t iqa_squelch_workspace_bytes(int64_t padded_samples, int32_t n_segs);
+/* Byte offset in that workspace of a per-sample stage array (iqa_sq_stage), valid after iqa_squelch; -1 if invalid. */
+int64_t iqa_squelch_stage_offset(int64_t padded_samples, int32_t n_segs, int32_t stage);
+int iqa_squelch(const iqa_squelch_params *params, const iqa_squelch_seg *segs, int32_t n_segs, const void *segs_dev,
+                const void *in_dev, void *out_dev, void *result_dev, void *work_dev, int64_t work_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -66,6 +66,32 @@ class DemodParams(ctypes.Structure):
                 ("agc_target", c_double), ("agc_decay", c_double)]
 
 
+class SquelchParams(ctypes.Structure):
+    """``iqa_squelch_params`` (include/iqa_hotpath.h)."""
+
+    _fields_ = [("method", c_int32), ("auto_floor", c_int32), ("trim", c_int32), ("out_pcm16", c_int32),
+                ("margin_db", c_double), ("transient_margin_db", c_double)]
+
+
+class SquelchSeg(ctypes.Structure):
+    """``iqa_squelch_seg`` (include/iqa_hotpath.h): one file of a segmented squelch launch."""
+
+    _fields_ = [("n", c_int64), ("in_off", c_int64), ("base", c_int64), ("channels", c_int32), ("window", c_int32),
+                ("short_window", c_int32), ("long_window", c_int32), ("hold", c_int32), ("fade", c_int32),
+                ("lead", c_int32), ("trail", c_int32), ("manual_floor_db", c_double), ("q_index", c_int64 * 6),
+                ("q_gamma", c_float * 3), ("reserved", c_int32)]
+
+
+class SquelchResult(ctypes.Structure):
+    """``iqa_squelch_result`` (include/iqa_hotpath.h)."""
+
+    _fields_ = [("noise_floor_db", c_double), ("threshold_db", c_double), ("start", c_int64), ("stop", c_int64)]
+
+
+SQ_TILE = 2048
+SQ_METHOD = {"adaptive": 0, "static": 1, "transient": 2}
+SQ_STAGE = {"envelope_db": 0, "level": 1, "threshold": 2, "mask": 3, "dilated": 4, "gain": 5}
+
 DEMOD_MODE = {"nfm": 0, "fm": 0, "am": 1, "usb": 2, "ssb": 2, "lsb": 3}
 
 _SIGNATURES = {
@@ -115,6 +141,10 @@ _SIGNATURES = {
     "iqa_psd_frames": (ctypes.c_int, [c_int32, c_int32, c_void_p, c_int64, c_int64, c_int64, c_int32, c_int32, c_int32, c_void_p,
                                       c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "iqa_pair_average_rows": (ctypes.c_int, [c_void_p, c_int32, c_int32, c_void_p, c_void_p]),
+    "iqa_squelch_workspace_bytes": (c_int64, [c_int64, c_int32]),
+    "iqa_squelch_stage_offset": (c_int64, [c_int64, c_int32, c_int32]),
+    "iqa_squelch": (ctypes.c_int, [ctypes.POINTER(SquelchParams), ctypes.POINTER(SquelchSeg), c_int32, c_void_p, c_void_p,
+                                   c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
 }
 
 EXPORTS = tuple(_SIGNATURES)

@@ -1,8 +1,8 @@
 """Command-line shim for the hot path.
 
-Only the reference flags that feed ``ProcessingConfig`` and ``--benchmark*`` exist here
-(reference ``cli.py:151-412, 500-578, 661-741``); the GUI, ``digital`` docker sub-command,
-``--audio-post`` squelch mode and ``--plot-stages`` are out of scope.  Same exit codes
+Only the reference flags that feed ``ProcessingConfig``, ``--benchmark*`` and the ``--audio-post*`` squelch mode
+exist here (reference ``cli.py:151-412, 424-578, 661-741``); the GUI, ``digital`` docker sub-command and
+``--plot-stages`` are out of scope.  Same exit codes
 (0 ok / cancelled, 1 processing error, 2 usage error via argparse), same limits (at most five
 ``--ft`` targets, duplicates within 0.5 Hz rejected), same output naming
 (``audio_<ft>_48k.wav``, ``_<freq>`` suffix on explicit ``--out`` with several targets,
@@ -10,6 +10,7 @@ Only the reference flags that feed ``ProcessingConfig`` and ``--benchmark*`` exi
 
     python -m iq_to_audio_amd.cli --in capture.wav --ft 400025000 --demod nfm
     python -m iq_to_audio_amd.cli --benchmark
+    python -m iq_to_audio_amd.cli --audio-post recordings/ --audio-post-mode adaptive
 """
 from __future__ import annotations
 
@@ -22,6 +23,7 @@ from pathlib import Path
 
 from .benchmark import run_benchmark
 from .processing import MultiChannelPipeline, ProcessingCancelled, ProcessingConfig, ProcessingPipeline
+from .squelch import AudioPostOptions, SquelchConfig, gather_audio_targets, process_audio_batch
 
 LOG = logging.getLogger("iq_to_audio_amd")
 
@@ -79,8 +81,77 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--benchmark-sample-rate", dest="benchmark_sample_rate", type=positive_float, default=2_500_000.0)
     p.add_argument("--benchmark-offset", dest="benchmark_offset", type=float, default=25_000.0)
     p.add_argument("--cli", dest="cli", action="store_true", help="Accepted for compatibility (there is no GUI here).")
+    # reference cli.py:333-398 (same names, dests, defaults and help)
+    p.add_argument("--audio-post", dest="audio_post_path", type=Path,
+                   help="Apply audio post-processing (auto squelch) to the given file or directory.")
+    p.add_argument("--audio-post-mode", dest="audio_post_mode", choices=["adaptive", "static", "transient"],
+                   default="adaptive", help="Squelch algorithm to use when --audio-post is supplied (default: adaptive).")
+    p.add_argument("--audio-post-noise-floor", dest="audio_post_noise_floor", type=float,
+                   help="Manual noise floor in dBFS for --audio-post (auto-detected by default).")
+    p.add_argument("--audio-post-noise-percentile", dest="audio_post_percentile", type=float, default=0.2,
+                   help="Percentile used for auto noise floor estimation (default: 0.2 → 20th percentile).")
+    p.add_argument("--audio-post-threshold", dest="audio_post_threshold", type=float, default=6.0,
+                   help="Margin above noise floor in dBFS for the squelch threshold (default: 6).")
+    p.add_argument("--audio-post-lead", dest="audio_post_lead", type=float, default=0.15,
+                   help="Lead-in seconds retained when trimming silence (default: 0.15).")
+    p.add_argument("--audio-post-trail", dest="audio_post_trail", type=float, default=0.35,
+                   help="Trailing seconds retained when trimming silence (default: 0.35).")
+    p.add_argument("--audio-post-no-trim", dest="audio_post_trim", action="store_false",
+                   help="Disable silence trimming when performing --audio-post.")
+    p.add_argument("--audio-post-overwrite", dest="audio_post_overwrite", action="store_true",
+                   help="Overwrite original files when performing --audio-post (default writes -cleaned copies).")
+    p.add_argument("--audio-post-suffix", dest="audio_post_suffix", default="-cleaned",
+                   help="Suffix to append when writing cleaned copies (default: -cleaned).")
     p.add_argument("--verbose", dest="verbose", action="store_true")
+    p.set_defaults(audio_post_trim=True)
     return p
+
+
+def run_audio_post(args) -> int:
+    """reference cli.py:434-498: squelch every audio file at --audio-post; 0 ok, 1 on any failure."""
+    squelch_config = SquelchConfig(
+        method=args.audio_post_mode,
+        auto_noise_floor=args.audio_post_noise_floor is None,
+        manual_noise_floor_db=args.audio_post_noise_floor,
+        noise_floor_percentile=args.audio_post_percentile,
+        threshold_margin_db=args.audio_post_threshold,
+        trim_silence=args.audio_post_trim,
+        trim_lead_seconds=args.audio_post_lead,
+        trim_trail_seconds=args.audio_post_trail,
+    )
+    post_options = AudioPostOptions(config=squelch_config, overwrite=args.audio_post_overwrite,
+                                    cleaned_suffix=args.audio_post_suffix)
+    try:
+        post_targets = gather_audio_targets(args.audio_post_path, post_options)
+    except Exception as exc:  # noqa: BLE001
+        LOG.error("Unable to enumerate audio targets: %s", exc)
+        return 1
+    if not post_targets:
+        LOG.error("No audio files found at %s.", args.audio_post_path)
+        return 1
+    LOG.info("Audio post-processing %d file(s) via %s squelch (%s).", len(post_targets), squelch_config.method,
+             "overwrite" if post_options.overwrite else f"suffix '{post_options.cleaned_suffix}'")
+
+    def _progress(completed: int, total: int, current: Path) -> None:
+        if total <= 0:
+            LOG.info("Processing %s", current)
+            return
+        completed = max(0, min(completed, total))
+        LOG.info(" [%6.2f%%] %s", (completed / total) * 100.0, current)
+
+    summary = process_audio_batch(post_targets, post_options, progress_cb=_progress)
+    for item in summary.results:
+        LOG.info("%s -> %s | %.2fs → %.2fs | %.1f%% retained | floor %.1f dB | threshold %.1f dB", item.input_path,
+                 item.output_path, item.duration_in, item.duration_out, item.retained_ratio * 100.0, item.noise_floor_db,
+                 item.threshold_db)
+    if summary.errors:
+        LOG.error("Audio post-processing failed on %d file(s).", summary.failed)
+        for path, error in summary.errors:
+            LOG.error(" - %s: %s", path, error)
+        return 1
+    LOG.info("Audio post-processing complete: Δsize %+d bytes, Δduration %+0.2f s.", summary.aggregate_size_delta(),
+             summary.aggregate_duration_delta())
+    return 0
 
 
 def _preview_output_path(config: ProcessingConfig) -> Path:
@@ -92,7 +163,13 @@ def _preview_output_path(config: ProcessingConfig) -> Path:
 def main(argv: list[str] | None = None) -> int:
     parser = build_parser()
     args = parser.parse_args(argv)
+    if args.audio_post_path and args.benchmark:
+        parser.error("--audio-post cannot be combined with --benchmark.")
+    if args.audio_post_path and not 0.0 <= args.audio_post_percentile <= 1.0:
+        parser.error("--audio-post-noise-percentile must be between 0.0 and 1.0.")
     logging.basicConfig(level=logging.DEBUG if args.verbose else logging.INFO, format="%(levelname)s %(message)s")
+    if args.audio_post_path:
+        return run_audio_post(args)
     frequencies = list(args.target_freqs or [])
     container = codec = None
     if args.input_format:

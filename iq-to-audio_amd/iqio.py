@@ -222,3 +222,114 @@ def read_wav_pcm16_mono(path: Path) -> tuple[np.ndarray, int]:
     rate = struct.unpack("<I", raw[24:28])[0]
     n = struct.unpack("<I", raw[40:44])[0]
     return np.frombuffer(raw[44 : 44 + n], dtype="<i2"), rate
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# Audio WAV I/O for the squelch post-processor (the reference reads and writes these through libsndfile,
+# squelch.py:241-260).  Reading follows libsndfile's float normalisation; writing follows the float->PCM rule of
+# encode_iq_slice's WAV leg -- parity of the written bytes with libsndfile is unpinned, as for the other WAV writers.
+
+AUDIO_SUBTYPE_BITS = {"PCM_U8": 8, "PCM_16": 16, "PCM_24": 24, "PCM_32": 32, "FLOAT": 32}
+
+
+def _audio_subtype(fmt_tag: int, bits: int) -> str:
+    if fmt_tag == 1 and bits == 8:
+        return "PCM_U8"
+    if fmt_tag == 1 and bits in (16, 24, 32):
+        return f"PCM_{bits}"
+    if fmt_tag == 3 and bits == 32:
+        return "FLOAT"
+    raise ValueError(f"unsupported WAV encoding (format tag {fmt_tag}, {bits} bits)")
+
+
+def read_wav_audio(path: Path) -> tuple[np.ndarray, int, str]:
+    """Whole WAV file -> (float32 frames [n, channels], sample rate, subtype).  PCM_U8 / PCM_16 / PCM_24 / PCM_32 /
+    FLOAT, mono or multi-channel; integers are normalised as libsndfile reads them: x / 2^(bits-1), U8 (x-128)/128.
+    The file is read completely before this returns (so the caller may overwrite it)."""
+    path = Path(path)
+    raw = path.read_bytes()
+    if len(raw) < 12 or raw[:4] not in (b"RIFF", b"RF64") or raw[8:12] != b"WAVE":
+        raise ValueError(f"{path} is not a RIFF/RF64 WAVE file")
+    fmt_tag = channels = bits = rate = None
+    data = None
+    ds64_len = None
+    pos = 12
+    while pos + 8 <= len(raw):
+        cid, clen = raw[pos:pos + 4], struct.unpack("<I", raw[pos + 4:pos + 8])[0]
+        body = pos + 8
+        if cid == b"ds64" and clen >= 16:
+            ds64_len = struct.unpack("<Q", raw[body + 8:body + 16])[0]
+        elif cid == b"fmt ":
+            fmt_tag, channels, rate, _, _, bits = struct.unpack("<HHIIHH", raw[body:body + 16])
+            if fmt_tag == 0xFFFE and clen >= 26:
+                fmt_tag = struct.unpack("<H", raw[body + 24:body + 26])[0]
+        elif cid == b"data":
+            if raw[:4] == b"RF64" and ds64_len:
+                clen = ds64_len
+            if clen in (0, 0xFFFFFFFF) or body + clen > len(raw):
+                clen = len(raw) - body
+            data = raw[body:body + clen]
+            break
+        pos = body + clen + (clen & 1)
+    if fmt_tag is None or data is None:
+        raise ValueError(f"{path}: missing fmt or data chunk")
+    if not channels:
+        raise ValueError(f"{path}: zero channels")
+    subtype = _audio_subtype(fmt_tag, bits)
+    width = bits // 8
+    n = len(data) // (width * channels)
+    data = data[: n * width * channels]
+    if subtype == "FLOAT":
+        out = np.frombuffer(data, dtype="<f4").astype(np.float32)
+    elif subtype == "PCM_U8":
+        out = ((np.frombuffer(data, dtype=np.uint8).astype(np.float32) - 128.0) / 128.0).astype(np.float32)
+    elif subtype == "PCM_24":
+        b = np.frombuffer(data, dtype=np.uint8).reshape(-1, 3).astype(np.int32)
+        v = (b[:, 0] | (b[:, 1] << 8) | (b[:, 2] << 16)) << 8 >> 8  # sign-extend
+        out = (v.astype(np.float64) / 8388608.0).astype(np.float32)
+    else:
+        v = np.frombuffer(data, dtype="<i2" if bits == 16 else "<i4")
+        out = (v.astype(np.float64) / float(1 << (bits - 1))).astype(np.float32)
+    return out.reshape(n, channels), int(rate), subtype
+
+
+def encode_audio(samples: np.ndarray, subtype: str) -> np.ndarray:
+    """float32 frames -> the subtype's sample values: rint(x * (2^(bits-1) - 1)) saturated, U8 rint(x*127)+128,
+    FLOAT unchanged (encode_iq_slice's WAV rule, extended to 24 and 32 bits)."""
+    x = np.asarray(samples, dtype=np.float32)
+    if subtype == "FLOAT":
+        return x.astype("<f4", copy=False)
+    if subtype == "PCM_U8":
+        return np.clip(np.rint(x.astype(np.float64) * 127.0) + 128.0, 0, 255).astype(np.uint8)
+    bits = AUDIO_SUBTYPE_BITS.get(subtype)
+    if bits is None:
+        raise ValueError(f"unsupported WAV subtype {subtype!r}")
+    top = float((1 << (bits - 1)) - 1)
+    v = np.clip(np.rint(x.astype(np.float64) * top), -top - 1.0, top)
+    return v.astype("<i2" if bits == 16 else "<i4")
+
+
+def write_wav_audio(path: Path, samples: np.ndarray, sample_rate: int, subtype: str = "PCM_16",
+                    *, encoded: np.ndarray | None = None) -> None:
+    """Write float32 frames [n, channels] (or [n]) as a WAV of ``subtype``; ``encoded``: values already in the
+    subtype's sample format (e.g. PCM16 made on the GPU), written as they are."""
+    frames = np.asarray(samples if encoded is None else encoded)
+    channels = 1 if frames.ndim == 1 else int(frames.shape[1])
+    values = encode_audio(frames, subtype) if encoded is None else frames
+    if subtype == "PCM_24":
+        v = np.ascontiguousarray(values, dtype="<i4").reshape(-1).view(np.uint8).reshape(-1, 4)[:, :3]
+        data = np.ascontiguousarray(v).tobytes()
+    else:
+        data = np.ascontiguousarray(values).tobytes()
+    bits = AUDIO_SUBTYPE_BITS[subtype]
+    tag = 3 if subtype == "FLOAT" else 1
+    block = channels * bits // 8
+    hdr = b"RIFF" + struct.pack("<I", 36 + len(data)) + b"WAVE" + b"fmt " + struct.pack(
+        "<IHHIIHH", 16, tag, channels, int(sample_rate), int(sample_rate) * block, block, bits
+    ) + b"data" + struct.pack("<I", len(data))
+    path = Path(path)
+    with path.open("wb") as fh:
+        fh.write(hdr)
+        fh.write(data)
+        if len(data) & 1:
+            fh.write(b"\0")
