@@ -149,8 +149,10 @@ __global__ __launch_bounds__(256) void k_f32_to_s16_exact(const float4 *in, long
 // S = 2^(15 - shift), |lo| <= 16384 -- exact to 2^(shift - 31) of full scale (every step but the last rint is exact in float32: multiplications by
 // powers of two, a difference of neighbours).  The channel filter is linear, so the matrix-core int16 channelizers give
 // z = z(hi) + 2^-15 z(lo): what SDR software writes as (u - 127.5) / 127.5 or k / 32767, resampled or filtered recordings,
-// any float capture within +-1.  flag bit 0: a value outside [-1, 1 - 2^-16] or a NaN (not representable: the caller
-// stays on the float32 kernel); bit 1: some lo != 0 (otherwise the capture IS an int16 capture and one pass suffices).
+// any float capture within +-1.  flag bit 0: a value whose hi = rint(S x) (ties to even) is outside [-32768, 32767], or a
+// NaN (not representable: the caller stays on the float32 kernel) -- at shift 0 x = (32767.5 / 32768) = 1 - 2^-16 rounds
+// to 32768 and is flagged, x = -32768.5 / 32768 rounds to -32768 and is accepted; bit 1: some lo != 0 (otherwise hi alone
+// IS the capture and one pass suffices).  hi and lo of a flagged value are clamped and carry no meaning.
 namespace iqa {
 __global__ __launch_bounds__(256) void k_f32_split_s16(const float4 *in, long long n4, const float *in_tail, int n_tail, float scale,
                                                        short *hi_out, short *lo_out, int *flag)

@@ -946,12 +946,14 @@ PRECISION_GUARD = 1000.0
 
 
 def pick_precision(kernel_for, base: str, demod_mode: str | None, channel_power, wideband_rms, guard: float | None = None,
-                   memo: dict | None = None) -> str:
+                   memo: dict | None = None, floor_scale: float = 1.0) -> str:
     """The cheapest precision, not below ``base``, at which a channel of mean power ``channel_power`` (|z|^2, from the
     mixer-sign probe) in a capture of wideband RMS ``wideband_rms`` keeps the 1e-4 audio bar.  Only NFM is guarded (AM
     and SSB do not divide by |z|).  ``kernel_for(precision)`` returns the planned ``_ChannelKernel``; ``memo`` (a dict the
     caller keeps per channel and sign) remembers each precision's (tap-rounding norm, floor), so that a batch asks the
-    kernels once, not once per capture."""
+    kernels once, not once per capture.  ``floor_scale``: what one unit of the kernel's full scale is worth in the capture's
+    -- 2^shift for a float32 capture run as int16 planes with ``shift`` bits of headroom (hi = rint(2^(15 - shift) x)): the
+    tap-rounding term follows the level and is unchanged, the level-independent floor grows by that factor."""
     levels = _ChannelKernel.PRECISIONS
     guard = PRECISION_GUARD if guard is None else guard
     if not guard or channel_power is None or wideband_rms is None or (demod_mode or "").lower() not in ("nfm", "fm"):
@@ -974,7 +976,7 @@ def pick_precision(kernel_for, base: str, demod_mode: str | None, channel_power,
                 memo[name] = known
         if known is False:
             continue
-        err = math.hypot(known[0] * wideband_rms, known[1])
+        err = math.hypot(known[0] * wideband_rms, floor_scale * known[1])
         if err <= 0.0 or level >= guard * err:
             return name
     return "float32"
@@ -1507,6 +1509,7 @@ class _Target:
             raise ValueError(f"Unsupported iq_order '{cfg.iq_order}'")
         self.chan = None
         self.sign_probe = None
+        self.f32_shift = 0  # headroom bits of the int16 planes a float32 capture runs as (set by the run before settle())
         self.mix_sign = 1
         self.pos_dec = 0
         self.peak = 0.0
@@ -1523,13 +1526,14 @@ class _Target:
     def _pick_precision(self, probe_power, wideband_rms) -> str:
         """The precision this target's channelizer runs at: "full" for SSB with the AGC on, otherwise "fast" unless the
         precision guard asks for more.  A float32 capture that may run as int16 (``f32_integer_path``) is judged by its
-        int16 twin -- that is the kernel its blocks take."""
+        int16 twin -- that is the kernel its blocks take, on planes with ``f32_shift`` bits of headroom."""
         base = "fast" if self.demod is None else base_precision(self.cfg.demod_mode, self.cfg.agc_enabled)
-        fmt = self.info.fmt
+        fmt, floor_scale = self.info.fmt, 1.0
         if fmt == "f32" and getattr(self.owner, "f32_integer_path", False):
-            fmt = "s16"
+            fmt, floor_scale = "s16", 2.0 ** self.f32_shift
         return pick_precision(lambda name: self._channelizer(self.mix_sign, fmt=fmt, precision=name)._kernel, base,
-                              None if self.demod is None else self.cfg.demod_mode, probe_power, wideband_rms, self.precision_guard)
+                              None if self.demod is None else self.cfg.demod_mode, probe_power, wideband_rms, self.precision_guard,
+                              floor_scale=floor_scale)
 
     def begin(self, warm) -> None:
         """Launch the mixer-sign probes (asynchronously) and plan the channelizer for the likely sign meanwhile."""
@@ -1734,7 +1738,16 @@ class MultiChannelPipeline:
             level = D.zeros(1, "float64")
             queue_raw_level(warm, info.fmt, level)
             wideband_rms = wideband_rms_from(float(level.item()), info.fmt)
+            # float32 captures as int16 planes: headroom from the warm-up block's largest value (a later block that exceeds
+            # it falls back to the float32 kernel); decided before settle(), whose precision guard scales by it
+            shift16 = 0
+            if info.fmt == "f32" and self.owners[0].f32_integer_path:
+                top = float(warm.view(D.torch_mod().float32).abs().max().item())
+                while shift16 < 8 and top * 2.0 ** (15 - shift16) > 32767.0:
+                    shift16 += 1
+            self.f32_shift = shift16
             for t in targets:
+                t.f32_shift = shift16
                 t.settle(wideband_rms)
             if cfg.probe_only:
                 tracker.advance("ingest", float(warm.numel() // 2))
@@ -1748,28 +1761,28 @@ class MultiChannelPipeline:
                 members = [t for t in targets if t.decimation == key]  # (a bank runs its "full" / "float32" members one by one)
                 banks.append((ChannelBank([t.chan for t in members]), members))
             self.banks = [b for b, _ in banks]
-            # float32 captures that are integer captures in disguise (every value k / 32768: what SDR software writes for
-            # int16 / 12-bit / int8 ADC samples): each block is re-packed to int16 on the device, checked value by value
-            # (iqa_f32_to_s16_exact), and takes the matrix-core channelizers; the first block that is NOT of that form
-            # switches the rest of the run to the float32 kernel (whose state has been carried along all the time).
-            # Every other float32 capture within the planes' range (RTL-SDR's (u - 127.5) / 127.5, k / 32767, resampled or
-            # filtered recordings) is TWO int16 planes, x = 2^shift (hi + lo / 32768) / 32768 exactly to 2^(shift - 31)
-            # (iqa_f32_split_s16), and the filter is linear: z = 2^shift (z(hi) + 2^-15 z(lo)), two passes of the int16
-            # channelizers (the second at "fast": its input is 2^-15 of the first's).
+            # float32 captures run on the int16 matrix-core channelizers: each block is split on the device into TWO int16
+            # planes, x = 2^shift (hi + lo / 32768) / 32768 exactly to 2^(shift - 31) (iqa_f32_split_s16), and the filter is
+            # linear: z = 2^shift (z(hi) + 2^-15 z(lo)), two passes of the int16 channelizers (the second at "fast": its input
+            # is 2^-15 of the first's).  A block whose low plane is all zeros (every value k / 32768 at shift 0: what SDR
+            # software writes for int16 / 12-bit / int8 ADC samples) needs only the hi pass unless the low plane's history
+            # reaches into it (below).  The first block with a value the planes cannot hold (rint(2^(15 - shift) x) outside
+            # int16, or a NaN) switches the rest of the run to the float32 kernel, whose state has been carried along.
             banks16 = banks16_lo = None
-            shift16 = 0
             if info.fmt == "f32" and self.owners[0].f32_integer_path:
                 banks16 = [(ChannelBank([t._channelizer(t.mix_sign, precision=t.precision, fmt="s16") for t in members]), members)
                            for _, members in banks]
                 banks16_lo = [(ChannelBank([t._channelizer(t.mix_sign, precision="fast", fmt="s16") for t in members]), members)
                               for _, members in banks]
                 flag16 = D.zeros(1, "int32")
-                # headroom from the warm-up block's largest value (a later block that exceeds it falls back to the float32 kernel)
-                top = float(warm.view(D.torch_mod().float32).abs().max().item())
-                while shift16 < 8 and top * 2.0 ** (15 - shift16) > 32767.0:
-                    shift16 += 1
-            self.integer_blocks = 0  # blocks of a float32 capture that ran as int16 (one plane)
-            self.split_blocks = 0  # blocks of a float32 capture that ran as two int16 planes
+                # the low plane's channelizers carry the last L-1 frames of the low plane into the next block: while those
+                # may hold a non-zero value, a block whose own low plane is all zeros still has outputs at its head that
+                # they reach (2^-15 z(lo) there), so the low plane is processed; frames of all-zero low plane seen since the
+                # last block that had one (the history is zero from the start)
+                lo_hist_frames = max(len(t.taps) for t in targets) - 1
+                lo_quiet = lo_hist_frames
+            self.integer_blocks = 0  # blocks of a float32 capture that ran as int16 planes with an all-zero low plane
+            self.split_blocks = 0  # blocks of a float32 capture that ran as int16 planes with some lo != 0
             done = 0
             while done < total:
                 _check_cancel(f"block at frame {done}")
@@ -1781,7 +1794,7 @@ class MultiChannelPipeline:
                 tracker.advance("ingest", float(n))
                 tracker.status(f"channel @ {done}")
                 raw16 = raw16_lo = None
-                lo_needed = False
+                lo_nonzero = lo_needed = False
                 if banks16 is not None:
                     raw16, raw16_lo = D.empty(2 * n, "int16"), D.empty(2 * n, "int16")
                     flag16.zero_()
@@ -1793,7 +1806,8 @@ class MultiChannelPipeline:
                                  shift16, done)
                         banks16 = banks16_lo = raw16 = raw16_lo = None
                     else:
-                        lo_needed = bool(bits & 2)
+                        lo_nonzero = bool(bits & 2)
+                        lo_needed = lo_nonzero or lo_quiet < lo_hist_frames
                 for bi, (bank, members) in enumerate(banks):  # one pass over the block per decimation, all its channels at once
                     for t in members:
                         t.before_block(done, n, chunk)
@@ -1802,7 +1816,7 @@ class MultiChannelPipeline:
                         if lo_needed:
                             zs_lo = banks16_lo[bi][0].process(raw16_lo)
                             zs = [z.add_(zl, alpha=2.0 ** -15) for z, zl in zip(zs, zs_lo)]
-                        else:  # (nothing in the low plane of this block: its channelizers' history and position move along)
+                        else:  # (low plane and its history all zeros: z(lo) = 0, its channelizers' history and position move along)
                             for c in banks16_lo[bi][0].chans:
                                 c._advance(raw16_lo, n)
                         if shift16:
@@ -1815,8 +1829,9 @@ class MultiChannelPipeline:
                     for t, z in zip(members, zs):
                         t.after_block(z, tracker)
                 if raw16 is not None:
-                    self.integer_blocks += 0 if lo_needed else 1
-                    self.split_blocks += 1 if lo_needed else 0
+                    self.integer_blocks += 0 if lo_nonzero else 1
+                    self.split_blocks += 1 if lo_nonzero else 0
+                    lo_quiet = 0 if lo_nonzero else lo_quiet + n
                 for bi, (_, members) in enumerate(banks):
                     for ti, t in enumerate(members):  # (for finish(): which kernel produced this target's last block)
                         t.chan16_kernel = banks16[bi][0].chans[ti]._kernel.last_kernel if raw16 is not None else None

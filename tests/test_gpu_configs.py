@@ -616,20 +616,30 @@ def dynamic_range_capture(n=4_000_000, fs=10e6, weak_db=-70.0):
     return np.rint(np.clip(iq, -0.999, 0.999) * 32767.0).astype(np.int16)
 
 
-@pytest.mark.parametrize("container", ["cs16", "cf32"])
+@pytest.mark.parametrize("container", ["cs16", "cf32", "cf32-shift1"])
 def test_precision_guard_routes_a_very_weak_nfm_channel_to_a_finer_precision(A, tmp_path, container):
     """The pipeline's precision guard (processing.pick_precision): the dynamic-range capture of the test above
     (0.95 tone, an NFM signal at -70 dBFS 300 kHz beside it) as a file, two NFM targets in one run -- the weak signal and
     the tone itself.  The weak channel's probed level is below guard x (expected z error of the "fast" kernel at this
     wideband level), so it runs at "fine" and meets the north-star bar (1e-4) where "fast" would be 2.8e-4 off; the strong
     channel stays "fast".  ``cf32``: the same capture stored as float32 (values k / 32768): its blocks run as int16 on the
-    matrix cores (``f32_integer_path``) and the guard must judge THAT kernel, not the float32 one the format maps to."""
+    matrix cores (``f32_integer_path``) and the guard must judge THAT kernel, not the float32 one the format maps to.
+    ``cf32-shift1``: the capture divided by 32767 (off the 2^-15 grid) with one +-1.0 frame in the warm-up chunk: two int16
+    planes with one bit of headroom, whose level-independent error floor is twice the int16 kernel's -- the guard must
+    scale it, so the weak channel still meets the bar."""
     from iq_to_audio_amd import iqio
 
     fs, n, fc = 10e6, 4_000_000, 1.0e9
     raw = dynamic_range_capture(n, fs)
-    path = tmp_path / f"dyn_1000000000Hz.{container}"
-    path.write_bytes(raw.tobytes() if container == "cs16" else (raw.astype(np.float32) / 32768.0).astype(np.float32).tobytes())
+    path = tmp_path / f"dyn_1000000000Hz.{container.split('-')[0]}"
+    if container == "cs16":
+        data = raw
+    elif container == "cf32":
+        data = (raw.astype(np.float32) / 32768.0).astype(np.float32)
+    else:
+        data = (raw.astype(np.float32) / np.float32(32767.0)).astype(np.float32)
+        data[1000] = (1.0, -1.0)
+    path.write_bytes(data.tobytes())
     cfgs = [A.ProcessingConfig(in_path=path, target_freq=fc + off, demod_mode="nfm", input_sample_rate=fs,
                                output_path=tmp_path / f"g{i}.wav") for i, off in enumerate((1.0e6, 1.3e6))]
     multi = A.MultiChannelPipeline(cfgs)
@@ -638,11 +648,19 @@ def test_precision_guard_routes_a_very_weak_nfm_channel_to_a_finer_precision(A, 
     res = multi.run()
     if container == "cf32":
         assert multi.integer_blocks >= 1  # the blocks ran as int16
-    # the weak target clears the guard at "fine" (two lanes per tap-row group on the same ring kernel); the strong one stays "fast"
-    assert [o.channelizer_precision for o in multi.owners] == ["fine", "fast"]
+    if container == "cf32-shift1":
+        assert multi.f32_shift == 1 and multi.split_blocks >= 1  # two int16 planes with one bit of headroom
+        assert multi.owners[0].channelizer_precision in ("fine", "full") and multi.owners[1].channelizer_precision == "fast"
+    else:
+        # the weak target clears the guard at "fine" (two lanes per tap-row group on the same ring kernel); the strong one
+        # stays "fast"
+        assert [o.channelizer_precision for o in multi.owners] == ["fine", "fast"]
     assert [o.channelizer_kernel for o in multi.owners] == ["k_channelize_mfma_s16_ring", "k_channelize_mfma_s16_ring"]
     for off, r, o in zip((1.0e6, 1.3e6), res, multi.owners):
-        want = O.run_chain(raw, sample_rate=fs, freq_offset=off, keep_decimated=False)
+        if container == "cf32-shift1":
+            want = O.run_chain(data.reshape(-1), sample_rate=fs, freq_offset=off, fmt="f32", keep_decimated=False)
+        else:
+            want = O.run_chain(raw, sample_rate=fs, freq_offset=off, keep_decimated=False)
         got = o.audio_fs_channel.cpu().numpy()
         assert got.size == want.audio.size and r.mix_sign == want.mix_sign
         err = rms(got - want.audio)
