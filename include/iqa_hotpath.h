@@ -136,12 +136,13 @@ typedef struct {
                                 * its LDS does not depend on outputs_per_block); 64|128 = the ring with 256*S1 + S2
                                 * in one int32, for fragments from a quantisation that bounds that sum
                                 * (dsp_plan.plan_mfma(acc32=True); iqa_mfma_ring_mode(fmt, D, k_first, k_count, 1) != 0);
-                                * bits 0..5 are timing diagnostics, never set in production; 256 = the low tap byte
+                                * bits 0..5 are timing diagnostics of the per-lane kernel, never
+                                * set in production; the ring ignores them; 256 = the low tap byte
                                 * of these fragments is zero throughout (a hint: the multi-lane launches act on it, lane bit 1) */
     double unit;               /* value of one tap LSB (ingest scale folded in) */
     double c_re, c_im;         /* 128 * sum of quantised taps per output component (low-byte bias) */
-    void *debug_stamps;        /* NULL in production; diagnostics builds write per-wave cycle stamps here
-                                * (64 B per wave) when bit 1 of `reserved` is set */
+    void *debug_stamps;        /* NULL in production; the per-lane kernel writes per-wave cycle stamps here
+                                * (64 B per wave) when bit 1 of `reserved` is set (the ring kernels never do) */
     int32_t q_group;           /* tap rows 64*q_group+1 .. 64*q_group+64 */
     int32_t k_first;           /* first k step (32 int16 values each) of this pass */
     int32_t k_count;           /* k steps in this pass; 0 = all remaining */

@@ -7,8 +7,6 @@ streams, events, buffer slots -- no arithmetic.
 """
 from __future__ import annotations
 
-import contextlib
-
 from ctypes import c_int32, c_int64, c_void_p
 
 import numpy as np
@@ -49,15 +47,12 @@ class ResidentCaptureRunner:
     SSB with the AGC on starts at the "full" precision (``processing.base_precision``).
     """
 
-    #: submit(resident=True): demodulator + resampler of capture i on their own stream, beside the channelizer of capture i + 1
-    tail_beside_next = bool(int(__import__("os").environ.get("IQA_TAIL_STREAM", "0")))
     # Output buffers in flight.  Three: the PCM16 copy of capture i (a handful of workgroups on the egress stream) is meant to
     # run beside the channelizer of capture i + 1, but a channelizer whose workgroups fill every SIMD's register file (twelve
     # waves of 160+ registers: the byte-plane kernels at 12-13 k steps) leaves it no wave slot -- the copy then completes when
     # that channelizer ends, and with two buffers the host could not queue capture i + 2 before: a bubble of one host
     # submission per capture (config 4's unit: 1.35 ms per capture for a 0.95 ms kernel).
     SLOTS = 3
-    probe_behind_channelizer = bool(int(__import__("os").environ.get("IQA_PROBE_BEHIND", "1")))  # submit(resident=True): see _chain
 
     def __init__(self, taps: np.ndarray, *, sample_rate: float, freq_offset: float, decimation: int, fs_channel: float,
                  chunk: int, n_frames: int, demod_mode: str = "nfm", deemph_us: float = 300.0, agc_enabled: bool = True,
@@ -168,31 +163,14 @@ class ResidentCaptureRunner:
         if resident:
             aux_done = torch.cuda.Event()
             aux_done.record(self.aux)
-            if self.tail_beside_next:
-                D.side_stream("tail").wait_event(aux_done)
-            else:
-                self.compute.wait_event(aux_done)  # start-up outputs and decoder state are in place (long ago)
+            self.compute.wait_event(aux_done)  # start-up outputs and decoder state are in place (long ago)
         if probe is not None:
             probe._done = [aux_done] if resident else [gate]
-        tail_done = None
-        if resident and self.tail_beside_next:
-            # demodulator + resampler on a stream of their own: they run beside the NEXT capture's channelizer (whose
-            # workgroups leave them LDS and registers on every CU, see IQA_RING_ROUNDS_MAX) instead of in front of it
-            tail = D.side_stream("tail")
-            tail.wait_event(ring_done)
-            with D.on_stream(tail, self.compute):
-                dem.process(slot["z"], self.starts, slot["audio"])
-                pcm = self.rs.process(slot["audio"], want="pcm16")
-                for t_ in (slot["z"], slot["audio"], pcm):
-                    t_.record_stream(tail)
-                tail_done = torch.cuda.Event()
-                tail_done.record(tail)
-        else:
-            dem.process(slot["z"], self.starts, slot["audio"])
-            pcm = self.rs.process(slot["audio"], want="pcm16")  # the float32 48 kHz stream is never stored
+        dem.process(slot["z"], self.starts, slot["audio"])
+        pcm = self.rs.process(slot["audio"], want="pcm16")  # the float32 48 kHz stream is never stored
         done = torch.cuda.Event()
         # tail_done: recorded lazily (tail_event) -- the next capture's gate lies behind it anyway
-        ticket = dict(chan=chan, dem=dem, pcm=pcm, done=done, tail_done=tail_done, kernel=chan._kernel.last_kernel,
+        ticket = dict(chan=chan, dem=dem, pcm=pcm, done=done, tail_done=None, kernel=chan._kernel.last_kernel,
                       slot=slot, egress_queued=False, resident=resident, precision=chan.precision, probe=probe)
         self._egress_pending = ticket
         return ticket
@@ -217,8 +195,6 @@ class ResidentCaptureRunner:
         torch = D.torch_mod()
         if gate is not None:
             self.egress.wait_event(gate)  # (behind the capture's last kernel too: same stream, recorded later)
-            if t.get("tail_done") is not None:
-                self.egress.wait_event(t["tail_done"])  # (its tail ran on a stream of its own)
         else:
             self.egress.wait_event(self.tail_event(t))
         # (called with the compute stream current: from submit/_chain and from collect)
@@ -264,7 +240,7 @@ class ResidentCaptureRunner:
             self.aux.wait_event(self._ring_done)
         sign = self.override if self.override is not None else self._spec_sign
         halo = (enclosing, int(lead_frames)) if enclosing is not None else None
-        if resident and self.probe_behind_channelizer:
+        if resident:
             ticket = self._chain(raw_dev, slot, sign, events, halo, resident, None, self._spec_precision,
                                  make_probe=lambda: self._probe(raw_dev, True))
         else:
@@ -463,22 +439,6 @@ class ResidentBankRunner:
 
     SLOTS = 3  # output buffers in flight: with the tails of capture i finishing somewhere inside the pass of capture i + 1, a
                # third slot lets the host queue capture i + 2 without waiting for them
-    overlap_tails = True  # the per-target chains of capture i beside the channelizer pass of capture i + 1
-    # Where a capture's float32 edge launches and combine launches go: False = the caller's stream, between the passes (they
-    # are short); True = the tails' stream, "own" = a third stream.  On a side stream they kept the caller's stream free for
-    # the passes while the previous capture's chains found room BESIDE a pass; behind a pass of twelve waves x 160+
-    # registers per workgroup the chains finish late, and everything queued behind them -- these launches, and with them the
-    # next pass -- waited: config 3 measured 13.6 ms per capture (= everything on one stream) against 13.2-13.3 with them on
-    # the caller's stream (profiles/r03_c3_tail_modes.txt).
-    edges_on_side = False
-    #: the mixer-sign probes of a capture on the tails' stream (read at ``collect`` only) instead of the caller's, in front of its pass
-    probes_on_side = bool(int(__import__("os").environ.get("IQA_PROBES_ON_SIDE", "0")))
-    #: streams the targets' chains of one capture are spread over (target i on stream i % tail_streams).  One: the chains
-    #: follow one another (each is a handful of small dependent kernels, latency-bound).
-    tail_streams = int(__import__("os").environ.get("IQA_TAIL_STREAMS", "1"))
-    #: the next capture's pass waits for this capture's chains (they then have the whole part to themselves -- for passes
-    #: whose workgroups leave no registers for another kernel's waves beside them)
-    pass_waits_for_tails = bool(int(__import__("os").environ.get("IQA_PASS_WAITS_FOR_TAILS", "0")))
 
     def __init__(self, targets: list, *, sample_rate: float, n_frames: int, chunk_size: int = 1_048_576,
                  fs_ch_target: float = 96_000.0, fmt: str = "s16", iq_order: str = "iq", precision_guard: float | None = None):
@@ -547,25 +507,23 @@ class ResidentBankRunner:
             self.collect(slot["busy"])
         warm = raw_dev[: 2 * min(self.chunk, self.n_frames)] if self.fmt != "f32" else raw_dev[: min(self.chunk, self.n_frames)]
         main = torch.cuda.current_stream()
-        side = D.side_stream("tail") if self.overlap_tails else None
-        if side is not None:  # the capture is resident when submit is called: what depends on it alone may start now
-            arrived = torch.cuda.Event()
-            arrived.record(main)
-            side.wait_event(arrived)
+        side = D.side_stream("tail")  # the targets' chains (see _submit_rest)
+        # the capture is resident when submit is called: what depends on it alone may start now
+        arrived = torch.cuda.Event()
+        arrived.record(main)
+        side.wait_event(arrived)
         # (the probes stay on the caller's stream: as ring-kernel launches they want most of a CU's LDS and would sit behind
         # the running pass until it ends, one per pass boundary; through the float32 kernel -- MixSignProbe(matrix_cores=
         # False) -- they fit beside it but the long filters' probes then take longer than the pass has room for: 10.4
         # against 9.4 ms per capture at config 3)
-        probe_ctx = D.on_stream(side, main) if (self.probes_on_side and side is not None) else contextlib.nullcontext()
-        with probe_ctx:
-            probes = self._queue_probes(warm, slot)
+        probes = self._queue_probes(warm, slot)
         signs = [s["mix_sign"] if s["mix_sign"] in (1, -1) else sp for s, sp in zip(self.targets, self._spec_sign)]
         precisions = list(self._spec_precision)
         chans = [self._channelizer(s, sg, pr) for s, sg, pr in zip(self.targets, signs, precisions)]
         for c in chans:
             c.plan_ahead()
         halo = (enclosing, int(lead_frames)) if enclosing is not None else None
-        return self._submit_rest(raw_dev, slot, probes, signs, precisions, chans, halo, events, main, side, arrived if side is not None else None)
+        return self._submit_rest(raw_dev, slot, probes, signs, precisions, chans, halo, events, main, side)
 
     def _queue_probes(self, warm, slot) -> list:
         todo = [i for i, s in enumerate(self.targets) if s["mix_sign"] not in (1, -1)]
@@ -582,63 +540,33 @@ class ResidentBankRunner:
                       for s in self.targets]
         return probes
 
-    def _submit_rest(self, raw_dev, slot, probes, signs, precisions, chans, halo, events, main, side, arrived) -> dict:
+    def _submit_rest(self, raw_dev, slot, probes, signs, precisions, chans, halo, events, main, side) -> dict:
         torch = D.torch_mod()
-        if self.pass_waits_for_tails:
-            for ev in self.__dict__.pop("_tails_done", []):
-                main.wait_event(ev)
         if events:
             events[0].record()
         bank = ChannelBank(chans)
-        # edges_on_side: True = the tails' stream (one queue: edges, combines and chains of the captures one after the other);
-        # "own" = a stream of their own -- the chains of capture i - 1, which find little room beside a pass whose workgroups fill
-        # the register files and finish late, then do not stand between pass i and its combine launches
-        own = self.edges_on_side in ("own", "edges")
-        edge = None if not self.edges_on_side or side is None else (D.side_stream("edge") if own else side)
-        if edge is not None and edge is not side:
-            edge.wait_event(arrived)
-        bank.combines_on_edge_stream = self.edges_on_side != "edges"  # "edges": only the edge launches leave the caller's stream
-        bank.process(raw_dev, outs=[p["z"] for p in slot["per"]], last_block=True, halo=halo, edge_stream=edge)
-        if edge is not None and edge is not side:
-            combined = torch.cuda.Event()
-            combined.record(edge)
-            side.wait_event(combined)
+        # The float32 edge launches and the combine launches stay on the caller's stream, between the passes (they are short).
+        # On a side stream they would queue behind the previous capture's chains, which finish late beside a pass of twelve
+        # waves x 160+ registers per workgroup, and hold up the next pass with them (profiles/r03_c3_tail_modes.txt).
+        bank.process(raw_dev, outs=[p["z"] for p in slot["per"]], last_block=True, halo=halo)
         if events:
             events[1].record()
         self.last_bank_launches = getattr(bank, "launches", None) or [bank.last_launch]  # (one entry per shared launch of the capture)
         # The targets' demodulator / resampler / copy chains run on ONE side stream behind the channelizer pass (and behind
-        # this capture's probes and float32 edge launches, queued there above), so the next capture's channelizer pass
-        # (other slot, caller's stream) does not wait for them.  The pass is
-        # matrix-bound and leaves 16 CUs idle (240 workgroups): the small kernels find room there and beside it.  (One
-        # stream per TARGET was measured and dropped: 14.2 against 11.3 ms per capture.)
-        if side is not None:
-            after_pass = torch.cuda.Event()
-            after_pass.record(main)
-            side.wait_event(after_pass)
-            sides = [side] + [D.side_stream(f"tail{k}") for k in range(1, max(1, min(self.tail_streams, len(slot["per"]))))]
-            for extra in sides[1:]:  # (behind the pass and behind what the first side stream had queued before it: probes, edges, combines)
-                behind_side = torch.cuda.Event()
-                behind_side.record(side)
-                extra.wait_event(behind_side)
-            for k, per in enumerate(slot["per"]):
-                st = sides[k % len(sides)]
-                with D.on_stream(st, main):
-                    self._finish_target(per)
-                    for key in ("z", "audio"):
-                        per[key].record_stream(st)
-            done = torch.cuda.Event()
-            for extra in sides[1:]:
-                joined = torch.cuda.Event()
-                joined.record(extra)
-                side.wait_event(joined)
-            done.record(side)
-            if self.pass_waits_for_tails:
-                self._tails_done = [done]
-        else:
-            for per in slot["per"]:
+        # this capture's arrival), so the next capture's channelizer pass (other slot, caller's stream) does not wait for
+        # them.  The pass is matrix-bound and leaves 16 CUs idle (240 workgroups): the small kernels find room there and
+        # beside it.  The chains follow one another (each is a handful of small dependent kernels, latency-bound; one stream
+        # per TARGET was measured and dropped: 14.2 against 11.3 ms per capture).
+        after_pass = torch.cuda.Event()
+        after_pass.record(main)
+        side.wait_event(after_pass)
+        for per in slot["per"]:
+            with D.on_stream(side, main):
                 self._finish_target(per)
-            done = torch.cuda.Event()
-            done.record()
+                for key in ("z", "audio"):
+                    per[key].record_stream(side)
+        done = torch.cuda.Event()
+        done.record(side)
         ticket = dict(slot=slot, probes=probes, signs=signs, precisions=[c.precision for c in chans], raw=raw_dev, halo=halo, done=done,
                       launch=bank.last_launch, kernel=chans[0]._kernel.last_kernel, collected=False)
         slot["busy"] = ticket

@@ -22,105 +22,20 @@
 //     block is not bounded by LDS: every CU gets ONE contiguous range of the launch (persistent blocks:
 //     one prologue per CU, 63 rows of halo per CU).
 //
-// Round 3: up to 13 k steps (and in every row-staged int16 kernel) the LDS-DMA copies are replaced by LOADER WAVES that fetch
-// the tiles into registers, split every int16 into its high byte and its biased low byte once per tile and write two byte
-// planes per slot; the multiplying waves read their MFMA operands as they lie in LDS (IQA_RING_SPLIT_STAGE below says what
-// that bought).  The ring of such a kernel is two slots per parity in LDS plus two or three rounds of loads in the loaders'
-// registers; the loaders also emit.  The text above describes the LDS-DMA form, which remains for uint8 captures and for
-// 14..16 k steps.  Up to 8 k steps a row whose last k step is at most half full ends in 32x32x16 MFMAs (the ..._half kernels).
+// Round 3: up to 13 k steps (and in every row-staged int16 kernel) LOADER WAVES feed the ring: they fetch the tiles into
+// registers, split every int16 into its high byte and its biased low byte once per tile and write two byte planes per slot;
+// the multiplying waves read their MFMA operands as they lie in LDS (RingGeo::SPLIT says what that bought).  The ring of
+// such a kernel is two slots per parity in LDS plus two rounds (lane pairs: three) of loads in the loaders' registers; the
+// loaders also emit.  The text above describes the LDS-DMA form, which remains at 14..16 k steps (the multiplying waves
+// issue the DMAs) and for uint8 captures (two loader waves issue them, ring_loader).  Up to 8 k steps a row whose last k
+// step is at most half full ends in 32x32x16 MFMAs (the ..._half kernels).  The forms measured against these and rejected
+// are recorded in DESIGN.md section 6.
 //
 // A contiguous slot is 1024*(2*KS + 1) bytes >= 32 rows at a pitch of D/4 (+1) 16-byte units (KS = ceil(2D/32) k steps;
 // the K padding of the last k step reads on into the next row, against zero taps); a tile takes 2*KS + 1 DMA
 // instructions; it needs D % 4 == 0 (16-byte aligned rows for ds_read_b128) and KS <= 16.
 // Every other decimation (odd D, D > 256 in several k-step ranges) uses row-staged slots, see RingGeo.
 #include "mfma_common.h"
-
-// cache-policy bits of the LDS-DMA loads (gfx940+: 1 = sc0, 2 = nt, 16 = sc1); a build-time knob for experiments
-#ifndef IQA_RING_DMA_AUX
-#define IQA_RING_DMA_AUX 0
-#endif
-// 1: a scheduling barrier behind every k step of the multiplying loop (what the loop needed while it also issued one
-// LDS-DMA per k step: the compiler will not move a ds_read across a DMA).  The refills now go out in front of the loop,
-// and the compiler's own interleaving of fragment reads, byte splits and MFMAs is faster: probe/kstep_probe.hip measures
-// 1483 ns per tile pair and SIMD against 1842 ns with the barriers (13 k steps, two waves per SIMD, no DMA, no scatter).
-#ifndef IQA_RING_SCHED_BARRIER
-#define IQA_RING_SCHED_BARRIER 0
-#endif
-// 1: in the kernels without loader waves (9..16 k steps: D = 132..256) the two column-tile parities run HALF A ROUND
-// apart: two workgroup barriers per round, each the tile boundary of one parity and a mid-tile barrier of the other.
-// A SIMD holds one wave of each parity; with one barrier per round both reach their tile boundary -- results out of the
-// matrix pipe, 16 LDS adds, the barrier, the first fragment reads of the next tile -- at the same time and the matrix
-// pipe idles for that long; half a round apart, one of them is always in the middle of its 3*KS MFMAs (one wave alone
-// keeps the pipe 96 % busy: probe/kstep_probe.hip).  MEASURED and left off: 9.48 against 9.15 ms on the five-target launch,
-// 1.057 against 1.055 ms on one channel at D = 208 -- tile boundaries are not what holds this kernel back (DESIGN.md
-// section 6).  Build-time knob for A/B measurements only.
-// Loader waves (extra waves that feed the ring and emit) up to this many k steps; 14..16 k steps need more registers than
-// twelve waves leave each other (168), there the multiplying waves issue LDS-DMAs themselves.  With LDS-DMA staging
-// (IQA_RING_SPLIT_STAGE=0) round 2 measured loaders at 13 k steps as 4 % faster on a five-target launch of single lanes but
-// with L2 misses of 1.1-1.4x the capture instead of 1.003x (the lanes of a range lose their lock-step); banks at 9..16 k
-// steps run as lane PAIRS (no loader waves, paced), so this concerns the single-lane kernels.
-#ifndef IQA_RING_LOADERS_MAX_KS
-#define IQA_RING_LOADERS_MAX_KS 13
-#endif
-// A/B knobs for the waves' interplay on a SIMD (diagnostic builds): IQA_RING_DEFER 0 = parity-1 waves scatter their tile
-// right behind it like parity 0; IQA_RING_PRIO 1 = parity-1 waves run at raised priority (s_setprio 1), 2 = parity-0 waves.
-#ifndef IQA_RING_DEFER
-#define IQA_RING_DEFER 1
-#endif
-#ifndef IQA_RING_PRIO
-#define IQA_RING_PRIO 0
-#endif
-#ifndef IQA_RING_STAGGER
-#define IQA_RING_STAGGER 0
-#endif
-#ifndef IQA_RING_ROUNDS_MAX
-#define IQA_RING_ROUNDS_MAX 5  // ring depth of the single-lane kernels in rounds of two tiles, where LDS allows it
-#endif
-// Lane pairs: data tiles per round.  1 (default): one tile per round, two issuing waves (RingGeo PAIR below).  2: a round is
-// TWO tiles and every wave multiplies both with its lane's tap rows -- half as many round barriers per tile, the ring fed
-// exactly as in the single-lane kernel (one issuing wave per SIMD), one emitting wave per lane every round.  Built,
-// bit-identical on every pair test, and MEASURED SLOWER on config 3 (same box, alternating: 9.12 against 8.78 ms with
-// every target "fast", 14.15 against 13.67 ms at the product's precisions; profiles/r03_ab_pair_tiles.txt): the round
-// barrier is not what the pair kernel waits for (the probe said the same).  A/B knob only.
-#ifndef IQA_RING_PAIR_TILES
-#define IQA_RING_PAIR_TILES 1
-#endif
-#ifndef IQA_RING_PAIR_ROUNDS
-#define IQA_RING_PAIR_ROUNDS 3  // ring depth of the lane-pair kernel in rounds (2..5).  Its speed does not depend on it (2, 3, 5:
-                                // 9.19 / 9.08 / 9.08 ms at config 3); at 3 a workgroup leaves 59 KB of a CU's LDS to the small
-                                // kernels of the previous capture's tail (the resampler wants 20), at 5 only 3
-#endif
-
-// 1: the kernels with loader waves over contiguous slots (<= IQA_RING_LOADERS_MAX_KS k steps: config 2) stage the capture as
-// BYTE PLANES: four loader waves fetch the tiles into registers (global_load_dwordx4, three rounds ahead), split every int16
-// into its high byte and its biased low byte ONCE and write the two planes into the slot; the multiplying waves read their
-// matrix operands straight out of the planes.  With raw tiles in LDS (0: LDS-DMA, the older form) each of a parity's four
-// multiplying waves split the same fragment again: 12 VALU instructions per k step and wave beside 3 MFMAs -- measured on the
-// sustained config-2 loop as 8.5 % of the kernel's time (diagnostic build "no byte splits", profiles/r03_sustained_ablation_splits.txt).
-#ifndef IQA_RING_SPLIT_STAGE
-#define IQA_RING_SPLIT_STAGE 1
-#endif
-#ifndef IQA_RING_HALF_STEP
-#define IQA_RING_HALF_STEP 1  // 0: the last k step of a row is always a whole 32x32x32 MFMA (A/B)
-#endif
-#ifndef IQA_RING_PD
-#define IQA_RING_PD 2
-#endif
-#ifndef IQA_RING_SPLIT_CONTIG
-#define IQA_RING_SPLIT_CONTIG 0  // 1: a parity's two loader waves take the first and the second half of a tile instead of every second piece (A/B)
-#endif
-#ifndef IQA_RING_PAIR_NLOADERS
-#define IQA_RING_PAIR_NLOADERS 4
-#endif
-#ifndef IQA_RING_PAIR_LOADERS
-#define IQA_RING_PAIR_LOADERS 1  // 0: lane pairs keep their issuing / emitting multiplying waves and LDS-DMA (A/B)
-#endif
-#ifndef IQA_RING_SPLIT_F3_MAX_KS
-#define IQA_RING_SPLIT_F3_MAX_KS 0  // three rounds of loads in flight up to this many k steps, two beyond.  Two everywhere: config 2's
-                                    // kernel measures the same with two and three (0.547 / 0.549 ms, profiles/r03b_ab_rounds_in_flight.txt),
-                                    // and with two a workgroup of the 7-k-step kernel takes 3 x 120 registers per SIMD instead of 3 x 152:
-                                    // the 80-register kernels of a capture's tail fit beside it
-#endif
 
 #include <atomic>
 #include <mutex>
@@ -148,14 +63,25 @@ constexpr unsigned int RG_PACE_AHEAD = 2;  // publications (of every second roun
 constexpr int RG_PACE_SPINS = 20000;
 constexpr int RG_PACE_WORDS = 16384;       // words of the pacing buffer: ranges x units of a launch must fit
 constexpr int RG_PAIR_IDLE = 1 << 28;  // MfmaArgs::pair_shift of the half of a pair that has no lane
+// Loader waves (extra waves that feed the ring and emit) up to this many k steps; 14..16 k steps need more registers than
+// twelve waves leave each other (168), there the multiplying waves issue LDS-DMAs themselves.  Banks at 9..16 k steps run
+// as lane pairs, so this concerns the single-lane kernels.
+constexpr int RG_LOADERS_MAX_KS = 13;
+constexpr int RG_ROUNDS_MAX = 5;  // ring depth of the single-lane kernels in rounds of two tiles, where LDS allows it
+// Ring depth of the lane-pair kernel in rounds (2..5).  Its speed does not depend on it (2, 3, 5: 9.19 / 9.08 / 9.08 ms at
+// config 3); at 3 a workgroup leaves 59 KB of a CU's LDS to the small kernels of the previous capture's tail (the resampler
+// wants 20), at 5 only 3.
+constexpr int RG_PAIR_ROUNDS = 3;
+constexpr int RG_PD = 2;  // k steps the fragment reads run ahead of the MFMAs
 
 // One LDS-DMA instruction: 64 lanes x 16 bytes, global -> LDS (global_load_lds_dwordx4).  The 16-byte form exists on
 // gfx950 only; the HOST pass of the compilation checks the builtin's size argument against ITS target and, inside
-// function templates, turns that into spurious "no matching function" errors -- it never needs the body.
+// function templates, turns that into spurious "no matching function" errors -- it never needs the body.  Default cache
+// policy: the others (nt, sc1, sc0 sc1, sc1 nt) measured the same.
 __device__ __forceinline__ void ring_dma16(const void *src, ring_lds_t *dst)
 {
 #if defined(__HIP_DEVICE_COMPILE__)
-    __builtin_amdgcn_global_load_lds(src, dst, 16, 0, IQA_RING_DMA_AUX);
+    __builtin_amdgcn_global_load_lds(src, dst, 16, 0, 0);
 #else
     (void)src;
     (void)dst;
@@ -183,7 +109,7 @@ __device__ __forceinline__ unsigned lds_addr(const void *p)
 //     row, so three passes read the capture about once instead of three times.  Always with loader waves.
 // U8 (row-staged only): uint8 I/Q captures -- a k step is 32 bytes of a row, one 16-byte fragment per lane, the
 // offset-binary bytes become int8 with one XOR, and there is a single data piece: two MFMAs per k step (q1*v, q2*v).
-// PAIR (contiguous slots without loader waves only): the workgroup holds TWO lanes -- the four waves of parity 0 the tap
+// PAIR (contiguous slots only): the workgroup holds TWO lanes -- the four waves of parity 0 the tap
 // rows of one, the four of parity 1 those of the other -- and all eight read the SAME staged tile: one tile per round
 // instead of two, so the ring is twice as deep in rounds at the same LDS (five rounds instead of two at 13 k steps: the
 // refill of a slot has four rounds to land instead of one) and a tile crosses L2 -> LDS once per two lanes; two windows
@@ -192,9 +118,7 @@ template <int KS, bool ROWS, bool U8 = false, bool PAIR = false>
 struct RingGeo {
     static_assert(ROWS || !U8, "uint8 captures use row-staged slots");
     static_assert(!PAIR || (!ROWS && !U8), "lane pairs: contiguous slots only");
-    static constexpr bool PAIR1 = PAIR && IQA_RING_PAIR_TILES == 1;  // lane pairs, one tile per round
-    static constexpr bool PAIR2 = PAIR && IQA_RING_PAIR_TILES != 1;  // lane pairs, two tiles per round (every wave takes both)
-    static constexpr int TPR = PAIR1 ? 1 : 2;  // tiles per round
+    static constexpr int TPR = PAIR ? 1 : 2;  // tiles per round
     static constexpr int ACCS = PAIR ? 2 : 1;  // windows of sums
     static constexpr int KBYTES = U8 ? 32 : 64;  // bytes of a row per k step
     static constexpr int PITCH = KBYTES * KS + 16;
@@ -207,26 +131,29 @@ struct RingGeo {
     static constexpr int UNITS_ROW = PITCH / 16;
     static constexpr int NI_ROWS = (32 * UNITS_ROW + 63) / 64;
     static constexpr int SLOT_RAW = ROWS ? (32 * PITCH > 1024 * NI_ROWS ? 32 * PITCH : 1024 * NI_ROWS) : 1024 * NI;
-    // extra waves that feed the ring and emit (a wave then has 168 registers).  Lane pairs: with byte-plane staging up to 13 k
-    // steps -- four loader waves share the round's ONE tile, the first two emit a lane each
-    static constexpr bool LOADERS = (!PAIR && (ROWS || KS <= IQA_RING_LOADERS_MAX_KS)) ||
-                                    (PAIR1 && IQA_RING_SPLIT_STAGE != 0 && IQA_RING_PAIR_LOADERS != 0 && KS <= 13);
-    // byte-plane staging (IQA_RING_SPLIT_STAGE): a slot is [high bytes: 32 rows at PLANE_PITCH][biased low bytes: ditto], the
-    // same 1024 * NI bytes; the pitch is an odd number of 16-byte units (conflict-free ds_read_b128, lane = row).  FOUR
-    // loader waves, two per parity (wave `half` of a parity takes the tile's 1 KiB pieces 2 j + half, j < KS), SPLIT_F rounds
-    // of loads in flight in their registers (4 KS SPLIT_F of them), two slots per parity in LDS (one read, one written).
-    static constexpr bool SPLIT = LOADERS && !U8 && (IQA_RING_SPLIT_STAGE != 0);
+    // extra waves that feed the ring and emit (a wave then has 168 registers).  Lane pairs: up to 13 k steps -- four loader
+    // waves share the round's ONE tile, the first two emit a lane each
+    static constexpr bool LOADERS = (!PAIR && (ROWS || KS <= RG_LOADERS_MAX_KS)) || (PAIR && KS <= 13);
+    // byte-plane staging (every int16 kernel with loader waves): a slot is [high bytes: 32 rows at PLANE_PITCH][biased low
+    // bytes: ditto], the same 1024 * NI bytes; the pitch is an odd number of 16-byte units (conflict-free ds_read_b128, lane =
+    // row).  FOUR loader waves, two per parity (wave `half` of a parity takes the tile's 1 KiB pieces 2 j + half, j < KS),
+    // SPLIT_F rounds of loads in flight in their registers (4 KS SPLIT_F of them), two slots per parity in LDS (one read, one
+    // written).  With raw tiles in LDS each of a parity's four multiplying waves split the same fragment again: 12 VALU
+    // instructions per k step and wave beside 3 MFMAs, 8.5 % of config 2's kernel time
+    // (profiles/r03_sustained_ablation_splits.txt).
+    static constexpr bool SPLIT = LOADERS && !U8;
     static constexpr int PLANE_PITCH = 32 * KS + 16;
-    static constexpr int SPLIT_F = ((PAIR && IQA_RING_PAIR_NLOADERS == 4) || KS <= IQA_RING_SPLIT_F3_MAX_KS) ? 3 : 2;  // (a loader wave has 168 registers: 4 KS SPLIT_F of data, 2 KS of offsets, the emission)
-    // (lane pairs: IQA_RING_PAIR_NLOADERS loader waves, 2 or 4.  Two: ten waves per workgroup -- SIMDs 2 and 3 hold two waves
-    // each and keep 176 registers free, room for a 256-thread workgroup of the small kernels of a capture's tail)
-    static constexpr int NLOADERS = SPLIT ? (PAIR ? IQA_RING_PAIR_NLOADERS : 4) : (LOADERS ? 2 : 0);
+    // (a loader wave has 168 registers: 4 KS SPLIT_F of data, 2 KS of offsets, the emission.)  Single lanes: two rounds in
+    // flight -- config 2's kernel measures the same with three (profiles/r03b_ab_rounds_in_flight.txt), and with two a
+    // workgroup of the 7-k-step kernel leaves room for the 80-register kernels of a capture's tail
+    static constexpr int SPLIT_F = PAIR ? 3 : 2;
+    static constexpr int NLOADERS = SPLIT ? 4 : (LOADERS ? 2 : 0);
     static constexpr int SLOT = SPLIT ? 64 * PLANE_PITCH : SLOT_RAW;
     static constexpr int NDMA = ROWS ? NI_ROWS : (LOADERS ? NI : KS + 1);  // DMAs per issuing wave and round
     static constexpr int FIT = (160 * 1024 - ACCS * RG_ACC_BYTES) / (TPR * SLOT);
     static constexpr int RMAX = 63 / NDMA + 2;  // (R - 2) * NDMA must fit the 6-bit vmcnt
     static constexpr int R0 = FIT < RMAX ? FIT : RMAX;
-    static constexpr int RCAP = PAIR ? IQA_RING_PAIR_ROUNDS : IQA_RING_ROUNDS_MAX;
+    static constexpr int RCAP = PAIR ? RG_PAIR_ROUNDS : RG_ROUNDS_MAX;
     static constexpr int R = SPLIT ? 2 : R0 > RCAP ? RCAP : (R0 < 2 ? 2 : R0);  // rounds (of two tiles; PAIR: of one) the ring holds
     static constexpr int THREADS = (RG_WAVES + NLOADERS) * kWave;
     static constexpr int LDS_BYTES = R * TPR * SLOT + ACCS * RG_ACC_BYTES;
@@ -243,7 +170,6 @@ struct RingCtx {
     int tiles, rounds, cnt, lane_off, rt, cp, col, h, lane;
     int row_units, pitch_units;  // contiguous slots: 16-byte units per data row in the capture / in LDS (odd)
     int tshift;  // lane pairs: this wave's own tile t is the staged tile of round t + tshift (0 without pairs)
-    int extra;   // lane pairs: rounds the workgroup runs beyond a lane's own tiles (the second lane works that far behind)
     int half_last;  // byte-plane kernels, contiguous slots: the row's last k step holds <= 16 values -- it is a 32x32x16 MFMA
 };
 
@@ -372,51 +298,38 @@ __device__ __forceinline__ void ring_wait_and_barrier(int younger)
     else asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
 }
 
-// A loader wave (parity cp): per round, wait for its DMAs of this round, join the barrier, refill the slot the
-// previous round has left with the tile R-1 rounds ahead (all 2*KS chunks), and emit the group of 64 outputs that
-// became complete two rounds ago when that group's parity is its own.
-template <int KS, int DBG, bool ACC64, bool ROWS, bool U8>
+// A loader wave of the uint8 kernels (row-staged slots, LDS-DMA; the int16 kernels stage byte planes, ring_loader_split),
+// parity cp: per round, wait for its DMAs of this round, join the barrier, refill the slot the previous round has left
+// with the tile R-1 rounds ahead, and emit the group of 64 outputs that became complete two rounds ago when that group's
+// parity is its own.
+template <int KS, bool ACC64>
 __device__ __forceinline__ void ring_loader(const MfmaArgs &a, const RingCtx &c)
 {
-    using G = RingGeo<KS, ROWS, U8>;
+    using G = RingGeo<KS, true, true>;
     constexpr int R = G::R, SLOT = G::SLOT;
-    constexpr bool STREAM = !(DBG & 16);
     const int cp = c.cp;
-    int soff[ROWS ? G::NI_ROWS : G::NI];
-    if constexpr (!ROWS) {
+    int soff[G::NI_ROWS];
+    const int row_bytes = static_cast<int>(c.tile_bytes >> 5);
 #pragma unroll
-        for (int i = 0; i < G::NI; ++i) soff[i] = ring_src_off(i, c.lane, c.row_units, c.pitch_units);
-    } else {
-        const int row_bytes = static_cast<int>(c.tile_bytes >> 5);
-#pragma unroll
-        for (int i = 0; i < G::NI_ROWS; ++i) {
-            const int q = 64 * i + c.lane;
-            int r = q / G::UNITS_ROW;
-            int u = q - r * G::UNITS_ROW;
-            if (r > 31) {
-                r = 31;
-                u = G::UNITS_ROW - 2;
-            }
-            soff[i] = r * row_bytes + min(u, G::UNITS_ROW - 2) * 16;  // (the last data unit again for the padding unit)
+    for (int i = 0; i < G::NI_ROWS; ++i) {
+        const int q = 64 * i + c.lane;
+        int r = q / G::UNITS_ROW;
+        int u = q - r * G::UNITS_ROW;
+        if (r > 31) {
+            r = 31;
+            u = G::UNITS_ROW - 2;
         }
+        soff[i] = r * row_bytes + min(u, G::UNITS_ROW - 2) * 16;  // (the last data unit again for the padding unit)
     }
     auto issue_tile = [&](int tile, int slot) {
         const char *src = c.stream0 + static_cast<long long>(min(tile, c.tiles - 1)) * c.tile_bytes;
         char *dst = c.smem + (slot * 2 + cp) * SLOT;
-        if constexpr (ROWS) {
 #pragma unroll
-            for (int i = 0; i < G::NI_ROWS; ++i)
-                ring_dma16(src + soff[i], (ring_lds_t *)(dst + i * 1024));
-        } else {
-#pragma unroll
-            for (int i = 0; i < G::NI; ++i)
-                ring_dma16(src + soff[i], (ring_lds_t *)(dst + i * 1024));
-        }
+        for (int i = 0; i < G::NI_ROWS; ++i)
+            ring_dma16(src + soff[i], (ring_lds_t *)(dst + i * 1024));
     };
-    if (STREAM) {
 #pragma unroll
-        for (int rr = 0; rr < R - 1; ++rr) issue_tile(2 * rr + cp, rr);
-    }
+    for (int rr = 0; rr < R - 1; ++rr) issue_tile(2 * rr + cp, rr);
     RingEmit em{1.0, 0.0};
     double st_re = a.rot64_re * a.rot64_re - a.rot64_im * a.rot64_im, st_im = 2.0 * a.rot64_re * a.rot64_im;  // 128 outputs
     if (a.finalize && a.rotate) {
@@ -429,9 +342,8 @@ __device__ __forceinline__ void ring_loader(const MfmaArgs &a, const RingCtx &c)
     a2.rot64_im = st_im;
     int slot = 0;
     for (int r = 0; r < c.rounds; ++r) {
-        if (STREAM) ring_wait_and_barrier<KS, ROWS, U8>(min(R - 2, c.rounds - 1 - r));
-        else asm volatile("s_barrier" ::: "memory");
-        if (STREAM && r + R - 1 < c.rounds) issue_tile(2 * (r + R - 1) + cp, (slot == 0) ? R - 1 : slot - 1);
+        ring_wait_and_barrier<KS, true, true>(min(R - 2, c.rounds - 1 - r));
+        if (r + R - 1 < c.rounds) issue_tile(2 * (r + R - 1) + cp, (slot == 0) ? R - 1 : slot - 1);
         if (r >= RG_EMIT_LAG && ((r - RG_EMIT_LAG) & 1) == cp) {
             // every wave has ISSUED the LDS adds of its round r-2 tile before this barrier (parity 1 defers a tile's
             // adds to the start of the next round); a wave has at most 15 LDS operations outstanding and they complete
@@ -461,20 +373,19 @@ struct __attribute__((packed, aligned(4))) ring_raw16 {  // 16 bytes of the capt
 
 // PAIR: the four loader waves (HALF 0..3) share the round's one tile, piece 4 j + HALF each; waves 0 and 1 emit lane 0's and
 // lane 1's outputs (c.cp = the lane; a, c.s_acc, c.tshift are that lane's), every group of their lane.
-template <int KS, int DBG, bool ACC64, bool ROWS, int HALF, bool PAIR = false>
+template <int KS, bool ACC64, bool ROWS, int HALF, bool PAIR = false>
 __device__ __forceinline__ void ring_loader_split(const MfmaArgs &a, const RingCtx &c)
 {
     constexpr bool EMITTER = PAIR ? HALF < 2 : HALF == 0;
     // pieces of a tile this wave takes: every second one, or -- from 12 k steps on, where 8 KS registers of data in flight
     // and the emission's float64 state do not fit one wave -- the emitting wave (half 0) the first KS - 2, the other the rest
-    constexpr bool UNEVEN = !PAIR && (KS >= 12 || IQA_RING_SPLIT_CONTIG != 0);
+    constexpr bool UNEVEN = !PAIR && KS >= 12;
     constexpr int P0 = KS >= 12 ? KS - 2 : KS;
     constexpr int STRIDE = PAIR ? RingGeo<KS, ROWS, false, PAIR>::NLOADERS : 2;
     constexpr int NP = UNEVEN ? (HALF ? 2 * KS - P0 : P0) : (2 * KS + STRIDE - 1) / STRIDE;
     auto piece = [](int j) { return UNEVEN ? (HALF ? P0 + j : j) : STRIDE * j + HALF; };
     using G = RingGeo<KS, ROWS, false, PAIR>;
     constexpr int SLOT = G::SLOT, PP = G::PLANE_PITCH, F = G::SPLIT_F;
-    constexpr bool STREAM = !(DBG & 16);
     const int cp = c.cp;
     // 16-byte units of a data row that are staged: the whole row (contiguous slots: rows follow one another in the capture)
     // or this pass's 4 KS units of it (row-staged slots); a tile is 32 rows of them, unit q = unit q % upr of row q / upr
@@ -545,13 +456,11 @@ __device__ __forceinline__ void ring_loader_split(const MfmaArgs &a, const RingC
         }
     };
     // prologue: the tile of round 0 into slot 0 (before the block's first barrier), rounds 1 .. F requested
-    if (STREAM) {
-        request(0, std::integral_constant<int, 0>{});
-        stage(0, std::integral_constant<int, 0>{});
-        request(1, std::integral_constant<int, 1 % F>{});
-        request(2, std::integral_constant<int, 2 % F>{});
-        if constexpr (F == 3) request(3, std::integral_constant<int, 0>{});
-    }
+    request(0, std::integral_constant<int, 0>{});
+    stage(0, std::integral_constant<int, 0>{});
+    request(1, std::integral_constant<int, 1 % F>{});
+    request(2, std::integral_constant<int, 2 % F>{});
+    if constexpr (F == 3) request(3, std::integral_constant<int, 0>{});
     static_assert(F == 2 || F == 3, "the prologue and the unrolled loop below are written for two or three rounds in flight");
     RingEmit em{1.0, 0.0};
     double st_re = a.rot64_re * a.rot64_re - a.rot64_im * a.rot64_im, st_im = 2.0 * a.rot64_re * a.rot64_im;  // 128 outputs
@@ -584,7 +493,7 @@ __device__ __forceinline__ void ring_loader_split(const MfmaArgs &a, const RingC
     auto round_body = [&](int r, auto set) {
         // (the planes of round r were written before this barrier: lgkmcnt(0) in front of it)
         asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-        if (STREAM && r + 1 < c.rounds) stage((r + 1) & 1, set);
+        if (r + 1 < c.rounds) stage((r + 1) & 1, set);
         const double2 pr_now = pr_next;
         if (PR_AHEAD && EMITTER && a.partial_in != nullptr) {
             const int kn = group_of(r + 1);
@@ -593,7 +502,7 @@ __device__ __forceinline__ void ring_loader_split(const MfmaArgs &a, const RingC
                 pr_next = (i >= 0 && i < c.cnt) ? a.partial_in[c.i0 + i] : make_double2(0.0, 0.0);
             }
         }
-        if (STREAM) request(r + 1 + F, set);  // (beyond the last tile: the last tile again, never staged)
+        request(r + 1 + F, set);  // (beyond the last tile: the last tile again, never staged)
         const int k = EMITTER ? group_of(r) : -1;
         if (k >= 0) {
             asm volatile("" ::: "memory");
@@ -645,12 +554,10 @@ __device__ __forceinline__ void ring_loader_split(const MfmaArgs &a, const RingC
 // The main loop of a multiplying wave.  ISSUER (kernels without loader waves): this wave also feeds the ring
 // (chunks 2i + (rt & 1) of its parity's slot).  EMIT (ditto): this wave also converts, rotates and stores the 64
 // outputs that became complete two rounds ago.
-// DBG bits (diagnostic instantiations only): 1 = no scatter, 16 = no data stream, 32 = no matrix work, 4 = every second
-// multiplying wave without fragment reads and byte splits, 8 = no byte splits.
 // SKIP: what this wave does with the q2*hi product (the third matrix instruction of a k step): 0 = always computes it;
 // 2 = never (its lane's low tap byte is zero throughout: the first lane of a "fine" / "full" tap-row group); 1 = asks the
 // lane's flag at run time (both bodies in the code: ~30 registers more, so only the kernels of such launches carry it).
-template <int KS, int DBG, bool ACC64, bool ROWS, bool U8, bool ISSUER, bool EMIT, bool DEFER, bool PAIR, typename SKIPT, bool HALF = false>
+template <int KS, bool ACC64, bool ROWS, bool U8, bool ISSUER, bool EMIT, bool DEFER, bool PAIR, typename SKIPT, bool HALF = false>
 __device__ __forceinline__ void ring_main(const MfmaArgs &a, const RingCtx &c, const v4i_t (&fq)[KS][2], SKIPT)
 {
     constexpr int SKIP = SKIPT::value;
@@ -660,13 +567,7 @@ __device__ __forceinline__ void ring_main(const MfmaArgs &a, const RingCtx &c, c
     // PAIR: round r works on tile r (both parities: two lanes' tap rows), whose slot is ring slot r mod R; a lane's group k
     // of 64 outputs (tiles 2k, 2k + 1) is emitted by that lane's emitting wave in round 2k + 5 (parity 0) / 2k + 6 (parity
     // 1): the two lanes' emissions fall into alternate rounds
-    const int RG_EMIT_LAG_PAIR = 5 + c.cp;  // (PAIR1 only)
-    constexpr bool PAIR1 = G::PAIR1, PAIR2 = G::PAIR2;
-    // PAIR2: a round is tiles 2r, 2r + 1 of the STAGED stream (the pair's first lane's), in slots 2 * slot + j like the
-    // single-lane kernel's; every wave multiplies both with its lane's tap rows; a lane's own tiles are the staged ones of
-    // tshift rounds earlier (one round per tap-row group of difference), its group k of 64 outputs is the two tiles of its
-    // round k and is emitted by the lane's emitting wave in round k + RG_EMIT_LAG of that lane's count, every round.
-    constexpr bool STREAM = ISSUER && !(DBG & 16);
+    const int RG_EMIT_LAG_PAIR = 5 + c.cp;  // (PAIR only)
     const int rt = c.rt, cp = c.cp;
     // the two issuing waves of a parity share the tile's 2*KS + 1 DMA instructions: wave p = rt & 1 issues numbers
     // p, p + 2, ...; both issue KS + 1 (the counted s_waitcnt wants one number for both), so the odd wave's last one
@@ -684,8 +585,8 @@ __device__ __forceinline__ void ring_main(const MfmaArgs &a, const RingCtx &c, c
     const int odd_kib = (rt & 1) * 1024;
     auto issue = [&](int tile, int slot, int i) {  // `i` is a compile-time constant at every call site
         // (PAIR: the stream runs on past this lane's own last tile for the partner that works pair_extra rounds behind)
-        const char *tile0 = c.stream0 + static_cast<long long>(min(tile, (PAIR1 ? c.rounds : PAIR2 ? c.tiles + 2 * c.extra : c.tiles) - 1)) * c.tile_bytes;
-        char *slot0 = c.smem + (PAIR1 ? slot : slot * 2 + cp) * SLOT;
+        const char *tile0 = c.stream0 + static_cast<long long>(min(tile, (PAIR ? c.rounds : c.tiles) - 1)) * c.tile_bytes;
+        char *slot0 = c.smem + (PAIR ? slot : slot * 2 + cp) * SLOT;
         const int at = (i < KS) ? odd_kib + i * 2048 : 2 * KS * 1024;  // instruction numbers p, p + 2, ..., then 2*KS
         if constexpr (ISSUER && G::PADDED) {
             ring_dma16(tile0 + soff[i], (ring_lds_t *)(slot0 + at));
@@ -693,11 +594,11 @@ __device__ __forceinline__ void ring_main(const MfmaArgs &a, const RingCtx &c, c
             ring_dma16(tile0 + soff[0] + at, (ring_lds_t *)(slot0 + at));
         }
     };
-    if (STREAM) {
+    if (ISSUER) {
 #pragma unroll
         for (int rr = 0; rr < R - 1; ++rr)
 #pragma unroll
-            for (int i = 0; i <= KS; ++i) issue(PAIR1 ? rr : 2 * rr + cp, rr, i);
+            for (int i = 0; i <= KS; ++i) issue(PAIR ? rr : 2 * rr + cp, rr, i);
     }
     RingEmit em{1.0, 0.0};
     if (EMIT && a.finalize && a.rotate) {
@@ -735,37 +636,17 @@ __device__ __forceinline__ void ring_main(const MfmaArgs &a, const RingCtx &c, c
             }
         }
     };
-    // STAGGER (see IQA_RING_STAGGER): barrier 2r is the tile boundary of parity 0's round r and falls into the middle of
-    // parity 1's tile of round r - 1; barrier 2r + 1 is parity 1's boundary and parity 0's mid-tile barrier.  Every wave
-    // executes the same 2 * rounds + 1 barriers: parity 1 one in front of its loop, parity 0 one behind it.
-    constexpr bool STAGGER = (IQA_RING_STAGGER != 0) && !G::LOADERS;
-    // (the older, weaker way of keeping a SIMD's two waves out of step.  Not in the byte-plane kernels: with three waves per SIMD
-    // and no byte splits it buys nothing -- config 2's kernel 0.558 either way, 13 k steps 0.975 / 0.979 ms -- and its 32 held
-    // registers made the 64-bit-sum lane pairs spill: config 3 at the product's precisions 13.84 -> 12.65 ms without,
-    // profiles/r03_ab_defer.txt)
-    constexpr bool DEFER_ADDS = DEFER && !STAGGER && (IQA_RING_DEFER != 0) && !G::SPLIT;
+    // Parity-1 waves scatter a tile at the start of the next round (DEFER).  Not in the byte-plane kernels: with three waves
+    // per SIMD and no byte splits it buys nothing, and its 32 held registers made the 64-bit-sum lane pairs spill
+    // (profiles/r03_ab_defer.txt)
+    constexpr bool DEFER_ADDS = DEFER && !G::SPLIT;
     v16i_t held1 = zero16, held2 = zero16;  // DEFER_ADDS: the previous tile's sums, scattered at the start of the next round
     int held_t = -1;
     int slot = 0;
-    if (STAGGER && cp == 1) asm volatile("s_barrier" ::: "memory");
-    if (IQA_RING_PRIO == 1 && cp == 1) asm volatile("s_setprio 1");
-    if (IQA_RING_PRIO == 2 && cp == 0) asm volatile("s_setprio 1");
-    // DBG & 2 (diagnostic builds): per wave, cycles spent waiting in front of / at the round barrier and cycles between
-    // barriers, summed over the rounds -> a.stamps[(workgroup * 8 + wave) * 4 + {0: wait, 1: work, 2: rounds, 3: first tile stamp}]
-    unsigned long long st_wait = 0, st_work = 0, st_prev = 0;
-    bool pace_on = PAIR && a.pace != nullptr && a.pace_units > 1 && c.rounds < (PAIR2 ? 4000 : 8000);  // (12 bits of publication count)
+    bool pace_on = PAIR && a.pace != nullptr && a.pace_units > 1 && c.rounds < 8000;  // (12 bits of publication count)
     for (int r = 0; r < c.rounds; ++r) {
-        unsigned long long st0 = 0;
-        if (DBG & 2) {
-            st0 = __builtin_amdgcn_s_memtime();
-            if (r) st_work += st0 - st_prev;
-        }
-        if (STREAM) ring_wait_and_barrier<KS, ROWS, U8, PAIR>(min(R - 2, c.rounds - 1 - r));
+        if (ISSUER) ring_wait_and_barrier<KS, ROWS, U8, PAIR>(min(R - 2, c.rounds - 1 - r));
         else asm volatile("s_barrier" ::: "memory");
-        if (DBG & 2) {
-            st_prev = __builtin_amdgcn_s_memtime();
-            st_wait += st_prev - st0;
-        }
         if constexpr (PAIR && !ISSUER && !EMIT && !DEFER) {
             // Pacing (wave rt 3 of parity 0: no counted waits of its own to disturb).  The workgroups of a range share the
             // capture through their XCD's L2, which at this rate keeps a line for ~10 us = a few rounds; single-lane
@@ -774,8 +655,8 @@ __device__ __forceinline__ void ring_main(const MfmaArgs &a, const RingCtx &c, c
             // the capture in HBM reads.  So every second round a workgroup publishes its round and the one that is more
             // than RG_PACE_AHEAD publications in front of the slowest STARTED workgroup of its range waits for it -- the
             // slowest never waits, a workgroup that has not started is not waited for: no cycle.
-            if (c.rt == 3 && c.cp == 0 && pace_on && (PAIR2 || (r & 1) == 0)) {  // (every second tile either way)
-                const unsigned int mine = static_cast<unsigned int>(PAIR2 ? r : r >> 1);
+            if (c.rt == 3 && c.cp == 0 && pace_on && (r & 1) == 0) {  // (every second tile)
+                const unsigned int mine = static_cast<unsigned int>(r >> 1);
                 if (c.lane == 0) __hip_atomic_store(a.pace + a.pace_slot, (a.pace_token << 12) | mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 for (int spin = 0;; ++spin) {
                     unsigned int q = mine;
@@ -796,8 +677,8 @@ __device__ __forceinline__ void ring_main(const MfmaArgs &a, const RingCtx &c, c
                 }
             }
         }
-        const bool pf = STREAM && (r + R - 1 < c.rounds);
-        const int pf_tile = PAIR1 ? r + R - 1 : 2 * (r + R - 1) + cp;
+        const bool pf = ISSUER && (r + R - 1 < c.rounds);
+        const int pf_tile = PAIR ? r + R - 1 : 2 * (r + R - 1) + cp;
         const int pf_slot = (slot == 0) ? R - 1 : slot - 1;  // the slot round r-1 has just left
         // The refill of that slot goes out FIRST, all KS + 1 instructions of it, before this round's matrix work: at
         // 13 k steps the ring holds two rounds only, so a DMA issued late in round r (one per k step, as this loop used
@@ -809,33 +690,36 @@ __device__ __forceinline__ void ring_main(const MfmaArgs &a, const RingCtx &c, c
             for (int i = 0; i <= KS; ++i) issue(pf_tile, pf_slot, i);
         }
         const int re = r - c.tshift;  // PAIR: the round in this lane's own count (its tile(s) of round re are staged now)
-        const bool emit_now = EMIT && (PAIR1 ? (re >= RG_EMIT_LAG_PAIR && ((re - RG_EMIT_LAG_PAIR) & 1) == 0) : re >= RG_EMIT_LAG);
+        const bool emit_now = EMIT && (PAIR ? (re >= RG_EMIT_LAG_PAIR && ((re - RG_EMIT_LAG_PAIR) & 1) == 0) : re >= RG_EMIT_LAG);
         RingEmitRegs eg;
         if (emit_now) {
             asm volatile("" ::: "memory");
             // see ring_loader for why these sums are final (PAIR: the group's last tile was round r - 4's, whose adds --
             // deferred by one round at most -- went out before the barrier of round r - 2)
-            ring_emit_load<ACC64, true>(a, c, PAIR1 ? (re - RG_EMIT_LAG_PAIR) >> 1 : re - RG_EMIT_LAG, eg);
+            ring_emit_load<ACC64, true>(a, c, PAIR ? (re - RG_EMIT_LAG_PAIR) >> 1 : re - RG_EMIT_LAG, eg);
             asm volatile("" ::: "memory");
         }
         if (DEFER_ADDS && held_t >= 0) {
             scatter(held_t, held1, held2);
             held_t = -1;
         }
-        bool store_pending = emit_now;  // the emitting wave finishes its group inside its first tile of the round
-        constexpr int NTW = PAIR2 ? 2 : 1;  // tiles this wave multiplies per round
+        bool store_pending = emit_now;  // the emitting wave finishes its group inside its tile of the round
+        // This wave's one tile of the round.  (A loop of one iteration: without it the compiler orders the tile's address
+        // arithmetic differently and 62 of the kernels come out with other registers and schedules.)
 #pragma unroll
-        for (int j = 0; j < NTW; ++j) {
-        const int t = PAIR1 ? re : PAIR2 ? 2 * re + j : 2 * r + cp;
+        for (int j = 0; j < 1; ++j) {
+        const int t = PAIR ? re : 2 * r + cp;
         if (t >= 0 && t < c.tiles) {
             const bool store_here = store_pending;
             store_pending = false;
-            const char *la = c.smem + (PAIR1 ? slot : PAIR2 ? slot * 2 + j : slot * 2 + cp) * SLOT + c.lane_off;
+            const char *la = c.smem + (PAIR ? slot : slot * 2 + cp) * SLOT + c.lane_off;
             // The data fragments are read PD k steps ahead by hand (an LDS-DMA is a store to LDS as far as the compiler knows,
             // so it never moves a ds_read above an earlier issue(): the refill in front of this loop is a fence for them).
+            // No scheduling barriers between the k steps: the compiler's own interleaving of fragment reads, byte splits and
+            // MFMAs measured faster (probe/kstep_probe.hip: 1483 against 1842 ns per tile pair and SIMD).
             auto tile_body = [&](auto skip_low) {
                 constexpr bool SKIP_LOW = decltype(skip_low)::value;  // q2 == 0 throughout: no q2*hi product
-                constexpr int PD = KS < IQA_RING_PD ? KS : IQA_RING_PD;  // k steps the fragment reads run ahead of the MFMAs
+                constexpr int PD = KS < RG_PD ? KS : RG_PD;
                 v16i_t acc1, acc2;
                 if constexpr (U8) {
                     // uint8 frames: this lane's 16 bytes of a k step are 8 frames; u ^ 0x80 = u - 128 as int8
@@ -852,10 +736,8 @@ __device__ __forceinline__ void ring_main(const MfmaArgs &a, const RingCtx &c, c
                         if (ks + PD < KS) du[ks + PD] = *reinterpret_cast<const v4i_t *>(la + 32 * (ks + PD));
                         acc1 = __builtin_amdgcn_mfma_i32_32x32x32_i8(fq[ks][0], v, ks ? acc1 : zero16, 0, 0, 0);
                         acc2 = __builtin_amdgcn_mfma_i32_32x32x32_i8(fq[ks][1], v, ks ? acc2 : zero16, 0, 0, 0);
-                        if (IQA_RING_SCHED_BARRIER) __builtin_amdgcn_sched_barrier(0);
                     }
-                } else {
-                if constexpr (G::SPLIT) {
+                } else if constexpr (G::SPLIT) {
                     // byte planes: the operands as they lie in the slot (high bytes at la, biased low bytes 32 rows further)
                     v4i_t hh[KS], ll[KS];
                     constexpr bool half_last = HALF;  // (a property of the kernel variant: both bodies in one kernel cost ~25 registers)
@@ -878,9 +760,7 @@ __device__ __forceinline__ void ring_main(const MfmaArgs &a, const RingCtx &c, c
                     for (int ks = 0; ks < KS; ++ks) {
                         const v4i_t hi = hh[ks], lo = ll[ks];
                         if (ks + PD < KS) fetch(ks + PD);
-                        if (DBG & 32) {
-                            asm volatile("" ::"v"(hi), "v"(lo));
-                        } else if (ks == KS - 1 && half_last) {
+                        if (ks == KS - 1 && half_last) {
                             auto pack = [](int x, int y) { return static_cast<long>((static_cast<unsigned long long>(static_cast<unsigned>(y)) << 32) | static_cast<unsigned>(x)); };
                             const long a1 = pack(fq[ks][0].x, fq[ks][0].y), a2 = pack(fq[ks][1].x, fq[ks][1].y);
                             const long bh = pack(hi.x, hi.y), bl = pack(lo.x, lo.y);
@@ -893,61 +773,37 @@ __device__ __forceinline__ void ring_main(const MfmaArgs &a, const RingCtx &c, c
                             if constexpr (!SKIP_LOW) acc2 = __builtin_amdgcn_mfma_i32_32x32x32_i8(fq[ks][1], hi, acc2, 0, 0, 0);
                         }
                     }
-                } else if ((DBG & 4) && (rt & 1)) {
-                    // diagnostic: every second wave multiplies register constants -- half the fragment reads and byte splits of
-                    // a workgroup, all of its matrix work (what a wave holding 64 tap rows per data fragment would save)
+                } else {
+                    // raw int16 tiles (14..16 k steps): every wave splits its fragments into high and biased low bytes itself
+                    v4i_t dd[KS][2];
+#pragma unroll
+                    for (int ks = 0; ks < PD; ++ks) {
+                        dd[ks][0] = *reinterpret_cast<const v4i_t *>(la + 64 * ks);
+                        dd[ks][1] = *reinterpret_cast<const v4i_t *>(la + 64 * ks + 16);
+                    }
 #pragma unroll
                     for (int ks = 0; ks < KS; ++ks) {
-                        acc1 = __builtin_amdgcn_mfma_i32_32x32x32_i8(fq[ks][0], fq[ks][1], ks ? acc1 : zero16, 0, 0, 0);
-                        acc2 = __builtin_amdgcn_mfma_i32_32x32x32_i8(fq[ks][0], fq[ks][0], ks ? acc2 : zero16, 0, 0, 0);
-                        if constexpr (!SKIP_LOW) acc2 = __builtin_amdgcn_mfma_i32_32x32x32_i8(fq[ks][1], fq[ks][1], acc2, 0, 0, 0);
-                    }
-                } else {
-                v4i_t dd[KS][2];
-#pragma unroll
-                for (int ks = 0; ks < PD; ++ks) {
-                    dd[ks][0] = *reinterpret_cast<const v4i_t *>(la + 64 * ks);
-                    dd[ks][1] = *reinterpret_cast<const v4i_t *>(la + 64 * ks + 16);
-                }
-#pragma unroll
-                for (int ks = 0; ks < KS; ++ks) {
-                    // the other parity's tile boundary: no memory clobber -- this wave's own fragment reads may move across it
-                    if (STAGGER && ks == KS / 2) asm volatile("s_barrier");
-                    if (EMIT && ks == KS - 3 && store_here) ring_emit_store<true>(a, c, em, eg);  // (its reads went out before k step 0)
-                    const v4i_t d0 = dd[ks][0], d1 = dd[ks][1];
-                    v4i_t hi, lo;
-                    if (DBG & 8) {  // diagnostic: no byte split
-                        hi = d0;
-                        lo = d1;
-                    } else {
-                    hi.x = __builtin_amdgcn_perm(d0.y, d0.x, 0x07050301);
-                    hi.y = __builtin_amdgcn_perm(d0.w, d0.z, 0x07050301);
-                    hi.z = __builtin_amdgcn_perm(d1.y, d1.x, 0x07050301);
-                    hi.w = __builtin_amdgcn_perm(d1.w, d1.z, 0x07050301);
-                    lo.x = __builtin_amdgcn_perm(d0.y, d0.x, 0x06040200) ^ 0x80808080;
-                    lo.y = __builtin_amdgcn_perm(d0.w, d0.z, 0x06040200) ^ 0x80808080;
-                    lo.z = __builtin_amdgcn_perm(d1.y, d1.x, 0x06040200) ^ 0x80808080;
-                    lo.w = __builtin_amdgcn_perm(d1.w, d1.z, 0x06040200) ^ 0x80808080;
-                    }
-                    if (ks + PD < KS) {
-                        dd[ks + PD][0] = *reinterpret_cast<const v4i_t *>(la + 64 * (ks + PD));
-                        dd[ks + PD][1] = *reinterpret_cast<const v4i_t *>(la + 64 * (ks + PD) + 16);
-                    }
-                    if (DBG & 32) {
-                        asm volatile("" ::"v"(hi), "v"(lo));
-                    } else {
+                        if (EMIT && ks == KS - 3 && store_here) ring_emit_store<true>(a, c, em, eg);  // (its reads went out before k step 0)
+                        const v4i_t d0 = dd[ks][0], d1 = dd[ks][1];
+                        v4i_t hi, lo;
+                        hi.x = __builtin_amdgcn_perm(d0.y, d0.x, 0x07050301);
+                        hi.y = __builtin_amdgcn_perm(d0.w, d0.z, 0x07050301);
+                        hi.z = __builtin_amdgcn_perm(d1.y, d1.x, 0x07050301);
+                        hi.w = __builtin_amdgcn_perm(d1.w, d1.z, 0x07050301);
+                        lo.x = __builtin_amdgcn_perm(d0.y, d0.x, 0x06040200) ^ 0x80808080;
+                        lo.y = __builtin_amdgcn_perm(d0.w, d0.z, 0x06040200) ^ 0x80808080;
+                        lo.z = __builtin_amdgcn_perm(d1.y, d1.x, 0x06040200) ^ 0x80808080;
+                        lo.w = __builtin_amdgcn_perm(d1.w, d1.z, 0x06040200) ^ 0x80808080;
+                        if (ks + PD < KS) {
+                            dd[ks + PD][0] = *reinterpret_cast<const v4i_t *>(la + 64 * (ks + PD));
+                            dd[ks + PD][1] = *reinterpret_cast<const v4i_t *>(la + 64 * (ks + PD) + 16);
+                        }
                         acc1 = __builtin_amdgcn_mfma_i32_32x32x32_i8(fq[ks][0], hi, ks ? acc1 : zero16, 0, 0, 0);
                         acc2 = __builtin_amdgcn_mfma_i32_32x32x32_i8(fq[ks][0], lo, ks ? acc2 : zero16, 0, 0, 0);
                         if constexpr (!SKIP_LOW) acc2 = __builtin_amdgcn_mfma_i32_32x32x32_i8(fq[ks][1], hi, acc2, 0, 0, 0);
                     }
-                    if (IQA_RING_SCHED_BARRIER) __builtin_amdgcn_sched_barrier(0);
                 }
-                }
-                }
-                if (DBG & 32) acc1 = acc2 = zero16;
-                if (DBG & 1) {
-                    asm volatile("" ::"v"(acc1), "v"(acc2));
-                } else if (DEFER_ADDS) {
+                if (DEFER_ADDS) {
                     held1 = acc1;
                     held2 = acc2;
                     held_t = t;
@@ -963,28 +819,19 @@ __device__ __forceinline__ void ring_main(const MfmaArgs &a, const RingCtx &c, c
             } else {
                 tile_body(std::false_type{});
             }
-        } else {
-            if (STAGGER) asm volatile("s_barrier" ::: "memory");  // no tile this round (odd tile count): the mid-tile barrier alone
         }
         }
         if (store_pending) ring_emit_store<true>(a, c, em, eg);  // (no tile of its own this round)
         slot = (slot + 1 == R) ? 0 : slot + 1;
     }
     if (DEFER_ADDS && held_t >= 0) scatter(held_t, held1, held2);
-    if (STAGGER && cp == 0) asm volatile("s_barrier" ::: "memory");
-    if ((DBG & 2) && a.stamps != nullptr && c.lane == 0) {
-        unsigned long long *o = a.stamps + (static_cast<size_t>(blockIdx.x) * RG_WAVES + (cp * 4 + rt)) * 4;
-        o[0] = st_wait;
-        o[1] = st_work + (__builtin_amdgcn_s_memtime() - st_prev);
-        o[2] = static_cast<unsigned long long>(c.rounds);
-    }
     // the last groups: everything has landed behind a full wait and one more barrier
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
     if (EMIT) {
         const int k_last = (c.cnt + 62) >> 6;
         // the groups the loop has not emitted: PAIR emitted group k in round 2k + RG_EMIT_LAG_PAIR
         const int own = c.rounds - c.tshift;  // rounds in this lane's own count
-        const int k_next = PAIR1 ? (own > RG_EMIT_LAG_PAIR ? ((own - 1 - RG_EMIT_LAG_PAIR) >> 1) + 1 : 0) : max(own - RG_EMIT_LAG, 0);
+        const int k_next = PAIR ? (own > RG_EMIT_LAG_PAIR ? ((own - 1 - RG_EMIT_LAG_PAIR) >> 1) + 1 : 0) : max(own - RG_EMIT_LAG, 0);
         if (!PAIR || c.tshift < RG_PAIR_IDLE)  // (the idle half of a pair without a second lane emits nothing)
             for (int k = k_next; k <= k_last; ++k) ring_emit_group<ACC64>(a, c, em, k);
     }
@@ -995,7 +842,7 @@ __device__ __forceinline__ void ring_main(const MfmaArgs &a, const RingCtx &c, c
 // SKIPK (kernels of launches in which some lanes have high-byte-only taps, see ring_main's SKIP): lane pairs -- the pair's
 // first lane (parity 0) skips the q2*hi product at compile time, the second never does (the host pairs a tap-row group's
 // high-byte lane with its residue lane); one lane per workgroup -- every wave asks its lane's flag.
-template <int KS, int DBG, bool ACC64, bool ROWS, bool U8, bool PAIR = false, bool SKIPK = false, bool HALF = false>
+template <int KS, bool ACC64, bool ROWS, bool U8, bool PAIR = false, bool SKIPK = false, bool HALF = false>
 __device__ __forceinline__ void ring_block(const MfmaArgs &a, long long range_idx)
 {
     using G = RingGeo<KS, ROWS, U8, PAIR>;
@@ -1015,8 +862,7 @@ __device__ __forceinline__ void ring_block(const MfmaArgs &a, long long range_id
     c.cnt = static_cast<int>(min(static_cast<long long>(a.range), a.n_out - c.i0));
     c.m0 = a.m_lo + c.i0;
     c.tiles = (c.cnt + 63 + 31) >> 5;  // data columns b in [m0-64, m0+cnt-2], rounded up to tiles of 32
-    c.rounds = G::PAIR1 ? c.tiles + a.pair_extra : ((c.tiles + 1) >> 1) + (PAIR ? a.pair_extra : 0);
-    c.extra = PAIR ? a.pair_extra : 0;
+    c.rounds = PAIR ? c.tiles + a.pair_extra : (c.tiles + 1) >> 1;
     c.tshift = PAIR ? a.pair_shift : 0;  // (RG_PAIR_IDLE: the idle half of a pair without a second lane -- barriers only)
     c.smem = smem;
     c.s_acc = reinterpret_cast<int *>(smem + R * G::TPR * SLOT);
@@ -1037,21 +883,19 @@ __device__ __forceinline__ void ring_block(const MfmaArgs &a, long long range_id
         if (wave >= RG_WAVES) {
             c.stream0 = stream;
             __syncthreads();
-            if constexpr (G::SPLIT && PAIR && G::NLOADERS == 2) {
-                if (wave - RG_WAVES) ring_loader_split<KS, DBG, ACC64, ROWS, 1, true>(a, c);
-                else ring_loader_split<KS, DBG, ACC64, ROWS, 0, true>(a, c);
-            } else if constexpr (G::SPLIT && PAIR) {
+            if constexpr (G::SPLIT && PAIR) {
                 switch (wave - RG_WAVES) {
-                    case 0: ring_loader_split<KS, DBG, ACC64, ROWS, 0, true>(a, c); break;
-                    case 1: ring_loader_split<KS, DBG, ACC64, ROWS, 1, true>(a, c); break;
-                    case 2: ring_loader_split<KS, DBG, ACC64, ROWS, 2, true>(a, c); break;
-                    default: ring_loader_split<KS, DBG, ACC64, ROWS, 3, true>(a, c); break;
+                    case 0: ring_loader_split<KS, ACC64, ROWS, 0, true>(a, c); break;
+                    case 1: ring_loader_split<KS, ACC64, ROWS, 1, true>(a, c); break;
+                    case 2: ring_loader_split<KS, ACC64, ROWS, 2, true>(a, c); break;
+                    default: ring_loader_split<KS, ACC64, ROWS, 3, true>(a, c); break;
                 }
             } else if constexpr (G::SPLIT) {
-                if ((wave - RG_WAVES) >> 1) ring_loader_split<KS, DBG, ACC64, ROWS, 1>(a, c);
-                else ring_loader_split<KS, DBG, ACC64, ROWS, 0>(a, c);
+                if ((wave - RG_WAVES) >> 1) ring_loader_split<KS, ACC64, ROWS, 1>(a, c);
+                else ring_loader_split<KS, ACC64, ROWS, 0>(a, c);
+            } else {
+                ring_loader<KS, ACC64>(a, c);
             }
-            else ring_loader<KS, DBG, ACC64, ROWS, U8>(a, c);
             return;
         }
     }
@@ -1090,51 +934,39 @@ __device__ __forceinline__ void ring_block(const MfmaArgs &a, long long range_id
     if constexpr (PAIR && G::SPLIT) {
         // loader waves feed the ring and emit: every multiplying wave only multiplies (parity 1 defers its adds)
         constexpr int SA = SKIPK ? 2 : 0, SB = 0;  // (parity 0 = the pair's first lane)
-        if (c.cp) ring_main<KS, DBG, ACC64, ROWS, U8, false, false, true, true>(a, c, fq, std::integral_constant<int, SB>{});
-        else ring_main<KS, DBG, ACC64, ROWS, U8, false, false, false, true>(a, c, fq, std::integral_constant<int, SA>{});
+        if (c.cp) ring_main<KS, ACC64, ROWS, U8, false, false, true, true>(a, c, fq, std::integral_constant<int, SB>{});
+        else ring_main<KS, ACC64, ROWS, U8, false, false, false, true>(a, c, fq, std::integral_constant<int, SA>{});
     } else if constexpr (PAIR) {
         // parity 0's first two waves feed the ring (one tile per round: the same KS + 1 instructions per issuing wave and
         // round as without pairs); one wave of either parity emits ITS lane's outputs; parity 1 defers its adds
         // (waves go to SIMDs cyclically: issuers on SIMDs 0 and 1, lane A's emitter -- wave 2 -- on SIMD 2, lane B's -- wave
         // 7 -- on SIMD 3)
         constexpr int SA = SKIPK ? 2 : 0, SB = 0;  // (parity 0 = the pair's first lane)
-        if constexpr (G::PAIR2) {
-            // the single-lane kernel's roles: one issuing wave per SIMD (rt 0, 1 of parity 0 feed the round's first tile, rt 2, 3
-            // of parity 1 its second), one emitting wave per LANE (wave 2 = lane A's rt 2 on SIMD 2, wave 5 = lane B's rt 1 on
-            // SIMD 1: neither issues); no deferred adds (two tiles per round keep a SIMD's two waves out of step by themselves)
-            if ((c.rt >> 1) == c.cp) {
-                if (c.cp) ring_main<KS, DBG, ACC64, ROWS, U8, true, false, false, true>(a, c, fq, std::integral_constant<int, SB>{});
-                else ring_main<KS, DBG, ACC64, ROWS, U8, true, false, false, true>(a, c, fq, std::integral_constant<int, SA>{});
-            } else if (c.cp == 0 && c.rt == 2) ring_main<KS, DBG, ACC64, ROWS, U8, false, true, false, true>(a, c, fq, std::integral_constant<int, SA>{});
-            else if (c.cp == 1 && c.rt == 1) ring_main<KS, DBG, ACC64, ROWS, U8, false, true, false, true>(a, c, fq, std::integral_constant<int, SB>{});
-            else if (c.cp) ring_main<KS, DBG, ACC64, ROWS, U8, false, false, false, true>(a, c, fq, std::integral_constant<int, SB>{});
-            else ring_main<KS, DBG, ACC64, ROWS, U8, false, false, false, true>(a, c, fq, std::integral_constant<int, SA>{});
-        } else
-        if (c.cp == 0 && c.rt < 2) ring_main<KS, DBG, ACC64, ROWS, U8, true, false, false, true>(a, c, fq, std::integral_constant<int, SA>{});
-        else if (c.cp == 0 && c.rt == 2) ring_main<KS, DBG, ACC64, ROWS, U8, false, true, false, true>(a, c, fq, std::integral_constant<int, SA>{});
-        else if (c.cp == 1 && c.rt == 3) ring_main<KS, DBG, ACC64, ROWS, U8, false, true, false, true>(a, c, fq, std::integral_constant<int, SB>{});
-        else if (c.cp) ring_main<KS, DBG, ACC64, ROWS, U8, false, false, true, true>(a, c, fq, std::integral_constant<int, SB>{});
-        else ring_main<KS, DBG, ACC64, ROWS, U8, false, false, false, true>(a, c, fq, std::integral_constant<int, SA>{});
+        if (c.cp == 0 && c.rt < 2) ring_main<KS, ACC64, ROWS, U8, true, false, false, true>(a, c, fq, std::integral_constant<int, SA>{});
+        else if (c.cp == 0 && c.rt == 2) ring_main<KS, ACC64, ROWS, U8, false, true, false, true>(a, c, fq, std::integral_constant<int, SA>{});
+        else if (c.cp == 1 && c.rt == 3) ring_main<KS, ACC64, ROWS, U8, false, true, false, true>(a, c, fq, std::integral_constant<int, SB>{});
+        else if (c.cp) ring_main<KS, ACC64, ROWS, U8, false, false, true, true>(a, c, fq, std::integral_constant<int, SB>{});
+        else ring_main<KS, ACC64, ROWS, U8, false, false, false, true>(a, c, fq, std::integral_constant<int, SA>{});
     } else if constexpr (LOADERS) {
         constexpr int S1 = SKIPK ? 1 : 0;
-        if (c.cp) ring_main<KS, DBG, ACC64, ROWS, U8, false, false, true, false, std::integral_constant<int, S1>, HALF>(a, c, fq, std::integral_constant<int, S1>{});
-        else ring_main<KS, DBG, ACC64, ROWS, U8, false, false, false, false, std::integral_constant<int, S1>, HALF>(a, c, fq, std::integral_constant<int, S1>{});
+        if (c.cp) ring_main<KS, ACC64, ROWS, U8, false, false, true, false, std::integral_constant<int, S1>, HALF>(a, c, fq, std::integral_constant<int, S1>{});
+        else ring_main<KS, ACC64, ROWS, U8, false, false, false, false, std::integral_constant<int, S1>, HALF>(a, c, fq, std::integral_constant<int, S1>{});
     } else {
         constexpr int S1 = SKIPK ? 1 : 0;
         // one issuing wave per SIMD (waves go to SIMDs in a cyclic order of period 4): rt 0,1 of parity 0, rt 2,3 of parity 1
         if ((c.rt >> 1) == c.cp) {
-            if (c.cp) ring_main<KS, DBG, ACC64, ROWS, U8, true, false, true, false>(a, c, fq, std::integral_constant<int, S1>{});
-            else ring_main<KS, DBG, ACC64, ROWS, U8, true, false, false, false>(a, c, fq, std::integral_constant<int, S1>{});
-        } else if (wave == RG_EMIT_WAVE) ring_main<KS, DBG, ACC64, ROWS, U8, false, true, false, false>(a, c, fq, std::integral_constant<int, S1>{});
-        else if (c.cp) ring_main<KS, DBG, ACC64, ROWS, U8, false, false, true, false>(a, c, fq, std::integral_constant<int, S1>{});
-        else ring_main<KS, DBG, ACC64, ROWS, U8, false, false, false, false>(a, c, fq, std::integral_constant<int, S1>{});
+            if (c.cp) ring_main<KS, ACC64, ROWS, U8, true, false, true, false>(a, c, fq, std::integral_constant<int, S1>{});
+            else ring_main<KS, ACC64, ROWS, U8, true, false, false, false>(a, c, fq, std::integral_constant<int, S1>{});
+        } else if (wave == RG_EMIT_WAVE) ring_main<KS, ACC64, ROWS, U8, false, true, false, false>(a, c, fq, std::integral_constant<int, S1>{});
+        else if (c.cp) ring_main<KS, ACC64, ROWS, U8, false, false, true, false>(a, c, fq, std::integral_constant<int, S1>{});
+        else ring_main<KS, ACC64, ROWS, U8, false, false, false, false>(a, c, fq, std::integral_constant<int, S1>{});
     }
 }
 
-template <int KS, int DBG, bool ACC64>
+template <int KS, bool ACC64>
 __global__ __launch_bounds__((RingGeo<KS, false>::THREADS), (RingGeo<KS, false>::LOADERS ? 3 : 2)) void k_channelize_mfma_s16_ring(MfmaArgs a)
 {
-    ring_block<KS, DBG, ACC64, false, false>(a, blockIdx.x);
+    ring_block<KS, ACC64, false, false>(a, blockIdx.x);
 }
 
 // The variant whose last k step is a 32x32x16 MFMA (rows of 32 (KS - 1) + 1 .. 16 values: D = 104 -> 208 = 6 x 32 + 16).
@@ -1142,7 +974,7 @@ template <int KS>
 __global__ __launch_bounds__((RingGeo<KS, false>::THREADS), 3) void k_channelize_mfma_s16_ring_half(MfmaArgs a)
 {
     static_assert(RingGeo<KS, false>::SPLIT, "byte-plane kernels only");
-    ring_block<KS, 0, false, false, false, false, false, true>(a, blockIdx.x);
+    ring_block<KS, false, false, false, false, false, true>(a, blockIdx.x);
 }
 
 // The same block under its own name for short launches (the mixer-sign probes: a few thousand outputs in blocks of
@@ -1150,21 +982,21 @@ __global__ __launch_bounds__((RingGeo<KS, false>::THREADS), 3) void k_channelize
 template <int KS>
 __global__ __launch_bounds__((RingGeo<KS, false>::THREADS), (RingGeo<KS, false>::LOADERS ? 3 : 2)) void k_channelize_mfma_s16_ring_short(MfmaArgs a)
 {
-    ring_block<KS, 0, false, false, false>(a, blockIdx.x);
+    ring_block<KS, false, false, false>(a, blockIdx.x);
 }
 
 // Row-staged slots (any D, one k-step range per pass), int32 sums.
 template <int KS>
 __global__ __launch_bounds__((RingGeo<KS, true>::THREADS), 3) void k_channelize_mfma_s16_ring_rows(MfmaArgs a)
 {
-    ring_block<KS, 0, false, true, false>(a, blockIdx.x);
+    ring_block<KS, false, true, false>(a, blockIdx.x);
 }
 
 // Row-staged slots, uint8 I/Q captures (cu8 / RTL-SDR), int32 sums.
 template <int KS>
 __global__ __launch_bounds__((RingGeo<KS, true, true>::THREADS), 3) void k_channelize_mfma_u8_ring_rows(MfmaArgs a)
 {
-    ring_block<KS, 0, false, true, true>(a, blockIdx.x);
+    ring_block<KS, false, true, true>(a, blockIdx.x);
 }
 
 
@@ -1236,8 +1068,8 @@ __device__ __forceinline__ void ring_multi_block(const RingMultiArgs &m)
         // tiles arrive 2 rounds per group of difference later; a pair without a second lane (afrag NULL) idles that half
         const RingLane &la = m.lane[li & ~1], &lb = m.lane[li | 1];
         const bool idle_b = lb.afrag == nullptr;
-        // (rounds the second lane works behind the first: two tiles per tap-row group of difference = one round of two tiles)
-        a.pair_extra = idle_b ? 0 : (la.col_shift - lb.col_shift) >> (RingGeo<KS, ROWS, U8, PAIR>::PAIR2 ? 6 : 5);
+        // (rounds the second lane works behind the first: two tiles, one round each, per tap-row group of difference)
+        a.pair_extra = idle_b ? 0 : (la.col_shift - lb.col_shift) >> 5;
         a.col_shift = la.col_shift;
         if (li & 1) {
             a.pair_shift = idle_b ? RG_PAIR_IDLE : a.pair_extra;
@@ -1247,7 +1079,7 @@ __device__ __forceinline__ void ring_multi_block(const RingMultiArgs &m)
         a.pace_slot = static_cast<int>(range_idx) * units + idx % units;
     }
     if (range_idx * a.range >= a.n_out) return;  // (the last ranges of a short launch)
-    ring_block<KS, 0, ACC64, ROWS, U8, PAIR, SKIPK, HALF>(a, range_idx);
+    ring_block<KS, ACC64, ROWS, U8, PAIR, SKIPK, HALF>(a, range_idx);
 }
 
 // ACC64: one int64 (S1 << 32) + S2 per output component instead of one int32 256*S1 + S2 -- 16-bit taps without the int32
@@ -1306,11 +1138,11 @@ static int ring_launch_kernel(K kernel, const char *name, int threads, const A &
     return check_launch(name);
 }
 
-template <int KS, int DBG, bool ACC64>
+template <int KS, bool ACC64>
 static int ring_launch_one(const MfmaArgs &a, unsigned blocks, size_t lds, hipStream_t stream)
 {
     static std::atomic<unsigned long long> done{0};
-    return ring_launch_kernel(k_channelize_mfma_s16_ring<KS, DBG, ACC64>, "k_channelize_mfma_s16_ring", RingGeo<KS, false>::THREADS, a, blocks, lds, stream, done);
+    return ring_launch_kernel(k_channelize_mfma_s16_ring<KS, ACC64>, "k_channelize_mfma_s16_ring", RingGeo<KS, false>::THREADS, a, blocks, lds, stream, done);
 }
 
 template <int KS>
@@ -1367,7 +1199,7 @@ static int ring_launch_multi(const RingMultiArgs &m, unsigned blocks, size_t lds
         }
     }
     if (skipk) return ring_launch_kernel(k_channelize_mfma_s16_ring_multi<KS, false, true>, "k_channelize_mfma_s16_ring_multi", RingGeo<KS, false>::THREADS, m, blocks, lds, stream, done[6]);
-    if constexpr (KS <= 8 && IQA_RING_HALF_STEP != 0 && IQA_RING_SPLIT_STAGE != 0) {
+    if constexpr (KS <= 8) {
         const int rem = (2 * m.c.D) & 31;  // values in the row's last k step
         if (rem != 0 && rem <= 16)
             return ring_launch_kernel(k_channelize_mfma_s16_ring_multi_half<KS>, "k_channelize_mfma_s16_ring_multi", RingGeo<KS, false>::THREADS, m, blocks, lds, stream, done[7]);
@@ -1381,7 +1213,7 @@ template <int KS>
 static int ring_launch_pairs(const RingMultiArgs &m, unsigned blocks, hipStream_t stream, bool acc64, bool skipk)
 {
     static std::atomic<unsigned long long> done{0}, done64{0}, done_s{0}, done64_s{0};
-    if constexpr (KS >= RG_PAIR_MIN_KS) {
+    if constexpr (KS >= RG_PAIR_MIN_KS && KS != 15) {  // (15: see mfma_ring_pairs_supported)
         using G = RingGeo<KS, false, false, true>;
         if (acc64) {
             if constexpr (KS <= 14) {
@@ -1395,7 +1227,7 @@ static int ring_launch_pairs(const RingMultiArgs &m, unsigned blocks, hipStream_
         if (skipk) return ring_launch_kernel(k_channelize_mfma_s16_ring_pairs<KS, false, true>, "k_channelize_mfma_s16_ring_pairs", G::THREADS, m, blocks, G::LDS_BYTES, stream, done_s);
         return ring_launch_kernel(k_channelize_mfma_s16_ring_pairs<KS>, "k_channelize_mfma_s16_ring_pairs", G::THREADS, m, blocks, G::LDS_BYTES, stream, done);
     } else {
-        set_error("lane pairs need at least %d k steps (got %d)", RG_PAIR_MIN_KS, KS);
+        set_error("lane pairs: %d k steps not instantiated (%d..14, 16)", KS, RG_PAIR_MIN_KS);
         return IQA_EINVAL;
     }
 }
@@ -1468,6 +1300,18 @@ bool mfma_ring_supported(int decimation)
     return decimation >= 4 && (decimation & 3) == 0 && ks <= RG_MAX_KS;
 }
 
+// f(std::integral_constant<int, K>{}) for the K in LO..HI that equals ks: where a run-time k-step count becomes the
+// template argument of a kernel.  ks must lie in LO..HI (the callers check it); `if constexpr` inside f decides which
+// kernels exist for a K.
+template <int LO, int HI, class F>
+static auto with_ks(int ks, F &&f)
+{
+    if constexpr (LO < HI) {
+        if (ks > LO) return with_ks<LO + 1, HI>(ks, f);
+    }
+    return f(std::integral_constant<int, LO>{});
+}
+
 template <int KS>
 static constexpr size_t ring_bytes_of(bool rows, bool u8)
 {
@@ -1478,100 +1322,36 @@ static constexpr size_t ring_bytes_of(bool rows, bool u8)
 
 size_t mfma_ring_lds_bytes(int ksteps, bool rows, bool u8)
 {
-    switch (ksteps) {
-#define RG_B(K) case K: return (rows && K > RG_ROWS_MAX_KS) ? 0 : ring_bytes_of<(K <= 16 ? K : 16)>(rows, u8)
-        RG_B(1); RG_B(2); RG_B(3); RG_B(4); RG_B(5); RG_B(6); RG_B(7); RG_B(8);
-        RG_B(9); RG_B(10); RG_B(11); RG_B(12); RG_B(13); RG_B(14); RG_B(15); RG_B(16);
-#undef RG_B
-        default: return 0;
-    }
+    if (ksteps < 1 || ksteps > (rows ? RG_ROWS_MAX_KS : RG_MAX_KS)) return 0;
+    return with_ks<1, RG_MAX_KS>(ksteps, [&](auto k) { return ring_bytes_of<decltype(k)::value>(rows, u8); });
 }
 
 // debug bit 7 (128) selects the 32-bit sums (needs fragments from dsp_plan.plan_mfma(acc32=True))
 int mfma_ring_launch(const MfmaArgs &a, unsigned blocks, size_t lds, hipStream_t stream, bool rows, bool u8)
 {
-    const int dbg = a.debug & (1 | 2 | 4 | 8 | 16 | 32);
     const bool acc64 = !(a.debug & 128);
-    if (u8) {
-        switch (a.ksteps) {
-#define RG_ROWS_U8(K) case K: return ring_launch_rows_u8<K>(a, blocks, lds, stream)
-            RG_ROWS_U8(1); RG_ROWS_U8(2); RG_ROWS_U8(3); RG_ROWS_U8(4); RG_ROWS_U8(5); RG_ROWS_U8(6); RG_ROWS_U8(7); RG_ROWS_U8(8);
-            RG_ROWS_U8(9); RG_ROWS_U8(10); RG_ROWS_U8(11);
-#undef RG_ROWS_U8
-            default: break;
-        }
-        set_error("uint8 ring kernel: %d k steps per pass not instantiated (1..%d)", a.ksteps, RG_ROWS_MAX_KS);
+    if ((u8 || rows) && (a.ksteps < 1 || a.ksteps > RG_ROWS_MAX_KS)) {
+        set_error("%s ring kernel: %d k steps per pass not instantiated (1..%d)", u8 ? "uint8" : "row-staged", a.ksteps, RG_ROWS_MAX_KS);
         return IQA_EINVAL;
     }
-    if (rows) {
-        switch (a.ksteps) {
-#define RG_ROWS(K) case K: return ring_launch_rows<K>(a, blocks, lds, stream)
-            RG_ROWS(1); RG_ROWS(2); RG_ROWS(3); RG_ROWS(4); RG_ROWS(5); RG_ROWS(6); RG_ROWS(7); RG_ROWS(8);
-            RG_ROWS(9); RG_ROWS(10); RG_ROWS(11);
-#undef RG_ROWS
-            default: break;
-        }
-        set_error("row-staged ring kernel: %d k steps per pass not instantiated (1..%d)", a.ksteps, RG_ROWS_MAX_KS);
+    if (a.ksteps < 1 || a.ksteps > RG_MAX_KS) {
+        set_error("ring kernel: %d k steps not instantiated (1..%d)", a.ksteps, RG_MAX_KS);
         return IQA_EINVAL;
     }
-    if (dbg && a.ksteps == 7 && !acc64) {  // diagnostic instantiations exist for the two benchmark shapes only
-        switch (dbg) {
-            case 1: return ring_launch_one<7, 1, false>(a, blocks, lds, stream);
-            case 16: return ring_launch_one<7, 16, false>(a, blocks, lds, stream);
-            case 17: return ring_launch_one<7, 17, false>(a, blocks, lds, stream);
-            case 32: return ring_launch_one<7, 32, false>(a, blocks, lds, stream);
-            case 33: return ring_launch_one<7, 33, false>(a, blocks, lds, stream);
-            case 4: return ring_launch_one<7, 4, false>(a, blocks, lds, stream);
-            case 8: return ring_launch_one<7, 8, false>(a, blocks, lds, stream);
-            case 5: return ring_launch_one<7, 5, false>(a, blocks, lds, stream);
-            case 13: return ring_launch_one<7, 13, false>(a, blocks, lds, stream);
-            default: break;
+    const int rem = (2 * a.D) & 31;  // values in the row's last k step
+    const bool half = !acc64 && a.range >= 512 && !a.high_taps_only && rem != 0 && rem <= 16;
+    return with_ks<1, RG_MAX_KS>(a.ksteps, [&](auto k) {
+        constexpr int K = decltype(k)::value;
+        if constexpr (K <= RG_ROWS_MAX_KS) {
+            if (u8) return ring_launch_rows_u8<K>(a, blocks, lds, stream);
+            if (rows) return ring_launch_rows<K>(a, blocks, lds, stream);
         }
-    }
-    if (dbg && a.ksteps == 13 && !acc64) {  // (D = 208: BASELINE configs 3 and 4, the kernel without loader waves)
-        switch (dbg) {
-            case 1: return ring_launch_one<13, 1, false>(a, blocks, lds, stream);
-            case 16: return ring_launch_one<13, 16, false>(a, blocks, lds, stream);
-            case 17: return ring_launch_one<13, 17, false>(a, blocks, lds, stream);
-            case 32: return ring_launch_one<13, 32, false>(a, blocks, lds, stream);
-            case 33: return ring_launch_one<13, 33, false>(a, blocks, lds, stream);
-            case 4: return ring_launch_one<13, 4, false>(a, blocks, lds, stream);
-            case 8: return ring_launch_one<13, 8, false>(a, blocks, lds, stream);
-            case 2: return ring_launch_one<13, 2, false>(a, blocks, lds, stream);    // per-wave barrier-wait / work cycles
-            case 18: return ring_launch_one<13, 18, false>(a, blocks, lds, stream);  // the same without the DMA stream
-            default: break;
+        if constexpr (K <= 8) {
+            if (half) return ring_launch_half<K>(a, blocks, lds, stream);
         }
-    }
-    if (IQA_RING_HALF_STEP != 0 && IQA_RING_SPLIT_STAGE != 0 && !dbg && !acc64 && a.range >= 512 && a.ksteps <= 8 && !a.high_taps_only) {
-        const int rem = (2 * a.D) & 31;  // values in the row's last k step
-        if (rem != 0 && rem <= 16) {
-            switch (a.ksteps) {
-#define RG_HALF(K) case K: return ring_launch_half<K>(a, blocks, lds, stream)
-                RG_HALF(1); RG_HALF(2); RG_HALF(3); RG_HALF(4); RG_HALF(5); RG_HALF(6); RG_HALF(7); RG_HALF(8);
-#undef RG_HALF
-                default: break;
-            }
-        }
-    }
-    if (!dbg && !acc64 && a.range < 512) {  // short launch (int32 sums): same code, its own kernel name
-        switch (a.ksteps) {
-#define RG_SHORT(K) case K: return ring_launch_short<K>(a, blocks, lds, stream)
-            RG_SHORT(1); RG_SHORT(2); RG_SHORT(3); RG_SHORT(4); RG_SHORT(5); RG_SHORT(6); RG_SHORT(7); RG_SHORT(8);
-            RG_SHORT(9); RG_SHORT(10); RG_SHORT(11); RG_SHORT(12); RG_SHORT(13); RG_SHORT(14); RG_SHORT(15); RG_SHORT(16);
-#undef RG_SHORT
-            default: break;
-        }
-    }
-    switch (a.ksteps) {
-#define RG_CASE(K) \
-    case K: return acc64 ? ring_launch_one<K, 0, true>(a, blocks, lds, stream) : ring_launch_one<K, 0, false>(a, blocks, lds, stream)
-        RG_CASE(1); RG_CASE(2); RG_CASE(3); RG_CASE(4); RG_CASE(5); RG_CASE(6); RG_CASE(7); RG_CASE(8);
-        RG_CASE(9); RG_CASE(10); RG_CASE(11); RG_CASE(12); RG_CASE(13); RG_CASE(14); RG_CASE(15); RG_CASE(16);
-#undef RG_CASE
-        default: break;
-    }
-    set_error("ring kernel: %d k steps not instantiated (1..%d)", a.ksteps, RG_MAX_KS);
-    return IQA_EINVAL;
+        if (!acc64 && a.range < 512) return ring_launch_short<K>(a, blocks, lds, stream);  // short launch: same code, its own kernel name
+        return acc64 ? ring_launch_one<K, true>(a, blocks, lds, stream) : ring_launch_one<K, false>(a, blocks, lds, stream);
+    });
 }
 
 // Several lanes (channels x tap-row groups) of one capture in one launch; int32 sums only.  `lanes` holds n_lanes
@@ -1641,27 +1421,18 @@ int mfma_ring_launch_multi(const MfmaArgs &a, const MfmaLane *lanes, int n_lanes
     const long long groups = (ranges + 7) / 8;  // ranges are dealt to the 8 XCD classes: workgroup b -> class b % 8
     const unsigned blocks = static_cast<unsigned>(groups * (pairs ? n_lanes / 2 : n_lanes) * 8);
     if (blocks_out) *blocks_out = blocks;
+    if (a.ksteps < 1 || a.ksteps > RG_MAX_KS) {
+        set_error("ring kernel: %d k steps not instantiated (1..%d)", a.ksteps, RG_MAX_KS);
+        return IQA_EINVAL;
+    }
     if (pairs) {
         m.c.pace = nullptr;
         m.c.pace = ring_pace_buffer(m.c.pace_token, static_cast<int>(std::min<long long>(groups * 8 * (n_lanes / 2), RG_PACE_WORDS + 1)), stream);
-        switch (a.ksteps) {
-#define RG_PAIRS(K) case K: return ring_launch_pairs<K>(m, blocks, stream, acc64, skipk)
-            RG_PAIRS(9); RG_PAIRS(10); RG_PAIRS(11); RG_PAIRS(12); RG_PAIRS(13); RG_PAIRS(14); RG_PAIRS(16);
-#undef RG_PAIRS
-            default: break;
-        }
-        set_error("lane pairs: %d k steps not instantiated (9..14, 16)", a.ksteps);
-        return IQA_EINVAL;
+        return with_ks<1, RG_MAX_KS>(a.ksteps, [&](auto k) { return ring_launch_pairs<decltype(k)::value>(m, blocks, stream, acc64, skipk); });
     }
-    switch (a.ksteps) {
-#define RG_MULTI(K) case K: return ring_launch_multi<K>(m, blocks, lds, stream, rows, u8, acc64, skipk)
-        RG_MULTI(1); RG_MULTI(2); RG_MULTI(3); RG_MULTI(4); RG_MULTI(5); RG_MULTI(6); RG_MULTI(7); RG_MULTI(8);
-        RG_MULTI(9); RG_MULTI(10); RG_MULTI(11); RG_MULTI(12); RG_MULTI(13); RG_MULTI(14); RG_MULTI(15); RG_MULTI(16);
-#undef RG_MULTI
-        default: break;
-    }
-    set_error("ring kernel: %d k steps not instantiated (1..%d)", a.ksteps, RG_MAX_KS);
-    return IQA_EINVAL;
+    return with_ks<1, RG_MAX_KS>(a.ksteps, [&](auto k) {
+        return ring_launch_multi<decltype(k)::value>(m, blocks, lds, stream, rows, u8, acc64, skipk);
+    });
 }
 
 }  // namespace iqa

@@ -609,7 +609,6 @@ class ChannelBank:
     """
 
     MAX_LANES = 16  # per launch (the lane table travels as kernel arguments)
-    skip_zero_low_taps = bool(int(__import__("os").environ.get("IQA_SKIP_ZERO_LOW_TAPS", "1")))  # (A/B switch for profiles/)
     pair_lanes = True  # two lanes of equal tap-row group per workgroup where the kernel offers it (see _run_shared)
 
     def __init__(self, channelizers: list):
@@ -662,7 +661,6 @@ class ChannelBank:
                 for acc32 in widths:
                     lanes = [i for i in capable if self.chans[i]._kernel.acc32 == acc32]
                     sub = ChannelBank([self.chans[i] for i in lanes])
-                    sub.combines_on_edge_stream = self.combines_on_edge_stream
                     got = sub.process(raw, outs=[outs[i] for i in lanes], last_block=last_block, halo=halo, edge_stream=edge_stream)
                     self.launches.append(sub.last_launch)
                     if self.last_launch is None:
@@ -717,8 +715,6 @@ class ChannelBank:
                c_int64(m_first), c_int64(n_out), N.stream_ptr())
         self.last_launch = dict(lanes=len(kernels), launches=1, combines=0, pairs=0)
         return True
-
-    combines_on_edge_stream = True  # (False: the combine launches stay on the caller's stream, only the float32 edge launches go to ``edge_stream``)
 
     def _run_shared(self, x, n: int, m_first: int, n_out: int, outs: list, halo, edge_stream=None, interior_only: bool = False):
         kernels = [c._kernel for c in self.chans]
@@ -782,7 +778,7 @@ class ChannelBank:
                     lane.q_group, lane.finalize = mp.groups[gi].q, int(fin)
                     lane.conj_sum, lane.rotate = k.params.conj_sum, k.params.rotate
                     lane.raw_partials = int(raw and not fin)
-                    lane.reserved = (0 if acc32 else 1) | (2 if (mp.groups[gi].high_only and self.skip_zero_low_taps) else 0)  # (bit 0: 64-bit sums; bit 1: q2 == 0)
+                    lane.reserved = (0 if acc32 else 1) | (2 if mp.groups[gi].high_only else 0)  # (bit 0: 64-bit sums; bit 1: q2 == 0)
                 N.call(entry, c_int32(P.FMT_CODE[self.fmt]), c_int32(self.decimation), c_int32(k_first), c_int32(k_count), c_int32(rng),
                        table, c_int32(len(part)), N.ptr(big), c_int64(big_frames), c_int64(big_consumed), c_int64(m_a), c_int64(n_int),
                        N.stream_ptr())
@@ -807,7 +803,7 @@ class ChannelBank:
                 part = ids[lo : lo + self.MAX_LANES]
                 launch(part, "iqa_channelize_mfma_multi", len(part))
         main = None
-        if edge_stream is not None and self.combines_on_edge_stream and any(len(mp.groups) > 1 for mp in plans):
+        if edge_stream is not None and any(len(mp.groups) > 1 for mp in plans):
             # the combine launches go where the consumers of the outputs are queued (behind the pass): the caller's stream
             # then holds the pass alone.  (No stream calls at all otherwise: this function also runs inside graph captures,
             # where a set_stream -- even to the current stream -- made the replays 2.5x slower.)

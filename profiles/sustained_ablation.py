@@ -1,7 +1,6 @@
-"""Ring-kernel ablations in the SUSTAINED (power-limited) regime: every variant runs N back-to-back launches and the
-median of the second half is reported, together with rocm-smi's clock/power at that point.  Debug bits (KS = 7 or, with FS=20e6, 13; int32
-sums): 1 = no scatter, 16 = no DMA, 32 = no matrix work, 4 = every second multiplying wave without fragment reads and byte
-splits, 8 = no byte splits.  Usage: python profiles/sustained_ablation.py [N]"""
+"""The ring kernel in the SUSTAINED (power-limited) regime: N back-to-back launches, the median of the second half is
+reported together with rocm-smi's clock/power at that point (KS = 7 or, with FS=20e6, 13).  The diagnostic variants of
+the recorded r0*_sustained_ablation*.txt runs were removed from the kernel.  Usage: python profiles/sustained_ablation.py [N]"""
 import re, subprocess, sys
 from pathlib import Path
 sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
@@ -24,7 +23,7 @@ taps = A.design_channel_filter(fs, bw, d)
 z = D.empty(-(-n_total // d), "complex64")
 PR._ChannelKernel.mfma_variant = "ring"
 PR._ChannelKernel.launch_blocks = int(os.environ.get("RING_BLOCKS", "256"))  # fewer than 256: some CUs stay free
-PR._ChannelKernel.ring_acc32 = os.environ.get("ACC32", "1") == "1"  # 0: int64 sums, 16-bit taps (no ablation builds: DBGS=0)
+PR._ChannelKernel.ring_acc32 = os.environ.get("ACC32", "1") == "1"  # 0: int64 sums, 16-bit taps
 
 def smi():
     try:
@@ -34,21 +33,15 @@ def smi():
     except Exception as e:
         return f"rocm-smi failed: {e}"
 
-names = {0: "everything", 1: "no scatter", 16: "no DMA", 32: "no matrix work", 33: "DMA + LDS reads only", 17: "matrix work + LDS reads only",
-         4: "half the fragment reads + splits", 8: "no byte splits", 5: "half reads + splits, no scatter", 13: "half reads, no splits, no scatter"}
-DBGS = [int(v) for v in os.environ.get("DBGS", "0,1,16,32,33,17").split(",")]
 for rnd in range(int(os.environ.get("ROUNDS", "2"))):
-    for dbg in DBGS:
-        PR._KERNEL_CACHE.clear()
-        ch = A.Channelizer(taps, sample_rate=fs, freq_offset=f_off, mix_sign=1, decimation=d)
-        ch.plan_ahead(); ch._kernel.mfma_params[0].reserved |= dbg
-        evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(N)]
-        for i in range(N):
-            ch.consumed = 0; ch._hist = None
-            ch.process(raw, out_dev=z, events=evs[i], last_block=True)
-            if i == N - 200:
-                pass
-        status = smi()  # sampled while the queue is still draining
-        torch.cuda.synchronize()
-        ts = np.array([a.elapsed_time(b) for a, b in evs])
-        print(f"round {rnd} {names[dbg]:30s}: first 5 {np.round(ts[:5], 3)}  median of last half {np.median(ts[N // 2:]):.4f} ms  [{status}]", flush=True)
+    PR._KERNEL_CACHE.clear()
+    ch = A.Channelizer(taps, sample_rate=fs, freq_offset=f_off, mix_sign=1, decimation=d)
+    ch.plan_ahead()
+    evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(N)]
+    for i in range(N):
+        ch.consumed = 0; ch._hist = None
+        ch.process(raw, out_dev=z, events=evs[i], last_block=True)
+    status = smi()  # sampled while the queue is still draining
+    torch.cuda.synchronize()
+    ts = np.array([a.elapsed_time(b) for a, b in evs])
+    print(f"round {rnd} ring kernel: first 5 {np.round(ts[:5], 3)}  median of last half {np.median(ts[N // 2:]):.4f} ms  [{status}]", flush=True)
