@@ -301,12 +301,12 @@ int iqa_real_part(const void *z_dev, int64_t n, void *out_dev, void *stream);
  * iqa_dc_block   : y[n] = x[n] - x[n-1] + r*y[n-1]     ref: DCBlocker.process, decoders/common.py:16-30
  *                  state_dev = double[2] {x[last], y[last]}; init 0,0.
  * iqa_agc        : g[n] = g[n-1] + decay*(target/|x[n]| - g[n-1]) if |x[n]| > 1e-6 else g[n-1];
- *                  out[n] = x[n]*g[n]; g restarts at 1.0 at every multiple of `reset_period`
- *                  counted from element index `reset_phase` (the reference restarts it on every
- *                  process() call, i.e. at every chunk boundary).  ref: SSBDecoder._apply_agc,
- *                  decoders/ssb.py:65-80.  reset_starts_dev: optional sorted int64[n_resets] of
- *                  element indices where the gain restarts (index 0 always restarts).
+ *                  out[n] = x[n]*g[n]; g restarts at 1.0 at element 0 and at every index in
+ *                  reset_starts_dev (optional, sorted int64[n_resets]; the reference restarts it on
+ *                  every process() call, i.e. at every chunk boundary).  ref: SSBDecoder._apply_agc,
+ *                  decoders/ssb.py:65-80.
  * work_dev: scratch, at least iqa_scan_workspace_bytes(n) bytes.
+ * The three run on the scan of iqa_demodulate below, from a float input to the unclipped output.
  */
 int64_t iqa_scan_workspace_bytes(int64_t n);
 int iqa_deemphasis(const void *x_dev, int64_t n, double alpha, void *state_dev, void *y_dev, void *work_dev,

@@ -33,6 +33,8 @@ inline int check_launch(const char *kernel)
 
 inline hipStream_t as_stream(void *s) { return reinterpret_cast<hipStream_t>(s); }
 
+inline dim3 grid1d(int64_t n, int block) { return dim3(static_cast<unsigned>((n + block - 1) / block)); }
+
 inline int frame_bytes(int fmt)
 {
     switch (fmt) {

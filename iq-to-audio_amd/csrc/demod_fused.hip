@@ -1,5 +1,6 @@
-// demod_fused.hip -- whole demodulator + AudioWriter.write for a block of channel samples in three
-// launches (reduce -> carry -> apply), instead of one launch per reference stage.
+// demod_fused.hip -- the demodulator's scan engine: whole demodulator + AudioWriter.write for a block of
+// channel samples in three launches (reduce -> carry -> apply), the pluggable stage API on the same passes,
+// and the source stages (discriminator, envelope, real part).
 //
 // Replaces, for one block of decimated samples z (reference src/iq_to_audio/):
 //   decoder.process(z)            processing.py:1128
@@ -9,14 +10,57 @@
 //   audio_writer.write(audio)     processing.py:1147 -> :440-456 (pre-clip peak, clip +-0.99)
 //   stats rms_dbfs per chunk      decoders/nfm.py:88-89 (sum of squares per reference chunk)
 //
+// The three IIR stages are per-sample Python/C loops in the reference.  Each is a first-order affine
+// recurrence s[n] = a[n]*s[n-1] + b[n]; affine maps compose associatively, so they run here as a block
+// scan in float64.  The AGC's "gain restarts at 1.0 on every process() call" becomes a segmented scan:
+// at a restart index the element's map is the constant a+b.
+//
 // The source stage (discriminator / envelope / real part) is evaluated on the fly inside the
 // scan passes, and the sink (peak, clip, per-chunk sum of squares) inside the apply pass, so z is
 // read twice and the audio written once: 20 B per channel sample instead of ~52.
 // SSB with AGC needs two dependent recurrences and therefore two scans (DC blocker to a float
 // scratch, then the segmented AGC scan with the sink).
-#include "scan_common.h"
+//
+// The stage API (iqa_deemphasis, iqa_dc_block, iqa_agc) runs one recurrence from a float input to the
+// unclipped output on the same passes, and the stand-alone source stages (iqa_quadrature, iqa_envelope,
+// iqa_real_part) evaluate the same source formulas: a block through the stages gives the audio of the
+// fused path before its clip.
+#include "common.h"
 
 namespace iqa {
+
+constexpr int SC_THREADS = 256;
+constexpr int SC_ITEMS = 8;
+constexpr int SC_TILE = SC_THREADS * SC_ITEMS;  // 2048 elements per block
+
+struct Aff {  // s -> A*s + B
+    double A, B;
+};
+// apply `l` first, then `r`
+__device__ __forceinline__ Aff then(const Aff &l, const Aff &r) { return Aff{r.A * l.A, fma(r.A, l.B, r.B)}; }
+
+// inclusive ordered wave scan; returns the inclusive prefix for this lane
+__device__ __forceinline__ Aff wave_inclusive(Aff v, int lane)
+{
+#pragma unroll
+    for (int o = 1; o < kWave; o <<= 1) {
+        const double la = __shfl_up(v.A, o, kWave);
+        const double lb = __shfl_up(v.B, o, kWave);
+        if (lane >= o) v = then(Aff{la, lb}, v);
+    }
+    return v;
+}
+
+// first index in sorted `arr[0..n)` that is >= v
+__device__ __forceinline__ long long lower_bound_ll(const long long *arr, long long n, long long v)
+{
+    long long lo = 0, hi = n;
+    while (lo < hi) {
+        const long long mid = (lo + hi) >> 1;
+        if (arr[mid] < v) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
 
 enum FOp { F_DEEMPH = 0, F_DC = 1, F_AGC = 2 };
 enum FSrc { S_F32 = 0, S_QUAD = 1, S_ENV = 2, S_REAL = 3 };
@@ -43,8 +87,9 @@ struct FusedArgs {
                 // carry pass clears the peak and the per-chunk sums -- iqa_demodulate_from_reset, no reset copy in front
 };
 
+// the source stage's value at a sample zc with predecessor zp (only the discriminator reads zp)
 template <int SRC>
-__device__ __forceinline__ float src_value(const FusedArgs &a, long long i, float2 zc, float2 zp)
+__device__ __forceinline__ float src_value(float2 zc, float2 zp)
 {
     if constexpr (SRC == S_QUAD) {
         const float re = zc.x * zp.x + zc.y * zp.y;  // z * conj(z_prev), float32 as numpy forms it
@@ -56,6 +101,35 @@ __device__ __forceinline__ float src_value(const FusedArgs &a, long long i, floa
         return zc.x;
     }
 }
+
+// ---- the source stages on their own (iqa_quadrature, iqa_envelope, iqa_real_part) -------------
+
+__global__ void k_quadrature(const float2 *z, long long n, const float2 *prev, float *out)
+{
+    const long long i = static_cast<long long>(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    out[i] = src_value<S_QUAD>(z[i], (i == 0) ? prev[0] : z[i - 1]);
+}
+
+// a launch of its own behind k_quadrature, whose element 0 still reads the old prev
+__global__ void k_store_last(const float2 *z, long long n, float2 *prev)
+{
+    if (threadIdx.x == 0 && blockIdx.x == 0) prev[0] = z[n - 1];
+}
+
+__global__ void k_envelope(const float2 *z, long long n, float *out)
+{
+    const long long i = static_cast<long long>(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (i < n) out[i] = src_value<S_ENV>(z[i], z[i]);
+}
+
+__global__ void k_real(const float2 *z, long long n, float *out)
+{
+    const long long i = static_cast<long long>(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (i < n) out[i] = src_value<S_REAL>(z[i], z[i]);
+}
+
+// ---- the scan engine ---------------------------------------------------------------------------
 
 // u[base-1 .. base+7] -> x[0..7] plus x_before (only DC needs u[base-1])
 template <int OP, int SRC>
@@ -111,11 +185,11 @@ __device__ __forceinline__ void load_u(const FusedArgs &a, long long base, float
             if (base == 0) zz[1] = a.fresh ? make_float2(1.f, 0.f) : a.prev[0];  // z[-1]
         }
 #pragma unroll
-        for (int i = 0; i < SC_ITEMS; ++i) u[i] = (base + i < a.n) ? src_value<SRC>(a, base + i, zz[i + 2], zz[i + 1]) : 0.f;
+        for (int i = 0; i < SC_ITEMS; ++i) u[i] = (base + i < a.n) ? src_value<SRC>(zz[i + 2], zz[i + 1]) : 0.f;
         if constexpr (OP == F_DC) {
             // DC blocker's x[n-1]: u[base-1] from z (ENV/REAL never need z[base-2]); carried state at 0
             if (base == 0) u_before = a.fresh ? 0.f : static_cast<float>(a.st[0]);
-            else u_before = src_value<SRC>(a, base - 1, zz[1], zz[0]);
+            else u_before = src_value<SRC>(zz[1], zz[0]);
         }
     }
 }
@@ -367,7 +441,7 @@ __global__ __launch_bounds__(SC_THREADS) void k_fused_apply(FusedArgs a, float2 
         } else if constexpr (OP == F_DC) {
             float last;
             if constexpr (SRC == S_F32) last = a.x[a.n - 1];
-            else last = src_value<SRC>(a, a.n - 1, a.z[a.n - 1], make_float2(0.f, 0.f));
+            else last = src_value<SRC>(a.z[a.n - 1], make_float2(0.f, 0.f));
             st_out[0] = static_cast<double>(last);
             st_out[1] = a.fin[0];
         }
@@ -475,4 +549,97 @@ extern "C" int iqa_demodulate_from_reset(const iqa_demod_params *p, const void *
 {
     if (n == 0) return fail_inval("iqa_demodulate_from_reset needs samples (an empty block resets nothing)");
     return demodulate(p, z_dev, n, state_dev, seg_starts_dev, n_segs, peak_dev, sumsq_dev, audio_out_dev, scratch_dev, work_dev, stream, 1);
+}
+
+extern "C" int64_t iqa_scan_workspace_bytes(int64_t n)
+{
+    const int64_t nb = (n + SC_TILE - 1) / SC_TILE;
+    return nb * (sizeof(Aff) + sizeof(double)) + 64;
+}
+
+// ---- the stage API: one recurrence, float input, unclipped output -------------------------------
+
+static FusedArgs stage_args(const void *x_dev, int64_t n, void *y_dev)
+{
+    FusedArgs a{};
+    a.x = static_cast<const float *>(x_dev);
+    a.y = static_cast<float *>(y_dev);
+    a.n = n;
+    a.y_aligned = (reinterpret_cast<uintptr_t>(y_dev) & 15) == 0;
+    return a;
+}
+
+extern "C" int iqa_deemphasis(const void *x_dev, int64_t n, double alpha, void *state_dev, void *y_dev,
+                              void *work_dev, void *stream)
+{
+    if (n < 0) return fail_inval("negative length");
+    if (n == 0) return IQA_OK;
+    if (!x_dev || !state_dev || !y_dev || !work_dev) return fail_inval("NULL device pointer");
+    FusedArgs a = stage_args(x_dev, n, y_dev);
+    a.p0 = alpha;
+    a.p1 = 1.0 - alpha;
+    a.st = static_cast<const double *>(state_dev);
+    return launch_fused<F_DEEMPH, S_F32, K_PLAIN>(a, nullptr, static_cast<double *>(state_dev), work_dev, as_stream(stream));
+}
+
+extern "C" int iqa_dc_block(const void *x_dev, int64_t n, double radius, void *state_dev, void *y_dev,
+                            void *work_dev, void *stream)
+{
+    if (n < 0) return fail_inval("negative length");
+    if (!(radius > 0.0 && radius < 1.0)) return fail_inval("radius must be between 0 and 1");
+    if (n == 0) return IQA_OK;
+    if (!x_dev || !state_dev || !y_dev || !work_dev) return fail_inval("NULL device pointer");
+    FusedArgs a = stage_args(x_dev, n, y_dev);
+    a.p0 = static_cast<double>(static_cast<float>(radius));  // the reference's in-loop r is float32
+    a.st = static_cast<const double *>(state_dev);
+    return launch_fused<F_DC, S_F32, K_PLAIN>(a, nullptr, static_cast<double *>(state_dev), work_dev, as_stream(stream));
+}
+
+extern "C" int iqa_agc(const void *x_dev, int64_t n, double target, double decay, const void *reset_starts_dev,
+                       int64_t n_resets, void *y_dev, void *work_dev, void *stream)
+{
+    if (n < 0 || n_resets < 0) return fail_inval("negative length");
+    if (n == 0) return IQA_OK;
+    if (!x_dev || !y_dev || !work_dev) return fail_inval("NULL device pointer");
+    FusedArgs a = stage_args(x_dev, n, y_dev);
+    a.p0 = static_cast<double>(static_cast<float>(target));
+    a.p1 = static_cast<double>(static_cast<float>(decay));
+    a.segs = static_cast<const long long *>(reset_starts_dev);  // the restarts (element 0 always restarts)
+    a.n_segs = n_resets;
+    return launch_fused<F_AGC, S_F32, K_PLAIN>(a, nullptr, nullptr, work_dev, as_stream(stream));
+}
+
+// ---- the source stages -----------------------------------------------------------------------------
+
+extern "C" int iqa_quadrature(const void *z_dev, int64_t n, void *prev_dev, void *out_dev, void *stream)
+{
+    if (n < 0) return fail_inval("negative length");
+    if (n == 0) return IQA_OK;
+    if (!z_dev || !prev_dev || !out_dev) return fail_inval("NULL device pointer");
+    hipStream_t s = as_stream(stream);
+    hipLaunchKernelGGL(k_quadrature, grid1d(n, 256), dim3(256), 0, s, static_cast<const float2 *>(z_dev), (long long)n,
+                       static_cast<const float2 *>(prev_dev), static_cast<float *>(out_dev));
+    hipLaunchKernelGGL(k_store_last, dim3(1), dim3(1), 0, s, static_cast<const float2 *>(z_dev), (long long)n,
+                       static_cast<float2 *>(prev_dev));
+    return check_launch("k_quadrature");
+}
+
+extern "C" int iqa_envelope(const void *z_dev, int64_t n, void *out_dev, void *stream)
+{
+    if (n < 0) return fail_inval("negative length");
+    if (n == 0) return IQA_OK;
+    if (!z_dev || !out_dev) return fail_inval("NULL device pointer");
+    hipLaunchKernelGGL(k_envelope, grid1d(n, 256), dim3(256), 0, as_stream(stream), static_cast<const float2 *>(z_dev),
+                       (long long)n, static_cast<float *>(out_dev));
+    return check_launch("k_envelope");
+}
+
+extern "C" int iqa_real_part(const void *z_dev, int64_t n, void *out_dev, void *stream)
+{
+    if (n < 0) return fail_inval("negative length");
+    if (n == 0) return IQA_OK;
+    if (!z_dev || !out_dev) return fail_inval("NULL device pointer");
+    hipLaunchKernelGGL(k_real, grid1d(n, 256), dim3(256), 0, as_stream(stream), static_cast<const float2 *>(z_dev),
+                       (long long)n, static_cast<float *>(out_dev));
+    return check_launch("k_real");
 }

@@ -542,6 +542,39 @@ def test_demodulate_from_reset_equals_reset_then_demodulate(A, mode, agc):
     assert a_peak > 0.0 and float(a_sums.sum()) > 0.0
 
 
+@pytest.mark.parametrize("n", [5_000, 131_072, 300_001])
+@pytest.mark.parametrize("mode,agc", [("nfm", False), ("am", False), ("usb", True), ("lsb", False)])
+def test_stage_api_equals_fused_demodulator(A, mode, agc, n):
+    """One block through a fresh pluggable decoder (the source stage, then iqa_deemphasis / iqa_dc_block [/ iqa_agc])
+    against one ChannelDemod.process of the same block: the same kernels in the same order, so the audio is equal after
+    the fused path's +-0.99 clip, and the carried state is equal -- for one tile, 64 tiles and more than a wave of tiles."""
+    import torch
+
+    from iq_to_audio_amd import _dev as D
+    from iq_to_audio_amd.processing import ChannelDemod
+
+    rng = np.random.default_rng(n)
+    fs_ch = 96_153.8
+    t = np.arange(n) / fs_ch
+    z = (0.3 * np.exp(2j * np.pi * (900.0 * t + 2.0 * np.sin(2 * np.pi * 3.0 * t))) * (1.0 + 0.4 * np.sin(2 * np.pi * 440.0 * t))
+         + 0.01 * (rng.normal(size=n) + 1j * rng.normal(size=n))).astype(np.complex64)
+    z_dev = D.to_device(z, "complex64")
+    dec = A.create_decoder(mode, deemph_us=300.0, agc_enabled=agc)
+    dec.setup(fs_ch)
+    stage, _ = dec.process(z_dev)
+    dem = ChannelDemod(mode, fs_ch, deemph_us=300.0, agc_enabled=agc)
+    fused = D.empty(n, "float32")
+    dem.process(z_dev, np.array([0], dtype=np.int64), fused)
+    assert torch.equal(torch.clamp(stage, -0.99, 0.99), fused)
+    # state block: float2 prev | double y_last | double x_last, y_last
+    state = dem.state_dev.view(torch.uint8)
+    if mode == "nfm":
+        assert torch.equal(dec.discriminator._last.view(torch.float32), dem.state_dev[:2])
+        assert torch.equal(dec.deemphasis._y, state[8:16].view(torch.float64))
+    else:
+        assert torch.equal(dec.dc._pair, state[16:32].view(torch.float64))
+
+
 @pytest.mark.parametrize("fs_ch", [150_000.0, 250_000.0, 192_000.0, 48_000.0, 44_100.0, 24_000.0, 8_000.0, 96_000.0, 131_071.0])
 def test_resampler_other_ratios(A, fs_ch):
     """Channel rates other than the 96 kHz class: longer polyphase rows (the 24 / 32 / 48 taps-per-lane builds; past the
