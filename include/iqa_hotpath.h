@@ -128,6 +128,8 @@ int iqa_channelize(const iqa_chan_params *p, const void *taps_dev, const void *r
  * 64 tap rows (each pass reads the capture again, shifted by 64*q_group rows), larger decimations into k-step
  * ranges (each pass reads its own part of every row); passes chain their raw sums through
  * partial_out_dev -> partial_in_dev (double2[n_out]) and the last pass (finalize 1) rotates, scales, stores z.
+ * A ring pass (reserved & 64) is a one-lane launch of iqa_channelize_mfma_multi: ranges = ceil(n_out/outputs_per_block),
+ * 8*ceil(ranges/8) workgroups (the ones past the last range return at once), the same read bounds.
  */
 typedef struct {
     int32_t outputs_per_block; /* multiple of 32; LDS = afrag + 16*(outputs_per_block+160) bytes <= 160 KiB */

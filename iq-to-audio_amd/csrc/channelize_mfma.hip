@@ -237,13 +237,17 @@ extern "C" int64_t iqa_mfma_afrag_bytes(int32_t decimation)
     return ksteps * MF_KSTEP_BYTES;
 }
 
+static int channelize_mfma_lanes(int32_t fmt, int32_t decimation, int32_t k_first, int32_t k_count, int32_t outputs_per_block,
+                                 const iqa_mfma_lane *lanes, int32_t n_lanes, const void *raw_dev, int64_t n_frames, int64_t consumed,
+                                 int64_t m_first, int64_t n_out, void *stream, bool pairs);
+
 extern "C" int iqa_channelize_mfma(const iqa_chan_params *p, const iqa_mfma_params *q, const void *afrag_dev,
                                    const void *raw_dev, int64_t n_frames, int64_t consumed, int64_t m_first,
                                    int64_t n_out, void *z_out_dev, void *stream)
 {
     if (p == nullptr || q == nullptr) return fail_inval("params is NULL");
-    const bool u8 = p->fmt == IQA_FMT_U8;  // uint8 captures: row-staged ring kernel only (reserved = 64|128)
-    if (p->fmt != IQA_FMT_S16 && !(u8 && (q->reserved & 64)))
+    const bool ring = (q->reserved & 64) != 0;  // block-wide ring (channelize_ring.hip)
+    if (p->fmt != IQA_FMT_S16 && !(p->fmt == IQA_FMT_U8 && ring))
         return fail_inval("the MFMA channelizer takes int16 captures (and uint8 ones with the ring variant) only");
     if (p->ntaps <= 0 || p->decimation < 1) return fail_inval("bad ntaps/decimation");
     const int64_t D = p->decimation;
@@ -260,6 +264,29 @@ extern "C" int iqa_channelize_mfma(const iqa_chan_params *p, const iqa_mfma_para
     if (!q->finalize && !q->partial_out_dev) return fail_inval("non-final pass needs partial_out_dev");
     int range = q->outputs_per_block;
     if (range <= 0 || (range & 31)) return fail_inval("outputs_per_block must be a positive multiple of 32");
+    if (ring) {
+        // a one-lane launch of iqa_channelize_mfma_multi.  Reserved bit 128 = 32-bit sums; bit 256 is accepted and ignored
+        // (a single-channel pass always computes the q2*hi product)
+        iqa_mfma_lane l{};
+        l.afrag_dev = afrag_dev;
+        l.z_out_dev = z_out_dev;
+        l.partial_in_dev = q->partial_in_dev;
+        l.partial_out_dev = q->partial_out_dev;
+        l.unit = q->unit;
+        l.c_re = q->c_re;
+        l.c_im = q->c_im;
+        l.rot_step = p->rot_step;
+        l.rot_base = p->rot_base;
+        l.out_scale_re = p->out_scale_re;
+        l.out_scale_im = p->out_scale_im;
+        l.q_group = q->q_group;
+        l.finalize = q->finalize;
+        l.conj_sum = p->conj_sum;
+        l.rotate = p->rotate;
+        l.reserved = (q->reserved & 128) ? 0 : 1;
+        return channelize_mfma_lanes(p->fmt, p->decimation, k_first, ksteps, range, &l, 1, raw_dev, n_frames, consumed, m_first, n_out,
+                                     stream, false);
+    }
     // every frame the kernel touches must lie inside [0, n_frames): columns b in [m_first-64, last], each read
     // from frame b*D+1 for 16*ksteps frames (the k padding reads past the row into the next one)
     const int64_t blocks = (n_out + range - 1) / range;
@@ -277,26 +304,10 @@ extern "C" int iqa_channelize_mfma(const iqa_chan_params *p, const iqa_mfma_para
     if (f_min < 0 || f_max >= n_frames || f_max_full >= n_frames)
         return fail_inval("MFMA channelizer range reads outside the block (use iqa_channelize for the edges)");
     const int64_t acc_len = full_tiles * 32 + MF_Q + 4;
-    const bool ring = (q->reserved & 64) != 0;  // block-wide contiguous LDS-DMA ring (channelize_ring.hip)
-    size_t lds = static_cast<size_t>(ksteps) * MF_KSTEP_BYTES + 4 * acc_len * sizeof(int);
-    int ring_mode = 0;
-    if (ring) {
-        ring_mode = mfma_ring_mode(static_cast<int>(D), k_first, ksteps, !(q->reserved & 128), u8);
-        if (ring_mode == 0)
-            return fail_inval("the ring kernel does not cover this (decimation, k-step range, sum width): see iqa_mfma_ring_mode");
-        if (ring_mode == 1) {
-            // a contiguous slot is filled in whole 1 KiB chunks: every tile reads 2048*ksteps bytes from its first frame
-            const int64_t slot_frames = 512LL * ksteps;
-            const int64_t t_last = m_first + (blocks - 1) * range - MF_Q - col_shift + (last_tiles - 1) * 32;
-            const int64_t t_full = blocks > 1 ? m_first + (blocks - 2) * range - MF_Q - col_shift + (full_tiles - 1) * 32 : t_last;
-            if (t_last * D + 1 - consumed + slot_frames > n_frames || t_full * D + 1 - consumed + slot_frames > n_frames)
-                return fail_inval("ring kernel range reads outside the block (use iqa_channelize for the edges)");
-        }  // row-staged slots read exactly what the per-lane kernel reads: covered by the checks above
-        lds = mfma_ring_lds_bytes(ksteps, ring_mode == 2, u8);  // ring + sliding window: independent of outputs_per_block
-    }
+    const size_t lds = static_cast<size_t>(ksteps) * MF_KSTEP_BYTES + 4 * acc_len * sizeof(int);
     if (lds > 160 * 1024) return fail_inval("tap fragments + accumulators exceed 160 KiB of LDS");
 
-    MfmaArgs a;
+    MfmaArgs a{};
     a.afrag = static_cast<const v4i_t *>(afrag_dev);
     a.raw = static_cast<const int *>(raw_dev);
     a.out = static_cast<float2 *>(z_out_dev);
@@ -322,18 +333,6 @@ extern "C" int iqa_channelize_mfma(const iqa_chan_params *p, const iqa_mfma_para
     a.rot_base = p->rot_base;
     a.sc_re = p->out_scale_re;
     a.sc_im = p->out_scale_im;
-    {
-        // rotation between outputs 64 apart, for the ring kernel's recurrence: frac(64*rot_step / 2^64) turns
-        const unsigned long long st = p->rot_step * 64ULL;
-        const double turns = static_cast<double>(st >> 11) * (1.0 / 9007199254740992.0);
-        a.rot64_re = std::cos(2.0 * M_PI * turns);
-        a.rot64_im = std::sin(2.0 * M_PI * turns);
-    }
-    a.raw_partials = 0;
-    a.high_taps_only = 0;  // (single-lane launches always compute the q2*hi product: reserved bit 8 is accepted and ignored)
-    if (ring) {
-        return mfma_ring_launch(a, static_cast<unsigned>(blocks), lds, as_stream(stream), ring_mode == 2, u8);
-    }
     {
         // the 160 KiB dynamic-LDS limit is a per-device attribute (one bit per device id; racing threads both set it)
         static std::atomic<unsigned long long> done{0};
@@ -384,8 +383,8 @@ static int channelize_mfma_lanes(int32_t fmt, int32_t decimation, int32_t k_firs
     if (pairs && !mfma_ring_pairs_supported(static_cast<int>(D), k_first, ksteps, u8, acc64))
         return fail_inval("lane pairs are not available for this (format, decimation, k-step range, sum width): see iqa_mfma_ring_lanes");
     // every frame any lane touches must lie inside [0, n_frames): the lane with the largest tap-row group reads the
-    // earliest data rows, group 0 the latest (see iqa_channelize_mfma for the geometry)
-    int q_max = 0;
+    // earliest data rows, the one with the smallest the latest (see iqa_channelize_mfma for the geometry)
+    int q_max = 0, q_min = INT32_MAX;
     for (int i = 0; i < n_lanes; ++i) {
         if (lanes[i].q_group < 0) return fail_inval("bad q group");
         if (!lanes[i].afrag_dev) {
@@ -394,14 +393,16 @@ static int channelize_mfma_lanes(int32_t fmt, int32_t decimation, int32_t k_firs
         }
         if (lanes[i].finalize ? !lanes[i].z_out_dev : !lanes[i].partial_out_dev) return fail_inval("lane without an output buffer");
         q_max = lanes[i].q_group > q_max ? lanes[i].q_group : q_max;
+        q_min = lanes[i].q_group < q_min ? lanes[i].q_group : q_min;
     }
     const int64_t blocks = (n_out + range - 1) / range;
     const int64_t last_cnt = n_out - (blocks - 1) * range;
     const int64_t last_tiles = (last_cnt + 63 + 31) / 32, full_tiles = (static_cast<int64_t>(range) + 63 + 31) / 32;
     const int64_t f_min = (m_first - MF_Q - static_cast<int64_t>(MF_Q) * q_max) * D + 1 - consumed;
     const int64_t tail = ring_mode == 1 ? 512LL * ksteps : 16LL * (k_first + ksteps);  // frames read from a row's first frame
-    const int64_t t_last = m_first + (blocks - 1) * range - MF_Q + (last_tiles - 1) * 32;  // first row of the last tile, group 0
-    const int64_t t_full = blocks > 1 ? m_first + (blocks - 2) * range - MF_Q + (full_tiles - 1) * 32 : t_last;
+    const int64_t b_last = m_first - MF_Q - static_cast<int64_t>(MF_Q) * q_min;  // first data row of the smallest group
+    const int64_t t_last = b_last + (blocks - 1) * range + (last_tiles - 1) * 32;  // first row of the last tile
+    const int64_t t_full = blocks > 1 ? b_last + (blocks - 2) * range + (full_tiles - 1) * 32 : t_last;
     const int64_t row_span = ring_mode == 1 ? 0 : 31;  // row-staged slots fetch each of the tile's 32 rows separately
     if (f_min < 0 || (t_last + row_span) * D + 1 - consumed + tail > n_frames || (t_full + row_span) * D + 1 - consumed + tail > n_frames)
         return fail_inval("multi-lane ring launch reads outside the block (use iqa_channelize for the edges)");
@@ -447,7 +448,7 @@ static int channelize_mfma_lanes(int32_t fmt, int32_t decimation, int32_t k_firs
         if (s.raw_partials && acc64) return fail_inval("raw partials are int32 sums: not with 64-bit sums");
         l.high_taps_only = (s.reserved & 2) != 0 ? 1 : 0;
     }
-    return mfma_ring_launch_multi(a, packed, n_lanes, lds, as_stream(stream), ring_mode == 2, u8, nullptr, pairs, acc64);
+    return mfma_ring_launch_multi(a, packed, n_lanes, lds, as_stream(stream), ring_mode == 2, u8, pairs, acc64);
 }
 
 extern "C" int iqa_channelize_mfma_multi(int32_t fmt, int32_t decimation, int32_t k_first, int32_t k_count,

@@ -31,6 +31,11 @@
 // step is at most half full ends in 32x32x16 MFMAs (the ..._half kernels).  The forms measured against these and rejected
 // are recorded in DESIGN.md section 6.
 //
+// Every launch goes through the lane table of mfma_ring_launch_multi (k_channelize_mfma_s16_ring_multi / _multi_half /
+// _pairs, ..._s16_ring_rows_multi, ..._u8_ring_rows_multi): a single-channel pass (iqa_channelize_mfma) is a launch of one
+// lane, 8 * ceil(ranges / 8) workgroups.  So traces name no kernel of their own for single channels or for the short
+// mixer-sign probes; the probes are the launches with a small grid.
+//
 // A contiguous slot is 1024*(2*KS + 1) bytes >= 32 rows at a pitch of D/4 (+1) 16-byte units (KS = ceil(2D/32) k steps;
 // the K padding of the last k step reads on into the next row, against zero taps); a tile takes 2*KS + 1 DMA
 // instructions; it needs D % 4 == 0 (16-byte aligned rows for ds_read_b128) and KS <= 16.
@@ -65,9 +70,9 @@ constexpr int RG_PACE_WORDS = 16384;       // words of the pacing buffer: ranges
 constexpr int RG_PAIR_IDLE = 1 << 28;  // MfmaArgs::pair_shift of the half of a pair that has no lane
 // Loader waves (extra waves that feed the ring and emit) up to this many k steps; 14..16 k steps need more registers than
 // twelve waves leave each other (168), there the multiplying waves issue LDS-DMAs themselves.  Banks at 9..16 k steps run
-// as lane pairs, so this concerns the single-lane kernels.
+// as lane pairs, so this concerns the kernels with one lane per workgroup.
 constexpr int RG_LOADERS_MAX_KS = 13;
-constexpr int RG_ROUNDS_MAX = 5;  // ring depth of the single-lane kernels in rounds of two tiles, where LDS allows it
+constexpr int RG_ROUNDS_MAX = 5;  // ring depth of the one-lane-per-workgroup kernels in rounds of two tiles, where LDS allows it
 // Ring depth of the lane-pair kernel in rounds (2..5).  Its speed does not depend on it (2, 3, 5: 9.19 / 9.08 / 9.08 ms at
 // config 3); at 3 a workgroup leaves 59 KB of a CU's LDS to the small kernels of the previous capture's tail (the resampler
 // wants 20), at 5 only 3.
@@ -963,43 +968,6 @@ __device__ __forceinline__ void ring_block(const MfmaArgs &a, long long range_id
     }
 }
 
-template <int KS, bool ACC64>
-__global__ __launch_bounds__((RingGeo<KS, false>::THREADS), (RingGeo<KS, false>::LOADERS ? 3 : 2)) void k_channelize_mfma_s16_ring(MfmaArgs a)
-{
-    ring_block<KS, ACC64, false, false>(a, blockIdx.x);
-}
-
-// The variant whose last k step is a 32x32x16 MFMA (rows of 32 (KS - 1) + 1 .. 16 values: D = 104 -> 208 = 6 x 32 + 16).
-template <int KS>
-__global__ __launch_bounds__((RingGeo<KS, false>::THREADS), 3) void k_channelize_mfma_s16_ring_half(MfmaArgs a)
-{
-    static_assert(RingGeo<KS, false>::SPLIT, "byte-plane kernels only");
-    ring_block<KS, false, false, false, false, false, true>(a, blockIdx.x);
-}
-
-// The same block under its own name for short launches (the mixer-sign probes: a few thousand outputs in blocks of
-// 64), so that profiles keep the capture-long launches and the probes in separate rows.
-template <int KS>
-__global__ __launch_bounds__((RingGeo<KS, false>::THREADS), (RingGeo<KS, false>::LOADERS ? 3 : 2)) void k_channelize_mfma_s16_ring_short(MfmaArgs a)
-{
-    ring_block<KS, false, false, false>(a, blockIdx.x);
-}
-
-// Row-staged slots (any D, one k-step range per pass), int32 sums.
-template <int KS>
-__global__ __launch_bounds__((RingGeo<KS, true>::THREADS), 3) void k_channelize_mfma_s16_ring_rows(MfmaArgs a)
-{
-    ring_block<KS, false, true, false>(a, blockIdx.x);
-}
-
-// Row-staged slots, uint8 I/Q captures (cu8 / RTL-SDR), int32 sums.
-template <int KS>
-__global__ __launch_bounds__((RingGeo<KS, true, true>::THREADS), 3) void k_channelize_mfma_u8_ring_rows(MfmaArgs a)
-{
-    ring_block<KS, false, true, true>(a, blockIdx.x);
-}
-
-
 // ---- several channels of ONE capture in one launch (shared ingest) ---------------------------------------------
 //
 // A lane = one (channel, tap-row group): its own tap fragments, output, scale, rotation.  All lanes of a launch share
@@ -1010,24 +978,12 @@ __global__ __launch_bounds__((RingGeo<KS, true, true>::THREADS), 3) void k_chann
 // here depends on it for correctness), so workgroup b takes lane (b / 8) % n_lanes of output range
 // ((b / 8) / n_lanes) * 8 + b % 8.  Every lane does the same work per tile, so the lanes of a range stay within a few
 // rounds of each other without any synchronisation (4 MiB of L2 per XCD = dozens of rounds of slack).
-struct RingLane {
-    const v4i_t *afrag;
-    float2 *out;
-    const double2 *partial_in;
-    double2 *partial_out;
-    double unit, c_re, c_im;
-    unsigned long long rot_step, rot_base;
-    double rot64_re, rot64_im;
-    float sc_re, sc_im;
-    int col_shift, finalize, conj_sum, rotate, raw_partials, high_taps_only;
-};
-
 constexpr int RG_MAX_LANES = 16;  // (<= 5 targets x <= 3 tap-row groups in the reference's CLI; the table travels as kernel arguments)
 
 struct RingMultiArgs {
     MfmaArgs c;  // what the lanes share; the per-lane fields of `c` are overwritten per workgroup
     int n_lanes;
-    RingLane lane[RG_MAX_LANES];
+    MfmaLane lane[RG_MAX_LANES];
 };
 
 template <int KS, bool ROWS, bool U8, bool PAIR = false, bool ACC64 = false, bool SKIPK = false, bool HALF = false>
@@ -1041,7 +997,7 @@ __device__ __forceinline__ void ring_multi_block(const RingMultiArgs &m)
     // (loader waves 8, 10 carry the first lane's arguments, 9, 11 the second's: waves 8 and 9 emit those lanes)
     const int li = PAIR ? 2 * (idx % units) + (wv >= RG_WAVES ? wv & 1 : (wv >> 2) & 1) : idx % units;
     const long long range_idx = static_cast<long long>(idx / units) * 8 + (blockIdx.x & 7);
-    const RingLane &l = m.lane[li];
+    const MfmaLane &l = m.lane[li];
     MfmaArgs a = m.c;
     a.pair_shift = a.pair_extra = 0;
     a.afrag = l.afrag;
@@ -1066,7 +1022,7 @@ __device__ __forceinline__ void ring_multi_block(const RingMultiArgs &m)
     if constexpr (PAIR) {
         // the pair's first lane has the larger (or the same) tap-row group: ITS stream is staged, the second lane's own
         // tiles arrive 2 rounds per group of difference later; a pair without a second lane (afrag NULL) idles that half
-        const RingLane &la = m.lane[li & ~1], &lb = m.lane[li | 1];
+        const MfmaLane &la = m.lane[li & ~1], &lb = m.lane[li | 1];
         const bool idle_b = lb.afrag == nullptr;
         // (rounds the second lane works behind the first: two tiles, one round each, per tap-row group of difference)
         a.pair_extra = idle_b ? 0 : (la.col_shift - lb.col_shift) >> 5;
@@ -1090,7 +1046,8 @@ __global__ __launch_bounds__((RingGeo<KS, false>::THREADS), (RingGeo<KS, false>:
     ring_multi_block<KS, false, false, false, ACC64, SKIPK>(m);
 }
 
-// ... with the row's last k step as a 32x32x16 MFMA (see k_channelize_mfma_s16_ring_half).
+// ... with the row's last k step as a 32x32x16 MFMA (rows of 32 (KS - 1) + 1 .. 16 values: D = 104 -> 208 = 6 x 32 + 16;
+// see ring_block).
 template <int KS>
 __global__ __launch_bounds__((RingGeo<KS, false>::THREADS), 3) void k_channelize_mfma_s16_ring_multi_half(RingMultiArgs m)
 {
@@ -1136,41 +1093,6 @@ static int ring_launch_kernel(K kernel, const char *name, int threads, const A &
     }
     hipLaunchKernelGGL(kernel, dim3(blocks), dim3(threads), lds, stream, a);
     return check_launch(name);
-}
-
-template <int KS, bool ACC64>
-static int ring_launch_one(const MfmaArgs &a, unsigned blocks, size_t lds, hipStream_t stream)
-{
-    static std::atomic<unsigned long long> done{0};
-    return ring_launch_kernel(k_channelize_mfma_s16_ring<KS, ACC64>, "k_channelize_mfma_s16_ring", RingGeo<KS, false>::THREADS, a, blocks, lds, stream, done);
-}
-
-template <int KS>
-static int ring_launch_half(const MfmaArgs &a, unsigned blocks, size_t lds, hipStream_t stream)
-{
-    static std::atomic<unsigned long long> done{0};
-    return ring_launch_kernel(k_channelize_mfma_s16_ring_half<KS>, "k_channelize_mfma_s16_ring", RingGeo<KS, false>::THREADS, a, blocks, lds, stream, done);
-}
-
-template <int KS>
-static int ring_launch_short(const MfmaArgs &a, unsigned blocks, size_t lds, hipStream_t stream)
-{
-    static std::atomic<unsigned long long> done{0};
-    return ring_launch_kernel(k_channelize_mfma_s16_ring_short<KS>, "k_channelize_mfma_s16_ring_short", RingGeo<KS, false>::THREADS, a, blocks, lds, stream, done);
-}
-
-template <int KS>
-static int ring_launch_rows(const MfmaArgs &a, unsigned blocks, size_t lds, hipStream_t stream)
-{
-    static std::atomic<unsigned long long> done{0};
-    return ring_launch_kernel(k_channelize_mfma_s16_ring_rows<KS>, "k_channelize_mfma_s16_ring_rows", RingGeo<KS, true>::THREADS, a, blocks, lds, stream, done);
-}
-
-template <int KS>
-static int ring_launch_rows_u8(const MfmaArgs &a, unsigned blocks, size_t lds, hipStream_t stream)
-{
-    static std::atomic<unsigned long long> done{0};
-    return ring_launch_kernel(k_channelize_mfma_u8_ring_rows<KS>, "k_channelize_mfma_u8_ring_rows", RingGeo<KS, true, true>::THREADS, a, blocks, lds, stream, done);
 }
 
 template <int KS>
@@ -1326,38 +1248,10 @@ size_t mfma_ring_lds_bytes(int ksteps, bool rows, bool u8)
     return with_ks<1, RG_MAX_KS>(ksteps, [&](auto k) { return ring_bytes_of<decltype(k)::value>(rows, u8); });
 }
 
-// debug bit 7 (128) selects the 32-bit sums (needs fragments from dsp_plan.plan_mfma(acc32=True))
-int mfma_ring_launch(const MfmaArgs &a, unsigned blocks, size_t lds, hipStream_t stream, bool rows, bool u8)
-{
-    const bool acc64 = !(a.debug & 128);
-    if ((u8 || rows) && (a.ksteps < 1 || a.ksteps > RG_ROWS_MAX_KS)) {
-        set_error("%s ring kernel: %d k steps per pass not instantiated (1..%d)", u8 ? "uint8" : "row-staged", a.ksteps, RG_ROWS_MAX_KS);
-        return IQA_EINVAL;
-    }
-    if (a.ksteps < 1 || a.ksteps > RG_MAX_KS) {
-        set_error("ring kernel: %d k steps not instantiated (1..%d)", a.ksteps, RG_MAX_KS);
-        return IQA_EINVAL;
-    }
-    const int rem = (2 * a.D) & 31;  // values in the row's last k step
-    const bool half = !acc64 && a.range >= 512 && !a.high_taps_only && rem != 0 && rem <= 16;
-    return with_ks<1, RG_MAX_KS>(a.ksteps, [&](auto k) {
-        constexpr int K = decltype(k)::value;
-        if constexpr (K <= RG_ROWS_MAX_KS) {
-            if (u8) return ring_launch_rows_u8<K>(a, blocks, lds, stream);
-            if (rows) return ring_launch_rows<K>(a, blocks, lds, stream);
-        }
-        if constexpr (K <= 8) {
-            if (half) return ring_launch_half<K>(a, blocks, lds, stream);
-        }
-        if (!acc64 && a.range < 512) return ring_launch_short<K>(a, blocks, lds, stream);  // short launch: same code, its own kernel name
-        return acc64 ? ring_launch_one<K, true>(a, blocks, lds, stream) : ring_launch_one<K, false>(a, blocks, lds, stream);
-    });
-}
-
-// Several lanes (channels x tap-row groups) of one capture in one launch; int32 sums only.  `lanes` holds n_lanes
-// entries whose fields mirror the per-lane part of MfmaArgs; `a` carries what they share.
+// Every ring pass: 1..16 lanes (channels x tap-row groups) of one capture in one launch.  `lanes` holds n_lanes entries,
+// the per-lane part of MfmaArgs; `a` carries what they share.
 int mfma_ring_launch_multi(const MfmaArgs &a, const MfmaLane *lanes, int n_lanes, size_t lds, hipStream_t stream, bool rows, bool u8,
-                           unsigned *blocks_out, bool pairs, bool acc64)
+                           bool pairs, bool acc64)
 {
     if (n_lanes < 1 || n_lanes > RG_MAX_LANES) {
         set_error("a multi-lane launch takes 1..%d lanes (got %d)", RG_MAX_LANES, n_lanes);
@@ -1377,29 +1271,7 @@ int mfma_ring_launch_multi(const MfmaArgs &a, const MfmaLane *lanes, int n_lanes
     RingMultiArgs m;
     m.c = a;
     m.n_lanes = n_lanes;
-    for (int i = 0; i < n_lanes; ++i) {
-        RingLane &l = m.lane[i];
-        const MfmaLane &s = lanes[i];
-        l.afrag = s.afrag;
-        l.out = s.out;
-        l.partial_in = s.partial_in;
-        l.partial_out = s.partial_out;
-        l.unit = s.unit;
-        l.c_re = s.c_re;
-        l.c_im = s.c_im;
-        l.rot_step = s.rot_step;
-        l.rot_base = s.rot_base;
-        l.rot64_re = s.rot64_re;
-        l.rot64_im = s.rot64_im;
-        l.sc_re = s.sc_re;
-        l.sc_im = s.sc_im;
-        l.col_shift = s.col_shift;
-        l.finalize = s.finalize;
-        l.conj_sum = s.conj_sum;
-        l.rotate = s.rotate;
-        l.raw_partials = s.raw_partials;
-        l.high_taps_only = s.high_taps_only;
-    }
+    for (int i = 0; i < n_lanes; ++i) m.lane[i] = lanes[i];
     for (int i = n_lanes; i < RG_MAX_LANES; ++i) m.lane[i] = m.lane[0];
     // Which lanes may skip the q2*hi product.  Pairs: the kernel variant skips it for every pair's FIRST lane at compile time,
     // so it is taken only when every first lane is high-byte-only and no second lane is (what the host's pairing of a
@@ -1420,7 +1292,6 @@ int mfma_ring_launch_multi(const MfmaArgs &a, const MfmaLane *lanes, int n_lanes
     const long long ranges = (a.n_out + a.range - 1) / a.range;
     const long long groups = (ranges + 7) / 8;  // ranges are dealt to the 8 XCD classes: workgroup b -> class b % 8
     const unsigned blocks = static_cast<unsigned>(groups * (pairs ? n_lanes / 2 : n_lanes) * 8);
-    if (blocks_out) *blocks_out = blocks;
     if (a.ksteps < 1 || a.ksteps > RG_MAX_KS) {
         set_error("ring kernel: %d k steps not instantiated (1..%d)", a.ksteps, RG_MAX_KS);
         return IQA_EINVAL;

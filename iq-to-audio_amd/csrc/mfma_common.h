@@ -108,9 +108,8 @@ __device__ __forceinline__ void mfma_emit(const MfmaArgs &a, const int *s_acc, i
 int mfma_ring_mode(int decimation, int k_first, int k_count, bool acc64, bool u8);  // 0 none, 1 contiguous, 2 row-staged slots
 bool mfma_ring_supported(int decimation);                                  // mode 1 possible for this decimation
 size_t mfma_ring_lds_bytes(int ksteps, bool rows, bool u8);                // LDS of a block: data ring + window of sums
-int mfma_ring_launch(const MfmaArgs &a, unsigned blocks, size_t lds_bytes, hipStream_t stream, bool rows, bool u8);  // IQA_* status
 
-// one (channel, tap-row group) of a multi-lane launch: the per-lane part of MfmaArgs
+// one (channel, tap-row group) of a ring launch: the per-lane part of MfmaArgs (the kernels' lane table)
 struct MfmaLane {
     const v4i_t *afrag;
     float2 *out;
@@ -123,7 +122,7 @@ struct MfmaLane {
     int col_shift, finalize, conj_sum, rotate, raw_partials, high_taps_only;
 };
 int mfma_ring_launch_multi(const MfmaArgs &common, const MfmaLane *lanes, int n_lanes, size_t lds_bytes, hipStream_t stream, bool rows,
-                           bool u8, unsigned *blocks_out, bool pairs = false, bool acc64 = false);
+                           bool u8, bool pairs, bool acc64);
 bool mfma_ring_pairs_supported(int decimation, int k_first, int k_count, bool u8, bool acc64 = false);  // two lanes per workgroup (contiguous slots, no loader waves)
 
 }  // namespace iqa

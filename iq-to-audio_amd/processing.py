@@ -676,6 +676,20 @@ class ChannelBank:
             c._advance(x, n, last_block)
         return zs
 
+    def _fill_lane(self, lane, k, mp, gi: int, ps, z_out=None, partial_in=None, partial_out=None, raw_partials: bool = False) -> None:
+        """One entry of a lane table (``N.MfmaLane``): tap-row group ``gi`` of channel kernel ``k`` (plan ``mp``) over the
+        k-step range of pass ``ps``.  ``z_out`` (device pointer): a final lane writes z there; else ``partial_out``."""
+        lane.afrag_dev = k.afrag_dev[gi][ps.k_first * P.MFMA_KSTEP_BYTES :].data_ptr()
+        lane.z_out_dev, lane.partial_in_dev, lane.partial_out_dev = z_out, partial_in, partial_out
+        lane.unit = mp.groups[gi].unit / (256.0 if self.fmt == "u8" else 1.0)
+        lane.c_re, lane.c_im = ps.c_re, ps.c_im
+        lane.rot_step, lane.rot_base = k.params.rot_step, k.params.rot_base
+        lane.out_scale_re, lane.out_scale_im = k.params.out_scale_re, k.params.out_scale_im
+        lane.q_group, lane.finalize = mp.groups[gi].q, int(z_out is not None)
+        lane.conj_sum, lane.rotate = k.params.conj_sum, k.params.rotate
+        lane.raw_partials = int(raw_partials)
+        lane.reserved = (0 if k.acc32 else 1) | (2 if mp.groups[gi].high_only else 0)  # (bit 0: 64-bit sums; bit 1: q2 == 0)
+
     def run_interior_only(self, x_all, n_frames: int, m_first: int, n_out: int, outs: list) -> bool:
         """Outputs [m_first, m_first + n_out) of a block that starts the capture, for every channel, matrix-core kernels
         only (no float32 edge launches): what ``_ChannelKernel.run_interior_only`` does for one channel, for callers that
@@ -698,17 +712,7 @@ class ChannelBank:
         rng = max(64, -(-(-(-n_out // ranges)) // 32) * 32)
         table = (N.MfmaLane * len(kernels))()
         for lane, k, mp, z in zip(table, kernels, plans, outs):
-            ps = mp.passes[0]
-            lane.afrag_dev = k.afrag_dev[0][ps.k_first * P.MFMA_KSTEP_BYTES :].data_ptr()
-            lane.z_out_dev = z.data_ptr()
-            lane.partial_in_dev = lane.partial_out_dev = None
-            lane.unit = mp.groups[0].unit / (256.0 if self.fmt == "u8" else 1.0)
-            lane.c_re, lane.c_im = ps.c_re, ps.c_im
-            lane.rot_step, lane.rot_base = k.params.rot_step, k.params.rot_base
-            lane.out_scale_re, lane.out_scale_im = k.params.out_scale_re, k.params.out_scale_im
-            lane.q_group, lane.finalize = mp.groups[0].q, 1
-            lane.conj_sum, lane.rotate = k.params.conj_sum, k.params.rotate
-            lane.raw_partials = 0
+            self._fill_lane(lane, k, mp, 0, mp.passes[0], z_out=z.data_ptr())
             k.last_kernel = ("k_channelize_mfma_u8" if self.fmt == "u8" else "k_channelize_mfma_s16") + "_ring"
         N.call("iqa_channelize_mfma_multi", c_int32(P.FMT_CODE[self.fmt]), c_int32(self.decimation), c_int32(ps0.k_first),
                c_int32(ps0.k_count), c_int32(rng), table, c_int32(len(kernels)), N.ptr(x_all), c_int64(n_frames), c_int64(0),
@@ -767,18 +771,9 @@ class ChannelBank:
                     ps = next(p_ for p_ in mp.passes if p_.group == gi and p_.k_first == k_first)
                     fin = last_range and len(mp.groups) == 1
                     buf = partial.get((ci, gi))
-                    lane.afrag_dev = k.afrag_dev[gi][k_first * P.MFMA_KSTEP_BYTES :].data_ptr()
-                    lane.z_out_dev = zs[ci][m_a - m_first :].data_ptr() if fin else None
-                    lane.partial_in_dev = buf.data_ptr() if (buf is not None and ri > 0) else None
-                    lane.partial_out_dev = None if fin else buf.data_ptr()
-                    lane.unit = mp.groups[gi].unit / (256.0 if self.fmt == "u8" else 1.0)
-                    lane.c_re, lane.c_im = ps.c_re, ps.c_im
-                    lane.rot_step, lane.rot_base = k.params.rot_step, k.params.rot_base
-                    lane.out_scale_re, lane.out_scale_im = k.params.out_scale_re, k.params.out_scale_im
-                    lane.q_group, lane.finalize = mp.groups[gi].q, int(fin)
-                    lane.conj_sum, lane.rotate = k.params.conj_sum, k.params.rotate
-                    lane.raw_partials = int(raw and not fin)
-                    lane.reserved = (0 if acc32 else 1) | (2 if mp.groups[gi].high_only else 0)  # (bit 0: 64-bit sums; bit 1: q2 == 0)
+                    self._fill_lane(lane, k, mp, gi, ps, z_out=zs[ci][m_a - m_first :].data_ptr() if fin else None,
+                                    partial_in=buf.data_ptr() if (buf is not None and ri > 0) else None,
+                                    partial_out=None if fin else buf.data_ptr(), raw_partials=raw and not fin)
                 N.call(entry, c_int32(P.FMT_CODE[self.fmt]), c_int32(self.decimation), c_int32(k_first), c_int32(k_count), c_int32(rng),
                        table, c_int32(len(part)), N.ptr(big), c_int64(big_frames), c_int64(big_consumed), c_int64(m_a), c_int64(n_int),
                        N.stream_ptr())
