@@ -378,11 +378,13 @@ def test_mfma_plan_quantisation_is_exact_and_overflow_proof(fs, bw, d):
         assert ps.c_re == 128.0 * float(sl[:64].sum()) and ps.c_im == 128.0 * float(sl[64:].sum())
 
 
-def _emulate_mfma_outputs(mp, raw_s16: np.ndarray, d: int, ms):
+def _emulate_mfma_outputs_loop(mp, raw_s16: np.ndarray, d: int, ms, acc32: bool = True):
     """What the int16 matrix-core kernels compute for outputs ``ms`` from a plan, in exact integer arithmetic on the
-    host: per group and k-step range 65536*S1 + 256*S2 + 128*sum(T) with S1 = sum q1*hi, S2 = sum q1*lo' + q2*hi (the
-    q2*lo' products are dropped, as the kernels drop them), scaled by the group's unit and added in group order --
-    ``mfma_scaled_sum`` + ``iqa_mfma_combine`` / the chained passes (csrc/mfma_common.h).  No rotation (theta = 0 plans)."""
+    host, one output and one tap row at a time: per group and k-step range 65536*S1 + 256*S2 + 128*sum(T) with
+    S1 = sum q1*hi, S2 = sum q1*lo' + q2*hi (the q2*lo' products are dropped, as the kernels drop them), scaled by the
+    group's unit and added in pass order -- ``mfma_scaled_sum`` + the chained passes (csrc/mfma_common.h).  No rotation
+    (theta = 0 plans).  ``acc32``: the ring kernel's one-int32 sums, whose bound is asserted per tap row and output.
+    The independent statement that ``oracle.mfma_model`` (the vectorised model) is held to bit for bit."""
     v = raw_s16.astype(np.int64)
     lo = (v & 255) - 128
     hi = (v - lo - 128) >> 8
@@ -404,12 +406,28 @@ def _emulate_mfma_outputs(mp, raw_s16: np.ndarray, d: int, ms):
                     r = comp * 64 + qq - 1
                     s1 = int((q1[r] * hi[seg]).sum())
                     s2 = int((q1[r] * lo[seg]).sum() + (q2[r] * hi[seg]).sum())
-                    assert abs(256 * s1 + s2) < 2**31  # what the ring kernel keeps in ONE int32 (per tap row here: a fortiori)
+                    if acc32:
+                        assert abs(256 * s1 + s2) < 2**31  # what the ring kernel keeps in ONE int32 (per tap row here: a fortiori)
                     s[comp] += 256 * s1 + s2
-            assert np.all(np.abs(s) < 2**31)
+            if acc32:
+                assert np.all(np.abs(s) < 2**31)
             c = np.array([ps.c_re, ps.c_im])
             out[i] += complex(*((256.0 * s + c) * grp.unit))
     return out
+
+
+def _emulate_mfma_outputs(mp, raw_s16: np.ndarray, d: int, m_first: int, n_out: int, acc32: bool = True):
+    """The same arithmetic for outputs m_first .. m_first + n_out - 1 through the shared vectorised model
+    (oracle/mfma_model.py), complex128 before any rotation or float32 rounding."""
+    from oracle import mfma_model as M
+
+    s = M.plan_sums(mp, raw_s16, "s16", d, 0, m_first, n_out, acc32)
+    if acc32:  # the int32 bound the plan guarantees: no pass's sum wrapped
+        for ps in mp.passes:
+            grp = mp.groups[ps.group]
+            s1, s2 = M.pass_sums(grp.tq, raw_s16, "s16", d, grp.q, ps.k_first, ps.k_count, 0, m_first, n_out)
+            assert np.array_equal(M.ring_value(s1, s2, True), M.ring_value(s1, s2, False))
+    return s[:, 0] + 1j * s[:, 1]
 
 
 @pytest.mark.parametrize("fs,bw,d,max_ks", [(10e6, 12_500.0, 104, None), (2.5e6, 12_500.0, 26, 11), (20e6, 2_800.0, 208, None), (50e6, 12_500.0, 521, 11)])
@@ -418,21 +436,34 @@ def test_mfma_plan_precisions_by_integer_emulation(fs, bw, d, max_ks):
     stands for, per precision of the plan: "fast" (one group per 64 tap rows, ~14-bit taps under the int32 bound) and
     "fine" (``residual=True``: high-byte-only taps + their residue as a second group of the same tap rows).  The error
     must match the plan's own prediction (``z_error_rms``: tap rounding x wideband level + the dropped q2*lo' floor), and
-    the fine plan must be >= 8x closer.  Runs over a full-scale capture (noise + tone), outputs spread over the block."""
+    the fine plan must be >= 8x closer.  Runs over a full-scale capture (noise + tone), outputs spread over the block:
+    7 of them through the per-output loop, which the vectorised model (oracle/mfma_model.py) must equal bit for bit, and
+    ~2000 consecutive ones through the model alone, held to the same prediction."""
     taps = P.design_channel_filter(fs, bw, d)
     plan = P.plan_channel(taps, sample_rate=fs, freq_offset=0.0, mix_sign=1, decimation=d, fmt="s16", iq_order="iq")
     groups_q = max(1, -(-(-(-len(taps) // d)) // P.MFMA_Q))
     rng = np.random.default_rng(5)
-    n = (64 * groups_q + 40) * d + 64 * d
+    n_long = 2000
+    n = (64 * groups_q + 40) * d + 64 * d + n_long * d
     t_ = np.arange(n) / fs
     x = 0.5 * np.exp(2j * np.pi * 3_000.0 * t_) + 0.25 * (rng.normal(size=n) + 1j * rng.normal(size=n))
     raw = np.rint(np.clip(np.column_stack((x.real, x.imag)), -0.999, 0.999) * 32767.0).astype(np.int16).reshape(-1)
     wide = float(np.sqrt(np.mean((raw.astype(np.float64) / 32768.0) ** 2) * 2.0))
-    ms = list(range(64 * groups_q + 1, 64 * groups_q + 36, 5))
+    m0 = 64 * groups_q + 1
+    ms = list(range(m0, 64 * groups_q + 36, 5))
     xc = (raw[0::2].astype(np.float64) + 1j * raw[1::2].astype(np.float64))
     g = plan.taps_natural  # ingest scale folded in
-    want = np.array([np.sum(g[: min(len(g), m * d + 1)] * xc[m * d - np.arange(min(len(g), m * d + 1))]) for m in ms])
-    errs = {}
+
+    def direct(ms_):
+        return np.array([np.sum(g[: min(len(g), m * d + 1)] * xc[m * d - np.arange(min(len(g), m * d + 1))]) for m in ms_])
+
+    want = direct(ms)
+    # the long run: every output m0 .. m0 + n_long - 1, float64 convolution by FFT (error ~1e-13 of full scale)
+    nfft = 1 << int(np.ceil(np.log2(xc.size + g.size)))
+    conv = np.fft.ifft(np.fft.fft(xc, nfft) * np.fft.fft(g, nfft))
+    want_long = conv[np.arange(m0, m0 + n_long) * d]
+    np.testing.assert_allclose(want_long[(np.array(ms) - m0)], want, rtol=0, atol=1e-12)
+    errs, errs_long = {}, {}
     for name, kw in (("fast", dict(acc32=True)), ("fine", dict(acc32=True, residual=True)), ("full", dict(acc32=False, residual=True))):
         mp = P.plan_mfma(plan, max_ksteps=max_ks, **kw)
         n_parts = 2 if kw.get("residual") else 1
@@ -441,34 +472,43 @@ def test_mfma_plan_precisions_by_integer_emulation(fs, bw, d, max_ks):
         if kw.get("residual"):
             for gr in mp.groups[0::2]:
                 assert not np.any(gr.tq & 255)  # high byte only: nothing for the kernels to drop
-        got = _emulate_mfma_outputs(mp, raw, d, ms) if kw["acc32"] else None
-        if got is None:
-            # 16-bit taps (separate S1/S2 sums: the per-lane kernel): the same arithmetic without the one-int32 bound
-            got = np.zeros(len(ms), dtype=np.complex128)
-            v = raw.astype(np.int64)
-            lo = (v & 255) - 128
-            hi = (v - lo - 128) >> 8
-            for ps in mp.passes:
-                grp = mp.groups[ps.group]
-                c0, c1 = 32 * ps.k_first, 32 * (ps.k_first + ps.k_count)
-                t = grp.tq[:, c0:c1].astype(np.int64)
-                q2 = ((t + 128) & 255) - 128
-                q1 = (t - q2) >> 8
-                for i, m in enumerate(ms):
-                    s = np.zeros(2)
-                    for qq in range(1, 65):
-                        first = 2 * ((m - (64 * grp.q + qq)) * d + 1) + c0
-                        seg = slice(first, first + c1 - c0)
-                        for comp in (0, 1):
-                            r = comp * 64 + qq - 1
-                            s[comp] += 65536.0 * float((q1[r] * hi[seg]).sum()) + 256.0 * float((q1[r] * lo[seg]).sum() + (q2[r] * hi[seg]).sum())
-                    got[i] += complex(*((s + np.array([ps.c_re, ps.c_im])) * grp.unit))
+        # (16-bit taps -- "full" -- are the separate S1/S2 sums of the per-lane kernel: no one-int32 bound to hold)
+        got = _emulate_mfma_outputs_loop(mp, raw, d, ms, acc32=kw["acc32"])
+        long = _emulate_mfma_outputs(mp, raw, d, m0, n_long, acc32=kw["acc32"])
+        assert np.array_equal(long[np.array(ms) - m0], got)  # the vectorised model IS the per-output loop, bit for bit
         err = float(np.sqrt(np.mean(np.abs(got - want) ** 2)))
         pred = mp.z_error_rms(wide)
         errs[name] = err
         assert err < 4.0 * pred + 1e-12, (name, err, pred)  # (7 outputs: a coarse estimate of an RMS)
+        errs_long[name] = err_long = float(np.sqrt(np.mean(np.abs(long - want_long) ** 2)))
+        assert err_long < 2.0 * pred + 1e-12, (name, err_long, pred)
     assert errs["fine"] * 8.0 < errs["fast"], errs
     assert errs["full"] < 3e-8 and errs["full"] <= errs["fine"], errs
+    assert errs_long["fine"] * 8.0 < errs_long["fast"], errs_long
+    assert errs_long["full"] < 3e-8 and errs_long["full"] <= errs_long["fine"], errs_long
+
+
+def test_mfma_exact_sweep_covers_every_ring_instantiation():
+    """tests/test_gpu_mfma_exact.py compares one launch of every ring-kernel instantiation with the exact model: its
+    sweep (oracle/mfma_dispatch.py) names all 129 kernels ring_launch_multi / ring_launch_pairs can select, and for every
+    case the library's own queries (iqa_mfma_ring_mode / _lanes / _pairs) agree with the restated dispatch on the slot
+    form and on pair availability."""
+    from oracle import mfma_dispatch as X
+
+    cases = X.sweep_cases()
+    got = {X.sweep_kernel(*c) for c in cases}
+    want = X.all_ring_instantiations()
+    assert len(want) == 129
+    assert got == want, (sorted(want - got), sorted(got - want))
+    lib = A.native.lib()
+    for kind, ks, d in cases:
+        entry, fmt, acc64, _ = X.case_launch(kind, ks, d)
+        assert -(-2 * d // 32) == ks
+        X.abi_agrees(lib, entry, fmt, d, 0, ks, acc64, X.sweep_kernel(kind, ks, d))
+    # the uint8 and int16 row-staged kernels over later k-step ranges of a long row (D = 521: three passes of 11)
+    for fmt in ("u8", "s16"):
+        for kf in (0, 11, 22):
+            X.abi_agrees(lib, "multi", fmt, 521, kf, 11, False, X.expected_kernel("multi", fmt, 521, kf, 11, False, False))
 
 
 def test_mfma_interior_with_lead_in_and_slack():
