@@ -362,12 +362,35 @@ int iqa_writer_clip(const void *a_dev, int64_t n, void *peak_dev, const void *se
  * table_dev: double[up][2T+1] polyphase rows; x zero outside [0, n_in).       *
  * y_dev: float32[n_out] and/or pcm16_dev: int16[n_out] = iqa_float_to_pcm16 of the float32 value (the writer's    *
  * `-acodec pcm_s16le` leg in the same pass); either may be NULL, not both.                                       *
+ * Rows of up to 192 taps run on the staged kernel; longer rows (input rates above ~6x the output rate, up to      *
+ * 4097 taps) on a direct one, sixteen lanes per output: the same sums, in another fixed order.                  *
  * ------------------------------------------------------------------------- */
 int iqa_resample(const void *x_dev, int64_t n_in, const void *table_dev, int32_t up, int32_t down, int32_t T,
                  int64_t j0, int64_t n_out, void *y_dev, void *pcm16_dev, void *stream);
 
 /* float32 -> PCM16 (round-half-even of y*32768, saturated).  Build-defined, see above. */
 int iqa_float_to_pcm16(const void *y_dev, int64_t n, void *pcm_dev, void *stream);
+
+/* ------------------------------------------------------------------------- *
+ * Wideband FM stereo (--demod wfm)                      *
+ * ------------------------------------------------------------------------- */
+
+/* Longest stereo-matrix filter (N taps): fs_channel up to ~1.4 MHz. */
+#define IQA_WFM_MAX_TAPS 2047
+/* Partial sums of |p|^2 a stereo-matrix call over n samples writes: ceil(n / 2048), 0 for n <= 0. */
+int64_t iqa_wfm_partials(int64_t n);
+/* One block of the stereo matrix.  theta_dev: float32[n] discriminator output (radians per sample); m = m_scale * theta is
+ * the composite (m_scale = fs / (2 pi 75 000)).  With N = ntaps (odd, 3..IQA_WFM_MAX_TAPS), D = (N-1)/2 and causal filters of
+ * zero initial state: p = h_p * m, c = -Im((p/|p|)^2) (0 where |p| < 1e-12), md[n] = m[n-D], a = h_a * md, b = h_a * (2 md c).
+ * taps_dev: float32[3(D+1)] = h_a[0..D], Re h_p[0..D], Im h_p[0..D] (h_a symmetric, h_p[N-1-k] = conj(h_p[k])).
+ * hist_dev: float32[2(N-1)], the discriminator values in front of theta[0] (NULL: zeros, the start of a stream).
+ * a_out_dev, b_out_dev: float32[n]; m_out_dev (optional): float32[n] composite; partials_dev (optional):
+ * double[iqa_wfm_partials(n)], the sum of |p|^2 over each 2048 outputs.  Every output is summed in one fixed order: the
+ * outputs do not depend on how a stream is cut into calls. */
+int iqa_wfm_stereo(int32_t ntaps, const void *taps_dev, float m_scale, const void *theta_dev, int64_t n, const void *hist_dev,
+                   void *m_out_dev, void *a_out_dev, void *b_out_dev, void *partials_dev, void *stream);
+/* left = a + b, right = a - b (float32[n]; in place allowed). */
+int iqa_wfm_matrix(const void *a_dev, const void *b_dev, int64_t n, void *left_dev, void *right_dev, void *stream);
 
 /* Audio egress (the drain of AudioWriter, processing.py:433-438, without a host thread): copy nbytes from device
  * memory into MAPPED pinned host memory (hipHostMalloc / torch pin_memory) with `workgroups` small workgroups

@@ -141,6 +141,10 @@ _SIGNATURES = {
     "iqa_psd_frames": (ctypes.c_int, [c_int32, c_int32, c_void_p, c_int64, c_int64, c_int64, c_int32, c_int32, c_int32, c_void_p,
                                       c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "iqa_pair_average_rows": (ctypes.c_int, [c_void_p, c_int32, c_int32, c_void_p, c_void_p]),
+    "iqa_wfm_partials": (c_int64, [c_int64]),
+    "iqa_wfm_stereo": (ctypes.c_int, [c_int32, c_void_p, c_float, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
+                                      c_void_p, c_void_p]),
+    "iqa_wfm_matrix": (ctypes.c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
     "iqa_squelch_workspace_bytes": (c_int64, [c_int64, c_int32]),
     "iqa_squelch_stage_offset": (c_int64, [c_int64, c_int32, c_int32]),
     "iqa_squelch": (ctypes.c_int, [ctypes.POINTER(SquelchParams), ctypes.POINTER(SquelchSeg), c_int32, c_void_p, c_void_p,

@@ -18,6 +18,14 @@ from .processing import (PRECISION_GUARD, ChannelBank, ChannelDemod, Channelizer
                          base_precision, immutable_taps, pick_precision, probe_targets, reserve_pinned_scalars)
 
 
+def reject_wfm(modes) -> None:
+    """The resident runners demodulate on the fused ``iqa_demodulate`` engine, which has no wideband FM form: a wfm target
+    is a ``ValueError`` up front (run it through ``ProcessingPipeline`` / ``MultiChannelPipeline``)."""
+    if any((m or "").lower() == "wfm" for m in modes):
+        raise ValueError("wfm targets are not supported by the resident batch runners or sharded runs: "
+                         "use ProcessingPipeline / MultiChannelPipeline")
+
+
 def _rank(precision: str) -> int:
     return _ChannelKernel.PRECISIONS.index(precision)
 
@@ -69,6 +77,7 @@ class ResidentCaptureRunner:
         of GPU time per capture for 50 MB) -- so the chains of two or three captures side by side fill the gaps of one
         another.  Only for captures that are complete in device memory when ``submit_captured`` is called (the replay is not
         ordered behind the caller's stream)."""
+        reject_wfm([demod_mode])
         torch = D.torch_mod()
         if slots is not None:
             if slots < 2:
@@ -444,6 +453,7 @@ class ResidentBankRunner:
                  fs_ch_target: float = 96_000.0, fmt: str = "s16", iq_order: str = "iq", precision_guard: float | None = None):
         """``targets``: dicts with ``freq_offset``, and optionally ``bandwidth`` (12 500), ``demod_mode`` ("nfm"),
         ``deemph_us`` (300), ``agc_enabled`` (True), ``mix_sign`` (None = probe), ``precision`` (None = by demodulator)."""
+        reject_wfm([t.get("demod_mode") for t in targets])
         torch = D.torch_mod()
         if not targets:
             raise ValueError("at least one target is required")
@@ -623,6 +633,7 @@ def demodulate_sharded(targets: list, *, sample_rate: float, n_frames: int, axis
     the broadcast (channel axis) and the final gather of the audio."""
     from . import dist as DS
 
+    reject_wfm([t.get("demod_mode") for t in targets])
     torch = D.torch_mod()
     if axis not in ("channels", "captures"):
         raise ValueError("axis must be 'channels' or 'captures'")

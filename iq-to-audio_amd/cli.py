@@ -53,17 +53,38 @@ def parse_user_format(text: str) -> tuple[str | None, str]:
     return container, codec
 
 
+class ModeDefault(float):
+    """A ``--bw`` / ``--fs-ch`` / ``--deemph`` value the user did not give: the existing modes' default (it compares equal
+    to it), replaced by ``resolve_mode_defaults`` where the mode has its own.  An explicit value is a plain float."""
+
+
+#: the defaults --demod wfm resolves unset --bw / --fs-ch / --deemph to (broadcast FM: 250 kHz channel, 480 kHz rate, 50 us)
+WFM_DEFAULTS = {"bandwidth": 250_000.0, "fs_ch": 480_000.0, "deemph_us": 50.0}
+
+
+def resolve_mode_defaults(args):
+    """Replace every unset ``--bw`` / ``--fs-ch`` / ``--deemph`` by the default of ``--demod``; explicit values win."""
+    for dest, wfm_value in WFM_DEFAULTS.items():
+        value = getattr(args, dest)
+        if isinstance(value, ModeDefault):
+            setattr(args, dest, wfm_value if args.demod == "wfm" else float(value))
+    return args
+
+
 def build_parser() -> argparse.ArgumentParser:
     p = argparse.ArgumentParser(prog="iq-to-audio-amd",
                                 description="Extract and demodulate narrowband channels from SDR I/Q captures on an MI355X.")
     p.add_argument("--in", dest="input_path", type=Path, help="Input capture (WAV PCM_U8/PCM_16/FLOAT or raw .cu8/.cs16/.cf32).")
     p.add_argument("--ft", dest="target_freqs", type=positive_float, action="append", default=None,
                    help="Target RF frequency in Hz. Supply up to five times to batch additional channels.")
-    p.add_argument("--bw", dest="bandwidth", type=positive_float, default=12_500.0)
+    p.add_argument("--bw", dest="bandwidth", type=positive_float, default=ModeDefault(12_500.0),
+                   help="Channel bandwidth in Hz (default 12 500; 250 000 for --demod wfm).")
     p.add_argument("--fc", dest="center_freq", type=positive_float, help="Centre frequency in Hz if filename parsing fails.")
-    p.add_argument("--fs-ch", dest="fs_ch", type=positive_float, default=96_000.0)
-    p.add_argument("--demod", dest="demod", choices=["nfm", "am", "usb", "lsb", "ssb", "none"], default="nfm")
-    p.add_argument("--deemph", dest="deemph_us", type=positive_float, default=300.0)
+    p.add_argument("--fs-ch", dest="fs_ch", type=positive_float, default=ModeDefault(96_000.0),
+                   help="Target channel rate in Hz (default 96 000; 480 000 for --demod wfm).")
+    p.add_argument("--demod", dest="demod", choices=["nfm", "am", "usb", "lsb", "ssb", "wfm", "none"], default="nfm")
+    p.add_argument("--deemph", dest="deemph_us", type=positive_float, default=ModeDefault(300.0),
+                   help="De-emphasis time constant in microseconds (default 300; 50 for --demod wfm, 75 in the Americas).")
     p.add_argument("--no-agc", dest="agc_enabled", action="store_false")
     p.add_argument("--out", dest="output_path", type=Path)
     p.add_argument("--dump-iq", dest="dump_iq", type=Path)
@@ -162,7 +183,7 @@ def _preview_output_path(config: ProcessingConfig) -> Path:
 
 def main(argv: list[str] | None = None) -> int:
     parser = build_parser()
-    args = parser.parse_args(argv)
+    args = resolve_mode_defaults(parser.parse_args(argv))
     if args.audio_post_path and args.benchmark:
         parser.error("--audio-post cannot be combined with --benchmark.")
     if args.audio_post_path and not 0.0 <= args.audio_post_percentile <= 1.0:

@@ -527,6 +527,38 @@ __global__ __launch_bounds__(RS_WAVES *kWave) void k_resample(RsArgs a)
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // no DMA may land in LDS the workgroup has given back
 }
 
+// Rows longer than the staged window holds (input rates above ~6x the output rate: the ~480 kHz channels of wideband FM
+// have 321 taps per row): sixteen lanes per output, lane s takes taps s, s + 16, ... in float64, and the sixteen partial
+// sums are added in a fixed butterfly order.  Same specification as k_resample.
+constexpr int RS_LONG_LANES = 16;
+
+template <bool WANT_Y, bool WANT_PCM>
+__global__ __launch_bounds__(256) void k_resample_long(const float *x, long long n_in, const double *table, int up, int down, int T,
+                                                       long long j0, long long n_out, float *y, short *pcm)
+{
+    const long long j = (static_cast<long long>(blockIdx.x) * blockDim.x + threadIdx.x) / RS_LONG_LANES;
+    const int s = static_cast<int>(threadIdx.x) & (RS_LONG_LANES - 1);
+    const bool live = j < n_out;
+    const long long c = (j0 + (live ? j : 0)) * down;
+    const long long q = c / up;
+    const int p = static_cast<int>(c - q * up);
+    const int row_len = 2 * T + 1;
+    const double *row = table + static_cast<long long>(p) * row_len;
+    double acc = 0.0;
+    for (int t = s; t < row_len; t += RS_LONG_LANES) {
+        const long long idx = q - (t - T);
+        const float v = (idx >= 0 && idx < n_in) ? x[idx] : 0.f;
+        acc = fma(row[t], static_cast<double>(v), acc);
+    }
+#pragma unroll
+    for (int o = RS_LONG_LANES / 2; o > 0; o >>= 1) acc += __shfl_xor(acc, o, kWave);
+    if (live && s == 0) {
+        const float v = static_cast<float>(acc);
+        if constexpr (WANT_Y) y[j] = v;
+        if constexpr (WANT_PCM) pcm[j] = pcm16_of_f32(v);
+    }
+}
+
 }  // namespace iqa
 
 using namespace iqa;
@@ -629,9 +661,21 @@ extern "C" int iqa_resample(const void *x_dev, int64_t n_in, const void *table_d
     if (n_in < 0 || n_out < 0 || j0 < 0 || up < 1 || down < 1 || T < 0) return fail_inval("bad resampler sizes");
     if (n_out == 0) return IQA_OK;
     if (!table_dev || (!y_dev && !pcm16_dev) || (n_in > 0 && !x_dev)) return fail_inval("NULL device pointer");
-    if (2 * T + 1 > 192) return fail_inval("resampler rows longer than 192 taps are not supported");
+    if (2 * T + 1 > 4097) return fail_inval("resampler rows longer than 4097 taps are not supported");
     if (n_in > (1LL << 30) - 4096) return fail_inval("resampler input longer than 2^30 samples: process it in blocks");
     if (j0 > (1LL << 40) || static_cast<int64_t>(up) * down >= (1LL << 50)) return fail_inval("resampler position out of range");
+    if (2 * T + 1 > 192) {
+        if (j0 + n_out > (1LL << 62) / down || n_out > (1LL << 36)) return fail_inval("resampler position out of range");
+        const dim3 grid = grid1d(n_out * RS_LONG_LANES, 256);
+        const float *x = static_cast<const float *>(x_dev);
+        const double *table = static_cast<const double *>(table_dev);
+        float *y = static_cast<float *>(y_dev);
+        short *pcm = static_cast<short *>(pcm16_dev);
+        if (y && pcm) hipLaunchKernelGGL((k_resample_long<true, true>), grid, dim3(256), 0, as_stream(stream), x, (long long)n_in, table, up, down, T, (long long)j0, (long long)n_out, y, pcm);
+        else if (y) hipLaunchKernelGGL((k_resample_long<true, false>), grid, dim3(256), 0, as_stream(stream), x, (long long)n_in, table, up, down, T, (long long)j0, (long long)n_out, y, pcm);
+        else hipLaunchKernelGGL((k_resample_long<false, true>), grid, dim3(256), 0, as_stream(stream), x, (long long)n_in, table, up, down, T, (long long)j0, (long long)n_out, y, pcm);
+        return check_launch("k_resample_long");
+    }
     RsArgs a;
     a.x = static_cast<const float *>(x_dev);
     a.n_in = n_in;

@@ -387,6 +387,64 @@ def chunk_output_starts(chunk: int, decimation: int, first_frame: int, n_frames:
     return (-(-starts // d) - m_first).astype(np.int64)
 
 
+# ---- wideband FM stereo plan (--demod wfm) --------------------------------
+
+WFM_DEVIATION = 75_000.0  # Hz of deviation that reads as composite 1.0
+WFM_PILOT_HZ = 19_000.0
+WFM_ATTEN_DB = 70.0
+WFM_TRANSITION_HZ = 3_000.0
+WFM_AUDIO_CUTOFF = 16_500.0
+WFM_PILOT_CUTOFF = 1_500.0
+WFM_MIN_RATE = 128_000.0  # below it the 38 kHz stereo subcarrier's upper band (53 kHz) does not fit the channel
+WFM_MAX_TAPS = 2047  # IQA_WFM_MAX_TAPS
+WFM_STEREO_LEVEL = 0.01  # sqrt(mean |p|^2) at or above which the output is stereo (a 10 % pilot reads 0.05)
+
+
+@dataclass(frozen=True)
+class WfmPlan:
+    fs: float
+    ntaps: int  # N
+    delay: int  # (N - 1) / 2
+    h_audio: np.ndarray  # float64[N], the 16.5 kHz low-pass h_a
+    h_pilot: np.ndarray  # complex128[N], the analytic pilot filter h_p
+    m_scale: float  # composite per radian of the discriminator: fs / (2 pi 75 000)
+    taps_packed: np.ndarray  # float32[3 (delay + 1)]: h_a[0..delay], Re h_p[0..delay], Im h_p[0..delay] (iqa_wfm_stereo)
+
+
+def wfm_num_taps(fs_channel: float) -> int:
+    """N = ceil((70 - 7.95) / (2.285 * 2 pi * 3000 / fs)) (Kaiser's length rule), rounded up to odd: 347 at 240 kHz, 693 at 480."""
+    n = int(math.ceil((WFM_ATTEN_DB - 7.95) / (2.285 * 2.0 * math.pi * WFM_TRANSITION_HZ / float(fs_channel))))
+    return n + 1 if n % 2 == 0 else n
+
+
+def _kaiser_lowpass(n: int, cutoff: float, fs: float, beta: float) -> np.ndarray:
+    """The windowed-sinc construction of ``design_channel_filter``, normalised to sum 1."""
+    fc = cutoff / (0.5 * fs)
+    m = np.arange(n, dtype=np.float64) - (n - 1) / 2.0
+    h = fc * np.sinc(fc * m) * np.kaiser(n, beta)
+    return h / h.sum()
+
+
+@functools.lru_cache(maxsize=16)
+def plan_wfm(fs_channel: float) -> WfmPlan:
+    """The stereo matrix's filters at channel rate ``fs_channel`` (float64; shared, read-only)."""
+    fs = float(fs_channel)
+    if not fs >= WFM_MIN_RATE:
+        raise ValueError(f"wfm needs a channel rate of at least {WFM_MIN_RATE:.0f} Hz (--fs-ch), not {fs:.0f} Hz")
+    n = wfm_num_taps(fs)
+    if n > WFM_MAX_TAPS:
+        raise ValueError(f"wfm channel rate {fs:.0f} Hz needs {n} taps; at most {WFM_MAX_TAPS} are supported (lower --fs-ch)")
+    beta = kaiser_beta(WFM_ATTEN_DB)
+    delay = (n - 1) // 2
+    h_a = _kaiser_lowpass(n, WFM_AUDIO_CUTOFF, fs, beta)
+    k = np.arange(n, dtype=np.float64) - delay
+    h_p = _kaiser_lowpass(n, WFM_PILOT_CUTOFF, fs, beta) * np.exp(2j * np.pi * WFM_PILOT_HZ * k / fs)
+    packed = np.concatenate([h_a[: delay + 1], h_p.real[: delay + 1], h_p.imag[: delay + 1]]).astype(np.float32)
+    for arr in (h_a, h_p, packed):
+        arr.setflags(write=False)
+    return WfmPlan(fs, n, delay, h_a, h_p, float(np.float32(fs / (2.0 * math.pi * WFM_DEVIATION))), packed)
+
+
 # ---- 48 kHz resampler plan (build-defined spec; see DESIGN.md "48 kHz stage") -----------------
 
 RS_ZERO_CROSSINGS = 16

@@ -32,6 +32,7 @@ from . import _native as N
 from . import dsp_plan as P
 from . import iqio
 from .decoders import create_decoder
+from .decoders.wfm import WfmStereoCore, stereo_matrix
 from .dsp_plan import design_channel_filter, tune_chunk_size  # noqa: F401  (re-exported API)
 from .progress import PhaseState, ProgressSink, ProgressTracker
 
@@ -934,6 +935,8 @@ def wideband_rms_from(mean_square: float, fmt: str) -> float:
 #: probed level is below guard x (expected z error) is therefore channelized at the next precision that clears it
 #: (measured: a -70 dBFS NFM signal beside a full-scale tone comes out 2.8e-4 RMS off the reference at "fast").
 PRECISION_GUARD = 1000.0
+#: the demodulators that divide by |z| (the discriminator): what the guard protects
+FM_MODES = ("nfm", "fm", "wfm")
 
 
 def pick_precision(kernel_for, base: str, demod_mode: str | None, channel_power, wideband_rms, guard: float | None = None,
@@ -947,7 +950,7 @@ def pick_precision(kernel_for, base: str, demod_mode: str | None, channel_power,
     tap-rounding term follows the level and is unchanged, the level-independent floor grows by that factor."""
     levels = _ChannelKernel.PRECISIONS
     guard = PRECISION_GUARD if guard is None else guard
-    if not guard or channel_power is None or wideband_rms is None or (demod_mode or "").lower() not in ("nfm", "fm"):
+    if not guard or channel_power is None or wideband_rms is None or (demod_mode or "").lower() not in FM_MODES:
         return base
     level = math.sqrt(max(float(channel_power), 0.0))
     for name in levels[levels.index(base):]:
@@ -1272,6 +1275,95 @@ class ChannelDemod:
         return out
 
 
+class WfmDemod:
+    """``ChannelDemod``'s block surface for ``--demod wfm``.
+
+    Per block: the discriminator and ONE launch of the stereo matrix kernel (``iqa_wfm_stereo``) write the mono and
+    stereo-difference planes (a, b) into the caller's ``(2, n)`` slice, and the block's per-tile sums of |p|^2 are added to a
+    device running sum -- nothing is read back.  ``finish`` reads that sum once, takes the run's stereo decision
+    (sqrt(mean |p|^2) >= ``dsp_plan.WFM_STEREO_LEVEL``) and runs the tail on the channels it writes (L, R or a): de-emphasis,
+    the writer's pre-clip peak, +-0.99 clip and per-chunk sums of squares, 48 kHz PCM16."""
+
+    def __init__(self, fs_channel: float, *, deemph_us: float):
+        self.decoder = create_decoder("wfm", deemph_us=deemph_us, agc_enabled=False, extensions=True)
+        self.decoder.setup(fs_channel)  # (plans the filters; ValueError below the mode's minimum rate)
+        self.fs_channel = float(fs_channel)
+        self.alpha = self.decoder.deemph["mono"].alpha  # the DeemphasisFilter rule
+        self.core = self.decoder.core  # the pipeline's stream: the decoder's own stage API is not used beside it
+        self._prev = D.from_numpy(np.array([1 + 0j], dtype=np.complex64))
+        self._pilot_sumsq = D.zeros(1, "float64")
+        self._starts: list = []  # chunk starts of the run, channel-rate sample index
+        self.n = 0
+        self._prepared = None
+        self.stereo = None
+        self.pilot_level = None
+        self.channel_audio = None  # de-emphasised, clipped channel-rate audio (list of device tensors) after finish
+        self._peak = 0.0
+        self._sumsq = None
+        self._counts = None
+
+    def prepare(self, n: int, chunk_starts: np.ndarray) -> None:
+        self._prepared = (n, D.empty(n, "float32"), D.empty(max(1, WfmStereoCore.partials_for(n)), "float64"))
+
+    def process(self, z_dev, chunk_starts: np.ndarray, out_dev) -> None:
+        """z_dev -> a, b written into ``out_dev`` (shape (2, len(z_dev)))."""
+        n = int(z_dev.numel())
+        if n == 0:
+            return
+        if self._prepared is None or self._prepared[0] != n:
+            self.prepare(n, chunk_starts)
+        _, theta, partials = self._prepared
+        self._prepared = None
+        N.call("iqa_quadrature", N.ptr(z_dev), c_int64(n), N.ptr(self._prev), N.ptr(theta), N.stream_ptr())
+        self.core.process(theta, out_dev[0], out_dev[1], partials=partials)
+        self._pilot_sumsq += partials[: WfmStereoCore.partials_for(n)].sum()
+        self._starts.append(np.asarray(chunk_starts, dtype=np.int64) + self.n)
+        self.n += n
+
+    def finish(self, planes):
+        """``planes``: device float32 (2, n), the run's (a, b).  Returns (host int16 PCM at 48 kHz, shape (n48, 2) when stereo
+        else (n48,), channel count)."""
+        torch = D.torch_mod()
+        n = int(planes.shape[1])
+        self.pilot_level = math.sqrt(max(float(self._pilot_sumsq.item()), 0.0) / n) if n else 0.0
+        self.stereo = bool(self.pilot_level >= P.WFM_STEREO_LEVEL)
+        chans = list(stereo_matrix(planes[0], planes[1])) if self.stereo else [planes[0]]
+        starts = np.concatenate(self._starts) if self._starts else np.zeros(1, dtype=np.int64)
+        starts_dev = D.from_numpy(starts)
+        sumsq = D.zeros(len(starts) * 8, "float64")  # IQA_SUMSQ_SLOTS sub-slots per chunk, both channels together
+        peak = D.zeros(1, "float32")
+        work = D.empty(max(1, int(N.lib().iqa_scan_workspace_bytes(n))), "uint8")
+        out = []
+        for x in chans:
+            y = D.empty(n, "float32")
+            if n:
+                state = D.zeros(1, "float64")
+                N.call("iqa_deemphasis", N.ptr(x), c_int64(n), c_double(self.alpha), N.ptr(state), N.ptr(y), N.ptr(work), N.stream_ptr())
+                N.call("iqa_writer_clip", N.ptr(y), c_int64(n), N.ptr(peak), N.ptr(starts_dev), c_int64(len(starts)), N.ptr(sumsq),
+                       N.ptr(y), N.stream_ptr())
+            out.append(y)
+        self.channel_audio = out
+        rs = Resampler48k(self.fs_channel)
+        pcm = [rs.process(y, want="pcm16") for y in out]
+        pcm = torch.stack(pcm, dim=1) if len(pcm) == 2 else pcm[0]  # interleaved L, R
+        self._sumsq, self._counts = sumsq, np.diff(np.append(starts, n)) * len(chans)
+        self._peak = float(peak.item())
+        return pcm.cpu().numpy(), len(chans)
+
+    @property
+    def peak(self) -> float:
+        return self._peak
+
+    def chunk_rms_dbfs(self) -> list[float]:
+        if self._sumsq is None:
+            return []
+        out = []
+        for s, c in zip(self._sumsq.cpu().numpy().reshape(-1, 8).sum(axis=1), self._counts):
+            if c > 0:
+                out.append(20.0 * math.log10(math.sqrt(float(s) / float(c) + 1e-18) + 1e-12))
+        return out
+
+
 class Resampler48k:
     """The ``-ar 48000 -acodec pcm_s16le`` leg (reference processing.py:399-418) on the GPU.
     Build-defined specification (dsp_plan.plan_resampler); parity with libswresample is unpinned."""
@@ -1446,6 +1538,8 @@ class ProcessingPipeline:
         self.channelizer_kernel = None  # name of the channelizer kernel that produced the last block of the run
         self.f32_integer_path = True  # float32 captures whose values are all k / 32768 run as int16 on the matrix cores
         self.channelizer_precision = None  # "fast" / "fine" / "full" / "float32": what the run's channelizer was planned at
+        self.wfm_stereo = None  # --demod wfm: whether the run's output is stereo (the pilot test, once per run)
+        self.wfm_planes = None  # --demod wfm with keep_channel_audio: the stereo matrix's (a, b) planes, shape (2, n)
 
     def cancel(self) -> None:
         self._cancelled = True
@@ -1490,12 +1584,18 @@ class _Target:
         self.target_freq = cfg.target_freq if cfg.target_freq > 0 else center_freq
         self.freq_offset = self.target_freq - center_freq
         self.pass_through = (cfg.demod_mode or "").lower() in {"none", "pass", "iq"}
+        self.wfm = (cfg.demod_mode or "").lower() == "wfm"
         self.taps = design_channel_filter(sample_rate, cfg.bandwidth, decimation)
         LOG.info("Designed FIR channel filter with %d taps.", len(self.taps))
         if cfg.filter_block <= 0:
             raise ValueError("block_size must be positive")
-        self.demod = None if self.pass_through else ChannelDemod(cfg.demod_mode, fs_channel, deemph_us=cfg.deemph_us,
-                                                                 agc_enabled=cfg.agc_enabled)
+        if self.pass_through:
+            self.demod = None
+        elif self.wfm:
+            self.demod = WfmDemod(fs_channel, deemph_us=cfg.deemph_us)
+        else:
+            self.demod = ChannelDemod(cfg.demod_mode, fs_channel, deemph_us=cfg.deemph_us, agc_enabled=cfg.agc_enabled)
+        self.stereo = None  # wfm: the run's stereo decision (finish)
         if cfg.iq_order not in N.ORDER:
             raise ValueError(f"Unsupported iq_order '{cfg.iq_order}'")
         self.chan = None
@@ -1544,7 +1644,7 @@ class _Target:
             power = self.sign_probe.power
             self.sign_probe = None
         self.precision = self._pick_precision(power, wideband_rms)
-        if self.precision != "fast" and (self.cfg.demod_mode or "").lower() in ("nfm", "fm"):
+        if self.precision != "fast" and (self.cfg.demod_mode or "").lower() in FM_MODES:
             LOG.info("Channel level %.1f dBFS against a wideband level of %.1f dBFS: '%s' channelizer for this target.",
                      10.0 * math.log10(max(power or 0.0, 1e-30)), 20.0 * math.log10(max(wideband_rms or 0.0, 1e-15)), self.precision)
         self.chan = self._channelizer(self.mix_sign, precision=self.precision)
@@ -1553,7 +1653,12 @@ class _Target:
         LOG.info("Selected mixer sign %d based on warm-up snippet.", self.mix_sign)
         n_dec_total = -(-self.total // self.decimation)
         self.z_all = D.empty(n_dec_total, "complex64") if (self.pass_through or self.cfg.dump_iq_path) else None
-        self.audio_all = None if self.pass_through else D.empty(n_dec_total, "float32")
+        self.audio_all = None
+        if self.wfm:  # the (a, b) planes of the stereo matrix
+            torch = D.torch_mod()
+            self.audio_all = torch.empty((2, n_dec_total), dtype=torch.float32, device=D.device())
+        elif not self.pass_through:
+            self.audio_all = D.empty(n_dec_total, "float32")
 
     def before_block(self, done: int, n: int, chunk: int) -> None:
         """Upload what the demodulator needs for the block of ``n`` frames at frame ``done`` ahead of the channelizer."""
@@ -1572,7 +1677,7 @@ class _Target:
             if self.cfg.dump_iq_path:
                 tracker.advance("dump_iq", float(n_out))
         if self.demod is not None and n_out:
-            self.demod.process(z, self._starts, self.audio_all[self.pos_dec : self.pos_dec + n_out])
+            self.demod.process(z, self._starts, self.audio_all[..., self.pos_dec : self.pos_dec + n_out])
         tracker.advance("demod", float(n_out))
         tracker.advance("encode", n_out / max(self.fs_channel, 1e-9) * 48_000.0)
         self.pos_dec += n_out
@@ -1593,6 +1698,20 @@ class _Target:
                 self.output_path.write_bytes(values.tobytes())
             return
         self.demod.decoder.finalize()
+        if self.wfm:
+            planes = self.audio_all[:, : self.pos_dec]
+            pcm, channels = self.demod.finish(planes)
+            iqio.write_wav_pcm16(self.output_path, pcm, 48_000, channels=channels)
+            self.stereo = self.demod.stereo
+            self.owner.wfm_stereo = self.stereo
+            if self.owner.keep_channel_audio:
+                self.owner.wfm_planes = planes
+                self.owner.audio_fs_channel = D.torch_mod().stack(self.demod.channel_audio)  # (channels, n), clipped
+            self.peak = self.demod.peak
+            self.owner.chunk_rms_dbfs = self.demod.chunk_rms_dbfs()
+            LOG.info("Pilot level %.4f: %s output. Audio peak level %.2f dBFS.", self.demod.pilot_level,
+                     "stereo" if self.stereo else "mono", 20.0 * math.log10(max(self.peak, 1e-6)))
+            return
         audio = self.audio_all[: self.pos_dec]
         if self.owner.keep_channel_audio:
             self.owner.audio_fs_channel = audio
@@ -1630,6 +1749,7 @@ class MultiChannelPipeline:
         self.configs = configs
         self.owners = [_owner] if _owner is not None else [ProcessingPipeline(c) for c in configs]
         self._cancelled = False
+        self.wfm_stereo = None  # after run(): per target, the wfm stereo decision (None for the other modes)
 
     def cancel(self) -> None:
         self._cancelled = True
@@ -1698,6 +1818,9 @@ class MultiChannelPipeline:
             n_est = 0.0
             for c, o in zip(self.configs, self.owners):
                 decimation, fs_channel = P.choose_decimation(sample_rate, c.fs_ch_target)
+                if (c.demod_mode or "").lower() == "wfm" and fs_channel < P.WFM_MIN_RATE:
+                    raise ValueError(f"wfm needs a channel rate of at least {P.WFM_MIN_RATE:.0f} Hz; --fs-ch {c.fs_ch_target:.0f} "
+                                     f"gives {fs_channel:.0f} Hz")
                 LOG.info("Input sample rate %.2f Hz; centre %.0f Hz, target %.0f Hz; decimation %d -> %.2f Hz",
                          sample_rate, center_freq, c.target_freq, decimation, fs_channel)
                 n_est += total / max(decimation, 1)
@@ -1832,6 +1955,7 @@ class MultiChannelPipeline:
             tracker.status("flush outputs")
             for t in targets:
                 t.finish()
+            self.wfm_stereo = [t.stereo for t in targets]  # per target: True / False for wfm, None for the other modes
             tracker.status("Processing complete")
             return [ProcessingResult(rate_probe, center_freq, t.target_freq, t.freq_offset, t.decimation, t.fs_channel,
                                      t.mix_sign, t.peak) for t in targets]
