@@ -392,6 +392,50 @@ int iqa_wfm_stereo(int32_t ntaps, const void *taps_dev, float m_scale, const voi
 /* left = a + b, right = a - b (float32[n]; in place allowed). */
 int iqa_wfm_matrix(const void *a_dev, const void *b_dev, int64_t n, void *left_dev, void *right_dev, void *stream);
 
+/* ------------------------------------------------------------------------- *
+ * RDS beside the stereo matrix (--demod wfm --rds)      *
+ * ------------------------------------------------------------------------- */
+
+/* Longest matched filter (2 half_taps + 1 taps) and largest decimation: what a channel rate of IQA_WFM_MAX_TAPS needs. */
+#define IQA_RDS_MAX_HALF 2400
+#define IQA_RDS_MAX_DECIM 80
+/* Discriminator values the caller carries in front of a block: 2 half_taps + 2 (ntaps - 1); 0 for invalid arguments. */
+int64_t iqa_rds_hist_len(int32_t ntaps, int32_t half_taps);
+/* Decimated outputs of a block of n samples whose first has the absolute index pos: the j with pos <= j decim < pos + n. */
+int64_t iqa_rds_outputs(int64_t pos, int64_t n, int32_t decim);
+/* Dynamic LDS of iqa_rds_baseband at these sizes; 0 where its windows do not fit 64 KiB (the call is then IQA_EINVAL). */
+int64_t iqa_rds_lds_bytes(int32_t ntaps, int32_t half_taps, int32_t decim);
+/* One block of the RDS baseband.  theta_dev, m_scale, ntaps (N), D and the carried history are iqa_wfm_stereo's; pos is the
+ * absolute index of theta[0] in the stream, all indices below are absolute.  With md[n] = m[n-D], p = h_p * m, u = p / |p|
+ * (0 where |p| < 1e-12), R = decim, M = half_taps, f = f_mix (57 000 / fs) and the antisymmetric matched filter h_r
+ * (h_r[2M-k] = -h_r[k]), for every j with pos <= jR < pos + n:
+ *   y[j] = (sum_k h_r[k] md[jR-k] exp(-j 2 pi frac(f (jR-k)))) exp(+j 2 pi frac(f jR)) conj(u[jR])^3
+ *   q[j] = rint(angle(u[jR] conj(u[(j-1)R]) exp(-j 2 pi clock_step)) / (2 pi) * 2^44),  q[0] = 0   (clock_step = 19 000 R / fs)
+ * pilot_taps_dev: float32[2(D+1)] = Re h_p[0..D], Im h_p[0..D]; mf_taps_dev: float32[M] = h_r[0..M-1];
+ * hist_dev: float32[iqa_rds_hist_len] in front of theta[0] (NULL: zeros); y_out_dev: complex64[iqa_rds_outputs];
+ * q_out_dev: int64[iqa_rds_outputs].  Every sum runs in one fixed order: outputs do not depend on how a stream is cut. */
+int iqa_rds_baseband(int32_t ntaps, const void *pilot_taps_dev, int32_t half_taps, const void *mf_taps_dev, int32_t decim,
+                     float m_scale, double f_mix, double clock_step, const void *theta_dev, int64_t n, int64_t pos,
+                     const void *hist_dev, void *y_out_dev, void *q_out_dev, void *stream);
+/* phi[i] = *total + q[0] + .. + q[i] (int64, exact), *total = phi[n-1]; psi[i] = ((j_first + i) clock_step + phi[i] 2^-44) / 16
+ * (float64, each operation rounded once).  total_dev: int64[1] on the device, carried from call to call; work_dev:
+ * int64[iqa_rds_clock_chunks(n)] workspace (reduce / apply / carry over chunks of 4096 values). */
+int64_t iqa_rds_clock_chunks(int64_t n);
+int iqa_rds_clock(const void *q_dev, int64_t n, int64_t j_first, double clock_step, void *total_dev, void *work_dev,
+                  void *phi_out_dev, void *psi_out_dev, void *stream);
+/* out[0..2] = Re Z, Im Z, sum |y|^2 over j0 <= j < n with Z = sum |y[j]|^2 exp(-j 2 pi psi[j]) (float64; per tile of 1024
+ * indices, then over the tiles, both in a fixed order).  partials_dev: double[3 iqa_rds_timing_partials(n)] workspace. */
+int64_t iqa_rds_timing_partials(int64_t n);
+int iqa_rds_timing(const void *y_dev, const void *psi_dev, int64_t n, int64_t j0, void *partials_dev, void *out_dev, void *stream);
+/* Symbols and bits.  r = psi - tau; for j0 < j < n with k = floor(r[j]) > floor(r[j-1]):
+ * sym[k - k_first] = y[j-1] + (y[j] - y[j-1]) (k - r[j-1]) / (r[j] - r[j-1]) (complex64; indices outside 0 .. nsym-1 are
+ * dropped; the caller zeroes sym), then bits[i] = Re(sym[i+1] conj(sym[i])) < 0 (uint8[nsym - 1]). */
+int iqa_rds_symbols(const void *y_dev, const void *psi_dev, int64_t n, int64_t j0, double tau, int64_t k_first, int64_t nsym,
+                    void *sym_out_dev, void *bits_out_dev, void *stream);
+/* For every bit offset i <= nbits - 26: words[i] = bits i .. i+25, first bit most significant (uint32), synd[i] =
+ * crc10(words[i] >> 10) xor (words[i] & 0x3FF) with g = x^10 + x^8 + x^7 + x^5 + x^4 + x^3 + 1 (uint16). */
+int iqa_rds_syndromes(const void *bits_dev, int64_t nbits, void *words_out_dev, void *synd_out_dev, void *stream);
+
 /* Audio egress (the drain of AudioWriter, processing.py:433-438, without a host thread): copy nbytes from device
  * memory into MAPPED pinned host memory (hipHostMalloc / torch pin_memory) with `workgroups` small workgroups
  * (<= 0: 8), so that the copy can run beside a kernel that occupies every CU.  Both pointers 16-byte aligned. */

@@ -145,6 +145,18 @@ _SIGNATURES = {
     "iqa_wfm_stereo": (ctypes.c_int, [c_int32, c_void_p, c_float, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
                                       c_void_p, c_void_p]),
     "iqa_wfm_matrix": (ctypes.c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
+    "iqa_rds_hist_len": (c_int64, [c_int32, c_int32]),
+    "iqa_rds_outputs": (c_int64, [c_int64, c_int64, c_int32]),
+    "iqa_rds_lds_bytes": (c_int64, [c_int32, c_int32, c_int32]),
+    "iqa_rds_baseband": (ctypes.c_int, [c_int32, c_void_p, c_int32, c_void_p, c_int32, c_float, c_double, c_double, c_void_p,
+                                        c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "iqa_rds_clock_chunks": (c_int64, [c_int64]),
+    "iqa_rds_clock": (ctypes.c_int, [c_void_p, c_int64, c_int64, c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "iqa_rds_timing_partials": (c_int64, [c_int64]),
+    "iqa_rds_timing": (ctypes.c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p]),
+    "iqa_rds_symbols": (ctypes.c_int, [c_void_p, c_void_p, c_int64, c_int64, c_double, c_int64, c_int64, c_void_p, c_void_p,
+                                       c_void_p]),
+    "iqa_rds_syndromes": (ctypes.c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
     "iqa_squelch_workspace_bytes": (c_int64, [c_int64, c_int32]),
     "iqa_squelch_stage_offset": (c_int64, [c_int64, c_int32, c_int32]),
     "iqa_squelch": (ctypes.c_int, [ctypes.POINTER(SquelchParams), ctypes.POINTER(SquelchSeg), c_int32, c_void_p, c_void_p,

@@ -16,6 +16,7 @@ from __future__ import annotations
 
 import argparse
 import dataclasses
+import json
 import logging
 import math
 import sys
@@ -85,6 +86,8 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--demod", dest="demod", choices=["nfm", "am", "usb", "lsb", "ssb", "wfm", "none"], default="nfm")
     p.add_argument("--deemph", dest="deemph_us", type=positive_float, default=ModeDefault(300.0),
                    help="De-emphasis time constant in microseconds (default 300; 50 for --demod wfm, 75 in the Americas).")
+    p.add_argument("--rds", dest="rds", action="store_true",
+                   help="With --demod wfm: decode RDS (PI, PS, RadioText) of every station and write <output stem>.rds.json.")
     p.add_argument("--no-agc", dest="agc_enabled", action="store_false")
     p.add_argument("--out", dest="output_path", type=Path)
     p.add_argument("--dump-iq", dest="dump_iq", type=Path)
@@ -189,6 +192,8 @@ def main(argv: list[str] | None = None) -> int:
     if args.audio_post_path and not 0.0 <= args.audio_post_percentile <= 1.0:
         parser.error("--audio-post-noise-percentile must be between 0.0 and 1.0.")
     logging.basicConfig(level=logging.DEBUG if args.verbose else logging.INFO, format="%(levelname)s %(message)s")
+    if args.rds and args.demod != "wfm":
+        parser.error("--rds needs --demod wfm.")
     if args.audio_post_path:
         return run_audio_post(args)
     frequencies = list(args.target_freqs or [])
@@ -242,8 +247,9 @@ def main(argv: list[str] | None = None) -> int:
     LOG.info("=== Processing %d target(s) in one pass over %s ===", len(configs), args.input_path)
     try:
         # the reference loops whole pipelines over the targets (cli.py:683-710); here the capture is read once
-        results = MultiChannelPipeline(configs).run(progress_sink=None) if len(configs) > 1 else [
-            ProcessingPipeline(configs[0]).run(progress_sink=None)]
+        runner = MultiChannelPipeline(configs, rds=args.rds) if len(configs) > 1 else ProcessingPipeline(configs[0], rds=args.rds)
+        results = runner.run(progress_sink=None)
+        results = results if len(configs) > 1 else [results]
     except ProcessingCancelled:
         LOG.info("Processing cancelled by user.")
         return 0
@@ -255,6 +261,12 @@ def main(argv: list[str] | None = None) -> int:
     for config, result in zip(configs, results):
         LOG.info("%.0f Hz: decimation %d -> %.2f Hz, mixer sign %+d, audio peak %.4f", config.target_freq,
                  result.decimation, result.fs_channel, result.mix_sign, result.audio_peak)
+    if args.rds and not args.probe_only:
+        stations = runner.rds if len(configs) > 1 else [runner.rds]
+        targets = runner.output_paths if len(configs) > 1 else [runner.output_path]
+        for config, station, wav in zip(configs, stations, targets):
+            print(f"{config.target_freq:.0f} Hz: " + (station.line() if station is not None else "no RDS"))
+            wav.with_name(wav.stem + ".rds.json").write_text(json.dumps(None if station is None else station.to_json(), indent=1) + "\n")
     return 0
 
 

@@ -445,6 +445,74 @@ def plan_wfm(fs_channel: float) -> WfmPlan:
     return WfmPlan(fs, n, delay, h_a, h_p, float(np.float32(fs / (2.0 * math.pi * WFM_DEVIATION))), packed)
 
 
+# ---- RDS plan (--demod wfm --rds) ------------------------------------------
+
+RDS_SUBCARRIER_HZ = 57_000.0  # three times the pilot
+RDS_BIT_RATE = 1_187.5  # the pilot divided by 16
+RDS_SPAN_SYMBOLS = 2  # the matched filter covers +-2 symbols
+RDS_MAX_HALF = 2400  # IQA_RDS_MAX_HALF
+RDS_MAX_DECIM = 80  # IQA_RDS_MAX_DECIM
+RDS_PHASE_BITS = 44  # q = rint(dev / 2 pi * 2^44)
+
+
+@dataclass(frozen=True)
+class RdsPlan:
+    fs: float
+    wfm: WfmPlan  # N, delay and the analytic pilot filter are the stereo matrix's
+    decim: int  # R = round(fs / 19 000)
+    half: int  # M: the matched filter has 2M + 1 taps
+    h_matched: np.ndarray  # float64[2M + 1], antisymmetric about M, sum of squares 1
+    f_mix: float  # 57 000 / fs, cycles per sample
+    clock_step: float  # 19 000 R / fs, pilot cycles per decimated sample
+    j0: int  # first decimated index past every filter's start-up: ceil((2 (N - 1) + 2M) / R)
+    hist_len: int  # discriminator values carried in front of a block: 2M + 2 (N - 1)
+    mf_packed: np.ndarray  # float32[M]: h_r[0 .. M-1] (iqa_rds_baseband)
+    pilot_packed: np.ndarray  # float32[2 (delay + 1)]: Re h_p[0..delay], Im h_p[0..delay]
+
+
+def _rds_s(v: np.ndarray) -> np.ndarray:
+    """s(v) = sin(4 pi v) / (pi v), s(0) = 4."""
+    return 4.0 * np.sinc(4.0 * v)
+
+
+def rds_pulse(x) -> np.ndarray:
+    """h(x) = (s(x + 1/8) + s(x - 1/8)) / 2, x in symbols: the inverse transform of H(f) = cos(pi f td / 4), |f| <= 2 / td."""
+    x = np.asarray(x, dtype=np.float64)
+    return 0.5 * (_rds_s(x + 0.125) + _rds_s(x - 0.125))
+
+
+def rds_symbol(x) -> np.ndarray:
+    """The centred biphase symbol g(x) = h(x + 1/4) - h(x - 1/4) (antisymmetric), x in symbols."""
+    x = np.asarray(x, dtype=np.float64)
+    return rds_pulse(x + 0.25) - rds_pulse(x - 0.25)
+
+
+@functools.lru_cache(maxsize=16)
+def plan_rds(fs_channel: float) -> RdsPlan:
+    """The RDS demodulator's constants and matched filter at channel rate ``fs_channel`` (float64; shared, read-only)."""
+    wfm = plan_wfm(fs_channel)
+    fs = wfm.fs
+    decim = int(round(fs / WFM_PILOT_HZ))
+    spp = fs / RDS_BIT_RATE  # samples per symbol
+    half = int(math.ceil(RDS_SPAN_SYMBOLS * spp))
+    if decim > RDS_MAX_DECIM or half > RDS_MAX_HALF:
+        raise ValueError(f"RDS at a channel rate of {fs:.0f} Hz needs decimation {decim} and {2 * half + 1} taps; at most "
+                         f"{RDS_MAX_DECIM} and {2 * RDS_MAX_HALF + 1} are supported (lower --fs-ch)")
+    k = np.arange(2 * half + 1, dtype=np.float64)
+    h = rds_symbol(-(k - half) / spp)
+    h[half] = 0.0
+    h = 0.5 * (h - h[::-1])  # (antisymmetric to the last bit)
+    h /= math.sqrt(float(np.sum(h * h)))
+    d = wfm.delay
+    pilot = np.concatenate([wfm.h_pilot.real[: d + 1], wfm.h_pilot.imag[: d + 1]]).astype(np.float32)
+    mf = h[:half].astype(np.float32)
+    for arr in (h, pilot, mf):
+        arr.setflags(write=False)
+    j0 = -(-(2 * (wfm.ntaps - 1) + 2 * half) // decim)
+    return RdsPlan(fs, wfm, decim, half, h, RDS_SUBCARRIER_HZ / fs, WFM_PILOT_HZ * decim / fs, j0,
+                   2 * half + 2 * (wfm.ntaps - 1), mf, pilot)
+
+
 # ---- 48 kHz resampler plan (build-defined spec; see DESIGN.md "48 kHz stage") -----------------
 
 RS_ZERO_CROSSINGS = 16

@@ -32,6 +32,7 @@ from . import _native as N
 from . import dsp_plan as P
 from . import iqio
 from .decoders import create_decoder
+from .decoders.rds import RdsCore, result_from as rds_result_from
 from .decoders.wfm import WfmStereoCore, stereo_matrix
 from .dsp_plan import design_channel_filter, tune_chunk_size  # noqa: F401  (re-exported API)
 from .progress import PhaseState, ProgressSink, ProgressTracker
@@ -1282,14 +1283,20 @@ class WfmDemod:
     stereo-difference planes (a, b) into the caller's ``(2, n)`` slice, and the block's per-tile sums of |p|^2 are added to a
     device running sum -- nothing is read back.  ``finish`` reads that sum once, takes the run's stereo decision
     (sqrt(mean |p|^2) >= ``dsp_plan.WFM_STEREO_LEVEL``) and runs the tail on the channels it writes (L, R or a): de-emphasis,
-    the writer's pre-clip peak, +-0.99 clip and per-chunk sums of squares, 48 kHz PCM16."""
+    the writer's pre-clip peak, +-0.99 clip and per-chunk sums of squares, 48 kHz PCM16.
 
-    def __init__(self, fs_channel: float, *, deemph_us: float):
+    ``rds=True``: each block's discriminator output also runs through ``iqa_rds_baseband`` and
+    ``iqa_rds_clock``; ``finish`` decodes the stored run after the stereo decision (``self.rds``: an ``RdsResult``, or
+    ``None`` for a run without a pilot or without an accepted group).  Off, no RDS entry point is called."""
+
+    def __init__(self, fs_channel: float, *, deemph_us: float, rds: bool = False):
         self.decoder = create_decoder("wfm", deemph_us=deemph_us, agc_enabled=False, extensions=True)
         self.decoder.setup(fs_channel)  # (plans the filters; ValueError below the mode's minimum rate)
         self.fs_channel = float(fs_channel)
         self.alpha = self.decoder.deemph["mono"].alpha  # the DeemphasisFilter rule
         self.core = self.decoder.core  # the pipeline's stream: the decoder's own stage API is not used beside it
+        self.rds_core = RdsCore(P.plan_rds(fs_channel)) if rds else None
+        self.rds = None
         self._prev = D.from_numpy(np.array([1 + 0j], dtype=np.complex64))
         self._pilot_sumsq = D.zeros(1, "float64")
         self._starts: list = []  # chunk starts of the run, channel-rate sample index
@@ -1316,6 +1323,8 @@ class WfmDemod:
         self._prepared = None
         N.call("iqa_quadrature", N.ptr(z_dev), c_int64(n), N.ptr(self._prev), N.ptr(theta), N.stream_ptr())
         self.core.process(theta, out_dev[0], out_dev[1], partials=partials)
+        if self.rds_core is not None:
+            self.rds_core.process(theta)
         self._pilot_sumsq += partials[: WfmStereoCore.partials_for(n)].sum()
         self._starts.append(np.asarray(chunk_starts, dtype=np.int64) + self.n)
         self.n += n
@@ -1348,6 +1357,9 @@ class WfmDemod:
         pcm = torch.stack(pcm, dim=1) if len(pcm) == 2 else pcm[0]  # interleaved L, R
         self._sumsq, self._counts = sumsq, np.diff(np.append(starts, n)) * len(chans)
         self._peak = float(peak.item())
+        if self.rds_core is not None and self.stereo:  # (a pilot to lock to)
+            res = rds_result_from(self.rds_core.finish())
+            self.rds = res if res.groups else None
         return pcm.cpu().numpy(), len(chans)
 
     @property
@@ -1528,8 +1540,10 @@ class ProcessingPipeline:
     #: frames per device block (rounded down to whole chunks); 64 Mi frames = 256 MiB of int16 I/Q
     block_frames_target = 64 * 1024 * 1024
 
-    def __init__(self, config: ProcessingConfig):
+    def __init__(self, config: ProcessingConfig, *, rds: bool = False):
         self.config = config
+        if rds and (config.demod_mode or "").lower() != "wfm":
+            raise ValueError("rds=True needs a wfm target: RDS rides on a broadcast FM multiplex (--demod wfm)")
         self._cancelled = False
         self._resolved_chunk_size: int | None = None
         self.chunk_rms_dbfs: list[float] = []
@@ -1540,6 +1554,8 @@ class ProcessingPipeline:
         self.channelizer_precision = None  # "fast" / "fine" / "full" / "float32": what the run's channelizer was planned at
         self.wfm_stereo = None  # --demod wfm: whether the run's output is stereo (the pilot test, once per run)
         self.wfm_planes = None  # --demod wfm with keep_channel_audio: the stereo matrix's (a, b) planes, shape (2, n)
+        self.rds_enabled = bool(rds)  # --rds: decode RDS beside wfm
+        self.rds = None  # after run(): the station's RdsResult (None without a pilot, without groups, or with rds off)
 
     def cancel(self) -> None:
         self._cancelled = True
@@ -1567,7 +1583,7 @@ class ProcessingPipeline:
 
     def run(self, progress_sink: ProgressSink | None = None) -> ProcessingResult:
         """One target frequency: a :class:`MultiChannelPipeline` with a single channel."""
-        multi = MultiChannelPipeline([self.config], _owner=self)
+        multi = MultiChannelPipeline([self.config], _owner=self, rds=self.rds_enabled)
         self._multi = multi
         if self._cancelled:
             multi.cancel()
@@ -1592,10 +1608,11 @@ class _Target:
         if self.pass_through:
             self.demod = None
         elif self.wfm:
-            self.demod = WfmDemod(fs_channel, deemph_us=cfg.deemph_us)
+            self.demod = WfmDemod(fs_channel, deemph_us=cfg.deemph_us, rds=bool(getattr(owner, "rds_enabled", False)))
         else:
             self.demod = ChannelDemod(cfg.demod_mode, fs_channel, deemph_us=cfg.deemph_us, agc_enabled=cfg.agc_enabled)
         self.stereo = None  # wfm: the run's stereo decision (finish)
+        self.rds = None  # wfm with rds: the station's RdsResult (finish)
         if cfg.iq_order not in N.ORDER:
             raise ValueError(f"Unsupported iq_order '{cfg.iq_order}'")
         self.chan = None
@@ -1704,6 +1721,9 @@ class _Target:
             iqio.write_wav_pcm16(self.output_path, pcm, 48_000, channels=channels)
             self.stereo = self.demod.stereo
             self.owner.wfm_stereo = self.stereo
+            self.rds = self.owner.rds = self.demod.rds
+            if self.rds is not None:
+                LOG.info("RDS %s", self.rds.line())
             if self.owner.keep_channel_audio:
                 self.owner.wfm_planes = planes
                 self.owner.audio_fs_channel = D.torch_mod().stack(self.demod.channel_audio)  # (channels, n), clipped
@@ -1734,7 +1754,7 @@ class MultiChannelPipeline:
     ``configs`` must agree on the input file and its interpretation.
     """
 
-    def __init__(self, configs: list, _owner=None):
+    def __init__(self, configs: list, _owner=None, *, rds: bool = False):
         if not configs:
             raise ValueError("at least one ProcessingConfig is required")
         if len(configs) > 5 and _owner is None:
@@ -1747,9 +1767,12 @@ class MultiChannelPipeline:
             if not same:
                 raise ValueError("all targets of a multi-channel run must share the input file, format, rate and chunking")
         self.configs = configs
-        self.owners = [_owner] if _owner is not None else [ProcessingPipeline(c) for c in configs]
+        if rds and any((c.demod_mode or "").lower() != "wfm" for c in configs):
+            raise ValueError("rds=True needs wfm targets: RDS rides on a broadcast FM multiplex (--demod wfm)")
+        self.owners = [_owner] if _owner is not None else [ProcessingPipeline(c, rds=rds) for c in configs]
         self._cancelled = False
         self.wfm_stereo = None  # after run(): per target, the wfm stereo decision (None for the other modes)
+        self.rds = None  # after run(): per target, the RdsResult (None for non-wfm or pilot-less targets, or with rds off)
 
     def cancel(self) -> None:
         self._cancelled = True
@@ -1956,6 +1979,10 @@ class MultiChannelPipeline:
             for t in targets:
                 t.finish()
             self.wfm_stereo = [t.stereo for t in targets]  # per target: True / False for wfm, None for the other modes
+            self.rds = [t.rds for t in targets]
+            self.output_paths = [t.output_path for t in targets]  # where each target's audio went
+            for t in targets:
+                t.owner.output_path = t.output_path
             tracker.status("Processing complete")
             return [ProcessingResult(rate_probe, center_freq, t.target_freq, t.freq_offset, t.decimation, t.fs_channel,
                                      t.mix_sign, t.peak) for t in targets]
