@@ -634,6 +634,37 @@ def test_launch_geometry(A, case):
         assert ph[i_wrap] == 3 and ph[i_wrap - 1] > 2**64 - 2 * step
 
 
+@pytest.mark.parametrize("d,acc64", [(104, False), (104, True), (75, False)], ids=["contiguous-int32", "contiguous-int64", "rows-int32"])
+def test_single_channel_ring_entry_equals_one_lane_launch(A, d, acc64):
+    """The ring branch of iqa_channelize_mfma (reserved = 64 | 128: int32 sums, 64: 64-bit sums) is a one-lane launch of
+    iqa_channelize_mfma_multi: the package's own driver calls only the latter, callers of the C ABI may use either.  The
+    same rotated, conjugated, scaled lane through both entries: z byte for byte the same (and the model's)."""
+    import torch
+
+    N, P = _N(), _P()
+    ks = -(-2 * d // 32)
+    mode = X.ring_mode("s16", d, 0, ks, acc64)
+    assert mode == (1 if d % 4 == 0 else 2)
+    L = 64 * d - 13
+    mp = make_plan(L, d, "s16", not acc64, seed=d + 1)
+    step, base = _rot(np.random.default_rng(d))
+    opb, n_out, m_first = 256, 256 * 5 + 37, 64 + 500
+    raw, x, n_frames, consumed = setup_capture("s16", d, mode, 0, ks, 0, 0, m_first, n_out, opb, seed=d + 2)
+    ln = Lane(mp, 0, rotate=1, conj=1, scale=1j, rot_step=step, rot_base=base)
+    launch("multi", "s16", d, 0, ks, opb, [ln], x, n_frames, consumed, m_first, n_out)
+    check_lane(ln, 0, raw, d, consumed, m_first, n_out, f"one lane, d={d}, acc64={acc64}")
+    ps = ln.pass_of(0)
+    chan = N.ChanParams(fmt=P.FMT_CODE["s16"], ntaps=L, decimation=d, conj_sum=1, rotate=1, reserved=0, rot_step=ln.rot_step,
+                        rot_base=ln.rot_base, out_scale_re=0.0, out_scale_im=1.0)
+    prm = N.MfmaParams(outputs_per_block=opb, reserved=64 | (0 if acc64 else 128), unit=M.lane_unit(mp, 0, "s16"), c_re=ps.c_re,
+                       c_im=ps.c_im, debug_stamps=None, q_group=0, k_first=0, k_count=ks, finalize=1, partial_in_dev=None,
+                       partial_out_dev=None)
+    z = torch.full((n_out,), complex(np.nan, np.nan), dtype=torch.complex64, device="cuda")
+    N.call("iqa_channelize_mfma", byref(chan), byref(prm), N.ptr(device_afrag(mp)[0]), N.ptr(x), c_int64(n_frames),
+           c_int64(consumed), c_int64(m_first), c_int64(n_out), N.ptr(z), N.stream_ptr())
+    assert torch.equal(torch.view_as_real(z).view(torch.int32), torch.view_as_real(ln.out).view(torch.int32))
+
+
 SINGLE_ROW = [("s16", 104, 104), ("s16", 104, 37), ("s16", 521, 521), ("s16", 521, 300), ("u8", 25, 25), ("u8", 521, 200)]
 
 
