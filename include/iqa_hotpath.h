@@ -436,6 +436,44 @@ int iqa_rds_symbols(const void *y_dev, const void *psi_dev, int64_t n, int64_t j
  * crc10(words[i] >> 10) xor (words[i] & 0x3FF) with g = x^10 + x^8 + x^7 + x^5 + x^4 + x^3 + 1 (uint16). */
 int iqa_rds_syndromes(const void *bits_dev, int64_t nbits, void *words_out_dev, void *synd_out_dev, void *stream);
 
+/* ------------------------------------------------------------------------- *
+ * POCSAG beside the NFM demodulator (--demod nfm --pocsag) *
+ * ------------------------------------------------------------------------- */
+
+/* Most samples per bit (and so the longest bit integrator): the sync kernel stages tile + rint(31 sps) + 1 integrator
+ * values in LDS (1024 + 11 905 int32 = 50.5 KiB at the limit).  A baud rate needs 8 <= fs / baud <= this. */
+#define IQA_POCSAG_MAX_SPS 384
+#define IQA_POCSAG_BAUDS 3
+/* Bit instants of one batch: offsets[i] = rint(i sps), i = 0 .. 544 (32 sync bits, 16 x 32 codeword bits, the next sync). */
+#define IQA_POCSAG_OFFSETS 545
+/* One block of the quantiser and the bit integrators.  t[n] = rint(theta[n] 2^20) (int32, half-even); for each baud b with
+ * window[b] = L > 0: S_b[n] = t[n] + t[n-1] + .. + t[n-L+1] (int32), t in front of the block taken from hist_dev.
+ * theta_dev: float32[n] (iqa_quadrature's output); hist_dev: int32[hist_len], the hist_len = max L - 1 values of t in front
+ * of theta[0], oldest first (NULL: zeros); t_out_dev: int32[n]; s_out_dev[b]: int32[n], or NULL where window[b] = 0.
+ * Integer sums: the outputs do not depend on how a stream is cut into blocks. */
+int iqa_pocsag_integrate(const void *theta_dev, int64_t n, const void *hist_dev, int32_t hist_len,
+                         const int32_t window[IQA_POCSAG_BAUDS], void *t_out_dev, void *const s_out_dev[IQA_POCSAG_BAUDS],
+                         void *stream);
+/* Sync search of one baud over a whole run.  s_dev: int32[n] (S_b); offsets: HOST int32[32], offsets[i] = rint(i sps),
+ * ascending, offsets[0] = 0, offsets[31] <= 31 IQA_POCSAG_MAX_SPS.  For every m with m + offsets[31] < n:
+ *   v_i = S[m + offsets[i]], Sigma = sum v_i, x_i = 32 v_i - Sigma, w_i = (x_i < 0), W = w_0 .. w_31 (w_0 most significant),
+ *   d+ = popcount(W xor 0x7CD215D8), d- = 32 - d+, E = sum |x_i|; m is a candidate iff min(d+, d-) <= 2 and
+ *   128 min |x_i| >= E; score[m] = 2 E + (d- < d+) for a candidate, 0 otherwise (and 0 where m is not evaluated).
+ * A candidate is kept iff no candidate m' with |m' - m| <= half_bit has E' > E, or E' = E and m' < m.  Kept syncs are
+ * appended in any order to list_dev: int64[4 capacity] = (m, Sigma, inverted, distance) each; *count_dev (int64, zeroed
+ * by the call) counts ALL kept syncs: a count above capacity means the list is incomplete and the call must be repeated
+ * with a larger one.  score_dev: int64[n] workspace. */
+int iqa_pocsag_sync(const void *s_dev, int64_t n, const int32_t offsets[32], int32_t half_bit, void *score_dev,
+                    void *list_dev, int64_t capacity, void *count_dev, void *stream);
+/* The 16 codewords behind every kept sync.  list_dev as above (nsync entries); offsets_dev: DEVICE int32[545].  For sync
+ * (m, Sigma, inverted), codeword c = 0 .. 15, bit b = 0 .. 31 (first bit most significant): instant m + offsets[32 (1 + c) + b],
+ * bit = (32 S[instant] < Sigma) xor inverted.  status 3 (absent: raw = fixed = 0) where the last instant is >= n; else with
+ * the syndrome of the upper 31 bits modulo x^10 + x^9 + x^8 + x^6 + x^5 + x^3 + 1 and the parity P of all 32 bits:
+ * 0 = syndrome 0, P even; 1 = P odd and the syndrome is 0 (parity bit flipped) or that of one of the 31 positions (that bit
+ * flipped); 2 = anything else (fixed = raw).  raw_out_dev, fixed_out_dev: uint32[16 nsync]; status_out_dev: uint8[16 nsync]. */
+int iqa_pocsag_codewords(const void *s_dev, int64_t n, const void *list_dev, int64_t nsync, const void *offsets_dev,
+                         void *fixed_out_dev, void *raw_out_dev, void *status_out_dev, void *stream);
+
 /* Audio egress (the drain of AudioWriter, processing.py:433-438, without a host thread): copy nbytes from device
  * memory into MAPPED pinned host memory (hipHostMalloc / torch pin_memory) with `workgroups` small workgroups
  * (<= 0: 8), so that the copy can run beside a kernel that occupies every CU.  Both pointers 16-byte aligned. */

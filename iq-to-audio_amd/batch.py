@@ -26,6 +26,14 @@ def reject_wfm(modes) -> None:
                          "use ProcessingPipeline / MultiChannelPipeline")
 
 
+def reject_pocsag(pocsag) -> None:
+    """POCSAG decoding stores a run's bit integrators and searches them at the end: the resident
+    runners keep no per-run store, so ``pocsag=True`` is a ``ValueError`` up front, as a wfm target is."""
+    if pocsag:
+        raise ValueError("pocsag=True is not supported by the resident batch runners or sharded runs: "
+                         "use ProcessingPipeline / MultiChannelPipeline")
+
+
 def _rank(precision: str) -> int:
     return _ChannelKernel.PRECISIONS.index(precision)
 
@@ -65,7 +73,7 @@ class ResidentCaptureRunner:
     def __init__(self, taps: np.ndarray, *, sample_rate: float, freq_offset: float, decimation: int, fs_channel: float,
                  chunk: int, n_frames: int, demod_mode: str = "nfm", deemph_us: float = 300.0, agc_enabled: bool = True,
                  fmt: str = "s16", iq_order: str = "iq", mix_sign_override: int | None = None, precision: str | None = None,
-                 precision_guard: float | None = None, slots: int | None = None, graph_streams: int = 1):
+                 precision_guard: float | None = None, slots: int | None = None, graph_streams: int = 1, pocsag: bool = False):
         """``precision``: the channelizer precision every capture starts at (default: by demodulator,
         ``processing.base_precision``); ``precision_guard``: see ``processing.PRECISION_GUARD`` (0 = off).
         ``slots``: captures in flight (output buffers; default 2).  ``submit`` of capture i first waits for capture
@@ -78,6 +86,7 @@ class ResidentCaptureRunner:
         another.  Only for captures that are complete in device memory when ``submit_captured`` is called (the replay is not
         ordered behind the caller's stream)."""
         reject_wfm([demod_mode])
+        reject_pocsag(pocsag)
         torch = D.torch_mod()
         if slots is not None:
             if slots < 2:
@@ -450,10 +459,12 @@ class ResidentBankRunner:
                # third slot lets the host queue capture i + 2 without waiting for them
 
     def __init__(self, targets: list, *, sample_rate: float, n_frames: int, chunk_size: int = 1_048_576,
-                 fs_ch_target: float = 96_000.0, fmt: str = "s16", iq_order: str = "iq", precision_guard: float | None = None):
+                 fs_ch_target: float = 96_000.0, fmt: str = "s16", iq_order: str = "iq", precision_guard: float | None = None,
+                 pocsag: bool = False):
         """``targets``: dicts with ``freq_offset``, and optionally ``bandwidth`` (12 500), ``demod_mode`` ("nfm"),
         ``deemph_us`` (300), ``agc_enabled`` (True), ``mix_sign`` (None = probe), ``precision`` (None = by demodulator)."""
         reject_wfm([t.get("demod_mode") for t in targets])
+        reject_pocsag(pocsag)
         torch = D.torch_mod()
         if not targets:
             raise ValueError("at least one target is required")
@@ -617,7 +628,7 @@ class ResidentBankRunner:
 
 
 def demodulate_sharded(targets: list, *, sample_rate: float, n_frames: int, axis: str, capture=None, captures=None,
-                       chunk_size: int = 1_048_576, fmt: str = "s16", iq_order: str = "iq"):
+                       chunk_size: int = 1_048_576, fmt: str = "s16", iq_order: str = "iq", pocsag: bool = False):
     """The N-GPU form of :class:`ResidentBankRunner` (one process per GPU under ``torch.distributed.run``; SURVEY.md
     section 8(e)), on either axis:
 
@@ -634,6 +645,7 @@ def demodulate_sharded(targets: list, *, sample_rate: float, n_frames: int, axis
     from . import dist as DS
 
     reject_wfm([t.get("demod_mode") for t in targets])
+    reject_pocsag(pocsag)
     torch = D.torch_mod()
     if axis not in ("channels", "captures"):
         raise ValueError("axis must be 'channels' or 'captures'")

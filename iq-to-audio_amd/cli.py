@@ -88,6 +88,9 @@ def build_parser() -> argparse.ArgumentParser:
                    help="De-emphasis time constant in microseconds (default 300; 50 for --demod wfm, 75 in the Americas).")
     p.add_argument("--rds", dest="rds", action="store_true",
                    help="With --demod wfm: decode RDS (PI, PS, RadioText) of every station and write <output stem>.rds.json.")
+    p.add_argument("--pocsag", dest="pocsag", action="store_true",
+                   help="With --demod nfm: decode POCSAG pager traffic (512 / 1200 / 2400 baud) of every target, print one line "
+                        "per message and write <output stem>.pocsag.json.")
     p.add_argument("--no-agc", dest="agc_enabled", action="store_false")
     p.add_argument("--out", dest="output_path", type=Path)
     p.add_argument("--dump-iq", dest="dump_iq", type=Path)
@@ -194,6 +197,8 @@ def main(argv: list[str] | None = None) -> int:
     logging.basicConfig(level=logging.DEBUG if args.verbose else logging.INFO, format="%(levelname)s %(message)s")
     if args.rds and args.demod != "wfm":
         parser.error("--rds needs --demod wfm.")
+    if args.pocsag and args.demod != "nfm":
+        parser.error("--pocsag needs --demod nfm.")
     if args.audio_post_path:
         return run_audio_post(args)
     frequencies = list(args.target_freqs or [])
@@ -247,7 +252,8 @@ def main(argv: list[str] | None = None) -> int:
     LOG.info("=== Processing %d target(s) in one pass over %s ===", len(configs), args.input_path)
     try:
         # the reference loops whole pipelines over the targets (cli.py:683-710); here the capture is read once
-        runner = MultiChannelPipeline(configs, rds=args.rds) if len(configs) > 1 else ProcessingPipeline(configs[0], rds=args.rds)
+        extras = dict(rds=args.rds, pocsag=args.pocsag)
+        runner = MultiChannelPipeline(configs, **extras) if len(configs) > 1 else ProcessingPipeline(configs[0], **extras)
         results = runner.run(progress_sink=None)
         results = results if len(configs) > 1 else [results]
     except ProcessingCancelled:
@@ -267,6 +273,13 @@ def main(argv: list[str] | None = None) -> int:
         for config, station, wav in zip(configs, stations, targets):
             print(f"{config.target_freq:.0f} Hz: " + (station.line() if station is not None else "no RDS"))
             wav.with_name(wav.stem + ".rds.json").write_text(json.dumps(None if station is None else station.to_json(), indent=1) + "\n")
+    if args.pocsag and not args.probe_only:
+        decoded = runner.pocsag if len(configs) > 1 else [runner.pocsag]
+        targets = runner.output_paths if len(configs) > 1 else [runner.output_path]
+        for config, res, wav in zip(configs, decoded, targets):
+            for msg in (res.messages if res is not None else []):
+                print(f"{config.target_freq:.0f} Hz: {msg.line()}")
+            wav.with_name(wav.stem + ".pocsag.json").write_text(json.dumps(None if res is None else res.to_json(), indent=1) + "\n")
     return 0
 
 

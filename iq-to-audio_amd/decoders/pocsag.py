@@ -1,0 +1,276 @@
+"""POCSAG paging beside narrowband FM: 512, 1200 and 2400 baud, all searched at once.
+
+Per block ``iqa_pocsag_integrate`` quantises the discriminator output and appends the bit integrators of the three baud
+rates to the run's stored planes; once per run ``iqa_pocsag_sync`` evaluates the sync correlator at every sample and baud
+and keeps the local maxima, and ``iqa_pocsag_codewords`` reads, checks and corrects the 16 codewords behind every kept
+sync.  Every batch carries its own sync word, so timing is re-acquired per batch by search: there is no loop.  Message
+assembly is integer host logic on the codewords and runs on plain numpy arrays as well (``parse_batches``)."""
+from __future__ import annotations
+
+from ctypes import c_int32, c_int64, c_void_p
+from dataclasses import asdict, dataclass, field
+
+import numpy as np
+
+from .. import _dev as D
+from .. import _native as N
+from .. import dsp_plan as P
+
+SYNC_WORD = 0x7CD215D8
+IDLE_WORD = 0x7A89C197
+BCH_POLY = 0x769  # x^10 + x^9 + x^8 + x^6 + x^5 + x^3 + 1
+NUMERIC = "0123456789*U -]["
+FUNCTION_KIND = ("numeric", "alpha", "alpha", "alpha")  # by function code 0 .. 3
+STATUS = ("ok", "corrected", "uncorrectable", "absent")
+
+
+@dataclass
+class PocsagMessage:
+    time_s: float  # of the address codeword's first bit instant
+    baud: int
+    inverted: bool
+    address: int
+    function: int
+    kind: str  # "numeric" for function 0, else "alpha"
+    text: str
+    payload_bits: int
+    corrected: int  # codewords of the message (address included) with status 1
+    batches: int  # batches the message touches
+    payload: str = ""  # the raw payload bits, first transmitted bit first, as hex (zero-padded to whole digits)
+
+    def line(self) -> str:
+        return f'POCSAG{self.baud} addr={self.address} func={self.function} {self.kind} "{self.text}"'
+
+
+@dataclass
+class PocsagResult:
+    messages: list = field(default_factory=list)  # PocsagMessage, in order of time
+    syncs: dict = field(default_factory=dict)  # baud -> kept syncs
+    codewords: dict = field(default_factory=dict)  # status name -> count
+    bauds_skipped: list = field(default_factory=list)
+    dc_hz: float | None = None  # median tuning error seen by the sync words
+    orphans: int = 0  # message codewords without an open message
+
+    def to_json(self) -> dict:
+        out = asdict(self)
+        out["syncs"] = {str(k): v for k, v in self.syncs.items()}
+        return out
+
+
+def _numeric(bits: list) -> str:
+    out = []
+    for i in range(0, len(bits) - 3, 4):
+        b = bits[i : i + 4]
+        out.append(NUMERIC[b[0] | (b[1] << 1) | (b[2] << 2) | (b[3] << 3)])  # each group LSB first
+    return "".join(out)
+
+
+def _alpha(bits: list) -> str:
+    codes = []
+    for i in range(0, len(bits) - 6, 7):
+        codes.append(sum(bit << k for k, bit in enumerate(bits[i : i + 7])))
+    while codes and codes[-1] in (0x00, 0x03, 0x04):  # NUL, ETX, EOT
+        codes.pop()
+    return "".join(chr(c) if 0x20 <= c <= 0x7E else "�" for c in codes)
+
+
+def parse_batches(plan: P.PocsagPlan, batches: dict) -> PocsagResult | None:
+    """``batches``: baud -> dict(n0=int64[k], sigma=int64[k], inverted=[k], words=uint32[k, 16], status=uint8[k, 16]) in
+    any order -> the run's messages.  Integer logic only; ``None`` when no baud has a kept sync."""
+    res = PocsagResult(bauds_skipped=list(plan.skipped), codewords={s: 0 for s in STATUS})
+    dcs = []
+    for pb in plan.bauds:
+        got = batches.get(pb.baud)
+        n0 = np.zeros(0, dtype=np.int64) if got is None else np.asarray(got["n0"], dtype=np.int64).reshape(-1)
+        res.syncs[pb.baud] = int(n0.size)
+        if not n0.size:
+            continue
+        order = np.argsort(n0, kind="stable")
+        n0 = n0[order]
+        sigma = np.asarray(got["sigma"], dtype=np.int64).reshape(-1)[order]
+        inverted = np.asarray(got["inverted"]).reshape(-1)[order]
+        words = np.asarray(got["words"]).astype(np.int64).reshape(-1, 16)[order]
+        status = np.asarray(got["status"]).astype(np.int64).reshape(-1, 16)[order]
+        for s in sigma.tolist():
+            dcs.append(s * plan.fs / (32.0 * pb.L * 2.0 ** P.POCSAG_THETA_BITS * 2.0 * np.pi))
+        span = int(pb.offsets[P.POCSAG_BATCH_BITS])
+        msg = None  # the open message
+        bits: list = []
+
+        def close():
+            nonlocal msg, bits
+            if msg is not None:
+                msg.payload_bits = len(bits)
+                msg.text = _numeric(bits) if msg.function == 0 else _alpha(bits)
+                pad = bits + [0] * (-len(bits) % 4)
+                msg.payload = "".join(f"{pad[i] << 3 | pad[i + 1] << 2 | pad[i + 2] << 1 | pad[i + 3]:x}" for i in range(0, len(pad), 4))
+                res.messages.append(msg)
+            msg, bits = None, []
+
+        for k in range(n0.size):
+            if k and abs(int(n0[k]) - (int(n0[k - 1]) + span)) > pb.h:
+                close()  # a missing continuation
+            if msg is not None:
+                msg.batches += 1
+            for c in range(16):
+                st, cw = int(status[k, c]), int(words[k, c])
+                res.codewords[STATUS[st]] += 1
+                if st >= 2 or cw == IDLE_WORD:
+                    close()
+                elif cw >> 31 == 0:
+                    close()
+                    fn = (cw >> 11) & 3
+                    msg = PocsagMessage(time_s=(int(n0[k]) + int(pb.offsets[32 * (1 + c)])) / plan.fs, baud=pb.baud,
+                                        inverted=bool(inverted[k]), address=((cw >> 13) & 0x3FFFF) << 3 | (c >> 1), function=fn,
+                                        kind=FUNCTION_KIND[fn], text="", payload_bits=0, corrected=int(st == 1), batches=1)
+                elif msg is None:
+                    res.orphans += 1
+                else:
+                    msg.corrected += int(st == 1)
+                    bits.extend((cw >> s) & 1 for s in range(30, 10, -1))
+        close()
+    if not dcs:
+        return None
+    res.messages.sort(key=lambda m: (m.time_s, m.baud))
+    res.dc_hz = float(np.median(np.asarray(dcs, dtype=np.float64)))
+    return res
+
+
+class PocsagCore:
+    """Per-stream device state: the carried quantised history, the absolute position, and the growing store of the
+    integrator planes (one device tensor per block and baud, joined by ``finish``).  ``keep_t`` also stores t."""
+
+    def __init__(self, plan: P.PocsagPlan, *, keep_t: bool = False):
+        self.plan = plan
+        self.hist_len = plan.hist_len
+        self._windows = (c_int32 * 3)(*plan.lengths())
+        self._active = [i for i, L in enumerate(plan.lengths()) if L]  # slots of P.POCSAG_BAUDS that run
+        self._offsets_dev = {pb.baud: D.from_numpy(np.ascontiguousarray(pb.offsets)) for pb in plan.bauds}
+        self._hist = None  # device int32[hist_len]; None = zeros
+        self.pos = 0  # absolute index of the next block's first sample
+        self.keep_t = keep_t
+        self._t: list = []
+        self._s: list = []  # per block: one int32 tensor per active baud
+
+    def process(self, theta) -> None:
+        """One block of the discriminator output (device float32[n], radians per sample)."""
+        n = int(theta.numel())
+        if n == 0:
+            return
+        t = D.empty(n, "int32")
+        planes = [D.empty(n, "int32") for _ in self._active]
+        outs = (c_void_p * 3)()
+        for slot, plane in zip(self._active, planes):
+            outs[slot] = plane.data_ptr()
+        N.call("iqa_pocsag_integrate", N.ptr(theta), c_int64(n), N.ptr(self._hist), c_int32(self.hist_len), self._windows, N.ptr(t),
+               outs, N.stream_ptr())
+        self._s.append(planes)
+        if self.keep_t:
+            self._t.append(t)
+        h = self.hist_len
+        if n >= h:
+            self._hist = t[n - h :].clone() if h else None
+        else:
+            prev = self._hist if self._hist is not None else D.zeros(h, "int32")
+            self._hist = D.torch_mod().cat([prev[n:], t])
+        self.pos += n
+
+    def joined(self) -> dict:
+        torch = D.torch_mod()
+        if len(self._s) > 1:
+            self._s = [[torch.cat(col) for col in zip(*self._s)]]
+            self._t = [torch.cat(self._t)] if self._t else []
+        planes = self._s[0] if self._s else [D.empty(0, "int32") for _ in self._active]
+        return dict(t=self._t[0] if self._t else None, S={pb.baud: s for pb, s in zip(self.plan.bauds, planes)})
+
+    def reset(self) -> None:
+        """Back to a stream that has seen nothing: no history, position 0, no stored planes."""
+        self._hist, self.pos, self._t, self._s = None, 0, [], []
+
+    def _search(self, pb, s, score, capacity: int, count):
+        lst = D.empty(4 * capacity, "int64")
+        offs = (c_int32 * 32)(*[int(v) for v in pb.offsets[:32]])
+        N.call("iqa_pocsag_sync", N.ptr(s), c_int64(int(s.numel())), offs, c_int32(pb.h), N.ptr(score), N.ptr(lst), c_int64(capacity),
+               N.ptr(count), N.stream_ptr())
+        return lst
+
+    def finish(self) -> dict:
+        """The sync search and the codewords of the stored run: baud -> dict(n0, sigma, inverted, distance, words, raw,
+        status) as numpy arrays sorted by n0.  The searches of all bauds are queued before the one read-back of their
+        counts; the codeword kernel reads the device list as the search left it, and the rows are sorted on the host."""
+        st = self.joined()
+        bauds = self.plan.bauds
+        counts = D.zeros(len(bauds), "int64")
+        score = D.empty(max(max(int(st["S"][pb.baud].numel()) for pb in bauds), 1), "int64")  # (shared: stream order)
+        capacity = 1024
+        lists = [self._search(pb, st["S"][pb.baud], score, capacity, counts[i : i + 1]) for i, pb in enumerate(bauds)]
+        kept = [int(v) for v in counts.cpu().numpy()]
+        for i, pb in enumerate(bauds):
+            if kept[i] > capacity:  # the list is incomplete: search again with room for all, never a truncated list
+                lists[i] = self._search(pb, st["S"][pb.baud], score, kept[i], counts[i : i + 1])
+                assert int(counts[i].item()) == kept[i]
+        words_dev = []
+        for i, pb in enumerate(bauds):
+            k, s = kept[i], st["S"][pb.baud]
+            both, status = D.empty(32 * k, "int32"), D.empty(16 * k, "uint8")  # [corrected | raw]
+            if k:
+                N.call("iqa_pocsag_codewords", N.ptr(s), c_int64(int(s.numel())), N.ptr(lists[i]), c_int64(k),
+                       N.ptr(self._offsets_dev[pb.baud]), N.ptr(both), N.ptr(both[16 * k :]), N.ptr(status), N.stream_ptr())
+            words_dev.append((both, status))
+        out = {}
+        for i, pb in enumerate(bauds):
+            k = kept[i]
+            entries = lists[i][: 4 * k].cpu().numpy().reshape(-1, 4)
+            order = np.argsort(entries[:, 0], kind="stable")
+            entries = entries[order]
+            both = words_dev[i][0].cpu().numpy().view(np.uint32).reshape(2, k, 16)
+            status = words_dev[i][1].cpu().numpy().reshape(k, 16)
+            out[pb.baud] = dict(n0=entries[:, 0].copy(), sigma=entries[:, 1].copy(), inverted=entries[:, 2].astype(bool),
+                                distance=entries[:, 3].astype(np.int32), words=both[0][order], raw=both[1][order], status=status[order])
+        return out
+
+
+class PocsagDecoder:
+    """The stage API: ``process(block)`` per block of the channel (complex: the channelizer's output, run through
+    ``iqa_quadrature`` with this decoder's own ``prev``; or float32: a discriminator output in radians per sample),
+    ``finish()`` once (a ``PocsagResult``, or ``None`` without a kept sync), ``stages()`` for the tests."""
+
+    def __init__(self, rate: float, *, keep_t: bool = True):
+        self.plan = P.plan_pocsag(float(rate))
+        self.core = PocsagCore(self.plan, keep_t=keep_t)
+        self._prev = D.from_numpy(np.array([1 + 0j], dtype=np.complex64))
+        self.theta: list = []  # with keep_t: the discriminator output of every block (device)
+        self._fin = None
+
+    def process(self, block) -> None:
+        torch = D.torch_mod()
+        is_complex = torch.is_complex(block) if D.is_tensor(block) else np.iscomplexobj(block)
+        if is_complex:
+            z = D.to_device(block, "complex64")
+            theta = D.empty(int(z.numel()), "float32")
+            if z.numel():
+                N.call("iqa_quadrature", N.ptr(z), c_int64(int(z.numel())), N.ptr(self._prev), N.ptr(theta), N.stream_ptr())
+        else:
+            theta = D.to_device(block, "float32")
+        if self.core.keep_t:
+            self.theta.append(theta)
+        self.core.process(theta)
+        self._fin = None
+
+    def _finished(self) -> dict:
+        if self._fin is None:
+            self._fin = self.core.finish()
+        return self._fin
+
+    def finish(self) -> PocsagResult | None:
+        return parse_batches(self.plan, self._finished())
+
+    def stages(self) -> dict:
+        """Host copies: ``theta`` and ``t`` (with keep_t), ``S`` (baud -> int32[n]) and ``batches`` (baud -> kept syncs
+        sorted by n0 with their corrected words, raw words and status)."""
+        fin = self._finished()
+        st = self.core.joined()
+        torch = D.torch_mod()
+        return dict(theta=torch.cat(self.theta).cpu().numpy() if self.theta else None,
+                    t=None if st["t"] is None else st["t"].cpu().numpy(),
+                    S={b: s.cpu().numpy() for b, s in st["S"].items()}, batches=fin)

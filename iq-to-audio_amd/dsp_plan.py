@@ -513,6 +513,58 @@ def plan_rds(fs_channel: float) -> RdsPlan:
                    2 * half + 2 * (wfm.ntaps - 1), mf, pilot)
 
 
+# ---- POCSAG plan (--demod nfm --pocsag) -------------------------------------
+
+POCSAG_BAUDS = (512, 1200, 2400)
+POCSAG_MIN_SPS = 8.0  # below this the bit integrator is too coarse for a half-bit timing search
+POCSAG_MAX_SPS = 384  # IQA_POCSAG_MAX_SPS: what the sync kernel's LDS window admits
+POCSAG_THETA_BITS = 20  # t = rint(theta 2^20)
+POCSAG_BATCH_BITS = 544  # sync word + 16 codewords
+
+
+@dataclass(frozen=True)
+class PocsagBaud:
+    baud: int
+    sps: float  # fs / baud (float64)
+    L: int  # rint(sps): the bit integrator's window
+    h: int  # floor(sps / 2): the local-maximum radius and the batch continuation tolerance
+    offsets: np.ndarray  # int32[545]: rint(i sps), i = 0 .. 544, half-even in float64 (bit i of a batch; [544] = the next sync)
+
+
+@dataclass(frozen=True)
+class PocsagPlan:
+    fs: float
+    bauds: tuple  # the PocsagBaud entries that run, in POCSAG_BAUDS order
+    skipped: tuple  # the baud rates that do not fit this channel rate
+    hist_len: int  # quantised discriminator values carried in front of a block: max L - 1
+
+    def lengths(self) -> tuple:
+        """(L at 512, L at 1200, L at 2400), 0 for a skipped baud: what ``iqa_pocsag_integrate`` takes."""
+        by = {b.baud: b.L for b in self.bauds}
+        return tuple(by.get(b, 0) for b in POCSAG_BAUDS)
+
+
+@functools.lru_cache(maxsize=16)
+def plan_pocsag(fs_channel: float) -> PocsagPlan:
+    """The POCSAG decoder's per-baud constants at channel rate ``fs_channel``; ``ValueError`` when no baud rate fits."""
+    fs = float(fs_channel)
+    if not math.isfinite(fs) or fs <= 0.0:
+        raise ValueError("the channel rate must be positive")
+    bauds, skipped = [], []
+    for baud in POCSAG_BAUDS:
+        sps = fs / baud
+        if sps < POCSAG_MIN_SPS or sps > POCSAG_MAX_SPS:
+            skipped.append(baud)
+            continue
+        offsets = np.rint(np.arange(POCSAG_BATCH_BITS + 1, dtype=np.float64) * sps).astype(np.int32)
+        offsets.setflags(write=False)
+        bauds.append(PocsagBaud(baud, sps, int(np.rint(sps)), int(math.floor(sps / 2.0)), offsets))
+    if not bauds:
+        raise ValueError(f"POCSAG needs {POCSAG_MIN_SPS:.0f} to {POCSAG_MAX_SPS} samples per bit at 512, 1200 or 2400 baud; "
+                         f"a channel rate of {fs:.0f} Hz gives none of them (--fs-ch between about 20 000 and 190 000)")
+    return PocsagPlan(fs, tuple(bauds), tuple(skipped), max(b.L for b in bauds) - 1)
+
+
 # ---- 48 kHz resampler plan (build-defined spec; see DESIGN.md "48 kHz stage") -----------------
 
 RS_ZERO_CROSSINGS = 16

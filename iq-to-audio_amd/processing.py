@@ -33,6 +33,7 @@ from . import iqio
 from .channelizer import (_KERNEL_CACHE, _KERNEL_CACHE_LOCK, _KERNEL_CACHE_MAX, _TAPS_MEMO, ChannelBank,  # noqa: F401  (re-exported)
                           Channelizer, _as_frames, _cached_kernel, _ChannelKernel, _taps_fingerprint, immutable_taps)
 from .decoders import create_decoder
+from .decoders.pocsag import PocsagCore, parse_batches as pocsag_parse_batches
 from .decoders.rds import RdsCore, result_from as rds_result_from
 from .decoders.wfm import WfmStereoCore, stereo_matrix
 from .dsp_plan import design_channel_filter, tune_chunk_size  # noqa: F401  (re-exported API)
@@ -551,12 +552,22 @@ class ChannelDemod:
     peak, +-0.99 clip and the per-chunk sum of squares (rms_dbfs) are fused into the last scan pass
     (``iqa_demodulate``).  ``self.decoder`` is the matching pluggable decoder object (kept for its
     parameters and API parity; the fused path carries its own device state).
+
+    ``pocsag=True`` (nfm only): after the fused call every block also runs ``iqa_quadrature`` with a
+    ``prev`` state of its own and ``iqa_pocsag_integrate``; ``pocsag_finish`` searches the stored run for sync words and
+    parses the batches (a ``PocsagResult``, or ``None`` without a kept sync).  Off, no POCSAG entry point is called.
     """
 
-    def __init__(self, mode: str, fs_channel: float, *, deemph_us: float, agc_enabled: bool):
+    def __init__(self, mode: str, fs_channel: float, *, deemph_us: float, agc_enabled: bool, pocsag: bool = False):
         self.decoder = create_decoder(mode, deemph_us=deemph_us, agc_enabled=agc_enabled)
         self.decoder.setup(fs_channel)
         self.params = self.decoder.fused_params()
+        self.pocsag_core = None
+        if pocsag:
+            if self.params.mode != N.DEMOD_MODE["nfm"]:
+                raise ValueError("pocsag=True needs an nfm target: POCSAG is 2-FSK on a narrowband FM channel (--demod nfm)")
+            self.pocsag_core = PocsagCore(P.plan_pocsag(fs_channel))  # (ValueError where no baud rate fits the channel rate)
+            self._pocsag_prev = D.from_numpy(np.array([1 + 0j], dtype=np.complex64))
         self._needs_scratch = self.params.mode in (N.DEMOD_MODE["usb"], N.DEMOD_MODE["lsb"]) and bool(self.params.agc_enabled)
         self.chunk_sumsq: list = []  # (device float64[n_chunks*8], counts)
         self._blk = None  # one device block: [state 32 B | peak 4 B (+pad to 64) | sumsq n_chunks*8 f64]
@@ -584,6 +595,9 @@ class ChannelDemod:
         """Back to a decoder that has seen nothing (states, peak, per-chunk sums): one small H2D copy from a
         pinned image (pinned on the first reset: pin_memory() costs milliseconds)."""
         self.chunk_sumsq = []
+        if self.pocsag_core is not None:  # (before the early return: POCSAG state is not part of ``_fresh``)
+            self.pocsag_core.reset()
+            self._pocsag_prev = D.from_numpy(np.array([1 + 0j], dtype=np.complex64))
         if self._fresh and not force:  # (force: a step being captured into a graph must not depend on what ran before it)
             return
         # nothing is copied: the next ``process`` starts from the initial state by itself and clears the peak and the
@@ -628,6 +642,16 @@ class ChannelDemod:
                N.stream_ptr())
         counts = np.diff(np.append(chunk_starts, n))
         self.chunk_sumsq.append((sumsq, counts))
+        if self.pocsag_core is not None:
+            theta = D.empty(n, "float32")
+            N.call("iqa_quadrature", N.ptr(z_dev), c_int64(n), N.ptr(self._pocsag_prev), N.ptr(theta), N.stream_ptr())
+            self.pocsag_core.process(theta)
+
+    def pocsag_finish(self):
+        """The run's ``PocsagResult`` (``None`` without a kept sync, or with pocsag off)."""
+        if self.pocsag_core is None:
+            return None
+        return pocsag_parse_batches(self.pocsag_core.plan, self.pocsag_core.finish())
 
     @property
     def peak(self) -> float:
@@ -906,10 +930,12 @@ class ProcessingPipeline:
     #: frames per device block (rounded down to whole chunks); 64 Mi frames = 256 MiB of int16 I/Q
     block_frames_target = 64 * 1024 * 1024
 
-    def __init__(self, config: ProcessingConfig, *, rds: bool = False):
+    def __init__(self, config: ProcessingConfig, *, rds: bool = False, pocsag: bool = False):
         self.config = config
         if rds and (config.demod_mode or "").lower() != "wfm":
             raise ValueError("rds=True needs a wfm target: RDS rides on a broadcast FM multiplex (--demod wfm)")
+        if pocsag and (config.demod_mode or "").lower() not in ("nfm", "fm"):
+            raise ValueError("pocsag=True needs an nfm target: POCSAG is 2-FSK on a narrowband FM channel (--demod nfm)")
         self._cancelled = False
         self._resolved_chunk_size: int | None = None
         self.chunk_rms_dbfs: list[float] = []
@@ -922,6 +948,8 @@ class ProcessingPipeline:
         self.wfm_planes = None  # --demod wfm with keep_channel_audio: the stereo matrix's (a, b) planes, shape (2, n)
         self.rds_enabled = bool(rds)  # --rds: decode RDS beside wfm
         self.rds = None  # after run(): the station's RdsResult (None without a pilot, without groups, or with rds off)
+        self.pocsag_enabled = bool(pocsag)  # --pocsag: decode POCSAG beside nfm
+        self.pocsag = None  # after run(): the target's PocsagResult (None without a kept sync, or with pocsag off)
 
     def cancel(self) -> None:
         self._cancelled = True
@@ -949,7 +977,7 @@ class ProcessingPipeline:
 
     def run(self, progress_sink: ProgressSink | None = None) -> ProcessingResult:
         """One target frequency: a :class:`MultiChannelPipeline` with a single channel."""
-        multi = MultiChannelPipeline([self.config], _owner=self, rds=self.rds_enabled)
+        multi = MultiChannelPipeline([self.config], _owner=self, rds=self.rds_enabled, pocsag=self.pocsag_enabled)
         self._multi = multi
         if self._cancelled:
             multi.cancel()
@@ -976,9 +1004,11 @@ class _Target:
         elif self.wfm:
             self.demod = WfmDemod(fs_channel, deemph_us=cfg.deemph_us, rds=bool(getattr(owner, "rds_enabled", False)))
         else:
-            self.demod = ChannelDemod(cfg.demod_mode, fs_channel, deemph_us=cfg.deemph_us, agc_enabled=cfg.agc_enabled)
+            self.demod = ChannelDemod(cfg.demod_mode, fs_channel, deemph_us=cfg.deemph_us, agc_enabled=cfg.agc_enabled,
+                                      pocsag=bool(getattr(owner, "pocsag_enabled", False)))
         self.stereo = None  # wfm: the run's stereo decision (finish)
         self.rds = None  # wfm with rds: the station's RdsResult (finish)
+        self.pocsag = None  # nfm with pocsag: the target's PocsagResult (finish)
         if cfg.iq_order not in N.ORDER:
             raise ValueError(f"Unsupported iq_order '{cfg.iq_order}'")
         self.chan = None
@@ -1107,6 +1137,10 @@ class _Target:
         self.peak = self.demod.peak
         self.owner.chunk_rms_dbfs = self.demod.chunk_rms_dbfs()
         LOG.info("Audio peak level %.2f dBFS.", 20.0 * math.log10(max(self.peak, 1e-6)))
+        if self.demod.pocsag_core is not None:
+            self.pocsag = self.owner.pocsag = self.demod.pocsag_finish()
+            if self.pocsag is not None:
+                LOG.info("POCSAG: %d message(s), %d sync word(s).", len(self.pocsag.messages), sum(self.pocsag.syncs.values()))
 
 
 class MultiChannelPipeline:
@@ -1120,7 +1154,7 @@ class MultiChannelPipeline:
     ``configs`` must agree on the input file and its interpretation.
     """
 
-    def __init__(self, configs: list, _owner=None, *, rds: bool = False):
+    def __init__(self, configs: list, _owner=None, *, rds: bool = False, pocsag: bool = False):
         if not configs:
             raise ValueError("at least one ProcessingConfig is required")
         if len(configs) > 5 and _owner is None:
@@ -1135,10 +1169,13 @@ class MultiChannelPipeline:
         self.configs = configs
         if rds and any((c.demod_mode or "").lower() != "wfm" for c in configs):
             raise ValueError("rds=True needs wfm targets: RDS rides on a broadcast FM multiplex (--demod wfm)")
-        self.owners = [_owner] if _owner is not None else [ProcessingPipeline(c, rds=rds) for c in configs]
+        if pocsag and any((c.demod_mode or "").lower() not in ("nfm", "fm") for c in configs):
+            raise ValueError("pocsag=True needs nfm targets: POCSAG is 2-FSK on a narrowband FM channel (--demod nfm)")
+        self.owners = [_owner] if _owner is not None else [ProcessingPipeline(c, rds=rds, pocsag=pocsag) for c in configs]
         self._cancelled = False
         self.wfm_stereo = None  # after run(): per target, the wfm stereo decision (None for the other modes)
         self.rds = None  # after run(): per target, the RdsResult (None for non-wfm or pilot-less targets, or with rds off)
+        self.pocsag = None  # after run(): per target, the PocsagResult (None without a kept sync, or with pocsag off)
 
     def cancel(self) -> None:
         self._cancelled = True
@@ -1346,6 +1383,7 @@ class MultiChannelPipeline:
                 t.finish()
             self.wfm_stereo = [t.stereo for t in targets]  # per target: True / False for wfm, None for the other modes
             self.rds = [t.rds for t in targets]
+            self.pocsag = [t.pocsag for t in targets]
             self.output_paths = [t.output_path for t in targets]  # where each target's audio went
             for t in targets:
                 t.owner.output_path = t.output_path
