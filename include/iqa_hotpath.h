@@ -474,6 +474,50 @@ int iqa_pocsag_sync(const void *s_dev, int64_t n, const int32_t offsets[32], int
 int iqa_pocsag_codewords(const void *s_dev, int64_t n, const void *list_dev, int64_t nsync, const void *offsets_dev,
                          void *fixed_out_dev, void *raw_out_dev, void *status_out_dev, void *stream);
 
+/* ------------------------------------------------------------------------- *
+ * Bell-202 AFSK / AX.25 beside the NFM demodulator (--demod nfm --ax25) *
+ * ------------------------------------------------------------------------- */
+
+/* Most samples per bit (and so the longest tone correlator): 12 868 . 256 . L stays inside int32 up to L = 512, and the
+ * correlator kernel stages 2048 + L quantised values and 4 L taps in LDS.  A channel needs 8 <= fs / 1200 <= this. */
+#define IQA_AFSK_MAX_SPS 400
+#define IQA_AFSK_PHASES 8   /* sampling phases per bit */
+#define IQA_AFSK_GAINS 3    /* slicer gain pairs (a, b) = (1,1), (1,4), (4,1); variant v = IQA_AFSK_PHASES g + p */
+#define IQA_AFSK_SLOT_BYTES 332  /* one kept frame's bytes in the list (a frame has 17 .. 330) */
+/* One block of the quantiser, the tone correlators and the slicers.  With L = window:
+ *   t[n] = rint(theta[n] 4096) (int32, half-even);
+ *   I_f[n] = sum_{k<L} c_f[k] t[n-k], Q_f[n] = sum_{k<L} s_f[k] t[n-k] (int32), f = 1200, 2200;
+ *   E_f[n] = (I_f[n]^2 + Q_f[n]^2) >> 4 (int64);
+ *   sign[n] = bit g set iff a_g E_1200[n] - b_g E_2200[n] > 0 (int64), g = 0 .. 2.
+ * theta_dev: float32[n] (iqa_quadrature's output); hist_dev: int32[L - 1], the values of t in front of theta[0], oldest
+ * first (NULL: zeros); taps_dev: int16[4][L] = c_1200, s_1200, c_2200, s_2200 with c_f[k] = rint(256 cos(2 pi f k / fs)),
+ * s_f[k] = rint(256 sin(2 pi f k / fs)), |tap| <= 256; t_out_dev: int32[n]; sign_out_dev: uint8[n]; e1200_out_dev,
+ * e2200_out_dev: int64[n] each, or NULL (not stored).  8 <= window <= IQA_AFSK_MAX_SPS.  Integer sums: the outputs do
+ * not depend on how a stream is cut into blocks.
+ * Precondition: |t| < 2^23 everywhere, that is |theta[n]| < 2048 rad (a discriminator output has |theta| <= pi, |t| <= 12 868)
+ * and |hist_dev[i]| < 2^23 (values of t_out_dev of the block before are).  The products are formed by the 24-bit multiply,
+ * which sign-extends its operands from bit 23: outside the precondition I_f and Q_f differ from the formula above. */
+int iqa_afsk_correlate(const void *theta_dev, int64_t n, const void *hist_dev, int32_t window, const void *taps_dev,
+                       void *t_out_dev, void *sign_out_dev, void *e1200_out_dev, void *e2200_out_dev, void *stream);
+/* The 24 NRZI-decoded bit streams of a whole run.  sign_dev: uint8[n]; step = sps / 8 (float64, made once by the caller).
+ * Variant v = 8 g + p, bit i = 0 .. nbits - 1: instant n_i = window - 1 + rint((8 i + p) step) (one float64 product, one
+ * rint, half-even); m_i = bit g of sign[n_i]; bits[v][i] = (m_i == m_{i-1}), bits[v][0] = 1; 0 where n_i >= n (the bit
+ * does not exist).  bits_out_dev: uint8[24][nbits]. */
+int iqa_afsk_bits(const void *sign_dev, int64_t n, int32_t window, double step, int64_t nbits, void *bits_out_dev, void *stream);
+/* HDLC frames of the 24 bit streams.  bits_dev: uint8[24][nbits]; count_of: HOST int64[8], the number of bits of phase p
+ * that exist (<= nbits).  In variant v (b = bits[v], nb = count_of[v mod 8]) position s, 8 <= s, opens a candidate iff
+ * b[s-8 .. s-1] = 0,1,1,1,1,1,1,0 and b[s .. s+7] is not that flag (bits at nb and beyond match nothing).  From s bits
+ * are collected least significant first into bytes; a 0 after five consecutive 1s is dropped; the sixth consecutive 1 ends
+ * the walk: a closing flag iff the next bit exists and is 0 and exactly 6 bits of the current byte are collected, an abort
+ * otherwise; a 331st byte aborts; so does the end of the stream.  A closed candidate of >= 17 bytes is counted in
+ * counts[1]; it is kept iff the CRC-16/X.25 (reflected 0x8408, init 0xFFFF, final xor 0xFFFF) of all but its last two
+ * bytes equals them, low byte first.  Kept frames are appended in any order: list_dev: int64[4 capacity] = (v, s, start
+ * instant n_s, byte count) each, slots_dev: uint8[capacity][IQA_AFSK_SLOT_BYTES] = the bytes, zero-filled.
+ * counts_dev: int64[2], zeroed by the call; counts[0] counts ALL kept frames: a count above capacity means the list is
+ * incomplete and the call must be repeated with a larger one. */
+int iqa_afsk_frames(const void *bits_dev, int64_t nbits, const int64_t count_of[IQA_AFSK_PHASES], int32_t window, double step,
+                    void *list_dev, void *slots_dev, int64_t capacity, void *counts_dev, void *stream);
+
 /* Audio egress (the drain of AudioWriter, processing.py:433-438, without a host thread): copy nbytes from device
  * memory into MAPPED pinned host memory (hipHostMalloc / torch pin_memory) with `workgroups` small workgroups
  * (<= 0: 8), so that the copy can run beside a kernel that occupies every CU.  Both pointers 16-byte aligned. */

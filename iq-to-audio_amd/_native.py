@@ -162,6 +162,10 @@ _SIGNATURES = {
     "iqa_pocsag_sync": (ctypes.c_int, [c_void_p, c_int64, ctypes.POINTER(c_int32), c_int32, c_void_p, c_void_p, c_int64, c_void_p,
                                        c_void_p]),
     "iqa_pocsag_codewords": (ctypes.c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "iqa_afsk_correlate": (ctypes.c_int, [c_void_p, c_int64, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "iqa_afsk_bits": (ctypes.c_int, [c_void_p, c_int64, c_int32, c_double, c_int64, c_void_p, c_void_p]),
+    "iqa_afsk_frames": (ctypes.c_int, [c_void_p, c_int64, ctypes.POINTER(c_int64), c_int32, c_double, c_void_p, c_void_p, c_int64,
+                                       c_void_p, c_void_p]),
     "iqa_squelch_workspace_bytes": (c_int64, [c_int64, c_int32]),
     "iqa_squelch_stage_offset": (c_int64, [c_int64, c_int32, c_int32]),
     "iqa_squelch": (ctypes.c_int, [ctypes.POINTER(SquelchParams), ctypes.POINTER(SquelchSeg), c_int32, c_void_p, c_void_p,

@@ -34,6 +34,14 @@ def reject_pocsag(pocsag) -> None:
                          "use ProcessingPipeline / MultiChannelPipeline")
 
 
+def reject_ax25(ax25) -> None:
+    """AX.25 decoding stores a run's slicer plane and searches it at the end: ``ax25=True`` is a
+    ``ValueError`` up front, as ``pocsag=True`` is."""
+    if ax25:
+        raise ValueError("ax25=True is not supported by the resident batch runners or sharded runs: "
+                         "use ProcessingPipeline / MultiChannelPipeline")
+
+
 def _rank(precision: str) -> int:
     return _ChannelKernel.PRECISIONS.index(precision)
 
@@ -73,7 +81,8 @@ class ResidentCaptureRunner:
     def __init__(self, taps: np.ndarray, *, sample_rate: float, freq_offset: float, decimation: int, fs_channel: float,
                  chunk: int, n_frames: int, demod_mode: str = "nfm", deemph_us: float = 300.0, agc_enabled: bool = True,
                  fmt: str = "s16", iq_order: str = "iq", mix_sign_override: int | None = None, precision: str | None = None,
-                 precision_guard: float | None = None, slots: int | None = None, graph_streams: int = 1, pocsag: bool = False):
+                 precision_guard: float | None = None, slots: int | None = None, graph_streams: int = 1, pocsag: bool = False,
+                 ax25: bool = False):
         """``precision``: the channelizer precision every capture starts at (default: by demodulator,
         ``processing.base_precision``); ``precision_guard``: see ``processing.PRECISION_GUARD`` (0 = off).
         ``slots``: captures in flight (output buffers; default 2).  ``submit`` of capture i first waits for capture
@@ -87,6 +96,7 @@ class ResidentCaptureRunner:
         ordered behind the caller's stream)."""
         reject_wfm([demod_mode])
         reject_pocsag(pocsag)
+        reject_ax25(ax25)
         torch = D.torch_mod()
         if slots is not None:
             if slots < 2:
@@ -460,11 +470,12 @@ class ResidentBankRunner:
 
     def __init__(self, targets: list, *, sample_rate: float, n_frames: int, chunk_size: int = 1_048_576,
                  fs_ch_target: float = 96_000.0, fmt: str = "s16", iq_order: str = "iq", precision_guard: float | None = None,
-                 pocsag: bool = False):
+                 pocsag: bool = False, ax25: bool = False):
         """``targets``: dicts with ``freq_offset``, and optionally ``bandwidth`` (12 500), ``demod_mode`` ("nfm"),
         ``deemph_us`` (300), ``agc_enabled`` (True), ``mix_sign`` (None = probe), ``precision`` (None = by demodulator)."""
         reject_wfm([t.get("demod_mode") for t in targets])
         reject_pocsag(pocsag)
+        reject_ax25(ax25)
         torch = D.torch_mod()
         if not targets:
             raise ValueError("at least one target is required")
@@ -628,7 +639,8 @@ class ResidentBankRunner:
 
 
 def demodulate_sharded(targets: list, *, sample_rate: float, n_frames: int, axis: str, capture=None, captures=None,
-                       chunk_size: int = 1_048_576, fmt: str = "s16", iq_order: str = "iq", pocsag: bool = False):
+                       chunk_size: int = 1_048_576, fmt: str = "s16", iq_order: str = "iq", pocsag: bool = False,
+                       ax25: bool = False):
     """The N-GPU form of :class:`ResidentBankRunner` (one process per GPU under ``torch.distributed.run``; SURVEY.md
     section 8(e)), on either axis:
 
@@ -646,6 +658,7 @@ def demodulate_sharded(targets: list, *, sample_rate: float, n_frames: int, axis
 
     reject_wfm([t.get("demod_mode") for t in targets])
     reject_pocsag(pocsag)
+    reject_ax25(ax25)
     torch = D.torch_mod()
     if axis not in ("channels", "captures"):
         raise ValueError("axis must be 'channels' or 'captures'")

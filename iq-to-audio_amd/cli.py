@@ -91,6 +91,9 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--pocsag", dest="pocsag", action="store_true",
                    help="With --demod nfm: decode POCSAG pager traffic (512 / 1200 / 2400 baud) of every target, print one line "
                         "per message and write <output stem>.pocsag.json.")
+    p.add_argument("--ax25", dest="ax25", action="store_true",
+                   help="With --demod nfm: decode 1200-baud Bell-202 AX.25 frames (APRS, packet) of every target, print one TNC2-style "
+                        "line per frame and write <output stem>.ax25.json.")
     p.add_argument("--no-agc", dest="agc_enabled", action="store_false")
     p.add_argument("--out", dest="output_path", type=Path)
     p.add_argument("--dump-iq", dest="dump_iq", type=Path)
@@ -199,6 +202,8 @@ def main(argv: list[str] | None = None) -> int:
         parser.error("--rds needs --demod wfm.")
     if args.pocsag and args.demod != "nfm":
         parser.error("--pocsag needs --demod nfm.")
+    if args.ax25 and args.demod != "nfm":
+        parser.error("--ax25 needs --demod nfm.")
     if args.audio_post_path:
         return run_audio_post(args)
     frequencies = list(args.target_freqs or [])
@@ -252,7 +257,7 @@ def main(argv: list[str] | None = None) -> int:
     LOG.info("=== Processing %d target(s) in one pass over %s ===", len(configs), args.input_path)
     try:
         # the reference loops whole pipelines over the targets (cli.py:683-710); here the capture is read once
-        extras = dict(rds=args.rds, pocsag=args.pocsag)
+        extras = dict(rds=args.rds, pocsag=args.pocsag, ax25=args.ax25)
         runner = MultiChannelPipeline(configs, **extras) if len(configs) > 1 else ProcessingPipeline(configs[0], **extras)
         results = runner.run(progress_sink=None)
         results = results if len(configs) > 1 else [results]
@@ -280,6 +285,13 @@ def main(argv: list[str] | None = None) -> int:
             for msg in (res.messages if res is not None else []):
                 print(f"{config.target_freq:.0f} Hz: {msg.line()}")
             wav.with_name(wav.stem + ".pocsag.json").write_text(json.dumps(None if res is None else res.to_json(), indent=1) + "\n")
+    if args.ax25 and not args.probe_only:
+        decoded = runner.ax25 if len(configs) > 1 else [runner.ax25]
+        targets = runner.output_paths if len(configs) > 1 else [runner.output_path]
+        for config, res, wav in zip(configs, decoded, targets):
+            for frame in (res.frames if res is not None else []):
+                print(f"{config.target_freq:.0f} Hz: AX25 {frame.line()}")
+            wav.with_name(wav.stem + ".ax25.json").write_text(json.dumps(None if res is None else res.to_json(), indent=1) + "\n")
     return 0
 
 

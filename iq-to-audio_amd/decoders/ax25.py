@@ -1,0 +1,273 @@
+"""AX.25 frames over 1200-baud Bell-202 AFSK beside narrowband FM: APRS, packet, telemetry.
+
+Per block ``iqa_afsk_correlate`` quantises the discriminator output, runs the mark and space tone correlators and appends
+one byte per sample (three slicer decisions) to the run's stored plane; once per run ``iqa_afsk_bits`` reads the plane at
+8 sampling phases x 3 space gains into 24 NRZI-decoded bit streams and ``iqa_afsk_frames`` walks every HDLC candidate of
+every stream and keeps those whose CRC holds.  Every frame carries its own check, so timing and tone balance are found by
+search: there is no loop.  Merging, address validation and parsing are integer host logic on the kept frames and run on
+plain numpy arrays as well (``parse_frames``)."""
+from __future__ import annotations
+
+from ctypes import c_double, c_int32, c_int64
+from dataclasses import asdict, dataclass, field
+
+import numpy as np
+
+from .. import _dev as D
+from .. import _native as N
+from .. import dsp_plan as P
+
+FLAG = 0x7E
+CRC_POLY = 0x8408  # CRC-16/X.25, reflected; init 0xFFFF, final xor 0xFFFF
+MIN_FRAME, MAX_FRAME = 17, 330  # bytes, FCS included
+SLOT_BYTES = 332  # IQA_AFSK_SLOT_BYTES
+VARIANTS = len(P.AFSK_GAINS) * P.AFSK_PHASES
+CALL_CHARS = frozenset(b"ABCDEFGHIJKLMNOPQRSTUVWXYZ0123456789 ")
+CONTROL_UI, PID_NO_LAYER3 = 0x03, 0xF0
+
+
+def crc16_x25(data: bytes) -> int:
+    reg = 0xFFFF
+    for byte in data:
+        reg ^= byte
+        for _ in range(8):
+            reg = (reg >> 1) ^ CRC_POLY if reg & 1 else reg >> 1
+    return reg ^ 0xFFFF
+
+
+@dataclass
+class Ax25Frame:
+    time_s: float  # of the first bit behind the opening flag
+    source: str
+    dest: str
+    path: list  # digipeaters, "*" behind one whose H bit is set
+    control: int
+    pid: int | None  # None for a frame without a PID field (S and U frames other than UI)
+    info: str  # UI frames (control 0x03, PID 0xF0): text, anything outside printable ASCII as U+FFFD; otherwise hex
+    raw: str  # the whole frame, FCS included, as hex
+    hits: int  # grid points (gain, phase) that decoded it
+
+    def line(self) -> str:
+        """TNC2 style: SOURCE>DEST,DIGI*,DIGI:info."""
+        return f"{self.source}>{','.join([self.dest] + list(self.path))}:{self.info}"
+
+
+@dataclass
+class Ax25Result:
+    frames: list = field(default_factory=list)  # Ax25Frame, in order of time
+    candidates: int = 0  # closed HDLC candidates of >= 17 bytes over all grid points
+    crc_ok: int = 0  # of those, the ones whose CRC holds
+    rejected: int = 0  # merged CRC-passing frames with an invalid address field
+
+    def to_json(self) -> dict:
+        return asdict(self)
+
+
+def _callsign(seven: bytes) -> str | None:
+    if any(c & 1 for c in seven[:6]) or any((c >> 1) not in CALL_CHARS for c in seven[:6]):
+        return None
+    name = bytes(c >> 1 for c in seven[:6]).decode("ascii").rstrip()
+    ssid = (seven[6] >> 1) & 15
+    return f"{name}-{ssid}" if ssid else name
+
+
+def parse_frame(raw: bytes):
+    """One CRC-checked frame (FCS included) -> dict(source, dest, path, control, pid, info), or ``None`` where the address
+    field is invalid: 2 to 10 addresses of 7 bytes, callsign characters ``>> 1`` in A-Z, 0-9, space with a zero low bit, the
+    extension bit on the last address and on no other."""
+    body = bytes(raw[:-2])
+    calls = []
+    while True:
+        seven = body[7 * len(calls) : 7 * len(calls) + 7]
+        if len(seven) < 7:
+            return None
+        name = _callsign(seven)
+        if name is None:
+            return None
+        calls.append((name, bool(seven[6] & 0x80)))
+        if seven[6] & 1:
+            break
+        if len(calls) == 10:
+            return None
+    rest = body[7 * len(calls) :]
+    if len(calls) < 2 or not rest:
+        return None
+    control = rest[0]
+    has_pid = ((control & 0xEF) == CONTROL_UI or (control & 1) == 0) and len(rest) >= 2
+    pid = rest[1] if has_pid else None
+    info = rest[2:] if has_pid else rest[1:]
+    if control == CONTROL_UI and pid == PID_NO_LAYER3:
+        text = "".join(chr(c) if 0x20 <= c <= 0x7E else "�" for c in info)
+    else:
+        text = info.hex()
+    return dict(dest=calls[0][0], source=calls[1][0], path=[c + ("*" if h else "") for c, h in calls[2:]], control=control, pid=pid, info=text)
+
+
+def _group_of(groups: list, raw: bytes, at: int, reach: int):
+    """The latest group with these bytes whose first start instant lies within ``reach`` of ``at``, or ``None``."""
+    for grp in reversed(groups):
+        if at - grp[0] > reach:
+            return None  # (ascending start instants: every earlier group is further back still)
+        if grp[1] == raw:
+            return grp
+    return None
+
+
+def parse_frames(plan: P.AfskPlan, records: dict, candidates: int = 0) -> Ax25Result | None:
+    """``records``: dict(variant=[k], s=[k], start=[k], nbytes=[k], data=uint8[k, >= nbytes]) in any order (the kept-frame
+    list of ``iqa_afsk_frames``) -> the run's frames.  Integer logic only; ``None`` where no frame survives."""
+    start = np.asarray(records["start"], dtype=np.int64).reshape(-1)
+    variant = np.asarray(records["variant"], dtype=np.int64).reshape(-1)
+    nbytes = np.asarray(records["nbytes"], dtype=np.int64).reshape(-1)
+    data = np.asarray(records["data"], dtype=np.uint8).reshape(start.size, -1) if start.size else np.zeros((0, 0), dtype=np.uint8)
+    res = Ax25Result(candidates=int(candidates), crc_ok=int(start.size))
+    groups: list = []  # [first start instant, bytes, hits], ascending in the first start instant
+    for k in np.lexsort((variant, start)).tolist():
+        raw, at = data[k, : int(nbytes[k])].tobytes(), int(start[k])
+        grp = _group_of(groups, raw, at, plan.L)
+        if grp is None:
+            groups.append([at, raw, 1])
+        else:
+            grp[2] += 1
+    for at, raw, hits in groups:
+        got = parse_frame(raw)
+        if got is None:
+            res.rejected += 1
+            continue
+        res.frames.append(Ax25Frame(time_s=at / plan.fs, raw=raw.hex(), hits=hits, **got))
+    return res if res.frames else None
+
+
+class AfskCore:
+    """Per-stream device state: the carried quantised history (L - 1 values), the absolute position, and the growing store
+    of the slicer plane (one uint8 device tensor per block, joined by ``finish``).  ``keep_stages`` also stores t and the
+    two energy planes, for the tests."""
+
+    def __init__(self, plan: P.AfskPlan, *, keep_stages: bool = False):
+        self.plan = plan
+        self.hist_len = plan.L - 1
+        self._taps = D.from_numpy(np.ascontiguousarray(plan.taps))
+        self._hist = None  # device int32[hist_len]; None = zeros
+        self.pos = 0  # absolute index of the next block's first sample
+        self.keep_stages = keep_stages
+        self._sign: list = []
+        self._t: list = []
+        self._e: list = []  # per block: (E_1200, E_2200)
+
+    def process(self, theta) -> None:
+        """One block of the discriminator output (device float32[n], radians per sample)."""
+        n = int(theta.numel())
+        if n == 0:
+            return
+        t, sign = D.empty(n, "int32"), D.empty(n, "uint8")
+        e = (D.empty(n, "int64"), D.empty(n, "int64")) if self.keep_stages else (None, None)
+        N.call("iqa_afsk_correlate", N.ptr(theta), c_int64(n), N.ptr(self._hist), c_int32(self.plan.L), N.ptr(self._taps), N.ptr(t),
+               N.ptr(sign), N.ptr(e[0]), N.ptr(e[1]), N.stream_ptr())
+        self._sign.append(sign)
+        if self.keep_stages:
+            self._t.append(t)
+            self._e.append(e)
+        h = self.hist_len
+        if n >= h:
+            self._hist = t[n - h :].clone()
+        else:
+            prev = self._hist if self._hist is not None else D.zeros(h, "int32")
+            self._hist = D.torch_mod().cat([prev[n:], t])
+        self.pos += n
+
+    def joined(self) -> dict:
+        torch = D.torch_mod()
+        if len(self._sign) > 1:
+            self._sign = [torch.cat(self._sign)]
+            self._t = [torch.cat(self._t)] if self._t else []
+            self._e = [tuple(torch.cat(col) for col in zip(*self._e))] if self._e else []
+        return dict(sign=self._sign[0] if self._sign else D.empty(0, "uint8"), t=self._t[0] if self._t else None,
+                    E=dict(zip(P.AFSK_TONES, self._e[0])) if self._e else None)
+
+    def reset(self) -> None:
+        """Back to a stream that has seen nothing: no history, position 0, no stored planes."""
+        self._hist, self.pos, self._sign, self._t, self._e = None, 0, [], [], []
+
+    def _frames(self, bits, nbits: int, count_of, capacity: int, counts):
+        lst, slots = D.empty(4 * capacity, "int64"), D.empty(SLOT_BYTES * capacity, "uint8")
+        N.call("iqa_afsk_frames", N.ptr(bits), c_int64(nbits), count_of, c_int32(self.plan.L), c_double(self.plan.step), N.ptr(lst),
+               N.ptr(slots), c_int64(capacity), N.ptr(counts), N.stream_ptr())
+        return lst, slots
+
+    def finish(self, capacity: int = 256) -> dict:
+        """The bit streams and the kept frames of the stored run: dict(variant, s, start, nbytes, data, candidates, bits,
+        count_of), the records as numpy arrays sorted by (variant, s).  A list too short for the kept frames is never used:
+        the search is repeated with room for all of them."""
+        plan = self.plan
+        sign = self.joined()["sign"]
+        n = int(sign.numel())
+        counts_of = [plan.bit_count(p, n) for p in range(P.AFSK_PHASES)]
+        nbits = max(counts_of)
+        count_of = (c_int64 * P.AFSK_PHASES)(*counts_of)
+        bits = D.empty(VARIANTS * nbits, "uint8")
+        N.call("iqa_afsk_bits", N.ptr(sign), c_int64(n), c_int32(plan.L), c_double(plan.step), c_int64(nbits), N.ptr(bits), N.stream_ptr())
+        counts = D.zeros(2, "int64")
+        lst, slots = self._frames(bits, nbits, count_of, capacity, counts)
+        kept, closed = (int(v) for v in counts.cpu().numpy())
+        if kept > capacity:
+            lst, slots = self._frames(bits, nbits, count_of, kept, counts)
+            assert int(counts[0].item()) == kept
+        entries = lst[: 4 * kept].cpu().numpy().reshape(-1, 4)
+        data = slots[: SLOT_BYTES * kept].cpu().numpy().reshape(-1, SLOT_BYTES)
+        order = np.lexsort((entries[:, 1], entries[:, 0]))
+        entries, data = entries[order], data[order]
+        return dict(variant=entries[:, 0].copy(), s=entries[:, 1].copy(), start=entries[:, 2].copy(), nbytes=entries[:, 3].copy(), data=data,
+                    candidates=closed, bits=bits, nbits=nbits, count_of=counts_of)
+
+
+class Ax25Decoder:
+    """The stage API: ``process(block)`` per block of the channel (complex: the channelizer's output, run through
+    ``iqa_quadrature`` with this decoder's own ``prev``; or float32: a discriminator output in radians per sample,
+    |theta| < 2048 as ``iqa_afsk_correlate`` requires; a discriminator gives |theta| <= pi),
+    ``finish()`` once (an ``Ax25Result``, or ``None`` without a frame), ``stages()`` for the tests."""
+
+    def __init__(self, rate: float, *, keep_stages: bool = True):
+        self.plan = P.plan_afsk(float(rate))
+        self.core = AfskCore(self.plan, keep_stages=keep_stages)
+        self._prev = D.from_numpy(np.array([1 + 0j], dtype=np.complex64))
+        self.theta: list = []  # with keep_stages: the discriminator output of every block (device)
+        self._fin = None
+
+    def process(self, block) -> None:
+        torch = D.torch_mod()
+        is_complex = torch.is_complex(block) if D.is_tensor(block) else np.iscomplexobj(block)
+        if is_complex:
+            z = D.to_device(block, "complex64")
+            theta = D.empty(int(z.numel()), "float32")
+            if z.numel():
+                N.call("iqa_quadrature", N.ptr(z), c_int64(int(z.numel())), N.ptr(self._prev), N.ptr(theta), N.stream_ptr())
+        else:
+            theta = D.to_device(block, "float32")
+        if self.core.keep_stages:
+            self.theta.append(theta)
+        self.core.process(theta)
+        self._fin = None
+
+    def _finished(self) -> dict:
+        if self._fin is None:
+            self._fin = self.core.finish()
+        return self._fin
+
+    def finish(self) -> Ax25Result | None:
+        fin = self._finished()
+        return parse_frames(self.plan, fin, fin["candidates"])
+
+    def stages(self) -> dict:
+        """Host copies: ``theta``, ``t`` and ``E`` (tone -> int64[n]; with keep_stages), ``sign``, ``bits`` (24 uint8 arrays, each
+        as long as its phase has bits) and ``records`` ([(variant, s, start instant, bytes)] sorted)."""
+        fin = self._finished()
+        st = self.core.joined()
+        torch = D.torch_mod()
+        plane = fin["bits"].cpu().numpy().reshape(VARIANTS, -1) if fin["nbits"] else np.zeros((VARIANTS, 0), dtype=np.uint8)
+        bits = [plane[v, : fin["count_of"][v % P.AFSK_PHASES]] for v in range(VARIANTS)]
+        records = [(int(v), int(s), int(at), fin["data"][k, : int(nb)].tobytes())
+                   for k, (v, s, at, nb) in enumerate(zip(fin["variant"], fin["s"], fin["start"], fin["nbytes"]))]
+        return dict(theta=torch.cat(self.theta).cpu().numpy() if self.theta else None,
+                    t=None if st["t"] is None else st["t"].cpu().numpy(),
+                    E=None if st["E"] is None else {f: e.cpu().numpy() for f, e in st["E"].items()},
+                    sign=st["sign"].cpu().numpy(), bits=bits, records=records, candidates=fin["candidates"])

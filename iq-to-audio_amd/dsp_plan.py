@@ -565,6 +565,59 @@ def plan_pocsag(fs_channel: float) -> PocsagPlan:
     return PocsagPlan(fs, tuple(bauds), tuple(skipped), max(b.L for b in bauds) - 1)
 
 
+# ---- AFSK / AX.25 plan (--demod nfm --ax25) ---------------------------------
+
+AFSK_BAUD = 1200
+AFSK_TONES = (1200, 2200)  # mark, space (Bell 202)
+AFSK_MIN_SPS = 8.0  # below this eight sampling phases per bit are not distinct
+AFSK_MAX_SPS = 400  # IQA_AFSK_MAX_SPS
+AFSK_THETA_BITS = 12  # t = rint(theta 2^12)
+AFSK_TAP_SCALE = 256.0
+AFSK_PHASES = 8  # IQA_AFSK_PHASES
+AFSK_GAINS = ((1, 1), (1, 4), (4, 1))  # (a, b) of d = a E_1200 - b E_2200: flat, de-emphasised and pre-emphasised space tone
+
+
+@dataclass(frozen=True)
+class AfskPlan:
+    fs: float
+    sps: float  # fs / 1200 (float64)
+    L: int  # rint(sps): the tone correlators' window
+    step: float  # sps / 8: the spacing of the sampling phases
+    taps: np.ndarray  # int16[4, L]: c_1200, s_1200, c_2200, s_2200
+
+    def instant(self, i, p: int):
+        """The instant of bit ``i`` (an int or an integer array) at phase ``p``: L - 1 + rint((8 i + p) step)."""
+        return self.L - 1 + np.rint((8.0 * np.asarray(i, dtype=np.float64) + p) * self.step).astype(np.int64)
+
+    def bit_count(self, p: int, n: int) -> int:
+        """How many bits of phase ``p`` have their instant inside a stream of ``n`` samples."""
+        i = max(int((n - self.L) / self.sps) - 2, 0)
+        while int(self.instant(i, p)) < n:
+            i += 1
+        return i
+
+
+@functools.lru_cache(maxsize=16)
+def plan_afsk(fs_channel: float) -> AfskPlan:
+    """The Bell-202 decoder's constants at channel rate ``fs_channel``; ``ValueError`` when 1200 baud does not fit it."""
+    fs = float(fs_channel)
+    if not math.isfinite(fs) or fs <= 0.0:
+        raise ValueError("the channel rate must be positive")
+    sps = fs / AFSK_BAUD
+    if sps < AFSK_MIN_SPS or sps > AFSK_MAX_SPS:
+        raise ValueError(f"AFSK at 1200 baud needs {AFSK_MIN_SPS:.0f} to {AFSK_MAX_SPS} samples per bit; a channel rate of {fs:.0f} Hz "
+                         f"gives {sps:.1f} (--fs-ch between 9 600 and 480 000)")
+    L = int(np.rint(sps))
+    k = np.arange(L, dtype=np.float64)
+    rows = []
+    for f in AFSK_TONES:
+        rows.append(np.rint(AFSK_TAP_SCALE * np.cos(2.0 * np.pi * f * k / fs)))
+        rows.append(np.rint(AFSK_TAP_SCALE * np.sin(2.0 * np.pi * f * k / fs)))
+    taps = np.ascontiguousarray(np.stack(rows).astype(np.int16))
+    taps.setflags(write=False)
+    return AfskPlan(fs, sps, L, sps / 8.0, taps)
+
+
 # ---- 48 kHz resampler plan (build-defined spec; see DESIGN.md "48 kHz stage") -----------------
 
 RS_ZERO_CROSSINGS = 16

@@ -33,6 +33,7 @@ from . import iqio
 from .channelizer import (_KERNEL_CACHE, _KERNEL_CACHE_LOCK, _KERNEL_CACHE_MAX, _TAPS_MEMO, ChannelBank,  # noqa: F401  (re-exported)
                           Channelizer, _as_frames, _cached_kernel, _ChannelKernel, _taps_fingerprint, immutable_taps)
 from .decoders import create_decoder
+from .decoders.ax25 import AfskCore, parse_frames as ax25_parse_frames
 from .decoders.pocsag import PocsagCore, parse_batches as pocsag_parse_batches
 from .decoders.rds import RdsCore, result_from as rds_result_from
 from .decoders.wfm import WfmStereoCore, stereo_matrix
@@ -556,9 +557,13 @@ class ChannelDemod:
     ``pocsag=True`` (nfm only): after the fused call every block also runs ``iqa_quadrature`` with a
     ``prev`` state of its own and ``iqa_pocsag_integrate``; ``pocsag_finish`` searches the stored run for sync words and
     parses the batches (a ``PocsagResult``, or ``None`` without a kept sync).  Off, no POCSAG entry point is called.
+
+    ``ax25=True`` (nfm only): likewise ``iqa_quadrature`` with a third ``prev`` and
+    ``iqa_afsk_correlate`` per block; ``ax25_finish`` reads the stored slicer plane into bit streams, walks the HDLC frames
+    and parses them (an ``Ax25Result``, or ``None`` without a frame).  Off, no AFSK entry point is called.
     """
 
-    def __init__(self, mode: str, fs_channel: float, *, deemph_us: float, agc_enabled: bool, pocsag: bool = False):
+    def __init__(self, mode: str, fs_channel: float, *, deemph_us: float, agc_enabled: bool, pocsag: bool = False, ax25: bool = False):
         self.decoder = create_decoder(mode, deemph_us=deemph_us, agc_enabled=agc_enabled)
         self.decoder.setup(fs_channel)
         self.params = self.decoder.fused_params()
@@ -568,6 +573,12 @@ class ChannelDemod:
                 raise ValueError("pocsag=True needs an nfm target: POCSAG is 2-FSK on a narrowband FM channel (--demod nfm)")
             self.pocsag_core = PocsagCore(P.plan_pocsag(fs_channel))  # (ValueError where no baud rate fits the channel rate)
             self._pocsag_prev = D.from_numpy(np.array([1 + 0j], dtype=np.complex64))
+        self.afsk_core = None
+        if ax25:
+            if self.params.mode != N.DEMOD_MODE["nfm"]:
+                raise ValueError("ax25=True needs an nfm target: AX.25 here is Bell-202 AFSK on a narrowband FM channel (--demod nfm)")
+            self.afsk_core = AfskCore(P.plan_afsk(fs_channel))  # (ValueError where 1200 baud does not fit the channel rate)
+            self._afsk_prev = D.from_numpy(np.array([1 + 0j], dtype=np.complex64))
         self._needs_scratch = self.params.mode in (N.DEMOD_MODE["usb"], N.DEMOD_MODE["lsb"]) and bool(self.params.agc_enabled)
         self.chunk_sumsq: list = []  # (device float64[n_chunks*8], counts)
         self._blk = None  # one device block: [state 32 B | peak 4 B (+pad to 64) | sumsq n_chunks*8 f64]
@@ -598,6 +609,9 @@ class ChannelDemod:
         if self.pocsag_core is not None:  # (before the early return: POCSAG state is not part of ``_fresh``)
             self.pocsag_core.reset()
             self._pocsag_prev = D.from_numpy(np.array([1 + 0j], dtype=np.complex64))
+        if self.afsk_core is not None:
+            self.afsk_core.reset()
+            self._afsk_prev = D.from_numpy(np.array([1 + 0j], dtype=np.complex64))
         if self._fresh and not force:  # (force: a step being captured into a graph must not depend on what ran before it)
             return
         # nothing is copied: the next ``process`` starts from the initial state by itself and clears the peak and the
@@ -646,6 +660,17 @@ class ChannelDemod:
             theta = D.empty(n, "float32")
             N.call("iqa_quadrature", N.ptr(z_dev), c_int64(n), N.ptr(self._pocsag_prev), N.ptr(theta), N.stream_ptr())
             self.pocsag_core.process(theta)
+        if self.afsk_core is not None:
+            theta = D.empty(n, "float32")
+            N.call("iqa_quadrature", N.ptr(z_dev), c_int64(n), N.ptr(self._afsk_prev), N.ptr(theta), N.stream_ptr())
+            self.afsk_core.process(theta)
+
+    def ax25_finish(self):
+        """The run's ``Ax25Result`` (``None`` without a frame, or with ax25 off)."""
+        if self.afsk_core is None:
+            return None
+        fin = self.afsk_core.finish()
+        return ax25_parse_frames(self.afsk_core.plan, fin, fin["candidates"])
 
     def pocsag_finish(self):
         """The run's ``PocsagResult`` (``None`` without a kept sync, or with pocsag off)."""
@@ -930,12 +955,14 @@ class ProcessingPipeline:
     #: frames per device block (rounded down to whole chunks); 64 Mi frames = 256 MiB of int16 I/Q
     block_frames_target = 64 * 1024 * 1024
 
-    def __init__(self, config: ProcessingConfig, *, rds: bool = False, pocsag: bool = False):
+    def __init__(self, config: ProcessingConfig, *, rds: bool = False, pocsag: bool = False, ax25: bool = False):
         self.config = config
         if rds and (config.demod_mode or "").lower() != "wfm":
             raise ValueError("rds=True needs a wfm target: RDS rides on a broadcast FM multiplex (--demod wfm)")
         if pocsag and (config.demod_mode or "").lower() not in ("nfm", "fm"):
             raise ValueError("pocsag=True needs an nfm target: POCSAG is 2-FSK on a narrowband FM channel (--demod nfm)")
+        if ax25 and (config.demod_mode or "").lower() not in ("nfm", "fm"):
+            raise ValueError("ax25=True needs an nfm target: AX.25 here is Bell-202 AFSK on a narrowband FM channel (--demod nfm)")
         self._cancelled = False
         self._resolved_chunk_size: int | None = None
         self.chunk_rms_dbfs: list[float] = []
@@ -950,6 +977,8 @@ class ProcessingPipeline:
         self.rds = None  # after run(): the station's RdsResult (None without a pilot, without groups, or with rds off)
         self.pocsag_enabled = bool(pocsag)  # --pocsag: decode POCSAG beside nfm
         self.pocsag = None  # after run(): the target's PocsagResult (None without a kept sync, or with pocsag off)
+        self.ax25_enabled = bool(ax25)  # --ax25: decode AX.25 over Bell-202 AFSK beside nfm
+        self.ax25 = None  # after run(): the target's Ax25Result (None without a frame, or with ax25 off)
 
     def cancel(self) -> None:
         self._cancelled = True
@@ -977,7 +1006,7 @@ class ProcessingPipeline:
 
     def run(self, progress_sink: ProgressSink | None = None) -> ProcessingResult:
         """One target frequency: a :class:`MultiChannelPipeline` with a single channel."""
-        multi = MultiChannelPipeline([self.config], _owner=self, rds=self.rds_enabled, pocsag=self.pocsag_enabled)
+        multi = MultiChannelPipeline([self.config], _owner=self, rds=self.rds_enabled, pocsag=self.pocsag_enabled, ax25=self.ax25_enabled)
         self._multi = multi
         if self._cancelled:
             multi.cancel()
@@ -1005,10 +1034,11 @@ class _Target:
             self.demod = WfmDemod(fs_channel, deemph_us=cfg.deemph_us, rds=bool(getattr(owner, "rds_enabled", False)))
         else:
             self.demod = ChannelDemod(cfg.demod_mode, fs_channel, deemph_us=cfg.deemph_us, agc_enabled=cfg.agc_enabled,
-                                      pocsag=bool(getattr(owner, "pocsag_enabled", False)))
+                                      pocsag=bool(getattr(owner, "pocsag_enabled", False)), ax25=bool(getattr(owner, "ax25_enabled", False)))
         self.stereo = None  # wfm: the run's stereo decision (finish)
         self.rds = None  # wfm with rds: the station's RdsResult (finish)
         self.pocsag = None  # nfm with pocsag: the target's PocsagResult (finish)
+        self.ax25 = None  # nfm with ax25: the target's Ax25Result (finish)
         if cfg.iq_order not in N.ORDER:
             raise ValueError(f"Unsupported iq_order '{cfg.iq_order}'")
         self.chan = None
@@ -1141,6 +1171,10 @@ class _Target:
             self.pocsag = self.owner.pocsag = self.demod.pocsag_finish()
             if self.pocsag is not None:
                 LOG.info("POCSAG: %d message(s), %d sync word(s).", len(self.pocsag.messages), sum(self.pocsag.syncs.values()))
+        if self.demod.afsk_core is not None:
+            self.ax25 = self.owner.ax25 = self.demod.ax25_finish()
+            if self.ax25 is not None:
+                LOG.info("AX.25: %d frame(s), %d CRC-passing candidate(s).", len(self.ax25.frames), self.ax25.crc_ok)
 
 
 class MultiChannelPipeline:
@@ -1154,7 +1188,7 @@ class MultiChannelPipeline:
     ``configs`` must agree on the input file and its interpretation.
     """
 
-    def __init__(self, configs: list, _owner=None, *, rds: bool = False, pocsag: bool = False):
+    def __init__(self, configs: list, _owner=None, *, rds: bool = False, pocsag: bool = False, ax25: bool = False):
         if not configs:
             raise ValueError("at least one ProcessingConfig is required")
         if len(configs) > 5 and _owner is None:
@@ -1171,11 +1205,14 @@ class MultiChannelPipeline:
             raise ValueError("rds=True needs wfm targets: RDS rides on a broadcast FM multiplex (--demod wfm)")
         if pocsag and any((c.demod_mode or "").lower() not in ("nfm", "fm") for c in configs):
             raise ValueError("pocsag=True needs nfm targets: POCSAG is 2-FSK on a narrowband FM channel (--demod nfm)")
-        self.owners = [_owner] if _owner is not None else [ProcessingPipeline(c, rds=rds, pocsag=pocsag) for c in configs]
+        if ax25 and any((c.demod_mode or "").lower() not in ("nfm", "fm") for c in configs):
+            raise ValueError("ax25=True needs nfm targets: AX.25 here is Bell-202 AFSK on a narrowband FM channel (--demod nfm)")
+        self.owners = [_owner] if _owner is not None else [ProcessingPipeline(c, rds=rds, pocsag=pocsag, ax25=ax25) for c in configs]
         self._cancelled = False
         self.wfm_stereo = None  # after run(): per target, the wfm stereo decision (None for the other modes)
         self.rds = None  # after run(): per target, the RdsResult (None for non-wfm or pilot-less targets, or with rds off)
         self.pocsag = None  # after run(): per target, the PocsagResult (None without a kept sync, or with pocsag off)
+        self.ax25 = None  # after run(): per target, the Ax25Result (None without a frame, or with ax25 off)
 
     def cancel(self) -> None:
         self._cancelled = True
@@ -1384,6 +1421,7 @@ class MultiChannelPipeline:
             self.wfm_stereo = [t.stereo for t in targets]  # per target: True / False for wfm, None for the other modes
             self.rds = [t.rds for t in targets]
             self.pocsag = [t.pocsag for t in targets]
+            self.ax25 = [t.ax25 for t in targets]
             self.output_paths = [t.output_path for t in targets]  # where each target's audio went
             for t in targets:
                 t.owner.output_path = t.output_path
