@@ -28,7 +28,7 @@ __global__ __launch_bounds__(256) void k_mean_power(const float2 *z, long long n
     const long long stride = static_cast<long long>(gridDim.x) * blockDim.x;
     for (long long i = skip + static_cast<long long>(blockIdx.x) * blockDim.x + threadIdx.x; i < n; i += stride) {
         const float2 v = z[i];
-        const float m = hypotf(v.x, v.y);  // np.abs(complex64) -> float32, then **2 in float32
+        const float m = np_abs_c64(v.x, v.y);  // np.abs(complex64) -> float32, then **2 in float32
         acc += static_cast<double>(m * m);
     }
     acc = wave_sum(acc);
@@ -50,7 +50,7 @@ __global__ __launch_bounds__(1024) void k_mean_power_small(const float2 *z, long
     double acc = 0.0;
     for (long long i = skip + threadIdx.x; i < n; i += 1024) {
         const float2 v = z[i];
-        const float m = hypotf(v.x, v.y);
+        const float m = np_abs_c64(v.x, v.y);
         acc += static_cast<double>(m * m);
     }
     acc = wave_sum(acc);
@@ -93,8 +93,9 @@ __global__ __launch_bounds__(1024) void k_raw_level(const uint4 *raw, long long 
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             if (FMT == IQA_FMT_S16) {
-                const float a = static_cast<float>(static_cast<short>(w[k] & 0xFFFF)), b = static_cast<float>(static_cast<short>(w[k] >> 16));
-                acc += static_cast<double>(a * a + b * b);
+                // exact: the two squares in integers (2 * 32768^2 = 2^31 fits 32 unsigned bits); float32 squares round at full scale
+                const int a = static_cast<short>(w[k] & 0xFFFF), b = static_cast<short>(w[k] >> 16);
+                acc += static_cast<double>(static_cast<unsigned>(a * a) + static_cast<unsigned>(b * b));
             } else if (FMT == IQA_FMT_U8) {
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {

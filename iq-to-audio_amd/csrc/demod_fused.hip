@@ -96,7 +96,7 @@ __device__ __forceinline__ float src_value(float2 zc, float2 zp)
         const float im = zc.y * zp.x - zc.x * zp.y;
         return atan2f(im, re);
     } else if constexpr (SRC == S_ENV) {
-        return hypotf(zc.x, zc.y);
+        return np_abs_c64(zc.x, zc.y);  // numpy's float32 value, bit for bit (common.h)
     } else {
         return zc.x;
     }

@@ -122,3 +122,39 @@ void agc_f64(const float *x, float *y, size_t n, double target, double decay)
         y[i] = (float)((double)s * gain);
     }
 }
+
+/*
+ * The float64 statements once more with the float64 values themselves handed out (tests/scan_model.py: the per-sample
+ * oracle of the scan engine needs the value BEFORE the float32 rounding, and the AGC's gain rather than the product).
+ * Same arithmetic as dc_block_f64 / agc_f64 above, statement for statement.
+ */
+void dc_block_f64_wide(const float *x, double *y, size_t n, double r, double *x_prev_io, double *y_prev_io)
+{
+    float xp = (float)(*x_prev_io);
+    double yp = *y_prev_io;
+    const double rr = (double)(float)r;
+    for (size_t i = 0; i < n; ++i) {
+        const float diff = x[i] - xp;
+        const double out = (double)diff + rr * yp;
+        y[i] = out;
+        xp = x[i];
+        yp = out;
+    }
+    *x_prev_io = (double)xp;
+    *y_prev_io = yp;
+}
+
+/* g[i] = the gain that multiplies x[i]; held[i] = 1 where |x[i]| <= float32(1e-6) left the gain as it was */
+void agc_gain_f64(const float *x, double *g, unsigned char *held, size_t n, double target, double decay)
+{
+    const double tf = (double)(float)target, df = (double)(float)decay;
+    const float thr = (float)1e-6;
+    double gain = 1.0;
+    for (size_t i = 0; i < n; ++i) {
+        const float mag = fabsf(x[i]);
+        held[i] = !(mag > thr);
+        if (mag > thr)
+            gain += df * ((double)((float)tf / mag) - gain);
+        g[i] = gain;
+    }
+}
