@@ -518,6 +518,50 @@ int iqa_afsk_bits(const void *sign_dev, int64_t n, int32_t window, double step, 
 int iqa_afsk_frames(const void *bits_dev, int64_t nbits, const int64_t count_of[IQA_AFSK_PHASES], int32_t window, double step,
                     void *list_dev, void *slots_dev, int64_t capacity, void *counts_dev, void *stream);
 
+/* ------------------------------------------------------------------------- *
+ * CTCSS tones and DTMF digits beside the NFM demodulator (--demod nfm --tones) *
+ * ------------------------------------------------------------------------- */
+
+/* The tone banks run behind a decimator by R = floor(fs / 8000), 1 <= R <= this (8000 <= fs < 520 000). */
+#define IQA_TONES_MAX_R 64
+#define IQA_TONES_MAX_FRAME 6400  /* the longest bank frame (CTCSS at fd just below 16 kHz); it is staged in LDS */
+#define IQA_TONES_MAX_TONES 64    /* most tones of one bank call */
+#define IQA_TONES_CTCSS 50        /* tones of the CTCSS bank, as iqa_tones_decide reads it */
+#define IQA_TONES_DTMF 8          /* tones of the DTMF bank: rows 0 .. 3, columns 4 .. 7 */
+#define IQA_TONES_NONE 255        /* the code of a frame without a hit */
+/* One block of the quantiser and the triangular decimator.  With w[j] = min(j + 1, 2R - 1 - j), j = 0 .. 2R - 2:
+ *   t[n] = rint(theta[n] 4096) (int32, half-even);
+ *   u[m] = floor((sum_j w[j] t[(m + 1) R - 1 - j]) / R) (int32; floor division), t zero in front of the stream.
+ * theta_dev: float32[n] (iqa_quadrature's output), the samples at absolute indices pos .. pos + n - 1; hist_dev:
+ * int32[2R - 2], the values of t at pos - (2R - 2) .. pos - 1, oldest first, zero where the index is negative (NULL: all
+ * zeros; not read when R = 1); t_out_dev: int32[n]; u_out_dev: int32[(pos + n) / R - pos / R], the outputs m = pos / R ..
+ * (pos + n) / R - 1 that this block completes and no other (NULL is allowed where there is none).  n >= 0, pos >= 0,
+ * 1 <= R <= IQA_TONES_MAX_R.  Integer sums: u does not depend on how a stream is cut into blocks, down to one sample.
+ * Precondition: |t| <= 2^31 / R^2 everywhere (a discriminator output has |theta| <= pi, |t| <= 12 868): the weighted
+ * sum is formed in int32. */
+int iqa_tones_decimate(const void *theta_dev, int64_t n, int64_t pos, const void *hist_dev, int32_t R, void *t_out_dev,
+                       void *u_out_dev, void *stream);
+/* One tone bank over a whole stored run.  Frame i = u[i hop .. i hop + frame - 1], i = 0 .. F - 1 with F = 0 where
+ * m < frame, else (m - frame) / hop + 1 (nothing is written where F = 0).  For tone f = 0 .. ntones - 1:
+ *   I_f = sum_{k < frame} c_f[k] u[i hop + k], Q_f with s_f (exact in int64);  E_f = (I_f >> 12)^2 + (Q_f >> 12)^2;
+ *   P = sum_{k < frame} u[i hop + k]^2 (int64).
+ * u_dev: int32[m]; taps_dev: int16[ntones][2][frame] = c_f, s_f with |tap| <= 256; e_out_dev: int64[F][ntones];
+ * p_out_dev: int64[F] or NULL (not computed).  1 <= hop <= frame <= IQA_TONES_MAX_FRAME, 1 <= ntones <=
+ * IQA_TONES_MAX_TONES.  Precondition: |u| < 2^20 (iqa_tones_decimate's output is): then |I| < 2^41, E < 2^59. */
+int iqa_tones_bank(const void *u_dev, int64_t m, int32_t frame, int32_t hop, int32_t ntones, const void *taps_dev,
+                   void *e_out_dev, void *p_out_dev, void *stream);
+/* One byte per frame of each bank; IQA_TONES_NONE where the frame carries nothing.  e_ctcss_dev:
+ * int64[frames_ctcss][IQA_TONES_CTCSS]; e_dtmf_dev: int64[frames_dtmf][IQA_TONES_DTMF]; p_dev: int64[frames_dtmf];
+ * frame_dtmf: the DTMF bank's frame length; ctcss_out_dev: uint8[frames_ctcss]; dtmf_out_dev: uint8[frames_dtmf].
+ * CTCSS: k = the lowest index of the maximum, med = the 25th smallest of the 50 energies; the code is k iff
+ * (E[k] >> 6) >= med and E[k] >= 2^16.  DTMF: r, c = the lowest indices of the maxima of E[0 .. 3] and E[4 .. 7], r2, c2 the
+ * largest of the other three of each group; the code is 4 r + c iff E_r >= 8 r2, E_c >= 8 c2, E_c <= 16 E_r,
+ * E_r <= 16 E_c, E_r >= 2^16, E_c >= 2^16 and 1024 (E_r + E_c) >= frame_dtmf P.  All in int64.
+ * Precondition: 0 <= E < 2^59 for CTCSS; 0 <= E < 2^52 and 0 <= frame_dtmf P < 2^63 for DTMF (iqa_tones_bank's outputs
+ * with frame_dtmf <= 320 are).  A plane with no frames may be NULL. */
+int iqa_tones_decide(const void *e_ctcss_dev, int64_t frames_ctcss, const void *e_dtmf_dev, const void *p_dev,
+                     int64_t frames_dtmf, int32_t frame_dtmf, void *ctcss_out_dev, void *dtmf_out_dev, void *stream);
+
 /* Audio egress (the drain of AudioWriter, processing.py:433-438, without a host thread): copy nbytes from device
  * memory into MAPPED pinned host memory (hipHostMalloc / torch pin_memory) with `workgroups` small workgroups
  * (<= 0: 8), so that the copy can run beside a kernel that occupies every CU.  Both pointers 16-byte aligned. */

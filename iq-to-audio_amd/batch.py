@@ -42,6 +42,14 @@ def reject_ax25(ax25) -> None:
                          "use ProcessingPipeline / MultiChannelPipeline")
 
 
+def reject_tones(tones) -> None:
+    """Tone detection stores a run's decimated discriminator output and runs the banks at the end:
+    ``tones=True`` is a ``ValueError`` up front, as ``ax25=True`` is."""
+    if tones:
+        raise ValueError("tones=True is not supported by the resident batch runners or sharded runs: "
+                         "use ProcessingPipeline / MultiChannelPipeline")
+
+
 def _rank(precision: str) -> int:
     return _ChannelKernel.PRECISIONS.index(precision)
 
@@ -82,7 +90,7 @@ class ResidentCaptureRunner:
                  chunk: int, n_frames: int, demod_mode: str = "nfm", deemph_us: float = 300.0, agc_enabled: bool = True,
                  fmt: str = "s16", iq_order: str = "iq", mix_sign_override: int | None = None, precision: str | None = None,
                  precision_guard: float | None = None, slots: int | None = None, graph_streams: int = 1, pocsag: bool = False,
-                 ax25: bool = False):
+                 ax25: bool = False, tones: bool = False):
         """``precision``: the channelizer precision every capture starts at (default: by demodulator,
         ``processing.base_precision``); ``precision_guard``: see ``processing.PRECISION_GUARD`` (0 = off).
         ``slots``: captures in flight (output buffers; default 2).  ``submit`` of capture i first waits for capture
@@ -97,6 +105,7 @@ class ResidentCaptureRunner:
         reject_wfm([demod_mode])
         reject_pocsag(pocsag)
         reject_ax25(ax25)
+        reject_tones(tones)
         torch = D.torch_mod()
         if slots is not None:
             if slots < 2:
@@ -470,12 +479,13 @@ class ResidentBankRunner:
 
     def __init__(self, targets: list, *, sample_rate: float, n_frames: int, chunk_size: int = 1_048_576,
                  fs_ch_target: float = 96_000.0, fmt: str = "s16", iq_order: str = "iq", precision_guard: float | None = None,
-                 pocsag: bool = False, ax25: bool = False):
+                 pocsag: bool = False, ax25: bool = False, tones: bool = False):
         """``targets``: dicts with ``freq_offset``, and optionally ``bandwidth`` (12 500), ``demod_mode`` ("nfm"),
         ``deemph_us`` (300), ``agc_enabled`` (True), ``mix_sign`` (None = probe), ``precision`` (None = by demodulator)."""
         reject_wfm([t.get("demod_mode") for t in targets])
         reject_pocsag(pocsag)
         reject_ax25(ax25)
+        reject_tones(tones)
         torch = D.torch_mod()
         if not targets:
             raise ValueError("at least one target is required")
@@ -640,7 +650,7 @@ class ResidentBankRunner:
 
 def demodulate_sharded(targets: list, *, sample_rate: float, n_frames: int, axis: str, capture=None, captures=None,
                        chunk_size: int = 1_048_576, fmt: str = "s16", iq_order: str = "iq", pocsag: bool = False,
-                       ax25: bool = False):
+                       ax25: bool = False, tones: bool = False):
     """The N-GPU form of :class:`ResidentBankRunner` (one process per GPU under ``torch.distributed.run``; SURVEY.md
     section 8(e)), on either axis:
 
@@ -659,6 +669,7 @@ def demodulate_sharded(targets: list, *, sample_rate: float, n_frames: int, axis
     reject_wfm([t.get("demod_mode") for t in targets])
     reject_pocsag(pocsag)
     reject_ax25(ax25)
+    reject_tones(tones)
     torch = D.torch_mod()
     if axis not in ("channels", "captures"):
         raise ValueError("axis must be 'channels' or 'captures'")

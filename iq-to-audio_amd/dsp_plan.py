@@ -618,6 +618,62 @@ def plan_afsk(fs_channel: float) -> AfskPlan:
     return AfskPlan(fs, sps, L, sps / 8.0, taps)
 
 
+# ---- CTCSS / DTMF plan (--demod nfm --tones) --------------------------------
+
+TONES_RATE = 8000.0  # the tone banks run at fd = fs / floor(fs / 8000), in [8000, 16000)
+TONES_MAX_R = 64  # IQA_TONES_MAX_R
+TONES_THETA_BITS = 12  # t = rint(theta 2^12)
+TONES_TAP_SCALE = 256.0
+TONES_NONE = 255  # IQA_TONES_NONE
+CTCSS_TONES = (67.0, 69.3, 71.9, 74.4, 77.0, 79.7, 82.5, 85.4, 88.5, 91.5, 94.8, 97.4, 100.0, 103.5, 107.2, 110.9, 114.8, 118.8, 123.0,
+               127.3, 131.8, 136.5, 141.3, 146.2, 151.4, 156.7, 159.8, 162.2, 165.5, 167.9, 171.3, 173.8, 177.3, 179.9, 183.5, 186.2,
+               189.9, 192.8, 196.6, 199.5, 203.5, 206.5, 210.7, 218.1, 225.7, 229.1, 233.6, 241.8, 250.3, 254.1)
+DTMF_TONES = (697.0, 770.0, 852.0, 941.0, 1209.0, 1336.0, 1477.0, 1633.0)  # rows, then columns
+DTMF_KEYS = "123A456B789C*0#D"  # the key of (row r, column c) is DTMF_KEYS[4 r + c]
+CTCSS_HOP_S, DTMF_HOP_S = 0.2, 0.01  # a frame is two hops
+
+
+def _tone_taps(tones, n: int, fd: float) -> np.ndarray:
+    k = np.arange(n, dtype=np.float64)
+    rows = [[np.rint(TONES_TAP_SCALE * np.cos(2.0 * np.pi * f * k / fd)), np.rint(TONES_TAP_SCALE * np.sin(2.0 * np.pi * f * k / fd))]
+            for f in tones]
+    taps = np.ascontiguousarray(np.array(rows).astype(np.int16))
+    taps.setflags(write=False)
+    return taps
+
+
+@dataclass(frozen=True)
+class TonesPlan:
+    fs: float
+    R: int  # floor(fs / 8000): the decimation in front of the banks
+    fd: float  # fs / R (float64)
+    Hd: int  # DTMF hop, rint(0.01 fd)
+    Nd: int  # DTMF frame, 2 Hd
+    Hc: int  # CTCSS hop, rint(0.2 fd)
+    Nc: int  # CTCSS frame, 2 Hc
+    ctcss_taps: np.ndarray  # int16[50, 2, Nc]: c_f, s_f
+    dtmf_taps: np.ndarray  # int16[8, 2, Nd]
+
+    def frames(self, n_frame: int, hop: int, m: int) -> int:
+        """How many frames of a bank fit ``m`` decimated samples."""
+        return 0 if m < n_frame else (m - n_frame) // hop + 1
+
+
+@functools.lru_cache(maxsize=16)
+def plan_tones(fs_channel: float) -> TonesPlan:
+    """The tone detectors' constants at channel rate ``fs_channel``; ``ValueError`` outside 8000 <= fs < 520 000."""
+    fs = float(fs_channel)
+    if not math.isfinite(fs) or fs <= 0.0:
+        raise ValueError("the channel rate must be positive")
+    R = int(math.floor(fs / TONES_RATE))
+    if R < 1 or R > TONES_MAX_R:
+        raise ValueError(f"tone detection decimates by floor(fs / 8000), which must be 1 to {TONES_MAX_R}; a channel rate of {fs:.0f} Hz "
+                         f"gives {R} (--fs-ch from 8 000 to below 520 000)")
+    fd = fs / R
+    Hd, Hc = int(np.rint(DTMF_HOP_S * fd)), int(np.rint(CTCSS_HOP_S * fd))
+    return TonesPlan(fs, R, fd, Hd, 2 * Hd, Hc, 2 * Hc, _tone_taps(CTCSS_TONES, 2 * Hc, fd), _tone_taps(DTMF_TONES, 2 * Hd, fd))
+
+
 # ---- 48 kHz resampler plan (build-defined spec; see DESIGN.md "48 kHz stage") -----------------
 
 RS_ZERO_CROSSINGS = 16

@@ -36,6 +36,7 @@ from .decoders import create_decoder
 from .decoders.ax25 import AfskCore, parse_frames as ax25_parse_frames
 from .decoders.pocsag import PocsagCore, parse_batches as pocsag_parse_batches
 from .decoders.rds import RdsCore, result_from as rds_result_from
+from .decoders.tones import TonesCore
 from .decoders.wfm import WfmStereoCore, stereo_matrix
 from .dsp_plan import design_channel_filter, tune_chunk_size  # noqa: F401  (re-exported API)
 from .progress import PhaseState, ProgressSink, ProgressTracker
@@ -561,9 +562,14 @@ class ChannelDemod:
     ``ax25=True`` (nfm only): likewise ``iqa_quadrature`` with a third ``prev`` and
     ``iqa_afsk_correlate`` per block; ``ax25_finish`` reads the stored slicer plane into bit streams, walks the HDLC frames
     and parses them (an ``Ax25Result``, or ``None`` without a frame).  Off, no AFSK entry point is called.
+
+    ``tones=True`` (nfm only): likewise ``iqa_quadrature`` with a ``prev`` of its own and
+    ``iqa_tones_decimate`` per block; ``tones_finish`` runs the CTCSS and DTMF banks and the decisions over the stored run
+    and parses the two code planes (a ``TonesResult``, or ``None`` without an event).  Off, no tone entry point is called.
     """
 
-    def __init__(self, mode: str, fs_channel: float, *, deemph_us: float, agc_enabled: bool, pocsag: bool = False, ax25: bool = False):
+    def __init__(self, mode: str, fs_channel: float, *, deemph_us: float, agc_enabled: bool, pocsag: bool = False, ax25: bool = False,
+                 tones: bool = False):
         self.decoder = create_decoder(mode, deemph_us=deemph_us, agc_enabled=agc_enabled)
         self.decoder.setup(fs_channel)
         self.params = self.decoder.fused_params()
@@ -579,6 +585,12 @@ class ChannelDemod:
                 raise ValueError("ax25=True needs an nfm target: AX.25 here is Bell-202 AFSK on a narrowband FM channel (--demod nfm)")
             self.afsk_core = AfskCore(P.plan_afsk(fs_channel))  # (ValueError where 1200 baud does not fit the channel rate)
             self._afsk_prev = D.from_numpy(np.array([1 + 0j], dtype=np.complex64))
+        self.tones_core = None
+        if tones:
+            if self.params.mode != N.DEMOD_MODE["nfm"]:
+                raise ValueError("tones=True needs an nfm target: CTCSS and DTMF ride on a narrowband FM voice channel (--demod nfm)")
+            self.tones_core = TonesCore(P.plan_tones(fs_channel))  # (ValueError where the channel rate is outside 8 000 .. 520 000)
+            self._tones_prev = D.from_numpy(np.array([1 + 0j], dtype=np.complex64))
         self._needs_scratch = self.params.mode in (N.DEMOD_MODE["usb"], N.DEMOD_MODE["lsb"]) and bool(self.params.agc_enabled)
         self.chunk_sumsq: list = []  # (device float64[n_chunks*8], counts)
         self._blk = None  # one device block: [state 32 B | peak 4 B (+pad to 64) | sumsq n_chunks*8 f64]
@@ -612,6 +624,9 @@ class ChannelDemod:
         if self.afsk_core is not None:
             self.afsk_core.reset()
             self._afsk_prev = D.from_numpy(np.array([1 + 0j], dtype=np.complex64))
+        if self.tones_core is not None:
+            self.tones_core.reset()
+            self._tones_prev = D.from_numpy(np.array([1 + 0j], dtype=np.complex64))
         if self._fresh and not force:  # (force: a step being captured into a graph must not depend on what ran before it)
             return
         # nothing is copied: the next ``process`` starts from the initial state by itself and clears the peak and the
@@ -664,6 +679,14 @@ class ChannelDemod:
             theta = D.empty(n, "float32")
             N.call("iqa_quadrature", N.ptr(z_dev), c_int64(n), N.ptr(self._afsk_prev), N.ptr(theta), N.stream_ptr())
             self.afsk_core.process(theta)
+        if self.tones_core is not None:
+            theta = D.empty(n, "float32")
+            N.call("iqa_quadrature", N.ptr(z_dev), c_int64(n), N.ptr(self._tones_prev), N.ptr(theta), N.stream_ptr())
+            self.tones_core.process(theta)
+
+    def tones_finish(self):
+        """The run's ``TonesResult`` (``None`` without an event, or with tones off)."""
+        return None if self.tones_core is None else self.tones_core.result()
 
     def ax25_finish(self):
         """The run's ``Ax25Result`` (``None`` without a frame, or with ax25 off)."""
@@ -955,7 +978,7 @@ class ProcessingPipeline:
     #: frames per device block (rounded down to whole chunks); 64 Mi frames = 256 MiB of int16 I/Q
     block_frames_target = 64 * 1024 * 1024
 
-    def __init__(self, config: ProcessingConfig, *, rds: bool = False, pocsag: bool = False, ax25: bool = False):
+    def __init__(self, config: ProcessingConfig, *, rds: bool = False, pocsag: bool = False, ax25: bool = False, tones: bool = False):
         self.config = config
         if rds and (config.demod_mode or "").lower() != "wfm":
             raise ValueError("rds=True needs a wfm target: RDS rides on a broadcast FM multiplex (--demod wfm)")
@@ -963,6 +986,8 @@ class ProcessingPipeline:
             raise ValueError("pocsag=True needs an nfm target: POCSAG is 2-FSK on a narrowband FM channel (--demod nfm)")
         if ax25 and (config.demod_mode or "").lower() not in ("nfm", "fm"):
             raise ValueError("ax25=True needs an nfm target: AX.25 here is Bell-202 AFSK on a narrowband FM channel (--demod nfm)")
+        if tones and (config.demod_mode or "").lower() not in ("nfm", "fm"):
+            raise ValueError("tones=True needs an nfm target: CTCSS and DTMF ride on a narrowband FM voice channel (--demod nfm)")
         self._cancelled = False
         self._resolved_chunk_size: int | None = None
         self.chunk_rms_dbfs: list[float] = []
@@ -979,6 +1004,8 @@ class ProcessingPipeline:
         self.pocsag = None  # after run(): the target's PocsagResult (None without a kept sync, or with pocsag off)
         self.ax25_enabled = bool(ax25)  # --ax25: decode AX.25 over Bell-202 AFSK beside nfm
         self.ax25 = None  # after run(): the target's Ax25Result (None without a frame, or with ax25 off)
+        self.tones_enabled = bool(tones)  # --tones: detect CTCSS and DTMF beside nfm
+        self.tones = None  # after run(): the target's TonesResult (None without an event, or with tones off)
 
     def cancel(self) -> None:
         self._cancelled = True
@@ -1006,7 +1033,8 @@ class ProcessingPipeline:
 
     def run(self, progress_sink: ProgressSink | None = None) -> ProcessingResult:
         """One target frequency: a :class:`MultiChannelPipeline` with a single channel."""
-        multi = MultiChannelPipeline([self.config], _owner=self, rds=self.rds_enabled, pocsag=self.pocsag_enabled, ax25=self.ax25_enabled)
+        multi = MultiChannelPipeline([self.config], _owner=self, rds=self.rds_enabled, pocsag=self.pocsag_enabled, ax25=self.ax25_enabled,
+                                     tones=self.tones_enabled)
         self._multi = multi
         if self._cancelled:
             multi.cancel()
@@ -1034,11 +1062,13 @@ class _Target:
             self.demod = WfmDemod(fs_channel, deemph_us=cfg.deemph_us, rds=bool(getattr(owner, "rds_enabled", False)))
         else:
             self.demod = ChannelDemod(cfg.demod_mode, fs_channel, deemph_us=cfg.deemph_us, agc_enabled=cfg.agc_enabled,
-                                      pocsag=bool(getattr(owner, "pocsag_enabled", False)), ax25=bool(getattr(owner, "ax25_enabled", False)))
+                                      pocsag=bool(getattr(owner, "pocsag_enabled", False)), ax25=bool(getattr(owner, "ax25_enabled", False)),
+                                      tones=bool(getattr(owner, "tones_enabled", False)))
         self.stereo = None  # wfm: the run's stereo decision (finish)
         self.rds = None  # wfm with rds: the station's RdsResult (finish)
         self.pocsag = None  # nfm with pocsag: the target's PocsagResult (finish)
         self.ax25 = None  # nfm with ax25: the target's Ax25Result (finish)
+        self.tones = None  # nfm with tones: the target's TonesResult (finish)
         if cfg.iq_order not in N.ORDER:
             raise ValueError(f"Unsupported iq_order '{cfg.iq_order}'")
         self.chan = None
@@ -1175,6 +1205,10 @@ class _Target:
             self.ax25 = self.owner.ax25 = self.demod.ax25_finish()
             if self.ax25 is not None:
                 LOG.info("AX.25: %d frame(s), %d CRC-passing candidate(s).", len(self.ax25.frames), self.ax25.crc_ok)
+        if self.demod.tones_core is not None:
+            self.tones = self.owner.tones = self.demod.tones_finish()
+            if self.tones is not None:
+                LOG.info("Tones: %d CTCSS event(s), %d DTMF digit(s).", len(self.tones.ctcss), len(self.tones.dtmf))
 
 
 class MultiChannelPipeline:
@@ -1188,7 +1222,7 @@ class MultiChannelPipeline:
     ``configs`` must agree on the input file and its interpretation.
     """
 
-    def __init__(self, configs: list, _owner=None, *, rds: bool = False, pocsag: bool = False, ax25: bool = False):
+    def __init__(self, configs: list, _owner=None, *, rds: bool = False, pocsag: bool = False, ax25: bool = False, tones: bool = False):
         if not configs:
             raise ValueError("at least one ProcessingConfig is required")
         if len(configs) > 5 and _owner is None:
@@ -1207,12 +1241,15 @@ class MultiChannelPipeline:
             raise ValueError("pocsag=True needs nfm targets: POCSAG is 2-FSK on a narrowband FM channel (--demod nfm)")
         if ax25 and any((c.demod_mode or "").lower() not in ("nfm", "fm") for c in configs):
             raise ValueError("ax25=True needs nfm targets: AX.25 here is Bell-202 AFSK on a narrowband FM channel (--demod nfm)")
-        self.owners = [_owner] if _owner is not None else [ProcessingPipeline(c, rds=rds, pocsag=pocsag, ax25=ax25) for c in configs]
+        if tones and any((c.demod_mode or "").lower() not in ("nfm", "fm") for c in configs):
+            raise ValueError("tones=True needs nfm targets: CTCSS and DTMF ride on a narrowband FM voice channel (--demod nfm)")
+        self.owners = [_owner] if _owner is not None else [ProcessingPipeline(c, rds=rds, pocsag=pocsag, ax25=ax25, tones=tones) for c in configs]
         self._cancelled = False
         self.wfm_stereo = None  # after run(): per target, the wfm stereo decision (None for the other modes)
         self.rds = None  # after run(): per target, the RdsResult (None for non-wfm or pilot-less targets, or with rds off)
         self.pocsag = None  # after run(): per target, the PocsagResult (None without a kept sync, or with pocsag off)
         self.ax25 = None  # after run(): per target, the Ax25Result (None without a frame, or with ax25 off)
+        self.tones = None  # after run(): per target, the TonesResult (None without an event, or with tones off)
 
     def cancel(self) -> None:
         self._cancelled = True
@@ -1422,6 +1459,7 @@ class MultiChannelPipeline:
             self.rds = [t.rds for t in targets]
             self.pocsag = [t.pocsag for t in targets]
             self.ax25 = [t.ax25 for t in targets]
+            self.tones = [t.tones for t in targets]
             self.output_paths = [t.output_path for t in targets]  # where each target's audio went
             for t in targets:
                 t.owner.output_path = t.output_path
