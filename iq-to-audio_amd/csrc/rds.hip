@@ -222,9 +222,14 @@ __global__ __launch_bounds__(RDS_THREADS) void k_rds_clock_apply(const long long
         if (i < n) {
             const long long f = before + v;
             phi[i] = f;
-            const double a = __dmul_rn(static_cast<double>(j_first + i), step);
-            const double b = __dmul_rn(static_cast<double>(f), 5.6843418860808015e-14);  // 2^-44
-            psi[i] = __dmul_rn(__dadd_rn(a, b), 0.0625);
+            {
+                // three float64 operations, each rounded once: no contraction of j step + b into one fma (__dmul_rn and
+                // __dadd_rn are a plain product and sum to this compiler, and fuse)
+#pragma clang fp contract(off)
+                const double a = static_cast<double>(j_first + i) * step;
+                const double b = static_cast<double>(f) * 5.6843418860808015e-14;  // 2^-44
+                psi[i] = (a + b) * 0.0625;
+            }
         }
         carry = all;
     }

@@ -136,11 +136,11 @@ def theta_of(m: np.ndarray, fs: float) -> np.ndarray:
 # ---- the float64 oracle ------------------------------------------------------------------------------------------------
 
 
-def _strided_fir(x: np.ndarray, h: np.ndarray, step: int, chunk: int = 4096) -> np.ndarray:
-    """(h * x)[::step] of the causal zero-state convolution, by rows of the sliding window."""
+def _strided_fir(x: np.ndarray, h: np.ndarray, step: int, chunk: int = 4096, start: int = 0) -> np.ndarray:
+    """(h * x)[start::step] of the causal zero-state convolution, by rows of the sliding window."""
     L = h.size
     xp = np.concatenate([np.zeros(L - 1, dtype=x.dtype), x])
-    win = np.lib.stride_tricks.sliding_window_view(xp, L)[::step]  # win[j, i] = x[j step - (L-1) + i]
+    win = np.lib.stride_tricks.sliding_window_view(xp, L)[start::step]  # win[j, i] = x[start + j step - (L-1) + i]
     hr = h[::-1].astype(np.complex128 if np.iscomplexobj(h) or np.iscomplexobj(x) else np.float64)
     out = np.empty(win.shape[0], dtype=hr.dtype)
     for lo in range(0, win.shape[0], chunk):
@@ -148,29 +148,36 @@ def _strided_fir(x: np.ndarray, h: np.ndarray, step: int, chunk: int = 4096) -> 
     return out
 
 
-def oracle_baseband(theta: np.ndarray, fs: float) -> dict:
-    """Steps 2 and 3 up to dev: y, u at the decimated instants, dev, q (float64 from the float32 discriminator values)."""
+def oracle_baseband(theta: np.ndarray, fs: float, pos: int = 0) -> dict:
+    """Steps 2 and 3 up to dev: y, u at the decimated instants, dev, q (float64 from the float32 discriminator values).
+    ``pos`` is the absolute index of ``theta[0]``: the stream is ``theta`` with zeros in front of it, the mixer phase comes
+    from the absolute index, and the outputs are those at j >= ``j_first`` = ceil(pos / R) (element i is output j_first + i).
+    dev of the first output is 0: u in front of it is 0 (the zero prefix), as at the start of a stream."""
     plan = P.plan_rds(fs)
     w = plan.wfm
     n, d, R = theta.size, w.delay, plan.decim
+    j_first = -(-int(pos) // R)
+    first = j_first * R - int(pos)  # index into theta of the first decimated instant
     m = theta.astype(np.float64) * fs / (2.0 * math.pi * P.WFM_DEVIATION)
-    p = _strided_fir(m, w.h_pilot, R)
+    p = _strided_fir(m, w.h_pilot, R, start=first)
     mag = np.abs(p)
     u = np.where(mag < 1e-12, 0.0, p / np.where(mag < 1e-12, 1.0, mag))
     md = np.concatenate([np.zeros(d), m[: n - d]])
-    nn = np.arange(n, dtype=np.float64)
+    nn = np.arange(n, dtype=np.float64) + float(int(pos))  # absolute indices: exact in float64 below 2^53
     x = md * np.exp(-2j * np.pi * np.mod(plan.f_mix * nn, 1.0))
-    y0 = _strided_fir(x, plan.h_matched, R)
-    y = y0 * np.exp(2j * np.pi * np.mod(plan.f_mix * nn[::R], 1.0)) * np.conj(u) ** 3
+    y0 = _strided_fir(x, plan.h_matched, R, start=first)
+    y = y0 * np.exp(2j * np.pi * np.mod(plan.f_mix * nn[first::R], 1.0)) * np.conj(u) ** 3
     dev = np.zeros(u.size)
     dev[1:] = np.angle(u[1:] * np.conj(u[:-1]) * np.exp(-2j * np.pi * plan.clock_step))
     q = np.rint(dev / (2.0 * np.pi) * 2.0 ** 44).astype(np.int64)
-    return dict(plan=plan, y=y, u=u, dev=dev, q=q)
+    return dict(plan=plan, y=y, u=u, dev=dev, q=q, j_first=j_first)
 
 
-def oracle_clock(q: np.ndarray, plan) -> tuple:
+def oracle_clock(q: np.ndarray, plan, j_first: int = 0) -> tuple:
+    """Phi and psi of the outputs j_first, j_first + 1, ... (Phi starts from 0 at the first of them)."""
     phi = np.cumsum(np.asarray(q, dtype=np.int64))
-    psi = (np.arange(phi.size, dtype=np.float64) * plan.clock_step + phi.astype(np.float64) * 2.0 ** -44) / 16.0
+    j = np.arange(phi.size, dtype=np.float64) + float(int(j_first))
+    psi = (j * plan.clock_step + phi.astype(np.float64) * 2.0 ** -44) / 16.0
     return phi, psi
 
 

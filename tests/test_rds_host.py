@@ -133,6 +133,40 @@ def test_oracle_decodes_the_model_multiplex(fs, ppm, sigma):
     assert all((b - a) % 104 == 0 for a, b in zip(res.group_offsets, res.group_offsets[1:]))
 
 
+@pytest.mark.parametrize("fs", [240_000.0, 128_000.0])
+def test_oracle_baseband_at_an_absolute_position(fs):
+    """``oracle_baseband(theta, fs, pos=...)`` is the oracle of the stream with ``pos`` zeros written out in front of
+    ``theta``, restricted to j >= ceil(pos / R): the same y (to the rounding of a float64 dot product whose rows sit
+    elsewhere in the matrix: 1e-12 of rms(y)) and the same q (to one count of 2^-44 cycle, 3.6e-13 rad, where that
+    rounding moves a value across a half) -- and the same clock from the same q."""
+    plan = P.plan_rds(fs)
+    R = plan.decim
+    pos = 1000 * R + 3
+    n = (plan.j0 + 150) * R + 5
+    m, _ = M.multiplex(fs, n / fs, ppm=40.0, sigma=0.01, seed=2)
+    theta = M.theta_of(m, fs)
+    got = M.oracle_baseband(theta, fs, pos=pos)
+    whole = M.oracle_baseband(np.concatenate([np.zeros(pos, np.float32), theta]), fs)
+    j_first = -(-pos // R)
+    assert got["j_first"] == j_first == 1001 and whole["j_first"] == 0
+    assert got["y"].size == whole["y"].size - j_first == A.native.lib().iqa_rds_outputs(pos, theta.size, R)
+    assert np.all(whole["y"][: j_first - 1] == 0) and np.all(whole["q"][:j_first] == 0)
+    scale = float(np.sqrt(np.mean(np.abs(whole["y"][j_first + plan.j0 :]) ** 2)))
+    assert scale > 1e-3
+    assert np.abs(got["y"] - whole["y"][j_first:]).max() <= 1e-12 * scale
+    assert got["q"][0] == 0 and got["dev"][0] == 0.0
+    assert np.abs(got["q"] - whole["q"][j_first:]).max() <= 1
+    # a position that is a multiple of R, and the default, keep the first output at the block's first sample
+    assert M.oracle_baseband(theta, fs, pos=7 * R)["j_first"] == 7
+    same = M.oracle_baseband(theta, fs)
+    np.testing.assert_array_equal(same["y"], M.oracle_baseband(theta, fs, pos=0)["y"])
+    # the clock of outputs j_first ...: the statement on absolute j, Phi from 0
+    phi, psi = M.oracle_clock(got["q"], plan, j_first=j_first)
+    phi_w, psi_w = M.oracle_clock(np.concatenate([np.zeros(j_first, np.int64), got["q"]]), plan)
+    np.testing.assert_array_equal(phi, phi_w[j_first:])
+    np.testing.assert_array_equal(psi, psi_w[j_first:])
+
+
 # ---- the parser --------------------------------------------------------------------------------------------------------
 
 
