@@ -1,11 +1,11 @@
 """Squelch post-processing (--audio-post) on the MI355X: fixture parity with the reference, stage checks at full size,
-batching, device input, the CLI.  Reads only tests/golden/squelch.npz (made by tests/golden/gen_squelch.py)."""
+batching, device input, the CLI.  Reads only tests/golden/squelch.npz and tests/golden/squelch_edges.npz (made by
+tests/golden/gen_squelch.py)."""
 from __future__ import annotations
-
-import json
 
 import numpy as np
 import pytest
+import squelch_model as M
 
 import iq_to_audio_amd.squelch as S
 from iq_to_audio_amd import cli, iqio
@@ -13,20 +13,21 @@ from iq_to_audio_amd import cli, iqio
 pytestmark = pytest.mark.gpu
 
 
-def _cases(golden):
-    z = golden("squelch.npz")
-    for name in z["cases"]:
-        name = str(name)
-        params = json.loads(str(z[f"{name}__params"]))
-        rate = params.pop("sample_rate")
-        pcm = ((z[f"{name}__pcm_hi"].astype(np.uint16) << 8) | z[f"{name}__pcm_lo"]).view(np.int16)
-        yield name, pcm, rate, S.SquelchConfig(**params), z[f"{name}__scalars"], z[f"{name}__mask"], z[f"{name}__gain"]
+def _cases(golden, fixture):
+    """PCM16 byte planes or, where the case says so, float32 input (M.fixture_cases)."""
+    for name, x, rate, params, scalars, mask_bits, gain in M.fixture_cases(golden(fixture)):
+        yield name, x, rate, S.SquelchConfig(**params), scalars, mask_bits, gain
 
 
 def test_fixture_parity_with_the_reference(golden):
+    for fixture, least in (("squelch.npz", 9), ("squelch_edges.npz", 12)):
+        seen = _fixture_parity(golden, fixture)
+        assert seen >= least and seen == len(golden(fixture)["cases"]), fixture
+
+
+def _fixture_parity(golden, fixture):
     seen = 0
-    for name, pcm, rate, cfg, scalars, mask_bits, gain in _cases(golden):
-        x = pcm.astype(np.float32) / np.float32(32768.0)
+    for name, x, rate, cfg, scalars, mask_bits, gain in _cases(golden, fixture):
         y, floor_db, thr_db, st = S.apply_squelch(x, float(rate), cfg, return_stages=True)
         want_floor, want_thr, start, stop = scalars
         assert abs(floor_db - want_floor) <= 1e-4, (name, floor_db, want_floor)
@@ -37,7 +38,7 @@ def test_fixture_parity_with_the_reference(golden):
         if y.size:
             assert float(np.max(np.abs(y - want))) <= 1e-6, name
         # the mask may only differ where the GPU's own level is within 1e-3 dB of its threshold
-        n = pcm.shape[0]
+        n = x.shape[0]
         want_mask = np.unpackbits(mask_bits)[:n].astype(bool)
         got_mask = st["mask"].cpu().numpy()
         level = (st["level"] if cfg.method == "transient" else st["envelope_db"]).cpu().numpy()
@@ -48,7 +49,7 @@ def test_fixture_parity_with_the_reference(golden):
         print(f"{name}: {int(differ.sum())} mask samples differ (all within 1e-3 dB of the threshold)")
         assert int(differ.sum()) == 0, name
         seen += 1
-    assert seen >= 9
+    return seen
 
 
 def _synthetic(rate=48000, secs=60.0, channels=2, seed=7):
