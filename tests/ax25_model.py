@@ -150,16 +150,21 @@ def plan(fs: float) -> dict:
     return dict(fs=float(fs), sps=sps, L=L, step=sps / 8.0, taps=taps)
 
 
-def energies(t, pl) -> dict:
-    """Step 2 -> {1200: E, 2200: E} (int64), and the int32 range check of the correlator sums."""
+def correlator_sums(t, pl) -> dict:
+    """Step 2 -> {1200: (I, Q), 2200: (I, Q)} (int64), and the int32 range check of the sums."""
     t = np.asarray(t, dtype=np.int64)
     out = {}
     for f, (c, s) in pl["taps"].items():
         i = np.convolve(t, c)[: t.size]
         q = np.convolve(t, s)[: t.size]
         assert max(np.abs(i).max(initial=0), np.abs(q).max(initial=0)) < 2 ** 31
-        out[f] = (i * i + q * q) >> 4
+        out[f] = (i, q)
     return out
+
+
+def energies(t, pl) -> dict:
+    """Step 2 -> {1200: E, 2200: E} (int64)."""
+    return {f: (i * i + q * q) >> 4 for f, (i, q) in correlator_sums(t, pl).items()}
 
 
 def sign_plane(E) -> np.ndarray:
@@ -310,3 +315,74 @@ def oracle(theta=None, fs: float = 96_000.0, *, t=None) -> dict:
 
 def tnc2(frame: dict) -> str:
     return f"{frame['source']}>{','.join([frame['dest']] + list(frame['path']))}:{frame['info']}"
+
+
+# ---- crafted inputs for the edge-shape tests (tests/test_ax25_shapes_host.py, tests/test_gpu_ax25_shapes.py) -------------
+
+T_PI = 12_868  # rint(float32(pi) 4096): the largest |t| a discriminator produces
+EDGE_RATES = (9_600.0, 12_600.0, 97_200.0, 100_800.0)  # L 8 (step 1), L 10 (sps 10.5, step 21/16), L 81, L 84 (step 10.5)
+TIE_RATES = (12_600.0, 97_200.0, 100_800.0)  # (at step 10.125 phase 4 is a tie: 4 x 10.125 = 40.5)
+EDGE_WINDOWS = (8, 9, 15, 16, 17, 393, 399, 400)
+EDGE_LENGTHS = (1, 7, 8, 9, 15, 2047, 2048, 2049, 2055)
+EDGE_FRAME = ("N0CALL-7", "APRS", ["WIDE1-1*", "WIDE2-1"], "!4903.50N/07201.75W-edge rates")
+
+
+def edge_stream(fs: float) -> np.ndarray:
+    return modulate(hdlc_bits([ui_frame(*EDGE_FRAME)]), fs, sigma=0.05, seed=3)
+
+
+def tie_instants(pl, n: int) -> list:
+    """[(i, p)] whose product (8 i + p) step lies exactly on a half and whose instant is inside n samples."""
+    out = []
+    for p in range(PHASES):
+        i = np.arange(instants(pl, p, n).size, dtype=np.float64)
+        x = (8.0 * i + p) * pl["step"]
+        out += [(int(k), p) for k in np.nonzero(x - np.floor(x) == 0.5)[0]]
+    return out
+
+
+def crafted_theta(L: int, n: int, seed: int) -> np.ndarray:
+    """float32[n] over [-pi, pi] at fs = 1200 L: random values, and (where n has room) two stretches of 2 L samples of a
+    full-scale square wave pi sign(cos(2 pi f k / fs)), f = 1200 and f = 2200: the correlators' largest sums."""
+    rng = np.random.default_rng(seed)
+    pi32 = np.float32(np.pi)
+    th = np.clip(rng.uniform(-np.pi, np.pi, n).astype(np.float32), -pi32, pi32)
+    k = np.arange(2 * L, dtype=np.float64)
+    at = 100
+    for f in (MARK, SPACE):
+        if at + 2 * L <= n:
+            th[at : at + 2 * L] = np.where(np.cos(2.0 * np.pi * f * k / (1200.0 * L)) >= 0.0, pi32, -pi32)
+        at += 2 * L + 55
+    return th
+
+
+def crafted_history(L: int, seed: int) -> np.ndarray:
+    """int32[L - 1] with |v| <= T_PI, both extremes present."""
+    h = np.random.default_rng(seed).integers(-T_PI, T_PI + 1, size=L - 1).astype(np.int32)
+    h[0], h[-1] = T_PI, -T_PI
+    return h
+
+
+def correlate_block(theta, hist, pl) -> tuple:
+    """What ``iqa_afsk_correlate`` owes for one block: (t, {f: E}, sign, {f: (I, Q)})."""
+    t = quantise(theta)
+    front = np.zeros(pl["L"] - 1, dtype=np.int64) if hist is None else np.asarray(hist, dtype=np.int64)
+    assert front.size == pl["L"] - 1
+    sums = {f: (i[front.size :], q[front.size :]) for f, (i, q) in correlator_sums(np.concatenate([front, t.astype(np.int64)]), pl).items()}
+    E = {f: (i * i + q * q) >> 4 for f, (i, q) in sums.items()}
+    return t, E, sign_plane(E), sums
+
+
+def bits_plane(sign, pl, nbits: int) -> np.ndarray:
+    """What ``iqa_afsk_bits`` owes: uint8[24, nbits], the bit streams with zeros where a bit's instant is beyond the plane."""
+    out = np.zeros((len(GAINS) * PHASES, nbits), dtype=np.uint8)
+    for v, (b, _at) in enumerate(bit_streams(sign, pl)):
+        assert b.size <= nbits
+        out[v, : b.size] = b
+    return out
+
+
+def bits_case(pl, i: int = 37, p: int = 3, seed: int = 0) -> tuple:
+    """(plane, n): a random slicer plane (bytes 0 .. 7) whose last sample is the instant of bit i at phase p."""
+    n = int(pl["L"] - 1 + np.rint((8.0 * i + p) * pl["step"])) + 1
+    return np.random.default_rng(seed).integers(0, 8, size=n).astype(np.uint8), n

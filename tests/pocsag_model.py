@@ -307,3 +307,140 @@ def triples(messages) -> list:
     """(address, function, text) of dict or dataclass messages."""
     get = (lambda m, k: m[k]) if messages and isinstance(messages[0], dict) else getattr
     return [(get(m, "address"), get(m, "function"), get(m, "text")) for m in messages]
+
+
+# ---- crafted inputs for the edge-shape tests (tests/test_pocsag_shapes_host.py, tests/test_gpu_pocsag_shapes.py) ---------
+
+T_PI = 3_294_199  # rint(float32(pi) 2^20): the largest |t| a discriminator produces
+EDGE_RATES = {  # fs -> (bauds skipped, {baud: offsets i of 545 whose i sps is a half-even tie})
+    4_096.0: ([1200, 2400], {512: 0}),
+    9_600.0: ([2400], {512: 136, 1200: 0}),
+    19_200.0: ([], {512: 272, 1200: 0, 2400: 0}),
+    96_600.0: ([], {512: 9, 1200: 272, 2400: 136}),
+    196_608.0: ([], {512: 0, 1200: 0, 2400: 0}),
+    196_609.0: ([512], {1200: 0, 2400: 0}),
+    921_600.0: ([512, 1200], {2400: 0}),
+}
+EDGE_MESSAGES = [(424242, 0, "0123456789"), (77, 1, "ok")]
+
+
+def tie_count(sps: float) -> int:
+    """How many of the 545 products i sps lie on a half: rint rounds those to even."""
+    frac = np.mod(np.arange(545, dtype=np.float64) * sps, 1.0)
+    return int((np.abs(frac - 0.5) < 1e-12).sum())
+
+
+def edge_stream(fs: float) -> np.ndarray:
+    """One transmission of EDGE_MESSAGES (one batch) per baud that fits ``fs``, behind one another."""
+    bits = transmission_bits(EDGE_MESSAGES)
+    parts = []
+    for baud in BAUDS:
+        if baud_plan(fs, baud) is not None:
+            pad = int(3 * fs / baud) + 50
+            parts.append(modulate(bits, fs, baud, sigma=0.05, seed=baud, lead=pad, tail=pad))
+    return np.concatenate(parts)
+
+
+def crafted_theta(n: int, l_max: int, seed: int) -> np.ndarray:
+    """float32[n] over [-pi, pi]: random values, every fourth one of the form (k + 0.5) / 2^20 (a tie of the quantiser),
+    and, where n has room for them, 2 l_max samples held at +pi and 2 l_max at -pi (the integrators' full scale)."""
+    rng = np.random.default_rng(seed)
+    pi32 = np.float32(np.pi)
+    th = np.clip(rng.uniform(-np.pi, np.pi, n).astype(np.float32), -pi32, pi32)
+    k = rng.integers(-T_PI + 1, T_PI - 1, size=n)
+    ties = ((k.astype(np.float64) + 0.5) / 2.0 ** 20).astype(np.float32)
+    assert np.array_equal(ties.astype(np.float64) * 2.0 ** 20, k + 0.5)  # exact in float32
+    th[::4] = ties[::4]
+    if n >= 100 + 4 * l_max:
+        th[50 : 50 + 2 * l_max] = pi32
+        th[100 + 2 * l_max : 100 + 4 * l_max] = -pi32
+    return th
+
+
+def crafted_history(hist_len: int, seed: int) -> np.ndarray:
+    """int32[hist_len] with |v| <= T_PI, the last third held at +T_PI."""
+    rng = np.random.default_rng(seed)
+    h = rng.integers(-T_PI, T_PI + 1, size=hist_len).astype(np.int32)
+    h[hist_len - hist_len // 3 :] = T_PI
+    return h
+
+
+def integrate_block(theta, hist, hist_len: int, windows) -> tuple:
+    """What ``iqa_pocsag_integrate`` owes for one block: t and, per window, S (None where the window is 0)."""
+    t = quantise(theta)
+    front = np.zeros(hist_len, dtype=np.int64) if hist is None else np.asarray(hist, dtype=np.int64)
+    assert front.size == hist_len
+    joined = np.concatenate([front, t.astype(np.int64)])
+    return t, [None if L == 0 else integrate(joined, L)[hist_len:] for L in windows]
+
+
+def word_levels(word: int, amplitude: int = 1000, inverted: bool = False) -> list:
+    """The 32 integrator levels of a word, first bit first: a 1 is -amplitude (x < 0), ``inverted`` swaps the signs."""
+    sign = -1 if inverted else 1
+    return [sign * (-amplitude if (word >> k) & 1 else amplitude) for k in range(31, -1, -1)]
+
+
+def crafted_plane(bp, starts, levels, n: int | None = None, tail: int = 40) -> np.ndarray:
+    """An integrator plane built straight from bit levels: for every start a and its list of levels, level i is held over
+    [a + off[i], a + off[i + 1]); zeros everywhere else.  Every position of the first bit period then sees the same 32
+    values: a plateau of candidates with identical energy.  int32[n] (default: ``tail`` zeros behind the last level)."""
+    off = bp["off"]
+    size = max(a + int(off[len(lv)]) for a, lv in zip(starts, levels)) + tail
+    S = np.zeros(size, dtype=np.int32)
+    for a, lv in zip(starts, levels):
+        for i, v in enumerate(lv):
+            S[a + int(off[i]) : a + int(off[i + 1])] = v
+    if n is not None:
+        S = S[:n].copy() if n <= size else np.concatenate([S, np.zeros(n - size, dtype=np.int32)])
+    return S
+
+
+def flipped(word: int, positions) -> int:
+    """``word`` with the bits at ``positions`` (counted from the first transmitted bit) inverted."""
+    for p in positions:
+        word ^= 1 << (31 - p)
+    return word
+
+
+def error_words(word: int, triples: int = 500, seed: int = 7) -> dict:
+    """Damaged copies of one codeword: all 32 single and all 496 double errors, and ``triples`` distinct triple errors."""
+    from itertools import combinations
+
+    rng = np.random.default_rng(seed)
+    all3 = list(combinations(range(32), 3))
+    pick = rng.choice(len(all3), size=triples, replace=False)
+    return dict(clean=[word], single=[flipped(word, (a,)) for a in range(32)],
+                double=[flipped(word, c) for c in combinations(range(32), 2)],
+                triple=[flipped(word, all3[k]) for k in sorted(pick.tolist())])
+
+
+def batch_plane(bp, words, lead: int = 40, gap: int = 100, amplitude: int = 1000) -> tuple:
+    """``words`` in batches of 16 (the last one filled with idle words), each behind its own sync word, ``gap`` zeros between
+    batches -> (plane, starts, batches)."""
+    words = list(words) + [IDLE] * (-len(words) % 16)
+    batches = [words[i : i + 16] for i in range(0, len(words), 16)]
+    span = int(bp["off"][544]) + gap
+    starts = [lead + k * span for k in range(len(batches))]
+    levels = [sum((word_levels(w, amplitude) for w in [SYNC] + b), []) for b in batches]
+    return crafted_plane(bp, starts, levels), starts, batches
+
+
+def eye_gate_flip(bp, amplitude: int, lead: int = 40) -> tuple:
+    """Shrinks the level of the sync word's first bit from ``amplitude`` downwards until the model drops the sync ->
+    (the last level kept, the plane at it, the plane one below), or None if the sync is never dropped."""
+    base = word_levels(SYNC, amplitude)
+
+    def plane(level):
+        return crafted_plane(bp, [lead], [[level] + base[1:]])
+
+    for level in range(amplitude, 0, -1):
+        if not sync_search(plane(level - 1), bp):
+            return (level, plane(level), plane(level - 1)) if sync_search(plane(level), bp) else None
+    return None
+
+
+def eye_gate_terms(S, bp, n0: int) -> tuple:
+    """(128 min |x_i|, E) at position n0."""
+    v = np.asarray(S, dtype=np.int64)[n0 + bp["off"][:32]]
+    x = 32 * v - v.sum()
+    return int(128 * np.abs(x).min()), int(np.abs(x).sum())
