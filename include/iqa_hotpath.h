@@ -562,6 +562,53 @@ int iqa_tones_bank(const void *u_dev, int64_t m, int32_t frame, int32_t hop, int
 int iqa_tones_decide(const void *e_ctcss_dev, int64_t frames_ctcss, const void *e_dtmf_dev, const void *p_dev,
                      int64_t frames_dtmf, int32_t frame_dtmf, void *ctcss_out_dev, void *dtmf_out_dev, void *stream);
 
+/* ------------------------------------------------------------------------- *
+ * ACARS beside the AM demodulator (--demod am --acars) *
+ * ------------------------------------------------------------------------- */
+
+/* A channel needs 8 <= fs / 2400 <= IQA_ACARS_MAX_SPS; the correlator window W = rint(fs / 1800) is then at most 533. */
+#define IQA_ACARS_MAX_SPS 400
+#define IQA_ACARS_MAX_WINDOW 536
+#define IQA_ACARS_PHASES 8        /* sampling phases per bit */
+#define IQA_ACARS_SLOT_BYTES 244  /* one kept block's bytes in the list: 13 .. 240 up to ETX / ETB, and the two check bytes */
+/* The largest value of a run's stored envelope.  e_dev: float32[n]; max_out_dev: float32[1], cleared by the call and then
+ * raised to max e (0 for n = 0) by an unsigned atomic maximum of the bit patterns: exact, whatever the order.
+ * Precondition: every e[i] is finite and >= 0 (iqa_envelope's output on finite input is); -0 counts as the largest value. */
+int iqa_acars_max(const void *e_dev, int64_t n, void *max_out_dev, void *stream);
+/* The quantiser, the 1800 Hz correlator and the one-bit differential detector over a whole run.  With W = window,
+ * L = delay, everything zero in front of the stream:
+ *   q[n] = rint(e[n] 2^shift) (int32, half-even; the scaling is exact);
+ *   I[n] = (sum_{k<W} c[k] q[n-k]) >> 8, Q[n] = (sum_{k<W} s[k] q[n-k]) >> 8 (int32 sums, arithmetic shift);
+ *   y[n] = cr (Q[n] I[n-L] - I[n] Q[n-L]) - sr (I[n] I[n-L] + Q[n] Q[n-L]) (int64);  same[n] = (y[n] > 0).
+ * e_dev: float32[n]; taps_dev: int16[2][W] = c, s with c[k] = rint(256 cos(2 pi 1800 k / fs)), s[k] likewise with sin;
+ * q_out_dev, i_out_dev, qq_out_dev (Q): int32[n] each or NULL; y_out_dev: int64[n] or NULL; same_out_dev: uint8[n].
+ * 1 <= window <= IQA_ACARS_MAX_WINDOW, 8 <= delay <= IQA_ACARS_MAX_SPS, |cr|, |sr| <= 256.
+ * Precondition: 0 <= q <= 2^15 everywhere, that is shift = 14 - floor(log2 max e) with iqa_acars_max's result (max e 2^shift
+ * lies in [2^14, 2^15); rounding takes its last 2^-9 up to 2^15), and
+ * |tap| <= 256: then a sum is at most 2^15 times a table's positive taps, below 2^31 for every window allowed here, and
+ * |I|, |Q| < 2^23, |y| < 2^57.  The products are formed by the 24-bit multiply, which sign-extends its operands from bit
+ * 23: outside the precondition I and Q differ from the formula above (nothing is read or written out of bounds). */
+int iqa_acars_detect(const void *e_dev, int64_t n, int32_t shift, int32_t window, int32_t delay, const void *taps_dev,
+                     int32_t cr, int32_t sr, void *q_out_dev, void *i_out_dev, void *qq_out_dev, void *y_out_dev,
+                     void *same_out_dev, void *stream);
+/* The 8 transition-symbol streams of a whole run.  same_dev: uint8[n]; step = sps / 8 (float64, made once by the caller).
+ * Phase p, symbol i = 0 .. nbits - 1: instant n_i = window - 1 + rint((8 i + p) step) (one float64 product, one rint,
+ * half-even); bits[p][i] = same[n_i]; 0 where n_i >= n (the symbol does not exist).  bits_out_dev: uint8[8][nbits]. */
+int iqa_acars_bits(const void *same_dev, int64_t n, int32_t window, double step, int64_t nbits, void *bits_out_dev, void *stream);
+/* ACARS blocks of the 8 symbol streams.  bits_dev: uint8[8][nbits]; count_of: HOST int64[8], the number of symbols of phase
+ * p that exist (<= nbits).  In phase p (g = bits[p], nb = count_of[p]) position s, 31 <= s <= nb, opens a candidate iff
+ * g[s-31 .. s-1] are the 31 transitions (1: a bit equals the one before it) inside the 32 bits of 2A 16 16 01, each byte
+ * least significant bit first.  With the bit in front of s a zero, bit i = bit i-1 xor !g[i]; bits are collected least
+ * significant first into bytes up to the first byte whose low 7 bits are 03 or 17 (ETX, ETB); a 240th byte that is neither
+ * aborts, so does the end of the stream.  A candidate that reached ETX / ETB is counted in counts[1].  It is kept iff the two
+ * bytes behind it exist, equal the CRC-16/KERMIT (reflected 0x8408, init 0, no final xor) of the bytes up to and including
+ * ETX / ETB, low byte first, and those are at least 13.  Kept blocks are appended in any order: list_dev: int64[4 capacity]
+ * = (p, s, start instant n_s, byte count with the two check bytes) each, slots_dev: uint8[capacity][IQA_ACARS_SLOT_BYTES] =
+ * the bytes, zero-filled.  counts_dev: int64[2], zeroed by the call; counts[0] counts ALL kept blocks: a count above
+ * capacity means the list is incomplete and the call must be repeated with a larger one. */
+int iqa_acars_frames(const void *bits_dev, int64_t nbits, const int64_t count_of[IQA_ACARS_PHASES], int32_t window, double step,
+                     void *list_dev, void *slots_dev, int64_t capacity, void *counts_dev, void *stream);
+
 /* Audio egress (the drain of AudioWriter, processing.py:433-438, without a host thread): copy nbytes from device
  * memory into MAPPED pinned host memory (hipHostMalloc / torch pin_memory) with `workgroups` small workgroups
  * (<= 0: 8), so that the copy can run beside a kernel that occupies every CU.  Both pointers 16-byte aligned. */

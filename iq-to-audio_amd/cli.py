@@ -97,6 +97,9 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--tones", dest="tones", action="store_true",
                    help="With --demod nfm: detect the CTCSS tone and the DTMF digits of every target, print one line per tone "
                         "event and digit sequence and write <output stem>.tones.json.")
+    p.add_argument("--acars", dest="acars", action="store_true",
+                   help="With --demod am: decode ACARS aircraft messages (2400 bit/s MSK on an airband AM channel) of every target, "
+                        "print one line per message and write <output stem>.acars.json.")
     p.add_argument("--no-agc", dest="agc_enabled", action="store_false")
     p.add_argument("--out", dest="output_path", type=Path)
     p.add_argument("--dump-iq", dest="dump_iq", type=Path)
@@ -209,6 +212,8 @@ def main(argv: list[str] | None = None) -> int:
         parser.error("--ax25 needs --demod nfm.")
     if args.tones and args.demod != "nfm":
         parser.error("--tones needs --demod nfm.")
+    if args.acars and args.demod != "am":
+        parser.error("--acars needs --demod am.")
     if args.audio_post_path:
         return run_audio_post(args)
     frequencies = list(args.target_freqs or [])
@@ -262,7 +267,7 @@ def main(argv: list[str] | None = None) -> int:
     LOG.info("=== Processing %d target(s) in one pass over %s ===", len(configs), args.input_path)
     try:
         # the reference loops whole pipelines over the targets (cli.py:683-710); here the capture is read once
-        extras = dict(rds=args.rds, pocsag=args.pocsag, ax25=args.ax25, tones=args.tones)
+        extras = dict(rds=args.rds, pocsag=args.pocsag, ax25=args.ax25, tones=args.tones, acars=args.acars)
         runner = MultiChannelPipeline(configs, **extras) if len(configs) > 1 else ProcessingPipeline(configs[0], **extras)
         results = runner.run(progress_sink=None)
         results = results if len(configs) > 1 else [results]
@@ -304,6 +309,13 @@ def main(argv: list[str] | None = None) -> int:
             for line in (res.lines() if res is not None else []):
                 print(f"{config.target_freq:.0f} Hz: {line}")
             wav.with_name(wav.stem + ".tones.json").write_text(json.dumps(None if res is None else res.to_json(), indent=1) + "\n")
+    if args.acars and not args.probe_only:
+        decoded = runner.acars if len(configs) > 1 else [runner.acars]
+        targets = runner.output_paths if len(configs) > 1 else [runner.output_path]
+        for config, res, wav in zip(configs, decoded, targets):
+            for msg in (res.messages if res is not None else []):
+                print(f"{config.target_freq:.0f} Hz: {msg.line()}")
+            wav.with_name(wav.stem + ".acars.json").write_text(json.dumps(None if res is None else res.to_json(), indent=1) + "\n")
     return 0
 
 

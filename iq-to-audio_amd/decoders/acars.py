@@ -1,0 +1,256 @@
+"""ACARS aircraft messages beside AM: 2400 bit/s audio MSK on an airband AM carrier.
+
+Per block only the envelope ``|z|`` is stored (``iqa_envelope`` into a buffer of the decoder's own).  Once per run
+``iqa_acars_max`` finds the largest envelope value, the host turns it into one power-of-two scale, ``iqa_acars_detect``
+quantises the run, correlates it with one cycle of 1800 Hz and writes one byte per sample (the last bit period advanced the
+phase: the bit stayed), ``iqa_acars_bits`` reads that plane at 8 sampling phases and ``iqa_acars_frames`` walks every
+candidate behind a ``* SYN SYN SOH`` opener and keeps those whose check sequence holds.  Every block carries its own
+check, so timing is found by search: there is no loop.  Merging and parsing are integer host logic on the kept blocks and
+run on plain numpy arrays as well (``parse_messages``)."""
+from __future__ import annotations
+
+import logging
+import math
+from ctypes import c_double, c_int32, c_int64
+from dataclasses import asdict, dataclass, field
+
+import numpy as np
+
+from .. import _dev as D
+from .. import _native as N
+from .. import dsp_plan as P
+
+LOG = logging.getLogger(__name__)
+
+SOH, STX, ETX, ETB = 0x01, 0x02, 0x03, 0x17
+CRC_POLY = 0x8408  # CRC-16/KERMIT, reflected; init 0, no final xor
+MIN_BODY, MAX_BODY = 13, 240  # bytes behind SOH up to and including ETX / ETB
+SLOT_BYTES = 244  # IQA_ACARS_SLOT_BYTES
+PHASES = P.ACARS_PHASES
+
+
+def crc16_kermit(data: bytes) -> int:
+    reg = 0
+    for byte in data:
+        reg ^= byte
+        for _ in range(8):
+            reg = (reg >> 1) ^ CRC_POLY if reg & 1 else reg >> 1
+    return reg
+
+
+def _text(data: bytes) -> str:
+    """Bit 7 stripped; anything outside printable ASCII as U+FFFD."""
+    return "".join(chr(c & 0x7F) if 0x20 <= (c & 0x7F) <= 0x7E else "�" for c in data)
+
+
+@dataclass
+class AcarsMessage:
+    time_s: float  # of the first bit behind SOH
+    mode: str
+    address: str  # the 7 characters as sent
+    registration: str  # the address without its leading dots
+    ack: str
+    label: str
+    block_id: str
+    text: str | None  # None for a block without STX; for a downlink, what follows the message number and the flight id
+    msgno: str | None  # downlinks (block id a digit): the 4 characters in front of the flight id
+    flight: str | None  # downlinks: the 6 characters behind the message number
+    more: bool  # the block ends in ETB: another block of the message follows
+    parity_errors: int  # bytes up to ETX / ETB whose parity is even
+    raw: str  # the bytes behind SOH up to ETX / ETB and the two check bytes, as hex
+    hits: int  # sampling phases that decoded it
+
+    def line(self) -> str:
+        parts = [self.address, self.label, self.block_id] + [v for v in (self.msgno, self.flight, self.text) if v]
+        return "ACARS " + " ".join(parts)
+
+
+@dataclass
+class AcarsResult:
+    messages: list = field(default_factory=list)  # AcarsMessage, in order of time
+    candidates: int = 0  # candidates behind an opener that reached ETX / ETB, over all phases
+    crc_ok: int = 0  # of those, the ones that were kept
+
+    def to_json(self) -> dict:
+        return asdict(self)
+
+
+def parse_message(raw: bytes) -> dict:
+    """One kept block (the bytes behind SOH up to ETX / ETB, then the two check bytes) -> the fields of an ``AcarsMessage``
+    but time and hits."""
+    body = bytes(raw[:-2])
+    out = dict(mode=_text(body[0:1]), address=_text(body[1:8]), ack=_text(body[8:9]), label=_text(body[9:11]), block_id=_text(body[11:12]),
+               text=None, msgno=None, flight=None, more=(body[-1] & 0x7F) == ETB,
+               parity_errors=sum(1 for c in body if bin(c).count("1") % 2 == 0), raw=bytes(raw).hex())
+    out["registration"] = out["address"].lstrip(".")
+    if len(body) > MIN_BODY and (body[12] & 0x7F) == STX:
+        text = _text(body[13:-1])
+        if out["block_id"].isdigit() and len(text) >= 10:
+            out["msgno"], out["flight"], text = text[:4], text[4:10], text[10:]
+        out["text"] = text
+    return out
+
+
+def _group_of(groups: list, raw: bytes, at: int, reach: int):
+    """The latest group with these bytes whose first start instant lies within ``reach`` of ``at``, or ``None``."""
+    for grp in reversed(groups):
+        if at - grp[0] > reach:
+            return None  # (ascending start instants: every earlier group is further back still)
+        if grp[1] == raw:
+            return grp
+    return None
+
+
+def parse_messages(plan: P.AcarsPlan, records: dict, candidates: int = 0) -> AcarsResult | None:
+    """``records``: dict(phase=[k], s=[k], start=[k], nbytes=[k], data=uint8[k, >= nbytes]) in any order (the kept list of
+    ``iqa_acars_frames``) -> the run's messages.  Integer logic only; ``None`` where no message survives."""
+    start = np.asarray(records["start"], dtype=np.int64).reshape(-1)
+    phase = np.asarray(records["phase"], dtype=np.int64).reshape(-1)
+    nbytes = np.asarray(records["nbytes"], dtype=np.int64).reshape(-1)
+    data = np.asarray(records["data"], dtype=np.uint8).reshape(start.size, -1) if start.size else np.zeros((0, 0), dtype=np.uint8)
+    res = AcarsResult(candidates=int(candidates), crc_ok=int(start.size))
+    groups: list = []  # [first start instant, bytes, hits], ascending in the first start instant
+    for k in np.lexsort((phase, start)).tolist():
+        raw, at = data[k, : int(nbytes[k])].tobytes(), int(start[k])
+        grp = _group_of(groups, raw, at, plan.L)
+        if grp is None:
+            groups.append([at, raw, 1])
+        else:
+            grp[2] += 1
+    for at, raw, hits in groups:
+        res.messages.append(AcarsMessage(time_s=at / plan.fs, hits=hits, **parse_message(raw)))
+    return res if res.messages else None
+
+
+def shift_of(emax: float) -> int:
+    """14 - floor(log2 emax) for a positive finite float: emax 2^shift lies in [2^14, 2^15)."""
+    mant, ex = math.frexp(float(emax))  # emax = mant 2^ex, 0.5 <= mant < 1
+    return 14 - (ex - 1)
+
+
+class AcarsCore:
+    """Per-stream device state: the run's stored envelope (one float32 device tensor per block, joined by ``finish``) and
+    the absolute position.  ``keep_stages`` also stores q, I, Q and y at ``finish``, for the tests."""
+
+    def __init__(self, plan: P.AcarsPlan, *, keep_stages: bool = False):
+        self.plan = plan
+        self._taps = D.from_numpy(np.ascontiguousarray(plan.taps))
+        self.keep_stages = keep_stages
+        self.pos = 0  # absolute index of the next block's first sample
+        self._e: list = []
+
+    def process(self, e) -> None:
+        """One block of the envelope (device float32[n], finite and >= 0).  The tensor is kept, not copied."""
+        n = int(e.numel())
+        if n == 0:
+            return
+        self._e.append(e)
+        self.pos += n
+
+    def joined(self):
+        if len(self._e) > 1:
+            self._e = [D.torch_mod().cat(self._e)]
+        return self._e[0] if self._e else D.empty(0, "float32")
+
+    def reset(self) -> None:
+        """Back to a stream that has seen nothing: position 0, no stored envelope."""
+        self.pos, self._e = 0, []
+
+    def _frames(self, bits, nbits: int, count_of, capacity: int, counts):
+        lst, slots = D.empty(4 * capacity, "int64"), D.empty(SLOT_BYTES * capacity, "uint8")
+        N.call("iqa_acars_frames", N.ptr(bits), c_int64(nbits), count_of, c_int32(self.plan.W), c_double(self.plan.step), N.ptr(lst),
+               N.ptr(slots), c_int64(capacity), N.ptr(counts), N.stream_ptr())
+        return lst, slots
+
+    def finish(self, capacity: int = 64) -> dict:
+        """The stages and the kept blocks of the stored run: dict(emax, sh, phase, s, start, nbytes, data, candidates, same,
+        bits, nbits, count_of[, q, I, Q, y]), the records as numpy arrays sorted by (phase, s); ``sh`` is ``None`` and nothing
+        behind the maximum is launched where the run's envelope is all zero.  A list too short for the kept blocks is never
+        used: the search is repeated with room for all of them."""
+        plan = self.plan
+        e = self.joined()
+        n = int(e.numel())
+        peak = D.zeros(1, "float32")
+        N.call("iqa_acars_max", N.ptr(e), c_int64(n), N.ptr(peak), N.stream_ptr())
+        emax = float(peak.item())
+        empty = dict(emax=emax, sh=None, phase=np.zeros(0, np.int64), s=np.zeros(0, np.int64), start=np.zeros(0, np.int64),
+                     nbytes=np.zeros(0, np.int64), data=np.zeros((0, SLOT_BYTES), np.uint8), candidates=0, same=None, bits=None, nbits=0,
+                     count_of=[0] * PHASES)
+        if not emax > 0.0 or not math.isfinite(emax):
+            if emax != 0.0:
+                LOG.warning("ACARS: the envelope is not finite; nothing is decoded.")
+            return empty
+        sh = shift_of(emax)
+        same = D.empty(n, "uint8")
+        stages = dict(q=D.empty(n, "int32"), I=D.empty(n, "int32"), Q=D.empty(n, "int32"), y=D.empty(n, "int64")) if self.keep_stages else {}
+        N.call("iqa_acars_detect", N.ptr(e), c_int64(n), c_int32(sh), c_int32(plan.W), c_int32(plan.L), N.ptr(self._taps), c_int32(plan.cr),
+               c_int32(plan.sr), N.ptr(stages.get("q")), N.ptr(stages.get("I")), N.ptr(stages.get("Q")), N.ptr(stages.get("y")), N.ptr(same),
+               N.stream_ptr())
+        counts_of = [plan.bit_count(p, n) for p in range(PHASES)]
+        nbits = max(counts_of)
+        if nbits == 0:
+            return dict(empty, sh=sh, same=same, **stages)
+        count_of = (c_int64 * PHASES)(*counts_of)
+        bits = D.empty(PHASES * nbits, "uint8")
+        N.call("iqa_acars_bits", N.ptr(same), c_int64(n), c_int32(plan.W), c_double(plan.step), c_int64(nbits), N.ptr(bits), N.stream_ptr())
+        counts = D.zeros(2, "int64")
+        lst, slots = self._frames(bits, nbits, count_of, capacity, counts)
+        kept, reached = (int(v) for v in counts.cpu().numpy())
+        if kept > capacity:
+            lst, slots = self._frames(bits, nbits, count_of, kept, counts)
+            assert int(counts[0].item()) == kept
+        entries = lst[: 4 * kept].cpu().numpy().reshape(-1, 4)
+        data = slots[: SLOT_BYTES * kept].cpu().numpy().reshape(-1, SLOT_BYTES)
+        order = np.lexsort((entries[:, 1], entries[:, 0]))
+        entries, data = entries[order], data[order]
+        return dict(emax=emax, sh=sh, phase=entries[:, 0].copy(), s=entries[:, 1].copy(), start=entries[:, 2].copy(),
+                    nbytes=entries[:, 3].copy(), data=data, candidates=reached, same=same, bits=bits, nbits=nbits, count_of=counts_of, **stages)
+
+
+class AcarsDecoder:
+    """The stage API: ``process(block)`` per block of the channel (complex: the channelizer's output, run through
+    ``iqa_envelope``; or float32: an envelope, finite and >= 0), ``finish()`` once (an ``AcarsResult``, or ``None`` without
+    a message), ``stages()`` for the tests."""
+
+    def __init__(self, rate: float, *, keep_stages: bool = True):
+        self.plan = P.plan_acars(float(rate))
+        self.core = AcarsCore(self.plan, keep_stages=keep_stages)
+        self._fin = None
+
+    def process(self, block) -> None:
+        torch = D.torch_mod()
+        is_complex = torch.is_complex(block) if D.is_tensor(block) else np.iscomplexobj(block)
+        if is_complex:
+            z = D.to_device(block, "complex64")
+            e = D.empty(int(z.numel()), "float32")
+            if z.numel():
+                N.call("iqa_envelope", N.ptr(z), c_int64(int(z.numel())), N.ptr(e), N.stream_ptr())
+        else:
+            e = D.to_device(block, "float32").clone()  # (the store keeps the tensor: the caller's may change)
+        self.core.process(e)
+        self._fin = None
+
+    def _finished(self) -> dict:
+        if self._fin is None:
+            self._fin = self.core.finish()
+        return self._fin
+
+    def finish(self) -> AcarsResult | None:
+        fin = self._finished()
+        return parse_messages(self.plan, fin, fin["candidates"])
+
+    def stages(self) -> dict:
+        """Host copies: ``e``, ``emax``, ``sh``, ``q``, ``I``, ``Q``, ``y`` (with keep_stages), ``same``, ``bits`` (8 uint8
+        arrays, each as long as its phase has symbols) and ``records`` ([(phase, s, start instant, bytes)] sorted); the
+        stages behind ``sh`` are ``None`` for an all-zero run."""
+        fin = self._finished()
+
+        def host(key):
+            return None if fin.get(key) is None else fin[key].cpu().numpy()
+
+        plane = fin["bits"].cpu().numpy().reshape(PHASES, -1) if fin["nbits"] else np.zeros((PHASES, 0), dtype=np.uint8)
+        bits = [plane[p, : fin["count_of"][p]] for p in range(PHASES)]
+        records = [(int(p), int(s), int(at), fin["data"][k, : int(nb)].tobytes())
+                   for k, (p, s, at, nb) in enumerate(zip(fin["phase"], fin["s"], fin["start"], fin["nbytes"]))]
+        return dict(e=self.core.joined().cpu().numpy(), emax=np.float32(fin["emax"]), sh=fin["sh"], q=host("q"), I=host("I"), Q=host("Q"),
+                    y=host("y"), same=host("same"), bits=bits, records=records, candidates=fin["candidates"])

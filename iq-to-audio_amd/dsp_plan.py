@@ -674,6 +674,62 @@ def plan_tones(fs_channel: float) -> TonesPlan:
     return TonesPlan(fs, R, fd, Hd, 2 * Hd, Hc, 2 * Hc, _tone_taps(CTCSS_TONES, 2 * Hc, fd), _tone_taps(DTMF_TONES, 2 * Hd, fd))
 
 
+# ---- ACARS plan (--demod am --acars) ----------------------------------------
+
+ACARS_BAUD = 2400
+ACARS_CENTRE = 1800.0  # MSK: 1200 Hz (the bit changes) and 2400 Hz (the bit stays) around it
+ACARS_MIN_SPS = 8.0  # below this eight sampling phases per bit are not distinct
+ACARS_MAX_SPS = 400  # IQA_ACARS_MAX_SPS
+ACARS_TAP_SCALE = 256.0
+ACARS_PHASES = 8  # IQA_ACARS_PHASES
+ACARS_Q_BITS = 15  # 0 <= q <= 2^15
+
+
+@dataclass(frozen=True)
+class AcarsPlan:
+    fs: float
+    sps: float  # fs / 2400 (float64)
+    L: int  # rint(sps): the differential detector's delay
+    W: int  # rint(fs / 1800): the correlator's window, one cycle of the centre frequency
+    step: float  # sps / 8: the spacing of the sampling phases
+    taps: np.ndarray  # int16[2, W]: c, s
+    cr: int  # rint(256 cos psi), psi = 2 pi 1800 L / fs
+    sr: int  # rint(256 sin psi)
+
+    def instant(self, i, p: int):
+        """The instant of symbol ``i`` (an int or an integer array) at phase ``p``: W - 1 + rint((8 i + p) step)."""
+        return self.W - 1 + np.rint((8.0 * np.asarray(i, dtype=np.float64) + p) * self.step).astype(np.int64)
+
+    def bit_count(self, p: int, n: int) -> int:
+        """How many symbols of phase ``p`` have their instant inside a stream of ``n`` samples."""
+        i = max(int((n - self.W) / self.sps) - 2, 0)
+        while int(self.instant(i, p)) < n:
+            i += 1
+        return i
+
+
+@functools.lru_cache(maxsize=16)
+def plan_acars(fs_channel: float) -> AcarsPlan:
+    """The ACARS decoder's constants at channel rate ``fs_channel``; ``ValueError`` when 2400 bit/s does not fit it."""
+    fs = float(fs_channel)
+    if not math.isfinite(fs) or fs <= 0.0:
+        raise ValueError("the channel rate must be positive")
+    sps = fs / ACARS_BAUD
+    if sps < ACARS_MIN_SPS or sps > ACARS_MAX_SPS:
+        raise ValueError(f"ACARS at 2400 bit/s needs {ACARS_MIN_SPS:.0f} to {ACARS_MAX_SPS} samples per bit; a channel rate of {fs:.0f} Hz "
+                         f"gives {sps:.1f} (--fs-ch between 19 200 and 960 000)")
+    L, W = int(np.rint(sps)), int(np.rint(fs / ACARS_CENTRE))
+    k = np.arange(W, dtype=np.float64)
+    rows = np.stack([np.rint(ACARS_TAP_SCALE * np.cos(2.0 * np.pi * ACARS_CENTRE * k / fs)),
+                     np.rint(ACARS_TAP_SCALE * np.sin(2.0 * np.pi * ACARS_CENTRE * k / fs))])
+    # q >= 0: a correlator sum is at most 2^15 times the positive (or the negative) taps of its table: inside int32
+    assert 2 ** ACARS_Q_BITS * max(np.maximum(rows, 0).sum(axis=1).max(), -np.minimum(rows, 0).sum(axis=1).min()) < 2 ** 31
+    taps = np.ascontiguousarray(rows.astype(np.int16))
+    taps.setflags(write=False)
+    psi = 2.0 * np.pi * ACARS_CENTRE * L / fs
+    return AcarsPlan(fs, sps, L, W, sps / 8.0, taps, int(np.rint(ACARS_TAP_SCALE * np.cos(psi))), int(np.rint(ACARS_TAP_SCALE * np.sin(psi))))
+
+
 # ---- 48 kHz resampler plan (build-defined spec; see DESIGN.md "48 kHz stage") -----------------
 
 RS_ZERO_CROSSINGS = 16

@@ -36,6 +36,7 @@ from .decoders import create_decoder
 from .decoders.ax25 import AfskCore, parse_frames as ax25_parse_frames
 from .decoders.pocsag import PocsagCore, parse_batches as pocsag_parse_batches
 from .decoders.rds import RdsCore, result_from as rds_result_from
+from .decoders.acars import AcarsCore, parse_messages as acars_parse_messages
 from .decoders.tones import TonesCore
 from .decoders.wfm import WfmStereoCore, stereo_matrix
 from .dsp_plan import design_channel_filter, tune_chunk_size  # noqa: F401  (re-exported API)
@@ -566,10 +567,14 @@ class ChannelDemod:
     ``tones=True`` (nfm only): likewise ``iqa_quadrature`` with a ``prev`` of its own and
     ``iqa_tones_decimate`` per block; ``tones_finish`` runs the CTCSS and DTMF banks and the decisions over the stored run
     and parses the two code planes (a ``TonesResult``, or ``None`` without an event).  Off, no tone entry point is called.
+
+    ``acars=True`` (am only): after the fused call every block also runs ``iqa_envelope`` into a buffer
+    of the decoder's own (never the audio buffer), which is stored; ``acars_finish`` scales, detects and searches the stored
+    run and parses the kept blocks (an ``AcarsResult``, or ``None`` without a message).  Off, no ACARS entry point is called.
     """
 
     def __init__(self, mode: str, fs_channel: float, *, deemph_us: float, agc_enabled: bool, pocsag: bool = False, ax25: bool = False,
-                 tones: bool = False):
+                 tones: bool = False, acars: bool = False):
         self.decoder = create_decoder(mode, deemph_us=deemph_us, agc_enabled=agc_enabled)
         self.decoder.setup(fs_channel)
         self.params = self.decoder.fused_params()
@@ -591,6 +596,11 @@ class ChannelDemod:
                 raise ValueError("tones=True needs an nfm target: CTCSS and DTMF ride on a narrowband FM voice channel (--demod nfm)")
             self.tones_core = TonesCore(P.plan_tones(fs_channel))  # (ValueError where the channel rate is outside 8 000 .. 520 000)
             self._tones_prev = D.from_numpy(np.array([1 + 0j], dtype=np.complex64))
+        self.acars_core = None
+        if acars:
+            if self.params.mode != N.DEMOD_MODE["am"]:
+                raise ValueError("acars=True needs an am target: ACARS is audio MSK on an AM airband carrier (--demod am)")
+            self.acars_core = AcarsCore(P.plan_acars(fs_channel))  # (ValueError where 2400 bit/s does not fit the channel rate)
         self._needs_scratch = self.params.mode in (N.DEMOD_MODE["usb"], N.DEMOD_MODE["lsb"]) and bool(self.params.agc_enabled)
         self.chunk_sumsq: list = []  # (device float64[n_chunks*8], counts)
         self._blk = None  # one device block: [state 32 B | peak 4 B (+pad to 64) | sumsq n_chunks*8 f64]
@@ -627,6 +637,8 @@ class ChannelDemod:
         if self.tones_core is not None:
             self.tones_core.reset()
             self._tones_prev = D.from_numpy(np.array([1 + 0j], dtype=np.complex64))
+        if self.acars_core is not None:
+            self.acars_core.reset()
         if self._fresh and not force:  # (force: a step being captured into a graph must not depend on what ran before it)
             return
         # nothing is copied: the next ``process`` starts from the initial state by itself and clears the peak and the
@@ -683,6 +695,17 @@ class ChannelDemod:
             theta = D.empty(n, "float32")
             N.call("iqa_quadrature", N.ptr(z_dev), c_int64(n), N.ptr(self._tones_prev), N.ptr(theta), N.stream_ptr())
             self.tones_core.process(theta)
+        if self.acars_core is not None:
+            env = D.empty(n, "float32")
+            N.call("iqa_envelope", N.ptr(z_dev), c_int64(n), N.ptr(env), N.stream_ptr())
+            self.acars_core.process(env)
+
+    def acars_finish(self):
+        """The run's ``AcarsResult`` (``None`` without a message, or with acars off)."""
+        if self.acars_core is None:
+            return None
+        fin = self.acars_core.finish()
+        return acars_parse_messages(self.acars_core.plan, fin, fin["candidates"])
 
     def tones_finish(self):
         """The run's ``TonesResult`` (``None`` without an event, or with tones off)."""
@@ -978,7 +1001,8 @@ class ProcessingPipeline:
     #: frames per device block (rounded down to whole chunks); 64 Mi frames = 256 MiB of int16 I/Q
     block_frames_target = 64 * 1024 * 1024
 
-    def __init__(self, config: ProcessingConfig, *, rds: bool = False, pocsag: bool = False, ax25: bool = False, tones: bool = False):
+    def __init__(self, config: ProcessingConfig, *, rds: bool = False, pocsag: bool = False, ax25: bool = False, tones: bool = False,
+                 acars: bool = False):
         self.config = config
         if rds and (config.demod_mode or "").lower() != "wfm":
             raise ValueError("rds=True needs a wfm target: RDS rides on a broadcast FM multiplex (--demod wfm)")
@@ -988,6 +1012,8 @@ class ProcessingPipeline:
             raise ValueError("ax25=True needs an nfm target: AX.25 here is Bell-202 AFSK on a narrowband FM channel (--demod nfm)")
         if tones and (config.demod_mode or "").lower() not in ("nfm", "fm"):
             raise ValueError("tones=True needs an nfm target: CTCSS and DTMF ride on a narrowband FM voice channel (--demod nfm)")
+        if acars and (config.demod_mode or "").lower() != "am":
+            raise ValueError("acars=True needs an am target: ACARS is audio MSK on an AM airband carrier (--demod am)")
         self._cancelled = False
         self._resolved_chunk_size: int | None = None
         self.chunk_rms_dbfs: list[float] = []
@@ -1006,6 +1032,8 @@ class ProcessingPipeline:
         self.ax25 = None  # after run(): the target's Ax25Result (None without a frame, or with ax25 off)
         self.tones_enabled = bool(tones)  # --tones: detect CTCSS and DTMF beside nfm
         self.tones = None  # after run(): the target's TonesResult (None without an event, or with tones off)
+        self.acars_enabled = bool(acars)  # --acars: decode ACARS beside am
+        self.acars = None  # after run(): the target's AcarsResult (None without a message, or with acars off)
 
     def cancel(self) -> None:
         self._cancelled = True
@@ -1034,7 +1062,7 @@ class ProcessingPipeline:
     def run(self, progress_sink: ProgressSink | None = None) -> ProcessingResult:
         """One target frequency: a :class:`MultiChannelPipeline` with a single channel."""
         multi = MultiChannelPipeline([self.config], _owner=self, rds=self.rds_enabled, pocsag=self.pocsag_enabled, ax25=self.ax25_enabled,
-                                     tones=self.tones_enabled)
+                                     tones=self.tones_enabled, acars=self.acars_enabled)
         self._multi = multi
         if self._cancelled:
             multi.cancel()
@@ -1063,12 +1091,13 @@ class _Target:
         else:
             self.demod = ChannelDemod(cfg.demod_mode, fs_channel, deemph_us=cfg.deemph_us, agc_enabled=cfg.agc_enabled,
                                       pocsag=bool(getattr(owner, "pocsag_enabled", False)), ax25=bool(getattr(owner, "ax25_enabled", False)),
-                                      tones=bool(getattr(owner, "tones_enabled", False)))
+                                      tones=bool(getattr(owner, "tones_enabled", False)), acars=bool(getattr(owner, "acars_enabled", False)))
         self.stereo = None  # wfm: the run's stereo decision (finish)
         self.rds = None  # wfm with rds: the station's RdsResult (finish)
         self.pocsag = None  # nfm with pocsag: the target's PocsagResult (finish)
         self.ax25 = None  # nfm with ax25: the target's Ax25Result (finish)
         self.tones = None  # nfm with tones: the target's TonesResult (finish)
+        self.acars = None  # am with acars: the target's AcarsResult (finish)
         if cfg.iq_order not in N.ORDER:
             raise ValueError(f"Unsupported iq_order '{cfg.iq_order}'")
         self.chan = None
@@ -1209,6 +1238,10 @@ class _Target:
             self.tones = self.owner.tones = self.demod.tones_finish()
             if self.tones is not None:
                 LOG.info("Tones: %d CTCSS event(s), %d DTMF digit(s).", len(self.tones.ctcss), len(self.tones.dtmf))
+        if self.demod.acars_core is not None:
+            self.acars = self.owner.acars = self.demod.acars_finish()
+            if self.acars is not None:
+                LOG.info("ACARS: %d message(s), %d CRC-passing candidate(s).", len(self.acars.messages), self.acars.crc_ok)
 
 
 class MultiChannelPipeline:
@@ -1222,7 +1255,8 @@ class MultiChannelPipeline:
     ``configs`` must agree on the input file and its interpretation.
     """
 
-    def __init__(self, configs: list, _owner=None, *, rds: bool = False, pocsag: bool = False, ax25: bool = False, tones: bool = False):
+    def __init__(self, configs: list, _owner=None, *, rds: bool = False, pocsag: bool = False, ax25: bool = False, tones: bool = False,
+                 acars: bool = False):
         if not configs:
             raise ValueError("at least one ProcessingConfig is required")
         if len(configs) > 5 and _owner is None:
@@ -1243,13 +1277,17 @@ class MultiChannelPipeline:
             raise ValueError("ax25=True needs nfm targets: AX.25 here is Bell-202 AFSK on a narrowband FM channel (--demod nfm)")
         if tones and any((c.demod_mode or "").lower() not in ("nfm", "fm") for c in configs):
             raise ValueError("tones=True needs nfm targets: CTCSS and DTMF ride on a narrowband FM voice channel (--demod nfm)")
-        self.owners = [_owner] if _owner is not None else [ProcessingPipeline(c, rds=rds, pocsag=pocsag, ax25=ax25, tones=tones) for c in configs]
+        if acars and any((c.demod_mode or "").lower() != "am" for c in configs):
+            raise ValueError("acars=True needs am targets: ACARS is audio MSK on an AM airband carrier (--demod am)")
+        self.owners = [_owner] if _owner is not None else [ProcessingPipeline(c, rds=rds, pocsag=pocsag, ax25=ax25, tones=tones, acars=acars)
+                                                           for c in configs]
         self._cancelled = False
         self.wfm_stereo = None  # after run(): per target, the wfm stereo decision (None for the other modes)
         self.rds = None  # after run(): per target, the RdsResult (None for non-wfm or pilot-less targets, or with rds off)
         self.pocsag = None  # after run(): per target, the PocsagResult (None without a kept sync, or with pocsag off)
         self.ax25 = None  # after run(): per target, the Ax25Result (None without a frame, or with ax25 off)
         self.tones = None  # after run(): per target, the TonesResult (None without an event, or with tones off)
+        self.acars = None  # after run(): per target, the AcarsResult (None without a message, or with acars off)
 
     def cancel(self) -> None:
         self._cancelled = True
@@ -1460,6 +1498,7 @@ class MultiChannelPipeline:
             self.pocsag = [t.pocsag for t in targets]
             self.ax25 = [t.ax25 for t in targets]
             self.tones = [t.tones for t in targets]
+            self.acars = [t.acars for t in targets]
             self.output_paths = [t.output_path for t in targets]  # where each target's audio went
             for t in targets:
                 t.owner.output_path = t.output_path
