@@ -609,6 +609,46 @@ int iqa_acars_bits(const void *same_dev, int64_t n, int32_t window, double step,
 int iqa_acars_frames(const void *bits_dev, int64_t nbits, const int64_t count_of[IQA_ACARS_PHASES], int32_t window, double step,
                      void *list_dev, void *slots_dev, int64_t capacity, void *counts_dev, void *stream);
 
+/* ------------------------------------------------------------------------- *
+ * AIS beside the NFM demodulator (--demod nfm --ais) *
+ * ------------------------------------------------------------------------- */
+
+/* A channel needs 5 <= fs / 9600 <= IQA_AIS_MAX_SPS; with L = rint(fs / 9600) the pulse filter has W = 3 L - 1 <= 299 taps,
+ * and 12 868 . 256 . 299 stays inside int32. */
+#define IQA_AIS_MAX_SPS 100
+#define IQA_AIS_PHASES 8        /* sampling phases per bit */
+#define IQA_AIS_SLOT_BYTES 128  /* one kept frame's bytes in the list (a frame has 11 .. 128, FCS included: five slots) */
+/* One block of the quantiser and the pulse filter.  With W = window:
+ *   t[n] = rint(theta[n] 4096) (int32, half-even);
+ *   S[n] = sum_{k<W} taps[k] t[n-k] (int32).
+ * theta_dev: float32[n] (iqa_quadrature's output); hist_dev: int32[W - 1], the values of t in front of theta[0], oldest
+ * first (NULL: zeros); taps_dev: int16[W], |tap| <= 256 (dsp_plan.plan_ais: a Gaussian of BT 0.4 over 2 L taps convolved
+ * with L ones, scaled to a peak of 256); t_out_dev: int32[n], or NULL (not stored); s_out_dev: int32[n].
+ * 1 <= window <= 3 IQA_AIS_MAX_SPS - 1.  Integer sums: the outputs do not depend on how a stream is cut into blocks.
+ * Precondition: |t| < 2^23 everywhere, that is |theta[n]| < 2048 rad (a discriminator output has |theta| <= pi, |t| <= 12 868)
+ * and |hist_dev[i]| < 2^23, and 12 868 . sum |taps| < 2^31.  The products are formed by the 24-bit multiply, which
+ * sign-extends its operands from bit 23: outside the precondition S differs from the formula above. */
+int iqa_ais_filter(const void *theta_dev, int64_t n, const void *hist_dev, int32_t window, const void *taps_dev, void *t_out_dev,
+                   void *s_out_dev, void *stream);
+/* The 8 symbol planes of a whole run.  s_dev: int32[n] (the run's S); step = sps / 8 (float64, made once by the caller).
+ * Phase p, symbol i = 0 .. nsym - 1: instant n_i = window - 1 + rint((8 i + p) step) (one float64 product, one rint,
+ * half-even); v[p][i] = S[n_i]; 0 where n_i >= n (the symbol does not exist).  v_out_dev: int32[8][nsym]. */
+int iqa_ais_symbols(const void *s_dev, int64_t n, int32_t window, double step, int64_t nsym, void *v_out_dev, void *stream);
+/* HDLC frames of the 8 symbol planes.  v_dev: int32[8][nsym]; count_of: HOST int64[8], the number of symbols of phase p that
+ * exist (<= nsym).  In phase p (v = v[p], nb = count_of[p]) position s, 24 <= s <= nb, has the level sum
+ * v[s-24] + .. + v[s-9] (int64, sixteen training symbols); under it m_i = (16 v_i > sum) and b_i = (m_i == m_{i-1}).  s opens a
+ * candidate iff b[s-8 .. s-1] = 0,1,1,1,1,1,1,0 and the fourteen bits b[s-22 .. s-9] alternate (either way round).  From s,
+ * under the same sum, bits are collected least significant first into bytes; a 0 after five consecutive 1s is dropped; the
+ * sixth consecutive 1 ends the walk: a closing flag iff the next bit exists and is 0 and exactly 6 bits of the current byte
+ * are collected, an abort otherwise; a 129th byte aborts; so does the end of the stream.  A closed candidate of >= 11 bytes
+ * is counted in counts[1]; it is kept iff the CRC-16/X.25 (reflected 0x8408, init 0xFFFF, final xor 0xFFFF) of all but its
+ * last two bytes equals them, low byte first.  Kept frames are appended in any order: list_dev: int64[4 capacity] = (p, s,
+ * start instant n_s, byte count) each, slots_dev: uint8[capacity][IQA_AIS_SLOT_BYTES] = the bytes, zero-filled.
+ * counts_dev: int64[2], zeroed by the call; counts[0] counts ALL kept frames: a count above capacity means the list is
+ * incomplete and the call must be repeated with a larger one. */
+int iqa_ais_frames(const void *v_dev, int64_t nsym, const int64_t count_of[IQA_AIS_PHASES], int32_t window, double step,
+                   void *list_dev, void *slots_dev, int64_t capacity, void *counts_dev, void *stream);
+
 /* Audio egress (the drain of AudioWriter, processing.py:433-438, without a host thread): copy nbytes from device
  * memory into MAPPED pinned host memory (hipHostMalloc / torch pin_memory) with `workgroups` small workgroups
  * (<= 0: 8), so that the copy can run beside a kernel that occupies every CU.  Both pointers 16-byte aligned. */

@@ -62,9 +62,14 @@ class ModeDefault(float):
 #: the defaults --demod wfm resolves unset --bw / --fs-ch / --deemph to (broadcast FM: 250 kHz channel, 480 kHz rate, 50 us)
 WFM_DEFAULTS = {"bandwidth": 250_000.0, "fs_ch": 480_000.0, "deemph_us": 50.0}
 
+#: the channel bandwidth an unset --bw resolves to under --ais (a 25 kHz marine VHF channel; 12 500 cuts into the GMSK skirts)
+AIS_BANDWIDTH = 25_000.0
+
 
 def resolve_mode_defaults(args):
     """Replace every unset ``--bw`` / ``--fs-ch`` / ``--deemph`` by the default of ``--demod``; explicit values win."""
+    if getattr(args, "ais", False) and args.demod == "nfm" and isinstance(args.bandwidth, ModeDefault):
+        args.bandwidth = AIS_BANDWIDTH
     for dest, wfm_value in WFM_DEFAULTS.items():
         value = getattr(args, dest)
         if isinstance(value, ModeDefault):
@@ -100,6 +105,9 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--acars", dest="acars", action="store_true",
                    help="With --demod am: decode ACARS aircraft messages (2400 bit/s MSK on an airband AM channel) of every target, "
                         "print one line per message and write <output stem>.acars.json.")
+    p.add_argument("--ais", dest="ais", action="store_true",
+                   help="With --demod nfm: decode AIS ship traffic (9600 bit/s GMSK; 161.975 / 162.025 MHz) of every target, print "
+                        "one line per message and its !AIVDM sentences and write <output stem>.ais.json.  An unset --bw becomes 25 000.")
     p.add_argument("--no-agc", dest="agc_enabled", action="store_false")
     p.add_argument("--out", dest="output_path", type=Path)
     p.add_argument("--dump-iq", dest="dump_iq", type=Path)
@@ -214,6 +222,8 @@ def main(argv: list[str] | None = None) -> int:
         parser.error("--tones needs --demod nfm.")
     if args.acars and args.demod != "am":
         parser.error("--acars needs --demod am.")
+    if args.ais and args.demod != "nfm":
+        parser.error("--ais needs --demod nfm.")
     if args.audio_post_path:
         return run_audio_post(args)
     frequencies = list(args.target_freqs or [])
@@ -267,7 +277,7 @@ def main(argv: list[str] | None = None) -> int:
     LOG.info("=== Processing %d target(s) in one pass over %s ===", len(configs), args.input_path)
     try:
         # the reference loops whole pipelines over the targets (cli.py:683-710); here the capture is read once
-        extras = dict(rds=args.rds, pocsag=args.pocsag, ax25=args.ax25, tones=args.tones, acars=args.acars)
+        extras = dict(rds=args.rds, pocsag=args.pocsag, ax25=args.ax25, tones=args.tones, acars=args.acars, ais=args.ais)
         runner = MultiChannelPipeline(configs, **extras) if len(configs) > 1 else ProcessingPipeline(configs[0], **extras)
         results = runner.run(progress_sink=None)
         results = results if len(configs) > 1 else [results]
@@ -316,6 +326,15 @@ def main(argv: list[str] | None = None) -> int:
             for msg in (res.messages if res is not None else []):
                 print(f"{config.target_freq:.0f} Hz: {msg.line()}")
             wav.with_name(wav.stem + ".acars.json").write_text(json.dumps(None if res is None else res.to_json(), indent=1) + "\n")
+    if args.ais and not args.probe_only:
+        decoded = runner.ais if len(configs) > 1 else [runner.ais]
+        targets = runner.output_paths if len(configs) > 1 else [runner.output_path]
+        for config, res, wav in zip(configs, decoded, targets):
+            for msg in (res.messages if res is not None else []):
+                print(f"{config.target_freq:.0f} Hz: {msg.line()}")
+                for sentence in msg.nmea:
+                    print(sentence)
+            wav.with_name(wav.stem + ".ais.json").write_text(json.dumps(None if res is None else res.to_json(), indent=1) + "\n")
     return 0
 
 

@@ -1,0 +1,359 @@
+"""AIS ship traffic beside narrowband FM: 9600 bit/s GMSK read straight off the discriminator.
+
+Per block ``iqa_ais_filter`` quantises the discriminator output, runs the pulse-matched FIR and appends four bytes per
+sample to the run's stored plane; once per run ``iqa_ais_symbols`` reads the plane at 8 sampling phases and
+``iqa_ais_frames`` takes a decision level from the training sequence in front of every start flag, walks the HDLC
+candidate behind it and keeps those whose CRC holds.  Every frame carries its own check, so timing is found by search and
+the level per burst: there is no loop.  Merging, the bit fields and the NMEA sentences are integer host logic on the kept
+frames and run on plain numpy arrays as well (``parse_frames``)."""
+from __future__ import annotations
+
+from ctypes import c_double, c_int32, c_int64
+from dataclasses import dataclass, field
+
+import numpy as np
+
+from .. import _dev as D
+from .. import _native as N
+from .. import dsp_plan as P
+
+PHASES = P.AIS_PHASES
+MIN_FRAME, MAX_FRAME = 11, 128  # bytes, FCS included
+SLOT_BYTES = 128  # IQA_AIS_SLOT_BYTES
+SENTENCE_CHARS = 60  # payload characters of one !AIVDM sentence
+CHANNEL_A, CHANNEL_B = 161_975_000.0, 162_025_000.0
+CHANNEL_REACH = 5_000.0
+LON_MISSING, LAT_MISSING = 181 * 600_000, 91 * 600_000
+_REVERSED = bytes(int(f"{b:08b}"[::-1], 2) for b in range(256))
+
+
+class _Bits:
+    """A message as one integer, fields read most significant bit first."""
+
+    def __init__(self, raw: bytes):
+        body = raw[:-2].translate(_REVERSED)  # a byte goes out least significant bit first
+        self.n = 8 * len(body)
+        self.value = int.from_bytes(body, "big")
+
+    def u(self, at: int, width: int) -> int:
+        return (self.value >> (self.n - at - width)) & ((1 << width) - 1)
+
+    def i(self, at: int, width: int) -> int:
+        v = self.u(at, width)
+        return v - (1 << width) if v & (1 << (width - 1)) else v
+
+    def text(self, at: int, chars: int) -> str:
+        codes = [self.u(at + 6 * k, 6) for k in range(chars)]
+        return "".join(chr(c | 0x40) if c < 32 else chr(c) for c in codes).rstrip("@ ")
+
+    def lon(self, at: int):
+        v = self.i(at, 28)
+        return None if v == LON_MISSING else v / 600_000
+
+    def lat(self, at: int):
+        v = self.i(at, 27)
+        return None if v == LAT_MISSING else v / 600_000
+
+    def unless(self, at: int, width: int, missing: int, scale: int = 1):
+        v = self.u(at, width)
+        if v == missing:
+            return None
+        return v / scale if scale != 1 else v
+
+    def dims(self, at: int) -> dict:
+        return dict(to_bow=self.u(at, 9), to_stern=self.u(at + 9, 9), to_port=self.u(at + 18, 6), to_starboard=self.u(at + 24, 6))
+
+
+def _position(b: _Bits) -> dict:
+    turn = b.i(42, 8)
+    return dict(status=b.u(38, 4), turn=None if turn == -128 else turn, speed=b.unless(50, 10, 1023, 10), accuracy=b.u(60, 1), lon=b.lon(61),
+                lat=b.lat(89), course=b.unless(116, 12, 3600, 10), heading=b.unless(128, 9, 511), second=b.u(137, 6))
+
+
+def _base_station(b: _Bits) -> dict:
+    return dict(year=b.u(38, 14), month=b.u(52, 4), day=b.u(56, 5), hour=b.u(61, 5), minute=b.u(66, 6), second=b.u(72, 6), accuracy=b.u(78, 1),
+                lon=b.lon(79), lat=b.lat(107))
+
+
+def _static(b: _Bits) -> dict:
+    return dict(imo=b.u(40, 30), callsign=b.text(70, 7), name=b.text(112, 20), ship_type=b.u(232, 8), **b.dims(240), eta_month=b.u(274, 4),
+                eta_day=b.u(278, 5), eta_hour=b.u(283, 5), eta_minute=b.u(288, 6), draught=b.u(294, 8) / 10, destination=b.text(302, 20))
+
+
+def _class_b(b: _Bits) -> dict:
+    return dict(speed=b.unless(46, 10, 1023, 10), accuracy=b.u(56, 1), lon=b.lon(57), lat=b.lat(85), course=b.unless(112, 12, 3600, 10),
+                heading=b.unless(124, 9, 511), second=b.u(133, 6))
+
+
+def _aid(b: _Bits) -> dict:
+    return dict(aid_type=b.u(38, 5), name=b.text(43, 20), accuracy=b.u(163, 1), lon=b.lon(164), lat=b.lat(192))
+
+
+def _static_24(b: _Bits) -> dict:
+    part = b.u(38, 2)
+    if part == 0:
+        return dict(part="A", name=b.text(40, 20))
+    if part == 1 and b.n >= 168:
+        return dict(part="B", ship_type=b.u(40, 8), vendor=b.text(48, 7), callsign=b.text(90, 7), **b.dims(132))
+    return {}
+
+
+#: type -> (bits the decoded fields need, their reader); a shorter message keeps type, mmsi, raw and nmea only
+_TYPES = {1: (168, _position), 2: (168, _position), 3: (168, _position), 4: (168, _base_station), 5: (424, _static), 18: (168, _class_b),
+          21: (272, _aid), 24: (160, _static_24)}
+
+
+def decode_message(raw: bytes) -> dict:
+    """One CRC-checked frame (FCS included) -> dict(type, repeat, mmsi, <fields of the decoded types>).  Speed in knots,
+    course and heading in degrees, longitude and latitude in degrees (value / 600 000), draught in metres; a "not
+    available" value (181 / 91 degrees, speed 1023, course 3600, heading 511, rate of turn -128) is ``None``."""
+    b = _Bits(raw)
+    out = dict(type=b.u(0, 6), repeat=b.u(6, 2), mmsi=b.u(8, 30))
+    need, reader = _TYPES.get(out["type"], (0, None))
+    if reader is not None and b.n >= need:
+        out.update(reader(b))
+    return out
+
+
+def channel_of(frequency) -> str:
+    """"A" within 5 kHz of 161.975 MHz, "B" within 5 kHz of 162.025 MHz, else empty."""
+    if frequency is None:
+        return ""
+    if abs(float(frequency) - CHANNEL_A) <= CHANNEL_REACH:
+        return "A"
+    if abs(float(frequency) - CHANNEL_B) <= CHANNEL_REACH:
+        return "B"
+    return ""
+
+
+def nmea_sentences(raw: bytes, channel: str = "", seq: int = 0) -> list:
+    """The ``!AIVDM`` sentences of one frame: six message bits per payload character, at most 60 characters per sentence,
+    the fill bits on the last one; ``seq`` is the id a multi-sentence message carries."""
+    b = _Bits(raw)
+    chars = -(-b.n // 6)
+    fill = 6 * chars - b.n
+    value = b.value << fill
+    payload = ""
+    for k in range(chars):
+        v = (value >> (6 * (chars - 1 - k))) & 63
+        payload += chr(v + 48 if v < 40 else v + 56)
+    parts = [payload[k : k + SENTENCE_CHARS] for k in range(0, chars, SENTENCE_CHARS)]
+    out = []
+    for k, part in enumerate(parts):
+        body = f"AIVDM,{len(parts)},{k + 1},{seq if len(parts) > 1 else ''},{channel},{part},{fill if k + 1 == len(parts) else 0}"
+        check = 0
+        for ch in body.encode("ascii"):
+            check ^= ch
+        out.append(f"!{body}*{check:02X}")
+    return out
+
+
+@dataclass
+class AisMessage:
+    time_s: float  # of the first bit behind the start flag
+    type: int
+    repeat: int
+    mmsi: int
+    raw: str  # the whole frame, FCS included, as hex
+    nmea: list  # !AIVDM sentences
+    channel: str  # "A", "B" or "" (from the target frequency)
+    hits: int  # sampling phases that decoded it
+    fields: dict = field(default_factory=dict)  # the decoded fields of types 1-5, 18, 21, 24
+
+    def line(self) -> str:
+        f = self.fields
+        parts = [f"AIS {self.type} mmsi={self.mmsi}"]
+        if f.get("lat") is not None and f.get("lon") is not None:
+            parts.append(f"{abs(f['lat']):.5f}{'N' if f['lat'] >= 0 else 'S'} {abs(f['lon']):.5f}{'E' if f['lon'] >= 0 else 'W'}")
+        if f.get("speed") is not None:
+            parts.append(f"{f['speed']:.1f}kn")
+        if f.get("course") is not None:
+            parts.append(f"{f['course']:.1f}°")
+        if "year" in f:
+            parts.append(f"{f['year']:04d}-{f['month']:02d}-{f['day']:02d} {f['hour']:02d}:{f['minute']:02d}:{f['second']:02d}Z")
+        for key in ("name", "callsign", "destination"):
+            if f.get(key):
+                parts.append(f"{key}={f[key]!r}")
+        return " ".join(parts)
+
+    def to_json(self) -> dict:
+        return dict(time_s=self.time_s, type=self.type, repeat=self.repeat, mmsi=self.mmsi, **self.fields, channel=self.channel, hits=self.hits,
+                    raw=self.raw, nmea=list(self.nmea))
+
+
+@dataclass
+class AisResult:
+    messages: list = field(default_factory=list)  # AisMessage, in order of time
+    candidates: int = 0  # closed HDLC candidates of >= 11 bytes over all phases
+    crc_ok: int = 0  # of those, the ones whose CRC holds
+
+    def to_json(self) -> dict:
+        return dict(messages=[m.to_json() for m in self.messages], candidates=self.candidates, crc_ok=self.crc_ok)
+
+
+def _group_of(groups: list, raw: bytes, at: int, reach: int):
+    """The latest group with these bytes whose first start instant lies within ``reach`` of ``at``, or ``None``."""
+    for grp in reversed(groups):
+        if at - grp[0] > reach:
+            return None  # (ascending start instants: every earlier group is further back still)
+        if grp[1] == raw:
+            return grp
+    return None
+
+
+def parse_frames(plan: P.AisPlan, records: dict, candidates: int = 0, *, frequency=None) -> AisResult | None:
+    """``records``: dict(phase=[k], s=[k], start=[k], nbytes=[k], data=uint8[k, >= nbytes]) in any order (the kept-frame list
+    of ``iqa_ais_frames``) -> the run's messages; ``frequency`` (Hz) names the channel of the sentences.  Integer logic only;
+    ``None`` where no frame survives."""
+    start = np.asarray(records["start"], dtype=np.int64).reshape(-1)
+    phase = np.asarray(records["phase"], dtype=np.int64).reshape(-1)
+    nbytes = np.asarray(records["nbytes"], dtype=np.int64).reshape(-1)
+    data = np.asarray(records["data"], dtype=np.uint8).reshape(start.size, -1) if start.size else np.zeros((0, 0), dtype=np.uint8)
+    res = AisResult(candidates=int(candidates), crc_ok=int(start.size))
+    groups: list = []  # [first start instant, bytes, hits], ascending in the first start instant
+    for k in np.lexsort((phase, start)).tolist():
+        raw, at = data[k, : int(nbytes[k])].tobytes(), int(start[k])
+        grp = _group_of(groups, raw, at, plan.L)
+        if grp is None:
+            groups.append([at, raw, 1])
+        else:
+            grp[2] += 1
+    channel, seq = channel_of(frequency), 0
+    for at, raw, hits in groups:
+        got = decode_message(raw)
+        nmea = nmea_sentences(raw, channel, seq)
+        if len(nmea) > 1:
+            seq = (seq + 1) % 10
+        head = {key: got.pop(key) for key in ("type", "repeat", "mmsi")}
+        res.messages.append(AisMessage(time_s=at / plan.fs, raw=raw.hex(), nmea=nmea, channel=channel, hits=hits, fields=got, **head))
+    return res if res.messages else None
+
+
+class AisCore:
+    """Per-stream device state: the carried quantised history (W - 1 values), the absolute position, and the growing store
+    of the filter output (one int32 device tensor per block, joined by ``finish``).  ``keep_stages`` also stores t, for the
+    tests."""
+
+    def __init__(self, plan: P.AisPlan, *, keep_stages: bool = False):
+        self.plan = plan
+        self.hist_len = plan.W - 1
+        self._taps = D.from_numpy(np.ascontiguousarray(plan.taps))
+        self._hist = None  # device int32[hist_len]; None = zeros
+        self.pos = 0  # absolute index of the next block's first sample
+        self.keep_stages = keep_stages
+        self._s: list = []
+        self._t: list = []
+
+    def process(self, theta) -> None:
+        """One block of the discriminator output (device float32[n], radians per sample)."""
+        n = int(theta.numel())
+        if n == 0:
+            return
+        t, s = D.empty(n, "int32"), D.empty(n, "int32")
+        N.call("iqa_ais_filter", N.ptr(theta), c_int64(n), N.ptr(self._hist), c_int32(self.plan.W), N.ptr(self._taps), N.ptr(t), N.ptr(s),
+               N.stream_ptr())
+        self._s.append(s)
+        if self.keep_stages:
+            self._t.append(t)
+        h = self.hist_len
+        if n >= h:
+            self._hist = t[n - h :].clone()
+        else:
+            prev = self._hist if self._hist is not None else D.zeros(h, "int32")
+            self._hist = D.torch_mod().cat([prev[n:], t])
+        self.pos += n
+
+    def joined(self) -> dict:
+        torch = D.torch_mod()
+        if len(self._s) > 1:
+            self._s = [torch.cat(self._s)]
+            self._t = [torch.cat(self._t)] if self._t else []
+        return dict(S=self._s[0] if self._s else D.empty(0, "int32"), t=self._t[0] if self._t else None)
+
+    def reset(self) -> None:
+        """Back to a stream that has seen nothing: no history, position 0, no stored plane."""
+        self._hist, self.pos, self._s, self._t = None, 0, [], []
+
+    def _frames(self, v, nsym: int, count_of, capacity: int, counts):
+        lst, slots = D.empty(4 * capacity, "int64"), D.empty(SLOT_BYTES * capacity, "uint8")
+        N.call("iqa_ais_frames", N.ptr(v), c_int64(nsym), count_of, c_int32(self.plan.W), c_double(self.plan.step), N.ptr(lst), N.ptr(slots),
+               c_int64(capacity), N.ptr(counts), N.stream_ptr())
+        return lst, slots
+
+    def finish(self, capacity: int = 256) -> dict:
+        """The symbol planes and the kept frames of the stored run: dict(phase, s, start, nbytes, data, candidates, v, nsym,
+        count_of), the records as numpy arrays sorted by (phase, s).  A list too short for the kept frames is never used:
+        the search is repeated with room for all of them."""
+        plan = self.plan
+        S = self.joined()["S"]
+        n = int(S.numel())
+        counts_of = [plan.symbol_count(p, n) for p in range(PHASES)]
+        nsym = max(counts_of)
+        count_of = (c_int64 * PHASES)(*counts_of)
+        v = D.empty(PHASES * nsym, "int32")
+        N.call("iqa_ais_symbols", N.ptr(S), c_int64(n), c_int32(plan.W), c_double(plan.step), c_int64(nsym), N.ptr(v), N.stream_ptr())
+        counts = D.zeros(2, "int64")
+        lst, slots = self._frames(v, nsym, count_of, capacity, counts)
+        kept, closed = (int(x) for x in counts.cpu().numpy())
+        if kept > capacity:
+            lst, slots = self._frames(v, nsym, count_of, kept, counts)
+            assert int(counts[0].item()) == kept
+        entries = lst[: 4 * kept].cpu().numpy().reshape(-1, 4)
+        data = slots[: SLOT_BYTES * kept].cpu().numpy().reshape(-1, SLOT_BYTES)
+        order = np.lexsort((entries[:, 1], entries[:, 0]))
+        entries, data = entries[order], data[order]
+        return dict(phase=entries[:, 0].copy(), s=entries[:, 1].copy(), start=entries[:, 2].copy(), nbytes=entries[:, 3].copy(), data=data,
+                    candidates=closed, v=v, nsym=nsym, count_of=counts_of)
+
+
+class AisDecoder:
+    """The stage API: ``process(block)`` per block of the channel (complex: the channelizer's output, run through
+    ``iqa_quadrature`` with this decoder's own ``prev``; or float32: a discriminator output in radians per sample,
+    |theta| < 2048 as ``iqa_ais_filter`` requires; a discriminator gives |theta| <= pi), ``finish()`` once (an
+    ``AisResult``, or ``None`` without a message), ``stages()`` for the tests.  ``frequency``: the channel's RF frequency
+    in Hz, which names the channel in the sentences."""
+
+    def __init__(self, rate: float, *, frequency=None, keep_stages: bool = True):
+        self.plan = P.plan_ais(float(rate))
+        self.frequency = frequency
+        self.core = AisCore(self.plan, keep_stages=keep_stages)
+        self._prev = D.from_numpy(np.array([1 + 0j], dtype=np.complex64))
+        self.theta: list = []  # with keep_stages: the discriminator output of every block (device)
+        self._fin = None
+
+    def process(self, block) -> None:
+        torch = D.torch_mod()
+        is_complex = torch.is_complex(block) if D.is_tensor(block) else np.iscomplexobj(block)
+        if is_complex:
+            z = D.to_device(block, "complex64")
+            theta = D.empty(int(z.numel()), "float32")
+            if z.numel():
+                N.call("iqa_quadrature", N.ptr(z), c_int64(int(z.numel())), N.ptr(self._prev), N.ptr(theta), N.stream_ptr())
+        else:
+            theta = D.to_device(block, "float32")
+        if self.core.keep_stages:
+            self.theta.append(theta)
+        self.core.process(theta)
+        self._fin = None
+
+    def _finished(self) -> dict:
+        if self._fin is None:
+            self._fin = self.core.finish()
+        return self._fin
+
+    def finish(self) -> AisResult | None:
+        fin = self._finished()
+        return parse_frames(self.plan, fin, fin["candidates"], frequency=self.frequency)
+
+    def stages(self) -> dict:
+        """Host copies: ``theta`` and ``t`` (with keep_stages), ``S``, ``v`` (8 int32 arrays, each as long as its phase has
+        symbols), ``records`` ([(phase, s, start instant, bytes)] sorted) and ``candidates``."""
+        fin = self._finished()
+        st = self.core.joined()
+        torch = D.torch_mod()
+        plane = fin["v"].cpu().numpy().reshape(PHASES, -1) if fin["nsym"] else np.zeros((PHASES, 0), dtype=np.int32)
+        v = [plane[p, : fin["count_of"][p]] for p in range(PHASES)]
+        records = [(int(p), int(s), int(at), fin["data"][k, : int(nb)].tobytes())
+                   for k, (p, s, at, nb) in enumerate(zip(fin["phase"], fin["s"], fin["start"], fin["nbytes"]))]
+        return dict(theta=torch.cat(self.theta).cpu().numpy() if self.theta else None, t=None if st["t"] is None else st["t"].cpu().numpy(),
+                    S=st["S"].cpu().numpy(), v=v, records=records, candidates=fin["candidates"])

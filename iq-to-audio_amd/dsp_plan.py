@@ -730,6 +730,62 @@ def plan_acars(fs_channel: float) -> AcarsPlan:
     return AcarsPlan(fs, sps, L, W, sps / 8.0, taps, int(np.rint(ACARS_TAP_SCALE * np.cos(psi))), int(np.rint(ACARS_TAP_SCALE * np.sin(psi))))
 
 
+# ---- AIS plan (--demod nfm --ais) -------------------------------------------
+
+AIS_BAUD = 9600
+AIS_BT = 0.4  # the transmitter's Gaussian filter
+AIS_MIN_SPS = 5.0  # below this the pulse filter has too few taps to tell eight sampling phases apart
+AIS_MAX_SPS = 100  # IQA_AIS_MAX_SPS
+AIS_THETA_BITS = 12  # t = rint(theta 2^12)
+AIS_T_MAX = 12_868  # rint(float32(pi) 4096)
+AIS_TAP_SCALE = 256.0
+AIS_PHASES = 8  # IQA_AIS_PHASES
+
+
+@dataclass(frozen=True)
+class AisPlan:
+    fs: float
+    sps: float  # fs / 9600 (float64)
+    L: int  # rint(sps)
+    W: int  # 3 L - 1: the pulse filter's taps
+    step: float  # sps / 8: the spacing of the sampling phases
+    taps: np.ndarray  # int16[W]
+
+    def instant(self, i, p: int):
+        """The instant of symbol ``i`` (an int or an integer array) at phase ``p``: W - 1 + rint((8 i + p) step)."""
+        return self.W - 1 + np.rint((8.0 * np.asarray(i, dtype=np.float64) + p) * self.step).astype(np.int64)
+
+    def symbol_count(self, p: int, n: int) -> int:
+        """How many symbols of phase ``p`` have their instant inside a stream of ``n`` samples."""
+        i = max(int((n - self.W) / self.sps) - 2, 0)
+        while int(self.instant(i, p)) < n:
+            i += 1
+        return i
+
+
+@functools.lru_cache(maxsize=16)
+def plan_ais(fs_channel: float) -> AisPlan:
+    """The AIS decoder's constants at channel rate ``fs_channel``; ``ValueError`` when 9600 bit/s does not fit it."""
+    fs = float(fs_channel)
+    if not math.isfinite(fs) or fs <= 0.0:
+        raise ValueError("the channel rate must be positive")
+    sps = fs / AIS_BAUD
+    if sps < AIS_MIN_SPS or sps > AIS_MAX_SPS:
+        raise ValueError(f"AIS at 9600 bit/s needs {AIS_MIN_SPS:.0f} to {AIS_MAX_SPS} samples per bit; a channel rate of {fs:.0f} Hz "
+                         f"gives {sps:.1f} (--fs-ch between 48 000 and 960 000)")
+    L = int(np.rint(sps))
+    W = 3 * L - 1
+    sigma = math.sqrt(math.log(2.0)) / (2.0 * math.pi * AIS_BT) * sps
+    k = np.arange(2 * L, dtype=np.float64)
+    gauss = np.exp(-((k - (2 * L - 1) / 2.0) ** 2) / (2.0 * sigma * sigma))
+    pulse = np.convolve(gauss, np.ones(L, dtype=np.float64))  # the Gaussian over one bit of the NRZ waveform
+    h = np.rint(AIS_TAP_SCALE * pulse / pulse.max())
+    assert h.size == W and AIS_T_MAX * int(np.abs(h).sum()) < 2 ** 31
+    taps = np.ascontiguousarray(h.astype(np.int16))
+    taps.setflags(write=False)
+    return AisPlan(fs, sps, L, W, sps / 8.0, taps)
+
+
 # ---- 48 kHz resampler plan (build-defined spec; see DESIGN.md "48 kHz stage") -----------------
 
 RS_ZERO_CROSSINGS = 16

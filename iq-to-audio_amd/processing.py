@@ -33,6 +33,7 @@ from . import iqio
 from .channelizer import (_KERNEL_CACHE, _KERNEL_CACHE_LOCK, _KERNEL_CACHE_MAX, _TAPS_MEMO, ChannelBank,  # noqa: F401  (re-exported)
                           Channelizer, _as_frames, _cached_kernel, _ChannelKernel, _taps_fingerprint, immutable_taps)
 from .decoders import create_decoder
+from .decoders.ais import AisCore, parse_frames as ais_parse_frames
 from .decoders.ax25 import AfskCore, parse_frames as ax25_parse_frames
 from .decoders.pocsag import PocsagCore, parse_batches as pocsag_parse_batches
 from .decoders.rds import RdsCore, result_from as rds_result_from
@@ -571,10 +572,14 @@ class ChannelDemod:
     ``acars=True`` (am only): after the fused call every block also runs ``iqa_envelope`` into a buffer
     of the decoder's own (never the audio buffer), which is stored; ``acars_finish`` scales, detects and searches the stored
     run and parses the kept blocks (an ``AcarsResult``, or ``None`` without a message).  Off, no ACARS entry point is called.
+
+    ``ais=True`` (nfm only): ``iqa_quadrature`` with a ``prev`` of its own and ``iqa_ais_filter`` per
+    block; ``ais_finish`` reads the stored filter output at 8 sampling phases, walks the HDLC frames behind every training
+    sequence and parses them (an ``AisResult``, or ``None`` without a message).  Off, no AIS entry point is called.
     """
 
     def __init__(self, mode: str, fs_channel: float, *, deemph_us: float, agc_enabled: bool, pocsag: bool = False, ax25: bool = False,
-                 tones: bool = False, acars: bool = False):
+                 tones: bool = False, acars: bool = False, ais: bool = False):
         self.decoder = create_decoder(mode, deemph_us=deemph_us, agc_enabled=agc_enabled)
         self.decoder.setup(fs_channel)
         self.params = self.decoder.fused_params()
@@ -601,6 +606,12 @@ class ChannelDemod:
             if self.params.mode != N.DEMOD_MODE["am"]:
                 raise ValueError("acars=True needs an am target: ACARS is audio MSK on an AM airband carrier (--demod am)")
             self.acars_core = AcarsCore(P.plan_acars(fs_channel))  # (ValueError where 2400 bit/s does not fit the channel rate)
+        self.ais_core = None
+        if ais:
+            if self.params.mode != N.DEMOD_MODE["nfm"]:
+                raise ValueError("ais=True needs an nfm target: AIS is 9600 bit/s GMSK on a narrowband FM channel (--demod nfm)")
+            self.ais_core = AisCore(P.plan_ais(fs_channel))  # (ValueError where 9600 bit/s does not fit the channel rate)
+            self._ais_prev = D.from_numpy(np.array([1 + 0j], dtype=np.complex64))
         self._needs_scratch = self.params.mode in (N.DEMOD_MODE["usb"], N.DEMOD_MODE["lsb"]) and bool(self.params.agc_enabled)
         self.chunk_sumsq: list = []  # (device float64[n_chunks*8], counts)
         self._blk = None  # one device block: [state 32 B | peak 4 B (+pad to 64) | sumsq n_chunks*8 f64]
@@ -639,6 +650,9 @@ class ChannelDemod:
             self._tones_prev = D.from_numpy(np.array([1 + 0j], dtype=np.complex64))
         if self.acars_core is not None:
             self.acars_core.reset()
+        if self.ais_core is not None:
+            self.ais_core.reset()
+            self._ais_prev = D.from_numpy(np.array([1 + 0j], dtype=np.complex64))
         if self._fresh and not force:  # (force: a step being captured into a graph must not depend on what ran before it)
             return
         # nothing is copied: the next ``process`` starts from the initial state by itself and clears the peak and the
@@ -699,6 +713,18 @@ class ChannelDemod:
             env = D.empty(n, "float32")
             N.call("iqa_envelope", N.ptr(z_dev), c_int64(n), N.ptr(env), N.stream_ptr())
             self.acars_core.process(env)
+        if self.ais_core is not None:
+            theta = D.empty(n, "float32")
+            N.call("iqa_quadrature", N.ptr(z_dev), c_int64(n), N.ptr(self._ais_prev), N.ptr(theta), N.stream_ptr())
+            self.ais_core.process(theta)
+
+    def ais_finish(self, frequency=None):
+        """The run's ``AisResult`` (``None`` without a message, or with ais off); ``frequency`` names the channel of the
+        sentences."""
+        if self.ais_core is None:
+            return None
+        fin = self.ais_core.finish()
+        return ais_parse_frames(self.ais_core.plan, fin, fin["candidates"], frequency=frequency)
 
     def acars_finish(self):
         """The run's ``AcarsResult`` (``None`` without a message, or with acars off)."""
@@ -1002,8 +1028,10 @@ class ProcessingPipeline:
     block_frames_target = 64 * 1024 * 1024
 
     def __init__(self, config: ProcessingConfig, *, rds: bool = False, pocsag: bool = False, ax25: bool = False, tones: bool = False,
-                 acars: bool = False):
+                 acars: bool = False, ais: bool = False):
         self.config = config
+        if ais and (config.demod_mode or "").lower() not in ("nfm", "fm"):
+            raise ValueError("ais=True needs an nfm target: AIS is 9600 bit/s GMSK on a narrowband FM channel (--demod nfm)")
         if rds and (config.demod_mode or "").lower() != "wfm":
             raise ValueError("rds=True needs a wfm target: RDS rides on a broadcast FM multiplex (--demod wfm)")
         if pocsag and (config.demod_mode or "").lower() not in ("nfm", "fm"):
@@ -1034,6 +1062,8 @@ class ProcessingPipeline:
         self.tones = None  # after run(): the target's TonesResult (None without an event, or with tones off)
         self.acars_enabled = bool(acars)  # --acars: decode ACARS beside am
         self.acars = None  # after run(): the target's AcarsResult (None without a message, or with acars off)
+        self.ais_enabled = bool(ais)  # --ais: decode AIS beside nfm
+        self.ais = None  # after run(): the target's AisResult (None without a message, or with ais off)
 
     def cancel(self) -> None:
         self._cancelled = True
@@ -1062,7 +1092,7 @@ class ProcessingPipeline:
     def run(self, progress_sink: ProgressSink | None = None) -> ProcessingResult:
         """One target frequency: a :class:`MultiChannelPipeline` with a single channel."""
         multi = MultiChannelPipeline([self.config], _owner=self, rds=self.rds_enabled, pocsag=self.pocsag_enabled, ax25=self.ax25_enabled,
-                                     tones=self.tones_enabled, acars=self.acars_enabled)
+                                     tones=self.tones_enabled, acars=self.acars_enabled, ais=self.ais_enabled)
         self._multi = multi
         if self._cancelled:
             multi.cancel()
@@ -1091,13 +1121,15 @@ class _Target:
         else:
             self.demod = ChannelDemod(cfg.demod_mode, fs_channel, deemph_us=cfg.deemph_us, agc_enabled=cfg.agc_enabled,
                                       pocsag=bool(getattr(owner, "pocsag_enabled", False)), ax25=bool(getattr(owner, "ax25_enabled", False)),
-                                      tones=bool(getattr(owner, "tones_enabled", False)), acars=bool(getattr(owner, "acars_enabled", False)))
+                                      tones=bool(getattr(owner, "tones_enabled", False)), acars=bool(getattr(owner, "acars_enabled", False)),
+                                      ais=bool(getattr(owner, "ais_enabled", False)))
         self.stereo = None  # wfm: the run's stereo decision (finish)
         self.rds = None  # wfm with rds: the station's RdsResult (finish)
         self.pocsag = None  # nfm with pocsag: the target's PocsagResult (finish)
         self.ax25 = None  # nfm with ax25: the target's Ax25Result (finish)
         self.tones = None  # nfm with tones: the target's TonesResult (finish)
         self.acars = None  # am with acars: the target's AcarsResult (finish)
+        self.ais = None  # nfm with ais: the target's AisResult (finish)
         if cfg.iq_order not in N.ORDER:
             raise ValueError(f"Unsupported iq_order '{cfg.iq_order}'")
         self.chan = None
@@ -1242,6 +1274,10 @@ class _Target:
             self.acars = self.owner.acars = self.demod.acars_finish()
             if self.acars is not None:
                 LOG.info("ACARS: %d message(s), %d CRC-passing candidate(s).", len(self.acars.messages), self.acars.crc_ok)
+        if self.demod.ais_core is not None:
+            self.ais = self.owner.ais = self.demod.ais_finish(frequency=self.target_freq)
+            if self.ais is not None:
+                LOG.info("AIS: %d message(s), %d CRC-passing candidate(s).", len(self.ais.messages), self.ais.crc_ok)
 
 
 class MultiChannelPipeline:
@@ -1256,7 +1292,7 @@ class MultiChannelPipeline:
     """
 
     def __init__(self, configs: list, _owner=None, *, rds: bool = False, pocsag: bool = False, ax25: bool = False, tones: bool = False,
-                 acars: bool = False):
+                 acars: bool = False, ais: bool = False):
         if not configs:
             raise ValueError("at least one ProcessingConfig is required")
         if len(configs) > 5 and _owner is None:
@@ -1279,8 +1315,10 @@ class MultiChannelPipeline:
             raise ValueError("tones=True needs nfm targets: CTCSS and DTMF ride on a narrowband FM voice channel (--demod nfm)")
         if acars and any((c.demod_mode or "").lower() != "am" for c in configs):
             raise ValueError("acars=True needs am targets: ACARS is audio MSK on an AM airband carrier (--demod am)")
-        self.owners = [_owner] if _owner is not None else [ProcessingPipeline(c, rds=rds, pocsag=pocsag, ax25=ax25, tones=tones, acars=acars)
-                                                           for c in configs]
+        if ais and any((c.demod_mode or "").lower() not in ("nfm", "fm") for c in configs):
+            raise ValueError("ais=True needs nfm targets: AIS is 9600 bit/s GMSK on a narrowband FM channel (--demod nfm)")
+        self.owners = [_owner] if _owner is not None else [ProcessingPipeline(c, rds=rds, pocsag=pocsag, ax25=ax25, tones=tones, acars=acars,
+                                                                              ais=ais) for c in configs]
         self._cancelled = False
         self.wfm_stereo = None  # after run(): per target, the wfm stereo decision (None for the other modes)
         self.rds = None  # after run(): per target, the RdsResult (None for non-wfm or pilot-less targets, or with rds off)
@@ -1288,6 +1326,7 @@ class MultiChannelPipeline:
         self.ax25 = None  # after run(): per target, the Ax25Result (None without a frame, or with ax25 off)
         self.tones = None  # after run(): per target, the TonesResult (None without an event, or with tones off)
         self.acars = None  # after run(): per target, the AcarsResult (None without a message, or with acars off)
+        self.ais = None  # after run(): per target, the AisResult (None without a message, or with ais off)
 
     def cancel(self) -> None:
         self._cancelled = True
@@ -1499,6 +1538,7 @@ class MultiChannelPipeline:
             self.ax25 = [t.ax25 for t in targets]
             self.tones = [t.tones for t in targets]
             self.acars = [t.acars for t in targets]
+            self.ais = [t.ais for t in targets]
             self.output_paths = [t.output_path for t in targets]  # where each target's audio went
             for t in targets:
                 t.owner.output_path = t.output_path
