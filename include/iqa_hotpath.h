@@ -649,6 +649,35 @@ int iqa_ais_symbols(const void *s_dev, int64_t n, int32_t window, double step, i
 int iqa_ais_frames(const void *v_dev, int64_t nsym, const int64_t count_of[IQA_AIS_PHASES], int32_t window, double step,
                    void *list_dev, void *slots_dev, int64_t capacity, void *counts_dev, void *stream);
 
+/* ------------------------------------------------------------------------------------- *
+ * ADS-B / Mode S squitters beside the AM demodulator (--demod am --adsb) *
+ * ------------------------------------------------------------------------------------- */
+
+/* A channel needs 2 <= fs / 1e6 <= IQA_ADSB_MAX_SPS samples per microsecond. */
+#define IQA_ADSB_MAX_SPS 20
+#define IQA_ADSB_CHIPS 240       /* half-microsecond chips of a long squitter: 16 of the preamble, 224 of 112 bits */
+#define IQA_ADSB_MAX_SPAN 2400   /* samples a candidate position reads: o[239] + h <= 240 * 10 */
+#define IQA_ADSB_TILE 2048       /* candidate positions of one workgroup of iqa_adsb_search */
+#define IQA_ADSB_SLOT_BYTES 14   /* one kept frame's bytes in the list; a 56-bit frame is zero-padded */
+/* The quantiser of one block.  e_dev: float32[n] (an envelope: >= 0, or NaN / +inf); q_out_dev: uint16[n].
+ * x = e 65536 (float32, exact); q = 65535 unless x < 65535, else rint(x) half-even; NaN and +inf give 65535.  A negative e
+ * is outside the precondition and gives 0. */
+int iqa_adsb_quantise(const void *e_dev, int64_t n, void *q_out_dev, void *stream);
+/* The squitter search over a whole run's q plane.  q_dev: uint16[n]; offsets_dev: int32[IQA_ADSB_CHIPS], o[0] = 0,
+ * ascending, o[k] + h <= span; 1 <= h <= IQA_ADSB_MAX_SPS / 2; span <= IQA_ADSB_MAX_SPAN (checked on the HOST copy
+ * offsets_host, which must hold the same 240 values).  Chip k at position p: C_k(p) = sum_{j<h} q[p + o[k] + j] (int32).
+ * Every p with p + span <= n is a candidate position.  It passes the preamble rule iff, with P = C0 + C2 + C7 + C9,
+ * C0 > C1, C2 > C1, C2 > C3, C7 > C6, C7 > C8, C9 > C8, C9 > C10 and 6 C_j < P for j = 4, 5, 11, 12, 13, 14 (all strict).
+ * Bit i = (C_{16+2i} > C_{17+2i}), i < 112; DF = bits 0 .. 4 MSB first; nbits = 112 for DF >= 16, else 56; the syndrome is
+ * the remainder of the first nbits bits under the generator 0x1FFF409.  A passing position with DF 11, 17 or 18 and
+ * syndrome 0 is kept, in any order: list_dev: int64[3 capacity] = (p, nbits, P) each; slots_dev:
+ * uint8[capacity][IQA_ADSB_SLOT_BYTES] = the bits MSB first, zero behind nbits.  flags_out_dev: uint8[n - span + 1] or NULL:
+ * 1 where the position passes the preamble rule.  counts_dev: int64[2], zeroed by the call: counts[0] counts ALL kept
+ * frames (a count above capacity means the list is incomplete and the call must be repeated with a larger one), counts[1]
+ * the positions that pass the preamble rule.  n < span: nothing is launched. */
+int iqa_adsb_search(const void *q_dev, int64_t n, const void *offsets_dev, const int32_t *offsets_host, int32_t h, int32_t span,
+                    void *flags_out_dev, void *list_dev, void *slots_dev, int64_t capacity, void *counts_dev, void *stream);
+
 /* Audio egress (the drain of AudioWriter, processing.py:433-438, without a host thread): copy nbytes from device
  * memory into MAPPED pinned host memory (hipHostMalloc / torch pin_memory) with `workgroups` small workgroups
  * (<= 0: 8), so that the copy can run beside a kernel that occupies every CU.  Both pointers 16-byte aligned. */

@@ -179,6 +179,9 @@ _SIGNATURES = {
     "iqa_ais_symbols": (ctypes.c_int, [c_void_p, c_int64, c_int32, c_double, c_int64, c_void_p, c_void_p]),
     "iqa_ais_frames": (ctypes.c_int, [c_void_p, c_int64, ctypes.POINTER(c_int64), c_int32, c_double, c_void_p, c_void_p, c_int64,
                                       c_void_p, c_void_p]),
+    "iqa_adsb_quantise": (ctypes.c_int, [c_void_p, c_int64, c_void_p, c_void_p]),
+    "iqa_adsb_search": (ctypes.c_int, [c_void_p, c_int64, c_void_p, ctypes.POINTER(c_int32), c_int32, c_int32, c_void_p, c_void_p, c_void_p,
+                                       c_int64, c_void_p, c_void_p]),
     "iqa_squelch_workspace_bytes": (c_int64, [c_int64, c_int32]),
     "iqa_squelch_stage_offset": (c_int64, [c_int64, c_int32, c_int32]),
     "iqa_squelch": (ctypes.c_int, [ctypes.POINTER(SquelchParams), ctypes.POINTER(SquelchSeg), c_int32, c_void_p, c_void_p,

@@ -66,6 +66,14 @@ def reject_ais(ais) -> None:
                          "use ProcessingPipeline / MultiChannelPipeline")
 
 
+def reject_adsb(adsb) -> None:
+    """Mode S decoding stores a run's quantised envelope and searches it at the end: ``adsb=True`` is a
+    ``ValueError`` up front, as ``acars=True`` is."""
+    if adsb:
+        raise ValueError("adsb=True is not supported by the resident batch runners or sharded runs: "
+                         "use ProcessingPipeline / MultiChannelPipeline")
+
+
 def _rank(precision: str) -> int:
     return _ChannelKernel.PRECISIONS.index(precision)
 
@@ -106,7 +114,7 @@ class ResidentCaptureRunner:
                  chunk: int, n_frames: int, demod_mode: str = "nfm", deemph_us: float = 300.0, agc_enabled: bool = True,
                  fmt: str = "s16", iq_order: str = "iq", mix_sign_override: int | None = None, precision: str | None = None,
                  precision_guard: float | None = None, slots: int | None = None, graph_streams: int = 1, pocsag: bool = False,
-                 ax25: bool = False, tones: bool = False, acars: bool = False, ais: bool = False):
+                 ax25: bool = False, tones: bool = False, acars: bool = False, ais: bool = False, adsb: bool = False):
         """``precision``: the channelizer precision every capture starts at (default: by demodulator,
         ``processing.base_precision``); ``precision_guard``: see ``processing.PRECISION_GUARD`` (0 = off).
         ``slots``: captures in flight (output buffers; default 2).  ``submit`` of capture i first waits for capture
@@ -124,6 +132,7 @@ class ResidentCaptureRunner:
         reject_tones(tones)
         reject_acars(acars)
         reject_ais(ais)
+        reject_adsb(adsb)
         torch = D.torch_mod()
         if slots is not None:
             if slots < 2:
@@ -497,7 +506,7 @@ class ResidentBankRunner:
 
     def __init__(self, targets: list, *, sample_rate: float, n_frames: int, chunk_size: int = 1_048_576,
                  fs_ch_target: float = 96_000.0, fmt: str = "s16", iq_order: str = "iq", precision_guard: float | None = None,
-                 pocsag: bool = False, ax25: bool = False, tones: bool = False, acars: bool = False, ais: bool = False):
+                 pocsag: bool = False, ax25: bool = False, tones: bool = False, acars: bool = False, ais: bool = False, adsb: bool = False):
         """``targets``: dicts with ``freq_offset``, and optionally ``bandwidth`` (12 500), ``demod_mode`` ("nfm"),
         ``deemph_us`` (300), ``agc_enabled`` (True), ``mix_sign`` (None = probe), ``precision`` (None = by demodulator)."""
         reject_wfm([t.get("demod_mode") for t in targets])
@@ -506,6 +515,7 @@ class ResidentBankRunner:
         reject_tones(tones)
         reject_acars(acars)
         reject_ais(ais)
+        reject_adsb(adsb)
         torch = D.torch_mod()
         if not targets:
             raise ValueError("at least one target is required")
@@ -670,7 +680,7 @@ class ResidentBankRunner:
 
 def demodulate_sharded(targets: list, *, sample_rate: float, n_frames: int, axis: str, capture=None, captures=None,
                        chunk_size: int = 1_048_576, fmt: str = "s16", iq_order: str = "iq", pocsag: bool = False,
-                       ax25: bool = False, tones: bool = False, acars: bool = False, ais: bool = False):
+                       ax25: bool = False, tones: bool = False, acars: bool = False, ais: bool = False, adsb: bool = False):
     """The N-GPU form of :class:`ResidentBankRunner` (one process per GPU under ``torch.distributed.run``; SURVEY.md
     section 8(e)), on either axis:
 
@@ -692,6 +702,7 @@ def demodulate_sharded(targets: list, *, sample_rate: float, n_frames: int, axis
     reject_tones(tones)
     reject_acars(acars)
     reject_ais(ais)
+    reject_adsb(adsb)
     torch = D.torch_mod()
     if axis not in ("channels", "captures"):
         raise ValueError("axis must be 'channels' or 'captures'")

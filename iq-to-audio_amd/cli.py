@@ -65,11 +65,18 @@ WFM_DEFAULTS = {"bandwidth": 250_000.0, "fs_ch": 480_000.0, "deemph_us": 50.0}
 #: the channel bandwidth an unset --bw resolves to under --ais (a 25 kHz marine VHF channel; 12 500 cuts into the GMSK skirts)
 AIS_BANDWIDTH = 25_000.0
 
+#: what an unset --bw / --fs-ch resolve to under --adsb (a Mode S pulse is 0.5 us wide: 2 MHz of channel at 2 MS/s at least)
+ADSB_DEFAULTS = {"bandwidth": 2_000_000.0, "fs_ch": 2_000_000.0}
+
 
 def resolve_mode_defaults(args):
     """Replace every unset ``--bw`` / ``--fs-ch`` / ``--deemph`` by the default of ``--demod``; explicit values win."""
     if getattr(args, "ais", False) and args.demod == "nfm" and isinstance(args.bandwidth, ModeDefault):
         args.bandwidth = AIS_BANDWIDTH
+    if getattr(args, "adsb", False) and args.demod == "am":
+        for dest, value in ADSB_DEFAULTS.items():
+            if isinstance(getattr(args, dest), ModeDefault):
+                setattr(args, dest, value)
     for dest, wfm_value in WFM_DEFAULTS.items():
         value = getattr(args, dest)
         if isinstance(value, ModeDefault):
@@ -108,6 +115,9 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--ais", dest="ais", action="store_true",
                    help="With --demod nfm: decode AIS ship traffic (9600 bit/s GMSK; 161.975 / 162.025 MHz) of every target, print "
                         "one line per message and its !AIVDM sentences and write <output stem>.ais.json.  An unset --bw becomes 25 000.")
+    p.add_argument("--adsb", dest="adsb", action="store_true",
+                   help="With --demod am: decode ADS-B / Mode S squitters (1090 MHz; DF11, 17, 18) of every target, print one line per "
+                        "message and write <output stem>.adsb.json.  An unset --bw and an unset --fs-ch become 2 000 000.")
     p.add_argument("--no-agc", dest="agc_enabled", action="store_false")
     p.add_argument("--out", dest="output_path", type=Path)
     p.add_argument("--dump-iq", dest="dump_iq", type=Path)
@@ -224,6 +234,8 @@ def main(argv: list[str] | None = None) -> int:
         parser.error("--acars needs --demod am.")
     if args.ais and args.demod != "nfm":
         parser.error("--ais needs --demod nfm.")
+    if args.adsb and args.demod != "am":
+        parser.error("--adsb needs --demod am.")
     if args.audio_post_path:
         return run_audio_post(args)
     frequencies = list(args.target_freqs or [])
@@ -277,7 +289,7 @@ def main(argv: list[str] | None = None) -> int:
     LOG.info("=== Processing %d target(s) in one pass over %s ===", len(configs), args.input_path)
     try:
         # the reference loops whole pipelines over the targets (cli.py:683-710); here the capture is read once
-        extras = dict(rds=args.rds, pocsag=args.pocsag, ax25=args.ax25, tones=args.tones, acars=args.acars, ais=args.ais)
+        extras = dict(rds=args.rds, pocsag=args.pocsag, ax25=args.ax25, tones=args.tones, acars=args.acars, ais=args.ais, adsb=args.adsb)
         runner = MultiChannelPipeline(configs, **extras) if len(configs) > 1 else ProcessingPipeline(configs[0], **extras)
         results = runner.run(progress_sink=None)
         results = results if len(configs) > 1 else [results]
@@ -335,6 +347,13 @@ def main(argv: list[str] | None = None) -> int:
                 for sentence in msg.nmea:
                     print(sentence)
             wav.with_name(wav.stem + ".ais.json").write_text(json.dumps(None if res is None else res.to_json(), indent=1) + "\n")
+    if args.adsb and not args.probe_only:
+        decoded = runner.adsb if len(configs) > 1 else [runner.adsb]
+        targets = runner.output_paths if len(configs) > 1 else [runner.output_path]
+        for config, res, wav in zip(configs, decoded, targets):
+            for msg in (res.messages if res is not None else []):
+                print(f"{config.target_freq:.0f} Hz: {msg.line()}")
+            wav.with_name(wav.stem + ".adsb.json").write_text(json.dumps(None if res is None else res.to_json(), indent=1) + "\n")
     return 0
 
 

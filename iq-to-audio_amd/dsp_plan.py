@@ -786,6 +786,43 @@ def plan_ais(fs_channel: float) -> AisPlan:
     return AisPlan(fs, sps, L, W, sps / 8.0, taps)
 
 
+# ---- ADS-B / Mode S plan (--demod am --adsb) --------------------------------
+
+ADSB_CHIP_RATE = 2e6  # half-microsecond chips: a bit is two of them (pulse position modulation)
+ADSB_MIN_SPS = 2.0  # samples per microsecond: one sample per chip at least
+ADSB_MAX_SPS = 20  # IQA_ADSB_MAX_SPS
+ADSB_CHIPS = 240  # 16 of the 8 us preamble, 224 of 112 bits (IQA_ADSB_CHIPS)
+ADSB_Q_MAX = 65535  # q is uint16
+
+
+@dataclass(frozen=True)
+class AdsbPlan:
+    fs: float
+    sps: float  # fs / 1e6 (float64): samples per microsecond
+    h: int  # floor(sps / 2): the samples summed per chip
+    offsets: np.ndarray  # int32[240]: o[k] = rint(k sps / 2)
+    span: int  # o[239] + h: the samples a candidate position reads
+    L: int  # rint(sps): the reach within which identical frames are one message
+
+
+@functools.lru_cache(maxsize=16)
+def plan_adsb(fs_channel: float) -> AdsbPlan:
+    """The Mode S decoder's constants at channel rate ``fs_channel``; ``ValueError`` when half-microsecond chips do not fit it."""
+    fs = float(fs_channel)
+    if not math.isfinite(fs) or fs <= 0.0:
+        raise ValueError("the channel rate must be positive")
+    sps = fs / 1e6
+    if sps < ADSB_MIN_SPS or sps > ADSB_MAX_SPS:
+        raise ValueError(f"Mode S on 1090 MHz needs {ADSB_MIN_SPS:.0f} to {ADSB_MAX_SPS} samples per microsecond; a channel rate of "
+                         f"{fs:.0f} Hz gives {sps:.2f} (--fs-ch between 2 000 000 and 20 000 000)")
+    h = int(math.floor(sps / 2.0))
+    offsets = np.rint(np.arange(ADSB_CHIPS, dtype=np.float64) * (sps / 2.0)).astype(np.int32)
+    # P is a sum of 4 chips and is compared with 6 chips: both stay inside int32
+    assert h >= 1 and 6 * h * ADSB_Q_MAX < 2 ** 31
+    offsets.setflags(write=False)
+    return AdsbPlan(fs, sps, h, offsets, int(offsets[-1]) + h, int(np.rint(sps)))
+
+
 # ---- 48 kHz resampler plan (build-defined spec; see DESIGN.md "48 kHz stage") -----------------
 
 RS_ZERO_CROSSINGS = 16

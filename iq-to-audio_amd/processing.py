@@ -33,6 +33,7 @@ from . import iqio
 from .channelizer import (_KERNEL_CACHE, _KERNEL_CACHE_LOCK, _KERNEL_CACHE_MAX, _TAPS_MEMO, ChannelBank,  # noqa: F401  (re-exported)
                           Channelizer, _as_frames, _cached_kernel, _ChannelKernel, _taps_fingerprint, immutable_taps)
 from .decoders import create_decoder
+from .decoders.adsb import AdsbCore, parse_frames as adsb_parse_frames
 from .decoders.ais import AisCore, parse_frames as ais_parse_frames
 from .decoders.ax25 import AfskCore, parse_frames as ax25_parse_frames
 from .decoders.pocsag import PocsagCore, parse_batches as pocsag_parse_batches
@@ -576,10 +577,15 @@ class ChannelDemod:
     ``ais=True`` (nfm only): ``iqa_quadrature`` with a ``prev`` of its own and ``iqa_ais_filter`` per
     block; ``ais_finish`` reads the stored filter output at 8 sampling phases, walks the HDLC frames behind every training
     sequence and parses them (an ``AisResult``, or ``None`` without a message).  Off, no AIS entry point is called.
+
+    ``adsb=True`` (am only): after the fused call every block also runs ``iqa_envelope`` into a buffer of
+    the decoder's own and ``iqa_adsb_quantise``, whose uint16 plane is stored; ``adsb_finish`` searches the stored run at
+    every sample position and parses the kept squitters (an ``AdsbResult``, or ``None`` without a message).  Off, no ADS-B
+    entry point is called.
     """
 
     def __init__(self, mode: str, fs_channel: float, *, deemph_us: float, agc_enabled: bool, pocsag: bool = False, ax25: bool = False,
-                 tones: bool = False, acars: bool = False, ais: bool = False):
+                 tones: bool = False, acars: bool = False, ais: bool = False, adsb: bool = False):
         self.decoder = create_decoder(mode, deemph_us=deemph_us, agc_enabled=agc_enabled)
         self.decoder.setup(fs_channel)
         self.params = self.decoder.fused_params()
@@ -612,6 +618,11 @@ class ChannelDemod:
                 raise ValueError("ais=True needs an nfm target: AIS is 9600 bit/s GMSK on a narrowband FM channel (--demod nfm)")
             self.ais_core = AisCore(P.plan_ais(fs_channel))  # (ValueError where 9600 bit/s does not fit the channel rate)
             self._ais_prev = D.from_numpy(np.array([1 + 0j], dtype=np.complex64))
+        self.adsb_core = None
+        if adsb:
+            if self.params.mode != N.DEMOD_MODE["am"]:
+                raise ValueError("adsb=True needs an am target: Mode S squitters are pulses on a 1090 MHz AM channel (--demod am)")
+            self.adsb_core = AdsbCore(P.plan_adsb(fs_channel))  # (ValueError where the channel rate is outside 2 .. 20 MHz)
         self._needs_scratch = self.params.mode in (N.DEMOD_MODE["usb"], N.DEMOD_MODE["lsb"]) and bool(self.params.agc_enabled)
         self.chunk_sumsq: list = []  # (device float64[n_chunks*8], counts)
         self._blk = None  # one device block: [state 32 B | peak 4 B (+pad to 64) | sumsq n_chunks*8 f64]
@@ -650,6 +661,8 @@ class ChannelDemod:
             self._tones_prev = D.from_numpy(np.array([1 + 0j], dtype=np.complex64))
         if self.acars_core is not None:
             self.acars_core.reset()
+        if self.adsb_core is not None:
+            self.adsb_core.reset()
         if self.ais_core is not None:
             self.ais_core.reset()
             self._ais_prev = D.from_numpy(np.array([1 + 0j], dtype=np.complex64))
@@ -717,6 +730,17 @@ class ChannelDemod:
             theta = D.empty(n, "float32")
             N.call("iqa_quadrature", N.ptr(z_dev), c_int64(n), N.ptr(self._ais_prev), N.ptr(theta), N.stream_ptr())
             self.ais_core.process(theta)
+        if self.adsb_core is not None:
+            env = D.empty(n, "float32")
+            N.call("iqa_envelope", N.ptr(z_dev), c_int64(n), N.ptr(env), N.stream_ptr())
+            self.adsb_core.process(env)
+
+    def adsb_finish(self):
+        """The run's ``AdsbResult`` (``None`` without a message, or with adsb off)."""
+        if self.adsb_core is None:
+            return None
+        fin = self.adsb_core.finish()
+        return adsb_parse_frames(self.adsb_core.plan, fin, fin["candidates"])
 
     def ais_finish(self, frequency=None):
         """The run's ``AisResult`` (``None`` without a message, or with ais off); ``frequency`` names the channel of the
@@ -1028,8 +1052,10 @@ class ProcessingPipeline:
     block_frames_target = 64 * 1024 * 1024
 
     def __init__(self, config: ProcessingConfig, *, rds: bool = False, pocsag: bool = False, ax25: bool = False, tones: bool = False,
-                 acars: bool = False, ais: bool = False):
+                 acars: bool = False, ais: bool = False, adsb: bool = False):
         self.config = config
+        if adsb and (config.demod_mode or "").lower() != "am":
+            raise ValueError("adsb=True needs an am target: Mode S squitters are pulses on a 1090 MHz AM channel (--demod am)")
         if ais and (config.demod_mode or "").lower() not in ("nfm", "fm"):
             raise ValueError("ais=True needs an nfm target: AIS is 9600 bit/s GMSK on a narrowband FM channel (--demod nfm)")
         if rds and (config.demod_mode or "").lower() != "wfm":
@@ -1064,6 +1090,8 @@ class ProcessingPipeline:
         self.acars = None  # after run(): the target's AcarsResult (None without a message, or with acars off)
         self.ais_enabled = bool(ais)  # --ais: decode AIS beside nfm
         self.ais = None  # after run(): the target's AisResult (None without a message, or with ais off)
+        self.adsb_enabled = bool(adsb)  # --adsb: decode Mode S squitters beside am
+        self.adsb = None  # after run(): the target's AdsbResult (None without a message, or with adsb off)
 
     def cancel(self) -> None:
         self._cancelled = True
@@ -1092,7 +1120,8 @@ class ProcessingPipeline:
     def run(self, progress_sink: ProgressSink | None = None) -> ProcessingResult:
         """One target frequency: a :class:`MultiChannelPipeline` with a single channel."""
         multi = MultiChannelPipeline([self.config], _owner=self, rds=self.rds_enabled, pocsag=self.pocsag_enabled, ax25=self.ax25_enabled,
-                                     tones=self.tones_enabled, acars=self.acars_enabled, ais=self.ais_enabled)
+                                     tones=self.tones_enabled, acars=self.acars_enabled, ais=self.ais_enabled,
+                                     adsb=self.adsb_enabled)
         self._multi = multi
         if self._cancelled:
             multi.cancel()
@@ -1122,7 +1151,7 @@ class _Target:
             self.demod = ChannelDemod(cfg.demod_mode, fs_channel, deemph_us=cfg.deemph_us, agc_enabled=cfg.agc_enabled,
                                       pocsag=bool(getattr(owner, "pocsag_enabled", False)), ax25=bool(getattr(owner, "ax25_enabled", False)),
                                       tones=bool(getattr(owner, "tones_enabled", False)), acars=bool(getattr(owner, "acars_enabled", False)),
-                                      ais=bool(getattr(owner, "ais_enabled", False)))
+                                      ais=bool(getattr(owner, "ais_enabled", False)), adsb=bool(getattr(owner, "adsb_enabled", False)))
         self.stereo = None  # wfm: the run's stereo decision (finish)
         self.rds = None  # wfm with rds: the station's RdsResult (finish)
         self.pocsag = None  # nfm with pocsag: the target's PocsagResult (finish)
@@ -1130,6 +1159,7 @@ class _Target:
         self.tones = None  # nfm with tones: the target's TonesResult (finish)
         self.acars = None  # am with acars: the target's AcarsResult (finish)
         self.ais = None  # nfm with ais: the target's AisResult (finish)
+        self.adsb = None  # am with adsb: the target's AdsbResult (finish)
         if cfg.iq_order not in N.ORDER:
             raise ValueError(f"Unsupported iq_order '{cfg.iq_order}'")
         self.chan = None
@@ -1278,6 +1308,11 @@ class _Target:
             self.ais = self.owner.ais = self.demod.ais_finish(frequency=self.target_freq)
             if self.ais is not None:
                 LOG.info("AIS: %d message(s), %d CRC-passing candidate(s).", len(self.ais.messages), self.ais.crc_ok)
+        if self.demod.adsb_core is not None:
+            self.adsb = self.owner.adsb = self.demod.adsb_finish()
+            if self.adsb is not None:
+                LOG.info("ADS-B: %d message(s) of %d aircraft, %d check-passing position(s).", len(self.adsb.messages), len(self.adsb.aircraft),
+                         self.adsb.crc_ok)
 
 
 class MultiChannelPipeline:
@@ -1292,7 +1327,7 @@ class MultiChannelPipeline:
     """
 
     def __init__(self, configs: list, _owner=None, *, rds: bool = False, pocsag: bool = False, ax25: bool = False, tones: bool = False,
-                 acars: bool = False, ais: bool = False):
+                 acars: bool = False, ais: bool = False, adsb: bool = False):
         if not configs:
             raise ValueError("at least one ProcessingConfig is required")
         if len(configs) > 5 and _owner is None:
@@ -1317,8 +1352,10 @@ class MultiChannelPipeline:
             raise ValueError("acars=True needs am targets: ACARS is audio MSK on an AM airband carrier (--demod am)")
         if ais and any((c.demod_mode or "").lower() not in ("nfm", "fm") for c in configs):
             raise ValueError("ais=True needs nfm targets: AIS is 9600 bit/s GMSK on a narrowband FM channel (--demod nfm)")
+        if adsb and any((c.demod_mode or "").lower() != "am" for c in configs):
+            raise ValueError("adsb=True needs am targets: Mode S squitters are pulses on a 1090 MHz AM channel (--demod am)")
         self.owners = [_owner] if _owner is not None else [ProcessingPipeline(c, rds=rds, pocsag=pocsag, ax25=ax25, tones=tones, acars=acars,
-                                                                              ais=ais) for c in configs]
+                                                                              ais=ais, adsb=adsb) for c in configs]
         self._cancelled = False
         self.wfm_stereo = None  # after run(): per target, the wfm stereo decision (None for the other modes)
         self.rds = None  # after run(): per target, the RdsResult (None for non-wfm or pilot-less targets, or with rds off)
@@ -1327,6 +1364,7 @@ class MultiChannelPipeline:
         self.tones = None  # after run(): per target, the TonesResult (None without an event, or with tones off)
         self.acars = None  # after run(): per target, the AcarsResult (None without a message, or with acars off)
         self.ais = None  # after run(): per target, the AisResult (None without a message, or with ais off)
+        self.adsb = None  # after run(): per target, the AdsbResult (None without a message, or with adsb off)
 
     def cancel(self) -> None:
         self._cancelled = True
@@ -1539,6 +1577,7 @@ class MultiChannelPipeline:
             self.tones = [t.tones for t in targets]
             self.acars = [t.acars for t in targets]
             self.ais = [t.ais for t in targets]
+            self.adsb = [t.adsb for t in targets]
             self.output_paths = [t.output_path for t in targets]  # where each target's audio went
             for t in targets:
                 t.owner.output_path = t.output_path
