@@ -665,6 +665,16 @@ extern "C" int iqa_resample(const void *x_dev, int64_t n_in, const void *table_d
     if (2 * T + 1 > 4097) return fail_inval("resampler rows longer than 4097 taps are not supported");
     if (n_in > (1LL << 30) - 4096) return fail_inval("resampler input longer than 2^30 samples: process it in blocks");
     if (j0 > (1LL << 40) || static_cast<int64_t>(up) * down >= (1LL << 50)) return fail_inval("resampler position out of range");
+    if (n_in == 0) {
+        // an empty stream (x may be NULL): every output is a sum over nothing.  Not the kernels' business: the unstaged
+        // waves load x[clamped index] unconditionally and mask afterwards, which needs one sample to point at.
+        hipError_t e = hipSuccess;
+        if (y_dev) e = hipMemsetAsync(y_dev, 0, static_cast<size_t>(n_out) * sizeof(float), as_stream(stream));
+        if (e == hipSuccess && pcm16_dev) e = hipMemsetAsync(pcm16_dev, 0, static_cast<size_t>(n_out) * sizeof(short), as_stream(stream));
+        if (e == hipSuccess) return IQA_OK;
+        set_error("zeroing the outputs of an empty stream failed: %s", hipGetErrorString(e));
+        return IQA_EHIP;
+    }
     if (2 * T + 1 > 192) {
         if (j0 + n_out > (1LL << 62) / down || n_out > (1LL << 36)) return fail_inval("resampler position out of range");
         const dim3 grid = grid1d(n_out * RS_LONG_LANES, 256);

@@ -10,6 +10,7 @@ from pathlib import Path
 
 import numpy as np
 import pytest
+import resampler_model as RM
 
 from oracle import cpu_ref as O
 
@@ -228,6 +229,6 @@ def test_long_row_resampler_matches_spec(A, fs_ch):
     x = (0.5 * np.sin(2 * np.pi * 1234.5 * np.arange(200_003) / fs_ch)
          + np.random.default_rng(1).normal(scale=0.05, size=200_003)).astype(np.float32)
     y, pcm = rs.process(D.to_device(x, "float32"), want="both")
-    want = O.resample_48k(x, fs_ch)
-    np.testing.assert_allclose(y.cpu().numpy(), want, rtol=0, atol=3e-7)
+    assert y.numel() == O.resample_48k(x, fs_ch).size
+    RM.check(y.cpu().numpy(), *RM.y64(x, fs_ch))
     np.testing.assert_array_equal(pcm.cpu().numpy(), O.float_to_pcm16(y.cpu().numpy()))
