@@ -7,6 +7,7 @@ stated per test.
 """
 from __future__ import annotations
 
+import channelizer_model as CM
 import numpy as np
 import pytest
 import resampler_model as RM
@@ -282,7 +283,9 @@ def test_decoders_chunked_vs_oracle(A, mode):
 @pytest.mark.parametrize("fmt", ["s16", "u8", "f32"])
 def test_channelizer_formats_orders_streaming(A, fmt, order):
     """Fused kernel == mix -> overlap-save -> decimate of the oracle, for every ingest format and
-    iq_order, fed in ragged blocks (history path, blocks shorter than L-1, D not dividing blocks)."""
+    iq_order, fed in ragged blocks (history path, blocks shorter than L-1, D not dividing blocks).  Every block's outputs
+    also lie within the derived bound of the float64 model (tests/channelizer_model.py: (depth + c_epi) 2^-24 B per
+    component, split-K depth), fed the same blocks with the history carried in numpy."""
     fs, f_off, d = 1e6, 31250.0, 10
     rng = np.random.default_rng(9)
     n = 30000
@@ -296,12 +299,25 @@ def test_channelizer_formats_orders_streaming(A, fmt, order):
     ch = A.Channelizer(taps, sample_rate=fs, freq_offset=f_off, mix_sign=-1, decimation=d, fmt=fmt, iq_order=order)
     nco, fir, dst = O.NcoState(f_off, fs), O.OverlapSaveState(taps, 4096), O.DecimState(d)
     edges = [0, 7, 500, 1501, 1502, 12345, 30000]
+    plan, hist, consumed = ch.plan, None, 0
+    kw = dict(ntaps=plan.ntaps, decimation=d)
     for lo, hi in zip(edges[:-1], edges[1:]):
-        got = ch.process(raw[2 * lo : 2 * hi])
-        x = O.ingest_to_complex64(raw[2 * lo : 2 * hi], fmt, order)
+        blk = raw[2 * lo : 2 * hi]
+        got = ch.process(blk)
+        x = O.ingest_to_complex64(blk, fmt, order)
         want = O.decimate(O.overlap_save(O.nco_mix(x, nco, -1), fir), dst)
         assert got.shape == want.shape, (lo, hi)
         np.testing.assert_allclose(got, want, rtol=0, atol=3e-6)
+        m_first = -(-consumed // d)
+        if got.size:
+            z64 = CM.direct(plan.taps_window, blk, fmt, hist, consumed, m_first, got.size, conj_sum=plan.conj_sum, rotate=plan.rotate,
+                            rot_step=plan.rot_step, rot_base=plan.rot_base, scale=plan.out_scale, **kw)
+            bound = CM.error_bound(plan.taps_window, blk, fmt, hist, consumed, m_first, got.size, form="splitk", scale=plan.out_scale, **kw)
+            ratio = CM.within(got, z64, bound)
+            assert np.all(ratio <= 1.0), (lo, hi, int(np.argmax(ratio)), float(ratio.max()))
+        hist = CM.history_next(hist, blk, fmt, plan.ntaps - 1, hi - lo).view(raw.dtype)
+        consumed += hi - lo
+    assert ch._kernel.last_kernel == "k_channelize_v1"
 
 
 def test_channelizer_c1_slice_against_reference_fixture(A, golden):
@@ -320,7 +336,9 @@ def test_channelizer_c1_slice_against_reference_fixture(A, golden):
 @pytest.mark.parametrize("fs,bw,d,f_off", [(10e6, 12500.0, 104, 1.2e6), (20e6, 2800.0, 208, -3.3e6),
                                            (50e6, 12500.0, 521, 7.7e6)])
 def test_channelizer_long_filters(A, fs, bw, d, f_off):
-    """BASELINE configs 2/3/5 filter shapes (6401 / 32769 / 32001 taps) on a short noise capture."""
+    """BASELINE configs 2/3/5 filter shapes (6401 / 32769 / 32001 taps) on a short noise capture.  Beside the RMS against
+    the oracle, every output lies within the derived bound of the float64 model (tests/channelizer_model.py; both blocks
+    are split-K launches; an output's value does not depend on how the stream is cut, so the model sees it whole)."""
     rng = np.random.default_rng(2)
     n = 400_000
     raw = rng.integers(-12000, 12000, size=2 * n).astype(np.int16)
@@ -336,6 +354,13 @@ def test_channelizer_long_filters(A, fs, bw, d, f_off):
     assert got.shape == want.shape
     assert rms(got - want) < 2e-6
     assert rms(want) > 0.05  # the tone is in the pass band: a non-trivial comparison
+    plan = ch.plan
+    assert ch._kernel.last_kernel == "k_channelize_v1" and CM.form_of(got.size) == "splitk"
+    kw = dict(ntaps=plan.ntaps, decimation=d)
+    z64 = CM.direct(plan.taps_window, raw, "s16", None, 0, 0, got.size, conj_sum=plan.conj_sum, rotate=plan.rotate,
+                    rot_step=plan.rot_step, rot_base=plan.rot_base, scale=plan.out_scale, **kw)
+    ratio = CM.within(got, z64, CM.error_bound(plan.taps_window, raw, "s16", None, 0, 0, got.size, form="splitk", **kw))
+    assert np.all(ratio <= 1.0), (int(np.argmax(ratio)), float(ratio.max()))
 
 
 # ---- whole chain ---------------------------------------------------------------------------------
