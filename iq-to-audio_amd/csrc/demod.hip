@@ -569,7 +569,8 @@ extern "C" int iqa_decimate(const void *in_dev, int64_t n, int64_t first, int32_
 {
     if (n < 0 || n_out < 0 || first < 0 || D < 1) return fail_inval("bad decimate sizes");
     if (n_out == 0) return IQA_OK;
-    if (first + (n_out - 1) * static_cast<int64_t>(D) >= n) return fail_inval("decimate reads past the input");
+    // first + (n_out - 1) D < n, in a form that cannot overflow (n_out = 2^62 with D = 4 wrapped to 0 and was accepted)
+    if (first >= n || n_out - 1 > (n - 1 - first) / D) return fail_inval("decimate reads past the input");
     if (!in_dev || !out_dev) return fail_inval("NULL device pointer");
     hipLaunchKernelGGL(k_decimate, grid1d(n_out, 256), dim3(256), 0, as_stream(stream),
                        static_cast<const float2 *>(in_dev), (long long)first, (int)D, static_cast<float2 *>(out_dev),

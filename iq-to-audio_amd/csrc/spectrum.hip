@@ -165,7 +165,10 @@ extern "C" int iqa_psd_frames(int32_t fmt, int32_t iq_order, const void *samples
     if (nfft < 2 || use < 1 || use > nfft) return fail_inval("need 1 <= use <= nfft, nfft >= 2");
     if (n_frames < 0 || hop < 1 || first < 0) return fail_inval("bad frame geometry");
     if (n_frames == 0) return IQA_OK;
-    if (first + static_cast<int64_t>(n_frames - 1) * hop + use > n_samples) return fail_inval("frames reach past the samples");
+    // first + (n_frames - 1) hop + use <= n_samples, in a form that cannot overflow (hop and first have no upper limit:
+    // with the product formed in int64, hop = 2^62 and 3 frames wrapped to a negative sum and were accepted)
+    if (n_samples < use || first > n_samples - use || (n_frames > 1 && hop > (n_samples - use - first) / (n_frames - 1)))
+        return fail_inval("frames reach past the samples");
     if (!samples_dev || !window_dev || !work_dev) return fail_inval("NULL device pointer");
     if (!(scale > 0.0)) return fail_inval("scale must be positive");
     hipStream_t s = as_stream(stream);

@@ -11,6 +11,7 @@ import channelizer_model as CM
 import numpy as np
 import pytest
 import resampler_model as RM
+import stage_model as SG
 
 from oracle import cpu_ref as O
 
@@ -52,10 +53,12 @@ def test_oscillator_matches_oracle_across_calls(A):
     osc = A.ComplexOscillator(12345.678, 1e6)
     st = O.NcoState(12345.678, 1e6)
     for lo, hi in ((0, 3000), (3000, 5000)):
+        phase0 = osc.phase
         got = osc.mix(x[lo:hi], 1)
         want = O.nco_mix(x[lo:hi], st, 1)
         assert isinstance(got, np.ndarray) and got.dtype == np.complex64 and got.shape == want.shape
         np.testing.assert_allclose(got, want, rtol=0, atol=1e-6)
+        SG.mix_ratio(got, x[lo:hi], phase0, osc.increment)  # every sample within the derived bound (tests/stage_model.py)
     assert abs(osc.phase - st.phase) < 1e-12
     assert osc.mix(x[:0], 1).size == 0  # empty in -> returned unchanged
 
@@ -65,7 +68,9 @@ def test_oscillator_golden(A, golden):
     rng = np.random.default_rng(int(g["seed"]))
     x = (rng.normal(size=5000) + 1j * rng.normal(size=5000)).astype(np.complex64)
     osc = A.ComplexOscillator(-4321.0, 1e6)
-    np.testing.assert_allclose(osc.mix(x, -1), g["mix_b"], rtol=0, atol=1e-6)
+    got = osc.mix(x, -1)
+    np.testing.assert_allclose(got, g["mix_b"], rtol=0, atol=1e-6)
+    SG.mix_ratio(got, x, 0.0, -osc.increment)
 
 
 @pytest.mark.parametrize("order", ["iq", "qi", "iq_inv", "qi_inv"])
@@ -73,9 +78,11 @@ def test_oscillator_golden(A, golden):
 def test_oscillator_ingest_formats(A, fmt, order):
     rng = np.random.default_rng(5)
     raw = rng.integers(-32768, 32767, size=2000).astype(np.int16) if fmt == "s16" else rng.integers(0, 255, size=2000).astype(np.uint8)
-    got = A.ComplexOscillator(1000.0, 48000.0).mix(raw, 1, fmt=fmt, iq_order=order)
+    osc = A.ComplexOscillator(1000.0, 48000.0)
+    got = osc.mix(raw, 1, fmt=fmt, iq_order=order)
     want = O.nco_mix(O.ingest_to_complex64(raw, fmt, order), O.NcoState(1000.0, 48000.0), 1)
     np.testing.assert_allclose(got, want, rtol=0, atol=1e-6)
+    SG.mix_ratio(got, O.ingest_to_complex64(raw, fmt, order), 0.0, osc.increment)
 
 
 def test_fir_stage_matches_overlap_save(A, golden):
