@@ -287,12 +287,12 @@ extern "C" int iqa_ais_frames(const void *v_dev, int64_t nsym, const int64_t cou
         g.count_of[p] = count_of[p];
     }
     if (nsym > (1LL << 37)) return fail_inval("length out of range");
+    if (nsym > 0 && (!v_dev || (capacity > 0 && (!list_dev || !slots_dev)))) return fail_inval("NULL device pointer");  // (a refused call clears nothing)
     if (hipMemsetAsync(counts_dev, 0, 2 * sizeof(long long), as_stream(stream)) != hipSuccess) {
         set_error("clearing the frame counts failed");
         return IQA_EHIP;
     }
     if (nsym == 0) return IQA_OK;
-    if (!v_dev || (capacity > 0 && (!list_dev || !slots_dev))) return fail_inval("NULL device pointer");
     g.v = static_cast<const int *>(v_dev);
     g.nsym = nsym;
     g.list = static_cast<long long *>(list_dev);

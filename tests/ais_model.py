@@ -571,3 +571,428 @@ def self_check() -> None:
     assert again[:143] == bits[:143] and again[149:] == bits[149:]
     assert armour(bits) == (REFERENCE_PAYLOAD, 0)
     assert sentences(bits, "B", 0) == [REFERENCE_SENTENCE]
+
+
+# ---- edge shapes (tests/test_gpu_ais_shapes.py, tests/test_ais_shapes_host.py) -------------------------------------------
+#
+# Case tables, block oracles and numpy stand-ins of the three entry points that follow csrc/ais.hip's launch arithmetic and
+# can be broken one way at a time.  The ``check_*`` functions hold the comparisons; they take the entry point as a callable,
+# so the GPU file passes the device call and the host file the stand-in.
+
+SENT = -7_777_777  # what untouched output words hold
+GUARD = 16  # sentinel words behind every output
+FRONT = 4  # words in front of every view (16 bytes, so that offset 0 stays 16-byte aligned); sentinels where it is an output
+TILE, RUN = 2048, 8  # AI_TILE, AI_RUN
+MAX_TAPS = 299
+MAX_N, MAX_NSYM = 1 << 40, 1 << 37
+SLOT_BYTES = 128
+FILTER_WINDOWS = (1, 2, 8, 9, 16, 17, 298, 299)
+FILTER_LENGTHS = (7, 8, 9, TILE + 8, 2 * TILE + 5)
+HOSTILE_F32 = np.array([np.nan, np.inf, -np.inf, 3.0e38], dtype=np.float32)
+HOSTILE_I32 = np.array([2 ** 31 - 1, -(2 ** 31), 2 ** 31 - 1, -(2 ** 31)], dtype=np.int32)
+
+
+def wrap32(x):
+    return ((np.asarray(x, dtype=np.int64) + 2 ** 31) % 2 ** 32) - 2 ** 31
+
+
+def s24(x):
+    """The low 24 bits, sign-extended: what v_mad_i32_i24 reads of an operand."""
+    return ((np.asarray(x, dtype=np.int64) & 0xFFFFFF) ^ 0x800000) - 0x800000
+
+
+def view_offsets() -> list:
+    """(theta, hist, t_out, s_out) element offsets inside their allocations: the four s_out offsets, each with theta
+    16-byte aligned and not; hist and t_out take all four values as well, not in step with either."""
+    out = []
+    for s_off in range(4):
+        for k, th_off in enumerate((0, 1 + s_off % 3)):
+            out.append((th_off, (2 * s_off + k + 1) % 4, (3 * s_off + 2 * k + 2) % 4, s_off))
+    return out
+
+
+def shape_taps(W: int, seed: int) -> np.ndarray:
+    """int16[W] in 0 .. 256, arbitrary (not symmetric), both ends at the bound."""
+    h = np.random.default_rng(seed).integers(0, 257, size=W).astype(np.int16)
+    h[0] = 256
+    h[-1] = 256 if W > 1 else h[-1]
+    return h
+
+
+def filter_theta(n: int, W: int, seed: int) -> np.ndarray:
+    rng = np.random.default_rng(seed)
+    pi32 = np.float32(np.pi)
+    th = np.clip(rng.uniform(-np.pi, np.pi, n).astype(np.float32), -pi32, pi32)
+    ties = ((np.arange(-6, 6, dtype=np.float64) + 0.5) / 4096.0).astype(np.float32)
+    th[: min(n, ties.size)] = ties[: min(n, ties.size)]
+    if n > TILE + 4:
+        th[TILE - 4 : TILE + 4] = ties[:8]
+    return th
+
+
+def filter_cases(W: int) -> list:
+    """dict(name, W, n, taps, theta, hist | None, offsets): arbitrary taps at every n x history x view offsets, and the two
+    full-scale sets (all taps 256, theta and history held at +pi / -pi), whose every output is +-12 868 . 256 . W."""
+    out = []
+    for n in FILTER_LENGTHS:
+        for with_hist in (False, True):
+            for k, offs in enumerate(view_offsets()):
+                seed = 10_000 * W + 10 * n + k + with_hist
+                hist = None
+                if with_hist:
+                    hist = np.random.default_rng(seed + 1).integers(-T_PI, T_PI + 1, size=W - 1).astype(np.int32)
+                    if W > 1:
+                        hist[0], hist[-1] = T_PI, -T_PI
+                out.append(dict(name=f"W {W} n {n} hist {'given' if with_hist else 'NULL'} offsets {offs}", W=W, n=n, taps=shape_taps(W, seed + 2),
+                                theta=filter_theta(n, W, seed), hist=hist, offsets=offs, full=0))
+    for sign in (1, -1):
+        for n, offs in ((TILE + 8, (0, 0, 0, 0)), (2 * TILE + 5, (1, 2, 3, 1)), (9, (2, 1, 0, 3))):
+            out.append(dict(name=f"W {W} n {n} all taps 256, theta {'+' if sign > 0 else '-'}pi, offsets {offs}", W=W, n=n, taps=np.full(W, 256, dtype=np.int16),
+                            theta=np.full(n, sign * np.float32(np.pi), dtype=np.float32), hist=np.full(W - 1, sign * T_PI, dtype=np.int32),
+                            offsets=offs, full=sign))
+    return out
+
+
+def check_filter(case: dict, call) -> None:
+    """``call(theta_alloc, th_at, n, hist_alloc | None, h_at, W, taps_alloc, t_alloc, t_at, s_alloc, s_at) -> (t_alloc,
+    s_alloc)`` after the call (int32 numpy); ``*_at`` is the element index of the view inside its allocation (FRONT + the
+    offset), the outputs arrive filled with SENT."""
+    W, n, taps = case["W"], case["n"], case["taps"]
+    th_off, h_off, t_off, s_off = case["offsets"]
+    want_t = quantise(case["theta"])
+    want_s = pulse_filter(want_t, dict(W=W, taps=taps.astype(np.int64)), case["hist"])
+    assert taps.min() >= 0 and taps.max() <= 256 and np.abs(want_t).max() <= T_PI
+    if case["full"]:
+        assert (want_s == case["full"] * T_PI * 256 * W).all() and T_PI * 256 * W < 2 ** 31, case["name"]
+    elif n >= 12:
+        assert list(want_t[:12]) == [-6, -4, -4, -2, -2, 0, 0, 2, 2, 4, 4, 6]  # half-even
+    if case["hist"] is not None and W > 1 and not case["full"]:
+        assert int(want_s[0]) != int(pulse_filter(want_t, dict(W=W, taps=taps.astype(np.int64)), None)[0]), case["name"]
+    theta = np.concatenate([np.resize(HOSTILE_F32, FRONT + th_off), case["theta"], HOSTILE_F32])
+    hist = None if case["hist"] is None else np.concatenate([np.resize(HOSTILE_I32, FRONT + h_off), case["hist"], HOSTILE_I32])
+    taps_alloc = np.concatenate([taps, np.full(8, 32767, dtype=np.int16)])
+    t_alloc = np.full(FRONT + t_off + n + GUARD, SENT, dtype=np.int32)
+    s_alloc = np.full(FRONT + s_off + n + GUARD, SENT, dtype=np.int32)
+    t_alloc, s_alloc = call(theta, FRONT + th_off, n, hist, FRONT + h_off, W, taps_alloc, t_alloc, FRONT + t_off, s_alloc, FRONT + s_off)
+    for got, off, want, what in ((s_alloc, s_off, want_s, "S"), (t_alloc, t_off, want_t, "t")):
+        a = FRONT + off
+        np.testing.assert_array_equal(got[a : a + n], want, err_msg=f"{what}: {case['name']}")
+        assert (got[:a] == SENT).all() and (got[a + n :] == SENT).all(), f"{what} guards: {case['name']}"
+
+
+def kernel_filter(theta, n: int, hist, W: int, taps, t_out, s_alloc, s_at: int, *, wide_store_always: bool = False) -> None:
+    """k_ais_filter and its launch in numpy, tile by tile: the staged image (history, block, zeros), the taps behind tap 0
+    zero-padded to H, 24-bit operands and an int32 accumulator, and the two store paths -- 8 words at once where the whole
+    run lies inside n and ``s_out`` is 16-byte aligned, element by element otherwise.  ``theta``, ``hist`` and ``t_out``
+    are the views; ``s_alloc`` is the allocation (16-byte aligned) and ``s_at`` the view's element index in it.  Break:
+    ``wide_store_always`` takes the 16-byte path whatever the address, which a memory path that ignores the low address
+    bits rounds down to a multiple of 16 bytes."""
+    H = (W - 1 + RUN - 1) // RUN * RUN
+    tp = np.zeros(1 + H, dtype=np.int64)
+    tp[:W] = np.asarray(taps[:W], dtype=np.int64)
+    aligned = (4 * s_at) % 16 == 0
+    for b in range(-(-n // TILE)):
+        A = b * TILE
+        a = A - H + np.arange(H + TILE)
+        img = np.zeros(H + TILE, dtype=np.int64)
+        if hist is not None:
+            sel = (a < 0) & (a >= -(W - 1))
+            img[sel] = np.asarray(hist)[(W - 1) + a[sel]]
+        ins = (a >= 0) & (a < n)
+        img[ins] = quantise(np.asarray(theta)[a[ins]])
+        own = ins & (np.arange(H + TILE) >= H)
+        if t_out is not None:
+            t_out[a[own]] = img[own]
+        acc = wrap32(np.convolve(s24(img), s24(tp))[H : H + TILE])  # acc[j] = sum_k tp[k] img[H + j - k]
+        for tid in range(TILE // RUN):
+            a0 = A + tid * RUN
+            if a0 >= n:
+                break
+            run = acc[tid * RUN : (tid + 1) * RUN]
+            if a0 + RUN <= n and (aligned or wide_store_always):
+                at = (s_at + a0) // 4 * 4 if not aligned else s_at + a0
+                s_alloc[at : at + RUN] = run
+            else:
+                for r in range(RUN):
+                    if a0 + r < n:
+                        s_alloc[s_at + a0 + r] = run[r]
+
+
+def window_ok(W) -> bool:
+    return 1 <= W <= MAX_TAPS
+
+
+def step_ok(step) -> bool:
+    return 5.0 / 8.0 <= step <= MAX_SPS / 8.0  # (false for a NaN)
+
+
+def entry_filter(theta, th_at, n, hist, h_at, W, taps, t_alloc, t_at, s_alloc, s_at, **breaks) -> None:
+    """iqa_ais_filter's checks in front of ``kernel_filter``; None stands for a NULL pointer."""
+    if n < 0:
+        raise ValueError("negative length")
+    if not window_ok(W):
+        raise ValueError("window must be 1 .. 3 IQA_AIS_MAX_SPS - 1")
+    if n == 0:
+        return
+    if theta is None or taps is None or s_alloc is None:
+        raise ValueError("NULL device pointer")
+    if n > MAX_N:
+        raise ValueError("length out of range")
+    kernel_filter(theta[th_at:], n, None if hist is None else hist[h_at:], W, taps, None if t_alloc is None else t_alloc[t_at:], s_alloc, s_at, **breaks)
+
+
+def filter_refusals() -> list:
+    """(what, n, W, theta?, taps?, s_out?, message)."""
+    return [("negative n", -1, 29, True, True, True, "negative"), ("window 0", 64, 0, True, True, True, "window must be"),
+            ("window 300", 64, MAX_TAPS + 1, True, True, True, "window must be"), ("NULL theta", 64, 29, False, True, True, "NULL"),
+            ("NULL taps", 64, 29, True, False, True, "NULL"), ("NULL s_out", 64, 29, True, True, False, "NULL"), ("n above 2^40", MAX_N + 1, 29, True, True, True, "out of range")]
+
+
+# -- symbols
+
+
+SYMBOL_COUNTS = (0, 1, 255, 256, 257)
+SYMBOL_SHAPES = ((10.0, 29), (6.0, 17), (5.0, 1), (100.0, 299), (10.125, 30))  # (sps, W): steps 1.25 and 0.75 have exact .5 ties
+
+
+def symbols_block(S, n: int, W: int, step: float, nsym: int) -> tuple:
+    """(v int32[8, nsym], instants int64[8, nsym], ties bool[8, nsym]): v = S[instant] where the instant lies inside n."""
+    x = (8.0 * np.arange(nsym, dtype=np.float64)[None, :] + np.arange(PHASES, dtype=np.float64)[:, None]) * step
+    at = W - 1 + np.rint(x).astype(np.int64)
+    v = np.zeros((PHASES, nsym), dtype=np.int32)
+    ok = at < n
+    v[ok] = np.asarray(S)[at[ok]]
+    return v, at, np.mod(x, 1.0) == 0.5
+
+
+def symbol_cases() -> list:
+    """dict(name, sps, W, n, nsym): every count at every shape, on a plane that ends inside the last symbols (so some phases
+    read zeros), and a plane shorter than W - 1 (every instant lies beyond it)."""
+    out = []
+    for sps, W in SYMBOL_SHAPES:
+        for nsym in SYMBOL_COUNTS:
+            n = W - 1 + int(np.rint(max(nsym - 2, 1) * sps)) + 3
+            out.append(dict(name=f"sps {sps} W {W} nsym {nsym} n {n}", sps=sps, W=W, n=n, nsym=nsym))
+        if W > 2:
+            out.append(dict(name=f"sps {sps} W {W}: a plane of W - 2 samples", sps=sps, W=W, n=W - 2, nsym=256))
+    return out
+
+
+def check_symbols(case: dict, call, stats: dict | None = None) -> None:
+    """``call(S_alloc, n, W, step, nsym, v_buf) -> v_buf`` (int32 numpy)."""
+    sps, W, n, nsym = case["sps"], case["W"], case["n"], case["nsym"]
+    step = sps / 8.0
+    S = np.random.default_rng(n + nsym).integers(-(2 ** 31), 2 ** 31, size=n).astype(np.int32)
+    S[S == 0] = 1
+    want, at, ties = symbols_block(S, n, W, step, nsym)
+    if n == W - 2:
+        assert (want == 0).all() and at.min() == W - 1 > n - 1
+    elif nsym >= 255:
+        assert (at >= n).any() and (want[:, : nsym - 4] != 0).all(), case["name"]  # the plane ends inside the last symbols
+    if stats is not None and nsym:
+        x = (8.0 * np.arange(nsym)[None, :] + np.arange(PHASES)[:, None]) * step
+        stats["ties"] = stats.get("ties", 0) + int(ties.sum())
+        stats["ties rounded down"] = stats.get("ties rounded down", 0) + int((ties & (np.rint(x) != np.floor(x + 0.5))).sum())
+    v_buf = np.full(PHASES * nsym + GUARD, SENT, dtype=np.int32)
+    v_buf = call(np.concatenate([S, HOSTILE_I32]), n, W, step, nsym, v_buf)
+    np.testing.assert_array_equal(v_buf[: PHASES * nsym].reshape(PHASES, nsym), want, err_msg=case["name"])
+    assert (v_buf[PHASES * nsym :] == SENT).all(), case["name"]
+
+
+def entry_symbols(S, n, W, step, nsym, v_out) -> None:
+    if n < 0 or nsym < 0:
+        raise ValueError("negative length")
+    if not window_ok(W):
+        raise ValueError("window must be 1 .. 3 IQA_AIS_MAX_SPS - 1")
+    if not step_ok(step):
+        raise ValueError("step must be sps / 8 with 5 <= sps <= IQA_AIS_MAX_SPS")
+    if nsym == 0:
+        return
+    if S is None or v_out is None:
+        raise ValueError("NULL device pointer")
+    if n > MAX_N or nsym > MAX_NSYM:
+        raise ValueError("length out of range")
+    v_out[: PHASES * nsym] = symbols_block(S, n, W, step, nsym)[0].reshape(-1)
+
+
+def symbol_refusals() -> list:
+    """(what, n, W, step, nsym, S?, v?, message)."""
+    return [("negative n", -1, 29, 1.25, 8, True, True, "negative"), ("negative nsym", 64, 29, 1.25, -1, True, True, "negative"),
+            ("window 0", 64, 0, 1.25, 8, True, True, "window must be"), ("window 300", 64, MAX_TAPS + 1, 1.25, 8, True, True, "window must be"),
+            ("step below 5/8", 64, 29, 0.624, 8, True, True, "step must be"), ("step above 100/8", 64, 29, 12.51, 8, True, True, "step must be"),
+            ("step not a number", 64, 29, float("nan"), 8, True, True, "step must be"), ("NULL S", 64, 29, 1.25, 8, False, True, "NULL"),
+            ("NULL v", 64, 29, 1.25, 8, True, False, "NULL"), ("n above 2^40", MAX_N + 1, 29, 1.25, 8, True, True, "out of range"),
+            ("nsym above 2^37", 64, 29, 1.25, MAX_NSYM + 1, True, True, "out of range")]
+
+
+# -- frames
+
+
+FRAME_NSYM = (255, 256, 257)
+FRAME_W, FRAME_STEP = 29, 1.25
+AFFINE_A = (2 ** 31 - 2) // 16_000  # 134 217: 9000 a + b = 2 147 472 001, just below 2^31 - 1
+AFFINE_B = 7_000 * AFFINE_A + 1  # -7000 a + b = 1: every symbol positive
+
+
+def affine(v) -> np.ndarray:
+    out = AFFINE_A * np.asarray(v, dtype=np.int64) + AFFINE_B
+    assert out.min() >= 1 and out.max() < 2 ** 31
+    return out.astype(np.int32)
+
+
+def _padded(v, nsym: int, *, right: bool = False) -> np.ndarray:
+    v = np.asarray(v, dtype=np.int32)
+    assert v.size <= nsym, (v.size, nsym)
+    pad = np.full(nsym - v.size, -7000, dtype=np.int32)
+    return np.concatenate([pad, v] if right else [v, pad])
+
+
+def frame_scenarios(nsym: int) -> list:
+    """dict(name, planes int32[8, nsym], count_of[8], kept[8]): eight different planes and counts in one call.
+    "cuts": the closing flag's last symbol at index nsym - 1 = count - 1 (the frame right-aligned in the plane), at
+    count - 1 inside the plane, at count (cut off); counts 0, 23, 24, 25 and nsym; a candidate that opens at s = 24.
+    "walks": the hand-made planes of the walker test, one per phase, each with its own count."""
+    hand = {name: (v, count, kept) for name, v, count, kept in hand_made_planes()}
+    base = hand["flag in the payload"][0]
+    end = hand["cut behind the closing flag"][1]  # the index behind the closing flag's last symbol
+    assert hand["cut inside the closing flag"][1] == end - 1
+    early = base[8:]  # 16 training symbols in front of the flag: the candidate opens at the first position there is
+    tie = hand["level tie"][0]
+    cuts = [(_padded(base[:end], nsym, right=True), nsym, 1), (_padded(base, nsym), end, 1), (_padded(base, nsym), end - 1, 0), (_padded(tie, nsym), 0, 0),
+            (_padded(early, nsym), 23, 0), (_padded(early, nsym), 24, 0), (_padded(early, nsym), 25, 0), (_padded(early, nsym), nsym, 1)]
+    names = ("level tie", "other polarity", "other alignment", "damaged", "abort", "flag off the byte boundary", "11 bytes", "10 bytes")
+    walks = [(_padded(hand[k][0], nsym), int(hand[k][0].size), hand[k][2]) for k in names]
+    out = []
+    for name, rows in (("cuts", cuts), ("walks", walks)):
+        out.append(dict(name=f"{name}, nsym {nsym}", planes=np.stack([r[0] for r in rows]), count_of=[int(r[1]) for r in rows], kept=[int(r[2]) for r in rows]))
+    return out
+
+
+def instant_of(W: int, step: float, s: int, p: int) -> int:
+    return W - 1 + int(np.rint(float(8 * s + p) * step))
+
+
+def frames_block(planes, count_of, W: int = FRAME_W, step: float = FRAME_STEP) -> tuple:
+    """(sorted [(phase, s, instant, bytes)], kept frames, closed candidates) of eight planes with their own counts."""
+    rows, closed = [], 0
+    for p in range(PHASES):
+        kept, c = frames_of(np.asarray(planes[p][: count_of[p]], dtype=np.int64))
+        closed += c
+        rows += [(p, int(s), instant_of(W, step, int(s), p), raw) for s, raw in kept]
+    return sorted(rows), len(rows), closed
+
+
+def check_frames(sc: dict, call, *, mapped: bool, capacity: int = 16) -> None:
+    """``call(planes_alloc, nsym, count_of, W, step, capacity, list_buf, slots_buf, counts_buf) -> (list, slots, counts)``
+    (int64, uint8, int64 numpy).  ``mapped``: the planes under v -> a v + b, which leaves every decision 16 v > sum as it
+    is; the kept frames must be the unmapped planes'."""
+    planes, count_of = sc["planes"], sc["count_of"]
+    nsym = planes.shape[1]
+    want, kept, closed = frames_block(planes, count_of)
+    assert [sum(1 for r in want if r[0] == p) for p in range(PHASES)] == sc["kept"] and kept > 0, sc["name"]
+    if "cuts" in sc["name"]:
+        assert {0, 23, 24, 25, nsym} <= set(count_of) and (7, 24) in {(r[0], r[1]) for r in want}
+        assert frames_block(planes, [nsym] * PHASES)[1] > kept  # the counts decide, not the planes
+    if mapped:
+        planes = np.stack([affine(v) for v in planes])
+        assert frames_block(planes, count_of) == (want, kept, closed) and int(planes.max()) > 2 ** 31 - 16_000
+    lst = np.full(4 * capacity + GUARD, SENT, dtype=np.int64)
+    slots = np.full(capacity * SLOT_BYTES + GUARD, 0xAA, dtype=np.uint8)
+    counts = np.array([99, 99, SENT, SENT], dtype=np.int64)
+    alloc = np.concatenate([np.ascontiguousarray(planes).reshape(-1), HOSTILE_I32])
+    lst, slots, counts = call(alloc, nsym, count_of, FRAME_W, FRAME_STEP, capacity, lst, slots, counts)
+    assert [int(x) for x in counts] == [kept, closed, SENT, SENT], sc["name"]
+    entries, data = lst[: 4 * capacity].reshape(-1, 4), slots[: capacity * SLOT_BYTES].reshape(capacity, -1)
+    assert (entries[kept:] == SENT).all() and (lst[4 * capacity :] == SENT).all() and (data[kept:] == 0xAA).all() and (slots[capacity * SLOT_BYTES :] == 0xAA).all()
+    got = sorted((int(p), int(s), int(at), data[i, : int(nb)].tobytes(), bool((data[i, int(nb) :] == 0).all())) for i, (p, s, at, nb) in enumerate(entries[:kept]))
+    assert got == [r + (True,) for r in want], sc["name"]
+
+
+def standin_frames_of(v, *, level32: bool = False, mul32: bool = False) -> tuple:
+    """``frames_of`` written position by position as k_ais_frames goes, with the two places an int32 could creep in."""
+    v = [int(x) for x in v]
+    kept, closed = [], 0
+    for s in range(24, len(v) + 1):
+        total = sum(v[s - 24 : s - 8])
+        if level32:
+            total = int(wrap32(total))
+
+        def m(j, total=total):
+            return int((int(wrap32(16 * v[j])) if mul32 else 16 * v[j]) > total)
+
+        b = [int(m(j) == m(j - 1)) for j in range(s - 22, s)]
+        if b[14:] != FLAG_BITS or not all(b[k] != b[k + 1] for k in range(13)):
+            continue
+        out, cur, nb, ones, got = bytearray(), 0, 0, 0, None
+        for j in range(s, len(v)):
+            bit = int(m(j) == m(j - 1))
+            if bit:
+                ones += 1
+                if ones == 6:
+                    if j + 1 < len(v) and m(j + 1) != m(j) and nb == 6:
+                        got = bytes(out)
+                    break
+            else:
+                stuffed, ones = ones == 5, 0
+                if stuffed:
+                    continue
+            cur |= bit << nb
+            nb += 1
+            if nb == 8:
+                if len(out) == MAX_FRAME:
+                    break
+                out.append(cur)
+                cur, nb = 0, 0
+        if got is None or len(got) < MIN_FRAME:
+            continue
+        closed += 1
+        if crc16(got[:-2]) == got[-2] | (got[-1] << 8):
+            kept.append((s, got))
+    return kept, closed
+
+
+def entry_frames(planes, nsym, count_of, W, step, capacity, lst, slots, counts, **breaks) -> None:
+    """iqa_ais_frames' checks, the cleared counters and the kernel's results in position order."""
+    if nsym < 0 or capacity < 0:
+        raise ValueError("negative length")
+    if count_of is None:
+        raise ValueError("NULL count table")
+    if counts is None:
+        raise ValueError("NULL device pointer")
+    if not window_ok(W):
+        raise ValueError("window must be 1 .. 3 IQA_AIS_MAX_SPS - 1")
+    if not step_ok(step):
+        raise ValueError("step must be sps / 8 with 5 <= sps <= IQA_AIS_MAX_SPS")
+    if any(c < 0 or c > nsym for c in count_of):
+        raise ValueError("count_of must be 0 .. nsym")
+    if nsym > MAX_NSYM:
+        raise ValueError("length out of range")
+    if nsym > 0 and (planes is None or (capacity > 0 and (lst is None or slots is None))):
+        raise ValueError("NULL device pointer")
+    counts[:2] = 0
+    if nsym == 0:
+        return
+    k = 0
+    for p in range(PHASES):
+        kept, closed = standin_frames_of(np.asarray(planes)[p * nsym : p * nsym + count_of[p]], **breaks)
+        counts[1] += closed
+        for s, raw in kept:
+            counts[0] += 1
+            if k < capacity:
+                lst[4 * k : 4 * k + 4] = (p, s, instant_of(W, step, s, p), len(raw))
+                slots[k * SLOT_BYTES : (k + 1) * SLOT_BYTES] = np.frombuffer(raw.ljust(SLOT_BYTES, b"\0"), dtype=np.uint8)
+                k += 1
+
+
+def frame_refusals() -> list:
+    """(what, nsym, count_of | None, W, step, capacity, v?, list?, slots?, counts?, message)."""
+    ok = [8] * PHASES
+    yes = (True,) * 4
+    return [("negative nsym", -1, ok, 29, 1.25, 4) + yes + ("negative",), ("negative capacity", 8, ok, 29, 1.25, -1) + yes + ("negative",),
+            ("NULL count table", 8, None, 29, 1.25, 4) + yes + ("NULL count table",), ("NULL counts", 8, ok, 29, 1.25, 4, True, True, True, False, "NULL"),
+            ("window 0", 8, ok, 0, 1.25, 4) + yes + ("window must be",), ("window 300", 8, ok, MAX_TAPS + 1, 1.25, 4) + yes + ("window must be",),
+            ("step below 5/8", 8, ok, 29, 0.624, 4) + yes + ("step must be",), ("step above 100/8", 8, ok, 29, 12.51, 4) + yes + ("step must be",),
+            ("a count above nsym", 8, [8, 8, 8, 9, 8, 8, 8, 8], 29, 1.25, 4) + yes + ("count_of must be",),
+            ("a negative count", 8, [8, 8, 8, 8, 8, 8, 8, -1], 29, 1.25, 4) + yes + ("count_of must be",),
+            ("nsym above 2^37", MAX_NSYM + 1, ok, 29, 1.25, 4) + yes + ("out of range",), ("NULL v", 8, ok, 29, 1.25, 4, False, True, True, True, "NULL"),
+            ("NULL list", 8, ok, 29, 1.25, 4, True, False, True, True, "NULL"), ("NULL slots", 8, ok, 29, 1.25, 4, True, True, False, True, "NULL")]
