@@ -309,8 +309,16 @@ int iqa_real_part(const void *z_dev, int64_t n, void *out_dev, void *stream);
  *                  decoders/ssb.py:65-80.
  * work_dev: scratch, at least iqa_scan_workspace_bytes(n) bytes.
  * The three run on the scan of iqa_demodulate below, from a float input to the unclipped output.
+ * y_dev must not alias x_dev: the one-launch form of iqa_deemphasis (iqa_scan_window) reads inputs in front of a
+ * workgroup's own range, and the last `window` inputs once more, while other workgroups write their outputs.
  */
 int64_t iqa_scan_workspace_bytes(int64_t n);
+/* ref: none (DeemphasisFilter.process is one sequential loop, decoders/nfm.py:48-62; this describes the scan's geometry).
+ * The de-emphasis scan runs in ONE launch where the pole forgets inside a workgroup's span: *window = the smallest multiple
+ * of 512 with alpha^window <= 2^-64, *span = positions per workgroup (the first `window` of them a warm-up from state 0,
+ * the rest its own; the first workgroup starts at index 0 from the carried state).  Returns 0 with both filled when that
+ * form is used for this pole (window <= span / 2), 1 when the three launches are kept (either pointer may be NULL). */
+int iqa_scan_window(double alpha, int64_t *window, int64_t *span);
 int iqa_deemphasis(const void *x_dev, int64_t n, double alpha, void *state_dev, void *y_dev, void *work_dev,
                    void *stream);
 int iqa_dc_block(const void *x_dev, int64_t n, double radius, void *state_dev, void *y_dev, void *work_dev,
@@ -319,7 +327,8 @@ int iqa_agc(const void *x_dev, int64_t n, double target, double decay, const voi
             int64_t n_resets, void *y_dev, void *work_dev, void *stream);
 
 /*
- * Whole demodulator + AudioWriter.write for a block of channel samples, in three launches.
+ * Whole demodulator + AudioWriter.write for a block of channel samples: three launches (reduce, carry, apply), or one
+ * for nfm where the de-emphasis pole forgets inside a workgroup's span (iqa_scan_window).
  * ref: decoder.process (processing.py:1128) for nfm / am / usb / lsb as listed above, followed by
  *      AudioWriter.write (processing.py:1147 -> :440-456) and the per-chunk rms statistic.
  * The source stage (discriminator / |z| / real) and the sink (pre-clip peak, clip +-0.99, per-segment
@@ -346,6 +355,12 @@ int iqa_demodulate(const iqa_demod_params *p, const void *z_dev, int64_t n, void
 int iqa_demodulate_from_reset(const iqa_demod_params *p, const void *z_dev, int64_t n, void *state_dev,
                               const void *seg_starts_dev, int64_t n_segs, void *peak_dev, void *sumsq_dev,
                               void *audio_out_dev, void *scratch_dev, void *work_dev, void *stream);
+
+/* ref: decoder setup / AudioWriter creation in ProcessingPipeline.run, processing.py:1040-1066, as a launch of its own:
+ * state_dev (32 bytes) becomes the block of a decoder that has seen nothing (prev = 1+0j, filter states 0), peak_dev
+ * (float[1], may be NULL) and sumsq_dev[0 .. n_sums) become 0.  For callers that can issue it on another stream ahead of
+ * time and then call iqa_demodulate; iqa_demodulate_from_reset does the same inside its own stream. */
+int iqa_demod_reset(void *state_dev, void *peak_dev, void *sumsq_dev, int64_t n_sums, void *stream);
 
 /* ref: AudioWriter.write, processing.py:440-456: peak = max(peak, max|a|) BEFORE the clip, then
  * clip to +-0.99.  peak_dev = float[1] (running, init 0).  In-place allowed (out_dev == a_dev).

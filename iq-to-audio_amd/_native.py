@@ -124,6 +124,7 @@ _SIGNATURES = {
     "iqa_envelope": (ctypes.c_int, [c_void_p, c_int64, c_void_p, c_void_p]),
     "iqa_real_part": (ctypes.c_int, [c_void_p, c_int64, c_void_p, c_void_p]),
     "iqa_scan_workspace_bytes": (c_int64, [c_int64]),
+    "iqa_scan_window": (ctypes.c_int, [c_double, ctypes.POINTER(c_int64), ctypes.POINTER(c_int64)]),
     "iqa_deemphasis": (ctypes.c_int, [c_void_p, c_int64, c_double, c_void_p, c_void_p, c_void_p, c_void_p]),
     "iqa_dc_block": (ctypes.c_int, [c_void_p, c_int64, c_double, c_void_p, c_void_p, c_void_p, c_void_p]),
     "iqa_agc": (ctypes.c_int, [c_void_p, c_int64, c_double, c_double, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
@@ -131,6 +132,7 @@ _SIGNATURES = {
                                       c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "iqa_demodulate_from_reset": (ctypes.c_int, [ctypes.POINTER(DemodParams), c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p,
                                       c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "iqa_demod_reset": (ctypes.c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     "iqa_writer_clip": (ctypes.c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
     "iqa_resample": (ctypes.c_int, [c_void_p, c_int64, c_void_p, c_int32, c_int32, c_int32, c_int64, c_int64, c_void_p,
                                     c_void_p, c_void_p]),

@@ -203,7 +203,7 @@ class ResidentCaptureRunner:
         dem = slot["dem"]
         side = self.aux if resident else None
         with D.on_stream(self.aux if resident else self.compute, self.compute):
-            dem.reset()
+            dem.reset(ahead=resident)  # (resident: the clear runs on the aux stream, beside the previous capture's tail)
         dem.prepare(self.n_dec, self.starts)
         # gate: compute stream, behind this capture's probes (if they are there), in front of its channelizer -- the
         # caller's timing event when there is one (it is recorded exactly there)

@@ -228,6 +228,148 @@ __device__ __forceinline__ bool block_has_restart(const FusedArgs &a, long long 
     return lo < a.n_segs && a.segs[lo] < hi_i;
 }
 
+// ---- the sink of the one-launch form ----------------------------------------------------------------------------
+// (k_fused_apply below carries the same steps inline: moving it onto these helpers took its NFM instance from 80 to 111
+// registers and the AGC's from 90 to 120 -- six and five resident waves per SIMD to four -- so it is left as it was)
+
+// The segment (reference chunk) of the first and of the last of a block's samples, counted by the whole block in ONE
+// round of loads (a two-thread binary search in front of the first barrier cost eight dependent global loads per block).
+// `seg_first`: this thread's share of the chunk starts, a.segs[tid], loaded by the caller in front of its tile's loads;
+// s_seg[0..1] hold -1 (behind a barrier).  The counts are complete behind the block's next barrier.
+template <int THREADS>
+__device__ __forceinline__ void sink_count_segments(const FusedArgs &a, long long seg_first, long long first, long long last,
+                                                    long long *s_seg)
+{
+    const int tid = threadIdx.x, lane = tid & 63;
+    int c0 = (tid < a.n_segs) && seg_first <= first, c1 = (tid < a.n_segs) && seg_first <= last;
+    for (long long kk = tid + THREADS; kk < a.n_segs; kk += THREADS) {
+        const long long st = a.segs[kk];
+        c0 += st <= first;
+        c1 += st <= last;
+    }
+    c0 = static_cast<int>(wave_sum(static_cast<float>(c0)));
+    c1 = static_cast<int>(wave_sum(static_cast<float>(c1)));
+    if (lane == 0 && (c0 | c1)) {
+        atomicAdd(reinterpret_cast<unsigned long long *>(&s_seg[0]), static_cast<unsigned long long>(c0));
+        atomicAdd(reinterpret_cast<unsigned long long *>(&s_seg[1]), static_cast<unsigned long long>(c1));
+    }
+}
+
+// A block's samples lie inside one reference chunk (`uniform`) or, a chunk being >= 40 k samples, straddle exactly one
+// boundary (`simple`): the squares go to a low and a high running sum split at that boundary, reduced over the block, two
+// atomics per block at most.  Only blocks with several boundaries (chunks shorter than a block's range) take the general
+// per-thread path with its own look-ups.
+struct SinkPlan {
+    bool stats, uniform, simple, general;
+    long long seg0, seg1, bnd;  // bnd: first index of the high part
+    int sub;                    // this block's sub-slot of a chunk's sums
+};
+__device__ __forceinline__ SinkPlan sink_plan(const FusedArgs &a, bool stats, const long long *s_seg)
+{
+    SinkPlan p;
+    p.stats = stats;
+    p.seg0 = stats ? s_seg[0] : -1;
+    p.seg1 = stats ? s_seg[1] : -1;
+    p.uniform = stats && (p.seg0 == p.seg1);
+    p.simple = stats && (p.seg1 == p.seg0 + 1);
+    p.general = stats && !p.uniform && !p.simple;
+    p.bnd = a.n;
+    if (p.simple) p.bnd = a.segs[p.seg1];
+    p.sub = blockIdx.x & (IQA_SUMSQ_SLOTS - 1);
+    return p;
+}
+
+struct SinkAcc {
+    float pk = 0.f;
+    double run = 0.0, run_hi = 0.0;
+    long long seg = 0;  // general path: the segment `run` belongs to
+};
+
+// one pre-clip value v at index idx: peak, sums; returns the value to store
+template <int SINK>
+__device__ __forceinline__ float sink_item(const FusedArgs &a, const SinkPlan &p, SinkAcc &k, float v, long long idx)
+{
+    if constexpr (SINK != K_CLIP) return v;
+    k.pk = fmaxf(k.pk, fabsf(v));
+    if (p.stats) {
+        const double vv = static_cast<double>(v) * static_cast<double>(v);
+        double run = k.run, run_hi = k.run_hi;  // (values, not members: the two sums must stay in registers)
+        long long seg = k.seg;
+        if (p.general) {
+            while (seg + 1 < a.n_segs && a.segs[seg + 1] <= idx) {
+                if (run != 0.0) atomicAdd(&a.sumsq[seg * IQA_SUMSQ_SLOTS + p.sub], run);
+                run = 0.0;
+                ++seg;
+            }
+            run += vv;
+        } else {
+            const bool low = idx < p.bnd;
+            run += low ? vv : 0.0;
+            run_hi += low ? 0.0 : vv;
+        }
+        k.run = run;
+        k.run_hi = run_hi;
+        k.seg = seg;
+    }
+    return fminf(fmaxf(v, -0.99f), 0.99f);
+}
+
+// general path: what a thread holds goes out (at the end of its run of consecutive samples)
+__device__ __forceinline__ void sink_flush_general(const FusedArgs &a, const SinkPlan &p, SinkAcc &k)
+{
+    if (p.general && k.run != 0.0) atomicAdd(&a.sumsq[k.seg * IQA_SUMSQ_SLOTS + p.sub], k.run);
+    if (p.general) k.run = 0.0;
+}
+
+// the block's peak and sums: wave reductions, one barrier, at most three atomics by thread 0
+template <int WAVES>
+__device__ __forceinline__ void sink_finish(const FusedArgs &a, const SinkPlan &p, SinkAcc &k, float *s_pk, double *s_sq)
+{
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    sink_flush_general(a, p, k);
+    const float pk = wave_max(k.pk);
+    const double wlo = (p.stats && !p.general) ? wave_sum(k.run) : 0.0;
+    const double whi = p.simple ? wave_sum(k.run_hi) : 0.0;
+    if (lane == 0) {
+        s_pk[wave] = pk;
+        s_sq[wave] = wlo;
+        s_sq[WAVES + wave] = whi;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        float m = s_pk[0];
+        double lo = s_sq[0], hi = s_sq[WAVES];
+#pragma unroll
+        for (int w = 1; w < WAVES; ++w) {
+            m = fmaxf(m, s_pk[w]);
+            lo += s_sq[w];
+            hi += s_sq[WAVES + w];
+        }
+        if (a.peak_bits != nullptr) {
+            // thousands of atomics on one word serialise in L2 (~11 ns each): skip the ones that cannot
+            // raise the running maximum (a stale read only costs a redundant atomic, never a wrong result)
+            const unsigned int mb = __float_as_uint(m);
+            if (mb > __hip_atomic_load(a.peak_bits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(a.peak_bits, mb);
+        }
+        if (p.stats && !p.general) atomicAdd(&a.sumsq[p.seg0 * IQA_SUMSQ_SLOTS + p.sub], lo);
+        if (p.simple) atomicAdd(&a.sumsq[p.seg1 * IQA_SUMSQ_SLOTS + p.sub], hi);
+    }
+}
+
+// a thread's eight values to y[base ..], those with index in [lo, hi): 32 contiguous, aligned bytes as two 16-byte stores
+__device__ __forceinline__ void store_items(const FusedArgs &a, long long base, long long lo, long long hi, const float (&vout)[SC_ITEMS])
+{
+    if (a.y_aligned && base >= lo && base + SC_ITEMS <= hi) {
+        float4 *yp = reinterpret_cast<float4 *>(a.y + base);
+        yp[0] = make_float4(vout[0], vout[1], vout[2], vout[3]);
+        yp[1] = make_float4(vout[4], vout[5], vout[6], vout[7]);
+    } else {
+#pragma unroll
+        for (int i = 0; i < SC_ITEMS; ++i)
+            if (base + i >= lo && base + i < hi) a.y[base + i] = vout[i];
+    }
+}
+
 template <int OP, int SRC>
 __global__ __launch_bounds__(SC_THREADS) void k_fused_reduce(FusedArgs a)
 {
@@ -458,9 +600,169 @@ __global__ __launch_bounds__(SC_THREADS) void k_fused_apply(FusedArgs a, float2 
     }
 }
 
+// ---- the one-launch form of the de-emphasis scan ----------------------------------------------------------
+//
+// The de-emphasis pole forgets: alpha^W <= 2^-64 after W samples (W from scan_window below, a multiple of 512).  A
+// workgroup therefore needs no state from its predecessors: it covers FW_SPAN consecutive positions, the first W of
+// them a warm-up from state 0 (computed, not stored, not in the peak or the sums), the other FW_SPAN - W its own.
+// The state it ignores is a y of this call, |y| <= S, so its first own sample is off by at most 2^-64 S: 2^-17 of the
+// floor term 64 * 2^-53 * S / (1 - alpha) that the scan's own roundings are allowed.  Block 0 starts at index 0 from
+// the carried state (the exact chain), and is the only block that reads the caller's state block; it also writes the
+// outgoing state, from a warm-up of its own over the last W samples where the call has more than one block.  So no
+// block waits for another: no flags, no counters, nothing kept in the workspace.
+// A block runs its span in FW_ROUNDS rounds of FW_THREADS * SC_ITEMS positions, handing the state from round to round.
+// 256 x 8 x 4 by measurement at config 2 (n = 5 769 231, W = 1536): 41 us against 44 for 512 x 8 x 2, 43 for
+// 512 x 8 x 4, 52 for 256 x 8 x 8, 60 for 1024 x 8 x 1 and 84 for 1024 x 8 x 2 -- 867 workgroups of four waves at 91 registers
+// are all resident at once (five waves per SIMD), and a longer span only adds serial rounds.
+constexpr int FW_THREADS = 256;
+constexpr int FW_ROUNDS = 4;
+constexpr int FW_WAVES = FW_THREADS / kWave;
+constexpr long long FW_ROUND = static_cast<long long>(FW_THREADS) * SC_ITEMS;
+constexpr long long FW_SPAN = FW_ROUND * FW_ROUNDS;
+
+// 0 and the window W where the one-launch form is used for this pole, 1 where the three launches are kept (no pole in
+// (0, 1), or a W above half a span: a long time constant, a high channel rate).  Depends on alpha alone.
+static int scan_window(double alpha, long long *window)
+{
+    if (!(alpha > 0.0 && alpha < 1.0)) return 1;
+    const double need = 64.0 * log(2.0) / -log(alpha);  // alpha^need = 2^-64
+    if (!(need < static_cast<double>(FW_SPAN))) return 1;
+    long long w = 512 * static_cast<long long>(ceil(need / 512.0));
+    if (w < 512) w = 512;
+    while (w > 512 && pow(alpha, static_cast<double>(w - 512)) <= 0x1p-64) w -= 512;  // (the logarithms' rounding)
+    while (pow(alpha, static_cast<double>(w)) > 0x1p-64) w += 512;
+    if (2 * w > FW_SPAN) return 1;
+    *window = w;
+    return 0;
+}
+
+// One round: the source values u of positions [base, base + 8) and the state in front of `base`, given the state
+// `s_run` in front of the round; `s_run` becomes the state behind the round.  Positions at or above `end` are identity
+// maps.  `skip0`: the value at index 0 is taken as 0 (a warm-up that begins at index 0 in a block other than block 0,
+// which does not read the carried prev).  One barrier; `s_w` is this round's table (the caller alternates two).
+template <int SRC>
+__device__ __forceinline__ double windowed_round(const FusedArgs &a, long long base, long long end, bool skip0, Aff *s_w,
+                                                 double &s_run, float (&u)[SC_ITEMS])
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    float ub;
+    load_u<F_DEEMPH, SRC>(a, base, u, ub);
+    if (skip0 && base == 0) u[0] = 0.f;
+    Aff t{1.0, 0.0};
+#pragma unroll
+    for (int i = 0; i < SC_ITEMS; ++i)
+        if (base + i < end) t = then(t, fmap<F_DEEMPH>(a, base + i, u[i], 0.f, false));
+    const Aff inc = wave_inclusive(t, lane);
+    if (lane == kWave - 1) s_w[wave] = inc;
+    __syncthreads();
+    const double ea = __shfl_up(inc.A, 1, kWave), eb = __shfl_up(inc.B, 1, kWave);
+    Aff ex = (lane == 0) ? Aff{1.0, 0.0} : Aff{ea, eb};
+    Aff acc{1.0, 0.0}, wpre{1.0, 0.0};
+#pragma unroll
+    for (int w = 0; w < FW_WAVES; ++w) {
+        if (w == wave) wpre = acc;
+        acc = then(acc, s_w[w]);
+    }
+    ex = then(wpre, ex);
+    const double s = fma(ex.A, s_run, ex.B);
+    s_run = fma(acc.A, s_run, acc.B);  // the same operations in every thread: one value for the whole block
+    return s;
+}
+
+// clears the peak and the per-chunk sums in front of a windowed launch (iqa_demodulate_from_reset); with `state`, also
+// writes the state block of a decoder that has seen nothing (iqa_demod_reset)
+__global__ __launch_bounds__(FC_THREADS) void k_fused_clear(float *state, unsigned int *peak_bits, double *sumsq, long long n_sums)
+{
+    if (state != nullptr && threadIdx.x < 8) state[threadIdx.x] = threadIdx.x ? 0.f : 1.f;  // prev = 1 + 0j, filter states 0
+    if (threadIdx.x == 0 && peak_bits != nullptr) peak_bits[0] = 0u;
+    if (sumsq != nullptr)
+        for (long long i = threadIdx.x; i < n_sums; i += FC_THREADS) sumsq[i] = 0.0;
+}
+
+template <int SRC, int SINK>
+__global__ __launch_bounds__(FW_THREADS) void k_fused_windowed(FusedArgs a, long long window, float2 *prev_out, double *st_out)
+{
+    __shared__ Aff s_w[2][FW_WAVES];
+    __shared__ float s_pk[FW_WAVES];
+    __shared__ double s_sq[2 * FW_WAVES];  // low | high part of an own range that straddles a chunk boundary
+    __shared__ long long s_seg[2];
+    const int tid = threadIdx.x;
+    const long long own = FW_SPAN - window;
+    const long long own0 = static_cast<long long>(blockIdx.x) * own, own1 = min(own0 + own, a.n);
+    const long long start = blockIdx.x ? own0 - window : 0;  // >= 0: window <= own
+    const bool skip0 = blockIdx.x != 0;
+    const bool stats = (SINK == K_CLIP) && a.sumsq != nullptr && a.n_segs > 0;
+    double s_run = (blockIdx.x == 0 && !a.fresh) ? a.st[0] : 0.0;
+    long long seg_first = 0;
+    if (stats && tid < a.n_segs) seg_first = a.segs[tid];
+    if (stats && tid < 2) s_seg[tid] = -1;
+    if (stats) {
+        __syncthreads();  // s_seg initialised
+        sink_count_segments<FW_THREADS>(a, seg_first, own0, own1 - 1, s_seg);
+    }
+    SinkPlan plan{};
+    SinkAcc acc;
+    for (int r = 0; r < FW_ROUNDS; ++r) {
+        const long long rbase = start + r * FW_ROUND;
+        if (rbase >= own1) break;  // (the whole block leaves together)
+        const long long base = rbase + static_cast<long long>(tid) * SC_ITEMS;
+        float u[SC_ITEMS];
+        double s = windowed_round<SRC>(a, base, own1, skip0, s_w[r & 1], s_run, u);
+        if (r == 0) plan = sink_plan(a, stats, s_seg);  // behind the round's barrier: the counts are complete
+        if (base + SC_ITEMS <= own0 || base >= own1) continue;  // warm-up only, or behind the end: nothing to emit
+        acc.seg = plan.seg0;
+        if (plan.general) acc.seg = lower_bound_ll(a.segs, a.n_segs, max(base, own0) + 1) - 1;
+        float vout[SC_ITEMS];
+#pragma unroll
+        for (int i = 0; i < SC_ITEMS; ++i) {
+            const long long idx = base + i;
+            if (idx < own1) {
+                const Aff mi = fmap<F_DEEMPH>(a, idx, u[i], 0.f, false);
+                s = fma(mi.A, s, mi.B);
+            }
+            vout[i] = 0.f;
+            if (idx >= own0 && idx < own1) vout[i] = sink_item<SINK>(a, plan, acc, static_cast<float>(s), idx);
+        }
+        sink_flush_general(a, plan, acc);  // (a thread's samples of the next round do not follow these)
+        store_items(a, base, own0, own1, vout);
+    }
+    if constexpr (SINK == K_CLIP) sink_finish<FW_WAVES>(a, plan, acc, s_pk, s_sq);
+    if (blockIdx.x != 0) return;
+    // Block 0 hands the streaming state to the next call.  Every read of the incoming state (round 0, in front of its
+    // barrier) lies behind it.  One block: s_run is the exact chain's state at n - 1.  More: a warm-up over the last
+    // `window` samples (from a multiple of 8, so the vector loads stay aligned), rounds of its own.
+    if (a.nblocks > 1) {
+        // t0 >= 0 (n > own >= window); it is 0 only where window == own and n < window + 8: the warm-up then runs from
+        // index 0 from state 0, not from the carried state, which costs alpha^(n-1) |state| <= 2^-64 S like any other
+        const long long t0 = (a.n - window) & ~7LL;
+        s_run = 0.0;
+        __syncthreads();  // the last round's table has been read
+        for (int r = 0; t0 + r * FW_ROUND < a.n; ++r) {
+            float u[SC_ITEMS];
+            windowed_round<SRC>(a, t0 + r * FW_ROUND + static_cast<long long>(tid) * SC_ITEMS, a.n, false, s_w[r & 1], s_run, u);
+        }
+    }
+    if (tid == 0) {
+        if constexpr (SRC == S_QUAD) prev_out[0] = a.z[a.n - 1];
+        st_out[0] = s_run;
+    }
+}
+
 template <int OP, int SRC, int SINK>
 static int launch_fused(FusedArgs a, float2 *prev_out, double *st_out, void *work, hipStream_t s)
 {
+    if constexpr (OP == F_DEEMPH) {
+        long long window;
+        if (scan_window(a.p0, &window) == 0) {
+            const long long own = FW_SPAN - window;
+            a.nblocks = static_cast<int>((a.n + own - 1) / own);
+            if (a.fresh && (a.peak_bits != nullptr || a.sumsq != nullptr))
+                hipLaunchKernelGGL(k_fused_clear, dim3(1), dim3(FC_THREADS), 0, s, static_cast<float *>(nullptr), a.peak_bits, a.sumsq,
+                                   a.n_segs * IQA_SUMSQ_SLOTS);
+            hipLaunchKernelGGL((k_fused_windowed<SRC, SINK>), dim3(a.nblocks), dim3(FW_THREADS), 0, s, a, window, prev_out, st_out);
+            return check_launch("windowed demodulator");
+        }
+    }
     a.nblocks = static_cast<int>((a.n + SC_TILE - 1) / SC_TILE);
     char *w = static_cast<char *>(work);
     a.agg = reinterpret_cast<Aff *>(w);
@@ -549,6 +851,25 @@ extern "C" int iqa_demodulate_from_reset(const iqa_demod_params *p, const void *
 {
     if (n == 0) return fail_inval("iqa_demodulate_from_reset needs samples (an empty block resets nothing)");
     return demodulate(p, z_dev, n, state_dev, seg_starts_dev, n_segs, peak_dev, sumsq_dev, audio_out_dev, scratch_dev, work_dev, stream, 1);
+}
+
+extern "C" int iqa_demod_reset(void *state_dev, void *peak_dev, void *sumsq_dev, int64_t n_sums, void *stream)
+{
+    if (n_sums < 0) return fail_inval("negative length");
+    if (!state_dev) return fail_inval("NULL device pointer");
+    if (n_sums > 0 && !sumsq_dev) return fail_inval("sumsq is NULL");
+    hipLaunchKernelGGL(k_fused_clear, dim3(1), dim3(FC_THREADS), 0, as_stream(stream), static_cast<float *>(state_dev),
+                       static_cast<unsigned int *>(peak_dev), static_cast<double *>(sumsq_dev), (long long)n_sums);
+    return check_launch("k_fused_clear");
+}
+
+extern "C" int iqa_scan_window(double alpha, int64_t *window, int64_t *span)
+{
+    long long w = 0;
+    if (scan_window(alpha, &w) != 0) return 1;
+    if (window != nullptr) *window = w;
+    if (span != nullptr) *span = FW_SPAN;
+    return 0;
 }
 
 extern "C" int64_t iqa_scan_workspace_bytes(int64_t n)

@@ -646,9 +646,12 @@ class ChannelDemod:
         self._sumsq = self._blk[64:].view(torch.float64)
         self._fresh = True
 
-    def reset(self, force: bool = False) -> None:
-        """Back to a decoder that has seen nothing (states, peak, per-chunk sums): one small H2D copy from a
-        pinned image (pinned on the first reset: pin_memory() costs milliseconds)."""
+    def reset(self, force: bool = False, ahead: bool = False) -> None:
+        """Back to a decoder that has seen nothing (states, peak, per-chunk sums).  Nothing is launched here: the next
+        ``process`` starts from the initial state by itself (``iqa_demodulate_from_reset``).  ``ahead=True`` (nfm): the
+        current stream is a side stream that the stream of ``process`` will wait for -- the state block, the peak and the
+        sums are put back there now (``iqa_demod_reset``, one small launch), and ``process`` is the plain
+        ``iqa_demodulate``: one launch on its stream instead of a clear and a scan."""
         self.chunk_sumsq = []
         if self.pocsag_core is not None:  # (before the early return: POCSAG state is not part of ``_fresh``)
             self.pocsag_core.reset()
@@ -667,6 +670,12 @@ class ChannelDemod:
             self.ais_core.reset()
             self._ais_prev = D.from_numpy(np.array([1 + 0j], dtype=np.complex64))
         if self._fresh and not force:  # (force: a step being captured into a graph must not depend on what ran before it)
+            return
+        if ahead and self.params.mode == N.DEMOD_MODE["nfm"]:
+            N.call("iqa_demod_reset", N.ptr(self.state_dev), N.ptr(self.peak_dev), N.ptr(self._sumsq), c_int64(self._sumsq.numel()),
+                   N.stream_ptr())
+            self._from_reset = False
+            self._fresh = True
             return
         # nothing is copied: the next ``process`` starts from the initial state by itself and clears the peak and the
         # per-chunk sums (iqa_demodulate_from_reset) -- one node less per capture in a captured step

@@ -1,4 +1,4 @@
-"""Scratch: the fused demodulator (iqa_demodulate: reduce / carry / apply / finish) alone on the bench shape, with and
+"""Scratch: the fused demodulator (iqa_demodulate: nfm in one windowed launch, am / ssb as reduce / carry / apply) alone on the bench shape, with and
 without the per-chunk statistics, and the resampler alone."""
 import sys
 from pathlib import Path
