@@ -14,6 +14,7 @@ import numpy as np
 from . import _dev as D
 from . import _native as N
 from . import dsp_plan as P
+from .decoders.side import NAMES
 from .processing import (PRECISION_GUARD, ChannelBank, ChannelDemod, Channelizer, MixSignProbe, Resampler48k, _ChannelKernel,
                          base_precision, immutable_taps, pick_precision, probe_targets, reserve_pinned_scalars)
 
@@ -26,52 +27,13 @@ def reject_wfm(modes) -> None:
                          "use ProcessingPipeline / MultiChannelPipeline")
 
 
-def reject_pocsag(pocsag) -> None:
-    """POCSAG decoding stores a run's bit integrators and searches them at the end: the resident
-    runners keep no per-run store, so ``pocsag=True`` is a ``ValueError`` up front, as a wfm target is."""
-    if pocsag:
-        raise ValueError("pocsag=True is not supported by the resident batch runners or sharded runs: "
-                         "use ProcessingPipeline / MultiChannelPipeline")
-
-
-def reject_ax25(ax25) -> None:
-    """AX.25 decoding stores a run's slicer plane and searches it at the end: ``ax25=True`` is a
-    ``ValueError`` up front, as ``pocsag=True`` is."""
-    if ax25:
-        raise ValueError("ax25=True is not supported by the resident batch runners or sharded runs: "
-                         "use ProcessingPipeline / MultiChannelPipeline")
-
-
-def reject_tones(tones) -> None:
-    """Tone detection stores a run's decimated discriminator output and runs the banks at the end:
-    ``tones=True`` is a ``ValueError`` up front, as ``ax25=True`` is."""
-    if tones:
-        raise ValueError("tones=True is not supported by the resident batch runners or sharded runs: "
-                         "use ProcessingPipeline / MultiChannelPipeline")
-
-
-def reject_acars(acars) -> None:
-    """ACARS decoding stores a run's envelope and searches it at the end: ``acars=True`` is a
-    ``ValueError`` up front, as ``ax25=True`` is."""
-    if acars:
-        raise ValueError("acars=True is not supported by the resident batch runners or sharded runs: "
-                         "use ProcessingPipeline / MultiChannelPipeline")
-
-
-def reject_ais(ais) -> None:
-    """AIS decoding stores a run's filter output and searches it at the end: ``ais=True`` is a
-    ``ValueError`` up front, as ``ax25=True`` is."""
-    if ais:
-        raise ValueError("ais=True is not supported by the resident batch runners or sharded runs: "
-                         "use ProcessingPipeline / MultiChannelPipeline")
-
-
-def reject_adsb(adsb) -> None:
-    """Mode S decoding stores a run's quantised envelope and searches it at the end: ``adsb=True`` is a
-    ``ValueError`` up front, as ``acars=True`` is."""
-    if adsb:
-        raise ValueError("adsb=True is not supported by the resident batch runners or sharded runs: "
-                         "use ProcessingPipeline / MultiChannelPipeline")
+def reject_side_decoders(**flags) -> None:
+    """Every side decoder (``decoders/side.py``) stores a run's planes and searches them at the end; the resident runners
+    keep no per-run store, so a switched-on decoder is a ``ValueError`` up front, as a wfm target is."""
+    for name in NAMES:
+        if flags.get(name):
+            raise ValueError(f"{name}=True is not supported by the resident batch runners or sharded runs: "
+                             "use ProcessingPipeline / MultiChannelPipeline")
 
 
 def _rank(precision: str) -> int:
@@ -127,12 +89,7 @@ class ResidentCaptureRunner:
         another.  Only for captures that are complete in device memory when ``submit_captured`` is called (the replay is not
         ordered behind the caller's stream)."""
         reject_wfm([demod_mode])
-        reject_pocsag(pocsag)
-        reject_ax25(ax25)
-        reject_tones(tones)
-        reject_acars(acars)
-        reject_ais(ais)
-        reject_adsb(adsb)
+        reject_side_decoders(pocsag=pocsag, ax25=ax25, tones=tones, acars=acars, ais=ais, adsb=adsb)
         torch = D.torch_mod()
         if slots is not None:
             if slots < 2:
@@ -510,12 +467,7 @@ class ResidentBankRunner:
         """``targets``: dicts with ``freq_offset``, and optionally ``bandwidth`` (12 500), ``demod_mode`` ("nfm"),
         ``deemph_us`` (300), ``agc_enabled`` (True), ``mix_sign`` (None = probe), ``precision`` (None = by demodulator)."""
         reject_wfm([t.get("demod_mode") for t in targets])
-        reject_pocsag(pocsag)
-        reject_ax25(ax25)
-        reject_tones(tones)
-        reject_acars(acars)
-        reject_ais(ais)
-        reject_adsb(adsb)
+        reject_side_decoders(pocsag=pocsag, ax25=ax25, tones=tones, acars=acars, ais=ais, adsb=adsb)
         torch = D.torch_mod()
         if not targets:
             raise ValueError("at least one target is required")
@@ -697,12 +649,7 @@ def demodulate_sharded(targets: list, *, sample_rate: float, n_frames: int, axis
     from . import dist as DS
 
     reject_wfm([t.get("demod_mode") for t in targets])
-    reject_pocsag(pocsag)
-    reject_ax25(ax25)
-    reject_tones(tones)
-    reject_acars(acars)
-    reject_ais(ais)
-    reject_adsb(adsb)
+    reject_side_decoders(pocsag=pocsag, ax25=ax25, tones=tones, acars=acars, ais=ais, adsb=adsb)
     torch = D.torch_mod()
     if axis not in ("channels", "captures"):
         raise ValueError("axis must be 'channels' or 'captures'")

@@ -23,6 +23,7 @@ import sys
 from pathlib import Path
 
 from .benchmark import run_benchmark
+from .decoders.side import SIDE_DECODERS
 from .processing import MultiChannelPipeline, ProcessingCancelled, ProcessingConfig, ProcessingPipeline
 from .squelch import AudioPostOptions, SquelchConfig, gather_audio_targets, process_audio_batch
 
@@ -98,26 +99,8 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--demod", dest="demod", choices=["nfm", "am", "usb", "lsb", "ssb", "wfm", "none"], default="nfm")
     p.add_argument("--deemph", dest="deemph_us", type=positive_float, default=ModeDefault(300.0),
                    help="De-emphasis time constant in microseconds (default 300; 50 for --demod wfm, 75 in the Americas).")
-    p.add_argument("--rds", dest="rds", action="store_true",
-                   help="With --demod wfm: decode RDS (PI, PS, RadioText) of every station and write <output stem>.rds.json.")
-    p.add_argument("--pocsag", dest="pocsag", action="store_true",
-                   help="With --demod nfm: decode POCSAG pager traffic (512 / 1200 / 2400 baud) of every target, print one line "
-                        "per message and write <output stem>.pocsag.json.")
-    p.add_argument("--ax25", dest="ax25", action="store_true",
-                   help="With --demod nfm: decode 1200-baud Bell-202 AX.25 frames (APRS, packet) of every target, print one TNC2-style "
-                        "line per frame and write <output stem>.ax25.json.")
-    p.add_argument("--tones", dest="tones", action="store_true",
-                   help="With --demod nfm: detect the CTCSS tone and the DTMF digits of every target, print one line per tone "
-                        "event and digit sequence and write <output stem>.tones.json.")
-    p.add_argument("--acars", dest="acars", action="store_true",
-                   help="With --demod am: decode ACARS aircraft messages (2400 bit/s MSK on an airband AM channel) of every target, "
-                        "print one line per message and write <output stem>.acars.json.")
-    p.add_argument("--ais", dest="ais", action="store_true",
-                   help="With --demod nfm: decode AIS ship traffic (9600 bit/s GMSK; 161.975 / 162.025 MHz) of every target, print "
-                        "one line per message and its !AIVDM sentences and write <output stem>.ais.json.  An unset --bw becomes 25 000.")
-    p.add_argument("--adsb", dest="adsb", action="store_true",
-                   help="With --demod am: decode ADS-B / Mode S squitters (1090 MHz; DF11, 17, 18) of every target, print one line per "
-                        "message and write <output stem>.adsb.json.  An unset --bw and an unset --fs-ch become 2 000 000.")
+    for e in SIDE_DECODERS:
+        p.add_argument(f"--{e.name}", dest=e.name, action="store_true", help=e.help)
     p.add_argument("--no-agc", dest="agc_enabled", action="store_false")
     p.add_argument("--out", dest="output_path", type=Path)
     p.add_argument("--dump-iq", dest="dump_iq", type=Path)
@@ -222,20 +205,9 @@ def main(argv: list[str] | None = None) -> int:
     if args.audio_post_path and not 0.0 <= args.audio_post_percentile <= 1.0:
         parser.error("--audio-post-noise-percentile must be between 0.0 and 1.0.")
     logging.basicConfig(level=logging.DEBUG if args.verbose else logging.INFO, format="%(levelname)s %(message)s")
-    if args.rds and args.demod != "wfm":
-        parser.error("--rds needs --demod wfm.")
-    if args.pocsag and args.demod != "nfm":
-        parser.error("--pocsag needs --demod nfm.")
-    if args.ax25 and args.demod != "nfm":
-        parser.error("--ax25 needs --demod nfm.")
-    if args.tones and args.demod != "nfm":
-        parser.error("--tones needs --demod nfm.")
-    if args.acars and args.demod != "am":
-        parser.error("--acars needs --demod am.")
-    if args.ais and args.demod != "nfm":
-        parser.error("--ais needs --demod nfm.")
-    if args.adsb and args.demod != "am":
-        parser.error("--adsb needs --demod am.")
+    for e in SIDE_DECODERS:
+        if getattr(args, e.name) and args.demod != e.mode:
+            parser.error(f"--{e.name} needs --demod {e.mode}.")
     if args.audio_post_path:
         return run_audio_post(args)
     frequencies = list(args.target_freqs or [])
@@ -289,7 +261,7 @@ def main(argv: list[str] | None = None) -> int:
     LOG.info("=== Processing %d target(s) in one pass over %s ===", len(configs), args.input_path)
     try:
         # the reference loops whole pipelines over the targets (cli.py:683-710); here the capture is read once
-        extras = dict(rds=args.rds, pocsag=args.pocsag, ax25=args.ax25, tones=args.tones, acars=args.acars, ais=args.ais, adsb=args.adsb)
+        extras = {e.name: getattr(args, e.name) for e in SIDE_DECODERS}
         runner = MultiChannelPipeline(configs, **extras) if len(configs) > 1 else ProcessingPipeline(configs[0], **extras)
         results = runner.run(progress_sink=None)
         results = results if len(configs) > 1 else [results]
@@ -304,56 +276,15 @@ def main(argv: list[str] | None = None) -> int:
     for config, result in zip(configs, results):
         LOG.info("%.0f Hz: decimation %d -> %.2f Hz, mixer sign %+d, audio peak %.4f", config.target_freq,
                  result.decimation, result.fs_channel, result.mix_sign, result.audio_peak)
-    if args.rds and not args.probe_only:
-        stations = runner.rds if len(configs) > 1 else [runner.rds]
-        targets = runner.output_paths if len(configs) > 1 else [runner.output_path]
-        for config, station, wav in zip(configs, stations, targets):
-            print(f"{config.target_freq:.0f} Hz: " + (station.line() if station is not None else "no RDS"))
-            wav.with_name(wav.stem + ".rds.json").write_text(json.dumps(None if station is None else station.to_json(), indent=1) + "\n")
-    if args.pocsag and not args.probe_only:
-        decoded = runner.pocsag if len(configs) > 1 else [runner.pocsag]
-        targets = runner.output_paths if len(configs) > 1 else [runner.output_path]
-        for config, res, wav in zip(configs, decoded, targets):
-            for msg in (res.messages if res is not None else []):
-                print(f"{config.target_freq:.0f} Hz: {msg.line()}")
-            wav.with_name(wav.stem + ".pocsag.json").write_text(json.dumps(None if res is None else res.to_json(), indent=1) + "\n")
-    if args.ax25 and not args.probe_only:
-        decoded = runner.ax25 if len(configs) > 1 else [runner.ax25]
-        targets = runner.output_paths if len(configs) > 1 else [runner.output_path]
-        for config, res, wav in zip(configs, decoded, targets):
-            for frame in (res.frames if res is not None else []):
-                print(f"{config.target_freq:.0f} Hz: AX25 {frame.line()}")
-            wav.with_name(wav.stem + ".ax25.json").write_text(json.dumps(None if res is None else res.to_json(), indent=1) + "\n")
-    if args.tones and not args.probe_only:
-        decoded = runner.tones if len(configs) > 1 else [runner.tones]
-        targets = runner.output_paths if len(configs) > 1 else [runner.output_path]
-        for config, res, wav in zip(configs, decoded, targets):
-            for line in (res.lines() if res is not None else []):
-                print(f"{config.target_freq:.0f} Hz: {line}")
-            wav.with_name(wav.stem + ".tones.json").write_text(json.dumps(None if res is None else res.to_json(), indent=1) + "\n")
-    if args.acars and not args.probe_only:
-        decoded = runner.acars if len(configs) > 1 else [runner.acars]
-        targets = runner.output_paths if len(configs) > 1 else [runner.output_path]
-        for config, res, wav in zip(configs, decoded, targets):
-            for msg in (res.messages if res is not None else []):
-                print(f"{config.target_freq:.0f} Hz: {msg.line()}")
-            wav.with_name(wav.stem + ".acars.json").write_text(json.dumps(None if res is None else res.to_json(), indent=1) + "\n")
-    if args.ais and not args.probe_only:
-        decoded = runner.ais if len(configs) > 1 else [runner.ais]
-        targets = runner.output_paths if len(configs) > 1 else [runner.output_path]
-        for config, res, wav in zip(configs, decoded, targets):
-            for msg in (res.messages if res is not None else []):
-                print(f"{config.target_freq:.0f} Hz: {msg.line()}")
-                for sentence in msg.nmea:
-                    print(sentence)
-            wav.with_name(wav.stem + ".ais.json").write_text(json.dumps(None if res is None else res.to_json(), indent=1) + "\n")
-    if args.adsb and not args.probe_only:
-        decoded = runner.adsb if len(configs) > 1 else [runner.adsb]
-        targets = runner.output_paths if len(configs) > 1 else [runner.output_path]
-        for config, res, wav in zip(configs, decoded, targets):
-            for msg in (res.messages if res is not None else []):
-                print(f"{config.target_freq:.0f} Hz: {msg.line()}")
-            wav.with_name(wav.stem + ".adsb.json").write_text(json.dumps(None if res is None else res.to_json(), indent=1) + "\n")
+    for e in SIDE_DECODERS:
+        if not getattr(args, e.name) or args.probe_only:
+            continue
+        wavs = runner.output_paths if len(configs) > 1 else [runner.output_path]
+        decoded = getattr(runner, e.name) if len(configs) > 1 else [getattr(runner, e.name)]
+        for config, res, wav in zip(configs, decoded, wavs):
+            for line in e.lines(res, f"{config.target_freq:.0f} Hz: "):
+                print(line)
+            wav.with_name(f"{wav.stem}.{e.name}.json").write_text(json.dumps(None if res is None else res.to_json(), indent=1) + "\n")
     return 0
 
 

@@ -19,6 +19,7 @@ import numpy as np
 from .. import _dev as D
 from .. import _native as N
 from .. import dsp_plan as P
+from .common import SideStage, group_records, search_with_room
 
 LOG = logging.getLogger(__name__)
 
@@ -91,16 +92,6 @@ def parse_message(raw: bytes) -> dict:
     return out
 
 
-def _group_of(groups: list, raw: bytes, at: int, reach: int):
-    """The latest group with these bytes whose first start instant lies within ``reach`` of ``at``, or ``None``."""
-    for grp in reversed(groups):
-        if at - grp[0] > reach:
-            return None  # (ascending start instants: every earlier group is further back still)
-        if grp[1] == raw:
-            return grp
-    return None
-
-
 def parse_messages(plan: P.AcarsPlan, records: dict, candidates: int = 0) -> AcarsResult | None:
     """``records``: dict(phase=[k], s=[k], start=[k], nbytes=[k], data=uint8[k, >= nbytes]) in any order (the kept list of
     ``iqa_acars_frames``) -> the run's messages.  Integer logic only; ``None`` where no message survives."""
@@ -109,15 +100,7 @@ def parse_messages(plan: P.AcarsPlan, records: dict, candidates: int = 0) -> Aca
     nbytes = np.asarray(records["nbytes"], dtype=np.int64).reshape(-1)
     data = np.asarray(records["data"], dtype=np.uint8).reshape(start.size, -1) if start.size else np.zeros((0, 0), dtype=np.uint8)
     res = AcarsResult(candidates=int(candidates), crc_ok=int(start.size))
-    groups: list = []  # [first start instant, bytes, hits], ascending in the first start instant
-    for k in np.lexsort((phase, start)).tolist():
-        raw, at = data[k, : int(nbytes[k])].tobytes(), int(start[k])
-        grp = _group_of(groups, raw, at, plan.L)
-        if grp is None:
-            groups.append([at, raw, 1])
-        else:
-            grp[2] += 1
-    for at, raw, hits in groups:
+    for at, raw, hits, _ in group_records(start, nbytes, data, plan.L, tie=phase):
         res.messages.append(AcarsMessage(time_s=at / plan.fs, hits=hits, **parse_message(raw)))
     return res if res.messages else None
 
@@ -194,11 +177,7 @@ class AcarsCore:
         bits = D.empty(PHASES * nbits, "uint8")
         N.call("iqa_acars_bits", N.ptr(same), c_int64(n), c_int32(plan.W), c_double(plan.step), c_int64(nbits), N.ptr(bits), N.stream_ptr())
         counts = D.zeros(2, "int64")
-        lst, slots = self._frames(bits, nbits, count_of, capacity, counts)
-        kept, reached = (int(v) for v in counts.cpu().numpy())
-        if kept > capacity:
-            lst, slots = self._frames(bits, nbits, count_of, kept, counts)
-            assert int(counts[0].item()) == kept
+        ((lst, slots),), (kept, reached) = search_with_room([lambda room: self._frames(bits, nbits, count_of, room, counts)], counts, capacity)
         entries = lst[: 4 * kept].cpu().numpy().reshape(-1, 4)
         data = slots[: SLOT_BYTES * kept].cpu().numpy().reshape(-1, SLOT_BYTES)
         order = np.lexsort((entries[:, 1], entries[:, 0]))
@@ -206,38 +185,21 @@ class AcarsCore:
         return dict(emax=emax, sh=sh, phase=entries[:, 0].copy(), s=entries[:, 1].copy(), start=entries[:, 2].copy(),
                     nbytes=entries[:, 3].copy(), data=data, candidates=reached, same=same, bits=bits, nbits=nbits, count_of=counts_of, **stages)
 
+    def result(self, fin=None, **context) -> AcarsResult | None:
+        """The run's ``AcarsResult`` (``None`` without a message); ``fin``: a ``finish()`` made earlier."""
+        fin = self.finish() if fin is None else fin
+        return parse_messages(self.plan, fin, fin["candidates"])
 
-class AcarsDecoder:
+
+class AcarsDecoder(SideStage):
     """The stage API: ``process(block)`` per block of the channel (complex: the channelizer's output, run through
     ``iqa_envelope``; or float32: an envelope, finite and >= 0), ``finish()`` once (an ``AcarsResult``, or ``None`` without
     a message), ``stages()`` for the tests."""
 
+    source = "envelope"
+
     def __init__(self, rate: float, *, keep_stages: bool = True):
-        self.plan = P.plan_acars(float(rate))
-        self.core = AcarsCore(self.plan, keep_stages=keep_stages)
-        self._fin = None
-
-    def process(self, block) -> None:
-        torch = D.torch_mod()
-        is_complex = torch.is_complex(block) if D.is_tensor(block) else np.iscomplexobj(block)
-        if is_complex:
-            z = D.to_device(block, "complex64")
-            e = D.empty(int(z.numel()), "float32")
-            if z.numel():
-                N.call("iqa_envelope", N.ptr(z), c_int64(int(z.numel())), N.ptr(e), N.stream_ptr())
-        else:
-            e = D.to_device(block, "float32").clone()  # (the store keeps the tensor: the caller's may change)
-        self.core.process(e)
-        self._fin = None
-
-    def _finished(self) -> dict:
-        if self._fin is None:
-            self._fin = self.core.finish()
-        return self._fin
-
-    def finish(self) -> AcarsResult | None:
-        fin = self._finished()
-        return parse_messages(self.plan, fin, fin["candidates"])
+        super().__init__(AcarsCore(P.plan_acars(float(rate)), keep_stages=keep_stages), keep=False)  # (the core stores e itself)
 
     def stages(self) -> dict:
         """Host copies: ``e``, ``emax``, ``sh``, ``q``, ``I``, ``Q``, ``y`` (with keep_stages), ``same``, ``bits`` (8 uint8

@@ -18,6 +18,7 @@ import numpy as np
 from .. import _dev as D
 from .. import _native as N
 from .. import dsp_plan as P
+from .common import SideStage, group_records, search_with_room
 
 LOG = logging.getLogger(__name__)
 
@@ -164,16 +165,6 @@ def parse_me(me: int) -> dict:
     return out
 
 
-def _group_of(groups: list, raw: bytes, at: int, reach: int):
-    """The latest group with these bytes whose first position lies within ``reach`` of ``at``, or ``None``."""
-    for grp in reversed(groups):
-        if at - grp[0] > reach:
-            return None  # (ascending positions: every earlier group is further back still)
-        if grp[1] == raw:
-            return grp
-    return None
-
-
 def parse_frames(plan: P.AdsbPlan, records: dict, candidates: int = 0) -> AdsbResult | None:
     """``records``: dict(n=[k], nbits=[k], P=[k], data=uint8[k, 14]) in any order (the kept list of ``iqa_adsb_search``) ->
     the run's messages and aircraft.  ``None`` where no message survives."""
@@ -182,18 +173,10 @@ def parse_frames(plan: P.AdsbPlan, records: dict, candidates: int = 0) -> AdsbRe
     level = np.asarray(records["P"], dtype=np.int64).reshape(-1)
     data = np.asarray(records["data"], dtype=np.uint8).reshape(at.size, -1) if at.size else np.zeros((0, SLOT_BYTES), dtype=np.uint8)
     res = AdsbResult(candidates=int(candidates), crc_ok=int(at.size))
-    groups: list = []  # [first position, bytes, hits, P of the first], ascending in the first position
-    for k in np.argsort(at, kind="stable").tolist():
-        raw, n = data[k, : int(nbits[k]) // 8].tobytes(), int(at[k])
-        grp = _group_of(groups, raw, n, plan.L)
-        if grp is None:
-            groups.append([n, raw, 1, int(level[k])])
-        else:
-            grp[2] += 1
     last_pos: dict = {}  # (icao, parity) -> the latest position message
     craft: dict = {}
-    for n, raw, hits, p in groups:
-        df = raw[0] >> 3
+    for n, raw, hits, first in group_records(at, nbits // 8, data, plan.L):
+        df, p = raw[0] >> 3, int(level[first])
         msg = AdsbMessage(time_s=n / plan.fs, df=df, icao=raw[1:4].hex().upper(), raw=raw.hex(), hits=hits,
                           level=p / (4.0 * plan.h * 65536.0), type_code=None)
         if df in (17, 18):
@@ -267,11 +250,7 @@ class AdsbCore:
         npos = max(n - self.plan.span + 1, 0)
         flags = D.empty(npos, "uint8") if keep_flags else None
         counts = D.zeros(2, "int64")
-        lst, slots = self.search(q, capacity, counts, flags)
-        kept, passed = (int(v) for v in counts.cpu().numpy())
-        if kept > capacity:
-            lst, slots = self.search(q, kept, counts, flags)
-            assert int(counts[0].item()) == kept
+        ((lst, slots),), (kept, passed) = search_with_room([lambda room: self.search(q, room, counts, flags)], counts, capacity)
         entries = lst[: 3 * kept].cpu().numpy().reshape(-1, 3)
         data = slots[: SLOT_BYTES * kept].cpu().numpy().reshape(-1, SLOT_BYTES)
         order = np.argsort(entries[:, 0], kind="stable")
@@ -281,46 +260,28 @@ class AdsbCore:
             out["flags"] = flags
         return out
 
+    def result(self, fin=None, **context) -> AdsbResult | None:
+        """The run's ``AdsbResult`` (``None`` without a message); ``fin``: a ``finish()`` made earlier."""
+        fin = self.finish() if fin is None else fin
+        return parse_frames(self.plan, fin, fin["candidates"])
 
-class AdsbDecoder:
+
+class AdsbDecoder(SideStage):
     """The stage API: ``process(block)`` per block of the channel (complex: the channelizer's output, run through
     ``iqa_envelope``; or float32: an envelope), ``finish()`` once (an ``AdsbResult``, or ``None`` without a message),
     ``stages()`` for the tests."""
 
+    source = "envelope"
+    finish_args = dict(keep_flags=True)
+
     def __init__(self, rate: float):
-        self.plan = P.plan_adsb(float(rate))
-        self.core = AdsbCore(self.plan)
-        self._e: list = []
-        self._fin = None
-
-    def process(self, block) -> None:
-        torch = D.torch_mod()
-        is_complex = torch.is_complex(block) if D.is_tensor(block) else np.iscomplexobj(block)
-        if is_complex:
-            z = D.to_device(block, "complex64")
-            e = D.empty(int(z.numel()), "float32")
-            if z.numel():
-                N.call("iqa_envelope", N.ptr(z), c_int64(int(z.numel())), N.ptr(e), N.stream_ptr())
-        else:
-            e = D.to_device(block, "float32").clone()  # (the store keeps the tensor: the caller's may change)
-        self._e.append(e)
-        self.core.process(e)
-        self._fin = None
-
-    def _finished(self) -> dict:
-        if self._fin is None:
-            self._fin = self.core.finish(keep_flags=True)
-        return self._fin
-
-    def finish(self) -> AdsbResult | None:
-        fin = self._finished()
-        return parse_frames(self.plan, fin, fin["candidates"])
+        super().__init__(AdsbCore(P.plan_adsb(float(rate))), keep=True)
 
     def stages(self) -> dict:
         """Host copies: ``e`` (float32), ``q`` (uint16), ``flags`` (uint8 per candidate position: passed the preamble rule),
         ``records`` ([(n, nbits, P, bytes)] sorted by n) and ``candidates``."""
         fin = self._finished()
-        e = D.torch_mod().cat(self._e).cpu().numpy() if self._e else np.zeros(0, dtype=np.float32)
+        e = self._inputs_host() if self.inputs else np.zeros(0, dtype=np.float32)
         records = [(int(n), int(nb), int(p), fin["data"][k, : int(nb) // 8].tobytes())
                    for k, (n, nb, p) in enumerate(zip(fin["n"], fin["nbits"], fin["P"]))]
         return dict(e=e, q=self.core.joined().cpu().numpy().view(np.uint16), flags=fin["flags"].cpu().numpy(), records=records,

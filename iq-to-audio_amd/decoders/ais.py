@@ -16,6 +16,7 @@ import numpy as np
 from .. import _dev as D
 from .. import _native as N
 from .. import dsp_plan as P
+from .common import SideStage, carried_history, group_records, search_with_room
 
 PHASES = P.AIS_PHASES
 MIN_FRAME, MAX_FRAME = 11, 128  # bytes, FCS included
@@ -191,16 +192,6 @@ class AisResult:
         return dict(messages=[m.to_json() for m in self.messages], candidates=self.candidates, crc_ok=self.crc_ok)
 
 
-def _group_of(groups: list, raw: bytes, at: int, reach: int):
-    """The latest group with these bytes whose first start instant lies within ``reach`` of ``at``, or ``None``."""
-    for grp in reversed(groups):
-        if at - grp[0] > reach:
-            return None  # (ascending start instants: every earlier group is further back still)
-        if grp[1] == raw:
-            return grp
-    return None
-
-
 def parse_frames(plan: P.AisPlan, records: dict, candidates: int = 0, *, frequency=None) -> AisResult | None:
     """``records``: dict(phase=[k], s=[k], start=[k], nbytes=[k], data=uint8[k, >= nbytes]) in any order (the kept-frame list
     of ``iqa_ais_frames``) -> the run's messages; ``frequency`` (Hz) names the channel of the sentences.  Integer logic only;
@@ -210,16 +201,8 @@ def parse_frames(plan: P.AisPlan, records: dict, candidates: int = 0, *, frequen
     nbytes = np.asarray(records["nbytes"], dtype=np.int64).reshape(-1)
     data = np.asarray(records["data"], dtype=np.uint8).reshape(start.size, -1) if start.size else np.zeros((0, 0), dtype=np.uint8)
     res = AisResult(candidates=int(candidates), crc_ok=int(start.size))
-    groups: list = []  # [first start instant, bytes, hits], ascending in the first start instant
-    for k in np.lexsort((phase, start)).tolist():
-        raw, at = data[k, : int(nbytes[k])].tobytes(), int(start[k])
-        grp = _group_of(groups, raw, at, plan.L)
-        if grp is None:
-            groups.append([at, raw, 1])
-        else:
-            grp[2] += 1
     channel, seq = channel_of(frequency), 0
-    for at, raw, hits in groups:
+    for at, raw, hits, _ in group_records(start, nbytes, data, plan.L, tie=phase):
         got = decode_message(raw)
         nmea = nmea_sentences(raw, channel, seq)
         if len(nmea) > 1:
@@ -255,12 +238,7 @@ class AisCore:
         self._s.append(s)
         if self.keep_stages:
             self._t.append(t)
-        h = self.hist_len
-        if n >= h:
-            self._hist = t[n - h :].clone()
-        else:
-            prev = self._hist if self._hist is not None else D.zeros(h, "int32")
-            self._hist = D.torch_mod().cat([prev[n:], t])
+        self._hist = carried_history(self._hist, t, self.hist_len)
         self.pos += n
 
     def joined(self) -> dict:
@@ -293,11 +271,7 @@ class AisCore:
         v = D.empty(PHASES * nsym, "int32")
         N.call("iqa_ais_symbols", N.ptr(S), c_int64(n), c_int32(plan.W), c_double(plan.step), c_int64(nsym), N.ptr(v), N.stream_ptr())
         counts = D.zeros(2, "int64")
-        lst, slots = self._frames(v, nsym, count_of, capacity, counts)
-        kept, closed = (int(x) for x in counts.cpu().numpy())
-        if kept > capacity:
-            lst, slots = self._frames(v, nsym, count_of, kept, counts)
-            assert int(counts[0].item()) == kept
+        ((lst, slots),), (kept, closed) = search_with_room([lambda room: self._frames(v, nsym, count_of, room, counts)], counts, capacity)
         entries = lst[: 4 * kept].cpu().numpy().reshape(-1, 4)
         data = slots[: SLOT_BYTES * kept].cpu().numpy().reshape(-1, SLOT_BYTES)
         order = np.lexsort((entries[:, 1], entries[:, 0]))
@@ -305,8 +279,14 @@ class AisCore:
         return dict(phase=entries[:, 0].copy(), s=entries[:, 1].copy(), start=entries[:, 2].copy(), nbytes=entries[:, 3].copy(), data=data,
                     candidates=closed, v=v, nsym=nsym, count_of=counts_of)
 
+    def result(self, fin=None, *, frequency=None, **context) -> AisResult | None:
+        """The run's ``AisResult`` (``None`` without a message); ``frequency`` names the channel of the sentences; ``fin``: a
+        ``finish()`` made earlier."""
+        fin = self.finish() if fin is None else fin
+        return parse_frames(self.plan, fin, fin["candidates"], frequency=frequency)
 
-class AisDecoder:
+
+class AisDecoder(SideStage):
     """The stage API: ``process(block)`` per block of the channel (complex: the channelizer's output, run through
     ``iqa_quadrature`` with this decoder's own ``prev``; or float32: a discriminator output in radians per sample,
     |theta| < 2048 as ``iqa_ais_filter`` requires; a discriminator gives |theta| <= pi), ``finish()`` once (an
@@ -314,46 +294,17 @@ class AisDecoder:
     in Hz, which names the channel in the sentences."""
 
     def __init__(self, rate: float, *, frequency=None, keep_stages: bool = True):
-        self.plan = P.plan_ais(float(rate))
+        super().__init__(AisCore(P.plan_ais(float(rate)), keep_stages=keep_stages), keep=keep_stages, frequency=frequency)
         self.frequency = frequency
-        self.core = AisCore(self.plan, keep_stages=keep_stages)
-        self._prev = D.from_numpy(np.array([1 + 0j], dtype=np.complex64))
-        self.theta: list = []  # with keep_stages: the discriminator output of every block (device)
-        self._fin = None
-
-    def process(self, block) -> None:
-        torch = D.torch_mod()
-        is_complex = torch.is_complex(block) if D.is_tensor(block) else np.iscomplexobj(block)
-        if is_complex:
-            z = D.to_device(block, "complex64")
-            theta = D.empty(int(z.numel()), "float32")
-            if z.numel():
-                N.call("iqa_quadrature", N.ptr(z), c_int64(int(z.numel())), N.ptr(self._prev), N.ptr(theta), N.stream_ptr())
-        else:
-            theta = D.to_device(block, "float32")
-        if self.core.keep_stages:
-            self.theta.append(theta)
-        self.core.process(theta)
-        self._fin = None
-
-    def _finished(self) -> dict:
-        if self._fin is None:
-            self._fin = self.core.finish()
-        return self._fin
-
-    def finish(self) -> AisResult | None:
-        fin = self._finished()
-        return parse_frames(self.plan, fin, fin["candidates"], frequency=self.frequency)
 
     def stages(self) -> dict:
         """Host copies: ``theta`` and ``t`` (with keep_stages), ``S``, ``v`` (8 int32 arrays, each as long as its phase has
         symbols), ``records`` ([(phase, s, start instant, bytes)] sorted) and ``candidates``."""
         fin = self._finished()
         st = self.core.joined()
-        torch = D.torch_mod()
         plane = fin["v"].cpu().numpy().reshape(PHASES, -1) if fin["nsym"] else np.zeros((PHASES, 0), dtype=np.int32)
         v = [plane[p, : fin["count_of"][p]] for p in range(PHASES)]
         records = [(int(p), int(s), int(at), fin["data"][k, : int(nb)].tobytes())
                    for k, (p, s, at, nb) in enumerate(zip(fin["phase"], fin["s"], fin["start"], fin["nbytes"]))]
-        return dict(theta=torch.cat(self.theta).cpu().numpy() if self.theta else None, t=None if st["t"] is None else st["t"].cpu().numpy(),
+        return dict(theta=self._inputs_host(), t=None if st["t"] is None else st["t"].cpu().numpy(),
                     S=st["S"].cpu().numpy(), v=v, records=records, candidates=fin["candidates"])

@@ -16,6 +16,7 @@ import numpy as np
 from .. import _dev as D
 from .. import _native as N
 from .. import dsp_plan as P
+from .common import SideStage, carried_history, group_records, search_with_room
 
 FLAG = 0x7E
 CRC_POLY = 0x8408  # CRC-16/X.25, reflected; init 0xFFFF, final xor 0xFFFF
@@ -103,16 +104,6 @@ def parse_frame(raw: bytes):
     return dict(dest=calls[0][0], source=calls[1][0], path=[c + ("*" if h else "") for c, h in calls[2:]], control=control, pid=pid, info=text)
 
 
-def _group_of(groups: list, raw: bytes, at: int, reach: int):
-    """The latest group with these bytes whose first start instant lies within ``reach`` of ``at``, or ``None``."""
-    for grp in reversed(groups):
-        if at - grp[0] > reach:
-            return None  # (ascending start instants: every earlier group is further back still)
-        if grp[1] == raw:
-            return grp
-    return None
-
-
 def parse_frames(plan: P.AfskPlan, records: dict, candidates: int = 0) -> Ax25Result | None:
     """``records``: dict(variant=[k], s=[k], start=[k], nbytes=[k], data=uint8[k, >= nbytes]) in any order (the kept-frame
     list of ``iqa_afsk_frames``) -> the run's frames.  Integer logic only; ``None`` where no frame survives."""
@@ -121,15 +112,7 @@ def parse_frames(plan: P.AfskPlan, records: dict, candidates: int = 0) -> Ax25Re
     nbytes = np.asarray(records["nbytes"], dtype=np.int64).reshape(-1)
     data = np.asarray(records["data"], dtype=np.uint8).reshape(start.size, -1) if start.size else np.zeros((0, 0), dtype=np.uint8)
     res = Ax25Result(candidates=int(candidates), crc_ok=int(start.size))
-    groups: list = []  # [first start instant, bytes, hits], ascending in the first start instant
-    for k in np.lexsort((variant, start)).tolist():
-        raw, at = data[k, : int(nbytes[k])].tobytes(), int(start[k])
-        grp = _group_of(groups, raw, at, plan.L)
-        if grp is None:
-            groups.append([at, raw, 1])
-        else:
-            grp[2] += 1
-    for at, raw, hits in groups:
+    for at, raw, hits, _ in group_records(start, nbytes, data, plan.L, tie=variant):
         got = parse_frame(raw)
         if got is None:
             res.rejected += 1
@@ -167,12 +150,7 @@ class AfskCore:
         if self.keep_stages:
             self._t.append(t)
             self._e.append(e)
-        h = self.hist_len
-        if n >= h:
-            self._hist = t[n - h :].clone()
-        else:
-            prev = self._hist if self._hist is not None else D.zeros(h, "int32")
-            self._hist = D.torch_mod().cat([prev[n:], t])
+        self._hist = carried_history(self._hist, t, self.hist_len)
         self.pos += n
 
     def joined(self) -> dict:
@@ -207,11 +185,7 @@ class AfskCore:
         bits = D.empty(VARIANTS * nbits, "uint8")
         N.call("iqa_afsk_bits", N.ptr(sign), c_int64(n), c_int32(plan.L), c_double(plan.step), c_int64(nbits), N.ptr(bits), N.stream_ptr())
         counts = D.zeros(2, "int64")
-        lst, slots = self._frames(bits, nbits, count_of, capacity, counts)
-        kept, closed = (int(v) for v in counts.cpu().numpy())
-        if kept > capacity:
-            lst, slots = self._frames(bits, nbits, count_of, kept, counts)
-            assert int(counts[0].item()) == kept
+        ((lst, slots),), (kept, closed) = search_with_room([lambda room: self._frames(bits, nbits, count_of, room, counts)], counts, capacity)
         entries = lst[: 4 * kept].cpu().numpy().reshape(-1, 4)
         data = slots[: SLOT_BYTES * kept].cpu().numpy().reshape(-1, SLOT_BYTES)
         order = np.lexsort((entries[:, 1], entries[:, 0]))
@@ -219,55 +193,30 @@ class AfskCore:
         return dict(variant=entries[:, 0].copy(), s=entries[:, 1].copy(), start=entries[:, 2].copy(), nbytes=entries[:, 3].copy(), data=data,
                     candidates=closed, bits=bits, nbits=nbits, count_of=counts_of)
 
+    def result(self, fin=None, **context) -> Ax25Result | None:
+        """The run's ``Ax25Result`` (``None`` without a frame); ``fin``: a ``finish()`` made earlier."""
+        fin = self.finish() if fin is None else fin
+        return parse_frames(self.plan, fin, fin["candidates"])
 
-class Ax25Decoder:
+
+class Ax25Decoder(SideStage):
     """The stage API: ``process(block)`` per block of the channel (complex: the channelizer's output, run through
     ``iqa_quadrature`` with this decoder's own ``prev``; or float32: a discriminator output in radians per sample,
     |theta| < 2048 as ``iqa_afsk_correlate`` requires; a discriminator gives |theta| <= pi),
     ``finish()`` once (an ``Ax25Result``, or ``None`` without a frame), ``stages()`` for the tests."""
 
     def __init__(self, rate: float, *, keep_stages: bool = True):
-        self.plan = P.plan_afsk(float(rate))
-        self.core = AfskCore(self.plan, keep_stages=keep_stages)
-        self._prev = D.from_numpy(np.array([1 + 0j], dtype=np.complex64))
-        self.theta: list = []  # with keep_stages: the discriminator output of every block (device)
-        self._fin = None
-
-    def process(self, block) -> None:
-        torch = D.torch_mod()
-        is_complex = torch.is_complex(block) if D.is_tensor(block) else np.iscomplexobj(block)
-        if is_complex:
-            z = D.to_device(block, "complex64")
-            theta = D.empty(int(z.numel()), "float32")
-            if z.numel():
-                N.call("iqa_quadrature", N.ptr(z), c_int64(int(z.numel())), N.ptr(self._prev), N.ptr(theta), N.stream_ptr())
-        else:
-            theta = D.to_device(block, "float32")
-        if self.core.keep_stages:
-            self.theta.append(theta)
-        self.core.process(theta)
-        self._fin = None
-
-    def _finished(self) -> dict:
-        if self._fin is None:
-            self._fin = self.core.finish()
-        return self._fin
-
-    def finish(self) -> Ax25Result | None:
-        fin = self._finished()
-        return parse_frames(self.plan, fin, fin["candidates"])
+        super().__init__(AfskCore(P.plan_afsk(float(rate)), keep_stages=keep_stages), keep=keep_stages)
 
     def stages(self) -> dict:
         """Host copies: ``theta``, ``t`` and ``E`` (tone -> int64[n]; with keep_stages), ``sign``, ``bits`` (24 uint8 arrays, each
         as long as its phase has bits) and ``records`` ([(variant, s, start instant, bytes)] sorted)."""
         fin = self._finished()
         st = self.core.joined()
-        torch = D.torch_mod()
         plane = fin["bits"].cpu().numpy().reshape(VARIANTS, -1) if fin["nbits"] else np.zeros((VARIANTS, 0), dtype=np.uint8)
         bits = [plane[v, : fin["count_of"][v % P.AFSK_PHASES]] for v in range(VARIANTS)]
         records = [(int(v), int(s), int(at), fin["data"][k, : int(nb)].tobytes())
                    for k, (v, s, at, nb) in enumerate(zip(fin["variant"], fin["s"], fin["start"], fin["nbytes"]))]
-        return dict(theta=torch.cat(self.theta).cpu().numpy() if self.theta else None,
-                    t=None if st["t"] is None else st["t"].cpu().numpy(),
+        return dict(theta=self._inputs_host(), t=None if st["t"] is None else st["t"].cpu().numpy(),
                     E=None if st["E"] is None else {f: e.cpu().numpy() for f, e in st["E"].items()},
                     sign=st["sign"].cpu().numpy(), bits=bits, records=records, candidates=fin["candidates"])

@@ -15,6 +15,7 @@ import numpy as np
 from .. import _dev as D
 from .. import _native as N
 from .. import dsp_plan as P
+from .common import SideStage, carried_history, search_with_room
 
 SYNC_WORD = 0x7CD215D8
 IDLE_WORD = 0x7A89C197
@@ -167,12 +168,7 @@ class PocsagCore:
         self._s.append(planes)
         if self.keep_t:
             self._t.append(t)
-        h = self.hist_len
-        if n >= h:
-            self._hist = t[n - h :].clone() if h else None
-        else:
-            prev = self._hist if self._hist is not None else D.zeros(h, "int32")
-            self._hist = D.torch_mod().cat([prev[n:], t])
+        self._hist = carried_history(self._hist, t, self.hist_len)
         self.pos += n
 
     def joined(self) -> dict:
@@ -202,13 +198,9 @@ class PocsagCore:
         bauds = self.plan.bauds
         counts = D.zeros(len(bauds), "int64")
         score = D.empty(max(max(int(st["S"][pb.baud].numel()) for pb in bauds), 1), "int64")  # (shared: stream order)
-        capacity = 1024
-        lists = [self._search(pb, st["S"][pb.baud], score, capacity, counts[i : i + 1]) for i, pb in enumerate(bauds)]
-        kept = [int(v) for v in counts.cpu().numpy()]
-        for i, pb in enumerate(bauds):
-            if kept[i] > capacity:  # the list is incomplete: search again with room for all, never a truncated list
-                lists[i] = self._search(pb, st["S"][pb.baud], score, kept[i], counts[i : i + 1])
-                assert int(counts[i].item()) == kept[i]
+        searches = [lambda capacity, i=i, pb=pb: self._search(pb, st["S"][pb.baud], score, capacity, counts[i : i + 1])
+                    for i, pb in enumerate(bauds)]
+        lists, kept = search_with_room(searches, counts, 1024)
         words_dev = []
         for i, pb in enumerate(bauds):
             k, s = kept[i], st["S"][pb.baud]
@@ -229,48 +221,23 @@ class PocsagCore:
                                 distance=entries[:, 3].astype(np.int32), words=both[0][order], raw=both[1][order], status=status[order])
         return out
 
+    def result(self, fin=None, **context) -> PocsagResult | None:
+        """The run's ``PocsagResult`` (``None`` without a kept sync); ``fin``: a ``finish()`` made earlier."""
+        return parse_batches(self.plan, self.finish() if fin is None else fin)
 
-class PocsagDecoder:
+
+class PocsagDecoder(SideStage):
     """The stage API: ``process(block)`` per block of the channel (complex: the channelizer's output, run through
     ``iqa_quadrature`` with this decoder's own ``prev``; or float32: a discriminator output in radians per sample),
     ``finish()`` once (a ``PocsagResult``, or ``None`` without a kept sync), ``stages()`` for the tests."""
 
     def __init__(self, rate: float, *, keep_t: bool = True):
-        self.plan = P.plan_pocsag(float(rate))
-        self.core = PocsagCore(self.plan, keep_t=keep_t)
-        self._prev = D.from_numpy(np.array([1 + 0j], dtype=np.complex64))
-        self.theta: list = []  # with keep_t: the discriminator output of every block (device)
-        self._fin = None
-
-    def process(self, block) -> None:
-        torch = D.torch_mod()
-        is_complex = torch.is_complex(block) if D.is_tensor(block) else np.iscomplexobj(block)
-        if is_complex:
-            z = D.to_device(block, "complex64")
-            theta = D.empty(int(z.numel()), "float32")
-            if z.numel():
-                N.call("iqa_quadrature", N.ptr(z), c_int64(int(z.numel())), N.ptr(self._prev), N.ptr(theta), N.stream_ptr())
-        else:
-            theta = D.to_device(block, "float32")
-        if self.core.keep_t:
-            self.theta.append(theta)
-        self.core.process(theta)
-        self._fin = None
-
-    def _finished(self) -> dict:
-        if self._fin is None:
-            self._fin = self.core.finish()
-        return self._fin
-
-    def finish(self) -> PocsagResult | None:
-        return parse_batches(self.plan, self._finished())
+        super().__init__(PocsagCore(P.plan_pocsag(float(rate)), keep_t=keep_t), keep=keep_t)
 
     def stages(self) -> dict:
         """Host copies: ``theta`` and ``t`` (with keep_t), ``S`` (baud -> int32[n]) and ``batches`` (baud -> kept syncs
         sorted by n0 with their corrected words, raw words and status)."""
         fin = self._finished()
         st = self.core.joined()
-        torch = D.torch_mod()
-        return dict(theta=torch.cat(self.theta).cpu().numpy() if self.theta else None,
-                    t=None if st["t"] is None else st["t"].cpu().numpy(),
+        return dict(theta=self._inputs_host(), t=None if st["t"] is None else st["t"].cpu().numpy(),
                     S={b: s.cpu().numpy() for b, s in st["S"].items()}, batches=fin)

@@ -17,6 +17,7 @@ import numpy as np
 from .. import _dev as D
 from .. import _native as N
 from .. import dsp_plan as P
+from .common import carried_history
 
 OFFSET_WORDS = {"A": 0x0FC, "B": 0x198, "C": 0x168, "C'": 0x350, "D": 0x1B4}
 CRC_POLY = 0x5B9  # x^10 + x^8 + x^7 + x^5 + x^4 + x^3 + 1
@@ -130,12 +131,7 @@ class RdsCore:
             N.call("iqa_rds_clock", N.ptr(q), c_int64(nj), c_int64(-(-self.pos // pl.decim)), c_double(pl.clock_step),
                    N.ptr(self.total), N.ptr(work), N.ptr(phi), N.ptr(psi), N.stream_ptr())
             self._store.append((y, q, phi, psi))
-        h = self.hist_len
-        if n >= h:
-            self._hist = theta[n - h :].clone()
-        else:
-            prev = self._hist if self._hist is not None else D.zeros(h, "float32")
-            self._hist = D.torch_mod().cat([prev[n:], theta])
+        self._hist = carried_history(self._hist, theta, self.hist_len, "float32")
         self.pos += n
 
     def joined(self) -> dict:
@@ -178,6 +174,11 @@ class RdsCore:
             out["words"], out["syndromes"] = words, synd
         return out
 
+    def result(self, fin=None, **context) -> RdsResult | None:
+        """The station's ``RdsResult`` (``None`` without an accepted group); ``fin``: a ``finish()`` made earlier."""
+        res = result_from(self.finish() if fin is None else fin)
+        return res if res.groups else None
+
 
 def result_from(fin: dict) -> RdsResult:
     """``RdsCore.finish()`` -> the parsed result (one copy of the words and syndromes to the host)."""
@@ -209,8 +210,7 @@ class RdsDecoder:
         return self._fin
 
     def finish(self) -> RdsResult | None:
-        res = result_from(self._finished())
-        return res if res.groups else None
+        return self.core.result(self._finished())
 
     def stages(self) -> dict:
         """Host copies of every stage: y, q, phi, psi, symbols, bits, words, syndromes (and tau, strength, k_first)."""

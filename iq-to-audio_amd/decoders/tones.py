@@ -16,6 +16,7 @@ import numpy as np
 from .. import _dev as D
 from .. import _native as N
 from .. import dsp_plan as P
+from .common import SideStage, carried_history
 
 NONE = P.TONES_NONE
 MIN_RUN = 3  # frames of one code that make an event
@@ -132,13 +133,7 @@ class TonesCore:
             self._u.append(u)
         if self.keep_stages:
             self._t.append(t)
-        h = self.hist_len
-        if h:
-            if n >= h:
-                self._hist = t[n - h :].clone()
-            else:
-                prev = self._hist if self._hist is not None else D.zeros(h, "int32")
-                self._hist = D.torch_mod().cat([prev[n:], t])
+        self._hist = carried_history(self._hist, t, self.hist_len)
         self.pos += n
 
     def joined(self) -> dict:
@@ -174,55 +169,26 @@ class TonesCore:
                    N.ptr(dtmf) if Fd else N.ptr(None), N.stream_ptr())
         return dict(E_ctcss=Ec, E_dtmf=Ed, P=Pw, ctcss=ctcss, dtmf=dtmf, m=m, Fc=Fc, Fd=Fd)
 
-    def result(self) -> TonesResult | None:
-        fin = self.finish()
+    def result(self, fin=None, **context) -> TonesResult | None:
+        """The run's ``TonesResult`` (``None`` without an event); ``fin``: a ``finish()`` made earlier."""
+        fin = self.finish() if fin is None else fin
         return parse_tones(self.plan, fin["ctcss"].cpu().numpy(), fin["dtmf"].cpu().numpy())
 
 
-class ToneDecoder:
+class ToneDecoder(SideStage):
     """The stage API: ``process(block)`` per block of the channel (complex: the channelizer's output, run through
     ``iqa_quadrature`` with this decoder's own ``prev``; or float32: a discriminator output in radians per sample,
     |theta| <= pi), ``finish()`` once (a ``TonesResult``, or ``None`` without an event), ``stages()`` for the tests."""
 
     def __init__(self, rate: float, *, keep_stages: bool = True):
-        self.plan = P.plan_tones(float(rate))
-        self.core = TonesCore(self.plan, keep_stages=keep_stages)
-        self._prev = D.from_numpy(np.array([1 + 0j], dtype=np.complex64))
-        self.theta: list = []  # with keep_stages: the discriminator output of every block (device)
-        self._fin = None
-
-    def process(self, block) -> None:
-        torch = D.torch_mod()
-        is_complex = torch.is_complex(block) if D.is_tensor(block) else np.iscomplexobj(block)
-        if is_complex:
-            z = D.to_device(block, "complex64")
-            theta = D.empty(int(z.numel()), "float32")
-            if z.numel():
-                N.call("iqa_quadrature", N.ptr(z), c_int64(int(z.numel())), N.ptr(self._prev), N.ptr(theta), N.stream_ptr())
-        else:
-            theta = D.to_device(block, "float32")
-        if self.core.keep_stages:
-            self.theta.append(theta)
-        self.core.process(theta)
-        self._fin = None
-
-    def _finished(self) -> dict:
-        if self._fin is None:
-            self._fin = self.core.finish()
-        return self._fin
-
-    def finish(self) -> TonesResult | None:
-        fin = self._finished()
-        return parse_tones(self.plan, fin["ctcss"].cpu().numpy(), fin["dtmf"].cpu().numpy())
+        super().__init__(TonesCore(P.plan_tones(float(rate)), keep_stages=keep_stages), keep=keep_stages)
 
     def stages(self) -> dict:
         """Host copies: ``theta`` and ``t`` (with keep_stages), ``u``, ``E_ctcss`` int64[Fc, 50], ``E_dtmf`` int64[Fd, 8],
         ``P`` int64[Fd], ``ctcss`` and ``dtmf`` (uint8, one code per frame)."""
         fin = self._finished()
         st = self.core.joined()
-        torch = D.torch_mod()
-        return dict(theta=torch.cat(self.theta).cpu().numpy() if self.theta else None,
-                    t=None if st["t"] is None else st["t"].cpu().numpy(), u=st["u"].cpu().numpy(),
+        return dict(theta=self._inputs_host(), t=None if st["t"] is None else st["t"].cpu().numpy(), u=st["u"].cpu().numpy(),
                     E_ctcss=fin["E_ctcss"].cpu().numpy().reshape(fin["Fc"], len(P.CTCSS_TONES)),
                     E_dtmf=fin["E_dtmf"].cpu().numpy().reshape(fin["Fd"], len(P.DTMF_TONES)), P=fin["P"].cpu().numpy(),
                     ctcss=fin["ctcss"].cpu().numpy(), dtmf=fin["dtmf"].cpu().numpy())

@@ -33,13 +33,9 @@ from . import iqio
 from .channelizer import (_KERNEL_CACHE, _KERNEL_CACHE_LOCK, _KERNEL_CACHE_MAX, _TAPS_MEMO, ChannelBank,  # noqa: F401  (re-exported)
                           Channelizer, _as_frames, _cached_kernel, _ChannelKernel, _taps_fingerprint, immutable_taps)
 from .decoders import create_decoder
-from .decoders.adsb import AdsbCore, parse_frames as adsb_parse_frames
-from .decoders.ais import AisCore, parse_frames as ais_parse_frames
-from .decoders.ax25 import AfskCore, parse_frames as ax25_parse_frames
-from .decoders.pocsag import PocsagCore, parse_batches as pocsag_parse_batches
-from .decoders.rds import RdsCore, result_from as rds_result_from
-from .decoders.acars import AcarsCore, parse_messages as acars_parse_messages
-from .decoders.tones import TonesCore
+from .decoders.common import unit_prev
+from .decoders.rds import RdsCore
+from .decoders.side import SIDE_DECODERS, check_modes
 from .decoders.wfm import WfmStereoCore, stereo_matrix
 from .dsp_plan import design_channel_filter, tune_chunk_size  # noqa: F401  (re-exported API)
 from .progress import PhaseState, ProgressSink, ProgressTracker
@@ -558,30 +554,10 @@ class ChannelDemod:
     (``iqa_demodulate``).  ``self.decoder`` is the matching pluggable decoder object (kept for its
     parameters and API parity; the fused path carries its own device state).
 
-    ``pocsag=True`` (nfm only): after the fused call every block also runs ``iqa_quadrature`` with a
-    ``prev`` state of its own and ``iqa_pocsag_integrate``; ``pocsag_finish`` searches the stored run for sync words and
-    parses the batches (a ``PocsagResult``, or ``None`` without a kept sync).  Off, no POCSAG entry point is called.
-
-    ``ax25=True`` (nfm only): likewise ``iqa_quadrature`` with a third ``prev`` and
-    ``iqa_afsk_correlate`` per block; ``ax25_finish`` reads the stored slicer plane into bit streams, walks the HDLC frames
-    and parses them (an ``Ax25Result``, or ``None`` without a frame).  Off, no AFSK entry point is called.
-
-    ``tones=True`` (nfm only): likewise ``iqa_quadrature`` with a ``prev`` of its own and
-    ``iqa_tones_decimate`` per block; ``tones_finish`` runs the CTCSS and DTMF banks and the decisions over the stored run
-    and parses the two code planes (a ``TonesResult``, or ``None`` without an event).  Off, no tone entry point is called.
-
-    ``acars=True`` (am only): after the fused call every block also runs ``iqa_envelope`` into a buffer
-    of the decoder's own (never the audio buffer), which is stored; ``acars_finish`` scales, detects and searches the stored
-    run and parses the kept blocks (an ``AcarsResult``, or ``None`` without a message).  Off, no ACARS entry point is called.
-
-    ``ais=True`` (nfm only): ``iqa_quadrature`` with a ``prev`` of its own and ``iqa_ais_filter`` per
-    block; ``ais_finish`` reads the stored filter output at 8 sampling phases, walks the HDLC frames behind every training
-    sequence and parses them (an ``AisResult``, or ``None`` without a message).  Off, no AIS entry point is called.
-
-    ``adsb=True`` (am only): after the fused call every block also runs ``iqa_envelope`` into a buffer of
-    the decoder's own and ``iqa_adsb_quantise``, whose uint16 plane is stored; ``adsb_finish`` searches the stored run at
-    every sample position and parses the kept squitters (an ``AdsbResult``, or ``None`` without a message).  Off, no ADS-B
-    entry point is called.
+    The side decoders (``pocsag= ax25= tones= acars= ais= adsb=``; ``decoders/side.py`` lists their modes, plans and cores):
+    after the fused call every block also runs, per active decoder in table order, ``iqa_quadrature`` with a ``prev`` of the
+    decoder's own or ``iqa_envelope``, into a buffer that is never the audio buffer, and the core's per-block launch.
+    ``side[name]`` is the core, ``side_result(name)`` the run's result.  Off, none of a decoder's entry points is called.
     """
 
     def __init__(self, mode: str, fs_channel: float, *, deemph_us: float, agc_enabled: bool, pocsag: bool = False, ax25: bool = False,
@@ -589,40 +565,13 @@ class ChannelDemod:
         self.decoder = create_decoder(mode, deemph_us=deemph_us, agc_enabled=agc_enabled)
         self.decoder.setup(fs_channel)
         self.params = self.decoder.fused_params()
-        self.pocsag_core = None
-        if pocsag:
-            if self.params.mode != N.DEMOD_MODE["nfm"]:
-                raise ValueError("pocsag=True needs an nfm target: POCSAG is 2-FSK on a narrowband FM channel (--demod nfm)")
-            self.pocsag_core = PocsagCore(P.plan_pocsag(fs_channel))  # (ValueError where no baud rate fits the channel rate)
-            self._pocsag_prev = D.from_numpy(np.array([1 + 0j], dtype=np.complex64))
-        self.afsk_core = None
-        if ax25:
-            if self.params.mode != N.DEMOD_MODE["nfm"]:
-                raise ValueError("ax25=True needs an nfm target: AX.25 here is Bell-202 AFSK on a narrowband FM channel (--demod nfm)")
-            self.afsk_core = AfskCore(P.plan_afsk(fs_channel))  # (ValueError where 1200 baud does not fit the channel rate)
-            self._afsk_prev = D.from_numpy(np.array([1 + 0j], dtype=np.complex64))
-        self.tones_core = None
-        if tones:
-            if self.params.mode != N.DEMOD_MODE["nfm"]:
-                raise ValueError("tones=True needs an nfm target: CTCSS and DTMF ride on a narrowband FM voice channel (--demod nfm)")
-            self.tones_core = TonesCore(P.plan_tones(fs_channel))  # (ValueError where the channel rate is outside 8 000 .. 520 000)
-            self._tones_prev = D.from_numpy(np.array([1 + 0j], dtype=np.complex64))
-        self.acars_core = None
-        if acars:
-            if self.params.mode != N.DEMOD_MODE["am"]:
-                raise ValueError("acars=True needs an am target: ACARS is audio MSK on an AM airband carrier (--demod am)")
-            self.acars_core = AcarsCore(P.plan_acars(fs_channel))  # (ValueError where 2400 bit/s does not fit the channel rate)
-        self.ais_core = None
-        if ais:
-            if self.params.mode != N.DEMOD_MODE["nfm"]:
-                raise ValueError("ais=True needs an nfm target: AIS is 9600 bit/s GMSK on a narrowband FM channel (--demod nfm)")
-            self.ais_core = AisCore(P.plan_ais(fs_channel))  # (ValueError where 9600 bit/s does not fit the channel rate)
-            self._ais_prev = D.from_numpy(np.array([1 + 0j], dtype=np.complex64))
-        self.adsb_core = None
-        if adsb:
-            if self.params.mode != N.DEMOD_MODE["am"]:
-                raise ValueError("adsb=True needs an am target: Mode S squitters are pulses on a 1090 MHz AM channel (--demod am)")
-            self.adsb_core = AdsbCore(P.plan_adsb(fs_channel))  # (ValueError where the channel rate is outside 2 .. 20 MHz)
+        flags = dict(pocsag=pocsag, ax25=ax25, tones=tones, acars=acars, ais=ais, adsb=adsb)
+        check_modes(flags, [mode], plural=False)
+        # (entry, core, the discriminator's prev or None) per active decoder, in table order; a plan raises ValueError where the
+        # channel rate does not fit it
+        self._side = tuple((e, e.core(e.plan(fs_channel)), unit_prev() if e.source == "theta" else None)
+                           for e in SIDE_DECODERS if flags.get(e.name))
+        self.side = {e.name: core for e, core, _ in self._side}
         self._needs_scratch = self.params.mode in (N.DEMOD_MODE["usb"], N.DEMOD_MODE["lsb"]) and bool(self.params.agc_enabled)
         self.chunk_sumsq: list = []  # (device float64[n_chunks*8], counts)
         self._blk = None  # one device block: [state 32 B | peak 4 B (+pad to 64) | sumsq n_chunks*8 f64]
@@ -653,22 +602,10 @@ class ChannelDemod:
         sums are put back there now (``iqa_demod_reset``, one small launch), and ``process`` is the plain
         ``iqa_demodulate``: one launch on its stream instead of a clear and a scan."""
         self.chunk_sumsq = []
-        if self.pocsag_core is not None:  # (before the early return: POCSAG state is not part of ``_fresh``)
-            self.pocsag_core.reset()
-            self._pocsag_prev = D.from_numpy(np.array([1 + 0j], dtype=np.complex64))
-        if self.afsk_core is not None:
-            self.afsk_core.reset()
-            self._afsk_prev = D.from_numpy(np.array([1 + 0j], dtype=np.complex64))
-        if self.tones_core is not None:
-            self.tones_core.reset()
-            self._tones_prev = D.from_numpy(np.array([1 + 0j], dtype=np.complex64))
-        if self.acars_core is not None:
-            self.acars_core.reset()
-        if self.adsb_core is not None:
-            self.adsb_core.reset()
-        if self.ais_core is not None:
-            self.ais_core.reset()
-            self._ais_prev = D.from_numpy(np.array([1 + 0j], dtype=np.complex64))
+        if self._side:  # (before the early return: the side decoders' state is not part of ``_fresh``)
+            for _, core, _ in self._side:
+                core.reset()
+            self._side = tuple((e, core, prev if prev is None else unit_prev()) for e, core, prev in self._side)
         if self._fresh and not force:  # (force: a step being captured into a graph must not depend on what ran before it)
             return
         if ahead and self.params.mode == N.DEMOD_MODE["nfm"]:
@@ -719,69 +656,19 @@ class ChannelDemod:
                N.stream_ptr())
         counts = np.diff(np.append(chunk_starts, n))
         self.chunk_sumsq.append((sumsq, counts))
-        if self.pocsag_core is not None:
-            theta = D.empty(n, "float32")
-            N.call("iqa_quadrature", N.ptr(z_dev), c_int64(n), N.ptr(self._pocsag_prev), N.ptr(theta), N.stream_ptr())
-            self.pocsag_core.process(theta)
-        if self.afsk_core is not None:
-            theta = D.empty(n, "float32")
-            N.call("iqa_quadrature", N.ptr(z_dev), c_int64(n), N.ptr(self._afsk_prev), N.ptr(theta), N.stream_ptr())
-            self.afsk_core.process(theta)
-        if self.tones_core is not None:
-            theta = D.empty(n, "float32")
-            N.call("iqa_quadrature", N.ptr(z_dev), c_int64(n), N.ptr(self._tones_prev), N.ptr(theta), N.stream_ptr())
-            self.tones_core.process(theta)
-        if self.acars_core is not None:
-            env = D.empty(n, "float32")
-            N.call("iqa_envelope", N.ptr(z_dev), c_int64(n), N.ptr(env), N.stream_ptr())
-            self.acars_core.process(env)
-        if self.ais_core is not None:
-            theta = D.empty(n, "float32")
-            N.call("iqa_quadrature", N.ptr(z_dev), c_int64(n), N.ptr(self._ais_prev), N.ptr(theta), N.stream_ptr())
-            self.ais_core.process(theta)
-        if self.adsb_core is not None:
-            env = D.empty(n, "float32")
-            N.call("iqa_envelope", N.ptr(z_dev), c_int64(n), N.ptr(env), N.stream_ptr())
-            self.adsb_core.process(env)
+        for entry, core, prev in self._side:
+            x = D.empty(n, "float32")
+            if entry.source == "theta":
+                N.call("iqa_quadrature", N.ptr(z_dev), c_int64(n), N.ptr(prev), N.ptr(x), N.stream_ptr())
+            else:
+                N.call("iqa_envelope", N.ptr(z_dev), c_int64(n), N.ptr(x), N.stream_ptr())
+            core.process(x)
 
-    def adsb_finish(self):
-        """The run's ``AdsbResult`` (``None`` without a message, or with adsb off)."""
-        if self.adsb_core is None:
-            return None
-        fin = self.adsb_core.finish()
-        return adsb_parse_frames(self.adsb_core.plan, fin, fin["candidates"])
-
-    def ais_finish(self, frequency=None):
-        """The run's ``AisResult`` (``None`` without a message, or with ais off); ``frequency`` names the channel of the
-        sentences."""
-        if self.ais_core is None:
-            return None
-        fin = self.ais_core.finish()
-        return ais_parse_frames(self.ais_core.plan, fin, fin["candidates"], frequency=frequency)
-
-    def acars_finish(self):
-        """The run's ``AcarsResult`` (``None`` without a message, or with acars off)."""
-        if self.acars_core is None:
-            return None
-        fin = self.acars_core.finish()
-        return acars_parse_messages(self.acars_core.plan, fin, fin["candidates"])
-
-    def tones_finish(self):
-        """The run's ``TonesResult`` (``None`` without an event, or with tones off)."""
-        return None if self.tones_core is None else self.tones_core.result()
-
-    def ax25_finish(self):
-        """The run's ``Ax25Result`` (``None`` without a frame, or with ax25 off)."""
-        if self.afsk_core is None:
-            return None
-        fin = self.afsk_core.finish()
-        return ax25_parse_frames(self.afsk_core.plan, fin, fin["candidates"])
-
-    def pocsag_finish(self):
-        """The run's ``PocsagResult`` (``None`` without a kept sync, or with pocsag off)."""
-        if self.pocsag_core is None:
-            return None
-        return pocsag_parse_batches(self.pocsag_core.plan, self.pocsag_core.finish())
+    def side_result(self, name: str, **context):
+        """The run's result of side decoder ``name`` (``None`` where it found nothing, or is off); ``context``: what names
+        the target in the result (``frequency`` for ais)."""
+        core = self.side.get(name)
+        return None if core is None else core.result(**context)
 
     @property
     def peak(self) -> float:
@@ -816,6 +703,7 @@ class WfmDemod:
         self.alpha = self.decoder.deemph["mono"].alpha  # the DeemphasisFilter rule
         self.core = self.decoder.core  # the pipeline's stream: the decoder's own stage API is not used beside it
         self.rds_core = RdsCore(P.plan_rds(fs_channel)) if rds else None
+        self.side = {"rds": self.rds_core} if rds else {}
         self.rds = None
         self._prev = D.from_numpy(np.array([1 + 0j], dtype=np.complex64))
         self._pilot_sumsq = D.zeros(1, "float64")
@@ -878,9 +766,12 @@ class WfmDemod:
         self._sumsq, self._counts = sumsq, np.diff(np.append(starts, n)) * len(chans)
         self._peak = float(peak.item())
         if self.rds_core is not None and self.stereo:  # (a pilot to lock to)
-            res = rds_result_from(self.rds_core.finish())
-            self.rds = res if res.groups else None
+            self.rds = self.rds_core.result()
         return pcm.cpu().numpy(), len(chans)
+
+    def side_result(self, name: str, **context):
+        """``ChannelDemod.side_result`` for the one side decoder of wfm: the ``RdsResult`` that ``finish`` decoded."""
+        return self.rds if name == "rds" else None
 
     @property
     def peak(self) -> float:
@@ -1063,20 +954,8 @@ class ProcessingPipeline:
     def __init__(self, config: ProcessingConfig, *, rds: bool = False, pocsag: bool = False, ax25: bool = False, tones: bool = False,
                  acars: bool = False, ais: bool = False, adsb: bool = False):
         self.config = config
-        if adsb and (config.demod_mode or "").lower() != "am":
-            raise ValueError("adsb=True needs an am target: Mode S squitters are pulses on a 1090 MHz AM channel (--demod am)")
-        if ais and (config.demod_mode or "").lower() not in ("nfm", "fm"):
-            raise ValueError("ais=True needs an nfm target: AIS is 9600 bit/s GMSK on a narrowband FM channel (--demod nfm)")
-        if rds and (config.demod_mode or "").lower() != "wfm":
-            raise ValueError("rds=True needs a wfm target: RDS rides on a broadcast FM multiplex (--demod wfm)")
-        if pocsag and (config.demod_mode or "").lower() not in ("nfm", "fm"):
-            raise ValueError("pocsag=True needs an nfm target: POCSAG is 2-FSK on a narrowband FM channel (--demod nfm)")
-        if ax25 and (config.demod_mode or "").lower() not in ("nfm", "fm"):
-            raise ValueError("ax25=True needs an nfm target: AX.25 here is Bell-202 AFSK on a narrowband FM channel (--demod nfm)")
-        if tones and (config.demod_mode or "").lower() not in ("nfm", "fm"):
-            raise ValueError("tones=True needs an nfm target: CTCSS and DTMF ride on a narrowband FM voice channel (--demod nfm)")
-        if acars and (config.demod_mode or "").lower() != "am":
-            raise ValueError("acars=True needs an am target: ACARS is audio MSK on an AM airband carrier (--demod am)")
+        flags = dict(rds=rds, pocsag=pocsag, ax25=ax25, tones=tones, acars=acars, ais=ais, adsb=adsb)
+        check_modes(flags, [config.demod_mode], plural=False)
         self._cancelled = False
         self._resolved_chunk_size: int | None = None
         self.chunk_rms_dbfs: list[float] = []
@@ -1087,20 +966,14 @@ class ProcessingPipeline:
         self.channelizer_precision = None  # "fast" / "fine" / "full" / "float32": what the run's channelizer was planned at
         self.wfm_stereo = None  # --demod wfm: whether the run's output is stereo (the pilot test, once per run)
         self.wfm_planes = None  # --demod wfm with keep_channel_audio: the stereo matrix's (a, b) planes, shape (2, n)
-        self.rds_enabled = bool(rds)  # --rds: decode RDS beside wfm
-        self.rds = None  # after run(): the station's RdsResult (None without a pilot, without groups, or with rds off)
-        self.pocsag_enabled = bool(pocsag)  # --pocsag: decode POCSAG beside nfm
-        self.pocsag = None  # after run(): the target's PocsagResult (None without a kept sync, or with pocsag off)
-        self.ax25_enabled = bool(ax25)  # --ax25: decode AX.25 over Bell-202 AFSK beside nfm
-        self.ax25 = None  # after run(): the target's Ax25Result (None without a frame, or with ax25 off)
-        self.tones_enabled = bool(tones)  # --tones: detect CTCSS and DTMF beside nfm
-        self.tones = None  # after run(): the target's TonesResult (None without an event, or with tones off)
-        self.acars_enabled = bool(acars)  # --acars: decode ACARS beside am
-        self.acars = None  # after run(): the target's AcarsResult (None without a message, or with acars off)
-        self.ais_enabled = bool(ais)  # --ais: decode AIS beside nfm
-        self.ais = None  # after run(): the target's AisResult (None without a message, or with ais off)
-        self.adsb_enabled = bool(adsb)  # --adsb: decode Mode S squitters beside am
-        self.adsb = None  # after run(): the target's AdsbResult (None without a message, or with adsb off)
+        for e in SIDE_DECODERS:  # --<name>: decode it beside the target (DESIGN.md section e.section)
+            setattr(self, e.name + "_enabled", bool(flags[e.name]))
+            setattr(self, e.name, None)  # after run(): the target's result (None where it found nothing, or with the decoder off)
+
+    @property
+    def side_enabled(self) -> dict:
+        """name -> True for the side decoders that are switched on: the keywords of a run with the same ones."""
+        return {e.name: True for e in SIDE_DECODERS if getattr(self, e.name + "_enabled")}
 
     def cancel(self) -> None:
         self._cancelled = True
@@ -1128,9 +1001,7 @@ class ProcessingPipeline:
 
     def run(self, progress_sink: ProgressSink | None = None) -> ProcessingResult:
         """One target frequency: a :class:`MultiChannelPipeline` with a single channel."""
-        multi = MultiChannelPipeline([self.config], _owner=self, rds=self.rds_enabled, pocsag=self.pocsag_enabled, ax25=self.ax25_enabled,
-                                     tones=self.tones_enabled, acars=self.acars_enabled, ais=self.ais_enabled,
-                                     adsb=self.adsb_enabled)
+        multi = MultiChannelPipeline([self.config], _owner=self, **self.side_enabled)
         self._multi = multi
         if self._cancelled:
             multi.cancel()
@@ -1152,23 +1023,16 @@ class _Target:
         LOG.info("Designed FIR channel filter with %d taps.", len(self.taps))
         if cfg.filter_block <= 0:
             raise ValueError("block_size must be positive")
+        enabled = dict(getattr(owner, "side_enabled", {}))  # (read once; the constructors have checked it against the modes)
+        rds = enabled.pop("rds", False)  # (WfmDemod's; the others are ChannelDemod's keywords)
         if self.pass_through:
             self.demod = None
         elif self.wfm:
-            self.demod = WfmDemod(fs_channel, deemph_us=cfg.deemph_us, rds=bool(getattr(owner, "rds_enabled", False)))
+            self.demod = WfmDemod(fs_channel, deemph_us=cfg.deemph_us, rds=rds)
         else:
-            self.demod = ChannelDemod(cfg.demod_mode, fs_channel, deemph_us=cfg.deemph_us, agc_enabled=cfg.agc_enabled,
-                                      pocsag=bool(getattr(owner, "pocsag_enabled", False)), ax25=bool(getattr(owner, "ax25_enabled", False)),
-                                      tones=bool(getattr(owner, "tones_enabled", False)), acars=bool(getattr(owner, "acars_enabled", False)),
-                                      ais=bool(getattr(owner, "ais_enabled", False)), adsb=bool(getattr(owner, "adsb_enabled", False)))
+            self.demod = ChannelDemod(cfg.demod_mode, fs_channel, deemph_us=cfg.deemph_us, agc_enabled=cfg.agc_enabled, **enabled)
         self.stereo = None  # wfm: the run's stereo decision (finish)
-        self.rds = None  # wfm with rds: the station's RdsResult (finish)
-        self.pocsag = None  # nfm with pocsag: the target's PocsagResult (finish)
-        self.ax25 = None  # nfm with ax25: the target's Ax25Result (finish)
-        self.tones = None  # nfm with tones: the target's TonesResult (finish)
-        self.acars = None  # am with acars: the target's AcarsResult (finish)
-        self.ais = None  # nfm with ais: the target's AisResult (finish)
-        self.adsb = None  # am with adsb: the target's AdsbResult (finish)
+        self.side_results = {e.name: None for e in SIDE_DECODERS}  # the target's result per side decoder (finish)
         if cfg.iq_order not in N.ORDER:
             raise ValueError(f"Unsupported iq_order '{cfg.iq_order}'")
         self.chan = None
@@ -1277,9 +1141,7 @@ class _Target:
             iqio.write_wav_pcm16(self.output_path, pcm, 48_000, channels=channels)
             self.stereo = self.demod.stereo
             self.owner.wfm_stereo = self.stereo
-            self.rds = self.owner.rds = self.demod.rds
-            if self.rds is not None:
-                LOG.info("RDS %s", self.rds.line())
+            self._finish_side()
             if self.owner.keep_channel_audio:
                 self.owner.wfm_planes = planes
                 self.owner.audio_fs_channel = D.torch_mod().stack(self.demod.channel_audio)  # (channels, n), clipped
@@ -1297,31 +1159,16 @@ class _Target:
         self.peak = self.demod.peak
         self.owner.chunk_rms_dbfs = self.demod.chunk_rms_dbfs()
         LOG.info("Audio peak level %.2f dBFS.", 20.0 * math.log10(max(self.peak, 1e-6)))
-        if self.demod.pocsag_core is not None:
-            self.pocsag = self.owner.pocsag = self.demod.pocsag_finish()
-            if self.pocsag is not None:
-                LOG.info("POCSAG: %d message(s), %d sync word(s).", len(self.pocsag.messages), sum(self.pocsag.syncs.values()))
-        if self.demod.afsk_core is not None:
-            self.ax25 = self.owner.ax25 = self.demod.ax25_finish()
-            if self.ax25 is not None:
-                LOG.info("AX.25: %d frame(s), %d CRC-passing candidate(s).", len(self.ax25.frames), self.ax25.crc_ok)
-        if self.demod.tones_core is not None:
-            self.tones = self.owner.tones = self.demod.tones_finish()
-            if self.tones is not None:
-                LOG.info("Tones: %d CTCSS event(s), %d DTMF digit(s).", len(self.tones.ctcss), len(self.tones.dtmf))
-        if self.demod.acars_core is not None:
-            self.acars = self.owner.acars = self.demod.acars_finish()
-            if self.acars is not None:
-                LOG.info("ACARS: %d message(s), %d CRC-passing candidate(s).", len(self.acars.messages), self.acars.crc_ok)
-        if self.demod.ais_core is not None:
-            self.ais = self.owner.ais = self.demod.ais_finish(frequency=self.target_freq)
-            if self.ais is not None:
-                LOG.info("AIS: %d message(s), %d CRC-passing candidate(s).", len(self.ais.messages), self.ais.crc_ok)
-        if self.demod.adsb_core is not None:
-            self.adsb = self.owner.adsb = self.demod.adsb_finish()
-            if self.adsb is not None:
-                LOG.info("ADS-B: %d message(s) of %d aircraft, %d check-passing position(s).", len(self.adsb.messages), len(self.adsb.aircraft),
-                         self.adsb.crc_ok)
+        self._finish_side()
+
+    def _finish_side(self) -> None:
+        """The active side decoders' results, in table order: kept per target, handed to the owner, logged."""
+        for e in SIDE_DECODERS:
+            if e.name in self.demod.side:
+                res = self.side_results[e.name] = self.demod.side_result(e.name, frequency=self.target_freq)
+                setattr(self.owner, e.name, res)
+                if res is not None:
+                    LOG.info("%s", e.log(res))
 
 
 class MultiChannelPipeline:
@@ -1349,31 +1196,13 @@ class MultiChannelPipeline:
             if not same:
                 raise ValueError("all targets of a multi-channel run must share the input file, format, rate and chunking")
         self.configs = configs
-        if rds and any((c.demod_mode or "").lower() != "wfm" for c in configs):
-            raise ValueError("rds=True needs wfm targets: RDS rides on a broadcast FM multiplex (--demod wfm)")
-        if pocsag and any((c.demod_mode or "").lower() not in ("nfm", "fm") for c in configs):
-            raise ValueError("pocsag=True needs nfm targets: POCSAG is 2-FSK on a narrowband FM channel (--demod nfm)")
-        if ax25 and any((c.demod_mode or "").lower() not in ("nfm", "fm") for c in configs):
-            raise ValueError("ax25=True needs nfm targets: AX.25 here is Bell-202 AFSK on a narrowband FM channel (--demod nfm)")
-        if tones and any((c.demod_mode or "").lower() not in ("nfm", "fm") for c in configs):
-            raise ValueError("tones=True needs nfm targets: CTCSS and DTMF ride on a narrowband FM voice channel (--demod nfm)")
-        if acars and any((c.demod_mode or "").lower() != "am" for c in configs):
-            raise ValueError("acars=True needs am targets: ACARS is audio MSK on an AM airband carrier (--demod am)")
-        if ais and any((c.demod_mode or "").lower() not in ("nfm", "fm") for c in configs):
-            raise ValueError("ais=True needs nfm targets: AIS is 9600 bit/s GMSK on a narrowband FM channel (--demod nfm)")
-        if adsb and any((c.demod_mode or "").lower() != "am" for c in configs):
-            raise ValueError("adsb=True needs am targets: Mode S squitters are pulses on a 1090 MHz AM channel (--demod am)")
-        self.owners = [_owner] if _owner is not None else [ProcessingPipeline(c, rds=rds, pocsag=pocsag, ax25=ax25, tones=tones, acars=acars,
-                                                                              ais=ais, adsb=adsb) for c in configs]
+        flags = dict(rds=rds, pocsag=pocsag, ax25=ax25, tones=tones, acars=acars, ais=ais, adsb=adsb)
+        check_modes(flags, [c.demod_mode for c in configs], plural=True)
+        self.owners = [_owner] if _owner is not None else [ProcessingPipeline(c, **flags) for c in configs]
         self._cancelled = False
         self.wfm_stereo = None  # after run(): per target, the wfm stereo decision (None for the other modes)
-        self.rds = None  # after run(): per target, the RdsResult (None for non-wfm or pilot-less targets, or with rds off)
-        self.pocsag = None  # after run(): per target, the PocsagResult (None without a kept sync, or with pocsag off)
-        self.ax25 = None  # after run(): per target, the Ax25Result (None without a frame, or with ax25 off)
-        self.tones = None  # after run(): per target, the TonesResult (None without an event, or with tones off)
-        self.acars = None  # after run(): per target, the AcarsResult (None without a message, or with acars off)
-        self.ais = None  # after run(): per target, the AisResult (None without a message, or with ais off)
-        self.adsb = None  # after run(): per target, the AdsbResult (None without a message, or with adsb off)
+        for e in SIDE_DECODERS:  # after run(): per target, the side decoder's result (None where it found nothing, or is off)
+            setattr(self, e.name, None)
 
     def cancel(self) -> None:
         self._cancelled = True
@@ -1580,13 +1409,8 @@ class MultiChannelPipeline:
             for t in targets:
                 t.finish()
             self.wfm_stereo = [t.stereo for t in targets]  # per target: True / False for wfm, None for the other modes
-            self.rds = [t.rds for t in targets]
-            self.pocsag = [t.pocsag for t in targets]
-            self.ax25 = [t.ax25 for t in targets]
-            self.tones = [t.tones for t in targets]
-            self.acars = [t.acars for t in targets]
-            self.ais = [t.ais for t in targets]
-            self.adsb = [t.adsb for t in targets]
+            for e in SIDE_DECODERS:
+                setattr(self, e.name, [t.side_results[e.name] for t in targets])
             self.output_paths = [t.output_path for t in targets]  # where each target's audio went
             for t in targets:
                 t.owner.output_path = t.output_path

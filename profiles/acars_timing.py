@@ -150,7 +150,7 @@ def stage_times(path: Path, n_targets: int, acars: bool) -> dict:
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         with CallTimes(("iqa_acars_",)) as ct:
-            results = [dem.acars_finish() for dem in dems]
+            results = [dem.side_result("acars") for dem in dems]
             torch.cuda.synchronize()
             out["finish_ms"] = (time.perf_counter() - t0) * 1e3
         out["finish_device_ms"] = sum(ct.ms.values())

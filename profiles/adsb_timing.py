@@ -107,11 +107,11 @@ def stage_times(raw, fs: float, fs_ch_target: float, adsb: bool) -> dict:
         t_blk += e[0].elapsed_time(e[1])
     out = dict(adsb=adsb, block_ms=t_blk, channel_rate=fs_ch, decimation=d, blocks=SECS)
     if adsb:
-        out["channel_samples"] = dem.adsb_core.pos
+        out["channel_samples"] = dem.side["adsb"].pos
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         with CallTimes(("iqa_adsb_",)) as ct:
-            res = dem.adsb_finish()
+            res = dem.side_result("adsb")
             torch.cuda.synchronize()
             out["finish_ms"] = (time.perf_counter() - t0) * 1e3
         out["finish_device_ms"] = sum(ct.ms.values())

@@ -173,7 +173,7 @@ def stage_times(path: Path, n_targets: int, ais: bool) -> dict:
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         with CallTimes(("iqa_ais_symbols", "iqa_ais_frames")) as ct:
-            results = [dem.ais_finish(frequency=FC + f) for dem, f in zip(dems, OFFSETS)]
+            results = [dem.side_result("ais", frequency=FC + f) for dem, f in zip(dems, OFFSETS)]
             torch.cuda.synchronize()
             out["finish_ms"] = (time.perf_counter() - t0) * 1e3
         out["finish_device_ms"] = sum(ct.ms.values())

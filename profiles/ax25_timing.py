@@ -159,7 +159,7 @@ def stage_times(path: Path, n_targets: int, ax25: bool) -> dict:
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         with CallTimes(("iqa_afsk_bits", "iqa_afsk_frames")) as ct:
-            results = [dem.ax25_finish() for dem in dems]
+            results = [dem.side_result("ax25") for dem in dems]
             torch.cuda.synchronize()
             out["finish_ms"] = (time.perf_counter() - t0) * 1e3
         out["finish_device_ms"] = sum(ct.ms.values())

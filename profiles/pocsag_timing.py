@@ -151,7 +151,7 @@ def stage_times(path: Path, n_targets: int, pocsag: bool) -> dict:
     if pocsag:
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        results = [dem.pocsag_finish() for dem in dems]
+        results = [dem.side_result("pocsag") for dem in dems]
         torch.cuda.synchronize()
         out["finish_ms"] = (time.perf_counter() - t0) * 1e3
         out["messages"] = [0 if r is None else len(r.messages) for r in results]

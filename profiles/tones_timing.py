@@ -125,14 +125,14 @@ def stage_times(path: Path, n_targets: int, tones: bool) -> dict:
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         with CallTimes(("iqa_tones_bank", "iqa_tones_decide")) as ct:
-            results = [dem.tones_finish() for dem in dems]
+            results = [dem.side_result("tones") for dem in dems]
             torch.cuda.synchronize()
             out["finish_ms"] = (time.perf_counter() - t0) * 1e3
         out["finish_device_ms"] = sum(ct.ms.values())
         out["finish_host_ms"] = out["finish_ms"] - out["finish_device_ms"]
         out["finish_per_call_ms"] = dict(ct.ms)
         out["results"] = [summary(r) for r in results]
-        out["stored_u"] = [int(dem.tones_core.joined()["u"].numel()) for dem in dems]
+        out["stored_u"] = [int(dem.side["tones"].joined()["u"].numel()) for dem in dems]
     return out
 
 

@@ -220,6 +220,6 @@ def test_pipelines_take_the_flag_and_check_the_mode(tmp_path):
         with pytest.raises(ValueError, match="--demod am"):
             make()
     with pytest.raises(ValueError, match="acars"):
-        batch.reject_acars(True)
-    batch.reject_acars(False)
+        batch.reject_side_decoders(acars=True)
+    batch.reject_side_decoders(acars=False)
     assert len(A.ProcessingConfig.__dataclass_fields__) == 23

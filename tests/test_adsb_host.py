@@ -239,6 +239,6 @@ def test_pipelines_take_the_flag_and_check_the_mode(tmp_path):
         with pytest.raises(ValueError, match="--demod am"):
             make()
     with pytest.raises(ValueError, match="adsb"):
-        batch.reject_adsb(True)
-    batch.reject_adsb(False)
+        batch.reject_side_decoders(adsb=True)
+    batch.reject_side_decoders(adsb=False)
     assert len(A.ProcessingConfig.__dataclass_fields__) == 23

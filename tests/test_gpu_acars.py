@@ -416,11 +416,11 @@ def test_reset_starts_a_new_run(A):
     run(fresh, second)
     plain = ChannelDemod("am", fs, deemph_us=300.0, agc_enabled=True)
     np.testing.assert_array_equal(audio.cpu().numpy(), run(plain, second).cpu().numpy())
-    assert used.acars_core.pos == fresh.acars_core.pos == int(second.numel()) and plain.acars_finish() is None
-    a, b = used.acars_core.finish(), fresh.acars_core.finish()
+    assert used.side["acars"].pos == fresh.side["acars"].pos == int(second.numel()) and plain.side_result("acars") is None
+    a, b = used.side["acars"].finish(), fresh.side["acars"].finish()
     assert len(b["start"]) >= 1
     for key in ("phase", "s", "start", "nbytes", "data"):
         np.testing.assert_array_equal(a[key], b[key], err_msg=key)
-    assert [m.line() for m in used.acars_finish().messages] == LINES[1:]
+    assert [m.line() for m in used.side_result("acars").messages] == LINES[1:]
     with pytest.raises(ValueError, match="--demod am"):
         ChannelDemod("nfm", fs, deemph_us=300.0, agc_enabled=True, acars=True)

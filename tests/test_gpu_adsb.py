@@ -381,8 +381,8 @@ def test_reset_starts_a_new_run(A):
     audio = run(used, second)
     plain = ChannelDemod("am", fs, deemph_us=300.0, agc_enabled=True)
     np.testing.assert_array_equal(audio.cpu().numpy(), run(plain, second).cpu().numpy())
-    assert used.adsb_core.pos == int(second.numel()) and plain.adsb_finish() is None
-    assert [m.line() for m in used.adsb_finish().messages] == [LINES[2]]
+    assert used.side["adsb"].pos == int(second.numel()) and plain.side_result("adsb") is None
+    assert [m.line() for m in used.side_result("adsb").messages] == [LINES[2]]
     with pytest.raises(ValueError, match="--demod am"):
         ChannelDemod("nfm", fs, deemph_us=300.0, agc_enabled=True, adsb=True)
     with pytest.raises(ValueError, match="--fs-ch"):

@@ -300,12 +300,12 @@ def test_reset_starts_a_new_run(A, streams):
     run(used, second)
     fresh = ChannelDemod("nfm", fs, deemph_us=300.0, agc_enabled=True, ais=True)
     run(fresh, second)
-    assert used.ais_core.pos == fresh.ais_core.pos == int(second.numel())
-    a, b = used.ais_core.finish(), fresh.ais_core.finish()
+    assert used.side["ais"].pos == fresh.side["ais"].pos == int(second.numel())
+    a, b = used.side["ais"].finish(), fresh.side["ais"].finish()
     assert len(b["start"]) >= 3
     for key in ("phase", "s", "start", "nbytes", "data"):
         np.testing.assert_array_equal(a[key], b[key], err_msg=key)
-    assert [m.raw for m in used.ais_finish().messages] == [m.raw for m in fresh.ais_finish(frequency=CHANNEL_B).messages] == [CLASS_B.hex()]
+    assert [m.raw for m in used.side_result("ais").messages] == [m.raw for m in fresh.side_result("ais", frequency=CHANNEL_B).messages] == [CLASS_B.hex()]
     for mode in ("am", "usb"):
         with pytest.raises(ValueError, match="--demod nfm"):
             ChannelDemod(mode, fs, deemph_us=300.0, agc_enabled=True, ais=True)

@@ -285,12 +285,12 @@ def test_reset_starts_a_new_run(A):
     run(used, second)
     fresh = ChannelDemod("nfm", fs, deemph_us=300.0, agc_enabled=True, ax25=True)
     run(fresh, second)
-    assert used.afsk_core.pos == fresh.afsk_core.pos == int(second.numel())
-    a, b = used.afsk_core.finish(), fresh.afsk_core.finish()
+    assert used.side["ax25"].pos == fresh.side["ax25"].pos == int(second.numel())
+    a, b = used.side["ax25"].finish(), fresh.side["ax25"].finish()
     assert len(b["start"]) >= 1
     for key in ("variant", "s", "start", "nbytes", "data"):
         np.testing.assert_array_equal(a[key], b[key], err_msg=key)
-    assert [f.line() for f in used.ax25_finish().frames] == [f.line() for f in fresh.ax25_finish().frames] == _lines()[2:]
+    assert [f.line() for f in used.side_result("ax25").frames] == [f.line() for f in fresh.side_result("ax25").frames] == _lines()[2:]
     with pytest.raises(ValueError, match="ax25"):
         ChannelDemod("am", fs, deemph_us=300.0, agc_enabled=True, ax25=True)
 

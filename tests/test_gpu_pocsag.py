@@ -173,13 +173,13 @@ def test_reset_starts_a_new_run(A):
     run(used, second)
     fresh = ChannelDemod("nfm", fs, deemph_us=300.0, agc_enabled=True, pocsag=True)
     run(fresh, second)
-    assert used.pocsag_core.pos == fresh.pocsag_core.pos == int(second.numel())
-    a, b = used.pocsag_core.finish(), fresh.pocsag_core.finish()
+    assert used.side["pocsag"].pos == fresh.side["pocsag"].pos == int(second.numel())
+    a, b = used.side["pocsag"].finish(), fresh.side["pocsag"].finish()
     assert len(b[1200]["n0"]) == 3
     for baud in M.BAUDS:
         for key in ("n0", "sigma", "inverted", "distance", "words", "raw", "status"):
             np.testing.assert_array_equal(a[baud][key], b[baud][key], err_msg=f"{key} {baud}")
-    assert M.triples(used.pocsag_finish().messages) == M.triples(fresh.pocsag_finish().messages)
+    assert M.triples(used.side_result("pocsag").messages) == M.triples(fresh.side_result("pocsag").messages)
 
 
 @pytest.mark.parametrize("fs", [96_000.0, 10e6 / 104])

@@ -245,12 +245,12 @@ def test_reset_starts_a_new_run(A):
     run(used, second)
     fresh = ChannelDemod("nfm", fs, deemph_us=300.0, agc_enabled=True, tones=True)
     run(fresh, second)
-    assert used.tones_core.pos == fresh.tones_core.pos == int(second.numel())
-    a, b = used.tones_core.finish(), fresh.tones_core.finish()
+    assert used.side["tones"].pos == fresh.side["tones"].pos == int(second.numel())
+    a, b = used.side["tones"].finish(), fresh.side["tones"].finish()
     for key in ("E_ctcss", "E_dtmf", "P", "ctcss", "dtmf"):
         np.testing.assert_array_equal(a[key].cpu().numpy(), b[key].cpu().numpy(), err_msg=key)
-    res = used.tones_finish()
-    assert res.to_json() == fresh.tones_finish().to_json()
+    res = used.side_result("tones")
+    assert res.to_json() == fresh.side_result("tones").to_json()
     assert [e.tone_hz for e in res.ctcss] == [254.1] and [s.digits for s in res.sequences] == [DIGITS]
     with pytest.raises(ValueError, match="tones"):
         ChannelDemod("am", fs, deemph_us=300.0, agc_enabled=True, tones=True)
