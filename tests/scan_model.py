@@ -371,3 +371,148 @@ def stream_blocks(n: int):
     edges = np.concatenate(([0], np.cumsum(STREAM_CUTS), [n]))
     assert edges[-2] < n
     return list(zip(edges[:-1].tolist(), edges[1:].tolist()))
+
+
+# ---- the one-launch (windowed) form of the de-emphasis scan: its window, layouts on its geometry, its sink plan -----------
+
+SPAN = 8192            # FW_SPAN: positions per workgroup of k_fused_windowed, four rounds of 2048
+WINDOW_STEP = 512
+FORGET = 2.0 ** -64    # what a warm-up leaves of the state it ignores
+WINDOWS = tuple(range(WINDOW_STEP, SPAN // 2 + 1, WINDOW_STEP))
+
+# (tau in microseconds, channel rate in Hz, W or None): the de-emphasis settings the product runs and the window each takes
+PRODUCT_WINDOWS = (
+    (50.0, FS_CH, 512),
+    (1.0, 480_000.0, 512),
+    (75.0, 250_000.0, 1024),
+    (300.0, FS_CH, 1536),
+    (75.0, 480_000.0, 2048),
+    (300.0, 192_000.0, 2560),
+    (300.0, 225_000.0, 3072),
+    (300.0, 250_000.0, 3584),
+    (300.0, 288_000.0, 4096),
+    (300.0, 384_000.0, None),
+    (750.0, 131_071.0, None),
+)
+
+
+def product_alpha(tau_us: float, fs: float) -> float:
+    """DeemphasisFilter's pole: exp(-1 / (fs tau)), tau = max(tau_us, 1) microseconds."""
+    return float(np.exp(-1.0 / (fs * max(tau_us * 1e-6, 1e-6))))
+
+
+def alpha_for_need(need: float) -> float:
+    """The pole with alpha^need = 2^-64."""
+    return float(np.exp(-64.0 * np.log(2.0) / need))
+
+
+def window(alpha: float, span: int = SPAN):
+    """The specification of scan_window: the smallest multiple of 512, at least 512, with alpha^W <= 2^-64 and 2 W <= span;
+    None where there is none (no pole in (0, 1), a pole that forgets too slowly): the three launches are kept."""
+    if not (alpha > 0.0 and alpha < 1.0):
+        return None
+    for w in range(WINDOW_STEP, span // 2 + 1, WINDOW_STEP):
+        if alpha ** w <= FORGET:
+            return w
+    return None
+
+
+WINDOWED_LAYOUTS = ("own", "own-1", "own+1", "own-last", "two-in-one", "fifty", "dup-own", "dup-own-1", "warmup-only")
+
+
+def windowed_layout(name: str, n: int, W: int, span: int = SPAN) -> np.ndarray:
+    """Sorted int64 starts inside [0, n), the first one 0, placed on the geometry of the one-launch form: block k owns
+    [k own, min((k + 1) own, n)), own = span - W, and warms up over the W positions in front."""
+    own = span - W
+    edges = np.arange(own, n, own, dtype=np.int64)  # own0 of every block but the first
+    if name in ("own", "own-1", "own+1"):
+        s = edges + {"own": 0, "own-1": -1, "own+1": 1}[name]
+    elif name == "own-last":     # the last sample of every own range (the last block's is n - 1)
+        s = np.append(edges - 1, n - 1)
+    elif name == "two-in-one":   # two starts strictly inside every own range: the general path in every block
+        first = np.arange(0, n, own, dtype=np.int64)
+        s = np.concatenate((first + 1, first + own // 2))
+    elif name == "fifty":        # more than 512 starts above n = 25 600, more than 100 boundaries in a block
+        s = np.arange(0, n, 50, dtype=np.int64)
+    elif name == "dup-own":      # chunk 1 has no samples; block 1's first sample belongs to chunk 2
+        return np.array([0, own, own], dtype=np.int64)
+    elif name == "dup-own-1":    # block 0 crosses two starts at once, the chunk between them empty
+        return np.array([0, own - 1, own - 1], dtype=np.int64)
+    elif name == "warmup-only":  # inside block 0's own range and inside block 1's warm-up
+        s = [own - W // 2]
+    else:
+        raise ValueError(name)
+    s = np.unique(np.concatenate(([0], np.asarray(s, dtype=np.int64))))
+    return s[(s >= 0) & (s < n)]
+
+
+@dataclass
+class BlockPlan:
+    """What sink_count_segments and sink_plan decide for one workgroup of k_fused_windowed."""
+
+    own0: int
+    own1: int
+    seg0: int            # the chunk of the block's first own sample: the last start <= own0
+    seg1: int            # the chunk of its last own sample: the last start <= own1 - 1
+    kind: str            # "uniform" (seg0 == seg1), "simple" (seg1 == seg0 + 1) or "general"
+    bnd: int             # simple: the first index of the high part, segs[seg1]
+    at_own0: bool        # a start (other than index 0) on the first own sample
+    after_own0: bool     # ... on own0 + 1
+    before_own0: bool    # ... on own0 - 1: the last sample of the block in front
+    at_last: bool        # ... on own1 - 1
+    warmup_only: bool    # starts inside [own0 - W, own0) and none inside [own0, own1)
+
+
+def windowed_plan_classes(n: int, W: int, span: int, segs) -> list:
+    """The restatement of the kernel's conditions, block by block (the counts are `start <= index`, so of equal starts
+    the last one takes the samples)."""
+    s = np.asarray(segs, dtype=np.int64)
+    inner = s[1:]
+    own = span - W
+    plans = []
+    for own0 in range(0, n, own):
+        own1 = min(own0 + own, n)
+        seg0 = int(np.count_nonzero(s <= own0)) - 1
+        seg1 = int(np.count_nonzero(s <= own1 - 1)) - 1
+        kind = "uniform" if seg0 == seg1 else "simple" if seg1 == seg0 + 1 else "general"
+        in_warmup = bool(own0 > 0 and np.any((inner >= own0 - W) & (inner < own0)))
+        in_own = bool(np.any((inner >= own0) & (inner < own1)))
+        plans.append(BlockPlan(own0, own1, seg0, seg1, kind, int(s[seg1]) if kind == "simple" else n,
+                               bool(np.any(inner == own0)), bool(np.any(inner == own0 + 1)), bool(np.any(inner == own0 - 1)),
+                               bool(np.any(inner == own1 - 1)), in_warmup and not in_own))
+    return plans
+
+
+def windowed_chunk_of(n: int, W: int, span: int, segs) -> np.ndarray:
+    """The chunk every sample's square is credited to by the one-launch form, from the plans above: a uniform block's go to
+    seg0, a simple block's to seg0 below ``bnd`` and to seg1 from it on, a general block looks every sample up."""
+    s = np.asarray(segs, dtype=np.int64)
+    out = np.empty(n, dtype=np.int64)
+    for p in windowed_plan_classes(n, W, span, s):
+        idx = np.arange(p.own0, p.own1, dtype=np.int64)
+        if p.kind == "general":
+            out[p.own0:p.own1] = np.searchsorted(s, idx, side="right") - 1
+        else:
+            out[p.own0:p.own1] = np.where(idx < p.bnd, p.seg0, p.seg1)
+    return out
+
+
+FIFTY_STARTS = 512  # `fifty` must hold more starts than this in one call: sink_count_segments' loop then runs twice for some threads
+
+
+def windowed_chunk_cases(W: int, span: int = SPAN) -> list:
+    """(layout, n, input class) of the chunk-boundary tests at window W.  Every layout at n = 3 own + W + 5 with class (a),
+    `own` and `own-last` with class (c) as well; `fifty` also at 4 own + 3 and, where that is not above 25 600 samples
+    (own < 6400), at the first own multiple + 3 that is: more than 512 starts at every window."""
+    own = span - W
+    n = 3 * own + W + 5
+    cases = []
+    for lay in WINDOWED_LAYOUTS:
+        cases.append((lay, n, "a"))
+        if lay in ("own", "own-last"):
+            cases.append((lay, n, "c"))
+        if lay == "fifty":
+            cases.append((lay, 4 * own + 3, "a"))
+            if 4 * own + 3 <= 50 * FIFTY_STARTS:
+                cases.append((lay, (50 * FIFTY_STARTS // own + 1) * own + 3, "a"))
+    return cases

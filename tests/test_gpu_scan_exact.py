@@ -133,13 +133,15 @@ def gpu_source(G, mode: str, z_dev, prev: np.complex64 = np.complex64(1 + 0j)) -
     return out.numpy()
 
 
-def gpu_stage(G, op: str, x: np.ndarray, *, state=(), resets=None, x_off=0, y_off=0):
-    """iqa_deemphasis / iqa_dc_block / iqa_agc on float input ``x``: (unclipped output, state after as float64[])."""
+def gpu_stage(G, op: str, x: np.ndarray, *, state=(), resets=None, x_off=0, y_off=0, alpha=None):
+    """iqa_deemphasis / iqa_dc_block / iqa_agc on float input ``x``: (unclipped output, state after as float64[]).
+    ``alpha``: the de-emphasis pole, M.ALPHA where none is given."""
+    alpha = M.ALPHA if alpha is None else alpha
     N, n = G.N, int(x.size)
     x_dev, out, work = dev_in(G, x.astype(np.float32), x_off), Out(G, n, y_off), workspace(G, n)
     st = dev_bytes(G, np.array(state, dtype=np.float64)) if len(state) else None
     if op == "deemph":
-        N.call("iqa_deemphasis", N.ptr(x_dev), c_int64(n), c_double(M.ALPHA), N.ptr(st), N.ptr(out.view), N.ptr(work), N.stream_ptr())
+        N.call("iqa_deemphasis", N.ptr(x_dev), c_int64(n), c_double(alpha), N.ptr(st), N.ptr(out.view), N.ptr(work), N.stream_ptr())
     elif op == "dc":
         N.call("iqa_dc_block", N.ptr(x_dev), c_int64(n), c_double(M.DC_RADIUS), N.ptr(st), N.ptr(out.view), N.ptr(work), N.stream_ptr())
     else:
@@ -154,13 +156,14 @@ class Fused:
     pass
 
 
-def gpu_demod(G, mode, agc, z_dev, segs, *, state_img=None, fresh=False, y_off=0, s_off=0, peak0=0.0):
+def gpu_demod(G, mode, agc, z_dev, segs, *, state_img=None, fresh=False, y_off=0, s_off=0, peak0=0.0, alpha=None):
     """iqa_demodulate (``state_img``: the 32-byte state block going in) or iqa_demodulate_from_reset (``fresh``: state,
-    peak and sums go in filled with 0x7F bytes).  Returns audio, state image, peak, sums[n_segs, 8], scratch."""
+    peak and sums go in filled with 0x7F bytes).  Returns audio, state image, peak, sums[n_segs, 8], scratch.
+    ``alpha``: the de-emphasis pole, M.ALPHA where none is given."""
     N, t, n = G.N, G.torch, int(z_dev.numel())
     segs = np.asarray(segs, dtype=np.int64)
-    p = N.DemodParams(mode=N.DEMOD_MODE[mode], agc_enabled=int(agc), deemph_alpha=M.ALPHA, dc_radius=M.DC_RADIUS,
-                      agc_target=M.AGC_TARGET, agc_decay=M.AGC_DECAY)
+    p = N.DemodParams(mode=N.DEMOD_MODE[mode], agc_enabled=int(agc), deemph_alpha=M.ALPHA if alpha is None else alpha,
+                      dc_radius=M.DC_RADIUS, agc_target=M.AGC_TARGET, agc_decay=M.AGC_DECAY)
     if fresh:
         state = t.full((32,), POISON, dtype=t.uint8, device=G.dev)
         peak = t.full((4,), POISON, dtype=t.uint8, device=G.dev).view(t.float32)
@@ -362,18 +365,20 @@ def test_agc_without_restart_list(G, n):
     check_block(f"agc-null-{n}", y, M.stage_agc(x, None))
 
 
-def _fused_oracle(G, mode, agc, z, z_dev, st, segs, got, img_in=None):
+def _fused_oracle(G, mode, agc, z, z_dev, st, segs, got, img_in=None, alpha=None):
     """The oracle of one fused call from the GPU's own source values; checks the audio (and the scratch of SSB with AGC).
     Returns (the source values, the block whose values reach the sink, the stage entry points' unclipped output, the state
     after, the linear filter's floor term).  The stage entry points start from the state block the fused call read
     (``img_in``; the oracle's own where none is given): in a stream the GPU's y_last may differ from the oracle's by up to F,
-    and the bit-for-bit comparisons with the stages' output (the peak, the scratch) must not hang on that."""
+    and the bit-for-bit comparisons with the stages' output (the peak, the scratch) must not hang on that.
+    ``alpha``: the de-emphasis pole the fused call ran with, M.ALPHA where none is given."""
+    alpha = M.ALPHA if alpha is None else alpha
     u = gpu_source(G, mode, z_dev, st.prev)
-    lin = M.demod_block(mode, u, st, M.ALPHA)
+    lin = M.demod_block(mode, u, st, alpha)
     after = M.advance(mode, st, z, u, lin)
     de_y, dc_x, dc_y = (st.de_y, st.dc_x, st.dc_y) if img_in is None else img_in[8:].view(np.float64)
     if mode == "nfm":
-        v_gpu, _ = gpu_stage(G, "deemph", u, state=[de_y])
+        v_gpu, _ = gpu_stage(G, "deemph", u, state=[de_y], alpha=alpha)
     else:
         v_gpu, _ = gpu_stage(G, "dc", u, state=[dc_x, dc_y])
     if not (agc and mode in ("usb", "lsb")):
