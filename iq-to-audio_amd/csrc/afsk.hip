@@ -12,38 +12,17 @@
 //   ones dropped, a sixth one ends the walk (a closing flag iff the next bit is 0 and 6 bits of the current byte are
 //   collected), more than 330 bytes abort; kept iff >= 17 bytes and the CRC-16/X.25 of all but the last two equals them.
 //
-// k_afsk_correlate: a workgroup owns 2048 consecutive samples.  It quantises them (and the window in front of them) into
-// LDS and stages the four tap tables as one int4 per k, zero-padded to a multiple of 8 taps.  Each thread then makes 8
-// consecutive outputs of all four correlators: per group of 8 taps it reads 8 more t values into a register window of 16
-// and does 8 x 8 x 4 multiply-adds (|t| < 2^23 and |tap| <= 256: the 24-bit multiply-add, which runs at the full vector
-// rate where the 32-bit multiply runs at a quarter of it).  Taps are read at a wave-uniform address (a broadcast).  Lanes
-// are 8 samples apart, so the t image is padded by one word per 8 as k_pocsag_integrate's is: a fixed tap of consecutive
-// lanes is 9 words apart, conflict-free on the 32 banks of a ds_read_b32 half-wave.
+// k_afsk_correlate: sideband.h's tile and front with the four tap tables interleaved (sb_fir_run8<4>: |t| < 2^23 and
+// |tap| <= 256, the 24-bit multiply-add, which runs at the full vector rate where the 32-bit multiply runs at a quarter of
+// it); the thread then makes the energies and the slicer flags of its 8 outputs.
 // k_afsk_bits and k_afsk_frames run once per run on the byte plane and read global memory directly.
-#include "common.h"
+#include "sideband.h"
 
 namespace iqa {
 
-constexpr int AF_THREADS = 256;
-constexpr int AF_RUN = 8;                       // consecutive outputs of a thread of k_afsk_correlate, and its tap group
-constexpr int AF_TILE = AF_THREADS * AF_RUN;    // 2048
-constexpr int AF_MAX_TAPS = (IQA_AFSK_MAX_SPS + AF_RUN - 1) / AF_RUN * AF_RUN;
 constexpr float AF_THETA_SCALE = 4096.0f;
 constexpr int AF_VARIANTS = IQA_AFSK_GAINS * IQA_AFSK_PHASES;  // 24
 constexpr int AF_MIN_FRAME = 17, AF_MAX_FRAME = 330;
-constexpr unsigned AF_CRC_POLY = 0x8408u;
-
-__host__ __device__ constexpr int af_pad(int i) { return i + (i >> 3); }
-__host__ __device__ constexpr int af_taps_padded(int L) { return (L + AF_RUN - 1) / AF_RUN * AF_RUN; }
-
-// acc += a b for |a|, |b| < 2^23 (the low 32 bits of the 24-bit product; the operands are sign-extended from bit 23, which is
-// why iqa_hotpath.h makes |t| < 2^23 a precondition of iqa_afsk_correlate).  Written out: from ``acc += __mul24(a, b)`` the
-// compiler makes 256 separate products per tap group and adds them three at a time, 1.5 instructions and a live register
-// per multiply-add.
-__device__ __forceinline__ void af_mad24(int &acc, int a, int b)
-{
-    asm("v_mad_i32_i24 %0, %1, %2, %0" : "+v"(acc) : "v"(a), "v"(b));
-}
 
 struct AfskCorrArgs {
     const float *theta;   // [n]
@@ -57,65 +36,24 @@ struct AfskCorrArgs {
     int L;
 };
 
-__global__ __launch_bounds__(AF_THREADS) void k_afsk_correlate(AfskCorrArgs g)
+__global__ __launch_bounds__(SB_THREADS) void k_afsk_correlate(AfskCorrArgs g)
 {
     extern __shared__ int4 s_af[];
-    // H = Lp values are staged in front of the tile: Lp - 1 that taps reach, and one more that the register window loads
-    // with its last group of 8 and never uses.
-    const int tid = threadIdx.x, L = g.L, Lp = af_taps_padded(L), H = Lp;
-    int4 *s_taps = s_af;                               // [Lp]: (c_1200, s_1200, c_2200, s_2200)[k], zero for k >= L
-    int *s_t = reinterpret_cast<int *>(s_af + Lp);     // s_t[af_pad(i)] = t at block index A - H + i, i = 0 .. H + AF_TILE - 1
-    const long long A = static_cast<long long>(blockIdx.x) * AF_TILE;
-    for (int k = tid; k < Lp; k += AF_THREADS) {
-        int4 v = make_int4(0, 0, 0, 0);
-        if (k < L) v = make_int4(g.taps[k], g.taps[L + k], g.taps[2 * L + k], g.taps[3 * L + k]);
-        s_taps[k] = v;
-    }
-    for (int i = tid; i < H + AF_TILE; i += AF_THREADS) {
-        const long long a = A - H + i;
-        int v = 0;
-        if (a < 0) {
-            if (g.hist && a >= -(L - 1)) v = g.hist[(L - 1) + a];  // (the index is 0 .. L-2; further back only zero taps reach)
-        } else if (a < g.n) {
-            v = __float2int_rn(g.theta[a] * AF_THETA_SCALE);
-            if (i >= H) g.t_out[a] = v;
-        }
-        s_t[af_pad(i)] = v;
-    }
+    const int tid = threadIdx.x, L = g.L, H = sb_front(L);
+    int *s_taps = reinterpret_cast<int *>(s_af);  // [H][4]: (c_1200, s_1200, c_2200, s_2200)[1 + j]
+    int *s_t = s_taps + 4 * H;                    // the image of t from block index A - H
+    const long long A = static_cast<long long>(blockIdx.x) * SB_TILE;
+    sb_stage_taps<4>(s_taps, g.taps, L, H);
+    sb_stage(s_t, H, A, g.n, g.theta, SbScale{AF_THETA_SCALE}, g.hist, L - 1, g.t_out, H);
     __syncthreads();
-    const long long a0 = A + tid * AF_RUN;
+    const long long a0 = A + tid * SB_RUN;
     if (a0 >= g.n) return;
-    const int first = H + tid * AF_RUN;  // LDS index (unpadded) of this thread's first output
-    int acc[4][AF_RUN];
+    const int tap0[4] = {g.taps[0], g.taps[L], g.taps[2 * L], g.taps[3 * L]};
+    int acc[4][SB_RUN];
+    sb_fir_run8<4>(s_af, s_t, H + tid * SB_RUN, H, tap0, acc);
+    unsigned char sg[SB_RUN];
 #pragma unroll
-    for (int f = 0; f < 4; ++f)
-#pragma unroll
-        for (int r = 0; r < AF_RUN; ++r) acc[f][r] = 0;
-    // w[j] = t at LDS index first - kb - 8 + j, j = 0 .. 15: output r, tap kb + kk reads index first + r - kb - kk = w[8 + r - kk]
-    int w[2 * AF_RUN];
-#pragma unroll
-    for (int j = 0; j < AF_RUN; ++j) w[AF_RUN + j] = s_t[af_pad(first + j)];
-    for (int kb = 0; kb < Lp; kb += AF_RUN) {
-#pragma unroll
-        for (int j = 0; j < AF_RUN; ++j) w[j] = s_t[af_pad(first - kb - AF_RUN + j)];  // (first - kb - 8 >= H - Lp = 0)
-#pragma unroll
-        for (int kk = 0; kk < AF_RUN; ++kk) {
-            const int4 tp = s_taps[kb + kk];
-#pragma unroll
-            for (int r = 0; r < AF_RUN; ++r) {
-                const int v = w[AF_RUN + r - kk];
-                af_mad24(acc[0][r], tp.x, v);
-                af_mad24(acc[1][r], tp.y, v);
-                af_mad24(acc[2][r], tp.z, v);
-                af_mad24(acc[3][r], tp.w, v);
-            }
-        }
-#pragma unroll
-        for (int j = 0; j < AF_RUN; ++j) w[AF_RUN + j] = w[j];
-    }
-    unsigned char sg[AF_RUN];
-#pragma unroll
-    for (int r = 0; r < AF_RUN; ++r) {
+    for (int r = 0; r < SB_RUN; ++r) {
         const long long i1 = acc[0][r], q1 = acc[1][r], i2 = acc[2][r], q2 = acc[3][r];
         const long long e1 = (i1 * i1 + q1 * q1) >> 4, e2 = (i2 * i2 + q2 * q2) >> 4;
         sg[r] = static_cast<unsigned char>((e1 - e2 > 0 ? 1 : 0) | (e1 - 4 * e2 > 0 ? 2 : 0) | (4 * e1 - e2 > 0 ? 4 : 0));
@@ -124,18 +62,7 @@ __global__ __launch_bounds__(AF_THREADS) void k_afsk_correlate(AfskCorrArgs g)
             if (g.e2200) g.e2200[a0 + r] = e2;
         }
     }
-    if (a0 + AF_RUN <= g.n) {  // (a0 is a multiple of 8 and the plane comes from an allocator: 8-byte aligned)
-        unsigned long long packed = 0;
-#pragma unroll
-        for (int r = 0; r < AF_RUN; ++r) packed |= static_cast<unsigned long long>(sg[r]) << (8 * r);
-        if ((reinterpret_cast<uintptr_t>(g.sign) & 7u) == 0) {
-            *reinterpret_cast<unsigned long long *>(g.sign + a0) = packed;
-            return;
-        }
-    }
-#pragma unroll
-    for (int r = 0; r < AF_RUN; ++r)
-        if (a0 + r < g.n) g.sign[a0 + r] = sg[r];
+    sb_store_flags8(g.sign, a0, g.n, sg);
 }
 
 struct AfskBitArgs {
@@ -146,88 +73,38 @@ struct AfskBitArgs {
     int L;
 };
 
-__device__ __forceinline__ long long af_instant(int L, double step, long long i, int p)
+__global__ __launch_bounds__(SB_THREADS) void k_afsk_bits(AfskBitArgs g)
 {
-    return L - 1 + static_cast<long long>(rint(static_cast<double>(8 * i + p) * step));
-}
-
-__global__ __launch_bounds__(AF_THREADS) void k_afsk_bits(AfskBitArgs g)
-{
-    const long long i = static_cast<long long>(blockIdx.x) * AF_THREADS + threadIdx.x;
+    const long long i = static_cast<long long>(blockIdx.x) * SB_THREADS + threadIdx.x;
     const int v = blockIdx.y, gain = v / IQA_AFSK_PHASES, p = v % IQA_AFSK_PHASES;
     if (i >= g.nbits) return;
-    const long long at = af_instant(g.L, g.step, i, p);
+    const long long at = sb_instant(g.L, g.step, i, p);
     unsigned char b = 0;  // (a bit whose instant lies beyond the stream does not exist: the frame kernel never reads it)
     if (at < g.n) {
         b = 1;
         if (i > 0) {
-            const int m = (g.sign[at] >> gain) & 1, m_prev = (g.sign[af_instant(g.L, g.step, i - 1, p)] >> gain) & 1;
+            const int m = (g.sign[at] >> gain) & 1, m_prev = (g.sign[sb_instant(g.L, g.step, i - 1, p)] >> gain) & 1;
             b = m == m_prev ? 1 : 0;
         }
     }
     g.bits[v * g.nbits + i] = b;
 }
 
-struct AfskFrameArgs {
-    const unsigned char *bits;  // [24][nbits]
-    long long nbits;
-    long long count_of[IQA_AFSK_PHASES];  // bits of phase p that exist
-    long long *list;            // [capacity][4]: variant, s, start instant, nbytes
-    unsigned char *slots;       // [capacity][IQA_AFSK_SLOT_BYTES]
-    long long capacity;
-    unsigned long long *counts; // [2]: kept frames; closed candidates of >= 17 bytes
-    double step;
-    int L;
+struct AfskFrameArgs : SbFrameArgs<unsigned char, IQA_AFSK_PHASES> {};  // plane: [24][n] bits; counts[1]: closed candidates of >= 17 bytes
+
+struct AfskBitSource {
+    const unsigned char *__restrict__ b;
+    __device__ unsigned bit(long long j) const { return b[j]; }
+    __device__ unsigned ahead(long long j) const { return b[j]; }
 };
 
-__device__ __forceinline__ unsigned af_crc_byte(unsigned reg, unsigned byte)
+__global__ __launch_bounds__(SB_THREADS) void k_afsk_frames(AfskFrameArgs g)
 {
-    reg ^= byte;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) reg = (reg & 1u) ? (reg >> 1) ^ AF_CRC_POLY : reg >> 1;
-    return reg;
-}
-
-// The walk from s: -1 for an abort / an over-long frame / the end of the stream, else the byte count.  crc_ok: the
-// CRC-16/X.25 of all but the last two bytes equals them (low byte first).  out != NULL also stores the bytes.
-__device__ int af_walk(const unsigned char *__restrict__ b, long long s, long long nb, unsigned char *out, bool &crc_ok)
-{
-    unsigned cur = 0, c0 = 0xFFFFu, c1 = 0xFFFFu, c2 = 0xFFFFu, last = 0, last2 = 0;  // c0: over all bytes; c2: all but two
-    int have = 0, ones = 0, nbytes = 0;
-    crc_ok = false;
-    for (long long j = s; j < nb; ++j) {
-        const unsigned bit = b[j];
-        if (bit) {
-            if (++ones == 6) {
-                if (!(j + 1 < nb && b[j + 1] == 0 && have == 6)) return -1;
-                crc_ok = nbytes >= 2 && ((c2 ^ 0xFFFFu) & 0xFFFFu) == (last2 | (last << 8));
-                return nbytes;
-            }
-        } else {
-            const bool stuffed = ones == 5;
-            ones = 0;
-            if (stuffed) continue;
-        }
-        cur |= bit << have;
-        if (++have == 8) {
-            if (nbytes == AF_MAX_FRAME) return -1;
-            if (out) out[nbytes] = static_cast<unsigned char>(cur);
-            ++nbytes;
-            c2 = c1, c1 = c0, c0 = af_crc_byte(c0, cur);
-            last2 = last, last = cur;
-            cur = 0, have = 0;
-        }
-    }
-    return -1;
-}
-
-__global__ __launch_bounds__(AF_THREADS) void k_afsk_frames(AfskFrameArgs g)
-{
-    const long long s = static_cast<long long>(blockIdx.x) * AF_THREADS + threadIdx.x;
+    const long long s = static_cast<long long>(blockIdx.x) * SB_THREADS + threadIdx.x;
     const int v = blockIdx.y, p = v % IQA_AFSK_PHASES;
     const long long nb = g.count_of[p];
     if (s < 8 || s > nb) return;
-    const unsigned char *b = g.bits + v * g.nbits;
+    const unsigned char *b = g.plane + v * g.n;
     unsigned before = 0, after = 0;  // first bit most significant
     for (int k = 0; k < 8; ++k) before = (before << 1) | b[s - 8 + k];
     if (before != 0x7Eu) return;
@@ -236,23 +113,16 @@ __global__ __launch_bounds__(AF_THREADS) void k_afsk_frames(AfskFrameArgs g)
         if (after == 0x7Eu) return;
     }
     bool crc_ok;
-    const int nbytes = af_walk(b, s, nb, nullptr, crc_ok);
+    const AfskBitSource src{b};
+    const int nbytes = sb_hdlc_walk<AF_MAX_FRAME>(src, s, nb, nullptr, crc_ok);
     if (nbytes < AF_MIN_FRAME) return;
-    atomicAdd(g.counts + 1, 1ULL);
-    if (!crc_ok) return;
-    const unsigned long long at = atomicAdd(g.counts, 1ULL);
-    if (at >= static_cast<unsigned long long>(g.capacity)) return;
-    long long *e4 = g.list + 4 * at;
-    e4[0] = v;
-    e4[1] = s;
-    e4[2] = af_instant(g.L, g.step, s, p);
-    e4[3] = nbytes;
-    unsigned char *slot = g.slots + at * IQA_AFSK_SLOT_BYTES;
-    af_walk(b, s, nb, slot, crc_ok);
+    unsigned char *slot = sb_emit(g, crc_ok, IQA_AFSK_SLOT_BYTES, v, s, p, nbytes);
+    if (!slot) return;
+    sb_hdlc_walk<AF_MAX_FRAME>(src, s, nb, slot, crc_ok);
     for (int k = nbytes; k < IQA_AFSK_SLOT_BYTES; ++k) slot[k] = 0;
 }
 
-static_assert((4 * AF_MAX_TAPS + af_pad(AF_MAX_TAPS + AF_TILE) + 1) * 4 <= 64 * 1024, "the correlator window must fit the default LDS allowance");
+static_assert(sb_fir_words(4, IQA_AFSK_MAX_SPS) * 4 <= 64 * 1024, "the correlator window must fit the default LDS allowance");
 static_assert(12868LL * 256 * 512 < (1LL << 31), "the correlator sums stay inside int32");
 static_assert(IQA_AFSK_SLOT_BYTES >= AF_MAX_FRAME, "a slot holds the longest frame");
 
@@ -278,9 +148,8 @@ extern "C" int iqa_afsk_correlate(const void *theta_dev, int64_t n, const void *
     g.e2200 = static_cast<long long *>(e2200_out_dev);
     g.n = n;
     g.L = window;
-    const int Lp = af_taps_padded(window);
-    const size_t lds = static_cast<size_t>(4 * Lp + af_pad(Lp + AF_TILE) + 1) * sizeof(int);
-    hipLaunchKernelGGL(k_afsk_correlate, grid1d(n, AF_TILE), dim3(AF_THREADS), lds, as_stream(stream), g);
+    const size_t lds = static_cast<size_t>(sb_fir_words(4, window)) * sizeof(int);
+    hipLaunchKernelGGL(k_afsk_correlate, grid1d(n, SB_TILE), dim3(SB_THREADS), lds, as_stream(stream), g);
     return check_launch("k_afsk_correlate");
 }
 
@@ -299,9 +168,9 @@ extern "C" int iqa_afsk_bits(const void *sign_dev, int64_t n, int32_t window, do
     g.nbits = nbits;
     g.step = step;
     g.L = window;
-    dim3 grid = grid1d(nbits, AF_THREADS);
+    dim3 grid = grid1d(nbits, SB_THREADS);
     grid.y = AF_VARIANTS;
-    hipLaunchKernelGGL(k_afsk_bits, grid, dim3(AF_THREADS), 0, as_stream(stream), g);
+    hipLaunchKernelGGL(k_afsk_bits, grid, dim3(SB_THREADS), 0, as_stream(stream), g);
     return check_launch("k_afsk_bits");
 }
 
@@ -314,27 +183,12 @@ extern "C" int iqa_afsk_frames(const void *bits_dev, int64_t nbits, const int64_
     if (window < 8 || window > IQA_AFSK_MAX_SPS) return fail_inval("window must be 8 .. IQA_AFSK_MAX_SPS");
     if (!(step >= 1.0 && step <= IQA_AFSK_MAX_SPS / 8.0)) return fail_inval("step must be sps / 8 with 8 <= sps <= IQA_AFSK_MAX_SPS");
     AfskFrameArgs g;
-    for (int p = 0; p < IQA_AFSK_PHASES; ++p) {
-        if (count_of[p] < 0 || count_of[p] > nbits) return fail_inval("count_of must be 0 .. nbits");
-        g.count_of[p] = count_of[p];
-    }
+    if (!sb_copy_counts(count_of, nbits, g.count_of)) return fail_inval("count_of must be 0 .. nbits");
     if (nbits > (1LL << 37)) return fail_inval("length out of range");
-    if (hipMemsetAsync(counts_dev, 0, 2 * sizeof(long long), as_stream(stream)) != hipSuccess) {
-        set_error("clearing the frame counts failed");
-        return IQA_EHIP;
-    }
+    if (int rc = sb_clear_counts(counts_dev, stream)) return rc;
     if (nbits == 0) return IQA_OK;
     if (!bits_dev || (capacity > 0 && (!list_dev || !slots_dev))) return fail_inval("NULL device pointer");
-    g.bits = static_cast<const unsigned char *>(bits_dev);
-    g.nbits = nbits;
-    g.list = static_cast<long long *>(list_dev);
-    g.slots = static_cast<unsigned char *>(slots_dev);
-    g.capacity = capacity;
-    g.counts = static_cast<unsigned long long *>(counts_dev);
-    g.step = step;
-    g.L = window;
-    dim3 grid = grid1d(nbits + 1, AF_THREADS);
-    grid.y = AF_VARIANTS;
-    hipLaunchKernelGGL(k_afsk_frames, grid, dim3(AF_THREADS), 0, as_stream(stream), g);
+    sb_fill_frames(g, bits_dev, nbits, list_dev, slots_dev, capacity, counts_dev, step, window);
+    hipLaunchKernelGGL(k_afsk_frames, sb_frames_grid(nbits, AF_VARIANTS), dim3(SB_THREADS), 0, as_stream(stream), g);
     return check_launch("k_afsk_frames");
 }

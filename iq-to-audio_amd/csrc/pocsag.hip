@@ -10,28 +10,22 @@
 //   (or the same E at a smaller index).  Codeword c, bit b of a kept sync: (32 S[n + off[32 (1 + c) + b]] < Sigma) xor inverted,
 //   then the BCH(31,21) syndrome (g = 0x769), the parity of all 32 bits and single-error correction.
 //
-// k_pocsag_integrate: a workgroup owns 2048 consecutive samples.  It quantises them (and the max L - 1 values in front of
-// them) into LDS; each thread then makes 8 consecutive outputs per baud: one full window sum, then seven slides.  Lanes
-// are 8 samples apart, so the LDS image is padded by one word per 8 (index i lives at i + i / 8): a fixed tap of
-// consecutive lanes is then 9 words apart, which is conflict-free on the 32 banks a ds_read_b32 half-wave sees.
+// k_pocsag_integrate: sideband.h's tile with all hist_len >= max L - 1 carried values as its front; each thread then makes
+// 8 consecutive outputs per baud: one full window sum, then seven slides.
 // k_pocsag_score: a workgroup stages 1024 + off[31] integrator values; a thread evaluates one n at a time, and for a fixed
 // bit i consecutive lanes read consecutive words.  k_pocsag_keep and k_pocsag_codewords work on the few candidates and
 // kept syncs and read global memory directly.
-#include "common.h"
+#include "sideband.h"
 
 #include <climits>
 
 namespace iqa {
 
-constexpr int PG_THREADS = 256;
-constexpr int PG_RUN = 8;                       // consecutive outputs of a thread of k_pocsag_integrate
-constexpr int PG_TILE = PG_THREADS * PG_RUN;    // 2048
+constexpr int PG_THREADS = SB_THREADS;
 constexpr int PG_SYNC_TILE = 1024;              // positions per workgroup of k_pocsag_score
 constexpr unsigned PG_SYNC_WORD = 0x7CD215D8u;
 constexpr unsigned PG_POLY = 0x769u;            // x^10 + x^9 + x^8 + x^6 + x^5 + x^3 + 1
 constexpr float PG_THETA_SCALE = 1048576.0f;    // 2^20
-
-__host__ __device__ constexpr int pg_pad(int i) { return i + (i >> 3); }
 
 struct PocsagIntArgs {
     const float *theta;  // [n]
@@ -45,23 +39,13 @@ struct PocsagIntArgs {
 
 __global__ __launch_bounds__(PG_THREADS) void k_pocsag_integrate(PocsagIntArgs g)
 {
-    extern __shared__ int s_t[];  // s_t[pg_pad(i)] = t at block index A - H + i, i = 0 .. H + PG_TILE - 1
+    extern __shared__ int s_t[];  // the image of t from block index A - H
     const int tid = threadIdx.x, H = g.hist_len;
-    const long long A = static_cast<long long>(blockIdx.x) * PG_TILE;
-    for (int i = tid; i < H + PG_TILE; i += PG_THREADS) {
-        const long long a = A - H + i;
-        int v = 0;
-        if (a < 0) {
-            v = g.hist ? g.hist[H + a] : 0;  // (-H <= a: the index is 0 .. H-1)
-        } else if (a < g.n) {
-            v = __float2int_rn(g.theta[a] * PG_THETA_SCALE);
-            if (i >= H) g.t_out[a] = v;
-        }
-        s_t[pg_pad(i)] = v;
-    }
+    const long long A = static_cast<long long>(blockIdx.x) * SB_TILE;
+    sb_stage(s_t, H, A, g.n, g.theta, SbScale{PG_THETA_SCALE}, g.hist, H, g.t_out, H);
     __syncthreads();
-    const int first = H + tid * PG_RUN;  // LDS index (unpadded) of this thread's first output
-    const long long a0 = A + tid * PG_RUN;
+    const int first = H + tid * SB_RUN;  // LDS index (unpadded) of this thread's first output
+    const long long a0 = A + tid * SB_RUN;
     if (a0 >= g.n) return;
 #pragma unroll
     for (int b = 0; b < IQA_POCSAG_BAUDS; ++b) {
@@ -69,11 +53,11 @@ __global__ __launch_bounds__(PG_THREADS) void k_pocsag_integrate(PocsagIntArgs g
         if (L == 0) continue;
         int *out = g.s_out[b];
         int acc = 0;
-        for (int k = 0; k < L; ++k) acc += s_t[pg_pad(first - k)];  // (first - k >= H - (L - 1) >= 0)
+        for (int k = 0; k < L; ++k) acc += s_t[sb_pad(first - k)];  // (first - k >= H - (L - 1) >= 0)
         out[a0] = acc;
 #pragma unroll
-        for (int r = 1; r < PG_RUN; ++r) {
-            acc += s_t[pg_pad(first + r)] - s_t[pg_pad(first + r - L)];
+        for (int r = 1; r < SB_RUN; ++r) {
+            acc += s_t[sb_pad(first + r)] - s_t[sb_pad(first + r - L)];
             if (a0 + r < g.n) out[a0 + r] = acc;
         }
     }
@@ -209,7 +193,7 @@ __global__ __launch_bounds__(PG_THREADS) void k_pocsag_codewords(const int *__re
 
 static_assert(pg_syndrome(PG_SYNC_WORD) == 0 && pg_syndrome(0x7A89C197u) == 0, "the sync and idle words are codewords of g");
 static_assert((PG_SYNC_TILE + 31 * IQA_POCSAG_MAX_SPS) * 4 <= 64 * 1024, "the sync window must fit the default LDS allowance");
-static_assert(pg_pad(IQA_POCSAG_MAX_SPS + PG_TILE) * 4 + 4 <= 64 * 1024, "the integrator window must fit the default LDS allowance");
+static_assert(sb_pad(IQA_POCSAG_MAX_SPS + SB_TILE) * 4 + 4 <= 64 * 1024, "the integrator window must fit the default LDS allowance");
 
 }  // namespace iqa
 
@@ -241,8 +225,8 @@ extern "C" int iqa_pocsag_integrate(const void *theta_dev, int64_t n, const void
     g.t_out = static_cast<int *>(t_out_dev);
     g.n = n;
     g.hist_len = hist_len;
-    const size_t lds = static_cast<size_t>(pg_pad(hist_len + PG_TILE) + 1) * sizeof(int);
-    hipLaunchKernelGGL(k_pocsag_integrate, grid1d(n, PG_TILE), dim3(PG_THREADS), lds, as_stream(stream), g);
+    const size_t lds = static_cast<size_t>(sb_pad(hist_len + SB_TILE) + 1) * sizeof(int);
+    hipLaunchKernelGGL(k_pocsag_integrate, grid1d(n, SB_TILE), dim3(PG_THREADS), lds, as_stream(stream), g);
     return check_launch("k_pocsag_integrate");
 }
 

@@ -178,9 +178,10 @@ def _detect(N, D, e_dev, n, sh, pl, taps_dev, outputs: str):
     return out
 
 
-@pytest.mark.parametrize("fs", [19_200.0, 21_600.0, 96_000.0, 957_600.0, 960_000.0])
+@pytest.mark.parametrize("fs", [19_200.0, 21_600.0, 28_800.0, 30_600.0, 41_400.0, 96_000.0, 957_600.0, 960_000.0])
 def test_detector_edge_shapes(A, fs):
-    """L = 8, 9, 40, 399, 400 with their W on a full-scale 0 / emax square wave at 1800 Hz (the largest |I|, |Q| and |y|; the
+    """L = 8, 9, 12, 13, 17, 40, 399, 400 with their W (W mod 8 = 3, 4, 0, 1, 7, 5, 4, 5: the middle three sit on, one behind
+    and one in front of a tap-group boundary) on a full-scale 0 / emax square wave at 1800 Hz (the largest |I|, |Q| and |y|; the
     host test checks the promised widths on it) at n = 1, W - 1, W, W + L - 1, W + L, one workgroup's outputs - 1, + 0, + 1
     and two of them + 3, with the optional outputs all, none and one of each."""
     from iq_to_audio_amd import _dev as D
@@ -190,7 +191,8 @@ def test_detector_edge_shapes(A, fs):
     pl = M.plan(fs)
     plan = P.plan_acars(fs)
     W, L = pl["W"], pl["L"]
-    assert (W, L) == (plan.W, plan.L) == {19_200.0: (11, 8), 21_600.0: (12, 9), 96_000.0: (53, 40), 957_600.0: (532, 399), 960_000.0: (533, 400)}[fs]
+    assert (W, L) == (plan.W, plan.L) == {19_200.0: (11, 8), 21_600.0: (12, 9), 28_800.0: (16, 12), 30_600.0: (17, 13), 41_400.0: (23, 17), 96_000.0: (53, 40),
+                                          957_600.0: (532, 399), 960_000.0: (533, 400)}[fs]
     T = TILE - (L + 7) // 8 * 8
     taps = D.from_numpy(np.ascontiguousarray(plan.taps))
     sizes = [1, W - 1, W, W + L - 1, W + L, T - 1, T, T + 1, 2 * T + 3]
