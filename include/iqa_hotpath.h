@@ -744,6 +744,52 @@ int iqa_psd_frames(int32_t fmt, int32_t iq_order, const void *samples_dev, int64
 int iqa_pair_average_rows(const void *rows_dev, int32_t n_rows, int32_t n_cols, void *out_dev, void *stream);
 
 /* ------------------------------------------------------------------------- *
+ * The occupied channels of a capture (--find-channels)  *
+ * ------------------------------------------------------------------------- */
+
+/* The finder works on the float32 dB rows of iqa_psd_frames (psd_db_f32_dev), frame f of the run at sample f hop, F frames
+ * in all, cut into n_slices = ceil(F / slice_frames) slices of slice_frames frames (the last one may be shorter).  Behind
+ * the quantiser every value is an integer in centi-dB, so the results do not depend on how the frames are cut into calls.
+ * All planes are int32[nbins] with values inside +-2^28 (the finder's own lie within +-30000). */
+#define IQA_FIND_MAX_HALF 8191            /* bins on either side in the window of the local floor */
+#define IQA_FIND_MAX_GAP 255              /* cold bins between two hot ones that can be closed */
+#define IQA_FIND_MAX_SLICE_FRAMES 65536   /* frames of one slice: its int32 sums cannot overflow */
+#define IQA_FIND_C_MIN (-30000)           /* the quantiser's range is IQA_FIND_C_MIN .. -IQA_FIND_C_MIN centi-dB */
+/* One batch of rows.  rows_dev: float32[n_frames][nbins], rows_dev[0] being frame first_frame of the run;
+ * c = clamp(rint(100.0f row), -30000, 30000) (one float32 product, half-even; NaN reads as -30000, +-inf as the ends).
+ * sum_dev: int64[nbins] += c; max_dev: int32[nbins] = max(itself, c) (the caller fills it with IQA_FIND_C_MIN before the
+ * first batch and zeroes the other two); slice_dev: int32[n_slices][nbins], row (first_frame + f) / slice_frames += c.
+ * first_frame + n_frames <= n_slices slice_frames.  c_out_dev: int16[n_frames][nbins] or NULL: c itself. */
+int iqa_find_accumulate(const void *rows_dev, int32_t n_frames, int32_t nbins, int64_t first_frame, int32_t slice_frames,
+                        int32_t n_slices, void *sum_dev, void *max_dev, void *slice_dev, void *c_out_dev, void *stream);
+/* mean_out_dev: int32[nbins] = floor(sum_dev[k] / frames) (floor division of int64; frames >= 1). */
+int iqa_find_mean(const void *sum_dev, int32_t nbins, int64_t frames, void *mean_out_dev, void *stream);
+/* The local floor of a plane: floor_out_dev[k] = the value of rank ((hi - lo) num) / den (0-based, ascending) among
+ * plane_dev[lo .. hi], lo = max(0, k - half), hi = min(nbins - 1, k + half).  0 <= half <= IQA_FIND_MAX_HALF,
+ * 0 <= num <= den <= 65536.  The plane's values must lie inside int16 (they are read as halfwords; anything outside is
+ * clamped to -32768 / 32767 first). */
+int iqa_find_floor(const void *plane_dev, int32_t nbins, int32_t half, int32_t num, int32_t den, void *floor_out_dev, void *stream);
+/* x_out_dev: int32[nbins] = max(mean - fmean - thr, max - fmax - thr_peak).  A bin is hot iff x >= 0 and
+ * |k - dc_bin| > dc_guard (a negative dc_guard: no guard), and closed iff it is hot or lies between two hot bins a < k < b
+ * with b - a - 1 <= gap (0 <= gap <= IQA_FIND_MAX_GAP).  mask_out_dev: uint8[nbins], bit 0 = hot, bit 1 = closed.  The
+ * thresholds lie inside +-2^20. */
+int iqa_find_mask(const void *mean_dev, const void *fmean_dev, const void *max_dev, const void *fmax_dev, int32_t nbins, int32_t thr,
+                  int32_t thr_peak, int32_t gap, int32_t dc_bin, int32_t dc_guard, void *x_out_dev, void *mask_out_dev, void *stream);
+/* A run is a maximal stretch [lo, hi] of closed bins of mask_dev.  Its record is int64[8]: lo, hi, its hot bins, the lowest
+ * index of the maximum of e = mean - fmean, e there, sum w and sum w (k - lo) with w = max(e, 0), max_k (max - fmax).  Runs
+ * with at least min_hot (>= 1) hot bins are kept, appended in any order to list_dev: int64[capacity][8].  counts_dev:
+ * int64[2], zeroed by the call: counts[0] counts ALL kept runs (a count above capacity means the list is incomplete and the
+ * call must be repeated with a larger one; nothing is written behind entry capacity - 1), counts[1] every run. */
+int iqa_find_runs(const void *mean_dev, const void *fmean_dev, const void *max_dev, const void *fmax_dev, const void *mask_dev,
+                  int32_t nbins, int32_t min_hot, void *list_dev, int64_t capacity, void *counts_dev, void *stream);
+/* on_out_dev: uint8[n_runs][n_slices]: run j (record j of list_dev, of which lo and hi are read) is on in slice s iff
+ * sum_{k = lo .. hi} (slice[s][k] - T_s fmean[k]) >= T_s (hi - lo + 1) thr_act in int64, T_s = min(slice_frames,
+ * frames - s slice_frames).  n_slices = ceil(frames / slice_frames); a record with lo < 0, hi >= nbins or lo > hi reads
+ * nothing and is off. */
+int iqa_find_activity(const void *slice_dev, const void *fmean_dev, const void *list_dev, int64_t n_runs, int32_t nbins,
+                      int64_t frames, int32_t slice_frames, int32_t n_slices, int32_t thr_act, void *on_out_dev, void *stream);
+
+/* ------------------------------------------------------------------------- *
  * Audio post-processing: automatic squelch (the reference's --audio-post)    *
  * ------------------------------------------------------------------------- */
 

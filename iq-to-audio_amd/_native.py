@@ -184,6 +184,16 @@ _SIGNATURES = {
     "iqa_adsb_quantise": (ctypes.c_int, [c_void_p, c_int64, c_void_p, c_void_p]),
     "iqa_adsb_search": (ctypes.c_int, [c_void_p, c_int64, c_void_p, ctypes.POINTER(c_int32), c_int32, c_int32, c_void_p, c_void_p, c_void_p,
                                        c_int64, c_void_p, c_void_p]),
+    "iqa_find_accumulate": (ctypes.c_int, [c_void_p, c_int32, c_int32, c_int64, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p,
+                                           c_void_p]),
+    "iqa_find_mean": (ctypes.c_int, [c_void_p, c_int32, c_int64, c_void_p, c_void_p]),
+    "iqa_find_floor": (ctypes.c_int, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
+    "iqa_find_mask": (ctypes.c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32,
+                                     c_void_p, c_void_p, c_void_p]),
+    "iqa_find_runs": (ctypes.c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_int64, c_void_p,
+                                     c_void_p]),
+    "iqa_find_activity": (ctypes.c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_int64, c_int32, c_int32, c_int32, c_void_p,
+                                         c_void_p]),
     "iqa_squelch_workspace_bytes": (c_int64, [c_int64, c_int32]),
     "iqa_squelch_stage_offset": (c_int64, [c_int64, c_int32, c_int32]),
     "iqa_squelch": (ctypes.c_int, [ctypes.POINTER(SquelchParams), ctypes.POINTER(SquelchSeg), c_int32, c_void_p, c_void_p,

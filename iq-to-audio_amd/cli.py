@@ -11,6 +11,8 @@ exist here (reference ``cli.py:151-412, 424-578, 661-741``); the GUI, ``digital`
     python -m iq_to_audio_amd.cli --in capture.wav --ft 400025000 --demod nfm
     python -m iq_to_audio_amd.cli --benchmark
     python -m iq_to_audio_amd.cli --audio-post recordings/ --audio-post-mode adaptive
+    python -m iq_to_audio_amd.cli --in capture_455500000Hz.wav --find-channels
+    python -m iq_to_audio_amd.cli --in capture_455500000Hz.wav --find-top 3 --find-grid 12500 --demod nfm
 """
 from __future__ import annotations
 
@@ -139,6 +141,14 @@ def build_parser() -> argparse.ArgumentParser:
                    help="Overwrite original files when performing --audio-post (default writes -cleaned copies).")
     p.add_argument("--audio-post-suffix", dest="audio_post_suffix", default="-cleaned",
                    help="Suffix to append when writing cleaned copies (default: -cleaned).")
+    p.add_argument("--find-channels", dest="find_channels", action="store_true",
+                   help="List the occupied channels of --in (frequency, width, level over the floor, activity) and stop.")
+    p.add_argument("--find-top", dest="find_top", type=int, metavar="N",
+                   help="Find the channels, then run with the N (1-5) strongest ones as the --ft targets.")
+    p.add_argument("--find-grid", dest="find_grid", type=float, metavar="HZ",
+                   help="Round the --find-top targets to the nearest multiple of HZ (default 1).")
+    p.add_argument("--find-threshold", dest="find_threshold", type=float, metavar="DB",
+                   help="dB a channel's mean spectrum must stand over its local floor (default 6).")
     p.add_argument("--verbose", dest="verbose", action="store_true")
     p.set_defaults(audio_post_trim=True)
     return p
@@ -191,6 +201,59 @@ def run_audio_post(args) -> int:
     return 0
 
 
+def check_find_args(parser, args) -> bool:
+    """``parser.error`` for every misuse of the ``--find-*`` flags; whether channels are to be found."""
+    given = [flag for flag, value in (("--find-channels", args.find_channels or None), ("--find-top", args.find_top),
+                                      ("--find-grid", args.find_grid), ("--find-threshold", args.find_threshold)) if value is not None]
+    if not given:
+        return False
+    for flag, value in (("--ft", args.target_freqs), ("--benchmark", args.benchmark), ("--audio-post", args.audio_post_path),
+                        ("--probe-only", args.probe_only)):
+        if value:
+            parser.error(f"{given[0]} cannot be combined with {flag}.")
+    if args.find_top is not None and not 1 <= args.find_top <= 5:
+        parser.error("--find-top must be between 1 and 5.")
+    for flag, value in (("--find-grid", args.find_grid), ("--find-threshold", args.find_threshold)):
+        if value is not None and not (math.isfinite(value) and value > 0.0):
+            parser.error(f"{flag} must be positive.")
+    if args.find_grid is not None and args.find_top is None:
+        parser.error("--find-grid needs --find-top.")
+    if not args.find_channels and args.find_top is None:
+        parser.error("--find-threshold needs --find-channels or --find-top.")
+    if args.input_path is None:
+        parser.error(f"{given[0]} needs --in.")
+    return True
+
+
+def run_find(args, codec, container):
+    """``--find-channels`` / ``--find-top``: print and store the capture's channels.  Returns (exit code or ``None`` to go on,
+    the ``--ft`` targets of the run that follows)."""
+    from .find import find_channels, select_targets
+
+    options = {} if args.find_threshold is None else {"threshold_db": args.find_threshold}
+    try:
+        result = find_channels(args.input_path, center_freq=args.center_freq, input_format=codec, input_container=container,
+                               input_sample_rate=args.input_sample_rate, iq_order=args.iq_order, max_seconds=args.preview_seconds,
+                               **options)
+    except Exception as exc:  # noqa: BLE001
+        LOG.error("Finding channels failed: %s", exc)
+        if args.verbose:
+            LOG.exception("Debug traceback")
+        return 1, []
+    for line in result.lines():
+        print(line)
+    args.input_path.with_name(f"{args.input_path.stem}.channels.json").write_text(json.dumps(result.to_json(), indent=1) + "\n")
+    if args.find_top is None:
+        return 0, []
+    if not result.channels:
+        LOG.info("No channel found: nothing to demodulate.")
+        return 0, []
+    if result.center_freq is None:
+        LOG.error("--find-top needs a centre frequency: pass --fc or name the capture after it.")
+        return 1, []
+    return None, select_targets(result, args.find_top, args.find_grid or 1.0)
+
+
 def _preview_output_path(config: ProcessingConfig) -> Path:
     """reference preview.py:15-21"""
     base = config.output_path or config.in_path.with_name(f"audio_{int(config.target_freq)}_48k.wav")
@@ -204,6 +267,7 @@ def main(argv: list[str] | None = None) -> int:
         parser.error("--audio-post cannot be combined with --benchmark.")
     if args.audio_post_path and not 0.0 <= args.audio_post_percentile <= 1.0:
         parser.error("--audio-post-noise-percentile must be between 0.0 and 1.0.")
+    finding = check_find_args(parser, args)
     logging.basicConfig(level=logging.DEBUG if args.verbose else logging.INFO, format="%(levelname)s %(message)s")
     for e in SIDE_DECODERS:
         if getattr(args, e.name) and args.demod != e.mode:
@@ -242,6 +306,11 @@ def main(argv: list[str] | None = None) -> int:
 
     if args.input_path is None:
         parser.error("--in is required (or use --benchmark).")
+    if finding:
+        code, frequencies = run_find(args, codec, container)
+        if code is not None:
+            return code
+        LOG.info("Targets from --find-top: %s", ", ".join(f"{f:.0f} Hz" for f in frequencies))
     if not frequencies and not args.probe_only:
         parser.error("Provide at least one --ft target frequency.")
 

@@ -823,6 +823,101 @@ def plan_adsb(fs_channel: float) -> AdsbPlan:
     return AdsbPlan(fs, sps, h, offsets, int(offsets[-1]) + h, int(np.rint(sps)))
 
 
+# ---- channel finder plan (--find-channels) --------------------------------
+
+FIND_MIN_NFFT, FIND_MAX_NFFT = 256, 1 << 18
+FIND_MIN_FRAMES = 8  # the default nfft is halved while fewer frames fit
+FIND_MAX_HALF = 8191  # IQA_FIND_MAX_HALF
+FIND_MAX_GAP = 255  # IQA_FIND_MAX_GAP
+FIND_MAX_SLICE_FRAMES = 65536  # IQA_FIND_MAX_SLICE_FRAMES
+FIND_C_MIN, FIND_C_MAX = -30000, 30000  # centi-dB range of the quantiser (IQA_FIND_C_MIN)
+FIND_RANK = (1, 4)  # the local floor is the lower quartile of its window
+
+
+@dataclass(frozen=True)
+class FindPlan:
+    fs: float
+    n_samples: int
+    nfft: int
+    hop: int  # nfft // 2
+    frames: int  # F = (n - nfft) // hop + 1
+    scale: float  # of the rows, as spectrum._PsdEngine makes it
+    bin_hz: float
+    dc_bin: int
+    max_slices: int
+    slice_frames: int  # T = ceil(F / max_slices)
+    slices: int  # S = ceil(F / T)
+    half: int  # h: bins on either side in the floor's window
+    num: int
+    den: int
+    thr: int  # centi-dB, mean over its floor
+    thr_peak: int  # centi-dB, max over its floor
+    thr_act: int  # centi-dB, a slice's mean over the floor of the mean
+    gap: int  # cold bins between two hot ones that are closed
+    dc_guard: int  # bins on either side of dc_bin that are never hot (negative: none)
+    min_hot: int
+    threshold_db: float
+    peak_threshold_db: float
+
+    def slice_len(self, s: int) -> int:
+        """T_s: the frames of slice ``s`` (the last one may be shorter)."""
+        return min(self.slice_frames, self.frames - s * self.slice_frames)
+
+
+def find_default_nfft(sample_rate: float, n_samples: int) -> int:
+    """The power of two with fs / nfft in (250, 500] Hz, clipped to [256, 2^18] and halved while fewer than 8 frames fit."""
+    nfft = 1 << max(0, math.ceil(math.log2(sample_rate / 500.0)))
+    while nfft < sample_rate / 500.0:  # (log2 of an exact power of two may land a hair low)
+        nfft *= 2
+    nfft = min(max(nfft, FIND_MIN_NFFT), FIND_MAX_NFFT)
+    while nfft > FIND_MIN_NFFT and (n_samples - nfft) // (nfft // 2) + 1 < FIND_MIN_FRAMES:
+        nfft //= 2
+    return nfft
+
+
+def plan_find(sample_rate: float, n_samples: int, *, nfft: int | None = None, threshold_db: float = 6.0,
+              peak_threshold_db: float = 10.0, floor_hz: float = 1e6, gap_hz: float = 5000.0, dc_guard_hz: float = 1000.0,
+              max_slices: int = 256, min_hot: int = 2) -> FindPlan:
+    """The channel finder's constants for a capture of ``n_samples`` frames at ``sample_rate``; ``ValueError`` where the capture
+    holds no frame, a slice would be longer than 65536 frames or an option is out of range."""
+    fs, n = float(sample_rate), int(n_samples)
+    if not math.isfinite(fs) or fs <= 0.0:
+        raise ValueError("the sample rate must be positive")
+    for name, value in (("threshold_db", threshold_db), ("peak_threshold_db", peak_threshold_db), ("floor_hz", floor_hz)):
+        if not math.isfinite(value) or value <= 0.0:
+            raise ValueError(f"{name} must be positive")
+    if not math.isfinite(gap_hz) or gap_hz < 0.0 or not math.isfinite(dc_guard_hz):
+        raise ValueError("gap_hz must not be negative and dc_guard_hz must be finite")
+    if max_slices < 1 or min_hot < 1:
+        raise ValueError("max_slices and min_hot must be at least 1")
+    if nfft is None:
+        if n < FIND_MIN_NFFT:
+            raise ValueError(f"the capture holds {n} samples: not one frame of {FIND_MIN_NFFT}")
+        nfft = find_default_nfft(fs, n)
+    nfft = int(nfft)
+    if nfft < 16 or nfft > FIND_MAX_NFFT or nfft & (nfft - 1):
+        raise ValueError(f"nfft must be a power of two between 16 and {FIND_MAX_NFFT}")
+    if n < nfft:
+        raise ValueError(f"the capture holds {n} samples: not one frame of {nfft}")
+    hop = nfft // 2
+    frames = (n - nfft) // hop + 1
+    slice_frames = -(-frames // int(max_slices))
+    if slice_frames > FIND_MAX_SLICE_FRAMES:
+        raise ValueError(f"{frames} frames in {max_slices} slices are {slice_frames} per slice: more than {FIND_MAX_SLICE_FRAMES}")
+    window = np.hanning(nfft).astype(np.float64)
+    scale = (nfft * fs * float(np.sum(window ** 2) / nfft)) + 1e-18
+    bin_hz = fs / nfft
+    thr = int(np.rint(100.0 * threshold_db))
+    if thr >= 1 << 20 or int(np.rint(100.0 * peak_threshold_db)) >= 1 << 20:
+        raise ValueError("a threshold must stay below 10 485 dB")
+    return FindPlan(fs=fs, n_samples=n, nfft=nfft, hop=hop, frames=frames, scale=scale, bin_hz=bin_hz, dc_bin=nfft // 2,
+                    max_slices=int(max_slices), slice_frames=slice_frames, slices=-(-frames // slice_frames),
+                    half=min(int(floor_hz / 2.0 / bin_hz), FIND_MAX_HALF), num=FIND_RANK[0], den=FIND_RANK[1], thr=thr,
+                    thr_peak=int(np.rint(100.0 * peak_threshold_db)), thr_act=thr // 2, gap=min(int(gap_hz / bin_hz), FIND_MAX_GAP),
+                    dc_guard=int(dc_guard_hz / bin_hz) if dc_guard_hz >= 0.0 else -1, min_hot=int(min_hot),
+                    threshold_db=float(threshold_db), peak_threshold_db=float(peak_threshold_db))
+
+
 # ---- 48 kHz resampler plan (build-defined spec; see DESIGN.md "48 kHz stage") -----------------
 
 RS_ZERO_CROSSINGS = 16
