@@ -212,12 +212,12 @@ extern "C" int iqa_acars_max(const void *e_dev, int64_t n, void *max_out_dev, vo
     if (n < 0) return fail_inval("negative length");
     if (!max_out_dev) return fail_inval("NULL device pointer");
     if (n > (1LL << 40)) return fail_inval("length out of range");
-    if (hipMemsetAsync(max_out_dev, 0, sizeof(unsigned), as_stream(stream)) != hipSuccess) {
+    if (n > 0 && !e_dev) return fail_inval("NULL device pointer");
+    if (hipMemsetAsync(max_out_dev, 0, sizeof(unsigned), as_stream(stream)) != hipSuccess) {  // (behind every check)
         set_error("clearing the maximum failed");
         return IQA_EHIP;
     }
     if (n == 0) return IQA_OK;
-    if (!e_dev) return fail_inval("NULL device pointer");
     const int64_t blocks = (n + SB_THREADS * 16 - 1) / (SB_THREADS * 16);
     hipLaunchKernelGGL(k_acars_max, dim3(static_cast<unsigned>(blocks < 1024 ? blocks : 1024)), dim3(SB_THREADS), 0, as_stream(stream),
                        static_cast<const float *>(e_dev), static_cast<long long>(n), static_cast<unsigned *>(max_out_dev));
@@ -287,9 +287,9 @@ extern "C" int iqa_acars_frames(const void *bits_dev, int64_t nbits, const int64
     AcarsFrameArgs g;
     if (!sb_copy_counts(count_of, nbits, g.count_of)) return fail_inval("count_of must be 0 .. nbits");
     if (nbits > (1LL << 37)) return fail_inval("length out of range");
-    if (int rc = sb_clear_counts(counts_dev, stream)) return rc;
+    if (nbits > 0 && (!bits_dev || (capacity > 0 && (!list_dev || !slots_dev)))) return fail_inval("NULL device pointer");
+    if (int rc = sb_clear_counts(counts_dev, stream)) return rc;  // (behind every check: a refused call changes no buffer)
     if (nbits == 0) return IQA_OK;
-    if (!bits_dev || (capacity > 0 && (!list_dev || !slots_dev))) return fail_inval("NULL device pointer");
     sb_fill_frames(g, bits_dev, nbits, list_dev, slots_dev, capacity, counts_dev, step, window);
     hipLaunchKernelGGL(k_acars_frames, sb_frames_grid(nbits, IQA_ACARS_PHASES), dim3(SB_THREADS), 0, as_stream(stream), g);
     return check_launch("k_acars_frames");

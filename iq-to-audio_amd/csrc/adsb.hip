@@ -173,12 +173,12 @@ extern "C" int iqa_adsb_search(const void *q_dev, int64_t n, const void *offsets
         if (offsets_host[k] < offsets_host[k - 1]) return fail_inval("the offsets must ascend");
     if (static_cast<int64_t>(offsets_host[IQA_ADSB_CHIPS - 1]) + h > span) return fail_inval("o[239] + h must be <= span");
     if (n > (1LL << 40)) return fail_inval("length out of range");
-    if (hipMemsetAsync(counts_dev, 0, 2 * sizeof(long long), as_stream(stream)) != hipSuccess) {
+    if (n >= span && (!q_dev || !offsets_dev || (capacity > 0 && (!list_dev || !slots_dev)))) return fail_inval("NULL device pointer");
+    if (hipMemsetAsync(counts_dev, 0, 2 * sizeof(long long), as_stream(stream)) != hipSuccess) {  // (behind every check)
         set_error("clearing the frame counts failed");
         return IQA_EHIP;
     }
     if (n < span) return IQA_OK;
-    if (!q_dev || !offsets_dev || (capacity > 0 && (!list_dev || !slots_dev))) return fail_inval("NULL device pointer");
     AdsbSearchArgs g;
     g.q = static_cast<const unsigned short *>(q_dev);
     g.o = static_cast<const int *>(offsets_dev);

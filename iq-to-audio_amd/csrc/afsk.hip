@@ -185,9 +185,9 @@ extern "C" int iqa_afsk_frames(const void *bits_dev, int64_t nbits, const int64_
     AfskFrameArgs g;
     if (!sb_copy_counts(count_of, nbits, g.count_of)) return fail_inval("count_of must be 0 .. nbits");
     if (nbits > (1LL << 37)) return fail_inval("length out of range");
-    if (int rc = sb_clear_counts(counts_dev, stream)) return rc;
+    if (nbits > 0 && (!bits_dev || (capacity > 0 && (!list_dev || !slots_dev)))) return fail_inval("NULL device pointer");
+    if (int rc = sb_clear_counts(counts_dev, stream)) return rc;  // (behind every check: a refused call changes no buffer)
     if (nbits == 0) return IQA_OK;
-    if (!bits_dev || (capacity > 0 && (!list_dev || !slots_dev))) return fail_inval("NULL device pointer");
     sb_fill_frames(g, bits_dev, nbits, list_dev, slots_dev, capacity, counts_dev, step, window);
     hipLaunchKernelGGL(k_afsk_frames, sb_frames_grid(nbits, AF_VARIANTS), dim3(SB_THREADS), 0, as_stream(stream), g);
     return check_launch("k_afsk_frames");

@@ -327,12 +327,12 @@ extern "C" int iqa_find_runs(const void *mean_dev, const void *fmean_dev, const 
     if (nbins > FD_MAX_BINS) return fail_inval("nbins out of range");
     if (min_hot < 1) return fail_inval("min_hot must be at least 1");
     if (!counts_dev) return fail_inval("NULL device pointer");
-    if (hipMemsetAsync(counts_dev, 0, 2 * sizeof(long long), as_stream(stream)) != hipSuccess) {
+    if (nbins > 0 && (!mean_dev || !fmean_dev || !max_dev || !fmax_dev || !mask_dev || (capacity > 0 && !list_dev))) return fail_inval("NULL device pointer");
+    if (hipMemsetAsync(counts_dev, 0, 2 * sizeof(long long), as_stream(stream)) != hipSuccess) {  // (behind every check)
         set_error("clearing the run counts failed");
         return IQA_EHIP;
     }
     if (nbins == 0) return IQA_OK;
-    if (!mean_dev || !fmean_dev || !max_dev || !fmax_dev || !mask_dev || (capacity > 0 && !list_dev)) return fail_inval("NULL device pointer");
     FindRunsArgs g;
     g.mean = static_cast<const int *>(mean_dev);
     g.fmean = static_cast<const int *>(fmean_dev);

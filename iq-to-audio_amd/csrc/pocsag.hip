@@ -244,12 +244,12 @@ extern "C" int iqa_pocsag_sync(const void *s_dev, int64_t n, const int32_t offse
     }
     if (o.off[31] > 31 * IQA_POCSAG_MAX_SPS) return fail_inval("offsets[31] must not exceed 31 IQA_POCSAG_MAX_SPS");
     if (n > (1LL << 40)) return fail_inval("length out of range");
-    if (hipMemsetAsync(count_dev, 0, sizeof(long long), as_stream(stream)) != hipSuccess) {
+    if (n > 0 && (!s_dev || !score_dev || (capacity > 0 && !list_dev))) return fail_inval("NULL device pointer");
+    if (hipMemsetAsync(count_dev, 0, sizeof(long long), as_stream(stream)) != hipSuccess) {  // (behind every check)
         set_error("clearing the sync count failed");
         return IQA_EHIP;
     }
     if (n == 0) return IQA_OK;
-    if (!s_dev || !score_dev || (capacity > 0 && !list_dev)) return fail_inval("NULL device pointer");
     const int *S = static_cast<const int *>(s_dev);
     long long *score = static_cast<long long *>(score_dev);
     const long long n_eval = n - o.off[31] > 0 ? n - o.off[31] : 0;

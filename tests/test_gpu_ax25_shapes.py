@@ -182,3 +182,22 @@ def test_bits_on_a_plane_that_ends_on_an_instant(A, fs):
             got = out.cpu().numpy()
             assert (got[24 * nbits :] == SENT8).all()
             np.testing.assert_array_equal(got[: 24 * nbits].reshape(24, nbits), want, err_msg=f"n {n}, nbits {nbits}")
+
+
+# ---- d. iqa_afsk_frames refuses before it clears ------------------------------------------------------------------------
+
+
+def test_frames_refuse_before_they_clear_the_counters(A):
+    """A call refused for a NULL bit plane, list or slot pointer leaves the counters, and every other buffer, as they were."""
+    from iq_to_audio_amd import _dev as D
+    from iq_to_audio_amd import _native as N
+
+    for missing in ("bits", "list", "slots"):
+        bufs = dict(bits=D.from_numpy(np.full(4096, SENT8, dtype=np.uint8)), list=D.from_numpy(np.full(64, SENT64, dtype=np.int64)),
+                    slots=D.from_numpy(np.full(4096, SENT8, dtype=np.uint8)), counts=D.from_numpy(np.array([SENT64, SENT64, SENT64], dtype=np.int64)))
+        arg = {k: None if k == missing else v for k, v in bufs.items()}
+        with pytest.raises(ValueError, match="NULL device pointer"):
+            N.call("iqa_afsk_frames", N.ptr(arg["bits"]), c_int64(8), (c_int64 * 8)(*[8] * 8), c_int32(40), c_double(5.0), N.ptr(arg["list"]), N.ptr(arg["slots"]),
+                   c_int64(4), N.ptr(arg["counts"]), N.stream_ptr())
+        D.torch_mod().cuda.synchronize()
+        assert all((v.cpu().numpy() == (SENT8 if v.dtype == D.torch_mod().uint8 else SENT64)).all() for v in bufs.values()), missing

@@ -395,3 +395,19 @@ def test_activity_one_slice_one_frame_no_run(G):
     # no run: nothing is written
     got, raw = G.activity(slices, fmean, records[:0], T=1, F=3, thr_act=thr_act)
     assert got.shape == (0, 3) and raw.tolist() == [77]
+
+
+def test_runs_refuse_before_they_clear_the_counters(G):
+    """A call refused for a NULL plane, mask or list pointer leaves the counters, and every other buffer, as they were."""
+    from iq_to_audio_amd import _dev as D
+    from iq_to_audio_amd import _native as N
+
+    names = ("mean", "fmean", "max", "fmax", "mask", "list")
+    for missing in names:
+        bufs = {k: D.from_numpy(np.full(256, -7, dtype=np.int64)) for k in names + ("counts",)}
+        arg = {k: None if k == missing else v for k, v in bufs.items()}
+        with pytest.raises(ValueError, match="NULL device pointer"):
+            N.call("iqa_find_runs", *(N.ptr(arg[k]) for k in names[:5]), c_int32(64), c_int32(1), N.ptr(arg["list"]), c_int64(4), N.ptr(arg["counts"]),
+                   N.stream_ptr())
+        D.torch_mod().cuda.synchronize()
+        assert all((v.cpu().numpy() == -7).all() for v in bufs.values()), missing

@@ -401,3 +401,20 @@ def test_codewords_at_the_largest_window(A):
     got = _codewords(S, BP384, [(832, 0, False)])
     for g, w, name in zip(got, want, ("corrected", "raw", "status")):
         np.testing.assert_array_equal(g, w, err_msg=name)
+
+
+def test_sync_refuses_before_it_clears_the_count(A):
+    """A call refused for a NULL plane, score or list pointer leaves the count, and every other buffer, as they were."""
+    from iq_to_audio_amd import _dev as D
+    from iq_to_audio_amd import _native as N
+
+    offs = (c_int32 * 32)(*[int(v) for v in BP8["off"][:32]])
+    for missing in ("s", "score", "list"):
+        bufs = dict(s=D.from_numpy(np.full(1024, SENT, dtype=np.int32)), score=D.from_numpy(np.full(1024, SENT, dtype=np.int64)),
+                    list=D.from_numpy(np.full(64, SENT, dtype=np.int64)), count=D.from_numpy(np.array([SENT, SENT], dtype=np.int64)))
+        arg = {k: None if k == missing else v for k, v in bufs.items()}
+        with pytest.raises(ValueError, match="NULL device pointer"):
+            N.call("iqa_pocsag_sync", N.ptr(arg["s"]), c_int64(1024), offs, c_int32(BP8["h"]), N.ptr(arg["score"]), N.ptr(arg["list"]), c_int64(4),
+                   N.ptr(arg["count"]), N.stream_ptr())
+        D.torch_mod().cuda.synchronize()
+        assert all((v.cpu().numpy() == SENT).all() for v in bufs.values()), missing
