@@ -790,6 +790,26 @@ int iqa_find_activity(const void *slice_dev, const void *fmean_dev, const void *
                       int64_t frames, int32_t slice_frames, int32_t n_slices, int32_t thr_act, void *on_out_dev, void *stream);
 
 /* ------------------------------------------------------------------------- *
+ * What a found channel is (--find-describe)            *
+ * ------------------------------------------------------------------------- */
+
+#define IQA_DESCRIBE_MAX_SHIFT 30   /* |sh| of the quantiser */
+/* Rows of iqa_describe_accumulate for n samples: ceil(n / 2048), 0 for n <= 0. */
+int64_t iqa_describe_tiles(int64_t n);
+/* Eight integer sums of a channel's baseband.  z_dev: complex64[n], z_dev[0] being sample pos of the channel stream (decimation
+ * D, filter delay `delay` raw frames).  q = clamp(rintf(ldexpf(x, sh)), -32767, 32767) per component (float32, half-even; NaN
+ * reads as 0, +-inf as +-32767).  Sample m counts iff gate_dev[s] != 0 (uint8[S]) with s = min(max(m D - delay, 0) / hop,
+ * F - 1) / T in int64; hop, T, F and S = ceil(F / T) are the find plan's.  With p = qi^2 + qq^2 and, against the sample in
+ * front, cr = qi qi' + qq qq', ci = qq qi' - qi qq', a = floor(sqrt(p p')), every tile of 2048 consecutive samples of the
+ * call writes one row of partials_dev (int64[iqa_describe_tiles(n)][8]): the gated samples, the pairs whose two samples are
+ * both gated, sum p, sum (p >> 8)^2, sum floor(sqrt(p)) over the gated samples, sum cr, sum ci, sum a over those pairs.
+ * prev_dev: complex64[1], the sample in front of z_dev[0], or NULL (sample 0 of the call then forms no pair; required at
+ * pos 0).  Exact integers: the rows' sums do not depend on how the stream is cut into calls.  (pos + n) D < 2^62.
+ * n = 0 returns IQA_OK and touches no pointer. */
+int iqa_describe_accumulate(const void *z_dev, int64_t n, int64_t pos, const void *prev_dev, int32_t sh, int32_t D, int32_t delay,
+                            int32_t hop, int32_t T, int64_t F, int32_t S, const void *gate_dev, void *partials_dev, void *stream);
+
+/* ------------------------------------------------------------------------- *
  * Audio post-processing: automatic squelch (the reference's --audio-post)    *
  * ------------------------------------------------------------------------- */
 

@@ -17,6 +17,7 @@ exist here (reference ``cli.py:151-412, 424-578, 661-741``); the GUI, ``digital`
 from __future__ import annotations
 
 import argparse
+import copy
 import dataclasses
 import json
 import logging
@@ -149,6 +150,12 @@ def build_parser() -> argparse.ArgumentParser:
                    help="Round the --find-top targets to the nearest multiple of HZ (default 1).")
     p.add_argument("--find-threshold", dest="find_threshold", type=float, metavar="DB",
                    help="dB a channel's mean spectrum must stand over its local floor (default 6).")
+    p.add_argument("--find-describe", dest="find_describe", action="store_true",
+                   help="Find the channels, then measure each one in a second pass: a label (nfm, am, ssb, wfm, carrier, unknown) "
+                        "and a suggested --demod, --bw and frequency.  Implies --find-channels.")
+    p.add_argument("--find-auto", dest="find_auto", action="store_true",
+                   help="With --find-top N: take the N strongest channels whose label is known and run each with its own "
+                        "suggested --demod, --bw and frequency.")
     p.add_argument("--verbose", dest="verbose", action="store_true")
     p.set_defaults(audio_post_trim=True)
     return p
@@ -204,7 +211,9 @@ def run_audio_post(args) -> int:
 def check_find_args(parser, args) -> bool:
     """``parser.error`` for every misuse of the ``--find-*`` flags; whether channels are to be found."""
     given = [flag for flag, value in (("--find-channels", args.find_channels or None), ("--find-top", args.find_top),
-                                      ("--find-grid", args.find_grid), ("--find-threshold", args.find_threshold)) if value is not None]
+                                      ("--find-grid", args.find_grid), ("--find-threshold", args.find_threshold),
+                                      ("--find-describe", args.find_describe or None), ("--find-auto", args.find_auto or None))
+             if value is not None]
     if not given:
         return False
     for flag, value in (("--ft", args.target_freqs), ("--benchmark", args.benchmark), ("--audio-post", args.audio_post_path),
@@ -218,7 +227,12 @@ def check_find_args(parser, args) -> bool:
             parser.error(f"{flag} must be positive.")
     if args.find_grid is not None and args.find_top is None:
         parser.error("--find-grid needs --find-top.")
-    if not args.find_channels and args.find_top is None:
+    if args.find_auto and args.find_top is None:
+        parser.error("--find-auto needs --find-top.")
+    for e in SIDE_DECODERS:
+        if args.find_auto and getattr(args, e.name):
+            parser.error(f"--find-auto cannot be combined with --{e.name}.")
+    if not args.find_channels and not args.find_describe and args.find_top is None:
         parser.error("--find-threshold needs --find-channels or --find-top.")
     if args.input_path is None:
         parser.error(f"{given[0]} needs --in.")
@@ -226,23 +240,37 @@ def check_find_args(parser, args) -> bool:
 
 
 def run_find(args, codec, container):
-    """``--find-channels`` / ``--find-top``: print and store the capture's channels.  Returns (exit code or ``None`` to go on,
-    the ``--ft`` targets of the run that follows)."""
+    """``--find-channels`` / ``--find-describe`` / ``--find-top``: print and store the capture's channels and, where asked for,
+    their descriptions.  Returns (exit code or ``None`` to go on, the targets of the run that follows: frequencies, or with
+    ``--find-auto`` (frequency, demod, bw) each)."""
     from .find import find_channels, select_targets
 
     options = {} if args.find_threshold is None else {"threshold_db": args.find_threshold}
+    describing = args.find_describe or args.find_auto
+    if describing:
+        options["describe"] = True
+    described = None
     try:
         result = find_channels(args.input_path, center_freq=args.center_freq, input_format=codec, input_container=container,
                                input_sample_rate=args.input_sample_rate, iq_order=args.iq_order, max_seconds=args.preview_seconds,
                                **options)
+        if describing:
+            result, described = result
     except Exception as exc:  # noqa: BLE001
         LOG.error("Finding channels failed: %s", exc)
         if args.verbose:
             LOG.exception("Debug traceback")
         return 1, []
-    for line in result.lines():
-        print(line)
+    if described is None or not result.channels:
+        for line in result.lines():
+            print(line)
+    else:
+        for line, about in zip(result.lines(), described.lines()):
+            print(line)
+            print(about)
     args.input_path.with_name(f"{args.input_path.stem}.channels.json").write_text(json.dumps(result.to_json(), indent=1) + "\n")
+    if described is not None:
+        args.input_path.with_name(f"{args.input_path.stem}.describe.json").write_text(json.dumps(described.to_json(), indent=1) + "\n")
     if args.find_top is None:
         return 0, []
     if not result.channels:
@@ -251,7 +279,17 @@ def run_find(args, codec, container):
     if result.center_freq is None:
         LOG.error("--find-top needs a centre frequency: pass --fc or name the capture after it.")
         return 1, []
-    return None, select_targets(result, args.find_top, args.find_grid or 1.0)
+    if not args.find_auto:
+        return None, select_targets(result, args.find_top, args.find_grid or 1.0)
+    from .describe import select_auto_targets
+
+    targets, skipped = select_auto_targets(result, described, args.find_top, args.find_grid or 1.0)
+    for ch in skipped:
+        LOG.info("--find-auto skips %.0f Hz: its modulation is unknown.", ch.freq_hz)
+    if not targets:
+        LOG.info("No channel of known modulation: nothing to demodulate.")
+        return 0, []
+    return None, targets
 
 
 def _preview_output_path(config: ProcessingConfig) -> Path:
@@ -262,7 +300,8 @@ def _preview_output_path(config: ProcessingConfig) -> Path:
 
 def main(argv: list[str] | None = None) -> int:
     parser = build_parser()
-    args = resolve_mode_defaults(parser.parse_args(argv))
+    given = parser.parse_args(argv)  # (the unset --bw / --fs-ch / --deemph still marked: --find-auto resolves them per target)
+    args = resolve_mode_defaults(copy.copy(given))
     if args.audio_post_path and args.benchmark:
         parser.error("--audio-post cannot be combined with --benchmark.")
     if args.audio_post_path and not 0.0 <= args.audio_post_percentile <= 1.0:
@@ -287,13 +326,16 @@ def main(argv: list[str] | None = None) -> int:
         if any(math.isclose(f, g, rel_tol=0.0, abs_tol=0.5) for g in frequencies[:i]):
             parser.error("Duplicate target frequencies are not allowed.")
 
-    shared = dict(bandwidth=args.bandwidth, center_freq=args.center_freq,
-                  center_freq_source="cli" if args.center_freq is not None else None, demod_mode=args.demod,
-                  fs_ch_target=args.fs_ch, deemph_us=args.deemph_us, agc_enabled=args.agc_enabled,
-                  chunk_size=args.chunk_size, filter_block=args.filter_block, iq_order=args.iq_order,
-                  probe_only=args.probe_only, mix_sign_override=args.mix_sign, fft_workers=args.fft_workers,
-                  input_format=codec, input_container=container, input_format_source="cli" if codec else None,
-                  input_sample_rate=args.input_sample_rate)
+    def settings(a) -> dict:
+        return dict(bandwidth=a.bandwidth, center_freq=a.center_freq,
+                    center_freq_source="cli" if a.center_freq is not None else None, demod_mode=a.demod,
+                    fs_ch_target=a.fs_ch, deemph_us=a.deemph_us, agc_enabled=a.agc_enabled,
+                    chunk_size=a.chunk_size, filter_block=a.filter_block, iq_order=a.iq_order,
+                    probe_only=a.probe_only, mix_sign_override=a.mix_sign, fft_workers=a.fft_workers,
+                    input_format=codec, input_container=container, input_format_source="cli" if codec else None,
+                    input_sample_rate=a.input_sample_rate)
+
+    shared = settings(args)
 
     if args.benchmark:
         try:
@@ -306,11 +348,21 @@ def main(argv: list[str] | None = None) -> int:
 
     if args.input_path is None:
         parser.error("--in is required (or use --benchmark).")
+    per_target: dict = {}  # --find-auto: a target's own settings
     if finding:
         code, frequencies = run_find(args, codec, container)
         if code is not None:
             return code
-        LOG.info("Targets from --find-top: %s", ", ".join(f"{f:.0f} Hz" for f in frequencies))
+        if args.find_auto:
+            # every target with its own suggested mode and bandwidth, the unset --fs-ch / --deemph resolved for that mode
+            for freq, demod, bw in frequencies:
+                mine = copy.copy(given)
+                mine.demod, mine.bandwidth = demod, float(bw)
+                per_target[freq] = settings(resolve_mode_defaults(mine))
+                LOG.info("Target from --find-auto: %.0f Hz, --demod %s --bw %.0f", freq, demod, bw)
+            frequencies = [t[0] for t in frequencies]
+        else:
+            LOG.info("Targets from --find-top: %s", ", ".join(f"{f:.0f} Hz" for f in frequencies))
     if not frequencies and not args.probe_only:
         parser.error("Provide at least one --ft target frequency.")
 
@@ -322,18 +374,23 @@ def main(argv: list[str] | None = None) -> int:
     configs = []
     for freq in frequencies or [0.0]:
         config = ProcessingConfig(in_path=args.input_path, target_freq=freq, output_path=annotate(args.output_path, freq),
-                                  dump_iq_path=annotate(args.dump_iq, freq), **shared)
+                                  dump_iq_path=annotate(args.dump_iq, freq), **per_target.get(freq, shared))
         if args.preview_seconds:
             config = dataclasses.replace(config, max_input_seconds=args.preview_seconds,
                                          output_path=_preview_output_path(config))
         configs.append(config)
-    LOG.info("=== Processing %d target(s) in one pass over %s ===", len(configs), args.input_path)
+    LOG.info("=== Processing %d target(s) in %s over %s ===", len(configs), "a pass each" if per_target else "one pass", args.input_path)
     try:
         # the reference loops whole pipelines over the targets (cli.py:683-710); here the capture is read once
         extras = {e.name: getattr(args, e.name) for e in SIDE_DECODERS}
-        runner = MultiChannelPipeline(configs, **extras) if len(configs) > 1 else ProcessingPipeline(configs[0], **extras)
-        results = runner.run(progress_sink=None)
-        results = results if len(configs) > 1 else [results]
+        if per_target:
+            # --find-auto: a pipeline per target, so that every output is what an explicit run with its --ft, --demod and
+            # --bw writes, bit for bit (the targets differ in mode and rate: a shared pass would group few of them)
+            results = [ProcessingPipeline(c).run(progress_sink=None) for c in configs]
+        else:
+            runner = MultiChannelPipeline(configs, **extras) if len(configs) > 1 else ProcessingPipeline(configs[0], **extras)
+            results = runner.run(progress_sink=None)
+            results = results if len(configs) > 1 else [results]
     except ProcessingCancelled:
         LOG.info("Processing cancelled by user.")
         return 0

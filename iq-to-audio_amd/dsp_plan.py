@@ -918,6 +918,44 @@ def plan_find(sample_rate: float, n_samples: int, *, nfft: int | None = None, th
                     threshold_db=float(threshold_db), peak_threshold_db=float(peak_threshold_db))
 
 
+# ---- channel description plan (--find-describe) ----------------------------
+
+DESCRIBE_MIN_BW = 6000.0  # Hz: the narrowest channel filter
+DESCRIBE_MIN_RATE = 12000.0  # Hz: the lowest channel rate asked for
+DESCRIBE_MAX_SHIFT = 30  # IQA_DESCRIBE_MAX_SHIFT
+DESCRIBE_TILE = 2048  # samples to a row of iqa_describe_accumulate
+
+
+@dataclass(frozen=True)
+class DescribePlan:
+    fs: float
+    offset_hz: float
+    width_hz: float
+    bw: float  # the channel filter's bandwidth
+    decimation: int
+    fs_ch: float
+    taps: np.ndarray  # float64, read-only
+    delay: int  # (L - 1) // 2 raw frames
+
+
+def plan_describe(sample_rate: float, offset_hz: float, width_hz: float) -> DescribePlan:
+    """The channelizer of one found channel: twice its occupied width (6 kHz at least, a quarter of the capture's rate at
+    most), at twice that rate (12 kHz at least)."""
+    fs, offset, width = float(sample_rate), float(offset_hz), float(width_hz)
+    if not math.isfinite(fs) or fs <= 0.0:
+        raise ValueError("the sample rate must be positive")
+    if not math.isfinite(width) or width <= 0.0:
+        raise ValueError("the channel's width must be positive")
+    if not math.isfinite(offset) or abs(offset) > fs / 2.0:
+        raise ValueError("the channel's offset must lie inside the capture")
+    bw = min(max(2.0 * width, DESCRIBE_MIN_BW), fs / 4.0)
+    decimation, fs_ch = choose_decimation(fs, max(2.0 * bw, DESCRIBE_MIN_RATE))
+    taps = design_channel_filter(fs, bw, decimation)
+    taps.setflags(write=False)
+    return DescribePlan(fs=fs, offset_hz=offset, width_hz=width, bw=bw, decimation=decimation, fs_ch=fs_ch, taps=taps,
+                        delay=(len(taps) - 1) // 2)
+
+
 # ---- 48 kHz resampler plan (build-defined spec; see DESIGN.md "48 kHz stage") -----------------
 
 RS_ZERO_CROSSINGS = 16

@@ -256,9 +256,11 @@ class ChannelFinder:
 
 def find_channels(path, *, center_freq: float | None = None, input_format: str | None = None, input_container: str | None = None,
                   input_sample_rate: float | None = None, iq_order: str = "iq", max_seconds: float | None = None,
-                  **plan_options) -> FindResult:
+                  describe: bool = False, **plan_options):
     """The occupied channels of the capture at ``path`` (``plan_options``: the keywords of ``dsp_plan.plan_find``).  The centre
-    frequency is taken from the file name where it is not given; without one the channels carry offsets only."""
+    frequency is taken from the file name where it is not given; without one the channels carry offsets only.  ``describe``:
+    a second pass over the mapped file measures every channel (``describe.ChannelDescriber``) and the
+    call returns ``(FindResult, DescribeResult)``."""
     path = Path(path)
     info = iqio.probe_capture(path, input_format=input_format, input_container=input_container, input_sample_rate=input_sample_rate)
     if not info.sample_rate:
@@ -275,4 +277,12 @@ def find_channels(path, *, center_freq: float | None = None, input_format: str |
     values = iqio.map_frames(info)
     for a in range(0, n, BLOCK_FRAMES):
         finder.process(np.ascontiguousarray(values[2 * a : 2 * min(n, a + BLOCK_FRAMES)]))
-    return finder.result(center_freq)
+    result = finder.result(center_freq)
+    if not describe:
+        return result
+    from .describe import ChannelDescriber
+
+    describer = ChannelDescriber(plan, finder.finish(), result.channels, info.fmt, iq_order)
+    for a in range(0, n, BLOCK_FRAMES):
+        describer.process(np.ascontiguousarray(values[2 * a : 2 * min(n, a + BLOCK_FRAMES)]))
+    return result, describer.result(center_freq)
