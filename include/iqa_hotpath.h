@@ -810,6 +810,33 @@ int iqa_describe_accumulate(const void *z_dev, int64_t n, int64_t pos, const voi
                             int32_t hop, int32_t T, int64_t F, int32_t S, const void *gate_dev, void *partials_dev, void *stream);
 
 /* ------------------------------------------------------------------------- *
+ * Whether a found channel is keyed (--find-decode)     *
+ * ------------------------------------------------------------------------- */
+
+#define IQA_KEYING_BAUDS 7     /* candidate symbol rates: 512, 1200, 1600, 2400, 3200, 4800, 9600 */
+#define IQA_KEYING_SUMS 16     /* int32 values of a row: P, K, then (C_k, Q_k) per candidate */
+/* Rows of iqa_keying_accumulate for the samples pos .. pos + n - 1: (pos + n - 1) / 2048 - pos / 2048 + 1, one per window
+ * w = m / 2048 of the absolute position that the call touches; 0 for n <= 0. */
+int64_t iqa_keying_windows(int64_t pos, int64_t n);
+/* The coherence of a discriminator's level crossings with a symbol clock, as exact integer sums.  theta_dev: float32[n]
+ * (iqa_quadrature's output of the channel stream, decimation D, filter delay `delay` raw frames), theta_dev[0] being sample
+ * pos.  t = clamp(rintf(theta 4096), -32767, 32767) (float32, half-even; NaN reads as 0, +-inf as +-32767); s = (t >= c), c
+ * the centre, |c| <= 32767.  gate(m) is iqa_describe_accumulate's: gate_dev[s] != 0 (uint8[S]) with s = min(max(m D - delay,
+ * 0) / hop, F - 1) / T in int64; hop, T, F and S = ceil(F / T) are the find plan's.  Sample m >= 1 is a pair iff gate(m) and
+ * gate(m - 1), and a crossing iff it is a pair and s[m] != s[m - 1].  front_dev: float32[1], the theta in front of
+ * theta_dev[0], or NULL (sample 0 of the call then forms no pair; required at pos 0).  inc: IQA_KEYING_BAUDS clock steps on
+ * the host, inc_k = rint(B_k 2^32 / fs_ch), 0 <= inc_k < 2^30 (0: a skipped candidate).  A crossing at m adds
+ * cs[((uint64(m) inc_k) mod 2^32) >> 22] to candidate k, cs_dev: int16[1024][2] = (rint(1024 cos(2 pi i / 1024)),
+ * rint(1024 sin(2 pi i / 1024))), 4-byte aligned.  Every window the call touches writes one row of rows_dev
+ * (int32[iqa_keying_windows(pos, n)][16]): P (pairs), K (crossings), then (C_k, Q_k) = the sums of cs over the crossings;
+ * |C_k| <= 2048 * 1024.  A window cut by two calls gets a partial row from each: the host adds the rows of one window number
+ * before it squares anything, so nothing depends on how the stream is cut into calls.  (pos + n) D < 2^62.  n = 0 returns
+ * IQA_OK and touches no pointer. */
+int iqa_keying_accumulate(const void *theta_dev, int64_t n, int64_t pos, const void *front_dev, int32_t c, const int32_t *inc,
+                          const void *cs_dev, int32_t D, int32_t delay, int32_t hop, int32_t T, int64_t F, int32_t S,
+                          const void *gate_dev, void *rows_dev, void *stream);
+
+/* ------------------------------------------------------------------------- *
  * Audio post-processing: automatic squelch (the reference's --audio-post)    *
  * ------------------------------------------------------------------------- */
 

@@ -197,6 +197,9 @@ _SIGNATURES = {
     "iqa_describe_tiles": (c_int64, [c_int64]),
     "iqa_describe_accumulate": (ctypes.c_int, [c_void_p, c_int64, c_int64, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int64,
                                                c_int32, c_void_p, c_void_p, c_void_p]),
+    "iqa_keying_windows": (c_int64, [c_int64, c_int64]),
+    "iqa_keying_accumulate": (ctypes.c_int, [c_void_p, c_int64, c_int64, c_void_p, c_int32, ctypes.POINTER(c_int32), c_void_p, c_int32,
+                                             c_int32, c_int32, c_int32, c_int64, c_int32, c_void_p, c_void_p, c_void_p]),
     "iqa_squelch_workspace_bytes": (c_int64, [c_int64, c_int32]),
     "iqa_squelch_stage_offset": (c_int64, [c_int64, c_int32, c_int32]),
     "iqa_squelch": (ctypes.c_int, [ctypes.POINTER(SquelchParams), ctypes.POINTER(SquelchSeg), c_int32, c_void_p, c_void_p,

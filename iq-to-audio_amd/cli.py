@@ -13,6 +13,7 @@ exist here (reference ``cli.py:151-412, 424-578, 661-741``); the GUI, ``digital`
     python -m iq_to_audio_amd.cli --audio-post recordings/ --audio-post-mode adaptive
     python -m iq_to_audio_amd.cli --in capture_455500000Hz.wav --find-channels
     python -m iq_to_audio_amd.cli --in capture_455500000Hz.wav --find-top 3 --find-grid 12500 --demod nfm
+    python -m iq_to_audio_amd.cli --in capture_455500000Hz.wav --find-top 5 --find-auto --find-decode
 """
 from __future__ import annotations
 
@@ -153,6 +154,10 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--find-describe", dest="find_describe", action="store_true",
                    help="Find the channels, then measure each one in a second pass: a label (nfm, am, ssb, wfm, carrier, unknown) "
                         "and a suggested --demod, --bw and frequency.  Implies --find-channels.")
+    p.add_argument("--find-decode", dest="find_decode", action="store_true",
+                   help="Find and describe the channels and measure the keying of each one: whether its discriminator switches on "
+                        "a symbol clock (fsk 512 ... 9600) and which side decoders fit it.  With --find-top N --find-auto every "
+                        "target runs with its chosen decoders.  Implies --find-describe.")
     p.add_argument("--find-auto", dest="find_auto", action="store_true",
                    help="With --find-top N: take the N strongest channels whose label is known and run each with its own "
                         "suggested --demod, --bw and frequency.")
@@ -212,7 +217,8 @@ def check_find_args(parser, args) -> bool:
     """``parser.error`` for every misuse of the ``--find-*`` flags; whether channels are to be found."""
     given = [flag for flag, value in (("--find-channels", args.find_channels or None), ("--find-top", args.find_top),
                                       ("--find-grid", args.find_grid), ("--find-threshold", args.find_threshold),
-                                      ("--find-describe", args.find_describe or None), ("--find-auto", args.find_auto or None))
+                                      ("--find-describe", args.find_describe or None), ("--find-auto", args.find_auto or None),
+                                      ("--find-decode", args.find_decode or None))
              if value is not None]
     if not given:
         return False
@@ -232,7 +238,7 @@ def check_find_args(parser, args) -> bool:
     for e in SIDE_DECODERS:
         if args.find_auto and getattr(args, e.name):
             parser.error(f"--find-auto cannot be combined with --{e.name}.")
-    if not args.find_channels and not args.find_describe and args.find_top is None:
+    if not args.find_channels and not args.find_describe and not args.find_decode and args.find_top is None:
         parser.error("--find-threshold needs --find-channels or --find-top.")
     if args.input_path is None:
         parser.error(f"{given[0]} needs --in.")
@@ -242,19 +248,23 @@ def check_find_args(parser, args) -> bool:
 def run_find(args, codec, container):
     """``--find-channels`` / ``--find-describe`` / ``--find-top``: print and store the capture's channels and, where asked for,
     their descriptions.  Returns (exit code or ``None`` to go on, the targets of the run that follows: frequencies, or with
-    ``--find-auto`` (frequency, demod, bw) each)."""
+    ``--find-auto`` (frequency, demod, bw) each, and with ``--find-decode`` beside it (frequency, demod, bw, side decoders))."""
     from .find import find_channels, select_targets
 
     options = {} if args.find_threshold is None else {"threshold_db": args.find_threshold}
-    describing = args.find_describe or args.find_auto
+    describing = args.find_describe or args.find_auto or args.find_decode
     if describing:
         options["describe"] = True
-    described = None
+    if args.find_decode:
+        options.update(keying=True, fs_ch=getattr(args, "find_fs_ch", None))
+    described = keyed = None
     try:
         result = find_channels(args.input_path, center_freq=args.center_freq, input_format=codec, input_container=container,
                                input_sample_rate=args.input_sample_rate, iq_order=args.iq_order, max_seconds=args.preview_seconds,
                                **options)
-        if describing:
+        if args.find_decode:
+            result, described, keyed = result
+        elif describing:
             result, described = result
     except Exception as exc:  # noqa: BLE001
         LOG.error("Finding channels failed: %s", exc)
@@ -265,12 +275,17 @@ def run_find(args, codec, container):
         for line in result.lines():
             print(line)
     else:
-        for line, about in zip(result.lines(), described.lines()):
+        under = keyed.lines() if keyed is not None else [None] * len(result.channels)
+        for line, about, keying in zip(result.lines(), described.lines(), under):
             print(line)
             print(about)
+            if keying is not None:
+                print(keying)
     args.input_path.with_name(f"{args.input_path.stem}.channels.json").write_text(json.dumps(result.to_json(), indent=1) + "\n")
     if described is not None:
         args.input_path.with_name(f"{args.input_path.stem}.describe.json").write_text(json.dumps(described.to_json(), indent=1) + "\n")
+    if keyed is not None:
+        args.input_path.with_name(f"{args.input_path.stem}.keying.json").write_text(json.dumps(keyed.to_json(), indent=1) + "\n")
     if args.find_top is None:
         return 0, []
     if not result.channels:
@@ -283,7 +298,11 @@ def run_find(args, codec, container):
         return None, select_targets(result, args.find_top, args.find_grid or 1.0)
     from .describe import select_auto_targets
 
-    targets, skipped = select_auto_targets(result, described, args.find_top, args.find_grid or 1.0)
+    if keyed is not None:
+        # every target with its channel's decoders, and the bandwidth they ask for
+        described = dataclasses.replace(described, channels=[dataclasses.replace(d, bw=k.bw) for d, k in zip(described.channels, keyed.channels)])
+    targets, skipped = select_auto_targets(result, described, args.find_top, args.find_grid or 1.0,
+                                           extras=None if keyed is None else [tuple(k.decoders) for k in keyed.channels])
     for ch in skipped:
         LOG.info("--find-auto skips %.0f Hz: its modulation is unknown.", ch.freq_hz)
     if not targets:
@@ -302,6 +321,7 @@ def main(argv: list[str] | None = None) -> int:
     parser = build_parser()
     given = parser.parse_args(argv)  # (the unset --bw / --fs-ch / --deemph still marked: --find-auto resolves them per target)
     args = resolve_mode_defaults(copy.copy(given))
+    args.find_fs_ch = None if isinstance(given.fs_ch, ModeDefault) else float(given.fs_ch)  # an explicit --fs-ch, for --find-decode
     if args.audio_post_path and args.benchmark:
         parser.error("--audio-post cannot be combined with --benchmark.")
     if args.audio_post_path and not 0.0 <= args.audio_post_percentile <= 1.0:
@@ -349,17 +369,20 @@ def main(argv: list[str] | None = None) -> int:
     if args.input_path is None:
         parser.error("--in is required (or use --benchmark).")
     per_target: dict = {}  # --find-auto: a target's own settings
+    decoders: dict = {}  # ... and, with --find-decode, its side decoders' keywords
     if finding:
         code, frequencies = run_find(args, codec, container)
         if code is not None:
             return code
         if args.find_auto:
             # every target with its own suggested mode and bandwidth, the unset --fs-ch / --deemph resolved for that mode
-            for freq, demod, bw in frequencies:
+            for freq, demod, bw, *chosen in frequencies:
                 mine = copy.copy(given)
                 mine.demod, mine.bandwidth = demod, float(bw)
                 per_target[freq] = settings(resolve_mode_defaults(mine))
-                LOG.info("Target from --find-auto: %.0f Hz, --demod %s --bw %.0f", freq, demod, bw)
+                decoders[freq] = {name: True for name in (chosen[0] if chosen else ())}
+                LOG.info("Target from --find-auto: %.0f Hz, --demod %s --bw %.0f%s", freq, demod, bw,
+                         "".join(f" --{name}" for name in decoders[freq]))
             frequencies = [t[0] for t in frequencies]
         else:
             LOG.info("Targets from --find-top: %s", ", ".join(f"{f:.0f} Hz" for f in frequencies))
@@ -385,8 +408,10 @@ def main(argv: list[str] | None = None) -> int:
         extras = {e.name: getattr(args, e.name) for e in SIDE_DECODERS}
         if per_target:
             # --find-auto: a pipeline per target, so that every output is what an explicit run with its --ft, --demod and
-            # --bw writes, bit for bit (the targets differ in mode and rate: a shared pass would group few of them)
-            results = [ProcessingPipeline(c).run(progress_sink=None) for c in configs]
+            # --bw writes, bit for bit (the targets differ in mode and rate: a shared pass would group few of them); with
+            # --find-decode it runs the side decoders chosen for its channel
+            runners = [ProcessingPipeline(c, **decoders.get(c.target_freq, {})) for c in configs]
+            results = [r.run(progress_sink=None) for r in runners]
         else:
             runner = MultiChannelPipeline(configs, **extras) if len(configs) > 1 else ProcessingPipeline(configs[0], **extras)
             results = runner.run(progress_sink=None)
@@ -402,6 +427,15 @@ def main(argv: list[str] | None = None) -> int:
     for config, result in zip(configs, results):
         LOG.info("%.0f Hz: decimation %d -> %.2f Hz, mixer sign %+d, audio peak %.4f", config.target_freq,
                  result.decimation, result.fs_channel, result.mix_sign, result.audio_peak)
+    for e in SIDE_DECODERS:  # --find-auto --find-decode: what an explicit run of the target with its decoders prints and writes
+        for config, one in zip(configs, runners if per_target else []):
+            if not decoders.get(config.target_freq, {}).get(e.name) or args.probe_only:
+                continue
+            res = getattr(one, e.name)
+            for line in e.lines(res, f"{config.target_freq:.0f} Hz: "):
+                print(line)
+            one.output_path.with_name(f"{one.output_path.stem}.{e.name}.json").write_text(
+                json.dumps(None if res is None else res.to_json(), indent=1) + "\n")
     for e in SIDE_DECODERS:
         if not getattr(args, e.name) or args.probe_only:
             continue

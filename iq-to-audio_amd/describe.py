@@ -7,9 +7,15 @@ sums, counting only the samples of the slices in which the finder saw the channe
 depth, carrier offset, RMS deviation, carrier line share, in-channel carrier-to-noise ratio) are formed on the host in
 float64 from those integers and from the finder's planes; the label and the suggestion follow from fixed rules.  Behind the
 quantiser everything is integer: the sums do not depend on how the stream is cut.  No CPU path: without a GPU or the built
-library the calls raise ``RuntimeError``."""
+library the calls raise ``RuntimeError``.
+
+With ``keying=True`` (``--find-decode``) the same pass also measures whether each channel's discriminator
+switches on a symbol clock: ``iqa_quadrature`` and ``iqa_keying_accumulate`` give, per window of 2048 samples, the gated pairs,
+the level crossings and the crossings' clock-phase sums at seven candidate bauds.  Fixed rules turn them into ``fsk <baud>`` or
+``unkeyed`` and into the side decoders a target of that channel runs with."""
 from __future__ import annotations
 
+import logging
 import math
 from ctypes import c_int32, c_int64
 from dataclasses import asdict, dataclass, field
@@ -19,6 +25,8 @@ import numpy as np
 from . import _dev as D
 from . import _native as N
 from . import dsp_plan as P
+
+LOG = logging.getLogger(__name__)
 
 SUMS = ("N", "NP", "S1", "S2", "E", "CR", "CI", "A")
 LABELS = ("nfm", "am", "ssb", "wfm", "carrier", "unknown")
@@ -189,10 +197,11 @@ def describe_channel(find_plan: P.FindPlan, fin: dict, channel, gate, sums, plan
                               tuned_hz=None if tuned is None or center_freq is None else center_freq + tuned, **figures)
 
 
-def select_auto_targets(found, described: DescribeResult, top: int, grid_hz: float = 1.0) -> tuple:
+def select_auto_targets(found, described: DescribeResult, top: int, grid_hz: float = 1.0, extras=None) -> tuple:
     """(targets, skipped) for ``--find-auto``: the ``top`` channels of highest ``snr_db`` (ties to the lower frequency) whose
     label is not unknown, each as (frequency rounded to ``grid_hz``, demod, bw), duplicates of a frequency dropped, ascending;
-    ``skipped`` are the unknown channels that stood in front of the last one taken.  Needs a centre frequency."""
+    ``skipped`` are the unknown channels that stood in front of the last one taken.  Needs a centre frequency.  ``extras``:
+    one value per channel, carried as a fourth entry of its target (the side decoders of ``--find-decode``)."""
     if described.center_freq is None or any(ch.freq_hz is None for ch in found.channels):
         raise ValueError("the targets need a centre frequency")
     grid = float(grid_hz)
@@ -206,8 +215,186 @@ def select_auto_targets(found, described: DescribeResult, top: int, grid_hz: flo
             skipped.append(found.channels[i])
             continue
         freq = math.floor(d.tuned_hz / grid + 0.5) * grid
-        targets.setdefault(freq, (freq, d.demod, d.bw))
+        targets.setdefault(freq, (freq, d.demod, d.bw) if extras is None else (freq, d.demod, d.bw, extras[i]))
     return sorted(targets.values()), skipped
+
+
+# ---- keying: the host arithmetic ---------------------------------------------------------------------
+
+# the rules' constants (design constants, as section 22's are)
+KEYING_MIN_PAIRS = 1024  # gated pairs of the describe rows before the centre is taken
+KEYING_MIN_CROSSINGS = 256
+KEYING_MIN_COH = 0.35
+KEYING_RATE_LOW, KEYING_RATE_HIGH = 0.25, 0.8  # crossings per second against the baud
+AIRBAND_HZ = (117.975e6, 137.0e6)
+AIS_BW = 25000.0
+POCSAG_BAUDS = (512, 1200, 2400)
+FLEX_BAUDS = (1600, 3200)
+NFM_RATE, WFM_RATE = 96_000.0, 480_000.0  # the channel rates a target of that mode asks for where --fs-ch is unset
+
+
+@dataclass
+class ChannelKeying:
+    offset_hz: float  # the finder's
+    freq_hz: float | None
+    described: str  # the label of section 22
+    fs_ch: float  # the rate of the measured stream
+    bauds: list  # the candidates
+    coh: list  # per candidate: the coherence of the crossings with its clock; None where skipped or not measured
+    rate_hz: float | None  # crossings per second of gated stream
+    crossings: int
+    pairs: int
+    centre: int | None  # c, in 1 / 4096 rad per sample; None where the channel never held 1024 gated pairs
+    label: str | None  # "fsk <baud>" or "unkeyed" for an nfm channel, None for every other
+    baud: int | None
+    decoders: list  # the side decoders a target of this channel runs with
+    bw: float | None  # the suggested --bw (section 22's, 25 000 for fsk 9600)
+    note: str  # why there is no decoder, where there is none
+
+    def line(self) -> str:
+        if self.label is None:
+            head = f"not measured ({self.described})"
+        else:
+            known = [(v, b) for v, b in zip(self.coh, self.bauds) if v is not None]
+            if not known or self.rate_hz is None:
+                head = f"{self.label} (not measured, {self.crossings} crossings)"
+            elif self.baud is not None:
+                head = f"{self.label} (coh {self.coh[self.bauds.index(self.baud)]:.2f}, {self.rate_hz:.0f} crossings/s)"
+            else:
+                best, at = max(known)
+                head = f"{self.label} (best coh {best:.2f} at {at}, {self.rate_hz:.0f} crossings/s)"
+        if not self.decoders:
+            return f"    keying: {head} -> {self.note or 'no decoder'}"
+        flags = " ".join(f"--{name}" for name in self.decoders)
+        return f"    keying: {head} -> {flags}" + (f" --bw {self.bw:.0f}" if "ais" in self.decoders else "")
+
+    def to_json(self) -> dict:
+        return asdict(self)
+
+
+@dataclass
+class KeyingResult:
+    channels: list = field(default_factory=list)  # ChannelKeying, in the order of the FindResult's channels
+    sample_rate: float = 0.0
+    center_freq: float | None = None
+
+    def lines(self) -> list:
+        return [ch.line() for ch in self.channels]
+
+    def to_json(self) -> dict:
+        return asdict(self)
+
+    @classmethod
+    def from_json(cls, data: dict) -> "KeyingResult":
+        data = dict(data)
+        data["channels"] = [ChannelKeying(**ch) for ch in data.get("channels", [])]
+        return cls(**data)
+
+
+def keying_centre(cr: int, ci: int) -> int:
+    """c = rint(atan2(CI, CR) 4096): the mean rotation per sample in the quantiser's units (float64, half-even)."""
+    return int(np.rint(math.atan2(int(ci), int(cr)) * P.KEYING_SCALE))
+
+
+def add_keying_rows(parts, windows: int) -> np.ndarray:
+    """int64[windows][16]: the rows of every call (``parts``: (first window, int32[k][16]) each) added by window number."""
+    out = np.zeros((int(windows), P.KEYING_SUMS), dtype=np.int64)
+    for first, rows in parts:
+        rows = np.asarray(rows, dtype=np.int64).reshape(-1, P.KEYING_SUMS)
+        out[first : first + rows.shape[0]] += rows
+    return out
+
+
+def _exact_sum(values: np.ndarray) -> int:
+    """The sum of int64 values below 2^44 as a Python integer: 2^19 at a time in int64, the partial sums added exactly."""
+    step = 1 << 19
+    return sum(int(values[a : a + step].sum(dtype=np.int64)) for a in range(0, values.size, step))
+
+
+def keying_figures(rows, plan: P.KeyingPlan) -> dict:
+    """coh per candidate, rate_hz, crossings and pairs from the window rows (added by window number): exact integer sums
+    (every term below 2^44), then one float64 quotient each."""
+    rows = np.asarray(rows, dtype=np.int64).reshape(-1, P.KEYING_SUMS)
+    pairs, crossings = _exact_sum(rows[:, 0]), _exact_sum(rows[:, 1])
+    den = 1024 * 1024 * _exact_sum(rows[:, 1] * rows[:, 1] - rows[:, 1])
+    coh = []
+    for k, skip in enumerate(plan.skipped):
+        if skip or den == 0:
+            coh.append(None)
+            continue
+        c, q = rows[:, 2 + 2 * k], rows[:, 3 + 2 * k]
+        coh.append((_exact_sum(c * c + q * q) - 1024 * 1024 * crossings) / den)
+    return dict(coh=coh, rate_hz=crossings / pairs * plan.fs_ch if pairs else None, crossings=crossings, pairs=pairs)
+
+
+def keying_label(coh, rate_hz, crossings: int, plan: P.KeyingPlan) -> tuple:
+    """("fsk <baud>", baud) for the lowest candidate whose clock the crossings keep and whose rate fits, else ("unkeyed", None)."""
+    if crossings < KEYING_MIN_CROSSINGS or rate_hz is None:
+        return "unkeyed", None
+    for b, v, skip in zip(plan.bauds, coh, plan.skipped):
+        if not skip and v is not None and v >= KEYING_MIN_COH and KEYING_RATE_LOW * b <= rate_hz <= KEYING_RATE_HIGH * b:
+            return f"fsk {b}", b
+    return "unkeyed", None
+
+
+def decoders_for(described: str, baud, tuned_hz) -> tuple:
+    """(side decoders, note, --bw override or None) of a channel: ``described`` the label of section 22, ``baud`` the keyed rate
+    of an nfm channel or None, ``tuned_hz`` the suggested frequency or None."""
+    if described == "nfm":
+        if baud in POCSAG_BAUDS:
+            return ["pocsag"], "", None
+        if baud == 9600:
+            return ["ais"], "", AIS_BW
+        if baud in FLEX_BAUDS:
+            return [], "FLEX rates: no decoder here", None
+        if baud == 4800:
+            return [], "4800 baud (DMR / P25 / NXDN class): no decoder here", None
+        return ["ax25", "tones"], "", None
+    if described == "wfm":
+        return ["rds"], "", None
+    if described == "am":
+        if tuned_hz is not None and AIRBAND_HZ[0] <= tuned_hz <= AIRBAND_HZ[1]:
+            return ["acars"], "", None
+        return [], "no decoder outside the airband" if tuned_hz is not None else "no decoder without a tuned frequency", None
+    return [], "no decoder", None
+
+
+def target_rate(sample_rate: float, demod: str | None, fs_ch: float | None = None) -> float:
+    """The channel rate a target of ``demod`` runs at: what the pipeline makes of ``--fs-ch`` (unset: the mode's default)."""
+    ask = float(fs_ch) if fs_ch is not None else (WFM_RATE if demod == "wfm" else NFM_RATE)
+    return P.choose_decimation(float(sample_rate), ask)[1]
+
+
+def usable_decoders(names, rate: float, where: str = "") -> list:
+    """``names`` without the decoders whose plan refuses the channel rate ``rate`` (the refusal is logged)."""
+    from .decoders.side import SIDE_DECODERS
+
+    rows = {e.name: e for e in SIDE_DECODERS}
+    kept = []
+    for name in names:
+        try:
+            rows[name].plan(rate)
+        except ValueError as exc:
+            LOG.info("%s--%s dropped: %s", where, name, exc)
+            continue
+        kept.append(name)
+    return kept
+
+
+def key_channel(desc: ChannelDescription, plan: P.KeyingPlan, rows, centre, sample_rate: float,
+                fs_ch: float | None = None) -> ChannelKeying:
+    """One channel's keying from its description, its window rows (None: never measured) and its centre."""
+    figures = dict(coh=[None] * len(plan.bauds), rate_hz=None, crossings=0, pairs=0)
+    if rows is not None and centre is not None:
+        figures = keying_figures(rows, plan)
+    label = baud = None
+    if desc.label == "nfm":
+        label, baud = keying_label(figures["coh"], figures["rate_hz"], figures["crossings"], plan)
+    names, note, bw = decoders_for(desc.label, baud, desc.tuned_hz)
+    where = f"{desc.offset_hz:+.0f} Hz: " if desc.freq_hz is None else f"{desc.freq_hz:.0f} Hz: "
+    names = usable_decoders(names, target_rate(sample_rate, desc.demod, fs_ch), where)
+    return ChannelKeying(offset_hz=desc.offset_hz, freq_hz=desc.freq_hz, described=desc.label, fs_ch=plan.fs_ch, bauds=list(plan.bauds),
+                         centre=centre, label=label, baud=baud, decoders=names, bw=desc.bw if bw is None else bw, note=note, **figures)
 
 
 # ---- the device pass --------------------------------------------------------------------------------------------------------
@@ -232,6 +419,19 @@ def add_rows(rows: np.ndarray) -> tuple:
     return tuple((int(h) << 32) + int(l) for h, l in zip(high, low))
 
 
+def accumulate_keying(theta, pos: int, front, centre: int, kplan: P.KeyingPlan, table_dev, plan: P.DescribePlan, find_plan: P.FindPlan,
+                      gate_dev):
+    """``iqa_keying_accumulate`` for one stretch of a channel's discriminator output (device float32): (first window, the
+    device rows int32[windows][16]).  The entry point checks its arguments before it launches (``ValueError``)."""
+    n = int(theta.numel())
+    rows = D.empty(int(N.lib().iqa_keying_windows(pos, n)) * P.KEYING_SUMS, "int32")
+    incs = (c_int32 * len(kplan.incs))(*kplan.incs)
+    N.call("iqa_keying_accumulate", N.ptr(theta), c_int64(n), c_int64(pos), N.ptr(front), c_int32(centre), incs, N.ptr(table_dev),
+           c_int32(plan.decimation), c_int32(plan.delay), c_int32(find_plan.hop), c_int32(find_plan.slice_frames),
+           c_int64(find_plan.frames), c_int32(find_plan.slices), N.ptr(gate_dev), N.ptr(rows), N.stream_ptr())
+    return pos // P.KEYING_WINDOW, rows
+
+
 class _Lane:
     """One channel of the pass: its plan, gate and carried state."""
 
@@ -243,6 +443,16 @@ class _Lane:
         self.pos = 0
         self.rows: list = []
         self.z: list = []
+        self.calls: list = []  # the samples of every feed
+        # keying (section 23)
+        self.kplan = None
+        self.qprev = None  # iqa_quadrature's state
+        self.front = None  # the theta in front of the next call
+        self.centre = None
+        self.run = [0, 0, 0]  # NP, CR, CI of the describe rows so far, until the centre is taken
+        self.keyed_from = None  # the stream position of the first keyed sample
+        self.krows: list = []  # (first window, device rows) per call
+        self.theta: list = []
 
 
 class ChannelDescriber:
@@ -250,13 +460,14 @@ class ChannelDescriber:
     (the eight sums of every channel), ``result()`` (a ``DescribeResult``), ``stages()`` for the tests, ``reset()``.
     ``fin`` is ``ChannelFinder.finish()`` of the same capture and ``channels`` the ``FoundChannel``s made from it."""
 
-    def __init__(self, find_plan: P.FindPlan, fin: dict, channels, fmt: str = "s16", iq_order: str = "iq", *, keep_stages: bool = False):
+    def __init__(self, find_plan: P.FindPlan, fin: dict, channels, fmt: str = "s16", iq_order: str = "iq", *, keep_stages: bool = False,
+                 keying: bool = False):
         if fmt not in _RAW_DTYPE:
             raise ValueError(f"Unsupported sample format '{fmt}'")
         if iq_order not in N.ORDER:
             raise ValueError(f"Unsupported iq_order '{iq_order}'")
         self.find_plan, self.fin, self.channels = find_plan, fin, list(channels)
-        self.fmt, self.iq_order, self._keep = fmt, iq_order, keep_stages
+        self.fmt, self.iq_order, self._keep, self._keying = fmt, iq_order, keep_stages, bool(keying)
         by_lo = {int(rec[0]): j for j, rec in enumerate(np.asarray(fin["runs"]).reshape(-1, 8))}
         self._run_of = []
         for ch in self.channels:
@@ -265,6 +476,8 @@ class ChannelDescriber:
             self._run_of.append(by_lo[ch.lo_bin])
         self.plans = [P.plan_describe(find_plan.fs, ch.offset_hz, ch.width_hz) for ch in self.channels]
         self.gates = [erode_gate(np.asarray(fin["on"])[j]) for j in self._run_of]
+        self.kplans = [P.plan_keying(plan.fs_ch) for plan in self.plans] if self._keying else []
+        self._table = None
         self.reset()
 
     def reset(self) -> None:
@@ -273,6 +486,7 @@ class ChannelDescriber:
         self._groups: list = []
         self.samples_seen = 0
         self._fin = None
+        self._kfin = None
 
     def _start(self) -> None:
         from .channelizer import ChannelBank, Channelizer
@@ -282,6 +496,12 @@ class ChannelDescriber:
             chan = Channelizer(plan.taps, sample_rate=plan.fs, freq_offset=plan.offset_hz, mix_sign=MIX_SIGN, decimation=plan.decimation,
                                fmt=self.fmt, iq_order=self.iq_order, precision="fast")
             self._lanes.append(_Lane(ch, plan, gate, chan))
+        if self._keying:
+            if self._table is None:
+                self._table = D.from_numpy(np.ascontiguousarray(self.kplans[0].table))
+            for lane, kplan in zip(self._lanes, self.kplans):
+                lane.kplan = kplan
+                lane.qprev = D.from_numpy(np.array([1.0, 0.0], dtype=np.float32))
         by_d: dict = {}
         for lane in self._lanes:
             by_d.setdefault(lane.plan.decimation, []).append(lane)
@@ -299,7 +519,7 @@ class ChannelDescriber:
             raise ValueError(f"the plan was made for {self.find_plan.n_samples} samples and the stream is longer")
         if self._lanes is None:
             self._start()
-        self._fin = None
+        self._fin = self._kfin = None
         for bank, lanes in self._groups:
             zs = bank.process(x) if bank is not None else [lanes[0].chan.process(x)]
             for lane, z in zip(lanes, zs):
@@ -315,10 +535,32 @@ class ChannelDescriber:
             N.call("iqa_mean_power", N.ptr(z), c_int64(n), c_int64(0), N.ptr(power), N.stream_ptr())
             lane.sh = choose_shift(float(power.cpu().numpy()[0]))
         lane.rows.append(accumulate(z, lane.pos, lane.prev, lane.sh, lane.plan, self.find_plan, lane.gate_dev))
+        if self._keying:
+            self._feed_keying(lane, z, n)
         lane.prev = z[n - 1 :].clone()
         lane.pos += n
         if self._keep:
             lane.z.append(z)
+            lane.calls.append(n)
+
+    def _feed_keying(self, lane: "_Lane", z, n: int) -> None:
+        """The discriminator of the stretch (its own state, carried) and, from the block whose describe rows bring the lane's
+        gated pairs to 1024 on, its keying rows."""
+        theta = D.empty(n, "float32")
+        N.call("iqa_quadrature", N.ptr(z), c_int64(n), N.ptr(lane.qprev), N.ptr(theta), N.stream_ptr())
+        if lane.centre is None and self._gated(lane, lane.pos, n):  # (a stretch without a gated sample adds no pair: no read-back)
+            new = add_rows(lane.rows[-1].cpu().numpy())
+            lane.run = [lane.run[0] + new[1], lane.run[1] + new[5], lane.run[2] + new[6]]
+            if lane.run[0] >= KEYING_MIN_PAIRS:
+                lane.centre = keying_centre(lane.run[1], lane.run[2])
+        if lane.centre is not None:
+            if lane.keyed_from is None:
+                lane.keyed_from = lane.pos
+            lane.krows.append(accumulate_keying(theta, lane.pos, lane.front if lane.pos >= 1 else None, lane.centre, lane.kplan,
+                                                self._table, lane.plan, self.find_plan, lane.gate_dev))
+        lane.front = theta[n - 1 :].clone()
+        if self._keep:
+            lane.theta.append(theta)
 
     def lanes(self) -> list:
         """The lanes of the pass in channel order (made by the first block; for the tests)."""
@@ -335,6 +577,42 @@ class ChannelDescriber:
             self._fin = [add_rows(torch.cat(lane.rows).cpu().numpy()) if lane.rows else (0,) * len(SUMS) for lane in self.lanes()]
         return self._fin
 
+    def _gated(self, lane: "_Lane", pos: int, n: int) -> bool:
+        """Whether any slice that the samples pos .. pos + n - 1 of the lane's stream lie in is on."""
+        p = self.find_plan
+        first, last = (min(max(m * lane.plan.decimation - lane.plan.delay, 0) // p.hop, p.frames - 1) // p.slice_frames
+                       for m in (pos, pos + n - 1))
+        return bool(lane.gate[first : last + 1].any())
+
+    def finish_keying(self) -> list:
+        """Per channel the keying rows added by window number (int64[windows][16]), or None where the channel never held 1024
+        gated pairs; in channel order."""
+        if not self._keying:
+            raise ValueError("the describer was made without keying=True")
+        self.finish()
+        if self._kfin is None:
+            torch = D.torch_mod()
+            self._kfin = []
+            for lane in self.lanes():
+                if lane.centre is None:
+                    self._kfin.append(None)
+                    continue
+                flat = torch.cat([rows for _, rows in lane.krows]).cpu().numpy().reshape(-1, P.KEYING_SUMS)  # one read-back per channel
+                ends = np.cumsum([int(rows.numel()) // P.KEYING_SUMS for _, rows in lane.krows])
+                parts = [(first, flat[end - int(rows.numel()) // P.KEYING_SUMS : end]) for (first, rows), end in zip(lane.krows, ends)]
+                self._kfin.append(add_keying_rows(parts, -(-lane.pos // P.KEYING_WINDOW)))
+        return self._kfin
+
+    def keying(self, center_freq: float | None = None, fs_ch: float | None = None) -> list:
+        """The ``ChannelKeying`` of every channel, in channel order.  ``fs_ch``: an explicit ``--fs-ch`` of the targets."""
+        rows = self.finish_keying()
+        described = self.result(center_freq)
+        return [key_channel(d, lane.kplan, r, lane.centre, self.find_plan.fs, fs_ch)
+                for d, lane, r in zip(described.channels, self.lanes(), rows)]
+
+    def keying_result(self, center_freq: float | None = None, fs_ch: float | None = None) -> KeyingResult:
+        return KeyingResult(channels=self.keying(center_freq, fs_ch), sample_rate=self.find_plan.fs, center_freq=center_freq)
+
     def result(self, center_freq: float | None = None) -> DescribeResult:
         sums = self.finish()
         out = [describe_channel(self.find_plan, self.fin, ch, gate, s, plan, center_freq)
@@ -343,12 +621,23 @@ class ChannelDescriber:
 
     def stages(self) -> list:
         """One dict per channel: sums, sh, gate, plan and, with ``keep_stages``, ``z`` (complex64, the whole channel stream) and
-        ``rows`` (int64[tiles of every call][8])."""
+        ``rows`` (int64[tiles of every call][8]).  With ``keying``: ``c`` (the centre or None), ``keyed_from`` (the position of the
+        first keyed sample), ``keying_rows`` (int64[windows][16], added by window number, or None) and, with ``keep_stages``,
+        ``theta`` (float32, the whole discriminator output), ``keying_parts`` ((first window, int32[k][16]) per call) and
+        ``calls`` (the samples of every feed)."""
         sums = self.finish()
         torch = D.torch_mod()
         out = []
-        for lane, s in zip(self.lanes(), sums):
+        krows = self.finish_keying() if self._keying else None
+        for j, (lane, s) in enumerate(zip(self.lanes(), sums)):
             d = dict(sums=s, sh=lane.sh, gate=lane.gate, plan=lane.plan)
+            if self._keying:
+                d.update(c=lane.centre, keyed_from=lane.keyed_from, keying_rows=krows[j], keying_plan=lane.kplan)
+                if self._keep:
+                    d["theta"] = torch.cat(lane.theta).cpu().numpy() if lane.theta else np.zeros(0, dtype=np.float32)
+                    d["keying_parts"] = [(first, rows.cpu().numpy().reshape(-1, P.KEYING_SUMS)) for first, rows in lane.krows]
+            if self._keep:
+                d["calls"] = list(lane.calls)
             if self._keep:
                 d["z"] = torch.cat(lane.z).cpu().numpy() if lane.z else np.zeros(0, dtype=np.complex64)
                 d["rows"] = torch.cat(lane.rows).cpu().numpy().reshape(-1, len(SUMS)) if lane.rows else np.zeros((0, 8), dtype=np.int64)

@@ -956,6 +956,44 @@ def plan_describe(sample_rate: float, offset_hz: float, width_hz: float) -> Desc
                         delay=(len(taps) - 1) // 2)
 
 
+# ---- keying plan (--find-decode) -------------------------------------------
+
+KEYING_BAUDS = (512, 1200, 1600, 2400, 3200, 4800, 9600)
+KEYING_WINDOW = 2048  # samples to a row of iqa_keying_accumulate, counted on the absolute position
+KEYING_SUMS = 16  # int32 values of a row: P, K, then (C_k, Q_k) per candidate
+KEYING_TABLE = 1024  # entries of the cos / sin table
+KEYING_SCALE = 4096.0  # the quantiser's: t = rint(theta 4096)
+KEYING_T_MAX = 32767
+
+
+@dataclass(frozen=True)
+class KeyingPlan:
+    fs_ch: float
+    bauds: tuple  # KEYING_BAUDS
+    incs: tuple  # rint(B 2^32 / fs_ch) per candidate; 0 for a skipped one
+    skipped: tuple  # bool per candidate: B >= fs_ch / 4
+    table: np.ndarray  # int16[1024][2]: rint(1024 cos), rint(1024 sin); read-only
+
+
+def keying_table() -> np.ndarray:
+    """int16[1024][2]: (rint(1024 cos(2 pi i / 1024)), rint(1024 sin(2 pi i / 1024))), float64 on the host."""
+    turn = 2.0 * np.pi * np.arange(KEYING_TABLE, dtype=np.float64) / KEYING_TABLE
+    table = np.stack((np.rint(1024.0 * np.cos(turn)), np.rint(1024.0 * np.sin(turn))), axis=1).astype(np.int16)
+    table.setflags(write=False)
+    return table
+
+
+def plan_keying(fs_ch: float) -> KeyingPlan:
+    """The clock steps of the candidate bauds at the channel rate ``fs_ch``: inc = rint(B 2^32 / fs_ch) in float64, and 0 for a
+    candidate of a quarter of the rate or more (skipped: fewer than four samples to a symbol)."""
+    fs_ch = float(fs_ch)
+    if not math.isfinite(fs_ch) or fs_ch <= 0.0:
+        raise ValueError("the channel rate must be positive")
+    skipped = tuple(b >= fs_ch / 4.0 for b in KEYING_BAUDS)
+    incs = tuple(0 if skip else int(np.rint(b * 4294967296.0 / fs_ch)) for b, skip in zip(KEYING_BAUDS, skipped))
+    return KeyingPlan(fs_ch=fs_ch, bauds=KEYING_BAUDS, incs=incs, skipped=skipped, table=keying_table())
+
+
 # ---- 48 kHz resampler plan (build-defined spec; see DESIGN.md "48 kHz stage") -----------------
 
 RS_ZERO_CROSSINGS = 16
