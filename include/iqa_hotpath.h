@@ -837,6 +837,48 @@ int iqa_keying_accumulate(const void *theta_dev, int64_t n, int64_t pos, const v
                           const void *gate_dev, void *rows_dev, void *stream);
 
 /* ------------------------------------------------------------------------- *
+ * Carrier squelch of a run's targets (--squelch)       *
+ * ------------------------------------------------------------------------- */
+
+#define IQA_GATE_CELL 256              /* samples to a cell, counted on the absolute position */
+#define IQA_GATE_MAX_SHIFT 30
+#define IQA_GATE_MAX_FRAME (1 << 20)   /* samples to a frame (Lf), a multiple of IQA_GATE_CELL */
+#define IQA_GATE_MAX_FRAMES (1 << 24)  /* frames of a run */
+#define IQA_GATE_MAX_NUM 1024000       /* num_open = rint(1024 10^(open_db / 10)) at open_db = 30 */
+/* Cells of iqa_gate_power for the samples pos .. pos + n - 1: (pos + n - 1) / 256 - pos / 256 + 1, one per cell c = m / 256
+ * of the absolute position that the call touches; 0 for n <= 0. */
+int64_t iqa_gate_cells(int64_t pos, int64_t n);
+/* The power of a channel stream in integer cells.  z_dev: complex64[n], 8-byte aligned, z_dev[0] being sample pos.
+ * q = clamp(rintf(ldexpf(x, sh)), -32767, 32767) per component (float32, half-even; NaN reads as 0, +-inf as +-32767),
+ * |sh| <= IQA_GATE_MAX_SHIFT; p = qi^2 + qq^2 (< 2^31).  Every cell the call touches writes one entry of cells_dev
+ * (int64[iqa_gate_cells(pos, n)]): the sum of p over the call's samples of the cell.  A cell cut by two calls gets a partial
+ * sum from each; iqa_gate_add_cells adds them by cell number, so nothing depends on how the stream is cut into calls.
+ * pos + n < 2^62.  n = 0 returns IQA_OK and touches no pointer. */
+int iqa_gate_power(const void *z_dev, int64_t n, int64_t pos, int32_t sh, void *cells_dev, void *stream);
+/* cells_dev[i] += part_dev[i], i < k (int64 each): a call's cells added to the run's at the call's first cell number. */
+int iqa_gate_add_cells(const void *part_dev, int64_t k, void *cells_dev, void *stream);
+/* From the cells of a stream of n samples (cells_dev: int64[ceil(n / 256)], added by cell number, each at most 256 (2^31 - 1))
+ * to the state per frame, without a host round trip.  Lf: samples to a frame, a multiple of 256, <= IQA_GATE_MAX_FRAME;
+ * F = max(1, n / Lf) <= IQA_GATE_MAX_FRAMES.  Frame f holds samples [f Lf, (f + 1) Lf), the last one runs to n.
+ *   v_dev     int64[F]  16 E[f] / N[f], E the sum of the frame's cells and N its samples
+ *   floor_dev int64[1]  max(1, the value of rank (F - 1) / 10 (0-based, ascending) among v)
+ *   s_dev     uint8[F]  1 where 1024 v >= num_open floor, 0 where 1024 v < num_close floor, else s[f - 1] (s[-1] = 0)
+ *   s2_dev    uint8[F]  s, without the runs of ones shorter than M frames
+ *   g_dev     uint8[F]  1 iff some s2[f'] = 1 with max(0, f - H) <= f' <= min(F - 1, f + A)
+ *   lo_dev, hi_dev int32[F]  (f0, f1 + 1) of the maximal run of ones [f0, f1] of g that holds f, or (-1, -1)
+ * work_dev: int32[2 F].  1 <= num_close <= num_open <= IQA_GATE_MAX_NUM, M >= 1, H >= 0, A >= 0.  Three launches.  n = 0
+ * returns IQA_OK and touches no pointer. */
+int iqa_gate_decide(const void *cells_dev, int64_t n, int32_t Lf, int32_t F, int64_t num_open, int64_t num_close, int32_t M,
+                    int32_t H, int32_t A, void *v_dev, void *floor_dev, void *s_dev, void *s2_dev, void *g_dev, void *lo_dev,
+                    void *hi_dev, void *work_dev, void *stream);
+/* The gated audio: for sample m, f = min(m / Lf, F - 1); out[m] = 0.0f where g[f] = 0, else audio[m] (k < R ? ramp[k] : 1.0f)
+ * with k = min(m - lo[f] Lf, b - 1 - m) and b = hi[f] Lf, or n where hi[f] = F: one float32 multiply, the ramps inside the
+ * transmission.  audio_dev, out_dev: float32[n], two buffers; ramp_dev: float32[R] (may be NULL at R = 0); g_dev, lo_dev,
+ * hi_dev as iqa_gate_decide leaves them.  n = 0 returns IQA_OK and touches no pointer. */
+int iqa_gate_apply(const void *audio_dev, int64_t n, int32_t Lf, int32_t F, const void *g_dev, const void *lo_dev,
+                   const void *hi_dev, const void *ramp_dev, int32_t R, void *out_dev, void *stream);
+
+/* ------------------------------------------------------------------------- *
  * Audio post-processing: automatic squelch (the reference's --audio-post)    *
  * ------------------------------------------------------------------------- */
 

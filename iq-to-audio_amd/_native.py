@@ -200,6 +200,13 @@ _SIGNATURES = {
     "iqa_keying_windows": (c_int64, [c_int64, c_int64]),
     "iqa_keying_accumulate": (ctypes.c_int, [c_void_p, c_int64, c_int64, c_void_p, c_int32, ctypes.POINTER(c_int32), c_void_p, c_int32,
                                              c_int32, c_int32, c_int32, c_int64, c_int32, c_void_p, c_void_p, c_void_p]),
+    "iqa_gate_cells": (c_int64, [c_int64, c_int64]),
+    "iqa_gate_power": (ctypes.c_int, [c_void_p, c_int64, c_int64, c_int32, c_void_p, c_void_p]),
+    "iqa_gate_add_cells": (ctypes.c_int, [c_void_p, c_int64, c_void_p, c_void_p]),
+    "iqa_gate_decide": (ctypes.c_int, [c_void_p, c_int64, c_int32, c_int32, c_int64, c_int64, c_int32, c_int32, c_int32, c_void_p,
+                                       c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "iqa_gate_apply": (ctypes.c_int, [c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_void_p,
+                                      c_void_p]),
     "iqa_squelch_workspace_bytes": (c_int64, [c_int64, c_int32]),
     "iqa_squelch_stage_offset": (c_int64, [c_int64, c_int32, c_int32]),
     "iqa_squelch": (ctypes.c_int, [ctypes.POINTER(SquelchParams), ctypes.POINTER(SquelchSeg), c_int32, c_void_p, c_void_p,

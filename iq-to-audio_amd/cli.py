@@ -14,6 +14,7 @@ exist here (reference ``cli.py:151-412, 424-578, 661-741``); the GUI, ``digital`
     python -m iq_to_audio_amd.cli --in capture_455500000Hz.wav --find-channels
     python -m iq_to_audio_amd.cli --in capture_455500000Hz.wav --find-top 3 --find-grid 12500 --demod nfm
     python -m iq_to_audio_amd.cli --in capture_455500000Hz.wav --find-top 5 --find-auto --find-decode
+    python -m iq_to_audio_amd.cli --in capture.wav --ft 400025000 --demod nfm --squelch --squelch-split
 """
 from __future__ import annotations
 
@@ -27,7 +28,9 @@ import sys
 from pathlib import Path
 
 from .benchmark import run_benchmark
+from . import dsp_plan as P
 from .decoders.side import SIDE_DECODERS
+from .gate import CarrierSquelch
 from .processing import MultiChannelPipeline, ProcessingCancelled, ProcessingConfig, ProcessingPipeline
 from .squelch import AudioPostOptions, SquelchConfig, gather_audio_targets, process_audio_batch
 
@@ -161,6 +164,16 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--find-auto", dest="find_auto", action="store_true",
                    help="With --find-top N: take the N strongest channels whose label is known and run each with its own "
                         "suggested --demod, --bw and frequency.")
+    p.add_argument("--squelch", dest="squelch", action="store_true",
+                   help="Mute every target's audio while its channel holds no carrier: the channel's power against the run's noise "
+                        "floor, with hysteresis, hang and lead.  The WAV keeps its length; the transmissions are printed and "
+                        "written to <output stem>.squelch.json.")
+    p.add_argument("--squelch-db", dest="squelch_db", type=float, metavar="DB",
+                   help="dB over the noise floor at which the squelch opens (default 6; it closes 2 dB below).")
+    p.add_argument("--squelch-hang", dest="squelch_hang", type=float, metavar="MS",
+                   help="Milliseconds the squelch stays open behind a transmission (default 300).")
+    p.add_argument("--squelch-split", dest="squelch_split", action="store_true",
+                   help="With --squelch: also write one WAV per transmission, <output stem>.tx0001.wav, ...")
     p.add_argument("--verbose", dest="verbose", action="store_true")
     p.set_defaults(audio_post_trim=True)
     return p
@@ -245,6 +258,32 @@ def check_find_args(parser, args) -> bool:
     return True
 
 
+def check_squelch_args(parser, args, finding: bool) -> CarrierSquelch | None:
+    """``parser.error`` for every misuse of the ``--squelch*`` flags; the options of the run's squelch, or None."""
+    extra = [flag for flag, value in (("--squelch-db", args.squelch_db), ("--squelch-hang", args.squelch_hang),
+                                      ("--squelch-split", args.squelch_split or None)) if value is not None]
+    if not args.squelch:
+        if extra:
+            parser.error(f"{extra[0]} needs --squelch.")
+        return None
+    if args.demod in ("wfm", "none"):
+        parser.error(f"--squelch cannot be combined with --demod {args.demod}.")
+    for flag, value in (("--benchmark", args.benchmark), ("--audio-post", args.audio_post_path), ("--probe-only", args.probe_only)):
+        if value:
+            parser.error(f"--squelch cannot be combined with {flag}.")
+    if finding and args.find_top is None:
+        parser.error("--squelch needs --find-top beside the other --find-* flags: it gates the targets of a run.")
+    hyst = P.GATE_DEFAULTS["hyst_db"]
+    if args.squelch_db is not None and not hyst < args.squelch_db <= P.GATE_MAX_OPEN_DB:
+        parser.error(f"--squelch-db must be greater than {hyst:g} and at most {P.GATE_MAX_OPEN_DB:g}.")
+    if args.squelch_hang is not None and not 0.0 <= args.squelch_hang <= P.GATE_MAX_MS:
+        parser.error(f"--squelch-hang must lie in 0 .. {P.GATE_MAX_MS:g} ms.")
+    options = {} if args.squelch_db is None else {"open_db": args.squelch_db}
+    if args.squelch_hang is not None:
+        options["hang_ms"] = args.squelch_hang
+    return CarrierSquelch(split=args.squelch_split, **options)
+
+
 def run_find(args, codec, container):
     """``--find-channels`` / ``--find-describe`` / ``--find-top``: print and store the capture's channels and, where asked for,
     their descriptions.  Returns (exit code or ``None`` to go on, the targets of the run that follows: frequencies, or with
@@ -327,6 +366,7 @@ def main(argv: list[str] | None = None) -> int:
     if args.audio_post_path and not 0.0 <= args.audio_post_percentile <= 1.0:
         parser.error("--audio-post-noise-percentile must be between 0.0 and 1.0.")
     finding = check_find_args(parser, args)
+    squelch = check_squelch_args(parser, args, finding)
     logging.basicConfig(level=logging.DEBUG if args.verbose else logging.INFO, format="%(levelname)s %(message)s")
     for e in SIDE_DECODERS:
         if getattr(args, e.name) and args.demod != e.mode:
@@ -410,10 +450,13 @@ def main(argv: list[str] | None = None) -> int:
             # --find-auto: a pipeline per target, so that every output is what an explicit run with its --ft, --demod and
             # --bw writes, bit for bit (the targets differ in mode and rate: a shared pass would group few of them); with
             # --find-decode it runs the side decoders chosen for its channel
-            runners = [ProcessingPipeline(c, **decoders.get(c.target_freq, {})) for c in configs]
+            # (a wfm target has no channel-rate mono audio to gate: it runs without the squelch)
+            runners = [ProcessingPipeline(c, **decoders.get(c.target_freq, {}), squelch=None if c.demod_mode == "wfm" else squelch)
+                       for c in configs]
             results = [r.run(progress_sink=None) for r in runners]
         else:
-            runner = MultiChannelPipeline(configs, **extras) if len(configs) > 1 else ProcessingPipeline(configs[0], **extras)
+            runner = (MultiChannelPipeline(configs, **extras, squelch=squelch) if len(configs) > 1
+                      else ProcessingPipeline(configs[0], **extras, squelch=squelch))
             results = runner.run(progress_sink=None)
             results = results if len(configs) > 1 else [results]
     except ProcessingCancelled:
@@ -427,6 +470,15 @@ def main(argv: list[str] | None = None) -> int:
     for config, result in zip(configs, results):
         LOG.info("%.0f Hz: decimation %d -> %.2f Hz, mixer sign %+d, audio peak %.4f", config.target_freq,
                  result.decimation, result.fs_channel, result.mix_sign, result.audio_peak)
+    if squelch is not None:  # the transmissions of every gated target, beside its WAV
+        ran = runners if per_target else (runner.owners if len(configs) > 1 else [runner])
+        for config, one in zip(configs, ran):
+            res = one.squelch_result
+            if res is None:
+                continue
+            for line in res.lines(f"{config.target_freq:.0f} Hz: "):
+                print(line)
+            one.output_path.with_name(f"{one.output_path.stem}.squelch.json").write_text(json.dumps(res.to_json(), indent=1) + "\n")
     for e in SIDE_DECODERS:  # --find-auto --find-decode: what an explicit run of the target with its decoders prints and writes
         for config, one in zip(configs, runners if per_target else []):
             if not decoders.get(config.target_freq, {}).get(e.name) or args.probe_only:

@@ -994,6 +994,65 @@ def plan_keying(fs_ch: float) -> KeyingPlan:
     return KeyingPlan(fs_ch=fs_ch, bauds=KEYING_BAUDS, incs=incs, skipped=skipped, table=keying_table())
 
 
+# ---- carrier squelch plan (--squelch) --------------------------------------
+
+GATE_CELL = 256  # IQA_GATE_CELL: samples to a cell, counted on the absolute position
+GATE_MAX_FRAME = 1 << 20  # IQA_GATE_MAX_FRAME
+GATE_MAX_FRAMES = 1 << 24  # IQA_GATE_MAX_FRAMES
+GATE_MAX_SHIFT = 30  # IQA_GATE_MAX_SHIFT
+GATE_MAX_OPEN_DB = 30.0
+GATE_MAX_MS = 10_000.0
+GATE_RANK = (1, 10)  # the floor is the run's tenth percentile: rank (F - 1) // 10
+GATE_DEFAULTS = dict(frame_ms=10.0, open_db=6.0, hyst_db=2.0, hang_ms=300.0, min_ms=40.0, lead_ms=20.0, ramp_ms=5.0)
+
+
+@dataclass(frozen=True)
+class GatePlan:
+    fs: float
+    frame: int  # Lf: samples to a frame, a multiple of GATE_CELL
+    hang: int  # H frames
+    min_frames: int  # M
+    lead: int  # A frames
+    ramp_len: int  # R samples
+    num_open: int  # rint(1024 10^(open_db / 10))
+    num_close: int  # rint(1024 10^((open_db - hyst_db) / 10))
+    ramp: np.ndarray  # float32[R]: (k + 1) / (R + 1); read-only
+
+    def frames(self, n: int) -> int:
+        """F = max(1, n // Lf) of a stream of ``n`` samples."""
+        return max(1, int(n) // self.frame)
+
+
+def plan_gate(fs: float, opts=None) -> GatePlan:
+    """The carrier squelch at the channel rate ``fs`` (float64 on the host).  ``opts``: anything with the attributes of
+    ``GATE_DEFAULTS`` (``gate.CarrierSquelch``); None takes the defaults."""
+    fs = float(fs)
+    if not math.isfinite(fs) or fs <= 0.0:
+        raise ValueError("the channel rate must be positive")
+    o = {k: float(getattr(opts, k, v)) if opts is not None else v for k, v in GATE_DEFAULTS.items()}
+    for k, v in o.items():
+        if not math.isfinite(v):
+            raise ValueError(f"{k} must be finite")
+    for k in ("frame_ms", "hang_ms", "min_ms", "lead_ms", "ramp_ms"):
+        if not 0.0 <= o[k] <= GATE_MAX_MS:
+            raise ValueError(f"{k} must lie in 0 .. {GATE_MAX_MS:.0f} ms")
+    if not (0.0 <= o["hyst_db"] < o["open_db"] <= GATE_MAX_OPEN_DB):
+        raise ValueError(f"open_db and hyst_db must satisfy 0 <= hyst_db < open_db <= {GATE_MAX_OPEN_DB:.0f}")
+    frame = GATE_CELL * max(1, int(fs * o["frame_ms"] / 1000.0 / GATE_CELL))
+    if frame > GATE_MAX_FRAME:
+        raise ValueError(f"a frame of {frame} samples exceeds {GATE_MAX_FRAME}")
+
+    def fr(ms: float) -> int:
+        return int(math.ceil(ms / 1000.0 * fs / frame))
+
+    ramp_len = int(np.rint(o["ramp_ms"] / 1000.0 * fs))
+    ramp = ((np.arange(ramp_len, dtype=np.float64) + 1.0) / (ramp_len + 1.0)).astype(np.float32)
+    ramp.setflags(write=False)
+    return GatePlan(fs=fs, frame=frame, hang=fr(o["hang_ms"]), min_frames=max(1, fr(o["min_ms"])), lead=fr(o["lead_ms"]),
+                    ramp_len=ramp_len, num_open=int(np.rint(1024.0 * 10.0 ** (o["open_db"] / 10.0))),
+                    num_close=int(np.rint(1024.0 * 10.0 ** ((o["open_db"] - o["hyst_db"]) / 10.0))), ramp=ramp)
+
+
 # ---- 48 kHz resampler plan (build-defined spec; see DESIGN.md "48 kHz stage") -----------------
 
 RS_ZERO_CROSSINGS = 16

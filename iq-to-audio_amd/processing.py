@@ -38,6 +38,7 @@ from .decoders.rds import RdsCore
 from .decoders.side import SIDE_DECODERS, check_modes
 from .decoders.wfm import WfmStereoCore, stereo_matrix
 from .dsp_plan import design_channel_filter, tune_chunk_size  # noqa: F401  (re-exported API)
+from .gate import CarrierGate, CarrierSquelch
 from .progress import PhaseState, ProgressSink, ProgressTracker
 
 LOG = logging.getLogger(__name__)
@@ -937,6 +938,20 @@ class _BlockStager:
         return dev
 
 
+def check_squelch(squelch, demod_mode):
+    """``squelch`` (a ``CarrierSquelch`` or None) for a target of ``demod_mode``: ``ValueError`` for a mode that has no
+    channel-rate mono audio to gate, or for options the plan refuses."""
+    if squelch is None:
+        return None
+    if not isinstance(squelch, CarrierSquelch):
+        raise ValueError("squelch must be a CarrierSquelch or None")
+    mode = (demod_mode or "").lower()
+    if mode == "wfm" or mode in {"none", "pass", "iq"}:
+        raise ValueError(f"squelch cannot gate a '{mode}' target")
+    P.plan_gate(96_000.0, squelch)  # (the options' own ranges, at the default channel rate)
+    return squelch
+
+
 class ProcessingPipeline:
     """``ProcessingPipeline(config).run(progress_sink) -> ProcessingResult``, ``.cancel()``
     (reference processing.py:682-1213).
@@ -952,10 +967,15 @@ class ProcessingPipeline:
     block_frames_target = 64 * 1024 * 1024
 
     def __init__(self, config: ProcessingConfig, *, rds: bool = False, pocsag: bool = False, ax25: bool = False, tones: bool = False,
-                 acars: bool = False, ais: bool = False, adsb: bool = False):
+                 acars: bool = False, ais: bool = False, adsb: bool = False, squelch: CarrierSquelch | None = None):
         self.config = config
         flags = dict(rds=rds, pocsag=pocsag, ax25=ax25, tones=tones, acars=acars, ais=ais, adsb=adsb)
         check_modes(flags, [config.demod_mode], plural=False)
+        self.squelch = check_squelch(squelch, config.demod_mode)  # --squelch: gate the audio by the channel's power
+        self.squelch_result = None  # after run(): the target's GateResult (None with the squelch off)
+        self.squelch_paths: list = []  # after run(): the WAV of every transmission (CarrierSquelch.split)
+        self.squelch_gate = None  # after run(): the target's CarrierGate (its stages(), for tests)
+        self.squelch_audio = None  # after run() with keep_channel_audio: the gated channel-rate audio (device float32)
         self._cancelled = False
         self._resolved_chunk_size: int | None = None
         self.chunk_rms_dbfs: list[float] = []
@@ -1001,7 +1021,7 @@ class ProcessingPipeline:
 
     def run(self, progress_sink: ProgressSink | None = None) -> ProcessingResult:
         """One target frequency: a :class:`MultiChannelPipeline` with a single channel."""
-        multi = MultiChannelPipeline([self.config], _owner=self, **self.side_enabled)
+        multi = MultiChannelPipeline([self.config], _owner=self, **self.side_enabled, squelch=self.squelch)
         self._multi = multi
         if self._cancelled:
             multi.cancel()
@@ -1042,6 +1062,9 @@ class _Target:
         self.pos_dec = 0
         self.peak = 0.0
         self.output_path = cfg.output_path if cfg.output_path else owner._default_output_path(info)
+        squelch = getattr(owner, "squelch", None)
+        self.gate = None if squelch is None else CarrierGate(P.plan_gate(fs_channel, squelch))
+        self.squelch_result = None
 
     def _channelizer(self, sign: int, exact: bool = False, fmt: str | None = None, precision: str | None = None) -> Channelizer:
         return Channelizer(self.taps, sample_rate=self.sample_rate, freq_offset=self.freq_offset, mix_sign=sign,
@@ -1115,6 +1138,8 @@ class _Target:
                 tracker.advance("dump_iq", float(n_out))
         if self.demod is not None and n_out:
             self.demod.process(z, self._starts, self.audio_all[..., self.pos_dec : self.pos_dec + n_out])
+            if self.gate is not None:
+                self.gate.process(z)
         tracker.advance("demod", float(n_out))
         tracker.advance("encode", n_out / max(self.fs_channel, 1e-9) * 48_000.0)
         self.pos_dec += n_out
@@ -1153,6 +1178,8 @@ class _Target:
         audio = self.audio_all[: self.pos_dec]
         if self.owner.keep_channel_audio:
             self.owner.audio_fs_channel = audio
+        if self.gate is not None:
+            audio = self._squelch(audio)
         rs = Resampler48k(self.fs_channel)
         pcm = rs.process(audio, want="pcm16").cpu().numpy()
         iqio.write_wav_pcm16(self.output_path, pcm, 48_000)
@@ -1160,6 +1187,27 @@ class _Target:
         self.owner.chunk_rms_dbfs = self.demod.chunk_rms_dbfs()
         LOG.info("Audio peak level %.2f dBFS.", 20.0 * math.log10(max(self.peak, 1e-6)))
         self._finish_side()
+
+    def _squelch(self, audio):
+        """Decide the gate with the whole run in view; the gated audio (a buffer of its own: ``keep_channel_audio``, the side
+        decoders, ``peak`` and ``chunk_rms_dbfs`` keep what they read).  With ``split`` every transmission's gated stretch
+        goes through a fresh resampler into ``<output stem>.tx0001.wav``, ..."""
+        self.gate.finish(self.pos_dec)
+        gated = self.gate.apply(audio)
+        res = self.squelch_result = self.owner.squelch_result = self.gate.result(frequency=self.target_freq)
+        self.owner.squelch_gate = self.gate
+        if self.owner.keep_channel_audio:
+            self.owner.squelch_audio = gated
+        self.owner.squelch_paths = []
+        for line in res.lines(f"{self.target_freq:.0f} Hz: "):
+            LOG.info("%s", line)
+        if self.owner.squelch.split:
+            for i, t in enumerate(res.transmissions, 1):
+                path = self.output_path.with_name(f"{self.output_path.stem}.tx{i:04d}.wav")
+                pcm = Resampler48k(self.fs_channel).process(gated[t.start : t.end], want="pcm16").cpu().numpy()
+                iqio.write_wav_pcm16(path, pcm, 48_000)
+                self.owner.squelch_paths.append(path)
+        return gated
 
     def _finish_side(self) -> None:
         """The active side decoders' results, in table order: kept per target, handed to the owner, logged."""
@@ -1183,7 +1231,7 @@ class MultiChannelPipeline:
     """
 
     def __init__(self, configs: list, _owner=None, *, rds: bool = False, pocsag: bool = False, ax25: bool = False, tones: bool = False,
-                 acars: bool = False, ais: bool = False, adsb: bool = False):
+                 acars: bool = False, ais: bool = False, adsb: bool = False, squelch=None):
         if not configs:
             raise ValueError("at least one ProcessingConfig is required")
         if len(configs) > 5 and _owner is None:
@@ -1198,7 +1246,14 @@ class MultiChannelPipeline:
         self.configs = configs
         flags = dict(rds=rds, pocsag=pocsag, ax25=ax25, tones=tones, acars=acars, ais=ais, adsb=adsb)
         check_modes(flags, [c.demod_mode for c in configs], plural=True)
-        self.owners = [_owner] if _owner is not None else [ProcessingPipeline(c, **flags) for c in configs]
+        # squelch: one CarrierSquelch for every target, or a list with one entry (or None) per target
+        each = list(squelch) if isinstance(squelch, (list, tuple)) else [squelch] * len(configs)
+        if len(each) != len(configs):
+            raise ValueError("squelch must name one entry per target")
+        for c, sq in zip(configs, each):
+            check_squelch(sq, c.demod_mode)
+        self.owners = [_owner] if _owner is not None else [ProcessingPipeline(c, **flags, squelch=sq) for c, sq in zip(configs, each)]
+        self.squelch_result = None  # after run(): per target, the GateResult (None where the squelch is off)
         self._cancelled = False
         self.wfm_stereo = None  # after run(): per target, the wfm stereo decision (None for the other modes)
         for e in SIDE_DECODERS:  # after run(): per target, the side decoder's result (None where it found nothing, or is off)
@@ -1411,6 +1466,7 @@ class MultiChannelPipeline:
             self.wfm_stereo = [t.stereo for t in targets]  # per target: True / False for wfm, None for the other modes
             for e in SIDE_DECODERS:
                 setattr(self, e.name, [t.side_results[e.name] for t in targets])
+            self.squelch_result = [t.squelch_result for t in targets]
             self.output_paths = [t.output_path for t in targets]  # where each target's audio went
             for t in targets:
                 t.owner.output_path = t.output_path
