@@ -2,8 +2,8 @@
 
 The per-chunk loop of the reference's ``ProcessingPipeline.run`` (processing.py:1070-1154) plus the writer's 48 kHz leg,
 for whole device-resident captures with one set of settings (the ``--benchmark`` pattern, multi-file batches;
-``bench.py`` is a loop over it).  Everything here is host-side sequencing of the stages in :mod:`.processing`:
-streams, events, buffer slots -- no arithmetic.
+``bench.py`` is a loop over it).  Everything here is host-side sequencing of the channelizer, the mixer-sign probe and
+the demodulator drivers: streams, events, buffer slots -- no arithmetic.
 """
 from __future__ import annotations
 
@@ -14,9 +14,11 @@ import numpy as np
 from . import _dev as D
 from . import _native as N
 from . import dsp_plan as P
+from .channel_demod import ChannelDemod, Resampler48k
+from .channelizer import ChannelBank, Channelizer, _ChannelKernel, immutable_taps
 from .decoders.side import NAMES
-from .processing import (PRECISION_GUARD, ChannelBank, ChannelDemod, Channelizer, MixSignProbe, Resampler48k, _ChannelKernel,
-                         base_precision, immutable_taps, pick_precision, probe_targets, reserve_pinned_scalars)
+from .mixsign import MixSignProbe, probe_targets, reserve_pinned_scalars
+from .precision import PRECISION_GUARD, base_precision, is_guarded, pick_precision
 
 
 def reject_wfm(modes) -> None:
@@ -40,6 +42,12 @@ def _rank(precision: str) -> int:
     return _ChannelKernel.PRECISIONS.index(precision)
 
 
+def warm_block(raw_dev, fmt: str, chunk: int, n_frames: int):
+    """The first reference chunk of a resident capture (what ``choose_mix_sign`` inspects): interleaved values, or
+    complex64 frames for 'f32'."""
+    return raw_dev[: 2 * min(chunk, n_frames)] if fmt != "f32" else raw_dev[: min(chunk, n_frames)]
+
+
 class ResidentCaptureRunner:
     """Ingest -> 48 kHz PCM16 for whole captures that already sit in HBM (multi-file batches with one set of
     settings; ``bench.py``): the per-chunk loop of the reference (processing.py:1070-1154) plus the writer's
@@ -59,10 +67,10 @@ class ResidentCaptureRunner:
 
     ``collect`` waits for a capture, reads the probe back and, if it chose -1 after all, re-runs that capture
     with the right sign before returning.  The same read-back carries the precision guard of the file pipeline
-    (``processing.pick_precision``): the probe's channel power against the wideband level of the warm-up block; an NFM
+    (``precision.pick_precision``): the probe's channel power against the wideband level of the warm-up block; an NFM
     channel too far below it for the precision the capture ran at is re-run at the one that clears it.  The last probed
     sign and precision are the next capture's speculation.  Nothing else is cached between captures except the plans.
-    SSB with the AGC on starts at the "full" precision (``processing.base_precision``).
+    SSB with the AGC on starts at the "full" precision (``precision.base_precision``).
     """
 
     # Output buffers in flight.  Three: the PCM16 copy of capture i (a handful of workgroups on the egress stream) is meant to
@@ -78,7 +86,7 @@ class ResidentCaptureRunner:
                  precision_guard: float | None = None, slots: int | None = None, graph_streams: int = 1, pocsag: bool = False,
                  ax25: bool = False, tones: bool = False, acars: bool = False, ais: bool = False, adsb: bool = False):
         """``precision``: the channelizer precision every capture starts at (default: by demodulator,
-        ``processing.base_precision``); ``precision_guard``: see ``processing.PRECISION_GUARD`` (0 = off).
+        ``precision.base_precision``); ``precision_guard``: see ``precision.PRECISION_GUARD`` (0 = off).
         ``slots``: captures in flight (output buffers; default 2).  ``submit`` of capture i first waits for capture
         i - slots: with captures of tens of microseconds (BASELINE config 1 replayed as hipGraphs) two in flight make every
         step a host round trip -- event wait, wake-up, graph launch -- which some hosts take 0.2 ms for; eight in flight
@@ -101,9 +109,12 @@ class ResidentCaptureRunner:
         self.override = mix_sign_override if mix_sign_override in (1, -1) else None
         self.base_precision = precision or base_precision(demod_mode, agc_enabled)
         self.guard = PRECISION_GUARD if precision_guard is None else float(precision_guard)
-        self._guarded = bool(self.guard) and self.override is None and (demod_mode or "").lower() in ("nfm", "fm")
+        self._guarded = bool(self.guard) and self.override is None and is_guarded(demod_mode)
+        self._guard_memo: dict = {}  # sign -> what pick_precision remembers of that sign's kernels
         self._spec_sign, self._spec_precision = 1, self.base_precision  # what the next capture is run with before its probe is read
         self.redone = dict(sign=0, precision=0)  # captures re-run in collect, by cause
+        self.replays_redone = 0  # ... of them, captures whose graph replay had assumed another sign / a coarser precision
+        self._graphs: dict = {}  # captured steps by (buffers, slot, speculation): submit_captured / submit_captured_batch
         self.n_dec = -(-self.n_frames // self.d)
         self.starts = P.chunk_output_starts(self.chunk, self.d, 0, self.n_frames)
         self.rs = Resampler48k(self.fs_ch)
@@ -124,28 +135,45 @@ class ResidentCaptureRunner:
         self._egress_pending = None  # ticket whose D2H has not been queued yet (see _flush_egress)
         self.egress_workgroups = 8
 
-    def _probe(self, raw_dev, resident: bool):
+    def _queue_probe(self, raw_dev):
+        """The capture's mixer-sign probe on the current stream (None with a sign override).  ``record_done=False``: the
+        events that lie behind the probes are the capture's own (set in _chain; a captured step has none) -- an event record
+        between two kernels of a stream costs ~7 us on this part."""
         if self.override is not None:
             return None
-        torch = D.torch_mod()
-        warm = raw_dev[: 2 * min(self.chunk, self.n_frames)] if self.fmt != "f32" else raw_dev[: min(self.chunk, self.n_frames)]
-        # record_done=False: the events that lie behind the probes are the capture's own (set in _chain) -- an event
-        # record between two kernels of a stream costs ~7 us on this part
-        with D.on_stream(self.aux if resident else self.compute, self.compute):
-            return MixSignProbe(warm, self.fs, self.f_off, self.taps, self.d, fmt=self.fmt, iq_order=self.iq_order,
-                                record_done=False, measure_level=self._guarded)
+        return MixSignProbe(warm_block(raw_dev, self.fmt, self.chunk, self.n_frames), self.fs, self.f_off, self.taps, self.d,
+                            fmt=self.fmt, iq_order=self.iq_order, record_done=False, measure_level=self._guarded)
 
-    def _kernel_for(self, sign: int):
-        return lambda name: Channelizer(self.taps, sample_rate=self.fs, freq_offset=self.f_off, mix_sign=sign, decimation=self.d,
-                                        fmt=self.fmt, iq_order=self.iq_order, precision=name)._kernel
+    def _probe(self, raw_dev, resident: bool):
+        with D.on_stream(self.aux if resident else self.compute, self.compute):
+            return self._queue_probe(raw_dev)
+
+    def _channelizer(self, sign: int, precision: str | None = None) -> Channelizer:
+        return Channelizer(self.taps, sample_rate=self.fs, freq_offset=self.f_off, mix_sign=sign, decimation=self.d,
+                           fmt=self.fmt, iq_order=self.iq_order, precision=precision or self.base_precision)
 
     def _needed_precision(self, probe, sign: int) -> str:
         """What the precision guard asks for, given a probe that has been read (``power``, ``wideband_rms`` set)."""
         if not self._guarded or probe is None:
             return self.base_precision
-        memo = self.__dict__.setdefault("_guard_memo", {}).setdefault(sign, {})
-        return pick_precision(self._kernel_for(sign), self.base_precision, self.demod_args["mode"], probe.power, probe.wideband_rms,
-                              self.guard, memo)
+        return pick_precision(lambda name: self._channelizer(sign, name)._kernel, self.base_precision, self.demod_args["mode"],
+                              probe.power, probe.wideband_rms, self.guard, self._guard_memo.setdefault(sign, {}))
+
+    @staticmethod
+    def _ticket(step: dict, slot: dict, done, *, sign: int, raw, halo, resident: bool = False, replayed: bool = False) -> dict:
+        """What ``collect`` needs of one queued capture.  ``step``: chan, dem, pcm, probe, kernel and precision of the launches
+        (``_chain`` / ``_captured_step``).  ``replayed``: they ran as a graph replay -- the PCM16 copy is part of it (``done``
+        lies behind it) and the probe is the graph's, whose pinned slot every replay writes (read with ``peek``)."""
+        return dict(chan=step["chan"], dem=step["dem"], pcm=step["pcm"], done=done, tail_done=done if replayed else None,
+                    kernel=step["kernel"], slot=slot, egress_queued=replayed, resident=resident, precision=step["precision"],
+                    probe=None if replayed else step["probe"], graph_probe=step["probe"] if replayed else None,
+                    sign=sign, raw=raw, halo=halo)
+
+    def _queue_pcm_copy(self, pcm, host, workgroups: int) -> None:
+        """The PCM16 of a capture into its pinned host buffer, on the current stream (a kernel whose waves sit on PCIe
+        stores: ``workgroups`` of them)."""
+        N.call("iqa_trickle_copy", N.ptr(pcm), c_void_p(host.data_ptr()), c_int64(host.numel() * host.element_size()),
+               c_int32(workgroups), N.stream_ptr())
 
     def _chain(self, raw_dev, slot, sign: int, events=None, halo=None, resident: bool = False, probe=None, precision: str | None = None,
                make_probe=None):
@@ -154,8 +182,7 @@ class ResidentCaptureRunner:
         wait for nothing on the compute stream, so queueing them first only delays the launch an idle GPU is waiting for (the
         first capture behind a synchronise: ~0.1 ms of host time)."""
         torch = D.torch_mod()
-        chan = Channelizer(self.taps, sample_rate=self.fs, freq_offset=self.f_off, mix_sign=sign, decimation=self.d,
-                           fmt=self.fmt, iq_order=self.iq_order, precision=precision or self.base_precision)
+        chan = self._channelizer(sign, precision)
         chan.plan_ahead()
         dem = slot["dem"]
         side = self.aux if resident else None
@@ -189,10 +216,9 @@ class ResidentCaptureRunner:
             probe._done = [aux_done] if resident else [gate]
         dem.process(slot["z"], self.starts, slot["audio"])
         pcm = self.rs.process(slot["audio"], want="pcm16")  # the float32 48 kHz stream is never stored
-        done = torch.cuda.Event()
-        # tail_done: recorded lazily (tail_event) -- the next capture's gate lies behind it anyway
-        ticket = dict(chan=chan, dem=dem, pcm=pcm, done=done, tail_done=None, kernel=chan._kernel.last_kernel,
-                      slot=slot, egress_queued=False, resident=resident, precision=chan.precision, probe=probe)
+        # (tail_done is recorded lazily, tail_event: the next capture's gate lies behind it anyway)
+        step = dict(chan=chan, dem=dem, pcm=pcm, probe=probe, kernel=chan._kernel.last_kernel, precision=chan.precision)
+        ticket = self._ticket(step, slot, torch.cuda.Event(), sign=sign, raw=raw_dev, halo=halo, resident=resident)
         self._egress_pending = ticket
         return ticket
 
@@ -221,10 +247,8 @@ class ResidentCaptureRunner:
         # (called with the compute stream current: from submit/_chain and from collect)
         with D.on_stream(self.egress, self.compute):
             t["pcm"].record_stream(self.egress)
-            host = t["slot"]["pcm_host"]
             # (ungated = the last capture of a batch, nothing to share the GPU with: as many workgroups as the link takes)
-            N.call("iqa_trickle_copy", N.ptr(t["pcm"]), c_void_p(host.data_ptr()), c_int64(host.numel() * host.element_size()),
-                   c_int32(self.egress_workgroups if gate is not None else max(self.egress_workgroups, 64)), N.stream_ptr())
+            self._queue_pcm_copy(t["pcm"], t["slot"]["pcm_host"], self.egress_workgroups if gate is not None else max(self.egress_workgroups, 64))
             t["done"].record(self.egress)
         t["egress_queued"] = True
         self._egress_pending = None
@@ -266,7 +290,6 @@ class ResidentCaptureRunner:
                                  make_probe=lambda: self._probe(raw_dev, True))
         else:
             ticket = self._chain(raw_dev, slot, sign, events, halo, resident, self._probe(raw_dev, resident), self._spec_precision)
-        ticket.update(sign=sign, raw=raw_dev, halo=halo)
         slot["busy"] = ticket
         return ticket
 
@@ -283,25 +306,18 @@ class ResidentCaptureRunner:
     def _captured_step(self, raw_dev, slot, halo):
         """Queue the whole step for the speculated sign / precision on the current (capturing) stream; returns what collect needs."""
         sign = self.override or self._spec_sign
-        chan = Channelizer(self.taps, sample_rate=self.fs, freq_offset=self.f_off, mix_sign=sign, decimation=self.d,
-                           fmt=self.fmt, iq_order=self.iq_order, precision=self._spec_precision)
+        chan = self._channelizer(sign, self._spec_precision)
         chan.plan_ahead()
         dem = slot["dem"]
-        probe = None
-        if self.override is None:
-            warm = raw_dev[: 2 * min(self.chunk, self.n_frames)] if self.fmt != "f32" else raw_dev[: min(self.chunk, self.n_frames)]
-            probe = MixSignProbe(warm, self.fs, self.f_off, self.taps, self.d, fmt=self.fmt, iq_order=self.iq_order, record_done=False,
-                                 measure_level=self._guarded)
+        probe = self._queue_probe(raw_dev)
         dem.reset(force=True)
         dem.prepare(self.n_dec, self.starts)
         chan.process(raw_dev, out_dev=slot["z"], last_block=True, halo=halo)
         dem.process(slot["z"], self.starts, slot["audio"])
         pcm = self.rs.process(slot["audio"], want="pcm16")
-        host = slot["pcm_host"]
         # (in a captured step the copy is a link of the chain, not a trickle beside the next channelizer: 64 workgroups --
         # config 1: 0.097 -> 0.0935 ms per capture)
-        N.call("iqa_trickle_copy", N.ptr(pcm), c_void_p(host.data_ptr()), c_int64(host.numel() * host.element_size()),
-               c_int32(max(self.egress_workgroups, 64)), N.stream_ptr())
+        self._queue_pcm_copy(pcm, slot["pcm_host"], max(self.egress_workgroups, 64))
         return dict(chan=chan, dem=dem, pcm=pcm, probe=probe, kernel=chan._kernel.last_kernel, sign=sign, precision=chan.precision)
 
     def submit_captured(self, raw_dev, enclosing=None, lead_frames: int = 0) -> dict:
@@ -321,8 +337,7 @@ class ResidentCaptureRunner:
                     self._spec_sign, self._spec_precision)
 
         key = graph_key()
-        graphs = self.__dict__.setdefault("_graphs", {})
-        entry = graphs.get(key)
+        entry = self._graphs.get(key)
         if entry is None:
             # once the ordinary way, in this very slot: plans, tap uploads and the pinned probe slot exist afterwards
             # (and the capture's own probe has set the speculation the graph is captured with)
@@ -333,7 +348,7 @@ class ResidentCaptureRunner:
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g):
                 parts = self._captured_step(raw_dev, slot, halo)
-            entry = graphs[key] = dict(graph=g, **parts)
+            entry = self._graphs[key] = dict(graph=g, **parts)
         else:
             self._next += 1
         entry["dem"].chunk_sumsq = entry["dem"].chunk_sumsq[-1:]  # (a replay re-runs the same demodulator call)
@@ -348,9 +363,7 @@ class ResidentCaptureRunner:
         else:
             entry["graph"].replay()
             done.record()
-        ticket = dict(chan=entry["chan"], dem=entry["dem"], pcm=entry["pcm"], done=done, tail_done=done, kernel=entry["kernel"],
-                      slot=slot, egress_queued=True, resident=False, probe=None, graph_probe=entry["probe"],
-                      sign=entry["sign"], precision=entry["precision"], raw=raw_dev, halo=halo)
+        ticket = self._ticket(entry, slot, done, sign=entry["sign"], raw=raw_dev, halo=halo, replayed=True)
         slot["busy"] = ticket
         return ticket
 
@@ -372,8 +385,7 @@ class ResidentCaptureRunner:
                                                                             for raw, enc, lead in captures)
 
         key = graph_key()
-        graphs = self.__dict__.setdefault("_graphs", {})
-        entry = graphs.get(key)
+        entry = self._graphs.get(key)
         if entry is None:
             self._next = 0
             for raw, enc, lead in captures:  # once the ordinary way, each in its slot
@@ -384,7 +396,7 @@ class ResidentCaptureRunner:
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g):
                 parts = [self._captured_step(raw, slot, halo) for (raw, _, _), slot, halo in zip(captures, self.slots, halos)]
-            entry = graphs[key] = dict(graph=g, parts=parts)
+            entry = self._graphs[key] = dict(graph=g, parts=parts)
         for p_ in entry["parts"]:
             p_["dem"].chunk_sumsq = p_["dem"].chunk_sumsq[-1:]
         entry["graph"].replay()
@@ -392,12 +404,27 @@ class ResidentCaptureRunner:
         done.record()
         tickets = []
         for (raw, _, _), slot, halo, p_ in zip(captures, self.slots, halos, entry["parts"]):
-            t = dict(chan=p_["chan"], dem=p_["dem"], pcm=p_["pcm"], done=done, tail_done=done, kernel=p_["kernel"], slot=slot,
-                     egress_queued=True, resident=False, probe=None, graph_probe=p_["probe"], sign=p_["sign"], precision=p_["precision"],
-                     raw=raw, halo=halo)
+            t = self._ticket(p_, slot, done, sign=p_["sign"], raw=raw, halo=halo, replayed=True)
             slot["busy"] = t
             tickets.append(t)
         return tickets
+
+    def _respeculate(self, ticket: dict, probe, sign: int) -> bool:
+        """``probe`` has been read and says ``sign``: that and the precision the guard asks for are the next capture's
+        speculation.  Where ``ticket``'s capture ran with another sign or at a coarser precision it is run again, the
+        ordinary way, in its slot (True).  A replayed step's graph probe is dropped with that: the probe of a capture run
+        the ordinary way had been read before."""
+        need = self._needed_precision(probe, sign)
+        self._spec_sign, self._spec_precision = sign, need
+        if sign == ticket["sign"] and _rank(need) <= _rank(ticket["precision"]):
+            return False
+        self.redone["sign" if sign != ticket["sign"] else "precision"] += 1
+        if ticket["graph_probe"] is None:  # (a replayed step has been waited for)
+            ticket["done"].synchronize()  # the slot's buffers are the first run's until then
+        redo = self._chain(ticket["raw"], ticket["slot"], sign, None, ticket["halo"], ticket["resident"], precision=need)
+        self._flush_egress()
+        ticket.update(redo, probe=ticket["probe"])
+        return True
 
     def collect(self, ticket: dict) -> dict:
         """Wait for a submitted capture.  Returns {"pcm_host", "sign", "demod" (``.peak``, ``.chunk_rms_dbfs()``),
@@ -405,41 +432,24 @@ class ResidentCaptureRunner:
         slot = ticket["slot"]
         if ticket.get("collected"):
             return ticket["result"]
-        if ticket.get("graph_probe") is not None:  # a replayed step: its probes' powers sit in the graph's pinned slot
-            ticket["done"].synchronize()
-            sign = ticket["graph_probe"].peek()
-            need = self._needed_precision(ticket["graph_probe"], sign)
-            self._spec_sign, self._spec_precision = sign, need
-            if sign != ticket["sign"] or _rank(need) > _rank(ticket["precision"]):
-                # the captured step assumed another sign / a coarser precision: this capture again, the ordinary way
-                self.replays_redone = getattr(self, "replays_redone", 0) + 1
-                self.redone["sign" if sign != ticket["sign"] else "precision"] += 1
-                redo = self._chain(ticket["raw"], slot, sign, None, ticket.get("halo"), False, precision=need)
-                self._flush_egress()
-                ticket.update(redo, sign=sign, probe=None, raw=ticket["raw"], graph_probe=None)
         if D.current_raw_stream() != self._compute_raw:  # (it may queue the D2H, or the whole capture again)
             raise RuntimeError("collect() must be called with the stream the runner was created on as the current stream")
-        sign = ticket["sign"]
-        if self._egress_pending is ticket:
+        replayed = ticket["graph_probe"] is not None  # a replayed step: its probes' powers sit in the graph's pinned slot
+        probe = ticket["graph_probe"] if replayed else ticket["probe"]
+        if replayed:
+            ticket["done"].synchronize()
+        elif self._egress_pending is ticket:
             self._flush_egress()
-        if ticket["probe"] is not None:
-            sign = ticket["probe"].result()
-            need = self._needed_precision(ticket["probe"], sign)
-            self._spec_sign, self._spec_precision = sign, need
-            if sign != ticket["sign"] or _rank(need) > _rank(ticket["precision"]):
-                # the speculation was wrong: this capture again, with the sign the probe chose / at the precision the guard asks for
-                self.redone["sign" if sign != ticket["sign"] else "precision"] += 1
-                ticket["done"].synchronize()
-                probe, raw = ticket["probe"], ticket["raw"]
-                redo = self._chain(raw, slot, sign, None, ticket.get("halo"), ticket.get("resident", False), precision=need)
-                self._flush_egress()
-                ticket.update(redo, sign=sign, probe=probe, raw=raw)
+        if probe is not None:
+            sign = probe.peek() if replayed else probe.result()
+            if self._respeculate(ticket, probe, sign) and replayed:
+                self.replays_redone += 1
         ticket["done"].synchronize()
         ticket["collected"] = True
         ticket["raw"] = ticket["pcm"] = None  # back to the allocator: the next capture reuses them
         if slot["busy"] is ticket:
             slot["busy"] = None
-        ticket["result"] = dict(pcm_host=slot["pcm_host"], sign=int(sign), audio=slot["audio"], z=slot["z"],
+        ticket["result"] = dict(pcm_host=slot["pcm_host"], sign=int(ticket["sign"]), audio=slot["audio"], z=slot["z"],
                                 kernel=ticket["kernel"], demod=ticket["dem"], done=ticket["done"], precision=ticket["precision"])
         return ticket["result"]
 
@@ -449,13 +459,13 @@ class ResidentBankRunner:
 
     The reference runs one pipeline per target over the same file (cli.py:683-710).  Here one ``submit`` queues, for one
     resident capture: every target's two mixer-sign probes (``choose_mix_sign``, processing.py:623-663), ONE pass of the
-    channelizer over the capture for all targets (:class:`processing.ChannelBank`, run speculatively for sign +1 like
+    channelizer over the capture for all targets (:class:`channelizer.ChannelBank`, run speculatively for sign +1 like
     :class:`ResidentCaptureRunner`), then per target the fused demodulator + writer clip, the 48 kHz resampler with PCM16
     output and the copy of that PCM16 into pinned host memory -- all on the caller's stream, no host<->device
     synchronisation.  ``collect`` waits, reads the probes back and re-runs the targets whose probe chose the other sign
-    or whose level asks for a finer precision (the precision guard, ``processing.pick_precision``); what a target's last
+    or whose level asks for a finer precision (the precision guard, ``precision.pick_precision``); what a target's last
     probe said is the next capture's speculation.  SSB targets with the AGC on run at "full" precision (their own chained
-    passes behind the shared one, ``processing.base_precision``).
+    passes behind the shared one, ``precision.base_precision``).
     """
 
     SLOTS = 3  # output buffers in flight: with the tails of capture i finishing somewhere inside the pass of capture i + 1, a
@@ -484,6 +494,7 @@ class ResidentBankRunner:
             spec.update(t)
             spec["taps"] = immutable_taps(P.design_channel_filter(self.fs, spec["bandwidth"], self.d))
             spec["base_precision"] = spec["precision"] or base_precision(spec["demod_mode"], spec["agc_enabled"])
+            spec["_guard_memo"] = {}  # sign -> what pick_precision remembers of that sign's kernels
             self.targets.append(spec)
         self.guard = PRECISION_GUARD if precision_guard is None else float(precision_guard)
         self._spec_sign = [1] * len(self.targets)
@@ -504,16 +515,15 @@ class ResidentBankRunner:
                            fmt=self.fmt, iq_order=self.iq_order, precision=precision or spec["base_precision"])
 
     def _guarded(self, spec) -> bool:
-        return bool(self.guard) and spec["mix_sign"] not in (1, -1) and (spec["demod_mode"] or "").lower() in ("nfm", "fm")
+        return bool(self.guard) and spec["mix_sign"] not in (1, -1) and is_guarded(spec["demod_mode"])
 
     def _needed_precision(self, spec, probe, sign: int) -> str:
         if probe is None or not self._guarded(spec):
             return spec["base_precision"]
-        memo = spec.setdefault("_guard_memo", {}).setdefault(sign, {})
         return pick_precision(lambda name: self._channelizer(spec, sign, name)._kernel, spec["base_precision"], spec["demod_mode"],
-                              probe.power, probe.wideband_rms, self.guard, memo)
+                              probe.power, probe.wideband_rms, self.guard, spec["_guard_memo"].setdefault(sign, {}))
 
-    def _finish_target(self, per, raw_unused=None) -> None:
+    def _finish_target(self, per) -> None:
         """Demodulator + writer clip, 48 kHz PCM16, copy to the host: for one target's z."""
         dem = per["dem"]
         dem.reset()
@@ -529,43 +539,21 @@ class ResidentBankRunner:
         self._next += 1
         if slot["busy"] is not None:
             self.collect(slot["busy"])
-        warm = raw_dev[: 2 * min(self.chunk, self.n_frames)] if self.fmt != "f32" else raw_dev[: min(self.chunk, self.n_frames)]
         main = torch.cuda.current_stream()
-        side = D.side_stream("tail")  # the targets' chains (see _submit_rest)
+        side = D.side_stream("tail")  # the targets' chains (below)
         # the capture is resident when submit is called: what depends on it alone may start now
         arrived = torch.cuda.Event()
         arrived.record(main)
         side.wait_event(arrived)
         # (the probes stay on the caller's stream: as ring-kernel launches they want most of a CU's LDS and would sit behind
-        # the running pass until it ends, one per pass boundary; through the float32 kernel -- MixSignProbe(matrix_cores=
-        # False) -- they fit beside it but the long filters' probes then take longer than the pass has room for: 10.4
-        # against 9.4 ms per capture at config 3)
-        probes = self._queue_probes(warm, slot)
+        # the running pass until it ends, one per pass boundary; through the float32 kernel they fit beside it but the long
+        # filters' probes then take longer than the pass has room for: 10.4 against 9.4 ms per capture at config 3)
+        probes = self._queue_probes(warm_block(raw_dev, self.fmt, self.chunk, self.n_frames), slot)
         signs = [s["mix_sign"] if s["mix_sign"] in (1, -1) else sp for s, sp in zip(self.targets, self._spec_sign)]
-        precisions = list(self._spec_precision)
-        chans = [self._channelizer(s, sg, pr) for s, sg, pr in zip(self.targets, signs, precisions)]
+        chans = [self._channelizer(s, sg, pr) for s, sg, pr in zip(self.targets, signs, self._spec_precision)]
         for c in chans:
             c.plan_ahead()
         halo = (enclosing, int(lead_frames)) if enclosing is not None else None
-        return self._submit_rest(raw_dev, slot, probes, signs, precisions, chans, halo, events, main, side)
-
-    def _queue_probes(self, warm, slot) -> list:
-        todo = [i for i, s in enumerate(self.targets) if s["mix_sign"] not in (1, -1)]
-        grouped = probe_targets(warm, self.fs, [(self.targets[i]["freq_offset"], self.targets[i]["taps"]) for i in todo], self.d,
-                                fmt=self.fmt, iq_order=self.iq_order, host=slot["probe_host"]) if len(todo) > 1 else None
-        if grouped is not None:  # every target's two probes as channels of one bank over the snippet
-            probes = [None] * len(self.targets)
-            for i, pr in zip(todo, grouped):
-                probes[i] = pr
-        else:
-            probes = [None if s["mix_sign"] in (1, -1) else
-                      MixSignProbe(warm, self.fs, s["freq_offset"], s["taps"], self.d, fmt=self.fmt, iq_order=self.iq_order,
-                                   measure_level=self._guarded(s))
-                      for s in self.targets]
-        return probes
-
-    def _submit_rest(self, raw_dev, slot, probes, signs, precisions, chans, halo, events, main, side) -> dict:
-        torch = D.torch_mod()
         if events:
             events[0].record()
         bank = ChannelBank(chans)
@@ -595,6 +583,21 @@ class ResidentBankRunner:
                       launch=bank.last_launch, kernel=chans[0]._kernel.last_kernel, collected=False)
         slot["busy"] = ticket
         return ticket
+
+    def _queue_probes(self, warm, slot) -> list:
+        todo = [i for i, s in enumerate(self.targets) if s["mix_sign"] not in (1, -1)]
+        grouped = probe_targets(warm, self.fs, [(self.targets[i]["freq_offset"], self.targets[i]["taps"]) for i in todo], self.d,
+                                fmt=self.fmt, iq_order=self.iq_order, host=slot["probe_host"]) if len(todo) > 1 else None
+        if grouped is not None:  # every target's two probes as channels of one bank over the snippet
+            probes = [None] * len(self.targets)
+            for i, pr in zip(todo, grouped):
+                probes[i] = pr
+        else:
+            probes = [None if s["mix_sign"] in (1, -1) else
+                      MixSignProbe(warm, self.fs, s["freq_offset"], s["taps"], self.d, fmt=self.fmt, iq_order=self.iq_order,
+                                   measure_level=self._guarded(s))
+                      for s in self.targets]
+        return probes
 
     def collect(self, ticket: dict) -> list:
         """Wait for a capture.  Returns one dict per target: {"pcm_host", "audio", "z", "sign", "demod"}; the buffers

@@ -134,7 +134,7 @@ def test_mix_sign_probes_share_a_launch(A):
 
     from iq_to_audio_amd import _dev as D
     from iq_to_audio_amd import _native as N
-    from iq_to_audio_amd.processing import MixSignProbe
+    from iq_to_audio_amd.mixsign import MixSignProbe, probe_window
 
     fs, d, f_off = 2.5e6, 26, 25e3
     taps = A.design_channel_filter(fs, 12_500.0, d)
@@ -147,11 +147,9 @@ def test_mix_sign_probes_share_a_launch(A):
         for s_ in (1, -1):
             ch = A.Channelizer(taps, sample_rate=fs, freq_offset=f_off, mix_sign=s_, decimation=d, fmt="s16")
             n_in = raw.numel() // 2
-            snippet = min(n_in, max(int(fs * 0.05), len(taps) * 4, 131_072))
-            n_z = -(-snippet // d)
-            discard = min(len(taps), n_z // 4)
-            z = D.empty(n_z - discard, "complex64")
-            assert ch._kernel.run_interior_only(raw, n_in, discard, n_z - discard, z)
+            _, _, discard, keep = probe_window(n_in, len(taps), fs, d)
+            z = D.empty(keep, "complex64")
+            assert ch._kernel.run_interior_only(raw, n_in, discard, keep, z)
             zz = z.cpu().numpy()
             powers.append(float(np.mean(np.abs(zz).astype(np.float32).astype(np.float64) ** 2)))
         assert sign == side == (1 if powers[0] >= powers[1] else -1)
@@ -161,7 +159,7 @@ def test_mix_sign_probes_share_a_launch(A):
     import torch
 
     from iq_to_audio_amd.benchmark import synthetic_multi_iq_s16
-    from iq_to_audio_amd.processing import probe_targets
+    from iq_to_audio_amd.mixsign import probe_targets
 
     fs3, d3 = 20e6, 208
     carriers = [(25e3, 0.2, "nfm"), (-150e3, 0.2, "am"), (400e3, 0.2, "usb"), (-1.1e6, 0.2, "nfm")]
