@@ -28,8 +28,10 @@
 // such a kernel is two slots per parity in LDS plus two rounds (lane pairs: three) of loads in the loaders' registers; the
 // loaders also emit.  The text above describes the LDS-DMA form, which remains at 14..16 k steps (the multiplying waves
 // issue the DMAs) and for uint8 captures (two loader waves issue them, ring_loader).  Up to 8 k steps a row whose last k
-// step is at most half full ends in 32x32x16 MFMAs (the ..._half kernels).  The forms measured against these and rejected
-// are recorded in DESIGN.md section 6.
+// step is at most half full (the ..._half kernels, D = 104 among them) runs on v_mfma_i32_16x16x64_i8 instead of 32x32x32:
+// the same tile per wave as four 16x16 blocks, the two off-diagonal ones in one accumulator, an odd last k step as a
+// 16x16x32 (ring_main_h16) -- equal cycles per product, but at its power limit the chip holds a higher clock on that shape.
+// The forms measured against these and rejected are recorded in DESIGN.md section 6.
 //
 // Every launch goes through the lane table of mfma_ring_launch_multi (k_channelize_mfma_s16_ring_multi / _multi_half /
 // _pairs, ..._s16_ring_rows_multi, ..._u8_ring_rows_multi): a single-channel pass (iqa_channelize_mfma) is a launch of one
@@ -119,10 +121,13 @@ __device__ __forceinline__ unsigned lds_addr(const void *p)
 // instead of two, so the ring is twice as deep in rounds at the same LDS (five rounds instead of two at 13 k steps: the
 // refill of a slot has four rounds to land instead of one) and a tile crosses L2 -> LDS once per two lanes; two windows
 // of sums.  The lanes of a pair share their tap-row group index (the staged stream depends on it).
-template <int KS, bool ROWS, bool U8 = false, bool PAIR = false>
+// H16 (single lanes over contiguous byte-plane slots): the kernels whose multiplying waves work on 16x16x64 matrix tiles
+// (ring_main_h16); their planes have a pitch of their own.
+template <int KS, bool ROWS, bool U8 = false, bool PAIR = false, bool H16 = false>
 struct RingGeo {
     static_assert(ROWS || !U8, "uint8 captures use row-staged slots");
     static_assert(!PAIR || (!ROWS && !U8), "lane pairs: contiguous slots only");
+    static_assert(!H16 || (!ROWS && !U8 && !PAIR && KS <= 8), "16x16x64 tiles: single lanes, contiguous byte-plane slots, up to 8 k steps");
     static constexpr int TPR = PAIR ? 1 : 2;  // tiles per round
     static constexpr int ACCS = PAIR ? 2 : 1;  // windows of sums
     static constexpr int KBYTES = U8 ? 32 : 64;  // bytes of a row per k step
@@ -147,7 +152,10 @@ struct RingGeo {
     // instructions per k step and wave beside 3 MFMAs, 8.5 % of config 2's kernel time
     // (profiles/r03_sustained_ablation_splits.txt).
     static constexpr bool SPLIT = LOADERS && !U8;
-    static constexpr int PLANE_PITCH = 32 * KS + 16;
+    // H16: lane l reads row l & 15 at unit 4 c + (l >> 4) of its row (ds_read_b128 serves lanes {0-3, 12-15, 20-27}, ... in one
+    // LDS cycle each): an odd pitch is a 2-way conflict for that pattern, a pitch of 4 n + 2 units -- 2 KS for odd KS, 2 KS + 2
+    // for even -- puts the 16 lanes of a group on 16 different bank quads
+    static constexpr int PLANE_PITCH = H16 ? 32 * (KS + 1 - (KS & 1)) : 32 * KS + 16;
     // (a loader wave has 168 registers: 4 KS SPLIT_F of data, 2 KS of offsets, the emission.)  Single lanes: two rounds in
     // flight -- config 2's kernel measures the same with three (profiles/r03b_ab_rounds_in_flight.txt), and with two a
     // workgroup of the 7-k-step kernel leaves room for the 80-register kernels of a capture's tail
@@ -175,7 +183,6 @@ struct RingCtx {
     int tiles, rounds, cnt, lane_off, rt, cp, col, h, lane;
     int row_units, pitch_units;  // contiguous slots: 16-byte units per data row in the capture / in LDS (odd)
     int tshift;  // lane pairs: this wave's own tile t is the staged tile of round t + tshift (0 without pairs)
-    int half_last;  // byte-plane kernels, contiguous slots: the row's last k step holds <= 16 values -- it is a 32x32x16 MFMA
 };
 
 // Source offset (bytes from the tile's first byte) of the 16 bytes lane `lane` of DMA instruction `idx` fetches: the
@@ -378,7 +385,7 @@ struct __attribute__((packed, aligned(4))) ring_raw16 {  // 16 bytes of the capt
 
 // PAIR: the four loader waves (HALF 0..3) share the round's one tile, piece 4 j + HALF each; waves 0 and 1 emit lane 0's and
 // lane 1's outputs (c.cp = the lane; a, c.s_acc, c.tshift are that lane's), every group of their lane.
-template <int KS, bool ACC64, bool ROWS, int HALF, bool PAIR = false>
+template <int KS, bool ACC64, bool ROWS, int HALF, bool PAIR = false, bool H16 = false>
 __device__ __forceinline__ void ring_loader_split(const MfmaArgs &a, const RingCtx &c)
 {
     constexpr bool EMITTER = PAIR ? HALF < 2 : HALF == 0;
@@ -389,7 +396,7 @@ __device__ __forceinline__ void ring_loader_split(const MfmaArgs &a, const RingC
     constexpr int STRIDE = PAIR ? RingGeo<KS, ROWS, false, PAIR>::NLOADERS : 2;
     constexpr int NP = UNEVEN ? (HALF ? 2 * KS - P0 : P0) : (2 * KS + STRIDE - 1) / STRIDE;
     auto piece = [](int j) { return UNEVEN ? (HALF ? P0 + j : j) : STRIDE * j + HALF; };
-    using G = RingGeo<KS, ROWS, false, PAIR>;
+    using G = RingGeo<KS, ROWS, false, PAIR, H16>;
     constexpr int SLOT = G::SLOT, PP = G::PLANE_PITCH, F = G::SPLIT_F;
     const int cp = c.cp;
     // 16-byte units of a data row that are staged: the whole row (contiguous slots: rows follow one another in the capture)
@@ -562,7 +569,7 @@ __device__ __forceinline__ void ring_loader_split(const MfmaArgs &a, const RingC
 // SKIP: what this wave does with the q2*hi product (the third matrix instruction of a k step): 0 = always computes it;
 // 2 = never (its lane's low tap byte is zero throughout: the first lane of a "fine" / "full" tap-row group); 1 = asks the
 // lane's flag at run time (both bodies in the code: ~30 registers more, so only the kernels of such launches carry it).
-template <int KS, bool ACC64, bool ROWS, bool U8, bool ISSUER, bool EMIT, bool DEFER, bool PAIR, typename SKIPT, bool HALF = false>
+template <int KS, bool ACC64, bool ROWS, bool U8, bool ISSUER, bool EMIT, bool DEFER, bool PAIR, typename SKIPT>
 __device__ __forceinline__ void ring_main(const MfmaArgs &a, const RingCtx &c, const v4i_t (&fq)[KS][2], SKIPT)
 {
     constexpr int SKIP = SKIPT::value;
@@ -745,19 +752,9 @@ __device__ __forceinline__ void ring_main(const MfmaArgs &a, const RingCtx &c, c
                 } else if constexpr (G::SPLIT) {
                     // byte planes: the operands as they lie in the slot (high bytes at la, biased low bytes 32 rows further)
                     v4i_t hh[KS], ll[KS];
-                    constexpr bool half_last = HALF;  // (a property of the kernel variant: both bodies in one kernel cost ~25 registers)
                     auto fetch = [&](int ks) {  // `ks` is a compile-time constant at every call site
-                        if (ks == KS - 1 && half_last) {  // this lane's 8 values of the half step: 8 h bytes into the step, not 16 h
-                            const int2 h2 = *reinterpret_cast<const int2 *>(la - 8 * c.h + 32 * ks);
-                            const int2 l2 = *reinterpret_cast<const int2 *>(la - 8 * c.h + 32 * G::PLANE_PITCH + 32 * ks);
-                            hh[ks].x = h2.x;
-                            hh[ks].y = h2.y;
-                            ll[ks].x = l2.x;
-                            ll[ks].y = l2.y;
-                        } else {
-                            hh[ks] = *reinterpret_cast<const v4i_t *>(la + 32 * ks);
-                            ll[ks] = *reinterpret_cast<const v4i_t *>(la + 32 * G::PLANE_PITCH + 32 * ks);
-                        }
+                        hh[ks] = *reinterpret_cast<const v4i_t *>(la + 32 * ks);
+                        ll[ks] = *reinterpret_cast<const v4i_t *>(la + 32 * G::PLANE_PITCH + 32 * ks);
                     };
 #pragma unroll
                     for (int ks = 0; ks < PD; ++ks) fetch(ks);
@@ -765,18 +762,9 @@ __device__ __forceinline__ void ring_main(const MfmaArgs &a, const RingCtx &c, c
                     for (int ks = 0; ks < KS; ++ks) {
                         const v4i_t hi = hh[ks], lo = ll[ks];
                         if (ks + PD < KS) fetch(ks + PD);
-                        if (ks == KS - 1 && half_last) {
-                            auto pack = [](int x, int y) { return static_cast<long>((static_cast<unsigned long long>(static_cast<unsigned>(y)) << 32) | static_cast<unsigned>(x)); };
-                            const long a1 = pack(fq[ks][0].x, fq[ks][0].y), a2 = pack(fq[ks][1].x, fq[ks][1].y);
-                            const long bh = pack(hi.x, hi.y), bl = pack(lo.x, lo.y);
-                            acc1 = __builtin_amdgcn_mfma_i32_32x32x16_i8(a1, bh, ks ? acc1 : zero16, 0, 0, 0);
-                            acc2 = __builtin_amdgcn_mfma_i32_32x32x16_i8(a1, bl, ks ? acc2 : zero16, 0, 0, 0);
-                            if constexpr (!SKIP_LOW) acc2 = __builtin_amdgcn_mfma_i32_32x32x16_i8(a2, bh, acc2, 0, 0, 0);
-                        } else {
-                            acc1 = __builtin_amdgcn_mfma_i32_32x32x32_i8(fq[ks][0], hi, ks ? acc1 : zero16, 0, 0, 0);
-                            acc2 = __builtin_amdgcn_mfma_i32_32x32x32_i8(fq[ks][0], lo, ks ? acc2 : zero16, 0, 0, 0);
-                            if constexpr (!SKIP_LOW) acc2 = __builtin_amdgcn_mfma_i32_32x32x32_i8(fq[ks][1], hi, acc2, 0, 0, 0);
-                        }
+                        acc1 = __builtin_amdgcn_mfma_i32_32x32x32_i8(fq[ks][0], hi, ks ? acc1 : zero16, 0, 0, 0);
+                        acc2 = __builtin_amdgcn_mfma_i32_32x32x32_i8(fq[ks][0], lo, ks ? acc2 : zero16, 0, 0, 0);
+                        if constexpr (!SKIP_LOW) acc2 = __builtin_amdgcn_mfma_i32_32x32x32_i8(fq[ks][1], hi, acc2, 0, 0, 0);
                     }
                 } else {
                     // raw int16 tiles (14..16 k steps): every wave splits its fragments into high and biased low bytes itself
@@ -842,6 +830,126 @@ __device__ __forceinline__ void ring_main(const MfmaArgs &a, const RingCtx &c, c
     }
 }
 
+// The main loop of a multiplying wave of the half-step kernels (k_channelize_mfma_s16_ring_multi_half: byte planes fed by
+// loader waves, int32 sums, one lane per workgroup): the wave's tile of 32 tap rows x 32 data rows as 16x16 blocks --
+// tap-row halves bi, data-row halves bj -- on v_mfma_i32_16x16x64_i8: a chunk of 64 values (two k steps) per instruction,
+// an odd last k step on v_mfma_i32_16x16x32_i8.  Held at its power limit the chip keeps a higher clock on this shape than on
+// 32x32x32 (probe/kstep_probe.hip `shape`).
+//   * Element r of lane l of block (bi, bj) is tap row 16 bi + 4 (l >> 4) + r against data row 16 bj + (l & 15): output
+//     position 16 (bi + bj) + (l & 15) + 4 (l >> 4) + r of the tile.  Blocks (0, 1) and (1, 0) are the same positions and
+//     share their accumulators: three blocks per sum, 12 adds per tile.  (dsp_plan.plan_mfma(acc32=True) bounds any
+//     partial sum of an output's terms, so no such sum overflows.)
+//   * Tap operand of chunk c, half bi: values 64 c + 16 (l >> 4) .. + 15 of tap row 16 bi + (l & 15) -- in the planner's
+//     fragments (32x32x32 order: lane = row + 32 * (value >> 4) of the k step) that is lane 16 bi + (l & 15) + 32 ((l >> 4) & 1)
+//     of k step 2 c + (l >> 5).  The odd last step: values 8 (l >> 4) .. + 7, half a fragment.  Gathered once per wave.
+//   * Data operand: 16 bytes at 64 c + 16 (l >> 4) of row 16 bj + (l & 15) of either plane (RingGeo::PLANE_PITCH keeps these
+//     reads conflict-free); the odd last step 8 bytes.  What a row holds past its 2 D values meets zero taps.
+template <int KS>
+__device__ __forceinline__ void ring_main_h16(const MfmaArgs &a, const RingCtx &c)
+{
+    using G = RingGeo<KS, false, false, false, true>;
+    static_assert(G::SPLIT && G::R == 2, "byte planes, two slots per parity");
+    constexpr int SLOT = G::SLOT, PP = G::PLANE_PITCH, NC = KS / 2, ODD = KS & 1;
+    const int r16 = c.lane & 15, g = c.lane >> 4;
+    v4i_t tq[NC ? NC : 1][2][2];  // [chunk][tap-row half][piece q1, q2]
+    long tl[2][2] = {};           // the odd last k step
+    const v4i_t *fa = a.afrag + c.rt * 128;
+#pragma unroll
+    for (int ch = 0; ch < NC; ++ch)
+#pragma unroll
+        for (int bi = 0; bi < 2; ++bi)
+#pragma unroll
+            for (int pc = 0; pc < 2; ++pc) tq[ch][bi][pc] = fa[((2 * ch + (g >> 1)) * 8 + pc) * 64 + 16 * bi + r16 + 32 * (g & 1)];
+    if constexpr (ODD) {
+#pragma unroll
+        for (int bi = 0; bi < 2; ++bi)
+#pragma unroll
+            for (int pc = 0; pc < 2; ++pc) tl[bi][pc] = reinterpret_cast<const long *>(fa + ((KS - 1) * 8 + pc) * 64 + 16 * bi + r16 + 32 * (g >> 1))[g & 1];
+    }
+    // have them arrive here: a wait for them inside the round loop would be met in every round
+#pragma unroll
+    for (int ch = 0; ch < NC; ++ch)
+#pragma unroll
+        for (int bi = 0; bi < 2; ++bi) asm volatile("" ::"v"(tq[ch][bi][0]), "v"(tq[ch][bi][1]));
+    asm volatile("" ::"v"(tl[0][0]), "v"(tl[0][1]), "v"(tl[1][0]), "v"(tl[1][1]));
+    const int lane_off = r16 * PP + 16 * g;
+    // The odd step's four 8-byte reads (data-row half, plane) each get an offset register of their own, and the compiler is
+    // not told how they relate: it would pair them into ds_read2st64_b64, whose 16-lane groups and 32 banks make this
+    // pitch a 4-way conflict (measured: 24 extra LDS cycles per instruction against 2 for a plain ds_read_b64)
+    int lane_off_odd[2][2];
+#pragma unroll
+    for (int pl = 0; pl < 2; ++pl)
+#pragma unroll
+        for (int bj = 0; bj < 2; ++bj) {
+            lane_off_odd[pl][bj] = r16 * PP + 32 * (KS - 1) + 8 * g + 32 * PP * pl + 16 * PP * bj;
+            asm volatile("" : "+v"(lane_off_odd[pl][bj]));
+        }
+    const v4i_t zero4 = {0, 0, 0, 0};
+    int slot = 0;
+    for (int r = 0; r < c.rounds; ++r) {
+        asm volatile("s_barrier" ::: "memory");
+        const int t = 2 * r + c.cp;
+        if (t < c.tiles) {
+            const char *la = c.smem + (slot * 2 + c.cp) * SLOT + lane_off;
+            const char *lb = c.smem + (slot * 2 + c.cp) * SLOT;
+            v4i_t hh[NC ? NC : 1][2], ll[NC ? NC : 1][2];  // [chunk][data-row half]: high bytes, biased low bytes
+            long ho[2] = {}, lo[2] = {};
+            v4i_t a1[3], a2[3];  // S1, S2 of the blocks bi + bj = 0, 1, 2
+            auto fetch = [&](int ch) {  // `ch` is a compile-time constant at every call site
+#pragma unroll
+                for (int bj = 0; bj < 2; ++bj) {
+                    if (ch < NC) {
+                        hh[ch][bj] = *reinterpret_cast<const v4i_t *>(la + 16 * PP * bj + 64 * ch);
+                        ll[ch][bj] = *reinterpret_cast<const v4i_t *>(la + 32 * PP + 16 * PP * bj + 64 * ch);
+                    } else {
+                        ho[bj] = *reinterpret_cast<const long *>(lb + lane_off_odd[0][bj]);
+                        lo[bj] = *reinterpret_cast<const long *>(lb + lane_off_odd[1][bj]);
+                    }
+                }
+            };
+            // the twelve products of a step (q1*hi into S1; q1*lo and q2*hi into S2); an accumulator's uses lie at least two
+            // instructions apart
+            auto step = [&](auto mf, const auto &q, const auto &hi, const auto &lw, bool first) {
+                a2[1] = mf(q[0][0], lw[1], first ? zero4 : a2[1]);
+                a1[0] = mf(q[0][0], hi[0], first ? zero4 : a1[0]);
+                a2[0] = mf(q[0][0], lw[0], first ? zero4 : a2[0]);
+                a2[1] = mf(q[1][0], lw[0], a2[1]);
+                a1[1] = mf(q[0][0], hi[1], first ? zero4 : a1[1]);
+                a1[2] = mf(q[1][0], hi[1], first ? zero4 : a1[2]);
+                a2[1] = mf(q[0][1], hi[1], a2[1]);
+                a2[2] = mf(q[1][0], lw[1], first ? zero4 : a2[2]);
+                a1[1] = mf(q[1][0], hi[0], a1[1]);
+                a2[1] = mf(q[1][1], hi[0], a2[1]);
+                a2[0] = mf(q[0][1], hi[0], a2[0]);
+                a2[2] = mf(q[1][1], hi[1], a2[2]);
+            };
+            auto mf64 = [](v4i_t x, v4i_t y, v4i_t z) { return __builtin_amdgcn_mfma_i32_16x16x64_i8(x, y, z, 0, 0, 0); };
+            auto mf32 = [](long x, long y, v4i_t z) { return __builtin_amdgcn_mfma_i32_16x16x32_i8(x, y, z, 0, 0, 0); };
+            fetch(0);  // reads run one step ahead of the MFMAs
+#pragma unroll
+            for (int ch = 0; ch < NC; ++ch) {
+                if (ch + 1 < NC + ODD) fetch(ch + 1);
+                step(mf64, tq[ch], hh[ch], ll[ch], ch == 0);
+            }
+            if constexpr (ODD) step(mf32, tl, ho, lo, NC == 0);
+            // diagonal scatter into the window of sums, 256*S1 + S2 in one int32 as in ring_main (inline asm for the same reason)
+            // (lanes 16 apart meet on 12 of a half wave's 20 addresses: a 2-way serialisation per add.  Sending the lanes of odd
+            // l >> 4 into a second window that the emission adds measured the same)
+            const unsigned p = lds_addr(c.s_acc + ((t * 32 + 32 * (c.rt & 1) + r16 + 4 * g + 1) & (RG_W - 1)) + (c.rt >> 1) * RG_AS);
+#pragma unroll
+            for (int s = 0; s < 3; ++s)
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const int comb = (a1[s][q] << 8) + a2[s][q];
+                    asm volatile("ds_add_u32 %0, %1 offset:%2" ::"v"(p), "v"(comb), "n"(4 * (16 * s + q)));
+                }
+        }
+        slot ^= 1;
+    }
+    // the loader waves emit the last groups behind a full wait and one more barrier
+    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
+}
+
 // One block = one contiguous range of outputs of any length (the host gives every CU one range): a persistent
 // stream through the ring, sums in a 512-position sliding window, outputs emitted two rounds behind the matrix work.
 // SKIPK (kernels of launches in which some lanes have high-byte-only taps, see ring_main's SKIP): lane pairs -- the pair's
@@ -850,7 +958,7 @@ __device__ __forceinline__ void ring_main(const MfmaArgs &a, const RingCtx &c, c
 template <int KS, bool ACC64, bool ROWS, bool U8, bool PAIR = false, bool SKIPK = false, bool HALF = false>
 __device__ __forceinline__ void ring_block(const MfmaArgs &a, long long range_idx)
 {
-    using G = RingGeo<KS, ROWS, U8, PAIR>;
+    using G = RingGeo<KS, ROWS, U8, PAIR, HALF>;
     constexpr int R = G::R, SLOT = G::SLOT;
     constexpr bool LOADERS = G::LOADERS;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -896,14 +1004,23 @@ __device__ __forceinline__ void ring_block(const MfmaArgs &a, long long range_id
                     default: ring_loader_split<KS, ACC64, ROWS, 3, true>(a, c); break;
                 }
             } else if constexpr (G::SPLIT) {
-                if ((wave - RG_WAVES) >> 1) ring_loader_split<KS, ACC64, ROWS, 1>(a, c);
-                else ring_loader_split<KS, ACC64, ROWS, 0>(a, c);
+                if ((wave - RG_WAVES) >> 1) ring_loader_split<KS, ACC64, ROWS, 1, false, HALF>(a, c);
+                else ring_loader_split<KS, ACC64, ROWS, 0, false, HALF>(a, c);
             } else {
                 ring_loader<KS, ACC64>(a, c);
             }
             return;
         }
     }
+    // A row of 2 D values whose last k step holds at most 16 of them (D = 104: 208 = 6 x 32 + 16), up to 8 k steps (the
+    // kernel variant HALF: the launcher picks it for rows of 32 (KS - 1) + 1 .. 16 values): 16x16x64 matrix tiles, which
+    // gather their own tap operands
+    if constexpr (HALF) {
+        static_assert(!ROWS && !U8 && !PAIR && !ACC64 && !SKIPK, "16x16x64 tiles: single lanes over contiguous byte-plane slots, int32 sums");
+        __syncthreads();
+        c.stream0 = stream;
+        ring_main_h16<KS>(a, c);
+    } else {
     // tap fragments of this wave's row tile: registers for the whole block
     v4i_t fq[KS][2];
     {
@@ -915,24 +1032,6 @@ __device__ __forceinline__ void ring_block(const MfmaArgs &a, long long range_id
         // have them arrive here, before the first DMA: a later wait for them would drain the DMA queue with them
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) asm volatile("" ::"v"(fq[ks][0]), "v"(fq[ks][1]));
-    }
-    // A row of 2 D values whose last k step holds at most 16 of them (D = 104: 208 = 6 x 32 + 16): the other half of that
-    // step multiplied padding against zero taps.  The byte planes make the half step a v_mfma_i32_32x32x16_i8 -- lanes 0..31
-    // take values 0..7 of the step, lanes 32..63 values 8..15: the tap fragment's first 8 bytes, and for the upper lanes the
-    // second 8 bytes of the lane 32 below (whose own bytes were the padding's zero taps); the data are two ds_read_b64.
-    // (The kernel variant HALF: the launcher picks it for rows of 32 (KS - 1) + 1 .. 16 values.)
-    c.half_last = HALF;
-    if constexpr (HALF) {
-        static_assert(!ROWS && !U8 && !PAIR, "the half last k step exists for single lanes over contiguous byte-plane slots");
-#pragma unroll
-        for (int pc = 0; pc < 2; ++pc) {
-            const v4i_t f = fq[KS - 1][pc];
-            const int z0 = __shfl(f.z, c.lane ^ 32, kWave), w0 = __shfl(f.w, c.lane ^ 32, kWave);
-            if (c.h) {
-                fq[KS - 1][pc].x = z0;
-                fq[KS - 1][pc].y = w0;
-            }
-        }
     }
     __syncthreads();
     c.stream0 = stream;
@@ -954,8 +1053,8 @@ __device__ __forceinline__ void ring_block(const MfmaArgs &a, long long range_id
         else ring_main<KS, ACC64, ROWS, U8, false, false, false, true>(a, c, fq, std::integral_constant<int, SA>{});
     } else if constexpr (LOADERS) {
         constexpr int S1 = SKIPK ? 1 : 0;
-        if (c.cp) ring_main<KS, ACC64, ROWS, U8, false, false, true, false, std::integral_constant<int, S1>, HALF>(a, c, fq, std::integral_constant<int, S1>{});
-        else ring_main<KS, ACC64, ROWS, U8, false, false, false, false, std::integral_constant<int, S1>, HALF>(a, c, fq, std::integral_constant<int, S1>{});
+        if (c.cp) ring_main<KS, ACC64, ROWS, U8, false, false, true, false>(a, c, fq, std::integral_constant<int, S1>{});
+        else ring_main<KS, ACC64, ROWS, U8, false, false, false, false>(a, c, fq, std::integral_constant<int, S1>{});
     } else {
         constexpr int S1 = SKIPK ? 1 : 0;
         // one issuing wave per SIMD (waves go to SIMDs in a cyclic order of period 4): rt 0,1 of parity 0, rt 2,3 of parity 1
@@ -965,6 +1064,7 @@ __device__ __forceinline__ void ring_block(const MfmaArgs &a, long long range_id
         } else if (wave == RG_EMIT_WAVE) ring_main<KS, ACC64, ROWS, U8, false, true, false, false>(a, c, fq, std::integral_constant<int, S1>{});
         else if (c.cp) ring_main<KS, ACC64, ROWS, U8, false, false, true, false>(a, c, fq, std::integral_constant<int, S1>{});
         else ring_main<KS, ACC64, ROWS, U8, false, false, false, false>(a, c, fq, std::integral_constant<int, S1>{});
+    }
     }
 }
 
@@ -1046,12 +1146,12 @@ __global__ __launch_bounds__((RingGeo<KS, false>::THREADS), (RingGeo<KS, false>:
     ring_multi_block<KS, false, false, false, ACC64, SKIPK>(m);
 }
 
-// ... with the row's last k step as a 32x32x16 MFMA (rows of 32 (KS - 1) + 1 .. 16 values: D = 104 -> 208 = 6 x 32 + 16;
-// see ring_block).
+// ... for rows whose last k step is at most half full (rows of 32 (KS - 1) + 1 .. 16 values: D = 104 -> 208 = 6 x 32 + 16),
+// on 16x16x64 matrix tiles (ring_main_h16).
 template <int KS>
-__global__ __launch_bounds__((RingGeo<KS, false>::THREADS), 3) void k_channelize_mfma_s16_ring_multi_half(RingMultiArgs m)
+__global__ __launch_bounds__((RingGeo<KS, false, false, false, true>::THREADS), 3) void k_channelize_mfma_s16_ring_multi_half(RingMultiArgs m)
 {
-    static_assert(RingGeo<KS, false>::SPLIT, "byte-plane kernels only");
+    static_assert(RingGeo<KS, false, false, false, true>::SPLIT, "byte-plane kernels only");
     ring_multi_block<KS, false, false, false, false, false, true>(m);
 }
 
@@ -1123,8 +1223,10 @@ static int ring_launch_multi(const RingMultiArgs &m, unsigned blocks, size_t lds
     if (skipk) return ring_launch_kernel(k_channelize_mfma_s16_ring_multi<KS, false, true>, "k_channelize_mfma_s16_ring_multi", RingGeo<KS, false>::THREADS, m, blocks, lds, stream, done[6]);
     if constexpr (KS <= 8) {
         const int rem = (2 * m.c.D) & 31;  // values in the row's last k step
-        if (rem != 0 && rem <= 16)
-            return ring_launch_kernel(k_channelize_mfma_s16_ring_multi_half<KS>, "k_channelize_mfma_s16_ring_multi", RingGeo<KS, false>::THREADS, m, blocks, lds, stream, done[7]);
+        if (rem != 0 && rem <= 16) {  // (planes at a pitch of their own: this family's LDS, not the caller's figure)
+            using GH = RingGeo<KS, false, false, false, true>;
+            return ring_launch_kernel(k_channelize_mfma_s16_ring_multi_half<KS>, "k_channelize_mfma_s16_ring_multi", GH::THREADS, m, blocks, GH::LDS_BYTES, stream, done[7]);
+        }
     }
     return ring_launch_kernel(k_channelize_mfma_s16_ring_multi<KS>, "k_channelize_mfma_s16_ring_multi", RingGeo<KS, false>::THREADS, m, blocks, lds, stream, done[0]);
 }

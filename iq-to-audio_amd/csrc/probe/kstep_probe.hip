@@ -7,11 +7,16 @@
 //   mode 4: mode 3 + the scatter (16 ds_add_u32 of 256*acc1 + acc2 per tile)
 // 256 workgroups x 8 waves (two per SIMD), tap fragments in registers as in the kernel.  Prints MFMAs per SIMD-cycle
 // against the pipe's 1 / 32.   Build: hipcc --offload-arch=gfx950 -O3 kstep_probe.hip -o kstep_probe
+//   kstep_probe shape [seconds] [pairs]: the 32x32x32 tile body against the 16x16x64 one at the same tile per wave (wall
+//     time, in-kernel clock, equal sums) and the bare issue rates of the four int8 forms -- see k_probe_shape
+//   kstep_probe lds: the LDS access patterns of both bodies, one kernel each, for a counters-only profiler run
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
 #include <type_traits>
 #include <cstdlib>
+#include <algorithm>
+#include <string>
 #include <vector>
 
 typedef int v4i __attribute__((ext_vector_type(4)));
@@ -352,8 +357,389 @@ static void run_rt(const v4i *taps, int *sink, int tiles, unsigned long long *cl
            ms * 1e6 / tiles / (BLK * WAVES * RT / 4.0));
 }
 
+// ---- the MFMA shape at the same tile per wave: 32 tap rows x 32 data rows, byte planes, 7 k steps, half last step ----
+// BODY 0: six v_mfma_i32_32x32x32_i8 steps and one 32x32x16 (plane pitch 15 sixteen-byte units), lane = data row.
+// BODY 1: three v_mfma_i32_16x16x64_i8 chunks and one 16x16x32 for the odd last k step (plane pitch 14 units); the two
+//         off-diagonal 16x16 blocks of the tile land on the same output positions and share one accumulator.
+// Both read the same logical tile (random bytes) and the same tap fragments (the library's afrag layout, random, zero
+// beyond value 208 as the planner pads them); the windows of sums they leave must be equal -- that also checks the tap
+// gather and the lane maps.  Twelve waves as in the kernel: eight multiply (two per SIMD), four only join the barriers
+// (the loader waves' place).  In-kernel clock: s_memtime ticks per 100 MHz s_memrealtime tick (diagnostic, this probe only).
+constexpr int SH_KS = 7, SH_AS = 576;
+template <int BODY>
+struct ShapeGeo {
+    static constexpr int PP = BODY ? 32 * SH_KS : 32 * SH_KS + 16;  // bytes per row of a plane
+    static constexpr int SLOT = 64 * PP;
+    static constexpr int LDS = 2 * SLOT + 2 * SH_AS * 4;
+};
+
+__device__ __forceinline__ unsigned sh_hash(unsigned x)
+{
+    x ^= x >> 16;
+    x *= 0x7feb352du;
+    x ^= x >> 15;
+    x *= 0x846ca68bu;
+    x ^= x >> 16;
+    return x;
+}
+
+template <int BODY>
+__global__ __launch_bounds__(768, 3) void k_probe_shape(const v4i *afrag, int *win_out, int tiles, unsigned long long *clk)
+{
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    using G = ShapeGeo<BODY>;
+    constexpr int KS = SH_KS, PP = G::PP;
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    int *s_acc = reinterpret_cast<int *>(smem + 2 * G::SLOT);
+    // the two parities' tiles: byte b of row `row` of plane `pl` of slot `cp` is the same in either body's layout
+    for (int i = tid; i < 2 * 2 * 32 * 32 * KS; i += 768) {
+        const int b = i % (32 * KS), row = (i / (32 * KS)) & 31, pl = (i / (32 * KS * 32)) & 1, cp = i / (32 * KS * 64);
+        smem[cp * G::SLOT + pl * 32 * PP + row * PP + b] = static_cast<char>(sh_hash(i) >> 13);
+    }
+    for (int i = tid; i < 2 * SH_AS; i += 768) s_acc[i] = 0;
+    __syncthreads();
+    const int rt = wave & 3, cp = (wave >> 2) & 1, h = lane >> 5, col = lane & 31;
+    const char *slot = smem + cp * G::SLOT;
+    unsigned long long c0 = 0, r0 = 0, c1 = 0, r1 = 0;
+    if (wave >= 8) {  // the loader waves' place: barriers only
+        for (int t = 0; t < tiles; ++t) asm volatile("s_barrier" ::: "memory");
+    } else if constexpr (BODY == 0) {
+        v4i fq[KS][2];
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks)
+#pragma unroll
+            for (int pc = 0; pc < 2; ++pc) fq[ks][pc] = afrag[(ks * 8 + rt * 2 + pc) * 64 + lane];
+#pragma unroll
+        for (int pc = 0; pc < 2; ++pc) {  // the half last step: the upper lanes take values 8..15 of the lane 32 below
+            const v4i f = fq[KS - 1][pc];
+            const int z0 = __shfl(f.z, lane ^ 32, 64), w0 = __shfl(f.w, lane ^ 32, 64);
+            if (h) {
+                fq[KS - 1][pc].x = z0;
+                fq[KS - 1][pc].y = w0;
+            }
+        }
+        const char *la = slot + col * PP + 16 * h;
+        const v16i zero16 = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+        c0 = __builtin_amdgcn_s_memtime(), r0 = __builtin_amdgcn_s_memrealtime();
+        for (int t = 0; t < tiles; ++t) {
+            asm volatile("s_barrier" ::: "memory");
+            typedef int v2i __attribute__((ext_vector_type(2)));
+            v4i hh[KS], ll[KS];
+            v16i acc1 = zero16, acc2 = zero16;
+            auto fetch = [&](int ks) {
+                if (ks == KS - 1) {
+                    const v2i h2 = *reinterpret_cast<const v2i *>(la - 8 * h + 32 * ks);
+                    const v2i l2 = *reinterpret_cast<const v2i *>(la - 8 * h + 32 * PP + 32 * ks);
+                    hh[ks].x = h2.x, hh[ks].y = h2.y, ll[ks].x = l2.x, ll[ks].y = l2.y;
+                } else {
+                    hh[ks] = *reinterpret_cast<const v4i *>(la + 32 * ks);
+                    ll[ks] = *reinterpret_cast<const v4i *>(la + 32 * PP + 32 * ks);
+                }
+            };
+            fetch(0);
+            fetch(1);
+#pragma unroll
+            for (int ks = 0; ks < KS; ++ks) {
+                const v4i hi = hh[ks], lo = ll[ks];
+                if (ks + 2 < KS) fetch(ks + 2);
+                if (ks == KS - 1) {
+                    auto pack = [](int x, int y) { return static_cast<long>((static_cast<unsigned long long>(static_cast<unsigned>(y)) << 32) | static_cast<unsigned>(x)); };
+                    const long a1 = pack(fq[ks][0].x, fq[ks][0].y), a2 = pack(fq[ks][1].x, fq[ks][1].y);
+                    const long bh = pack(hi.x, hi.y), bl = pack(lo.x, lo.y);
+                    acc1 = __builtin_amdgcn_mfma_i32_32x32x16_i8(a1, bh, acc1, 0, 0, 0);
+                    acc2 = __builtin_amdgcn_mfma_i32_32x32x16_i8(a1, bl, acc2, 0, 0, 0);
+                    acc2 = __builtin_amdgcn_mfma_i32_32x32x16_i8(a2, bh, acc2, 0, 0, 0);
+                } else {
+                    acc1 = __builtin_amdgcn_mfma_i32_32x32x32_i8(fq[ks][0], hi, acc1, 0, 0, 0);
+                    acc2 = __builtin_amdgcn_mfma_i32_32x32x32_i8(fq[ks][0], lo, acc2, 0, 0, 0);
+                    acc2 = __builtin_amdgcn_mfma_i32_32x32x32_i8(fq[ks][1], hi, acc2, 0, 0, 0);
+                }
+            }
+            const unsigned p = static_cast<unsigned>(reinterpret_cast<size_t>((__attribute__((address_space(3))) const void *)(
+                s_acc + ((t * 64 + cp * 32 + col + 4 * h + 1) & 511) + (rt >> 1) * SH_AS + (rt & 1) * 32)));
+#pragma unroll
+            for (int q = 0; q < 16; ++q) {
+                const int comb = (acc1[q] << 8) + acc2[q];
+                asm volatile("ds_add_u32 %0, %1 offset:%2" ::"v"(p), "v"(comb), "n"(4 * ((q & 3) + 8 * (q >> 2))));
+            }
+        }
+        c1 = __builtin_amdgcn_s_memtime(), r1 = __builtin_amdgcn_s_memrealtime();
+    } else {
+        constexpr int NC = KS / 2;  // 64-value chunks; KS odd: one 32-value step behind them
+        const int r16 = lane & 15, g = lane >> 4;
+        v4i tq[NC][2][2];  // [chunk][tap-row half][piece]
+        long tl[2][2];     // the odd last k step
+#pragma unroll
+        for (int c = 0; c < NC; ++c)
+#pragma unroll
+            for (int bi = 0; bi < 2; ++bi)
+#pragma unroll
+                for (int pc = 0; pc < 2; ++pc) tq[c][bi][pc] = afrag[((2 * c + (g >> 1)) * 8 + rt * 2 + pc) * 64 + 16 * bi + r16 + 32 * (g & 1)];
+#pragma unroll
+        for (int bi = 0; bi < 2; ++bi)
+#pragma unroll
+            for (int pc = 0; pc < 2; ++pc)
+                tl[bi][pc] = reinterpret_cast<const long *>(afrag + ((KS - 1) * 8 + rt * 2 + pc) * 64 + 16 * bi + r16 + 32 * (g >> 1))[g & 1];
+        const char *la = slot + r16 * PP + 16 * g;
+        const char *lb = slot + r16 * PP + 32 * (KS - 1) + 8 * g;
+        const v4i zero4 = {0, 0, 0, 0};
+        c0 = __builtin_amdgcn_s_memtime(), r0 = __builtin_amdgcn_s_memrealtime();
+        for (int t = 0; t < tiles; ++t) {
+            asm volatile("s_barrier" ::: "memory");
+            v4i hh[NC][2], ll[NC][2];
+            long ho[2], lo[2];
+            v4i a1[3], a2[3];
+            auto fetch = [&](int c) {
+                if (c < NC) {
+#pragma unroll
+                    for (int bj = 0; bj < 2; ++bj) {
+                        hh[c][bj] = *reinterpret_cast<const v4i *>(la + 16 * PP * bj + 64 * c);
+                        ll[c][bj] = *reinterpret_cast<const v4i *>(la + 32 * PP + 16 * PP * bj + 64 * c);
+                    }
+                } else {
+#pragma unroll
+                    for (int bj = 0; bj < 2; ++bj) {
+                        ho[bj] = *reinterpret_cast<const long *>(lb + 16 * PP * bj);
+                        lo[bj] = *reinterpret_cast<const long *>(lb + 32 * PP + 16 * PP * bj);
+                    }
+                }
+            };
+            // the twelve products of a step; an accumulator's uses lie at least two instructions apart
+            auto step = [&](auto mf, const auto &q, const auto &hi, const auto &lw, bool first) {
+                a2[1] = mf(q[0][0], lw[1], first ? zero4 : a2[1]);
+                a1[0] = mf(q[0][0], hi[0], first ? zero4 : a1[0]);
+                a2[0] = mf(q[0][0], lw[0], first ? zero4 : a2[0]);
+                a2[1] = mf(q[1][0], lw[0], a2[1]);
+                a1[1] = mf(q[0][0], hi[1], first ? zero4 : a1[1]);
+                a1[2] = mf(q[1][0], hi[1], first ? zero4 : a1[2]);
+                a2[1] = mf(q[0][1], hi[1], a2[1]);
+                a2[2] = mf(q[1][0], lw[1], first ? zero4 : a2[2]);
+                a1[1] = mf(q[1][0], hi[0], a1[1]);
+                a2[1] = mf(q[1][1], hi[0], a2[1]);
+                a2[0] = mf(q[0][1], hi[0], a2[0]);
+                a2[2] = mf(q[1][1], hi[1], a2[2]);
+            };
+            auto mf64 = [](v4i x, v4i y, v4i z) { return __builtin_amdgcn_mfma_i32_16x16x64_i8(x, y, z, 0, 0, 0); };
+            auto mf32 = [](long x, long y, v4i z) { return __builtin_amdgcn_mfma_i32_16x16x32_i8(x, y, z, 0, 0, 0); };
+            fetch(0);
+#pragma unroll
+            for (int c = 0; c < NC; ++c) {
+                if (c + 1 < NC + (KS & 1)) fetch(c + 1);
+                step(mf64, tq[c], hh[c], ll[c], c == 0);
+            }
+            if (KS & 1) step(mf32, tl, ho, lo, NC == 0);
+            const unsigned p = static_cast<unsigned>(reinterpret_cast<size_t>((__attribute__((address_space(3))) const void *)(
+                s_acc + ((t * 64 + cp * 32 + (rt & 1) * 32 + r16 + 4 * g + 1) & 511) + (rt >> 1) * SH_AS)));
+#pragma unroll
+            for (int s = 0; s < 3; ++s)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int comb = (a1[s][r] << 8) + a2[s][r];
+                    asm volatile("ds_add_u32 %0, %1 offset:%2" ::"v"(p), "v"(comb), "n"(4 * (16 * s + r)));
+                }
+        }
+        c1 = __builtin_amdgcn_s_memtime(), r1 = __builtin_amdgcn_s_memrealtime();
+    }
+    if (lane == 0 && wave == 0) {
+        clk[2 * blockIdx.x] = c1 - c0;
+        clk[2 * blockIdx.x + 1] = r1 - r0;
+    }
+    // the window this block leaves, folded over the guard's aliases: equal for the two bodies
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (blockIdx.x == 0)
+        for (int i = tid; i < 1024; i += 768) {
+            const int s = i & 511, o = (i >> 9) * SH_AS;
+            win_out[i] = s_acc[o + s] + (s < 64 ? s_acc[o + 512 + s] : 0);
+        }
+}
+
+// bare issue rate of one MFMA form: one wave per SIMD, eight independent accumulators, cycles per instruction
+template <int FORM>  // 0: 32x32x32, 1: 32x32x16, 2: 16x16x64, 3: 16x16x32
+__global__ __launch_bounds__(256) void k_probe_rate(const v4i *taps, int *sink, int n, unsigned long long *clk)
+{
+    const int lane = threadIdx.x & 63;
+    const v4i x = taps[lane], y = taps[64 + lane];
+    const long xl = (static_cast<long>(x.y) << 32) | static_cast<unsigned>(x.x), yl = (static_cast<long>(y.y) << 32) | static_cast<unsigned>(y.x);
+    v16i b[4] = {};
+    v4i s[8] = {};
+    const unsigned long long c0 = __builtin_amdgcn_s_memtime();
+    for (int i = 0; i < n; ++i) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            // (inline asm: left to itself the compiler keeps these sums in accumulation registers and copies all of them
+            // to and fro in every iteration; an accumulator's next use is 4 or 8 instructions away, past every hazard)
+            if constexpr (FORM == 0) asm volatile("v_mfma_i32_32x32x32_i8 %0, %1, %2, %0" : "+v"(b[j & 3]) : "v"(x), "v"(y));
+            if constexpr (FORM == 1) asm volatile("v_mfma_i32_32x32x16_i8 %0, %1, %2, %0" : "+v"(b[j & 3]) : "v"(xl), "v"(yl));
+            if constexpr (FORM == 2) asm volatile("v_mfma_i32_16x16x64_i8 %0, %1, %2, %0" : "+v"(s[j]) : "v"(x), "v"(y));
+            if constexpr (FORM == 3) asm volatile("v_mfma_i32_16x16x32_i8 %0, %1, %2, %0" : "+v"(s[j]) : "v"(xl), "v"(yl));
+        }
+    }
+    asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");  // (the last results, before the VALU reads them)
+    const unsigned long long c1 = __builtin_amdgcn_s_memtime();
+    int acc = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+#pragma unroll
+        for (int q = 0; q < 16; ++q) acc += b[j][q];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) acc += s[j].x + s[j].y + s[j].z + s[j].w;
+    if (acc == 0x12345678) sink[0] = acc;
+    if (threadIdx.x == 0 && blockIdx.x == 0) clk[0] = c1 - c0;
+}
+
+template <int FORM>
+static void run_rate(const v4i *taps, int *sink, unsigned long long *clk)
+{
+    const int n = 100000;
+    for (int rep = 0; rep < 2; ++rep) hipLaunchKernelGGL((k_probe_rate<FORM>), dim3(256), dim3(256), 0, 0, taps, sink, n, clk);
+    unsigned long long h = 0;
+    hipMemcpy(&h, clk, 8, hipMemcpyDeviceToHost);
+    static const char *names[4] = {"v_mfma_i32_32x32x32_i8", "v_mfma_i32_32x32x16_i8", "v_mfma_i32_16x16x64_i8", "v_mfma_i32_16x16x32_i8"};
+    printf("%s: %.2f cycles per instruction, one wave per SIMD, back to back\n", names[FORM], double(h) / (8.0 * n));
+}
+
+// LDS access patterns of the two bodies, one per kernel name, for a counters-only run (SQ_LDS_BANK_CONFLICT,
+// SQ_LDS_IDX_ACTIVE, SQ_INSTS_LDS per dispatch): `kstep_probe lds`.
+//   KIND 0: ds_read_b128, lane l at row l & 15, unit l >> 4, rows P units apart (the 16x16x64 data operand)
+//   KIND 1: ds_read_b128, lane l at row l & 31, unit l >> 5, rows P units apart (the 32x32x32 data operand)
+//   KIND 2: ds_read_b64, lane l at row l & 15, 8 (l >> 4) bytes into the row (the 16x16x32 data operand)
+//   KIND 3: ds_add_u32 at position (l & 15) + 4 (l >> 4) (the 16x16 blocks' scatter); KIND 4: at (l & 31) + 4 (l >> 5)
+template <int KIND, int P>
+__global__ __launch_bounds__(64) void k_probe_lds(int *sink, int n)
+{
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int lane = threadIdx.x;
+    for (int i = lane; i < 4096; i += 64) reinterpret_cast<int *>(smem)[i] = i;
+    __syncthreads();
+    int off;
+    if (KIND == 0) off = (lane & 15) * P * 16 + 16 * (lane >> 4);
+    else if (KIND == 1) off = (lane & 31) * P * 16 + 16 * (lane >> 5);
+    else if (KIND == 2) off = (lane & 15) * P * 16 + 8 * (lane >> 4);
+    else if (KIND == 3) off = 4 * ((lane & 15) + 4 * (lane >> 4));
+    else off = 4 * ((lane & 31) + 4 * (lane >> 5));
+    const unsigned p = static_cast<unsigned>(reinterpret_cast<size_t>((__attribute__((address_space(3))) const void *)(smem + off)));
+    v4i v = {0, 0, 0, 0};
+    for (int i = 0; i < n; ++i) {
+        if (KIND <= 1) asm volatile("ds_read_b128 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(v) : "v"(p) : "memory");
+        else if (KIND == 2) asm volatile("ds_read_b64 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(*reinterpret_cast<long *>(&v)) : "v"(p) : "memory");
+        else asm volatile("ds_add_u32 %0, %1\n\ts_waitcnt lgkmcnt(0)" ::"v"(p), "v"(lane) : "memory");
+    }
+    if (v.x == 0x12345678) sink[0] = v.y;
+}
+
+template <int KIND, int P>
+static void run_lds(int *sink)
+{
+    hipLaunchKernelGGL((k_probe_lds<KIND, P>), dim3(256), dim3(64), 16384, 0, sink, 1000);
+    hipDeviceSynchronize();
+}
+
+static int lds_main()
+{
+    int *sink;
+    hipMalloc(&sink, 64);
+    run_lds<0, 13>(sink);
+    run_lds<0, 14>(sink);
+    run_lds<0, 15>(sink);
+    run_lds<0, 16>(sink);
+    run_lds<0, 18>(sink);
+    run_lds<1, 14>(sink);
+    run_lds<1, 15>(sink);
+    run_lds<2, 14>(sink);
+    run_lds<2, 15>(sink);
+    run_lds<3, 0>(sink);
+    run_lds<4, 0>(sink);
+    return 0;
+}
+
+struct ShapeResult {
+    double ns_per_round, ghz;
+    std::vector<int> win;
+};
+
+// `seconds` of back-to-back launches; the time and the in-kernel clock (median over workgroups) of the last batch
+template <int BODY>
+static ShapeResult run_shape(const v4i *afrag, int *win, unsigned long long *clk, int tiles, double seconds)
+{
+    using G = ShapeGeo<BODY>;
+    hipFuncSetAttribute(reinterpret_cast<const void *>(k_probe_shape<BODY>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    hipEvent_t e0, e1;
+    hipEventCreate(&e0);
+    hipEventCreate(&e1);
+    constexpr int BATCH = 8;
+    double total_ms = 0;
+    float ms = 0;
+    while (total_ms < seconds * 1e3) {
+        hipEventRecord(e0);
+        for (int i = 0; i < BATCH; ++i) hipLaunchKernelGGL((k_probe_shape<BODY>), dim3(256), dim3(768), G::LDS, 0, afrag, win, tiles, clk);
+        hipEventRecord(e1);
+        if (hipEventSynchronize(e1) != hipSuccess) {
+            printf("launch failed: %s\n", hipGetErrorString(hipGetLastError()));
+            exit(1);
+        }
+        hipEventElapsedTime(&ms, e0, e1);
+        total_ms += ms;
+    }
+    std::vector<unsigned long long> h(512);
+    hipMemcpy(h.data(), clk, 512 * 8, hipMemcpyDeviceToHost);
+    std::vector<double> ghz(256);
+    for (int i = 0; i < 256; ++i) ghz[i] = double(h[2 * i]) / double(h[2 * i + 1]) * 0.1;
+    std::sort(ghz.begin(), ghz.end());
+    ShapeResult r;
+    r.ns_per_round = ms * 1e6 / (double(BATCH) * tiles);
+    r.ghz = ghz[128];
+    r.win.resize(1024);
+    hipMemcpy(r.win.data(), win, 1024 * 4, hipMemcpyDeviceToHost);
+    hipEventDestroy(e0);
+    hipEventDestroy(e1);
+    return r;
+}
+
+// kstep_probe shape [seconds per run] [pairs]
+static int shape_main(double seconds, int pairs)
+{
+    const int tiles = 20000;
+    std::vector<signed char> ha(SH_KS * 8 * 64 * 16);
+    unsigned seed = 12345u;
+    for (int ks = 0; ks < SH_KS; ++ks)
+        for (int rp = 0; rp < 8; ++rp)
+            for (int l = 0; l < 64; ++l)
+                for (int j = 0; j < 16; ++j) {
+                    seed = seed * 1664525u + 1013904223u;
+                    const int k = 32 * ks + 16 * (l >> 5) + j;  // lane l holds tap row l & 31, values 16 (l >> 5) + j of the k step
+                    ha[((ks * 8 + rp) * 64 + l) * 16 + j] = k < 208 ? static_cast<signed char>(seed >> 24) : 0;
+                }
+    v4i *afrag;
+    int *win, *sink;
+    unsigned long long *clk;
+    hipMalloc(&afrag, ha.size());
+    hipMemcpy(afrag, ha.data(), ha.size(), hipMemcpyHostToDevice);
+    hipMalloc(&win, 1024 * 4);
+    hipMalloc(&sink, 64);
+    hipMalloc(&clk, 512 * 8);
+    run_rate<0>(afrag, sink, clk);
+    run_rate<1>(afrag, sink, clk);
+    run_rate<2>(afrag, sink, clk);
+    run_rate<3>(afrag, sink, clk);
+    int bad = 0;
+    for (int p = 0; p < pairs; ++p) {
+        const ShapeResult a = run_shape<0>(afrag, win, clk, tiles, seconds);
+        const ShapeResult b = run_shape<1>(afrag, win, clk, tiles, seconds);
+        int diff = 0;
+        for (int i = 0; i < 1024; ++i) diff += a.win[i] != b.win[i];
+        bad += diff;
+        printf("pair %d: 32x32x32 body %.1f ns per round (two tiles per SIMD pair of waves) at %.3f GHz; 16x16x64 body %.1f ns at %.3f GHz; ratio %.4f; "
+               "windows differ in %d of 1024 sums (first %d)\n",
+               p, a.ns_per_round, a.ghz, b.ns_per_round, b.ghz, b.ns_per_round / a.ns_per_round, diff, a.win[7]);
+    }
+    return bad ? 1 : 0;
+}
+
 int main(int argc, char **argv)
 {
+    if (argc > 1 && std::string(argv[1]) == "lds") return lds_main();
+    if (argc > 1 && std::string(argv[1]) == "shape") return shape_main(argc > 2 ? atof(argv[2]) : 2.0, argc > 3 ? atoi(argv[3]) : 4);
     const int tiles = argc > 1 ? atoi(argv[1]) : 20000;
     v4i *taps;
     int *sink;
