@@ -837,6 +837,38 @@ int iqa_keying_accumulate(const void *theta_dev, int64_t n, int64_t pos, const v
                           const void *gate_dev, void *rows_dev, void *stream);
 
 /* ------------------------------------------------------------------------- *
+ * The protocol of a keyed channel (--find-identify)    *
+ * ------------------------------------------------------------------------- */
+
+#define IQA_IDENT_MIN_SPS 4        /* samples to a symbol, and the integrator's window L = rint(sps) */
+#define IQA_IDENT_MAX_SPS 224
+#define IQA_IDENT_OFFSETS 64       /* o[i] = rint(i sps), i = -16 .. 47, o[i] at index 16 + i */
+#define IQA_IDENT_MAX_SYMBOLS 32   /* symbols of a sync pattern */
+#define IQA_IDENT_MAX_PATTERNS 8   /* patterns of one search */
+#define IQA_IDENT_RECORD 6         /* int64 values of a kept hit: pattern, m, C, E, pre, post */
+/* The symbol-long integrator of a stored discriminator stream.  theta_dev: float32[n], index 0 the first stored sample; in
+ * front of it t - c reads as 0.  t = clamp(rintf(theta 4096), -32767, 32767) (float32, half-even; NaN reads as 0, +-inf as
+ * +-32767); S[m] = sum over j < L, j <= m of (t[m - j] - c) in int32, c the centre, |c| <= 32767; v_dev[m] = S[m] >> sh
+ * (int32[n], an arithmetic shift).  IQA_IDENT_MIN_SPS <= L <= IQA_IDENT_MAX_SPS, 0 <= sh <= 8 with (L 65534) >> sh <=
+ * 64 * 65534, so |v| <= 64 * 65534.  n <= 2^30.  n = 0 returns IQA_OK and touches no pointer. */
+int iqa_ident_integrate(const void *theta_dev, int64_t n, int32_t L, int32_t sh, int32_t c, void *v_dev, void *stream);
+/* The frame synchronisation words of one family in v_dev (int32[n], |v| <= 64 * 65534: iqa_ident_integrate's output).
+ * offsets (host): IQA_IDENT_OFFSETS sample offsets o[-16] .. o[47], ascending in steps of at most IQA_IDENT_MAX_SPS + 1, o[0]
+ * (index 16) = 0.  symbols (host): int8[npat][IQA_IDENT_MAX_SYMBOLS], pattern p's first nsym[p] entries each -3, -1, +1 or
+ * +3; 1 <= npat <= IQA_IDENT_MAX_PATTERNS, 1 <= nsym[p] <= IQA_IDENT_MAX_SYMBOLS, o[nsym[p] - 1] <= 31 IQA_IDENT_MAX_SPS.
+ * At every m with m + o[N - 1] < n: C = sum p_i v[m + o[i]], E = sum v[m + o[i]]^2 (int64), Pn = sum p_i^2; m is a candidate
+ * of p iff E > 0 and 16 C^2 >= 13 Pn E.  score_dev (int32[npat][n]) receives 2 |C| + (C < 0) for a candidate and 0 for every
+ * other m.  A candidate is kept iff no candidate of the same pattern within +-half has a larger |C|, or the same |C| at a
+ * smaller index (0 <= half <= IQA_IDENT_MAX_SPS).  A kept hit appends IQA_IDENT_RECORD int64 to list_dev
+ * (int64[capacity][6]) in no particular order: p, m, C, E, pre, post; bit k of pre = (v[m + o[-16 + k]] > 0) and of post =
+ * (v[m + o[N + k]] > 0), k = 0 .. 15, 0 where the position lies outside 0 .. n - 1.  count_dev (int64[1]) is cleared and
+ * then counts every kept hit, also those past the capacity: a caller that reads count > capacity repeats the call with
+ * room for all.  n <= 2^30.  n = 0 returns IQA_OK and touches no pointer (the count stays as it is). */
+int iqa_ident_search(const void *v_dev, int64_t n, const int32_t offsets[IQA_IDENT_OFFSETS], int32_t npat, const int8_t *symbols,
+                     const int32_t *nsym, int32_t half, void *score_dev, void *list_dev, int64_t capacity, void *count_dev,
+                     void *stream);
+
+/* ------------------------------------------------------------------------- *
  * Carrier squelch of a run's targets (--squelch)       *
  * ------------------------------------------------------------------------- */
 

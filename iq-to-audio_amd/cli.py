@@ -161,6 +161,10 @@ def build_parser() -> argparse.ArgumentParser:
                    help="Find and describe the channels and measure the keying of each one: whether its discriminator switches on "
                         "a symbol clock (fsk 512 ... 9600) and which side decoders fit it.  With --find-top N --find-auto every "
                         "target runs with its chosen decoders.  Implies --find-describe.")
+    p.add_argument("--find-identify", dest="find_identify", action="store_true",
+                   help="Find, describe and key the channels, and name the protocol of every channel keyed at 1600, 2400, 3200 or "
+                        "4800 baud by its frame synchronisation words: DMR, P25, YSF, NXDN or FLEX with its mode.  Implies "
+                        "--find-decode.")
     p.add_argument("--find-auto", dest="find_auto", action="store_true",
                    help="With --find-top N: take the N strongest channels whose label is known and run each with its own "
                         "suggested --demod, --bw and frequency.")
@@ -231,10 +235,12 @@ def check_find_args(parser, args) -> bool:
     given = [flag for flag, value in (("--find-channels", args.find_channels or None), ("--find-top", args.find_top),
                                       ("--find-grid", args.find_grid), ("--find-threshold", args.find_threshold),
                                       ("--find-describe", args.find_describe or None), ("--find-auto", args.find_auto or None),
-                                      ("--find-decode", args.find_decode or None))
+                                      ("--find-decode", args.find_decode or None), ("--find-identify", args.find_identify or None))
              if value is not None]
     if not given:
         return False
+    if args.find_identify:
+        args.find_decode = True
     for flag, value in (("--ft", args.target_freqs), ("--benchmark", args.benchmark), ("--audio-post", args.audio_post_path),
                         ("--probe-only", args.probe_only)):
         if value:
@@ -285,8 +291,8 @@ def check_squelch_args(parser, args, finding: bool) -> CarrierSquelch | None:
 
 
 def run_find(args, codec, container):
-    """``--find-channels`` / ``--find-describe`` / ``--find-top``: print and store the capture's channels and, where asked for,
-    their descriptions.  Returns (exit code or ``None`` to go on, the targets of the run that follows: frequencies, or with
+    """``--find-channels`` / ``--find-describe`` / ``--find-decode`` / ``--find-identify`` / ``--find-top``: print and store the
+    capture's channels and, where asked for, their descriptions, keying and protocols.  Returns (exit code or ``None`` to go on, the targets of the run that follows: frequencies, or with
     ``--find-auto`` (frequency, demod, bw) each, and with ``--find-decode`` beside it (frequency, demod, bw, side decoders))."""
     from .find import find_channels, select_targets
 
@@ -296,12 +302,16 @@ def run_find(args, codec, container):
         options["describe"] = True
     if args.find_decode:
         options.update(keying=True, fs_ch=getattr(args, "find_fs_ch", None))
-    described = keyed = None
+    if args.find_identify:
+        options["identify"] = True
+    described = keyed = named = None
     try:
         result = find_channels(args.input_path, center_freq=args.center_freq, input_format=codec, input_container=container,
                                input_sample_rate=args.input_sample_rate, iq_order=args.iq_order, max_seconds=args.preview_seconds,
                                **options)
-        if args.find_decode:
+        if args.find_identify:
+            result, described, keyed, named = result
+        elif args.find_decode:
             result, described, keyed = result
         elif describing:
             result, described = result
@@ -315,16 +325,21 @@ def run_find(args, codec, container):
             print(line)
     else:
         under = keyed.lines() if keyed is not None else [None] * len(result.channels)
-        for line, about, keying in zip(result.lines(), described.lines(), under):
+        third = named.lines() if named is not None else [None] * len(result.channels)
+        for line, about, keying, protocol in zip(result.lines(), described.lines(), under, third):
             print(line)
             print(about)
             if keying is not None:
                 print(keying)
+            if protocol is not None:
+                print(protocol)
     args.input_path.with_name(f"{args.input_path.stem}.channels.json").write_text(json.dumps(result.to_json(), indent=1) + "\n")
     if described is not None:
         args.input_path.with_name(f"{args.input_path.stem}.describe.json").write_text(json.dumps(described.to_json(), indent=1) + "\n")
     if keyed is not None:
         args.input_path.with_name(f"{args.input_path.stem}.keying.json").write_text(json.dumps(keyed.to_json(), indent=1) + "\n")
+    if named is not None:
+        args.input_path.with_name(f"{args.input_path.stem}.protocols.json").write_text(json.dumps(named.to_json(), indent=1) + "\n")
     if args.find_top is None:
         return 0, []
     if not result.channels:

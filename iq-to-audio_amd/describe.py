@@ -12,7 +12,11 @@ library the calls raise ``RuntimeError``.
 With ``keying=True`` (``--find-decode``) the same pass also measures whether each channel's discriminator
 switches on a symbol clock: ``iqa_quadrature`` and ``iqa_keying_accumulate`` give, per window of 2048 samples, the gated pairs,
 the level crossings and the crossings' clock-phase sums at seven candidate bauds.  Fixed rules turn them into ``fsk <baud>`` or
-``unkeyed`` and into the side decoders a target of that channel runs with."""
+``unkeyed`` and into the side decoders a target of that channel runs with.
+
+With ``identify=True`` beside it (``--find-identify``) the pass keeps every channel's discriminator output
+from the keyed-from block on, and ``finish_identify`` searches the channels labelled ``fsk 1600 | 2400 | 3200 | 4800`` for the
+frame synchronisation words of their family (``identify.py``)."""
 from __future__ import annotations
 
 import logging
@@ -453,6 +457,7 @@ class _Lane:
         self.keyed_from = None  # the stream position of the first keyed sample
         self.krows: list = []  # (first window, device rows) per call
         self.theta: list = []
+        self.stored: list = []  # identify (section 25): the theta of every block from the keyed-from one on
 
 
 class ChannelDescriber:
@@ -461,11 +466,14 @@ class ChannelDescriber:
     ``fin`` is ``ChannelFinder.finish()`` of the same capture and ``channels`` the ``FoundChannel``s made from it."""
 
     def __init__(self, find_plan: P.FindPlan, fin: dict, channels, fmt: str = "s16", iq_order: str = "iq", *, keep_stages: bool = False,
-                 keying: bool = False):
+                 keying: bool = False, identify: bool = False):
         if fmt not in _RAW_DTYPE:
             raise ValueError(f"Unsupported sample format '{fmt}'")
         if iq_order not in N.ORDER:
             raise ValueError(f"Unsupported iq_order '{iq_order}'")
+        if identify and not keying:
+            raise ValueError("identify=True needs keying=True")
+        self._identify = bool(identify)
         self.find_plan, self.fin, self.channels = find_plan, fin, list(channels)
         self.fmt, self.iq_order, self._keep, self._keying = fmt, iq_order, keep_stages, bool(keying)
         by_lo = {int(rec[0]): j for j, rec in enumerate(np.asarray(fin["runs"]).reshape(-1, 8))}
@@ -487,6 +495,8 @@ class ChannelDescriber:
         self.samples_seen = 0
         self._fin = None
         self._kfin = None
+        self._ifin = None
+        self._keyed: dict = {}  # identify: the last ``keying()`` per centre frequency, so that the protocols do not key again
 
     def _start(self) -> None:
         from .channelizer import ChannelBank, Channelizer
@@ -519,7 +529,8 @@ class ChannelDescriber:
             raise ValueError(f"the plan was made for {self.find_plan.n_samples} samples and the stream is longer")
         if self._lanes is None:
             self._start()
-        self._fin = self._kfin = None
+        self._fin = self._kfin = self._ifin = None
+        self._keyed = {}
         for bank, lanes in self._groups:
             zs = bank.process(x) if bank is not None else [lanes[0].chan.process(x)]
             for lane, z in zip(lanes, zs):
@@ -558,6 +569,8 @@ class ChannelDescriber:
                 lane.keyed_from = lane.pos
             lane.krows.append(accumulate_keying(theta, lane.pos, lane.front if lane.pos >= 1 else None, lane.centre, lane.kplan,
                                                 self._table, lane.plan, self.find_plan, lane.gate_dev))
+            if self._identify:
+                lane.stored.append(theta)
         lane.front = theta[n - 1 :].clone()
         if self._keep:
             lane.theta.append(theta)
@@ -607,8 +620,52 @@ class ChannelDescriber:
         """The ``ChannelKeying`` of every channel, in channel order.  ``fs_ch``: an explicit ``--fs-ch`` of the targets."""
         rows = self.finish_keying()
         described = self.result(center_freq)
-        return [key_channel(d, lane.kplan, r, lane.centre, self.find_plan.fs, fs_ch)
-                for d, lane, r in zip(described.channels, self.lanes(), rows)]
+        out = [key_channel(d, lane.kplan, r, lane.centre, self.find_plan.fs, fs_ch)
+               for d, lane, r in zip(described.channels, self.lanes(), rows)]
+        if self._identify:
+            self._keyed[center_freq] = list(out)
+        return out
+
+    def finish_identify(self) -> list:
+        """Per channel a dict of its identification: ``rate`` (R, None where the channel is not one to
+        identify), ``plan`` (the ``IdentPlan``, None where the rate does not fit), ``note``, ``hits`` (int64[K][6], the kept sync
+        words sorted by (pattern, m), m counted from ``keyed_from``; None where nothing was searched) and, with ``keep_stages``,
+        ``v`` and ``score`` (device tensors).  The whole search runs here, on the stored stream as one piece."""
+        from . import identify as I
+
+        if not self._identify:
+            raise ValueError("the describer was made without identify=True")
+        if self._ifin is None:
+            torch = D.torch_mod()
+            out = []
+            # (label and baud depend neither on the centre frequency nor on the targets' rate: any keying of this pass will do)
+            for lane, keyed in zip(self.lanes(), next(iter(self._keyed.values())) if self._keyed else self.keying()):
+                rate, plan, note = I.family_plan(keyed.label, keyed.baud if keyed.label is not None else None, lane.plan.fs_ch)
+                d = dict(rate=rate, plan=plan, note=note, hits=None)
+                if plan is not None and lane.centre is not None and lane.stored:
+                    theta = lane.stored[0] if len(lane.stored) == 1 else torch.cat(lane.stored)
+                    if int(theta.numel()) > P.IDENT_MAX_N:
+                        raise ValueError(f"a stored stream of {int(theta.numel())} samples is longer than 2^30")
+                    v = I.integrate(theta, plan, lane.centre)
+                    score, d["hits"] = I.search(v, plan, I.patterns_for(rate))
+                    if self._keep:
+                        d.update(v=v, score=score)
+                out.append(d)
+            self._ifin = out
+        return self._ifin
+
+    def protocols(self, center_freq: float | None = None) -> list:
+        """The ``ChannelProtocol`` of every channel, in channel order."""
+        from . import identify as I
+
+        found = self.finish_identify()
+        return [I.protocol_of(keyed, d["hits"], d["plan"], d["rate"], d["note"], lane.keyed_from)
+                for keyed, d, lane in zip(self._keyed.get(center_freq) or self.keying(center_freq), found, self.lanes())]
+
+    def protocol_result(self, center_freq: float | None = None):
+        from . import identify as I
+
+        return I.ProtocolResult(channels=self.protocols(center_freq), sample_rate=self.find_plan.fs, center_freq=center_freq)
 
     def keying_result(self, center_freq: float | None = None, fs_ch: float | None = None) -> KeyingResult:
         return KeyingResult(channels=self.keying(center_freq, fs_ch), sample_rate=self.find_plan.fs, center_freq=center_freq)
@@ -624,7 +681,9 @@ class ChannelDescriber:
         ``rows`` (int64[tiles of every call][8]).  With ``keying``: ``c`` (the centre or None), ``keyed_from`` (the position of the
         first keyed sample), ``keying_rows`` (int64[windows][16], added by window number, or None) and, with ``keep_stages``,
         ``theta`` (float32, the whole discriminator output), ``keying_parts`` ((first window, int32[k][16]) per call) and
-        ``calls`` (the samples of every feed)."""
+        ``calls`` (the samples of every feed).  With ``identify``: ``ident_rate``, ``ident_plan``, ``hits`` (int64[K][6] or None) and,
+        with ``keep_stages``, ``v`` (int32[n]) and ``score`` (int32[patterns][n]) of the identified channels, ``stored`` (float32,
+        the stored theta: ``theta`` from ``keyed_from`` on)."""
         sums = self.finish()
         torch = D.torch_mod()
         out = []
@@ -636,6 +695,13 @@ class ChannelDescriber:
                 if self._keep:
                     d["theta"] = torch.cat(lane.theta).cpu().numpy() if lane.theta else np.zeros(0, dtype=np.float32)
                     d["keying_parts"] = [(first, rows.cpu().numpy().reshape(-1, P.KEYING_SUMS)) for first, rows in lane.krows]
+            if self._identify:
+                i = self.finish_identify()[j]
+                d.update(ident_rate=i["rate"], ident_plan=i["plan"], hits=i["hits"])
+                if self._keep:
+                    d["stored"] = torch.cat(lane.stored).cpu().numpy() if lane.stored else np.zeros(0, dtype=np.float32)
+                    if "v" in i:
+                        d.update(v=i["v"].cpu().numpy(), score=i["score"].cpu().numpy())
             if self._keep:
                 d["calls"] = list(lane.calls)
             if self._keep:

@@ -994,6 +994,45 @@ def plan_keying(fs_ch: float) -> KeyingPlan:
     return KeyingPlan(fs_ch=fs_ch, bauds=KEYING_BAUDS, incs=incs, skipped=skipped, table=keying_table())
 
 
+# ---- protocol identification plan (--find-identify) -------------------------
+
+IDENT_MIN_SPS, IDENT_MAX_SPS = 4.0, 224.0  # samples to a symbol
+IDENT_LEAD = 16  # o[i] sits at index 16 + i of ``offsets``: i = -16 .. 47
+IDENT_OFFSETS = 64
+IDENT_MAX_SYMBOLS = 32
+IDENT_MAX_N = 1 << 30  # samples of one stored stream
+IDENT_RECORD = 6  # int64 values of a kept hit: pattern, m, C, E, pre, post
+
+
+@dataclass(frozen=True)
+class IdentPlan:
+    fs_ch: float
+    rate: int  # R: the family's symbol rate
+    sps: float  # fs_ch / R
+    window: int  # L = rint(sps)
+    half: int  # h = floor(sps / 2)
+    shift: int  # sh = max(0, bit_length(L - 1) - 6)
+    offsets: tuple  # o[i] = rint(i sps), i = -16 .. 47 (half-even, float64)
+
+    def o(self, i: int) -> int:
+        return self.offsets[IDENT_LEAD + i]
+
+
+def plan_ident(fs_ch: float, rate: int) -> IdentPlan:
+    """The integrator's window and the sample offsets of the symbols of a family of ``rate`` symbols/s at the channel rate
+    ``fs_ch``.  ``ValueError`` unless 4 <= sps <= 224."""
+    fs_ch, rate = float(fs_ch), int(rate)
+    if not math.isfinite(fs_ch) or fs_ch <= 0.0 or rate <= 0:
+        raise ValueError("the channel rate and the symbol rate must be positive")
+    sps = fs_ch / rate
+    if not IDENT_MIN_SPS <= sps <= IDENT_MAX_SPS:
+        raise ValueError(f"{sps:.2f} samples to a symbol at {fs_ch:.0f} Hz and {rate} symbols/s: must be 4 .. 224")
+    window = int(np.rint(sps))
+    offsets = tuple(int(np.rint(i * sps)) for i in range(-IDENT_LEAD, IDENT_OFFSETS - IDENT_LEAD))
+    return IdentPlan(fs_ch=fs_ch, rate=rate, sps=sps, window=window, half=int(math.floor(sps / 2.0)),
+                     shift=max(0, (window - 1).bit_length() - 6), offsets=offsets)
+
+
 # ---- carrier squelch plan (--squelch; DESIGN.md section 24) --------------------------------------
 
 GATE_CELL = 256  # IQA_GATE_CELL: samples to a cell, counted on the absolute position

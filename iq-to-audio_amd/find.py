@@ -256,15 +256,20 @@ class ChannelFinder:
 
 def find_channels(path, *, center_freq: float | None = None, input_format: str | None = None, input_container: str | None = None,
                   input_sample_rate: float | None = None, iq_order: str = "iq", max_seconds: float | None = None,
-                  describe: bool = False, keying: bool = False, fs_ch: float | None = None, **plan_options):
+                  describe: bool = False, keying: bool = False, identify: bool = False, fs_ch: float | None = None,
+                  **plan_options):
     """The occupied channels of the capture at ``path`` (``plan_options``: the keywords of ``dsp_plan.plan_find``).  The centre
     frequency is taken from the file name where it is not given; without one the channels carry offsets only.  ``describe``:
     a second pass over the mapped file measures every channel (``describe.ChannelDescriber``) and the
     call returns ``(FindResult, DescribeResult)``.  ``keying`` (with ``describe``): the same pass also measures every channel's
     keying and chooses its side decoders (``fs_ch``: an explicit channel rate of the targets that follow),
-    and the call returns ``(FindResult, DescribeResult, KeyingResult)``."""
+    and the call returns ``(FindResult, DescribeResult, KeyingResult)``.  ``identify`` (with ``keying``): the keyed channels of
+    the usual digital rates are searched for their frame synchronisation words, and the call returns a
+    fourth result, ``ProtocolResult``."""
     if keying and not describe:
         raise ValueError("keying=True needs describe=True")
+    if identify and not keying:
+        raise ValueError("identify=True needs keying=True")
     path = Path(path)
     info = iqio.probe_capture(path, input_format=input_format, input_container=input_container, input_sample_rate=input_sample_rate)
     if not info.sample_rate:
@@ -286,9 +291,12 @@ def find_channels(path, *, center_freq: float | None = None, input_format: str |
         return result
     from .describe import ChannelDescriber
 
-    describer = ChannelDescriber(plan, finder.finish(), result.channels, info.fmt, iq_order, keying=keying)
+    describer = ChannelDescriber(plan, finder.finish(), result.channels, info.fmt, iq_order, keying=keying, identify=identify)
     for a in range(0, n, BLOCK_FRAMES):
         describer.process(np.ascontiguousarray(values[2 * a : 2 * min(n, a + BLOCK_FRAMES)]))
+    if identify:
+        return (result, describer.result(center_freq), describer.keying_result(center_freq, fs_ch),
+                describer.protocol_result(center_freq))
     if keying:
         return result, describer.result(center_freq), describer.keying_result(center_freq, fs_ch)
     return result, describer.result(center_freq)
