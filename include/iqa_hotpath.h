@@ -869,6 +869,42 @@ int iqa_ident_search(const void *v_dev, int64_t n, const int32_t offsets[IQA_IDE
                      void *stream);
 
 /* ------------------------------------------------------------------------- *
+ * The pages of a FLEX channel (--find-flex)            *
+ * ------------------------------------------------------------------------- */
+
+#define IQA_FLEX_HEADER_OFFSETS 112 /* o16[i] = rint(i sps), i = -16 .. 95, o16[i] at index 16 + i */
+#define IQA_FLEX_BLOCKS 11          /* data blocks of a frame */
+#define IQA_FLEX_SHIFTS 5           /* timing shifts of a block: (e - 2) step, e = 0 .. 4 */
+#define IQA_FLEX_PHASES 4           /* A, B, C, D */
+#define IQA_FLEX_WORDS 88           /* words of a phase in a frame */
+#define IQA_FLEX_SYMBOLS 2816       /* data symbols of a frame at 1600 symbols/s; twice as many at 3200 */
+#define IQA_FLEX_MAX_STEP 28        /* floor(IQA_IDENT_MAX_SPS / 8) */
+/* The levels and the frame information word of K sync-1 hits.  plane_dev: int32[n], iqa_ident_integrate's output (|v| <=
+ * 64 * 65534).  hits_dev: int64[K][2], (m, s): m where bit 0 of the marker 0xA6C6AAAA ends, s the sign of the hit (negative:
+ * -1, else +1).  offsets16 (host): the IQA_FLEX_HEADER_OFFSETS sample offsets of the 1600 bit/s grid, ascending in steps of at
+ * most IQA_IDENT_MAX_SPS + 1, o16[0] (index 16) = 0.  out_dev: int64[K][6] per hit: Sigma = sum of x_i = s plane[m + o16[i]]
+ * over i = 0 .. 31; A = sum of p_i x_i, p_i the marker's bit i (MSB first) as +-1; the frame information word W as sliced, bit j
+ * of it (32 s plane[m + o16[64 + j]] - Sigma > 0); W after the codeword rule; the status; the valid flag.  The codeword rule:
+ * W with its bits reversed is a BCH(31,21) codeword of g = 0x769 with even parity over 32 bits; status 0 clean, 1 one bit
+ * restored, 2 refused (the raw word kept), 3 an instant of bits 64 .. 95 outside 0 .. n - 1 (both words 0).  valid is 0, with
+ * Sigma = A = 0 and status 3, where an instant of bits 0 .. 31 lies outside the stream.  n <= 2^30, K <= 2^20.  n = 0 or K = 0
+ * returns IQA_OK and touches no pointer. */
+int iqa_flex_frames(const void *plane_dev, int64_t n, const void *hits_dev, int64_t K,
+                    const int32_t offsets16[IQA_FLEX_HEADER_OFFSETS], void *out_dev, void *stream);
+/* The words of F frames of one mode at five timing shifts.  frames_dev: int64[F][4], (m, s, Sigma, A) of the plane read here.
+ * levels 2 or 4; u = 1 (1600 symbols/s) or 2 (3200); offsets_dev: int32[IQA_FLEX_SYMBOLS u] on the device, data symbol q ending
+ * at m + offsets[q]; 1 <= step <= IQA_FLEX_MAX_STEP.  At shift e = 0 .. 4 every instant moves by (e - 2) step.  y = s
+ * plane[instant], d = 32 y - Sigma: bit_a = (d > 0), bit_b = (3 |d| < 2 A) (4 levels only).  With per = 256 u: block b = q / per,
+ * r = q % per, k = r / u, pair = r % u; pair 0 feeds phase A with bit_a and phase B with bit_b, pair 1 phases C and D; bit k of
+ * a block and phase is bit k / 8 of word 8 b + k % 8.  fixed_dev, raw_dev (uint32) and status_dev (uint8), each
+ * [F][IQA_FLEX_SHIFTS][IQA_FLEX_PHASES][IQA_FLEX_WORDS]: the word after the codeword rule of iqa_flex_frames, as sliced, and
+ * its status 0 .. 3 (3: an instant of the word outside 0 .. n - 1, both words 0); a phase that the mode does not send (B and D
+ * at 2 levels, C and D at u = 1) reads 0, 0 and status 4.  Every instant is checked against 0 .. n - 1 before it is read.
+ * n <= 2^30, F <= 2^20.  n = 0 or F = 0 returns IQA_OK and touches no pointer. */
+int iqa_flex_words(const void *plane_dev, int64_t n, const void *frames_dev, int64_t F, int32_t levels, int32_t u, int32_t step,
+                   const void *offsets_dev, void *fixed_dev, void *raw_dev, void *status_dev, void *stream);
+
+/* ------------------------------------------------------------------------- *
  * Carrier squelch of a run's targets (--squelch)       *
  * ------------------------------------------------------------------------- */
 

@@ -165,6 +165,9 @@ def build_parser() -> argparse.ArgumentParser:
                    help="Find, describe and key the channels, and name the protocol of every channel keyed at 1600, 2400, 3200 or "
                         "4800 baud by its frame synchronisation words: DMR, P25, YSF, NXDN or FLEX with its mode.  Implies "
                         "--find-decode.")
+    p.add_argument("--find-flex", dest="find_flex", action="store_true",
+                   help="Find, describe, key and identify the channels, and decode the pages of every FLEX channel: capcode, type "
+                        "and text, one line per page, also written to <capture stem>.flex.json.  Implies --find-identify.")
     p.add_argument("--find-auto", dest="find_auto", action="store_true",
                    help="With --find-top N: take the N strongest channels whose label is known and run each with its own "
                         "suggested --demod, --bw and frequency.")
@@ -235,10 +238,12 @@ def check_find_args(parser, args) -> bool:
     given = [flag for flag, value in (("--find-channels", args.find_channels or None), ("--find-top", args.find_top),
                                       ("--find-grid", args.find_grid), ("--find-threshold", args.find_threshold),
                                       ("--find-describe", args.find_describe or None), ("--find-auto", args.find_auto or None),
-                                      ("--find-decode", args.find_decode or None), ("--find-identify", args.find_identify or None))
+                                      ("--find-decode", args.find_decode or None), ("--find-identify", args.find_identify or None), ("--find-flex", args.find_flex or None))
              if value is not None]
     if not given:
         return False
+    if args.find_flex:
+        args.find_identify = True
     if args.find_identify:
         args.find_decode = True
     for flag, value in (("--ft", args.target_freqs), ("--benchmark", args.benchmark), ("--audio-post", args.audio_post_path),
@@ -291,7 +296,7 @@ def check_squelch_args(parser, args, finding: bool) -> CarrierSquelch | None:
 
 
 def run_find(args, codec, container):
-    """``--find-channels`` / ``--find-describe`` / ``--find-decode`` / ``--find-identify`` / ``--find-top``: print and store the
+    """``--find-channels`` / ``--find-describe`` / ``--find-decode`` / ``--find-identify`` / ``--find-flex`` / ``--find-top``: print and store the
     capture's channels and, where asked for, their descriptions, keying and protocols.  Returns (exit code or ``None`` to go on, the targets of the run that follows: frequencies, or with
     ``--find-auto`` (frequency, demod, bw) each, and with ``--find-decode`` beside it (frequency, demod, bw, side decoders))."""
     from .find import find_channels, select_targets
@@ -304,12 +309,16 @@ def run_find(args, codec, container):
         options.update(keying=True, fs_ch=getattr(args, "find_fs_ch", None))
     if args.find_identify:
         options["identify"] = True
-    described = keyed = named = None
+    if args.find_flex:
+        options["flex"] = True
+    described = keyed = named = paged = None
     try:
         result = find_channels(args.input_path, center_freq=args.center_freq, input_format=codec, input_container=container,
                                input_sample_rate=args.input_sample_rate, iq_order=args.iq_order, max_seconds=args.preview_seconds,
                                **options)
-        if args.find_identify:
+        if args.find_flex:
+            result, described, keyed, named, paged = result
+        elif args.find_identify:
             result, described, keyed, named = result
         elif args.find_decode:
             result, described, keyed = result
@@ -340,6 +349,10 @@ def run_find(args, codec, container):
         args.input_path.with_name(f"{args.input_path.stem}.keying.json").write_text(json.dumps(keyed.to_json(), indent=1) + "\n")
     if named is not None:
         args.input_path.with_name(f"{args.input_path.stem}.protocols.json").write_text(json.dumps(named.to_json(), indent=1) + "\n")
+    if paged is not None:
+        for line in paged.lines():
+            print(line)
+        args.input_path.with_name(f"{args.input_path.stem}.flex.json").write_text(json.dumps(paged.to_json(), indent=1) + "\n")
     if args.find_top is None:
         return 0, []
     if not result.channels:

@@ -16,7 +16,8 @@ the level crossings and the crossings' clock-phase sums at seven candidate bauds
 
 With ``identify=True`` beside it (``--find-identify``) the pass keeps every channel's discriminator output
 from the keyed-from block on, and ``finish_identify`` searches the channels labelled ``fsk 1600 | 2400 | 3200 | 4800`` for the
-frame synchronisation words of their family (``identify.py``)."""
+frame synchronisation words of their family (``identify.py``).  With ``flex=True`` beside that (``--find-flex``, DESIGN.md section
+26) ``finish_flex`` decodes the pages behind the FLEX sync words among those hits (``flex.py``)."""
 from __future__ import annotations
 
 import logging
@@ -466,14 +467,16 @@ class ChannelDescriber:
     ``fin`` is ``ChannelFinder.finish()`` of the same capture and ``channels`` the ``FoundChannel``s made from it."""
 
     def __init__(self, find_plan: P.FindPlan, fin: dict, channels, fmt: str = "s16", iq_order: str = "iq", *, keep_stages: bool = False,
-                 keying: bool = False, identify: bool = False):
+                 keying: bool = False, identify: bool = False, flex: bool = False):
         if fmt not in _RAW_DTYPE:
             raise ValueError(f"Unsupported sample format '{fmt}'")
         if iq_order not in N.ORDER:
             raise ValueError(f"Unsupported iq_order '{iq_order}'")
         if identify and not keying:
             raise ValueError("identify=True needs keying=True")
-        self._identify = bool(identify)
+        if flex and not identify:
+            raise ValueError("flex=True needs identify=True")
+        self._identify, self._flex = bool(identify), bool(flex)
         self.find_plan, self.fin, self.channels = find_plan, fin, list(channels)
         self.fmt, self.iq_order, self._keep, self._keying = fmt, iq_order, keep_stages, bool(keying)
         by_lo = {int(rec[0]): j for j, rec in enumerate(np.asarray(fin["runs"]).reshape(-1, 8))}
@@ -496,6 +499,7 @@ class ChannelDescriber:
         self._fin = None
         self._kfin = None
         self._ifin = None
+        self._xfin = None
         self._keyed: dict = {}  # identify: the last ``keying()`` per centre frequency, so that the protocols do not key again
 
     def _start(self) -> None:
@@ -529,7 +533,7 @@ class ChannelDescriber:
             raise ValueError(f"the plan was made for {self.find_plan.n_samples} samples and the stream is longer")
         if self._lanes is None:
             self._start()
-        self._fin = self._kfin = self._ifin = None
+        self._fin = self._kfin = self._ifin = self._xfin = None
         self._keyed = {}
         for bank, lanes in self._groups:
             zs = bank.process(x) if bank is not None else [lanes[0].chan.process(x)]
@@ -650,9 +654,53 @@ class ChannelDescriber:
                     score, d["hits"] = I.search(v, plan, I.patterns_for(rate))
                     if self._keep:
                         d.update(v=v, score=score)
+                    if self._flex and rate == 1600:
+                        d["flex_v"] = v  # (section 26 reads the same plane)
                 out.append(d)
             self._ifin = out
         return self._ifin
+
+    def finish_flex(self) -> list:
+        """Per channel the output of ``flex.decode_stream`` with ``plan`` (the ``FlexPlan``) and ``note``,
+        or a dict of ``note`` alone where nothing is decoded: the channel is not of the 1600 family, its rate does not fit or
+        nothing was searched.  It reuses the hits of ``finish_identify`` and runs no second search."""
+        from . import flex as X
+        from . import identify as I
+
+        if not self._flex:
+            raise ValueError("the describer was made without flex=True")
+        if self._xfin is None:
+            torch = D.torch_mod()
+            out = []
+            for lane, d in zip(self.lanes(), self.finish_identify()):
+                if d["rate"] != 1600:
+                    out.append(dict(note="no flex channel"))
+                    continue
+                try:
+                    plan = P.plan_flex(lane.plan.fs_ch)
+                except ValueError:
+                    plan = None
+                if plan is None or d["hits"] is None:
+                    out.append(dict(note="rate does not fit" if plan is None or d["plan"] is None else "not measured"))
+                    continue
+                theta = lane.stored[0] if len(lane.stored) == 1 else torch.cat(lane.stored)
+                st = X.decode_stream(theta, plan, lane.centre, d["hits"], I.patterns_for(1600), d["flex_v"])
+                st.update(plan=plan, note="")
+                out.append(st)
+            self._xfin = out
+        return self._xfin
+
+    def flex_result(self, center_freq: float | None = None):
+        from . import flex as X
+
+        chans = []
+        for ch, lane, st in zip(self.channels, self.lanes(), self.finish_flex()):
+            freq = None if center_freq is None else center_freq + ch.offset_hz
+            if "rows" not in st:
+                chans.append(X.FlexChannel(offset_hz=ch.offset_hz, freq_hz=freq, note=st["note"]))
+            else:
+                chans.append(X.channel_of(st, lane.plan.fs_ch, lane.keyed_from, ch.offset_hz, freq))
+        return X.FlexResult(channels=chans, sample_rate=self.find_plan.fs, center_freq=center_freq)
 
     def protocols(self, center_freq: float | None = None) -> list:
         """The ``ChannelProtocol`` of every channel, in channel order."""
@@ -683,7 +731,9 @@ class ChannelDescriber:
         ``theta`` (float32, the whole discriminator output), ``keying_parts`` ((first window, int32[k][16]) per call) and
         ``calls`` (the samples of every feed).  With ``identify``: ``ident_rate``, ``ident_plan``, ``hits`` (int64[K][6] or None) and,
         with ``keep_stages``, ``v`` (int32[n]) and ``score`` (int32[patterns][n]) of the identified channels, ``stored`` (float32,
-        the stored theta: ``theta`` from ``keyed_from`` on)."""
+        the stored theta: ``theta`` from ``keyed_from`` on).  With ``flex``: ``flex_frames`` ((m, s, mode) per decoded frame, None where
+        the channel is no FLEX channel) and, with ``keep_stages``, ``flex_words``, ``flex_raw``, ``flex_status`` ([F][5][4][88]),
+        ``flex_chosen``, ``flex_rec16``, ``flex_rec32``, ``flex_ok``, ``flex_v32`` and ``flex_plan``."""
         sums = self.finish()
         torch = D.torch_mod()
         out = []
@@ -702,6 +752,13 @@ class ChannelDescriber:
                     d["stored"] = torch.cat(lane.stored).cpu().numpy() if lane.stored else np.zeros(0, dtype=np.float32)
                     if "v" in i:
                         d.update(v=i["v"].cpu().numpy(), score=i["score"].cpu().numpy())
+            if self._flex:
+                x = self.finish_flex()[j]
+                d["flex_frames"] = x.get("rows")
+                if self._keep and "rows" in x:
+                    d.update(flex_plan=x["plan"], flex_rec16=x["rec16"], flex_rec32=x["rec32"], flex_ok=x["ok"], flex_words=x["fixed"],
+                             flex_raw=x["raw"], flex_status=x["status"], flex_chosen=x["chosen"],
+                             flex_v32=None if x["v32"] is None else x["v32"].cpu().numpy())
             if self._keep:
                 d["calls"] = list(lane.calls)
             if self._keep:

@@ -1033,6 +1033,51 @@ def plan_ident(fs_ch: float, rate: int) -> IdentPlan:
                      shift=max(0, (window - 1).bit_length() - 6), offsets=offsets)
 
 
+# ---- FLEX page decoding plan (--find-flex) ---------------------------------
+
+FLEX_MIN_SPS, FLEX_MAX_SPS = 8.0, 224.0  # samples to a 1600 bit/s bit: 3200 symbols/s keeps 4 samples to a symbol
+FLEX_LEAD = 16  # o16[i] sits at index 16 + i of ``header``: i = -16 .. 95
+FLEX_HEADER_OFFSETS = 112
+FLEX_DATA_BIT = 135  # the data begin where bit 135 of the 1600 bit/s grid ends
+FLEX_SYMBOLS = 2816  # data symbols of a frame at 1600 symbols/s: 11 blocks of 256
+FLEX_BLOCKS, FLEX_SHIFTS, FLEX_PHASES, FLEX_WORDS = 11, 5, 4, 88
+
+
+@dataclass(frozen=True)
+class FlexPlan:
+    fs_ch: float
+    sps: float  # fs_ch / 1600
+    header: tuple  # o16[i] = rint(i sps), i = -16 .. 95 (half-even, float64)
+    data: tuple  # per u = 1, 2: int32[2816 u], data symbol q ends at m + rint((135 + (q + 1) / u) sps)
+    steps: tuple  # per u = 1, 2: max(1, floor(sps / (8 u)))
+    ident: tuple  # the IdentPlans at 1600 and 3200 symbols/s
+
+    def o16(self, i: int) -> int:
+        return self.header[FLEX_LEAD + i]
+
+
+def plan_flex(fs_ch: float) -> FlexPlan:
+    """The sample offsets of a FLEX frame behind its first sync word at the channel rate ``fs_ch``: the 1600 bit/s grid of the
+    header, the data symbols at 1600 and 3200 symbols/s, the timing steps and the integrator plans of both rates.
+    ``ValueError`` unless 8 <= sps <= 224."""
+    fs_ch = float(fs_ch)
+    if not math.isfinite(fs_ch) or fs_ch <= 0.0:
+        raise ValueError("the channel rate must be positive")
+    sps = fs_ch / 1600.0
+    if not FLEX_MIN_SPS <= sps <= FLEX_MAX_SPS:
+        raise ValueError(f"{sps:.2f} samples to a bit at {fs_ch:.0f} Hz and 1600 bit/s: must be 8 .. 224")
+    header = tuple(int(np.rint(i * sps)) for i in range(-FLEX_LEAD, FLEX_HEADER_OFFSETS - FLEX_LEAD))
+    data, steps = [], []
+    for u in (1, 2):
+        q = np.arange(FLEX_SYMBOLS * u, dtype=np.float64)
+        off = np.rint((FLEX_DATA_BIT + (q + 1.0) / u) * sps).astype(np.int32)
+        off.setflags(write=False)
+        data.append(off)
+        steps.append(max(1, int(math.floor(sps / (8.0 * u)))))
+    return FlexPlan(fs_ch=fs_ch, sps=sps, header=header, data=tuple(data), steps=tuple(steps),
+                    ident=(plan_ident(fs_ch, 1600), plan_ident(fs_ch, 3200)))
+
+
 # ---- carrier squelch plan (--squelch; DESIGN.md section 24) --------------------------------------
 
 GATE_CELL = 256  # IQA_GATE_CELL: samples to a cell, counted on the absolute position

@@ -256,7 +256,8 @@ class ChannelFinder:
 
 def find_channels(path, *, center_freq: float | None = None, input_format: str | None = None, input_container: str | None = None,
                   input_sample_rate: float | None = None, iq_order: str = "iq", max_seconds: float | None = None,
-                  describe: bool = False, keying: bool = False, identify: bool = False, fs_ch: float | None = None,
+                  describe: bool = False, keying: bool = False, identify: bool = False, flex: bool = False,
+                  fs_ch: float | None = None,
                   **plan_options):
     """The occupied channels of the capture at ``path`` (``plan_options``: the keywords of ``dsp_plan.plan_find``).  The centre
     frequency is taken from the file name where it is not given; without one the channels carry offsets only.  ``describe``:
@@ -265,11 +266,14 @@ def find_channels(path, *, center_freq: float | None = None, input_format: str |
     keying and chooses its side decoders (``fs_ch``: an explicit channel rate of the targets that follow),
     and the call returns ``(FindResult, DescribeResult, KeyingResult)``.  ``identify`` (with ``keying``): the keyed channels of
     the usual digital rates are searched for their frame synchronisation words, and the call returns a
-    fourth result, ``ProtocolResult``."""
+    fourth result, ``ProtocolResult``.  ``flex`` (with ``identify``): the pages of the FLEX channels among them are decoded
+    (DESIGN.md section 26), and the call returns a fifth result, ``FlexResult``."""
     if keying and not describe:
         raise ValueError("keying=True needs describe=True")
     if identify and not keying:
         raise ValueError("identify=True needs keying=True")
+    if flex and not identify:
+        raise ValueError("flex=True needs identify=True")
     path = Path(path)
     info = iqio.probe_capture(path, input_format=input_format, input_container=input_container, input_sample_rate=input_sample_rate)
     if not info.sample_rate:
@@ -291,9 +295,12 @@ def find_channels(path, *, center_freq: float | None = None, input_format: str |
         return result
     from .describe import ChannelDescriber
 
-    describer = ChannelDescriber(plan, finder.finish(), result.channels, info.fmt, iq_order, keying=keying, identify=identify)
+    describer = ChannelDescriber(plan, finder.finish(), result.channels, info.fmt, iq_order, keying=keying, identify=identify, flex=flex)
     for a in range(0, n, BLOCK_FRAMES):
         describer.process(np.ascontiguousarray(values[2 * a : 2 * min(n, a + BLOCK_FRAMES)]))
+    if flex:
+        return (result, describer.result(center_freq), describer.keying_result(center_freq, fs_ch),
+                describer.protocol_result(center_freq), describer.flex_result(center_freq))
     if identify:
         return (result, describer.result(center_freq), describer.keying_result(center_freq, fs_ch),
                 describer.protocol_result(center_freq))
