@@ -30,6 +30,7 @@ from pathlib import Path
 from .benchmark import run_benchmark
 from . import dsp_plan as P
 from .decoders.side import SIDE_DECODERS
+from .find_layers import FIND_LAYERS
 from .gate import CarrierSquelch
 from .processing import MultiChannelPipeline, ProcessingCancelled, ProcessingConfig, ProcessingPipeline
 from .squelch import AudioPostOptions, SquelchConfig, gather_audio_targets, process_audio_batch
@@ -154,20 +155,8 @@ def build_parser() -> argparse.ArgumentParser:
                    help="Round the --find-top targets to the nearest multiple of HZ (default 1).")
     p.add_argument("--find-threshold", dest="find_threshold", type=float, metavar="DB",
                    help="dB a channel's mean spectrum must stand over its local floor (default 6).")
-    p.add_argument("--find-describe", dest="find_describe", action="store_true",
-                   help="Find the channels, then measure each one in a second pass: a label (nfm, am, ssb, wfm, carrier, unknown) "
-                        "and a suggested --demod, --bw and frequency.  Implies --find-channels.")
-    p.add_argument("--find-decode", dest="find_decode", action="store_true",
-                   help="Find and describe the channels and measure the keying of each one: whether its discriminator switches on "
-                        "a symbol clock (fsk 512 ... 9600) and which side decoders fit it.  With --find-top N --find-auto every "
-                        "target runs with its chosen decoders.  Implies --find-describe.")
-    p.add_argument("--find-identify", dest="find_identify", action="store_true",
-                   help="Find, describe and key the channels, and name the protocol of every channel keyed at 1600, 2400, 3200 or "
-                        "4800 baud by its frame synchronisation words: DMR, P25, YSF, NXDN or FLEX with its mode.  Implies "
-                        "--find-decode.")
-    p.add_argument("--find-flex", dest="find_flex", action="store_true",
-                   help="Find, describe, key and identify the channels, and decode the pages of every FLEX channel: capcode, type "
-                        "and text, one line per page, also written to <capture stem>.flex.json.  Implies --find-identify.")
+    for layer in FIND_LAYERS:
+        p.add_argument(layer.option, dest=layer.flag, action="store_true", help=layer.help)
     p.add_argument("--find-auto", dest="find_auto", action="store_true",
                    help="With --find-top N: take the N strongest channels whose label is known and run each with its own "
                         "suggested --demod, --bw and frequency.")
@@ -235,17 +224,17 @@ def run_audio_post(args) -> int:
 
 def check_find_args(parser, args) -> bool:
     """``parser.error`` for every misuse of the ``--find-*`` flags; whether channels are to be found."""
+    layers = [(layer.option, getattr(args, layer.flag) or None) for layer in FIND_LAYERS]
     given = [flag for flag, value in (("--find-channels", args.find_channels or None), ("--find-top", args.find_top),
-                                      ("--find-grid", args.find_grid), ("--find-threshold", args.find_threshold),
-                                      ("--find-describe", args.find_describe or None), ("--find-auto", args.find_auto or None),
-                                      ("--find-decode", args.find_decode or None), ("--find-identify", args.find_identify or None), ("--find-flex", args.find_flex or None))
+                                      ("--find-grid", args.find_grid), ("--find-threshold", args.find_threshold), layers[0],
+                                      ("--find-auto", args.find_auto or None), *layers[1:])
              if value is not None]
     if not given:
         return False
-    if args.find_flex:
-        args.find_identify = True
-    if args.find_identify:
-        args.find_decode = True
+    # a layer's flag sets the flags of the layers in front of it, down to the second: the first is derived (run_find)
+    for below, layer in reversed(list(zip(FIND_LAYERS[1:], FIND_LAYERS[2:]))):
+        if getattr(args, layer.flag):
+            setattr(args, below.flag, True)
     for flag, value in (("--ft", args.target_freqs), ("--benchmark", args.benchmark), ("--audio-post", args.audio_post_path),
                         ("--probe-only", args.probe_only)):
         if value:
@@ -262,7 +251,7 @@ def check_find_args(parser, args) -> bool:
     for e in SIDE_DECODERS:
         if args.find_auto and getattr(args, e.name):
             parser.error(f"--find-auto cannot be combined with --{e.name}.")
-    if not args.find_channels and not args.find_describe and not args.find_decode and args.find_top is None:
+    if not args.find_channels and not any(getattr(args, layer.flag) for layer in FIND_LAYERS) and args.find_top is None:
         parser.error("--find-threshold needs --find-channels or --find-top.")
     if args.input_path is None:
         parser.error(f"{given[0]} needs --in.")
@@ -296,63 +285,40 @@ def check_squelch_args(parser, args, finding: bool) -> CarrierSquelch | None:
 
 
 def run_find(args, codec, container):
-    """``--find-channels`` / ``--find-describe`` / ``--find-decode`` / ``--find-identify`` / ``--find-flex`` / ``--find-top``: print and store the
-    capture's channels and, where asked for, their descriptions, keying and protocols.  Returns (exit code or ``None`` to go on, the targets of the run that follows: frequencies, or with
-    ``--find-auto`` (frequency, demod, bw) each, and with ``--find-decode`` beside it (frequency, demod, bw, side decoders))."""
+    """``--find-channels``, ``--find-top`` and the flags of ``FIND_LAYERS``: print and store the capture's channels and, where
+    asked for, what every layer of the second pass says about them.  Returns (exit code or ``None`` to go on, the targets of the
+    run that follows: frequencies, or with ``--find-auto`` (frequency, demod, bw) each, and with ``--find-decode`` beside it
+    (frequency, demod, bw, side decoders))."""
     from .find import find_channels, select_targets
 
     options = {} if args.find_threshold is None else {"threshold_db": args.find_threshold}
-    describing = args.find_describe or args.find_auto or args.find_decode
-    if describing:
-        options["describe"] = True
-    if args.find_decode:
-        options.update(keying=True, fs_ch=getattr(args, "find_fs_ch", None))
-    if args.find_identify:
-        options["identify"] = True
-    if args.find_flex:
-        options["flex"] = True
-    described = keyed = named = paged = None
+    wanted = [getattr(args, layer.flag) for layer in FIND_LAYERS]
+    wanted[0] = args.find_auto or any(wanted)  # (a higher flag leaves the first unset, and --find-auto needs the descriptions)
+    layers = [layer for layer, on in zip(FIND_LAYERS, wanted) if on]
+    options.update({layer.name: True for layer in layers})
     try:
-        result = find_channels(args.input_path, center_freq=args.center_freq, input_format=codec, input_container=container,
-                               input_sample_rate=args.input_sample_rate, iq_order=args.iq_order, max_seconds=args.preview_seconds,
-                               **options)
-        if args.find_flex:
-            result, described, keyed, named, paged = result
-        elif args.find_identify:
-            result, described, keyed, named = result
-        elif args.find_decode:
-            result, described, keyed = result
-        elif describing:
-            result, described = result
+        found = find_channels(args.input_path, center_freq=args.center_freq, input_format=codec, input_container=container,
+                              input_sample_rate=args.input_sample_rate, iq_order=args.iq_order, max_seconds=args.preview_seconds,
+                              fs_ch=getattr(args, "find_fs_ch", None), **options)
     except Exception as exc:  # noqa: BLE001
         LOG.error("Finding channels failed: %s", exc)
         if args.verbose:
             LOG.exception("Debug traceback")
         return 1, []
-    if described is None or not result.channels:
-        for line in result.lines():
-            print(line)
-    else:
-        under = keyed.lines() if keyed is not None else [None] * len(result.channels)
-        third = named.lines() if named is not None else [None] * len(result.channels)
-        for line, about, keying, protocol in zip(result.lines(), described.lines(), under, third):
-            print(line)
-            print(about)
-            if keying is not None:
-                print(keying)
-            if protocol is not None:
-                print(protocol)
-    args.input_path.with_name(f"{args.input_path.stem}.channels.json").write_text(json.dumps(result.to_json(), indent=1) + "\n")
-    if described is not None:
-        args.input_path.with_name(f"{args.input_path.stem}.describe.json").write_text(json.dumps(described.to_json(), indent=1) + "\n")
-    if keyed is not None:
-        args.input_path.with_name(f"{args.input_path.stem}.keying.json").write_text(json.dumps(keyed.to_json(), indent=1) + "\n")
-    if named is not None:
-        args.input_path.with_name(f"{args.input_path.stem}.protocols.json").write_text(json.dumps(named.to_json(), indent=1) + "\n")
-    if paged is not None:
-        for line in paged.lines():
-            print(line)
-        args.input_path.with_name(f"{args.input_path.stem}.flex.json").write_text(json.dumps(paged.to_json(), indent=1) + "\n")
+    result, *above = found if layers else (found,)
+    results = {layer.name: res for layer, res in zip(layers, above)}
+    under = [results[layer.name].lines() for layer in layers if layer.inline] if result.channels else []
+    for i, line in enumerate(result.lines()):
+        print(line)
+        for lines in under:
+            print(lines[i])
+    for layer in layers:
+        if not layer.inline:
+            for line in results[layer.name].lines():
+                print(line)
+    for suffix, res in [("channels", result)] + [(layer.suffix, results[layer.name]) for layer in layers]:
+        args.input_path.with_name(f"{args.input_path.stem}.{suffix}.json").write_text(json.dumps(res.to_json(), indent=1) + "\n")
+    described, keyed = results.get("describe"), results.get("keying")
     if args.find_top is None:
         return 0, []
     if not result.channels:
@@ -367,7 +333,8 @@ def run_find(args, codec, container):
 
     if keyed is not None:
         # every target with its channel's decoders, and the bandwidth they ask for
-        described = dataclasses.replace(described, channels=[dataclasses.replace(d, bw=k.bw) for d, k in zip(described.channels, keyed.channels)])
+        described = dataclasses.replace(described, channels=[dataclasses.replace(d, bw=k.bw)
+                                                             for d, k in zip(described.channels, keyed.channels)])
     targets, skipped = select_auto_targets(result, described, args.find_top, args.find_grid or 1.0,
                                            extras=None if keyed is None else [tuple(k.decoders) for k in keyed.channels])
     for ch in skipped:

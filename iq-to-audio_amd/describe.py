@@ -9,18 +9,12 @@ float64 from those integers and from the finder's planes; the label and the sugg
 quantiser everything is integer: the sums do not depend on how the stream is cut.  No CPU path: without a GPU or the built
 library the calls raise ``RuntimeError``.
 
-With ``keying=True`` (``--find-decode``) the same pass also measures whether each channel's discriminator
-switches on a symbol clock: ``iqa_quadrature`` and ``iqa_keying_accumulate`` give, per window of 2048 samples, the gated pairs,
-the level crossings and the crossings' clock-phase sums at seven candidate bauds.  Fixed rules turn them into ``fsk <baud>`` or
-``unkeyed`` and into the side decoders a target of that channel runs with.
-
-With ``identify=True`` beside it (``--find-identify``) the pass keeps every channel's discriminator output
-from the keyed-from block on, and ``finish_identify`` searches the channels labelled ``fsk 1600 | 2400 | 3200 | 4800`` for the
-frame synchronisation words of their family (``identify.py``).  With ``flex=True`` beside that (``--find-flex``, DESIGN.md section
-26) ``finish_flex`` decodes the pages behind the FLEX sync words among those hits (``flex.py``)."""
+The layers above this one (``find_layers.FIND_LAYERS``, each in the module of its name) ride on the same pass: with ``keying=True``
+it also takes every channel's discriminator and, once the channel holds 1024 gated pairs, its keying rows (``keying.py``); with
+``identify=True`` it keeps that discriminator output for the sync-word search of ``identify.py``, whose hits ``flex.py`` decodes
+with ``flex=True``."""
 from __future__ import annotations
 
-import logging
 import math
 from ctypes import c_int32, c_int64
 from dataclasses import asdict, dataclass, field
@@ -30,8 +24,11 @@ import numpy as np
 from . import _dev as D
 from . import _native as N
 from . import dsp_plan as P
-
-LOG = logging.getLogger(__name__)
+from . import flex as X
+from . import identify as I
+from . import keying as KY
+from .find import _RAW_DTYPE
+from .find_layers import FIND_LAYERS, active_layers
 
 SUMS = ("N", "NP", "S1", "S2", "E", "CR", "CI", "A")
 LABELS = ("nfm", "am", "ssb", "wfm", "carrier", "unknown")
@@ -48,7 +45,6 @@ AM_LINE = 0.6
 SSB_WIDTH_HZ = 6000.0
 SSB_USB_FROM_HZ = 10e6
 SSB_EDGE_HZ = 300.0
-_RAW_DTYPE = {"s16": "int16", "u8": "uint8", "f32": "float32"}
 
 
 @dataclass
@@ -224,184 +220,6 @@ def select_auto_targets(found, described: DescribeResult, top: int, grid_hz: flo
     return sorted(targets.values()), skipped
 
 
-# ---- keying: the host arithmetic ---------------------------------------------------------------------
-
-# the rules' constants (design constants, as section 22's are)
-KEYING_MIN_PAIRS = 1024  # gated pairs of the describe rows before the centre is taken
-KEYING_MIN_CROSSINGS = 256
-KEYING_MIN_COH = 0.35
-KEYING_RATE_LOW, KEYING_RATE_HIGH = 0.25, 0.8  # crossings per second against the baud
-AIRBAND_HZ = (117.975e6, 137.0e6)
-AIS_BW = 25000.0
-POCSAG_BAUDS = (512, 1200, 2400)
-FLEX_BAUDS = (1600, 3200)
-NFM_RATE, WFM_RATE = 96_000.0, 480_000.0  # the channel rates a target of that mode asks for where --fs-ch is unset
-
-
-@dataclass
-class ChannelKeying:
-    offset_hz: float  # the finder's
-    freq_hz: float | None
-    described: str  # the label of section 22
-    fs_ch: float  # the rate of the measured stream
-    bauds: list  # the candidates
-    coh: list  # per candidate: the coherence of the crossings with its clock; None where skipped or not measured
-    rate_hz: float | None  # crossings per second of gated stream
-    crossings: int
-    pairs: int
-    centre: int | None  # c, in 1 / 4096 rad per sample; None where the channel never held 1024 gated pairs
-    label: str | None  # "fsk <baud>" or "unkeyed" for an nfm channel, None for every other
-    baud: int | None
-    decoders: list  # the side decoders a target of this channel runs with
-    bw: float | None  # the suggested --bw (section 22's, 25 000 for fsk 9600)
-    note: str  # why there is no decoder, where there is none
-
-    def line(self) -> str:
-        if self.label is None:
-            head = f"not measured ({self.described})"
-        else:
-            known = [(v, b) for v, b in zip(self.coh, self.bauds) if v is not None]
-            if not known or self.rate_hz is None:
-                head = f"{self.label} (not measured, {self.crossings} crossings)"
-            elif self.baud is not None:
-                head = f"{self.label} (coh {self.coh[self.bauds.index(self.baud)]:.2f}, {self.rate_hz:.0f} crossings/s)"
-            else:
-                best, at = max(known)
-                head = f"{self.label} (best coh {best:.2f} at {at}, {self.rate_hz:.0f} crossings/s)"
-        if not self.decoders:
-            return f"    keying: {head} -> {self.note or 'no decoder'}"
-        flags = " ".join(f"--{name}" for name in self.decoders)
-        return f"    keying: {head} -> {flags}" + (f" --bw {self.bw:.0f}" if "ais" in self.decoders else "")
-
-    def to_json(self) -> dict:
-        return asdict(self)
-
-
-@dataclass
-class KeyingResult:
-    channels: list = field(default_factory=list)  # ChannelKeying, in the order of the FindResult's channels
-    sample_rate: float = 0.0
-    center_freq: float | None = None
-
-    def lines(self) -> list:
-        return [ch.line() for ch in self.channels]
-
-    def to_json(self) -> dict:
-        return asdict(self)
-
-    @classmethod
-    def from_json(cls, data: dict) -> "KeyingResult":
-        data = dict(data)
-        data["channels"] = [ChannelKeying(**ch) for ch in data.get("channels", [])]
-        return cls(**data)
-
-
-def keying_centre(cr: int, ci: int) -> int:
-    """c = rint(atan2(CI, CR) 4096): the mean rotation per sample in the quantiser's units (float64, half-even)."""
-    return int(np.rint(math.atan2(int(ci), int(cr)) * P.KEYING_SCALE))
-
-
-def add_keying_rows(parts, windows: int) -> np.ndarray:
-    """int64[windows][16]: the rows of every call (``parts``: (first window, int32[k][16]) each) added by window number."""
-    out = np.zeros((int(windows), P.KEYING_SUMS), dtype=np.int64)
-    for first, rows in parts:
-        rows = np.asarray(rows, dtype=np.int64).reshape(-1, P.KEYING_SUMS)
-        out[first : first + rows.shape[0]] += rows
-    return out
-
-
-def _exact_sum(values: np.ndarray) -> int:
-    """The sum of int64 values below 2^44 as a Python integer: 2^19 at a time in int64, the partial sums added exactly."""
-    step = 1 << 19
-    return sum(int(values[a : a + step].sum(dtype=np.int64)) for a in range(0, values.size, step))
-
-
-def keying_figures(rows, plan: P.KeyingPlan) -> dict:
-    """coh per candidate, rate_hz, crossings and pairs from the window rows (added by window number): exact integer sums
-    (every term below 2^44), then one float64 quotient each."""
-    rows = np.asarray(rows, dtype=np.int64).reshape(-1, P.KEYING_SUMS)
-    pairs, crossings = _exact_sum(rows[:, 0]), _exact_sum(rows[:, 1])
-    den = 1024 * 1024 * _exact_sum(rows[:, 1] * rows[:, 1] - rows[:, 1])
-    coh = []
-    for k, skip in enumerate(plan.skipped):
-        if skip or den == 0:
-            coh.append(None)
-            continue
-        c, q = rows[:, 2 + 2 * k], rows[:, 3 + 2 * k]
-        coh.append((_exact_sum(c * c + q * q) - 1024 * 1024 * crossings) / den)
-    return dict(coh=coh, rate_hz=crossings / pairs * plan.fs_ch if pairs else None, crossings=crossings, pairs=pairs)
-
-
-def keying_label(coh, rate_hz, crossings: int, plan: P.KeyingPlan) -> tuple:
-    """("fsk <baud>", baud) for the lowest candidate whose clock the crossings keep and whose rate fits, else ("unkeyed", None)."""
-    if crossings < KEYING_MIN_CROSSINGS or rate_hz is None:
-        return "unkeyed", None
-    for b, v, skip in zip(plan.bauds, coh, plan.skipped):
-        if not skip and v is not None and v >= KEYING_MIN_COH and KEYING_RATE_LOW * b <= rate_hz <= KEYING_RATE_HIGH * b:
-            return f"fsk {b}", b
-    return "unkeyed", None
-
-
-def decoders_for(described: str, baud, tuned_hz) -> tuple:
-    """(side decoders, note, --bw override or None) of a channel: ``described`` the label of section 22, ``baud`` the keyed rate
-    of an nfm channel or None, ``tuned_hz`` the suggested frequency or None."""
-    if described == "nfm":
-        if baud in POCSAG_BAUDS:
-            return ["pocsag"], "", None
-        if baud == 9600:
-            return ["ais"], "", AIS_BW
-        if baud in FLEX_BAUDS:
-            return [], "FLEX rates: no decoder here", None
-        if baud == 4800:
-            return [], "4800 baud (DMR / P25 / NXDN class): no decoder here", None
-        return ["ax25", "tones"], "", None
-    if described == "wfm":
-        return ["rds"], "", None
-    if described == "am":
-        if tuned_hz is not None and AIRBAND_HZ[0] <= tuned_hz <= AIRBAND_HZ[1]:
-            return ["acars"], "", None
-        return [], "no decoder outside the airband" if tuned_hz is not None else "no decoder without a tuned frequency", None
-    return [], "no decoder", None
-
-
-def target_rate(sample_rate: float, demod: str | None, fs_ch: float | None = None) -> float:
-    """The channel rate a target of ``demod`` runs at: what the pipeline makes of ``--fs-ch`` (unset: the mode's default)."""
-    ask = float(fs_ch) if fs_ch is not None else (WFM_RATE if demod == "wfm" else NFM_RATE)
-    return P.choose_decimation(float(sample_rate), ask)[1]
-
-
-def usable_decoders(names, rate: float, where: str = "") -> list:
-    """``names`` without the decoders whose plan refuses the channel rate ``rate`` (the refusal is logged)."""
-    from .decoders.side import SIDE_DECODERS
-
-    rows = {e.name: e for e in SIDE_DECODERS}
-    kept = []
-    for name in names:
-        try:
-            rows[name].plan(rate)
-        except ValueError as exc:
-            LOG.info("%s--%s dropped: %s", where, name, exc)
-            continue
-        kept.append(name)
-    return kept
-
-
-def key_channel(desc: ChannelDescription, plan: P.KeyingPlan, rows, centre, sample_rate: float,
-                fs_ch: float | None = None) -> ChannelKeying:
-    """One channel's keying from its description, its window rows (None: never measured) and its centre."""
-    figures = dict(coh=[None] * len(plan.bauds), rate_hz=None, crossings=0, pairs=0)
-    if rows is not None and centre is not None:
-        figures = keying_figures(rows, plan)
-    label = baud = None
-    if desc.label == "nfm":
-        label, baud = keying_label(figures["coh"], figures["rate_hz"], figures["crossings"], plan)
-    names, note, bw = decoders_for(desc.label, baud, desc.tuned_hz)
-    where = f"{desc.offset_hz:+.0f} Hz: " if desc.freq_hz is None else f"{desc.freq_hz:.0f} Hz: "
-    names = usable_decoders(names, target_rate(sample_rate, desc.demod, fs_ch), where)
-    return ChannelKeying(offset_hz=desc.offset_hz, freq_hz=desc.freq_hz, described=desc.label, fs_ch=plan.fs_ch, bauds=list(plan.bauds),
-                         centre=centre, label=label, baud=baud, decoders=names, bw=desc.bw if bw is None else bw, note=note, **figures)
-
-
 # ---- the device pass --------------------------------------------------------------------------------------------------------
 
 
@@ -424,17 +242,7 @@ def add_rows(rows: np.ndarray) -> tuple:
     return tuple((int(h) << 32) + int(l) for h, l in zip(high, low))
 
 
-def accumulate_keying(theta, pos: int, front, centre: int, kplan: P.KeyingPlan, table_dev, plan: P.DescribePlan, find_plan: P.FindPlan,
-                      gate_dev):
-    """``iqa_keying_accumulate`` for one stretch of a channel's discriminator output (device float32): (first window, the
-    device rows int32[windows][16]).  The entry point checks its arguments before it launches (``ValueError``)."""
-    n = int(theta.numel())
-    rows = D.empty(int(N.lib().iqa_keying_windows(pos, n)) * P.KEYING_SUMS, "int32")
-    incs = (c_int32 * len(kplan.incs))(*kplan.incs)
-    N.call("iqa_keying_accumulate", N.ptr(theta), c_int64(n), c_int64(pos), N.ptr(front), c_int32(centre), incs, N.ptr(table_dev),
-           c_int32(plan.decimation), c_int32(plan.delay), c_int32(find_plan.hop), c_int32(find_plan.slice_frames),
-           c_int64(find_plan.frames), c_int32(find_plan.slices), N.ptr(gate_dev), N.ptr(rows), N.stream_ptr())
-    return pos // P.KEYING_WINDOW, rows
+_MODULES = {m.__name__.rpartition(".")[2]: m for m in (KY, I, X)}  # a layer above the first lives in the module of its keyword
 
 
 class _Lane:
@@ -464,21 +272,21 @@ class _Lane:
 class ChannelDescriber:
     """The stage API: ``process(raw_block)`` per block of the capture (what ``ChannelFinder.process`` takes), ``finish()`` once
     (the eight sums of every channel), ``result()`` (a ``DescribeResult``), ``stages()`` for the tests, ``reset()``.
-    ``fin`` is ``ChannelFinder.finish()`` of the same capture and ``channels`` the ``FoundChannel``s made from it."""
+    ``fin`` is ``ChannelFinder.finish()`` of the same capture and ``channels`` the ``FoundChannel``s made from it.  ``layers``: the
+    keywords of ``FIND_LAYERS`` above the first (``keying=True``, ``identify=True``, ``flex=True``), each with the one in front of it."""
 
     def __init__(self, find_plan: P.FindPlan, fin: dict, channels, fmt: str = "s16", iq_order: str = "iq", *, keep_stages: bool = False,
-                 keying: bool = False, identify: bool = False, flex: bool = False):
+                 **layers):
         if fmt not in _RAW_DTYPE:
             raise ValueError(f"Unsupported sample format '{fmt}'")
         if iq_order not in N.ORDER:
             raise ValueError(f"Unsupported iq_order '{iq_order}'")
-        if identify and not keying:
-            raise ValueError("identify=True needs keying=True")
-        if flex and not identify:
-            raise ValueError("flex=True needs identify=True")
-        self._identify, self._flex = bool(identify), bool(flex)
+        for name in layers:
+            if name not in _MODULES:
+                raise TypeError(f"ChannelDescriber() got an unexpected keyword argument '{name}'")
+        self._names = tuple(layer.name for layer in active_layers({FIND_LAYERS[0].name: True, **layers}))  # this layer, then the others
         self.find_plan, self.fin, self.channels = find_plan, fin, list(channels)
-        self.fmt, self.iq_order, self._keep, self._keying = fmt, iq_order, keep_stages, bool(keying)
+        self.fmt, self.iq_order, self._keep, self._keying = fmt, iq_order, keep_stages, "keying" in self._names
         by_lo = {int(rec[0]): j for j, rec in enumerate(np.asarray(fin["runs"]).reshape(-1, 8))}
         self._run_of = []
         for ch in self.channels:
@@ -496,11 +304,7 @@ class ChannelDescriber:
         self._lanes = None
         self._groups: list = []
         self.samples_seen = 0
-        self._fin = None
-        self._kfin = None
-        self._ifin = None
-        self._xfin = None
-        self._keyed: dict = {}  # identify: the last ``keying()`` per centre frequency, so that the protocols do not key again
+        self._done: dict = {}  # what the finishes made of the blocks so far, by name
 
     def _start(self) -> None:
         from .channelizer import ChannelBank, Channelizer
@@ -533,8 +337,7 @@ class ChannelDescriber:
             raise ValueError(f"the plan was made for {self.find_plan.n_samples} samples and the stream is longer")
         if self._lanes is None:
             self._start()
-        self._fin = self._kfin = self._ifin = self._xfin = None
-        self._keyed = {}
+        self._done = {}
         for bank, lanes in self._groups:
             zs = bank.process(x) if bank is not None else [lanes[0].chan.process(x)]
             for lane, z in zip(lanes, zs):
@@ -566,14 +369,14 @@ class ChannelDescriber:
         if lane.centre is None and self._gated(lane, lane.pos, n):  # (a stretch without a gated sample adds no pair: no read-back)
             new = add_rows(lane.rows[-1].cpu().numpy())
             lane.run = [lane.run[0] + new[1], lane.run[1] + new[5], lane.run[2] + new[6]]
-            if lane.run[0] >= KEYING_MIN_PAIRS:
-                lane.centre = keying_centre(lane.run[1], lane.run[2])
+            if lane.run[0] >= KY.KEYING_MIN_PAIRS:
+                lane.centre = KY.keying_centre(lane.run[1], lane.run[2])
         if lane.centre is not None:
             if lane.keyed_from is None:
                 lane.keyed_from = lane.pos
-            lane.krows.append(accumulate_keying(theta, lane.pos, lane.front if lane.pos >= 1 else None, lane.centre, lane.kplan,
-                                                self._table, lane.plan, self.find_plan, lane.gate_dev))
-            if self._identify:
+            lane.krows.append(KY.accumulate_keying(theta, lane.pos, lane.front if lane.pos >= 1 else None, lane.centre, lane.kplan,
+                                                   self._table, lane.plan, self.find_plan, lane.gate_dev))
+            if "identify" in self._names:
                 lane.stored.append(theta)
         lane.front = theta[n - 1 :].clone()
         if self._keep:
@@ -585,14 +388,22 @@ class ChannelDescriber:
             self._start()
         return self._lanes
 
+    def _once(self, name: str, make):
+        """``make()`` of the blocks so far, made once: kept until the next block or ``reset()``."""
+        if name not in self._done:
+            self._done[name] = make()
+        return self._done[name]
+
+    def _need(self, name: str) -> None:
+        if name not in self._names:
+            raise ValueError(f"the describer was made without {name}=True")
+
     def finish(self) -> list:
         """The eight sums of every channel (Python integers), in channel order."""
         if self.samples_seen != self.find_plan.n_samples:
             raise ValueError(f"the plan was made for {self.find_plan.n_samples} samples and the stream held {self.samples_seen}")
-        if self._fin is None:
-            torch = D.torch_mod()
-            self._fin = [add_rows(torch.cat(lane.rows).cpu().numpy()) if lane.rows else (0,) * len(SUMS) for lane in self.lanes()]
-        return self._fin
+        return self._once("sums", lambda: [add_rows(D.torch_mod().cat(lane.rows).cpu().numpy()) if lane.rows else (0,) * len(SUMS)
+                                           for lane in self.lanes()])
 
     def _gated(self, lane: "_Lane", pos: int, n: int) -> bool:
         """Whether any slice that the samples pos .. pos + n - 1 of the lane's stream lie in is on."""
@@ -601,122 +412,52 @@ class ChannelDescriber:
                        for m in (pos, pos + n - 1))
         return bool(lane.gate[first : last + 1].any())
 
+    # ---- the layers above: each a one-liner into its module, through the cache ----
+
     def finish_keying(self) -> list:
         """Per channel the keying rows added by window number (int64[windows][16]), or None where the channel never held 1024
         gated pairs; in channel order."""
-        if not self._keying:
-            raise ValueError("the describer was made without keying=True")
+        self._need("keying")
         self.finish()
-        if self._kfin is None:
-            torch = D.torch_mod()
-            self._kfin = []
-            for lane in self.lanes():
-                if lane.centre is None:
-                    self._kfin.append(None)
-                    continue
-                flat = torch.cat([rows for _, rows in lane.krows]).cpu().numpy().reshape(-1, P.KEYING_SUMS)  # one read-back per channel
-                ends = np.cumsum([int(rows.numel()) // P.KEYING_SUMS for _, rows in lane.krows])
-                parts = [(first, flat[end - int(rows.numel()) // P.KEYING_SUMS : end]) for (first, rows), end in zip(lane.krows, ends)]
-                self._kfin.append(add_keying_rows(parts, -(-lane.pos // P.KEYING_WINDOW)))
-        return self._kfin
+        return self._once("keying", lambda: KY.finish_keying(self.lanes()))
 
     def keying(self, center_freq: float | None = None, fs_ch: float | None = None) -> list:
-        """The ``ChannelKeying`` of every channel, in channel order.  ``fs_ch``: an explicit ``--fs-ch`` of the targets."""
+        """The ``ChannelKeying`` of every channel, in channel order.  ``fs_ch``: an explicit ``--fs-ch`` of the targets.  The last
+        one per centre frequency is kept for the layers above, so that they do not key (and log a dropped decoder) again."""
         rows = self.finish_keying()
         described = self.result(center_freq)
-        out = [key_channel(d, lane.kplan, r, lane.centre, self.find_plan.fs, fs_ch)
+        out = [KY.key_channel(d, lane.kplan, r, lane.centre, self.find_plan.fs, fs_ch)
                for d, lane, r in zip(described.channels, self.lanes(), rows)]
-        if self._identify:
-            self._keyed[center_freq] = list(out)
+        self._done.setdefault("keyed", {})[center_freq] = list(out)
         return out
 
+    def keying_result(self, center_freq: float | None = None, fs_ch: float | None = None) -> KY.KeyingResult:
+        return KY.KeyingResult(channels=self.keying(center_freq, fs_ch), sample_rate=self.find_plan.fs, center_freq=center_freq)
+
     def finish_identify(self) -> list:
-        """Per channel a dict of its identification: ``rate`` (R, None where the channel is not one to
-        identify), ``plan`` (the ``IdentPlan``, None where the rate does not fit), ``note``, ``hits`` (int64[K][6], the kept sync
-        words sorted by (pattern, m), m counted from ``keyed_from``; None where nothing was searched) and, with ``keep_stages``,
-        ``v`` and ``score`` (device tensors).  The whole search runs here, on the stored stream as one piece."""
-        from . import identify as I
-
-        if not self._identify:
-            raise ValueError("the describer was made without identify=True")
-        if self._ifin is None:
-            torch = D.torch_mod()
-            out = []
-            # (label and baud depend neither on the centre frequency nor on the targets' rate: any keying of this pass will do)
-            for lane, keyed in zip(self.lanes(), next(iter(self._keyed.values())) if self._keyed else self.keying()):
-                rate, plan, note = I.family_plan(keyed.label, keyed.baud if keyed.label is not None else None, lane.plan.fs_ch)
-                d = dict(rate=rate, plan=plan, note=note, hits=None)
-                if plan is not None and lane.centre is not None and lane.stored:
-                    theta = lane.stored[0] if len(lane.stored) == 1 else torch.cat(lane.stored)
-                    if int(theta.numel()) > P.IDENT_MAX_N:
-                        raise ValueError(f"a stored stream of {int(theta.numel())} samples is longer than 2^30")
-                    v = I.integrate(theta, plan, lane.centre)
-                    score, d["hits"] = I.search(v, plan, I.patterns_for(rate))
-                    if self._keep:
-                        d.update(v=v, score=score)
-                    if self._flex and rate == 1600:
-                        d["flex_v"] = v  # (section 26 reads the same plane)
-                out.append(d)
-            self._ifin = out
-        return self._ifin
-
-    def finish_flex(self) -> list:
-        """Per channel the output of ``flex.decode_stream`` with ``plan`` (the ``FlexPlan``) and ``note``,
-        or a dict of ``note`` alone where nothing is decoded: the channel is not of the 1600 family, its rate does not fit or
-        nothing was searched.  It reuses the hits of ``finish_identify`` and runs no second search."""
-        from . import flex as X
-        from . import identify as I
-
-        if not self._flex:
-            raise ValueError("the describer was made without flex=True")
-        if self._xfin is None:
-            torch = D.torch_mod()
-            out = []
-            for lane, d in zip(self.lanes(), self.finish_identify()):
-                if d["rate"] != 1600:
-                    out.append(dict(note="no flex channel"))
-                    continue
-                try:
-                    plan = P.plan_flex(lane.plan.fs_ch)
-                except ValueError:
-                    plan = None
-                if plan is None or d["hits"] is None:
-                    out.append(dict(note="rate does not fit" if plan is None or d["plan"] is None else "not measured"))
-                    continue
-                theta = lane.stored[0] if len(lane.stored) == 1 else torch.cat(lane.stored)
-                st = X.decode_stream(theta, plan, lane.centre, d["hits"], I.patterns_for(1600), d["flex_v"])
-                st.update(plan=plan, note="")
-                out.append(st)
-            self._xfin = out
-        return self._xfin
-
-    def flex_result(self, center_freq: float | None = None):
-        from . import flex as X
-
-        chans = []
-        for ch, lane, st in zip(self.channels, self.lanes(), self.finish_flex()):
-            freq = None if center_freq is None else center_freq + ch.offset_hz
-            if "rows" not in st:
-                chans.append(X.FlexChannel(offset_hz=ch.offset_hz, freq_hz=freq, note=st["note"]))
-            else:
-                chans.append(X.channel_of(st, lane.plan.fs_ch, lane.keyed_from, ch.offset_hz, freq))
-        return X.FlexResult(channels=chans, sample_rate=self.find_plan.fs, center_freq=center_freq)
+        """Per channel the dict of ``identify.finish_identify``, ``v`` also for a layer above that reads it."""
+        self._need("identify")
+        above = self._names[self._names.index("identify") + 1 :]
+        rates = tuple(r for name in above for r in getattr(_MODULES[name], "PLANE_RATES", ()))
+        # (label and baud depend neither on the centre frequency nor on the targets' rate: any keying of this pass will do)
+        return self._once("identify", lambda: I.finish_identify(
+            self.lanes(), next(iter(self._done.get("keyed", {}).values()), None) or self.keying(), self._keep, rates))
 
     def protocols(self, center_freq: float | None = None) -> list:
         """The ``ChannelProtocol`` of every channel, in channel order."""
-        from . import identify as I
-
         found = self.finish_identify()
-        return [I.protocol_of(keyed, d["hits"], d["plan"], d["rate"], d["note"], lane.keyed_from)
-                for keyed, d, lane in zip(self._keyed.get(center_freq) or self.keying(center_freq), found, self.lanes())]
+        return I.protocols(self.lanes(), self._done.get("keyed", {}).get(center_freq) or self.keying(center_freq), found)
 
-    def protocol_result(self, center_freq: float | None = None):
-        from . import identify as I
-
+    def protocol_result(self, center_freq: float | None = None) -> I.ProtocolResult:
         return I.ProtocolResult(channels=self.protocols(center_freq), sample_rate=self.find_plan.fs, center_freq=center_freq)
 
-    def keying_result(self, center_freq: float | None = None, fs_ch: float | None = None) -> KeyingResult:
-        return KeyingResult(channels=self.keying(center_freq, fs_ch), sample_rate=self.find_plan.fs, center_freq=center_freq)
+    def finish_flex(self) -> list:
+        """Per channel the dict of ``flex.finish_flex``."""
+        self._need("flex")
+        return self._once("flex", lambda: X.finish_flex(self.lanes(), self.finish_identify()))
+
+    def flex_result(self, center_freq: float | None = None) -> X.FlexResult:
+        return X.flex_result(self.channels, self.lanes(), self.finish_flex(), self.find_plan.fs, center_freq)
 
     def result(self, center_freq: float | None = None) -> DescribeResult:
         sums = self.finish()
@@ -725,43 +466,18 @@ class ChannelDescriber:
         return DescribeResult(channels=out, sample_rate=self.find_plan.fs, center_freq=center_freq)
 
     def stages(self) -> list:
-        """One dict per channel: sums, sh, gate, plan and, with ``keep_stages``, ``z`` (complex64, the whole channel stream) and
-        ``rows`` (int64[tiles of every call][8]).  With ``keying``: ``c`` (the centre or None), ``keyed_from`` (the position of the
-        first keyed sample), ``keying_rows`` (int64[windows][16], added by window number, or None) and, with ``keep_stages``,
-        ``theta`` (float32, the whole discriminator output), ``keying_parts`` ((first window, int32[k][16]) per call) and
-        ``calls`` (the samples of every feed).  With ``identify``: ``ident_rate``, ``ident_plan``, ``hits`` (int64[K][6] or None) and,
-        with ``keep_stages``, ``v`` (int32[n]) and ``score`` (int32[patterns][n]) of the identified channels, ``stored`` (float32,
-        the stored theta: ``theta`` from ``keyed_from`` on).  With ``flex``: ``flex_frames`` ((m, s, mode) per decoded frame, None where
-        the channel is no FLEX channel) and, with ``keep_stages``, ``flex_words``, ``flex_raw``, ``flex_status`` ([F][5][4][88]),
-        ``flex_chosen``, ``flex_rec16``, ``flex_rec32``, ``flex_ok``, ``flex_v32`` and ``flex_plan``."""
+        """One dict per channel: sums, sh, gate, plan and, with ``keep_stages``, ``z`` (complex64, the whole channel stream), ``rows``
+        (int64[tiles of every call][8]) and ``calls`` (the samples of every feed); then the keys of every layer above, in chain order
+        (``stage_keys`` of its module)."""
         sums = self.finish()
         torch = D.torch_mod()
         out = []
-        krows = self.finish_keying() if self._keying else None
         for j, (lane, s) in enumerate(zip(self.lanes(), sums)):
             d = dict(sums=s, sh=lane.sh, gate=lane.gate, plan=lane.plan)
-            if self._keying:
-                d.update(c=lane.centre, keyed_from=lane.keyed_from, keying_rows=krows[j], keying_plan=lane.kplan)
-                if self._keep:
-                    d["theta"] = torch.cat(lane.theta).cpu().numpy() if lane.theta else np.zeros(0, dtype=np.float32)
-                    d["keying_parts"] = [(first, rows.cpu().numpy().reshape(-1, P.KEYING_SUMS)) for first, rows in lane.krows]
-            if self._identify:
-                i = self.finish_identify()[j]
-                d.update(ident_rate=i["rate"], ident_plan=i["plan"], hits=i["hits"])
-                if self._keep:
-                    d["stored"] = torch.cat(lane.stored).cpu().numpy() if lane.stored else np.zeros(0, dtype=np.float32)
-                    if "v" in i:
-                        d.update(v=i["v"].cpu().numpy(), score=i["score"].cpu().numpy())
-            if self._flex:
-                x = self.finish_flex()[j]
-                d["flex_frames"] = x.get("rows")
-                if self._keep and "rows" in x:
-                    d.update(flex_plan=x["plan"], flex_rec16=x["rec16"], flex_rec32=x["rec32"], flex_ok=x["ok"], flex_words=x["fixed"],
-                             flex_raw=x["raw"], flex_status=x["status"], flex_chosen=x["chosen"],
-                             flex_v32=None if x["v32"] is None else x["v32"].cpu().numpy())
+            for name in self._names[1:]:
+                d.update(_MODULES[name].stage_keys(self, j, lane, self._keep))
             if self._keep:
                 d["calls"] = list(lane.calls)
-            if self._keep:
                 d["z"] = torch.cat(lane.z).cpu().numpy() if lane.z else np.zeros(0, dtype=np.complex64)
                 d["rows"] = torch.cat(lane.rows).cpu().numpy().reshape(-1, len(SUMS)) if lane.rows else np.zeros((0, 8), dtype=np.int64)
             out.append(d)

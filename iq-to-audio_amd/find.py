@@ -27,6 +27,7 @@ from . import _native as N
 from . import dsp_plan as P
 from . import iqio
 from .decoders.common import search_with_room
+from .find_layers import FIND_LAYERS, active_layers
 
 LOG = logging.getLogger(__name__)
 
@@ -256,24 +257,16 @@ class ChannelFinder:
 
 def find_channels(path, *, center_freq: float | None = None, input_format: str | None = None, input_container: str | None = None,
                   input_sample_rate: float | None = None, iq_order: str = "iq", max_seconds: float | None = None,
-                  describe: bool = False, keying: bool = False, identify: bool = False, flex: bool = False,
-                  fs_ch: float | None = None,
-                  **plan_options):
-    """The occupied channels of the capture at ``path`` (``plan_options``: the keywords of ``dsp_plan.plan_find``).  The centre
-    frequency is taken from the file name where it is not given; without one the channels carry offsets only.  ``describe``:
-    a second pass over the mapped file measures every channel (``describe.ChannelDescriber``) and the
-    call returns ``(FindResult, DescribeResult)``.  ``keying`` (with ``describe``): the same pass also measures every channel's
-    keying and chooses its side decoders (``fs_ch``: an explicit channel rate of the targets that follow),
-    and the call returns ``(FindResult, DescribeResult, KeyingResult)``.  ``identify`` (with ``keying``): the keyed channels of
-    the usual digital rates are searched for their frame synchronisation words, and the call returns a
-    fourth result, ``ProtocolResult``.  ``flex`` (with ``identify``): the pages of the FLEX channels among them are decoded
-    (DESIGN.md section 26), and the call returns a fifth result, ``FlexResult``."""
-    if keying and not describe:
-        raise ValueError("keying=True needs describe=True")
-    if identify and not keying:
-        raise ValueError("identify=True needs keying=True")
-    if flex and not identify:
-        raise ValueError("flex=True needs identify=True")
+                  fs_ch: float | None = None, **options):
+    """The occupied channels of the capture at ``path``.  The centre frequency is taken from the file name where it is not
+    given; without one the channels carry offsets only.  ``options``: the keywords of ``dsp_plan.plan_find`` and the layers of a
+    second pass over the mapped file (``find_layers.FIND_LAYERS``, each with the one in front of it): ``describe=True`` measures
+    every channel (``describe.ChannelDescriber``), ``keying=True`` also its keying and its side decoders
+    (section 23; ``fs_ch``: an explicit channel rate of the targets that follow), ``identify=True`` searches the keyed channels of
+    the usual digital rates for their frame synchronisation words (section 25), ``flex=True`` decodes the pages of the FLEX
+    channels among them (section 26).  Returns the ``FindResult`` alone without a layer, else a tuple of it and every layer's
+    result in that order: ``DescribeResult``, ``KeyingResult``, ``ProtocolResult``, ``FlexResult``."""
+    layers = active_layers({layer.name: options.pop(layer.name, False) for layer in FIND_LAYERS})
     path = Path(path)
     info = iqio.probe_capture(path, input_format=input_format, input_container=input_container, input_sample_rate=input_sample_rate)
     if not info.sample_rate:
@@ -283,27 +276,24 @@ def find_channels(path, *, center_freq: float | None = None, input_format: str |
         n = min(n, int(float(max_seconds) * info.sample_rate))
     if center_freq is None:
         center_freq, _ = iqio.center_frequency_from_filename(path)
-    plan = P.plan_find(info.sample_rate, n, **plan_options)
+    plan = P.plan_find(info.sample_rate, n, **options)
     LOG.info("Finding channels: %d frames of %d bins (%.1f Hz), %d slices of %d frames.", plan.frames, plan.nfft, plan.bin_hz,
              plan.slices, plan.slice_frames)
-    finder = ChannelFinder(plan, info.fmt, iq_order)
     values = iqio.map_frames(info)
-    for a in range(0, n, BLOCK_FRAMES):
-        finder.process(np.ascontiguousarray(values[2 * a : 2 * min(n, a + BLOCK_FRAMES)]))
+
+    def blocks():
+        for a in range(0, n, BLOCK_FRAMES):
+            yield np.ascontiguousarray(values[2 * a : 2 * min(n, a + BLOCK_FRAMES)])
+
+    finder = ChannelFinder(plan, info.fmt, iq_order)
+    for block in blocks():
+        finder.process(block)
     result = finder.result(center_freq)
-    if not describe:
+    if not layers:
         return result
     from .describe import ChannelDescriber
 
-    describer = ChannelDescriber(plan, finder.finish(), result.channels, info.fmt, iq_order, keying=keying, identify=identify, flex=flex)
-    for a in range(0, n, BLOCK_FRAMES):
-        describer.process(np.ascontiguousarray(values[2 * a : 2 * min(n, a + BLOCK_FRAMES)]))
-    if flex:
-        return (result, describer.result(center_freq), describer.keying_result(center_freq, fs_ch),
-                describer.protocol_result(center_freq), describer.flex_result(center_freq))
-    if identify:
-        return (result, describer.result(center_freq), describer.keying_result(center_freq, fs_ch),
-                describer.protocol_result(center_freq))
-    if keying:
-        return result, describer.result(center_freq), describer.keying_result(center_freq, fs_ch)
-    return result, describer.result(center_freq)
+    describer = ChannelDescriber(plan, finder.finish(), result.channels, info.fmt, iq_order, **{layer.name: True for layer in layers[1:]})
+    for block in blocks():
+        describer.process(block)
+    return (result, *(layer.result(describer, center_freq, fs_ch) for layer in layers))

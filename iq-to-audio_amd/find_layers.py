@@ -1,0 +1,53 @@
+"""The layers of the second pass over a capture: what ``--find-describe``, ``--find-decode``, ``--find-identify`` and
+``--find-flex`` add to the finder's channel list (DESIGN.md sections 22, 23, 25 and 26).
+
+``FIND_LAYERS`` is the one place that lists them, in chain order: every row needs the row in front of it.  ``find_channels``,
+``ChannelDescriber`` and the CLI read a layer's keyword, flag, result and file suffix from its row; a new layer is a row here,
+a keyword on ``ChannelDescriber`` and its own module ("Adding a layer to the second pass").  Nothing heavy is
+imported here: the CLI reads the table before the GPU is touched."""
+from __future__ import annotations
+
+from dataclasses import dataclass
+from typing import Callable
+
+
+@dataclass(frozen=True)
+class FindLayer:
+    name: str  # the keyword of ``find_channels`` and, above the first row, of ``ChannelDescriber``
+    flag: str  # the CLI dest; the flag is ``--`` + the dest with dashes
+    section: int  # its DESIGN.md section
+    result: Callable  # (describer, center_freq, fs_ch) -> the layer's result object
+    suffix: str  # the result is written to ``<capture stem>.<suffix>.json``
+    inline: bool  # line i of ``result.lines()`` goes under channel i's line; False: all its lines follow the channel list
+    help: str  # the CLI flag's help text
+
+    @property
+    def option(self) -> str:
+        return "--" + self.flag.replace("_", "-")
+
+
+FIND_LAYERS = (
+    FindLayer("describe", "find_describe", 22, lambda d, fc, fs_ch: d.result(fc), "describe", True,
+              "Find the channels, then measure each one in a second pass: a label (nfm, am, ssb, wfm, carrier, unknown) "
+              "and a suggested --demod, --bw and frequency.  Implies --find-channels."),
+    FindLayer("keying", "find_decode", 23, lambda d, fc, fs_ch: d.keying_result(fc, fs_ch), "keying", True,
+              "Find and describe the channels and measure the keying of each one: whether its discriminator switches on "
+              "a symbol clock (fsk 512 ... 9600) and which side decoders fit it.  With --find-top N --find-auto every "
+              "target runs with its chosen decoders.  Implies --find-describe."),
+    FindLayer("identify", "find_identify", 25, lambda d, fc, fs_ch: d.protocol_result(fc), "protocols", True,
+              "Find, describe and key the channels, and name the protocol of every channel keyed at 1600, 2400, 3200 or "
+              "4800 baud by its frame synchronisation words: DMR, P25, YSF, NXDN or FLEX with its mode.  Implies "
+              "--find-decode."),
+    FindLayer("flex", "find_flex", 26, lambda d, fc, fs_ch: d.flex_result(fc), "flex", False,
+              "Find, describe, key and identify the channels, and decode the pages of every FLEX channel: capcode, type "
+              "and text, one line per page, also written to <capture stem>.flex.json.  Implies --find-identify."),
+)
+
+
+def active_layers(switches: dict) -> tuple:
+    """The rows switched on in ``switches`` (name -> bool), in chain order; ``ValueError`` for the first row (in chain order)
+    that is on while the row in front of it is not."""
+    for below, layer in zip(FIND_LAYERS, FIND_LAYERS[1:]):
+        if switches.get(layer.name) and not switches.get(below.name):
+            raise ValueError(f"{layer.name}=True needs {below.name}=True")
+    return tuple(layer for layer in FIND_LAYERS if switches.get(layer.name))

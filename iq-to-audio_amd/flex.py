@@ -481,3 +481,55 @@ class FlexDecoder:
         for name in ("v16", "v32"):
             st[name] = None if st[name] is None else st[name].cpu().numpy()
         return st
+
+
+# ---- the layer of the second pass (describe.py) ---------------------------------------------------------------------------------
+
+PLANE_RATES = (1600,)  # the families whose integrated plane ``finish_flex`` reads from section 25's dicts (``v``)
+
+
+def finish_flex(lanes, found) -> list:
+    """Per lane of the pass (``found``: its dict of ``identify.finish_identify``) the output of ``decode_stream`` with ``plan`` (the
+    ``FlexPlan``) and ``note``, or a dict of ``note`` alone where nothing is decoded: the channel is not of the 1600 family, its
+    rate does not fit or nothing was searched.  It reuses section 25's hits and plane and runs no second search."""
+    out = []
+    for lane, d in zip(lanes, found):
+        if d["rate"] != 1600:
+            out.append(dict(note="no flex channel"))
+            continue
+        try:
+            plan = P.plan_flex(lane.plan.fs_ch)
+        except ValueError:
+            plan = None
+        if plan is None or d["hits"] is None:
+            out.append(dict(note="rate does not fit" if plan is None or d["plan"] is None else "not measured"))
+            continue
+        st = decode_stream(I._stored_theta(lane), plan, lane.centre, d["hits"], I.patterns_for(1600), d["v"])
+        st.update(plan=plan, note="")
+        out.append(st)
+    return out
+
+
+def flex_result(channels, lanes, decoded, sample_rate: float, center_freq: float | None = None) -> FlexResult:
+    """The ``FlexResult`` of the pass: ``channels`` the finder's, ``decoded`` the dicts of ``finish_flex``."""
+    chans = []
+    for ch, lane, st in zip(channels, lanes, decoded):
+        freq = None if center_freq is None else center_freq + ch.offset_hz
+        if "rows" not in st:
+            chans.append(FlexChannel(offset_hz=ch.offset_hz, freq_hz=freq, note=st["note"]))
+        else:
+            chans.append(channel_of(st, lane.plan.fs_ch, lane.keyed_from, ch.offset_hz, freq))
+    return FlexResult(channels=chans, sample_rate=sample_rate, center_freq=center_freq)
+
+
+def stage_keys(describer, j: int, lane, keep: bool) -> dict:
+    """This layer's keys of ``ChannelDescriber.stages()`` for channel ``j``: ``flex_frames`` ((m, s, mode) per decoded frame, None
+    where the channel is no FLEX channel) and, with ``keep``, ``flex_words``, ``flex_raw``, ``flex_status`` ([F][5][4][88]),
+    ``flex_chosen``, ``flex_rec16``, ``flex_rec32``, ``flex_ok``, ``flex_v32`` and ``flex_plan``."""
+    x = describer.finish_flex()[j]
+    d = dict(flex_frames=x.get("rows"))
+    if keep and "rows" in x:
+        d.update(flex_plan=x["plan"], flex_rec16=x["rec16"], flex_rec32=x["rec32"], flex_ok=x["ok"], flex_words=x["fixed"],
+                 flex_raw=x["raw"], flex_status=x["status"], flex_chosen=x["chosen"],
+                 flex_v32=None if x["v32"] is None else x["v32"].cpu().numpy())
+    return d

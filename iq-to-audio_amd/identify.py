@@ -281,3 +281,54 @@ def protocol_of(keyed, hits, plan: P.IdentPlan | None, rate, note: str, keyed_fr
     first = None if d["first_m"] is None else (int(keyed_from or 0) + d["first_m"]) / plan.fs_ch
     return ChannelProtocol(**base, hits=d["hits"], pairs=d["pairs"], protocol=d["protocol"], confirmed=d["confirmed"], mode=d["mode"],
                            first_s=first, note="" if d["protocol"] is not None else "no sync word")
+
+
+# ---- the layer of the second pass (describe.py) ---------------------------------------------------------------------------------
+
+
+def _stored_theta(lane):
+    """A lane's stored discriminator stream as one device tensor: the single block, or the blocks joined.  Made anew by every
+    call and kept by none: the stream can approach 2^30 samples."""
+    return lane.stored[0] if len(lane.stored) == 1 else D.torch_mod().cat(lane.stored)
+
+
+def finish_identify(lanes, keyed, keep: bool, plane_rates=()) -> list:
+    """Per lane of the pass (``keyed``: its ``ChannelKeying``) a dict of its identification: ``rate`` (R, None where the channel is
+    not one to identify), ``plan`` (the ``IdentPlan``, None where the rate does not fit), ``note``, ``hits`` (int64[K][6], the kept
+    sync words sorted by (pattern, m), m counted from ``keyed_from``; None where nothing was searched), ``v`` (the integrated plane,
+    a device tensor) with ``keep`` or where a layer behind this one reads the planes of R (``plane_rates``), and ``score`` with
+    ``keep``.  The whole search runs here, on the stored stream as one piece."""
+    out = []
+    for lane, k in zip(lanes, keyed):
+        rate, plan, note = family_plan(k.label, k.baud if k.label is not None else None, lane.plan.fs_ch)
+        d = dict(rate=rate, plan=plan, note=note, hits=None)
+        if plan is not None and lane.centre is not None and lane.stored:
+            theta = _stored_theta(lane)
+            if int(theta.numel()) > P.IDENT_MAX_N:
+                raise ValueError(f"a stored stream of {int(theta.numel())} samples is longer than 2^30")
+            v = integrate(theta, plan, lane.centre)
+            score, d["hits"] = search(v, plan, patterns_for(rate))
+            if keep or rate in plane_rates:
+                d["v"] = v
+            if keep:
+                d["score"] = score
+        out.append(d)
+    return out
+
+
+def protocols(lanes, keyed, found) -> list:
+    """The ``ChannelProtocol`` of every lane from its ``ChannelKeying`` and its dict of ``finish_identify``."""
+    return [protocol_of(k, d["hits"], d["plan"], d["rate"], d["note"], lane.keyed_from) for k, d, lane in zip(keyed, found, lanes)]
+
+
+def stage_keys(describer, j: int, lane, keep: bool) -> dict:
+    """This layer's keys of ``ChannelDescriber.stages()`` for channel ``j``: ``ident_rate``, ``ident_plan``, ``hits`` (int64[K][6] or
+    None) and, with ``keep``, ``stored`` (float32, the stored theta: ``theta`` from ``keyed_from`` on) and, of the identified
+    channels, ``v`` (int32[n]) and ``score`` (int32[patterns][n])."""
+    i = describer.finish_identify()[j]
+    d = dict(ident_rate=i["rate"], ident_plan=i["plan"], hits=i["hits"])
+    if keep:
+        d["stored"] = D.torch_mod().cat(lane.stored).cpu().numpy() if lane.stored else np.zeros(0, dtype=np.float32)
+        if "v" in i:
+            d.update(v=i["v"].cpu().numpy(), score=i["score"].cpu().numpy())
+    return d

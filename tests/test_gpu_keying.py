@@ -127,7 +127,7 @@ def test_labels_and_decoders(A, gpu):
 
 def test_cuts_of_a_stream_change_no_bit(A, gpu):
     from iq_to_audio_amd import _dev as D
-    from iq_to_audio_amd.describe import add_keying_rows
+    from iq_to_audio_amd.keying import add_keying_rows
 
     describer = A.ChannelDescriber(gpu["plan"], gpu["fin"], gpu["found"].channels, "s16", "iq", keying=True)
     lanes = describer.lanes()
@@ -149,7 +149,7 @@ def test_centre_comes_with_the_first_block_of_1024_pairs(A, gpu):
     """A channel whose gate comes on late: the calls in front of the one that brings the describe rows to 1024 pairs are not
     keyed, that call and the ones behind it are; a channel that never gets there has no figures."""
     from iq_to_audio_amd import _dev as D
-    from iq_to_audio_amd import describe as DS
+    from iq_to_audio_amd import keying as KY
 
     plan = gpu["plan"]
     describer = A.ChannelDescriber(plan, gpu["fin"], gpu["found"].channels, "s16", "iq", keep_stages=True, keying=True)
@@ -177,7 +177,7 @@ def test_centre_comes_with_the_first_block_of_1024_pairs(A, gpu):
     theta = D.torch_mod().cat(lane.theta).cpu().numpy()
     kp = K.plan(dp.fs_ch)
     want = K.stream_rows(theta, calls, c, start, kp["incs"], gate, **find)
-    got = DS.add_keying_rows([(first, r.cpu().numpy()) for first, r in lane.krows], -(-at // 2048))
+    got = KY.add_keying_rows([(first, r.cpu().numpy()) for first, r in lane.krows], -(-at // 2048))
     np.testing.assert_array_equal(got, want)
     assert want[: start // 2048].sum() == 0 and want[:, 0].sum() == st["z"].size - start  # the 510 samples of the second call are not keyed
     # never 1024 pairs: no centre, no rows, and the channel reads unkeyed without figures
@@ -186,7 +186,7 @@ def test_centre_comes_with_the_first_block_of_1024_pairs(A, gpu):
     lane.sh, lane.gate_dev = gpu["stages"][2]["sh"], D.from_numpy(lane.gate)
     describer.feed(lane, D.from_numpy(gpu["stages"][2]["z"]))
     assert lane.centre is None and lane.krows == [] and lane.keyed_from is None
-    k = DS.key_channel(gpu["result"].channels[2], lane.kplan, None, lane.centre, FS)
+    k = KY.key_channel(gpu["result"].channels[2], lane.kplan, None, lane.centre, FS)
     assert (k.label, k.coh, k.crossings, k.decoders) == ("unkeyed", [None] * 7, 0, ["ax25", "tones"])
 
 

@@ -233,7 +233,7 @@ P_INCS_LOW = K.plan(12000.0)["incs"]  # 3200, 4800 and 9600 skipped
 def test_the_plan_the_package_passes(A, table):
     """The package's own wrapper on a describer's plans: the same rows."""
     from iq_to_audio_amd import _dev as D
-    from iq_to_audio_amd import describe as DS
+    from iq_to_audio_amd import keying as KY
     from iq_to_audio_amd import dsp_plan as P
 
     assert P_INCS_LOW == P.plan_keying(12000.0).incs and P_INCS_LOW[4:] == (0, 0, 0)
@@ -243,7 +243,7 @@ def test_the_plan_the_package_passes(A, table):
     g = (np.random.default_rng(9).random(fp.slices) < 0.8).astype(np.uint8)
     theta = _wave(11, 5000)
     theta_dev, front_dev, gate_dev = D.from_numpy(theta), D.from_numpy(np.array([0.25], dtype=np.float32)), D.from_numpy(g)
-    first, rows = DS.accumulate_keying(theta_dev, 3000, front_dev, 17, kp, table, dp, fp, gate_dev)
+    first, rows = KY.accumulate_keying(theta_dev, 3000, front_dev, 17, kp, table, dp, fp, gate_dev)
     want = K.rows(theta, 3000, np.float32(0.25), 17, K.plan(dp.fs_ch)["incs"], g, D=dp.decimation, delay=dp.delay, hop=fp.hop, T=fp.slice_frames, F=fp.frames)
     assert first == 1
     np.testing.assert_array_equal(rows.cpu().numpy().reshape(-1, 16), want)

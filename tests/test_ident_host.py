@@ -29,6 +29,7 @@ K = IM.K
 import iq_to_audio_amd as A  # noqa: E402
 from iq_to_audio_amd import cli  # noqa: E402
 from iq_to_audio_amd import describe as DS  # noqa: E402
+from iq_to_audio_amd import keying as KY  # noqa: E402
 from iq_to_audio_amd import dsp_plan as P  # noqa: E402
 from iq_to_audio_amd import identify as I  # noqa: E402
 
@@ -150,7 +151,7 @@ def test_package_rules_equal_the_oracle(model):
     for name, k, nm, d in zip(IM.NAMES, model["keyed"], model["named"], model["described"]):
         rate, plan, note = I.family_plan(k["label"], k["baud"], d["plan"]["fs_ch"])
         assert rate == nm["rate"]
-        keyed = DS.ChannelKeying(offset_hz=1.0, freq_hz=None, described="nfm", fs_ch=d["plan"]["fs_ch"], bauds=[], coh=[], rate_hz=None, crossings=0,
+        keyed = KY.ChannelKeying(offset_hz=1.0, freq_hz=None, described="nfm", fs_ch=d["plan"]["fs_ch"], bauds=[], coh=[], rate_hz=None, crossings=0,
                                  pairs=0, centre=k["c"], label=k["label"], baud=k["baud"], decoders=[], bw=None, note="")
         if rate is None:
             got = I.protocol_of(keyed, None, plan, rate, note, None)

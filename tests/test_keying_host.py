@@ -30,6 +30,7 @@ M = K.M
 import iq_to_audio_amd as A  # noqa: E402
 from iq_to_audio_amd import cli  # noqa: E402
 from iq_to_audio_amd import describe as DS  # noqa: E402
+from iq_to_audio_amd import keying as KY  # noqa: E402
 from iq_to_audio_amd import dsp_plan as P  # noqa: E402
 
 FIND = dict(D=40, delay=1600, hop=4096, T=5, F=1170)  # a find plan's figures: S = 234 slices of 5 frames
@@ -97,7 +98,7 @@ def test_cut_windows_add_up():
     for n in cuts:
         parts.append((pos // 2048, K.rows(theta[pos : pos + n], pos, None if pos == 0 else theta[pos - 1], 40, kp["incs"], g, **FIND)))
         pos += n
-    np.testing.assert_array_equal(DS.add_keying_rows(parts, 5), whole)
+    np.testing.assert_array_equal(KY.add_keying_rows(parts, 5), whole)
     # without the front value the pair across the cut is lost: the front is what makes the cut invisible
     lost = K.add_by_window([(0, K.rows(theta[:100], 0, None, 40, kp["incs"], g, **FIND)), (0, K.rows(theta[100:2048], 100, None, 40, kp["incs"], g, **FIND))], 1)
     assert lost[0, 0] in (whole[0, 0], whole[0, 0] - 1)
@@ -109,7 +110,7 @@ def test_cut_windows_add_up():
 def test_centre_rule():
     assert [K.centre(cr, ci) for cr, ci in ((1, 0), (0, 1), (-1, 0), (1, 1), (1000, -1))] == [0, 6434, 12868, 3217, -4]
     for cr, ci in ((1, 0), (0, 1), (-1, 0), (1, 1), (1000, -1), (-3, -4), (123456789012345, 98765432109876)):
-        assert DS.keying_centre(cr, ci) == K.centre(cr, ci) and abs(K.centre(cr, ci)) <= 12868
+        assert KY.keying_centre(cr, ci) == K.centre(cr, ci) and abs(K.centre(cr, ci)) <= 12868
     # the first call after which the describe rows hold 1024 pairs gives the centre, and the keying begins with that call
     row = lambda np_, cr, ci: [0, np_, 0, 0, 0, cr, ci, 0]  # noqa: E731
     rows = np.array([row(500, 10, 0), row(400, 10, 0), row(100, 0, 20), row(24, 0, 0), row(2000, -500, 0)], dtype=np.int64)
@@ -157,7 +158,7 @@ def test_model_capture_gives_its_runs_and_labels(model):
 
 
 def test_model_capture_decoders(model):
-    from iq_to_audio_amd.describe import decoders_for
+    from iq_to_audio_amd.keying import decoders_for
 
     for fc in (K.FC_AIR, K.FC_OUT):
         for (name, offset, lab, key, want), d, k in zip(K.CHANNELS, model["described"], model["keyed"]):
@@ -179,9 +180,9 @@ def test_model_capture_decoders(model):
 def test_package_host_arithmetic_equals_the_oracle(model):
     for name, d, k in zip(K.NAMES, model["described"], model["keyed"]):
         kp = P.plan_keying(d["plan"]["fs_ch"])
-        got, want = DS.keying_figures(k["rows"], kp), K.figures(k["rows"], k["plan"])
+        got, want = KY.keying_figures(k["rows"], kp), K.figures(k["rows"], k["plan"])
         assert got == want, name
-        assert DS.keying_label(got["coh"], got["rate_hz"], got["crossings"], kp) == K.rule(want["coh"], want["rate_hz"], want["crossings"], k["plan"])
+        assert KY.keying_label(got["coh"], got["rate_hz"], got["crossings"], kp) == K.rule(want["coh"], want["rate_hz"], want["crossings"], k["plan"])
 
 
 def _about(label: str, demod=None, bw=None, tuned=None, freq=455.8e6):
@@ -201,7 +202,7 @@ def _rows(per_window, fs_ch=48000.0, baud_at=1, coherent=True, pairs=2047):
 
 def test_every_rule_at_its_boundary():
     kp = P.plan_keying(48000.0)
-    lab = lambda coh, rate, K_: DS.keying_label(coh, rate, K_, kp)  # noqa: E731
+    lab = lambda coh, rate, K_: KY.keying_label(coh, rate, K_, kp)  # noqa: E731
     none = [0.0] * 7
     at = lambda k, v: none[:k] + [v] + none[k + 1 :]  # noqa: E731
     # 256 crossings
@@ -218,48 +219,48 @@ def test_every_rule_at_its_boundary():
     assert lab([0.9] * 7, 256.0, 1000) == ("fsk 512", 512)
     # a skipped candidate is never taken, whatever stands in its place
     low = P.plan_keying(12000.0)
-    assert DS.keying_label([0.0, 0.0, 0.0, 0.0, 0.9, 0.9, 0.9], 1600.0, 1000, low) == ("unkeyed", None)
-    assert DS.keying_label([0.0, 0.0, 0.0, 0.0, None, None, None], 1600.0, 1000, low) == ("unkeyed", None)
+    assert KY.keying_label([0.0, 0.0, 0.0, 0.0, 0.9, 0.9, 0.9], 1600.0, 1000, low) == ("unkeyed", None)
+    assert KY.keying_label([0.0, 0.0, 0.0, 0.0, None, None, None], 1600.0, 1000, low) == ("unkeyed", None)
     # the figures from rows: crossings all on one phase give 1, none coherent gives -1 / (K - 1) per window, den = 0 gives None
-    f = DS.keying_figures(_rows([20, 30, 10]), kp)
+    f = KY.keying_figures(_rows([20, 30, 10]), kp)
     assert f["coh"][1] == 1.0 and f["crossings"] == 60 and f["pairs"] == 3 * 2047 and f["rate_hz"] == 60 / (3 * 2047) * 48000.0
     assert f["coh"][0] == (0 - 1024 ** 2 * 60) / (1024 ** 2 * (20 * 19 + 30 * 29 + 10 * 9))
-    assert DS.keying_figures(_rows([1, 1, 0]), kp)["coh"] == [None] * 7 and DS.keying_figures(_rows([]), kp)["rate_hz"] is None
-    assert DS.keying_figures(_rows([20]), low)["coh"][4:] == [None] * 3
+    assert KY.keying_figures(_rows([1, 1, 0]), kp)["coh"] == [None] * 7 and KY.keying_figures(_rows([]), kp)["rate_hz"] is None
+    assert KY.keying_figures(_rows([20]), low)["coh"][4:] == [None] * 3
     # the largest window: 2048 crossings on one phase, exact in Python integers
-    assert DS.keying_figures(_rows([2048] * 4, pairs=2048), kp)["coh"][1] == 1.0
+    assert KY.keying_figures(_rows([2048] * 4, pairs=2048), kp)["coh"][1] == 1.0
 
 
 def test_key_channel_and_the_dropped_decoder(caplog):
     kp = P.plan_keying(48000.0)
     nfm = _about("nfm", "nfm", 12500.0, 455.8e6)
-    k = DS.key_channel(nfm, kp, _rows([30] * 10), 12, 2.4e6)
+    k = KY.key_channel(nfm, kp, _rows([30] * 10), 12, 2.4e6)
     assert (k.label, k.baud, k.decoders, k.bw, k.centre, k.crossings) == ("fsk 1200", 1200, ["pocsag"], 12500.0, 12, 300)
     assert k.line() == f"    keying: fsk 1200 (coh 1.00, {300 / 20470 * 48000.0:.0f} crossings/s) -> --pocsag"
-    k = DS.key_channel(nfm, kp, _rows([300] * 10, baud_at=6), 0, 2.4e6)
+    k = KY.key_channel(nfm, kp, _rows([300] * 10, baud_at=6), 0, 2.4e6)
     assert (k.label, k.decoders, k.bw) == ("fsk 9600", ["ais"], 25000.0) and k.line().endswith("-> --ais --bw 25000")
     # fs_ch as the pipeline resolves it: an explicit --fs-ch 24000 leaves AIS too few samples per bit, and the decoder is dropped
-    with caplog.at_level(logging.INFO, logger="iq_to_audio_amd.describe"):
-        k = DS.key_channel(nfm, kp, _rows([300] * 10, baud_at=6), 0, 2.4e6, fs_ch=24000.0)
+    with caplog.at_level(logging.INFO, logger="iq_to_audio_amd.keying"):
+        k = KY.key_channel(nfm, kp, _rows([300] * 10, baud_at=6), 0, 2.4e6, fs_ch=24000.0)
     assert (k.label, k.decoders) == ("fsk 9600", []) and "--ais dropped: AIS at 9600 bit/s needs 5 to 100 samples per bit" in caplog.text
-    assert DS.target_rate(2.4e6, "nfm") == 96000.0 and DS.target_rate(2.4e6, "wfm") == 480000.0 and DS.target_rate(2.4e6, "am", 24000.0) == 24000.0
-    assert DS.usable_decoders(["rds"], 96000.0) == [] and DS.usable_decoders(["rds"], 480000.0) == ["rds"]
-    assert DS.usable_decoders(["ax25", "tones"], 8000.0) == ["tones"]
+    assert KY.target_rate(2.4e6, "nfm") == 96000.0 and KY.target_rate(2.4e6, "wfm") == 480000.0 and KY.target_rate(2.4e6, "am", 24000.0) == 24000.0
+    assert KY.usable_decoders(["rds"], 96000.0) == [] and KY.usable_decoders(["rds"], 480000.0) == ["rds"]
+    assert KY.usable_decoders(["ax25", "tones"], 8000.0) == ["tones"]
     for baud_at, per, note in ((2, 30, "FLEX rates: no decoder here"), (5, 100, "4800 baud (DMR / P25 / NXDN class): no decoder here")):
-        k = DS.key_channel(nfm, kp, _rows([per] * 10, baud_at=baud_at), 0, 2.4e6)
+        k = KY.key_channel(nfm, kp, _rows([per] * 10, baud_at=baud_at), 0, 2.4e6)
         assert k.decoders == [] and k.line().endswith("-> " + note), k.line()
     # unkeyed, and a channel that never held 1024 pairs: no figures, unkeyed
-    k = DS.key_channel(nfm, kp, _rows([30] * 10, coherent=False), 0, 2.4e6)
+    k = KY.key_channel(nfm, kp, _rows([30] * 10, coherent=False), 0, 2.4e6)
     assert (k.label, k.decoders) == ("unkeyed", ["ax25", "tones"]) and "best coh" in k.line() and k.line().endswith("-> --ax25 --tones")
-    k = DS.key_channel(nfm, kp, None, None, 2.4e6)
+    k = KY.key_channel(nfm, kp, None, None, 2.4e6)
     assert (k.label, k.baud, k.centre, k.coh, k.rate_hz, k.crossings) == ("unkeyed", None, None, [None] * 7, None, 0) and "not measured" in k.line()
     # the other labels are not keyed FM
-    k = DS.key_channel(_about("wfm", "wfm", 250000.0, 98.1e6), kp, _rows([30] * 10), 0, 2.4e6)
+    k = KY.key_channel(_about("wfm", "wfm", 250000.0, 98.1e6), kp, _rows([30] * 10), 0, 2.4e6)
     assert (k.label, k.decoders) == (None, ["rds"]) and k.line() == "    keying: not measured (wfm) -> --rds"
-    assert DS.key_channel(_about("am", "am", 10000.0, 131.55e6), kp, _rows([3]), 0, 2.4e6).decoders == ["acars"]
-    assert DS.key_channel(_about("am", "am", 10000.0, 455.8e6), kp, _rows([3]), 0, 2.4e6).decoders == []
-    assert DS.key_channel(_about("unknown"), kp, None, None, 2.4e6).line() == "    keying: not measured (unknown) -> no decoder"
-    res = A.KeyingResult(channels=[DS.key_channel(nfm, kp, _rows([30] * 10), 12, 2.4e6), DS.key_channel(_about("unknown"), kp, None, None, 2.4e6)],
+    assert KY.key_channel(_about("am", "am", 10000.0, 131.55e6), kp, _rows([3]), 0, 2.4e6).decoders == ["acars"]
+    assert KY.key_channel(_about("am", "am", 10000.0, 455.8e6), kp, _rows([3]), 0, 2.4e6).decoders == []
+    assert KY.key_channel(_about("unknown"), kp, None, None, 2.4e6).line() == "    keying: not measured (unknown) -> no decoder"
+    res = A.KeyingResult(channels=[KY.key_channel(nfm, kp, _rows([30] * 10), 12, 2.4e6), KY.key_channel(_about("unknown"), kp, None, None, 2.4e6)],
                          sample_rate=2.4e6, center_freq=455.5e6)
     assert A.KeyingResult.from_json(res.to_json()) == res and len(res.lines()) == 2
     import json
@@ -311,10 +312,11 @@ def test_cli_refuses_misuse(capsys):
 
 def test_package_surface():
     for name in ("ChannelKeying", "KeyingResult"):
-        assert getattr(A, name) is getattr(DS, name)
+        assert getattr(A, name) is getattr(KY, name)
     assert A.plan_keying is P.plan_keying and A.KEYING_BAUDS == (512, 1200, 1600, 2400, 3200, 4800, 9600)
-    text = Path(DS.__file__).read_text()
-    assert "scipy" not in text and "import oracle" not in text and "from oracle" not in text
+    for module in (DS, KY):
+        text = Path(module.__file__).read_text()
+        assert "scipy" not in text and "import oracle" not in text and "from oracle" not in text
     plan = P.plan_find(2.4e6, 100_000)
     fin = dict(runs=np.zeros((0, 8), dtype=np.int64), on=np.zeros((0, plan.slices), dtype=np.uint8))
     with pytest.raises(ValueError, match="without keying=True"):
