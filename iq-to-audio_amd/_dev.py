@@ -2,6 +2,8 @@
 all arithmetic happens in the HIP library behind ``_native``."""
 from __future__ import annotations
 
+import threading
+
 import numpy as np
 
 from . import _native as N
@@ -30,6 +32,7 @@ class on_stream:
 
 
 _SIDE_STREAMS: dict = {}
+_SIDE_STREAMS_LOCK = threading.Lock()
 
 
 def side_stream(role: str, index: int | None = None):
@@ -40,13 +43,33 @@ def side_stream(role: str, index: int | None = None):
     stream gets depends on every stream the process has used before (measured: config 4's unit 1.17 -> 1.33 ms, config 3
     13.6 -> 15.3 ms per capture after an unrelated runner had taken four more streams).  A fixed,
     small set of streams keeps the mapping the same for every runner of the process.  Sharing costs nothing in
-    correctness (stream order only adds dependencies) and runners are used one at a time."""
+    correctness (stream order only adds dependencies).
+
+    Threads: concurrent first requests for one (device, role) get ONE stream (the table is filled under a lock;
+    ``tests/test_threads_host.py``).  What the streams are shared BY, the resident batch runners, stays single-threaded by
+    design: they keep the current stream and their events per runner, so a process drives its runners from one thread
+    at a time ("Threading contract").  Pipelines and stage objects do not use these streams."""
     torch = torch_mod()
     key = (torch.cuda.current_device() if index is None else int(index), role)
     s = _SIDE_STREAMS.get(key)
     if s is None:
-        s = _SIDE_STREAMS[key] = torch.cuda.Stream(device=key[0])
+        with _SIDE_STREAMS_LOCK:
+            s = _SIDE_STREAMS.get(key)
+            if s is None:
+                s = _SIDE_STREAMS[key] = torch.cuda.Stream(device=key[0])
     return s
+
+
+def uploads_complete() -> None:
+    """Wait until everything this thread has queued on its current stream has completed.  For objects that are about to
+    be PUBLISHED to other host threads through a process-wide cache (planned channelizer kernels, resampler tables): their
+    small uploads are asynchronous copies on the builder's stream, and a thread that takes the object from the cache
+    launches on a stream of its own, which nothing orders behind those copies.  Once per configuration, off the hot path.
+    (Nothing can be waited for inside a stream capture; there the capturing thread is the only user.)"""
+    torch = torch_mod()
+    if torch.cuda.is_current_stream_capturing():
+        return
+    torch.cuda.current_stream().synchronize()
 
 
 def current_raw_stream() -> int:
@@ -93,9 +116,11 @@ def to_device(x, dtype: str):
 # Small host arrays are staged through a pool of persistent pinned buffers and copied asynchronously:
 # a pageable `.to(device)` synchronises the stream (the host could not run ahead of the GPU), and
 # `Tensor.pin_memory()` costs ~2.6 ms per call on this stack.  A slot is reused once the event recorded
-# after its last copy has completed.
+# after its last copy has completed.  A slot is [pinned buffer, event of its last copy, claimed]: uploads come from any
+# host thread, so "find a free slot and mark it claimed" happens under _PIN_LOCK; the staging write and the copy do not.
 _PIN_LIMIT = 1 << 20
 _pin_pool: dict[int, list] = {}
+_PIN_LOCK = threading.Lock()
 
 
 def _upload(torch, arr: np.ndarray):
@@ -109,22 +134,32 @@ def _upload(torch, arr: np.ndarray):
                 return torch.from_numpy(arr).to(device())
         return torch.from_numpy(arr).to(device())
     cls = max(256, 1 << (nbytes - 1).bit_length())
-    slots = _pin_pool.setdefault(cls, [])
     slot = None
-    for cand in slots:
-        if cand[1] is None or cand[1].query():
-            slot = cand
-            break
-    if slot is None:
-        slot = [torch.empty(cls, dtype=torch.uint8).pin_memory(), None]
-        slots.append(slot)
-    staged = slot[0][:nbytes]
-    staged.numpy()[:] = arr.reshape(-1).view(np.uint8)
-    dev = torch.empty(nbytes, dtype=torch.uint8, device=device())
-    dev.copy_(staged, non_blocking=True)
-    ev = torch.cuda.Event()
-    ev.record()
-    slot[1] = ev
+    with _PIN_LOCK:
+        slots = _pin_pool.setdefault(cls, [])
+        for cand in slots:
+            if not cand[2] and (cand[1] is None or cand[1].query()):
+                slot = cand
+                break
+        if slot is None:  # (pinned outside the lock: ~2.6 ms; the claimed entry keeps the place)
+            slot = [None, None, True]
+            slots.append(slot)
+        slot[2] = True
+    try:
+        if slot[0] is None:
+            slot[0] = torch.empty(cls, dtype=torch.uint8).pin_memory()
+        staged = slot[0][:nbytes]
+        staged.numpy()[:] = arr.reshape(-1).view(np.uint8)
+        dev = torch.empty(nbytes, dtype=torch.uint8, device=device())
+        dev.copy_(staged, non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record()
+        slot[1] = ev  # (before the claim goes: whoever sees the slot unclaimed sees this copy's event)
+    except BaseException:
+        with _PIN_LOCK:  # a slot whose copy may or may not have been queued is not handed out again
+            _pin_pool[cls][:] = [s for s in _pin_pool[cls] if s is not slot]
+        raise
+    slot[2] = False
     return dev.view(getattr(torch, arr.dtype.name)).reshape(arr.shape)
 
 

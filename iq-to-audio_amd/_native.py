@@ -9,6 +9,7 @@ from __future__ import annotations
 
 import ctypes
 import subprocess
+import threading
 from ctypes import c_double, c_float, c_int32, c_int64, c_uint64, c_void_p
 from pathlib import Path
 
@@ -222,6 +223,7 @@ _SIGNATURES = {
 EXPORTS = tuple(_SIGNATURES)
 
 _lib = None
+_LIB_LOCK = threading.Lock()  # the first call of lib() may come from several host threads at once: one handle, bound once
 
 
 def build(force: bool = False) -> Path:
@@ -235,9 +237,15 @@ def build(force: bool = False) -> Path:
 
 def lib() -> ctypes.CDLL:
     """The loaded library; raises RuntimeError (never falls back) when it is unavailable."""
-    global _lib
     if _lib is not None:
         return _lib
+    with _LIB_LOCK:
+        return _lib if _lib is not None else _load()
+
+
+def _load() -> ctypes.CDLL:
+    """Load the library and bind every signature (``lib`` holds ``_LIB_LOCK``); the handle is published last."""
+    global _lib
     if not LIB_PATH.exists():
         raise RuntimeError(
             f"HIP hot-path library not built: {LIB_PATH} is missing. Run `python -c 'import __graft_entry__ as g; "

@@ -269,6 +269,7 @@ class Resampler48k:
             table = self._TABLES.get(key)
         if table is None:
             table = D.from_numpy(self.plan.table.reshape(-1))
+            D.uploads_complete()  # before another thread (on another stream) can take the table from _TABLES
             with _KERNEL_CACHE_LOCK:
                 if len(self._TABLES) >= 16:
                     self._TABLES.clear()

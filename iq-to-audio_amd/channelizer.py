@@ -159,6 +159,7 @@ class _ChannelKernel:
                 self._passes = [(ps, None if ring else N.MfmaParams(
                     reserved=0, unit=mp.groups[ps.group].unit, c_re=ps.c_re, c_im=ps.c_im, q_group=mp.groups[ps.group].q,
                     k_first=ps.k_first, k_count=ps.k_count)) for ps in mp.passes]
+                D.uploads_complete()  # the fragments' copies: this kernel is shared through _KERNEL_CACHE (see there)
                 self.mfma = mp
             return self.mfma
 
@@ -347,6 +348,7 @@ def _cached_kernel(taps: np.ndarray, *, sample_rate: float, freq_offset: float, 
     plan = P.plan_channel(taps, sample_rate=sample_rate, freq_offset=freq_offset, mix_sign=mix_sign,
                           decimation=decimation, fmt=fmt, iq_order=iq_order, padded_len=lpad)
     kernel = _ChannelKernel(plan, exact, precision)
+    D.uploads_complete()  # the tap window's copy, before another thread (on another stream) can take the kernel from the cache
     with _KERNEL_CACHE_LOCK:
         _KERNEL_CACHE[key] = (raw, plan, kernel)
         while len(_KERNEL_CACHE) > _KERNEL_CACHE_MAX:

@@ -92,6 +92,11 @@ class _BlockStager:
             th, slot = self.pending[0], self.pending[1]
             th.join()
         else:
+            if self.pending is not None:
+                # a prefetch for other bounds is filling the very buffer this fetch is about to fill (both take slot ^ 1):
+                # let the helper finish first.  (The pipeline's block loop always fetches what it prefetched; this is
+                # for other callers of the class.)
+                self.pending[0].join()
             slot = self.slot ^ 1
             if self.events[slot] is not None:
                 self.events[slot].synchronize()
