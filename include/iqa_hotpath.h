@@ -905,6 +905,36 @@ int iqa_flex_words(const void *plane_dev, int64_t n, const void *frames_dev, int
                    const void *offsets_dev, void *fixed_dev, void *raw_dev, void *status_dev, void *stream);
 
 /* ------------------------------------------------------------------------- *
+ * The link control and calls of a DMR channel (--find-dmr) *
+ * ------------------------------------------------------------------------- */
+
+#define IQA_DMR_OFFSETS 144 /* o[i] = rint(i sps), i = -66 .. 77, o[i] at index 66 + i */
+#define IQA_DMR_WORDS 9     /* uint32 words of a sliced burst: 24 CACH bits, then 264 burst bits */
+#define IQA_DMR_RECORD 8    /* int32 values of a decoded burst */
+/* The levels and the bits of K sync hits.  plane_dev: int32[n], iqa_ident_integrate's output at 4800 symbols/s (|v| <=
+ * 64 * 65534).  hits_dev: int64[K][3], (m, s, kind): m where sync symbol 0 ends, s the sign of the hit (negative: -1, else +1),
+ * kind 0 bs voice, 1 bs data, 2 ms voice, 3 ms data (its two low bits are read).  offsets (host): the IQA_DMR_OFFSETS sample
+ * offsets of the symbols -66 .. 77, ascending in steps of at most IQA_IDENT_MAX_SPS + 1, o[0] (index 66) = 0.  The burst is
+ * symbols -54 .. 77 and is valid iff all their instants lie in 0 .. n - 1; the CACH is symbols -66 .. -55 and is valid iff
+ * the kind is a bs one and all its instants do.  Sigma = sum of x_i = plane[m + o[i]] over the sync symbols i = 0 .. 23; A = s
+ * sum of sgn_i x_i, sgn_i the sign of symbol i of the bs (kinds 0, 1) or ms (kinds 2, 3) voice sync word.  A symbol at the
+ * instant t reads as d = 24 plane[t] - Sigma: its first bit (d < 0), its second (3 |d| >= 2 A).  bits_dev: uint32[K][9], the 24
+ * CACH bits then the 264 burst bits, the first sent bit the MSB of word 0; every bit of a burst that is not valid is 0, and so
+ * are the CACH bits of a CACH that is not.  levels_dev: int64[K][3]: Sigma, A (both 0 for a burst that is not valid), flags (bit
+ * 0 burst valid, bit 1 CACH valid).  Every instant is checked against 0 .. n - 1 before it is read.  n <= 2^30, K <= 2^20.
+ * n = 0 or K = 0 returns IQA_OK and touches no pointer. */
+int iqa_dmr_slice(const void *plane_dev, int64_t n, const void *hits_dev, int64_t K, const int32_t offsets[IQA_DMR_OFFSETS],
+                  void *bits_dev, void *levels_dev, void *stream);
+/* The TACT, the slot type and the BPTC(196,96) payload of K sliced bursts.  bits_dev: uint32[K][9] as iqa_dmr_slice writes
+ * them; kinds_dev: uint8[K] (the two low bits are read).  info_dev: uint32[K][3], the 96 information bits, the first the MSB of
+ * word 0 (0 where the payload is not read).  rec_dev: int32[K][8]: the TACT status (0 clean, 1 one bit restored, 4 an ms kind)
+ * and nibble (AT, TC, LCSS1, LCSS0); the slot type's status (0 clean, 1 corrected at a distance of 1 .. 3, 2 refused with the
+ * raw top byte kept, 4 a voice kind), distance and byte (colour code, data type); the payload's status (0 clean, 1 corrected,
+ * 2 failed, 4 not read: a voice kind or a refused slot type), flips and rounds.  The codes are DESIGN.md section 29's.
+ * K <= 2^20.  K = 0 returns IQA_OK and touches no pointer. */
+int iqa_dmr_decode(const void *bits_dev, const void *kinds_dev, int64_t K, void *info_dev, void *rec_dev, void *stream);
+
+/* ------------------------------------------------------------------------- *
  * Carrier squelch of a run's targets (--squelch)       *
  * ------------------------------------------------------------------------- */
 

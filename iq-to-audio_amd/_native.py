@@ -207,6 +207,8 @@ _SIGNATURES = {
     "iqa_flex_frames": (ctypes.c_int, [c_void_p, c_int64, c_void_p, c_int64, ctypes.POINTER(c_int32), c_void_p, c_void_p]),
     "iqa_flex_words": (ctypes.c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p,
                                       c_void_p, c_void_p]),
+    "iqa_dmr_slice": (ctypes.c_int, [c_void_p, c_int64, c_void_p, c_int64, ctypes.POINTER(c_int32), c_void_p, c_void_p, c_void_p]),
+    "iqa_dmr_decode": (ctypes.c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
     "iqa_gate_cells": (c_int64, [c_int64, c_int64]),
     "iqa_gate_power": (ctypes.c_int, [c_void_p, c_int64, c_int64, c_int32, c_void_p, c_void_p]),
     "iqa_gate_add_cells": (ctypes.c_int, [c_void_p, c_int64, c_void_p, c_void_p]),

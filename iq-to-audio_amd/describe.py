@@ -12,7 +12,7 @@ library the calls raise ``RuntimeError``.
 The layers above this one (``find_layers.FIND_LAYERS``, each in the module of its name) ride on the same pass: with ``keying=True``
 it also takes every channel's discriminator and, once the channel holds 1024 gated pairs, its keying rows (``keying.py``); with
 ``identify=True`` it keeps that discriminator output for the sync-word search of ``identify.py``, whose hits ``flex.py`` decodes
-with ``flex=True``."""
+with ``flex=True`` and ``dmr.py`` with ``dmr=True``."""
 from __future__ import annotations
 
 import math
@@ -24,6 +24,7 @@ import numpy as np
 from . import _dev as D
 from . import _native as N
 from . import dsp_plan as P
+from . import dmr as DM
 from . import flex as X
 from . import identify as I
 from . import keying as KY
@@ -242,7 +243,7 @@ def add_rows(rows: np.ndarray) -> tuple:
     return tuple((int(h) << 32) + int(l) for h, l in zip(high, low))
 
 
-_MODULES = {m.__name__.rpartition(".")[2]: m for m in (KY, I, X)}  # a layer above the first lives in the module of its keyword
+_MODULES = {m.__name__.rpartition(".")[2]: m for m in (KY, I, X, DM)}  # a layer above the first lives in the module of its keyword
 
 
 class _Lane:
@@ -273,7 +274,8 @@ class ChannelDescriber:
     """The stage API: ``process(raw_block)`` per block of the capture (what ``ChannelFinder.process`` takes), ``finish()`` once
     (the eight sums of every channel), ``result()`` (a ``DescribeResult``), ``stages()`` for the tests, ``reset()``.
     ``fin`` is ``ChannelFinder.finish()`` of the same capture and ``channels`` the ``FoundChannel``s made from it.  ``layers``: the
-    keywords of ``FIND_LAYERS`` above the first (``keying=True``, ``identify=True``, ``flex=True``), each with the one in front of it."""
+    keywords of ``FIND_LAYERS`` above the first (``keying=True``, ``identify=True``, ``flex=True``), each with the one in front of
+    it, and of ``FIND_BRANCHES`` (``dmr=True``, with ``identify=True``)."""
 
     def __init__(self, find_plan: P.FindPlan, fin: dict, channels, fmt: str = "s16", iq_order: str = "iq", *, keep_stages: bool = False,
                  **layers):
@@ -458,6 +460,14 @@ class ChannelDescriber:
 
     def flex_result(self, center_freq: float | None = None) -> X.FlexResult:
         return X.flex_result(self.channels, self.lanes(), self.finish_flex(), self.find_plan.fs, center_freq)
+
+    def finish_dmr(self) -> list:
+        """Per channel the dict of ``dmr.finish_dmr``."""
+        self._need("dmr")
+        return self._once("dmr", lambda: DM.finish_dmr(self.lanes(), self.finish_identify()))
+
+    def dmr_result(self, center_freq: float | None = None) -> DM.DmrResult:
+        return DM.dmr_result(self.channels, self.lanes(), self.finish_dmr(), self.find_plan.fs, center_freq)
 
     def result(self, center_freq: float | None = None) -> DescribeResult:
         sums = self.finish()

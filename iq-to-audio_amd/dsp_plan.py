@@ -1078,6 +1078,33 @@ def plan_flex(fs_ch: float) -> FlexPlan:
                     ident=(plan_ident(fs_ch, 1600), plan_ident(fs_ch, 3200)))
 
 
+# ---- DMR burst decoding plan (--find-dmr) ----------------------------------
+
+DMR_LEAD = 66  # o[i] sits at index 66 + i of ``offsets``: i = -66 .. 77
+DMR_OFFSETS = 144
+DMR_WORDS = 9  # uint32 words of a sliced burst: 24 CACH bits, then 264 burst bits
+DMR_RECORD = 8  # int32 values of a decoded burst
+
+
+@dataclass(frozen=True)
+class DmrPlan:
+    fs_ch: float
+    sps: float  # fs_ch / 4800
+    offsets: tuple  # o[i] = rint(i sps), i = -66 .. 77 (half-even, float64)
+    ident: IdentPlan  # section 25's plan at 4800 symbols/s
+
+    def o(self, i: int) -> int:
+        return self.offsets[DMR_LEAD + i]
+
+
+def plan_dmr(fs_ch: float) -> DmrPlan:
+    """The sample offsets of a DMR burst and its CACH around sync symbol 0 at the channel rate ``fs_ch``, and section 25's plan at
+    4800 symbols/s.  ``ValueError`` unless 4 <= sps <= 224 (``plan_ident``'s limits)."""
+    ident = plan_ident(fs_ch, 4800)
+    offsets = tuple(int(np.rint(i * ident.sps)) for i in range(-DMR_LEAD, DMR_OFFSETS - DMR_LEAD))
+    return DmrPlan(fs_ch=ident.fs_ch, sps=ident.sps, offsets=offsets, ident=ident)
+
+
 # ---- carrier squelch plan (--squelch; DESIGN.md section 24) --------------------------------------
 
 GATE_CELL = 256  # IQA_GATE_CELL: samples to a cell, counted on the absolute position

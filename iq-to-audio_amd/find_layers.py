@@ -1,10 +1,11 @@
-"""The layers of the second pass over a capture: what ``--find-describe``, ``--find-decode``, ``--find-identify`` and
-``--find-flex`` add to the finder's channel list (DESIGN.md sections 22, 23, 25 and 26).
+"""The layers of the second pass over a capture: what ``--find-describe``, ``--find-decode``, ``--find-identify``,
+``--find-flex`` and ``--find-dmr`` add to the finder's channel list (DESIGN.md sections 22, 23, 25, 26 and 29).
 
-``FIND_LAYERS`` is the one place that lists them, in chain order: every row needs the row in front of it.  ``find_channels``,
-``ChannelDescriber`` and the CLI read a layer's keyword, flag, result and file suffix from its row; a new layer is a row here,
-a keyword on ``ChannelDescriber`` and its own module ("Adding a layer to the second pass").  Nothing heavy is
-imported here: the CLI reads the table before the GPU is touched."""
+``FIND_LAYERS`` lists the chain, in order: every row needs the row in front of it.  ``FIND_BRANCHES`` lists the layers that
+hang off one row of the chain (``needs``) and off nothing else.  ``find_channels``, ``ChannelDescriber`` and the CLI read a
+layer's keyword, flag, result and file suffix from its row; a new layer is a row here, a keyword on ``ChannelDescriber`` and
+its own module ("Adding a layer to the second pass").  Nothing heavy is imported here: the CLI reads the tables
+before the GPU is touched."""
 from __future__ import annotations
 
 from dataclasses import dataclass
@@ -20,6 +21,7 @@ class FindLayer:
     suffix: str  # the result is written to ``<capture stem>.<suffix>.json``
     inline: bool  # line i of ``result.lines()`` goes under channel i's line; False: all its lines follow the channel list
     help: str  # the CLI flag's help text
+    needs: str | None = None  # a branch: the name of the chain row it hangs off; None for a row of the chain
 
     @property
     def option(self) -> str:
@@ -44,10 +46,22 @@ FIND_LAYERS = (
 )
 
 
+FIND_BRANCHES = (
+    FindLayer("dmr", "find_dmr", 29, lambda d, fc, fs_ch: d.dmr_result(fc), "dmr", False,
+              "Find, describe, key and identify the channels, and decode the data bursts of every channel that carries DMR "
+              "sync words: colour code, slot, link control and CSBKs, one line per call and per CSBK, also written to "
+              "<capture stem>.dmr.json.  Implies --find-identify.", needs="identify"),
+)
+
+
 def active_layers(switches: dict) -> tuple:
-    """The rows switched on in ``switches`` (name -> bool), in chain order; ``ValueError`` for the first row (in chain order)
-    that is on while the row in front of it is not."""
+    """The rows switched on in ``switches`` (name -> bool): the chain's in chain order, then the branches'.  ``ValueError`` for
+    the first row of the chain that is on while the row in front of it is not, then for the first branch that is on while the
+    row it needs is not."""
     for below, layer in zip(FIND_LAYERS, FIND_LAYERS[1:]):
         if switches.get(layer.name) and not switches.get(below.name):
             raise ValueError(f"{layer.name}=True needs {below.name}=True")
-    return tuple(layer for layer in FIND_LAYERS if switches.get(layer.name))
+    for layer in FIND_BRANCHES:
+        if switches.get(layer.name) and not switches.get(layer.needs):
+            raise ValueError(f"{layer.name}=True needs {layer.needs}=True")
+    return tuple(layer for layer in FIND_LAYERS + FIND_BRANCHES if switches.get(layer.name))
