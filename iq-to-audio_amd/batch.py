@@ -48,6 +48,45 @@ def warm_block(raw_dev, fmt: str, chunk: int, n_frames: int):
     return raw_dev[: 2 * min(chunk, n_frames)] if fmt != "f32" else raw_dev[: min(chunk, n_frames)]
 
 
+class GraphBook:
+    """The captured steps of a runner and, per place, what that place's captures last probed.
+
+    A *place* is whatever fixes a graph's addresses: (buffer, slot, enclosing buffer, lead) of ``submit_captured``, the
+    tuple of them of ``submit_captured_batch``.  A graph also holds the speculation -- one (sign, precision) per capture
+    in it -- its launches were captured with, so it is kept under (place, speculation); ``spec[place]`` is what the place's
+    captures last probed, i.e. which of its graphs the next call replays.  Buffers that probe differently (carriers on either
+    side, a weak channel beside a strong one) each replay their own graph, whatever the runner last collected.  No GPU
+    call in here: the runner hands in the two callables."""
+
+    def __init__(self):
+        self.graphs: dict = {}  # (place, speculation) -> entry
+        self.spec: dict = {}  # place -> speculation: a tuple of (sign, precision), one per capture of the place
+        self.captures = 0  # graphs captured so far (each (place, speculation) at most once)
+
+    def lookup(self, place):
+        spec = self.spec.get(place)
+        return None if spec is None else self.graphs.get((place, spec))
+
+    def entry_for(self, place, run_ordinary, capture):
+        """The graph to replay for ``place``.  Where its last speculation has none (a new place; a place whose captures
+        now probe something else): ``run_ordinary()`` runs the captures once the ordinary way and returns what they probed,
+        and only if that speculation has no graph either ``capture(speculation)`` makes one."""
+        entry = self.lookup(place)
+        if entry is None:
+            spec = self.spec[place] = tuple(run_ordinary())
+            entry = self.graphs.get((place, spec))
+            if entry is None:
+                entry = self.graphs[(place, spec)] = capture(spec)
+                self.captures += 1
+        return entry
+
+    def probed(self, place, part: int, sign: int, precision: str) -> None:
+        """Capture ``part`` of a replay at ``place`` has been read: that is its speculation from now on."""
+        spec = self.spec.get(place)
+        if spec is not None and spec[part] != (sign, precision):
+            self.spec[place] = spec[:part] + ((sign, precision),) + spec[part + 1 :]
+
+
 class ResidentCaptureRunner:
     """Ingest -> 48 kHz PCM16 for whole captures that already sit in HBM (multi-file batches with one set of
     settings; ``bench.py``): the per-chunk loop of the reference (processing.py:1070-1154) plus the writer's
@@ -114,7 +153,7 @@ class ResidentCaptureRunner:
         self._spec_sign, self._spec_precision = 1, self.base_precision  # what the next capture is run with before its probe is read
         self.redone = dict(sign=0, precision=0)  # captures re-run in collect, by cause
         self.replays_redone = 0  # ... of them, captures whose graph replay had assumed another sign / a coarser precision
-        self._graphs: dict = {}  # captured steps by (buffers, slot, speculation): submit_captured / submit_captured_batch
+        self._book = GraphBook()  # captured steps by (buffers, slot) and speculation: submit_captured / submit_captured_batch
         self.n_dec = -(-self.n_frames // self.d)
         self.starts = P.chunk_output_starts(self.chunk, self.d, 0, self.n_frames)
         self.rs = Resampler48k(self.fs_ch)
@@ -303,10 +342,21 @@ class ResidentCaptureRunner:
     # belongs to the graph; ``collect`` reads it after the replay has finished and, if it says -1, runs that capture
     # again the ordinary way with the right sign.
 
-    def _captured_step(self, raw_dev, slot, halo):
-        """Queue the whole step for the speculated sign / precision on the current (capturing) stream; returns what collect needs."""
-        sign = self.override or self._spec_sign
-        chan = self._channelizer(sign, self._spec_precision)
+    @property
+    def _graphs(self) -> dict:
+        return self._book.graphs
+
+    @property
+    def graph_captures(self) -> int:
+        """Graphs captured so far by ``submit_captured`` / ``submit_captured_batch``: one per (buffers, slot) and speculation
+        they have met, however often the buffers alternate."""
+        return self._book.captures
+
+    def _captured_step(self, raw_dev, slot, halo, spec):
+        """Queue the whole step for the speculation ``spec`` = (sign, precision) on the current (capturing) stream; returns
+        what collect needs."""
+        sign = self.override or spec[0]
+        chan = self._channelizer(sign, spec[1])
         chan.plan_ahead()
         dem = slot["dem"]
         probe = self._queue_probe(raw_dev)
@@ -323,6 +373,9 @@ class ResidentCaptureRunner:
     def submit_captured(self, raw_dev, enclosing=None, lead_frames: int = 0) -> dict:
         """``submit`` for a capture in a fixed buffer: the first call per (buffer, slot) runs the step once the ordinary way
         (plans, tap uploads, pinned slots come into being), captures it into a graph and replays it; later calls replay.
+        The graph replayed is the one of the sign and precision THIS buffer's capture last probed in this slot (``GraphBook``),
+        not of what the runner collected last: buffers with carriers on either side, or a weak and a strong channel, in
+        turn each replay their own graph, and ``graph_captures`` stands still once every (buffer, slot) has been met.
         Returns a ticket for ``collect``."""
         torch = D.torch_mod()
         if D.current_raw_stream() != self._compute_raw:
@@ -332,24 +385,25 @@ class ResidentCaptureRunner:
         if slot["busy"] is not None:
             self.collect(slot["busy"])
         halo = (enclosing, int(lead_frames)) if enclosing is not None else None
-        def graph_key():  # (a graph holds the speculation it was captured with)
-            return (int(raw_dev.data_ptr()), index, None if enclosing is None else int(enclosing.data_ptr()), int(lead_frames),
-                    self._spec_sign, self._spec_precision)
+        place = (int(raw_dev.data_ptr()), index, None if enclosing is None else int(enclosing.data_ptr()), int(lead_frames))
 
-        key = graph_key()
-        entry = self._graphs.get(key)
-        if entry is None:
+        def run_ordinary():
             # once the ordinary way, in this very slot: plans, tap uploads and the pinned probe slot exist afterwards
             # (and the capture's own probe has set the speculation the graph is captured with)
             self.collect(self.submit(raw_dev, enclosing=enclosing, lead_frames=lead_frames))
-            key = graph_key()
+            return [(self._spec_sign, self._spec_precision)]
+
+        def capture(spec):
             torch.cuda.synchronize()
             reserve_pinned_scalars(1)
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g):
-                parts = self._captured_step(raw_dev, slot, halo)
-            entry = self._graphs[key] = dict(graph=g, **parts)
-        else:
+                parts = self._captured_step(raw_dev, slot, halo, spec[0])
+            return dict(graph=g, **parts)
+
+        before = self._next
+        entry = self._book.entry_for(place, run_ordinary, capture)
+        if self._next == before:  # (no ordinary run: the slot is taken here)
             self._next += 1
         entry["dem"].chunk_sumsq = entry["dem"].chunk_sumsq[-1:]  # (a replay re-runs the same demodulator call)
         done = entry.get("done_event")  # (one event per graph: its slot's previous capture was collected above)
@@ -364,6 +418,7 @@ class ResidentCaptureRunner:
             entry["graph"].replay()
             done.record()
         ticket = self._ticket(entry, slot, done, sign=entry["sign"], raw=raw_dev, halo=halo, replayed=True)
+        ticket["place"] = (place, 0)
         slot["busy"] = ticket
         return ticket
 
@@ -380,23 +435,25 @@ class ResidentCaptureRunner:
             if slot["busy"] is not None:
                 self.collect(slot["busy"])
         halos = [(enc, int(lead)) if enc is not None else None for _, enc, lead in captures]
-        def graph_key():
-            return ("batch", self._spec_sign, self._spec_precision) + tuple((int(raw.data_ptr()), None if enc is None else int(enc.data_ptr()), int(lead))
-                                                                            for raw, enc, lead in captures)
+        place = ("batch",) + tuple((int(raw.data_ptr()), None if enc is None else int(enc.data_ptr()), int(lead)) for raw, enc, lead in captures)
 
-        key = graph_key()
-        entry = self._graphs.get(key)
-        if entry is None:
+        def run_ordinary():
             self._next = 0
+            specs = []
             for raw, enc, lead in captures:  # once the ordinary way, each in its slot
                 self.collect(self.submit(raw, enclosing=enc, lead_frames=lead))
-            key = graph_key()
+                specs.append((self._spec_sign, self._spec_precision))
+            return specs
+
+        def capture(spec):
             torch.cuda.synchronize()
             reserve_pinned_scalars(len(captures))
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g):
-                parts = [self._captured_step(raw, slot, halo) for (raw, _, _), slot, halo in zip(captures, self.slots, halos)]
-            entry = self._graphs[key] = dict(graph=g, parts=parts)
+                parts = [self._captured_step(raw, slot, halo, sp) for (raw, _, _), slot, halo, sp in zip(captures, self.slots, halos, spec)]
+            return dict(graph=g, parts=parts)
+
+        entry = self._book.entry_for(place, run_ordinary, capture)
         for p_ in entry["parts"]:
             p_["dem"].chunk_sumsq = p_["dem"].chunk_sumsq[-1:]
         entry["graph"].replay()
@@ -405,6 +462,7 @@ class ResidentCaptureRunner:
         tickets = []
         for (raw, _, _), slot, halo, p_ in zip(captures, self.slots, halos, entry["parts"]):
             t = self._ticket(p_, slot, done, sign=p_["sign"], raw=raw, halo=halo, replayed=True)
+            t["place"] = (place, len(tickets))
             slot["busy"] = t
             tickets.append(t)
         return tickets
@@ -442,8 +500,10 @@ class ResidentCaptureRunner:
             self._flush_egress()
         if probe is not None:
             sign = probe.peek() if replayed else probe.result()
-            if self._respeculate(ticket, probe, sign) and replayed:
-                self.replays_redone += 1
+            redone = self._respeculate(ticket, probe, sign)
+            if replayed:
+                self.replays_redone += int(redone)
+                self._book.probed(*ticket["place"], self._spec_sign, self._spec_precision)
         ticket["done"].synchronize()
         ticket["collected"] = True
         ticket["raw"] = ticket["pcm"] = None  # back to the allocator: the next capture reuses them

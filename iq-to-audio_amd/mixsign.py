@@ -118,12 +118,28 @@ def _release_scalars(buf) -> None:
                 t[1] = None
 
 
+LEVEL_VECTOR_BYTES = 16  # iqa_raw_level reads whole 16-byte vectors from a 16-byte aligned address
+
+
+def level_window(address: int, n_values: int, value_bytes: int) -> tuple[int, int]:
+    """(skip, count): the values of a run of ``n_values`` values of ``value_bytes`` bytes at byte ``address`` that
+    ``iqa_raw_level`` is given -- the run from its first 16-byte boundary on (a run that ends before it: nothing).  Of fewer
+    values than one vector the library reads nothing, whatever their address, and reports 0."""
+    if value_bytes not in (1, 2, 4) or address % value_bytes:
+        raise ValueError("raw values must be 1, 2 or 4 bytes wide and aligned to their own size")
+    skip = min((-address % LEVEL_VECTOR_BYTES) // value_bytes, max(n_values, 0))
+    return skip, max(n_values, 0) - skip
+
+
 def queue_raw_level(warmup, fmt: str, out_slot) -> None:
     """Queue the wideband-level estimate of raw frames (``iqa_raw_level``: mean square of up to 65536 values spread over
-    ``warmup``) into ``out_slot`` (double[1], device or pinned host memory) on the current stream."""
+    ``warmup``) into ``out_slot`` (double[1], device or pinned host memory) on the current stream.  ``warmup`` may start
+    anywhere (a capture behind a lead-in of a few frames): the estimate is taken from its first 16-byte boundary on
+    (``level_window``), at most 15 bytes of a block of a hundred thousand frames and more."""
     x, n = _as_frames(warmup, fmt)
     flat = x.view(D.torch_mod().float32) if x.is_complex() else x
-    N.call("iqa_raw_level", c_int32(P.FMT_CODE[fmt]), N.ptr(flat), c_int64(flat.numel()), N.ptr(out_slot), N.stream_ptr())
+    skip, count = level_window(int(flat.data_ptr()), int(flat.numel()), int(flat.element_size()))
+    N.call("iqa_raw_level", c_int32(P.FMT_CODE[fmt]), N.ptr(flat[skip:] if skip else flat), c_int64(count), N.ptr(out_slot), N.stream_ptr())
 
 
 def wideband_rms_from(mean_square: float, fmt: str) -> float:

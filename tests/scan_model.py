@@ -516,3 +516,20 @@ def windowed_chunk_cases(W: int, span: int = SPAN) -> list:
             if 4 * own + 3 <= 50 * FIFTY_STARTS:
                 cases.append((lay, (50 * FIFTY_STARTS // own + 1) * own + 3, "a"))
     return cases
+
+
+# ---- iqa_raw_level ---------------------------------------------------------------------------------------------------
+
+RAW_LEVEL_FORMATS = {"s16": (0, 8, np.int16), "u8": (1, 16, np.uint8), "f32": (2, 4, np.float32)}  # fmt -> (code, values per 16-byte vector, dtype)
+
+
+def raw_level_want(fmt: str, raw: np.ndarray) -> float:
+    """Mean of value^2 over the eight documented stretches: vectors r * max(1024, n_vec // 8) + [0, 1024), cut at n_vec."""
+    _, per_vec, _ = RAW_LEVEL_FORMATS[fmt]
+    n_vec = raw.size // per_vec
+    step = max(1024, n_vec // 8)
+    v = raw[:n_vec * per_vec].astype(np.float64).reshape(n_vec, per_vec) - (128.0 if fmt == "u8" else 0.0)
+    rows = np.concatenate([np.arange(r * step, min(r * step + 1024, n_vec)) for r in range(8)]).astype(np.int64) if n_vec else np.zeros(0, np.int64)
+    rows = rows[rows < n_vec]
+    assert np.unique(rows).size == rows.size
+    return float(np.mean(v[rows] ** 2)) if rows.size else 0.0

@@ -497,14 +497,23 @@ def test_captured_step_replays_to_the_same_audio(A):
         r = runner.collect(runner.submit(x))
         want.append((r["sign"], r["pcm_host"].numpy().copy(), r["audio"].clone()))
     assert [w[0] for w in want] == [1, -1]
-    for rep in range(3):  # first round captures (per buffer and slot), later rounds replay
+    def counters(rn):
+        return rn.graph_captures, dict(rn.redone), rn.replays_redone
+
+    settled = None
+    for rep in range(5):  # two buffers in turn over three slots: every (buffer, slot) has been met after three rounds
         tickets = [runner.submit_captured(x) for x in bufs]
         for (sign, pcm, audio), t in zip(want, tickets):
             r = runner.collect(t)
             assert r["sign"] == sign
             assert np.array_equal(r["pcm_host"].numpy(), pcm), rep
             assert torch.equal(r["audio"], audio)
-    assert 2 <= len(runner._graphs) <= 2 * runner.SLOTS  # one graph per (buffer, slot) the rounds above have touched
+        if rep == 2:
+            settled = counters(runner)
+        # from then on a buffer replays the graph of ITS sign: nothing is captured again, nothing run again
+        assert rep < 2 or counters(runner) == settled, (rep, counters(runner), settled)
+    assert len(runner._graphs) == runner.graph_captures == 2 * runner.SLOTS  # one graph per (buffer, slot), each captured once
+    assert runner.replays_redone == 0  # (no replay ever assumed the other buffer's sign)
     # the same fixed buffer with another capture in it: the replay reads what is there now
     bufs[0].copy_(D.to_device(caps[2].reshape(-1), "int16"))
     torch.cuda.synchronize()
@@ -523,6 +532,9 @@ def test_captured_step_replays_to_the_same_audio(A):
         for (sign, pcm, audio), t in zip(want, tickets):
             r = runner.collect(t)
             assert r["sign"] == sign and np.array_equal(r["pcm_host"].numpy(), pcm) and torch.equal(r["audio"], audio), rep
+        if rep == 0:
+            settled = counters(runner)
+        assert counters(runner) == settled, (rep, counters(runner), settled)  # each capture of the batch replays at its own sign
     with pytest.raises(ValueError):
         runner.submit_captured_batch([(bufs[0], None, 0)] * (runner.SLOTS + 1))
     # replays on two streams (graph_streams=2: consecutive captures' chains side by side), eight slots: the same PCM16 and
@@ -535,6 +547,10 @@ def test_captured_step_replays_to_the_same_audio(A):
             sign, pcm, audio = want[k % 2]
             r = multi.collect(t)
             assert r["sign"] == sign and np.array_equal(r["pcm_host"].numpy(), pcm) and torch.equal(r["audio"], audio), (rep, k)
+        if rep == 0:  # ten submits over eight slots, buffer k % 2 in slot k % 8: all eight (buffer, slot) pairs in the first round
+            settled = counters(multi)
+            assert multi.graph_captures == 8
+        assert counters(multi) == settled, (rep, counters(multi), settled)
 
 
 # ---- dynamic range: a full-scale interferer beside an empty channel and beside a weak one ----------
@@ -830,6 +846,24 @@ def test_precision_guard_in_the_batch_runners(A):
         err = rms(r["audio"].cpu().numpy() - want[1.0e6].audio)
         assert r["precision"] == "fine" and err < 1e-4, (k, r["precision"], err)
     assert runner.redone["precision"] <= 2 and runner.redone["sign"] == 0, runner.redone
+    # a weak and a strong capture in turn (the guard asks "fine" for one, "fast" for the other): each buffer replays the
+    # graph of its own precision; once every (buffer, slot) has been met nothing is captured or run again
+    strong = D.to_device(O.synth_capture_s16(fs, n / fs, 1.0e6, seed=7).reshape(-1), "int16")
+    torch.cuda.synchronize()
+    pair = ResidentCaptureRunner(taps, sample_rate=fs, freq_offset=1.0e6, decimation=d, fs_channel=fs_ch,
+                                 chunk=P.tune_chunk_size(fs, 1_048_576), n_frames=n)
+    settled = None
+    for rep in range(5):
+        for x, precision in ((dev, "fine"), (strong, "fast")):
+            r = pair.collect(pair.submit_captured(x))
+            assert r["precision"] == precision and r["sign"] == want[1.0e6].mix_sign == 1, (rep, precision, r["precision"], r["sign"])
+            if x is dev:
+                assert rms(r["audio"].cpu().numpy() - want[1.0e6].audio) < 1e-4, rep
+        now = (pair.graph_captures, dict(pair.redone), pair.replays_redone)
+        if rep == 2:
+            settled = now
+        assert rep < 2 or now == settled, (rep, now, settled)
+    assert pair.graph_captures == len(pair._graphs) == 2 * pair.SLOTS and pair.replays_redone == 0
     # with the guard off the same capture stays at "fast" and misses the bar (what round 2 shipped)
     off_runner = ResidentCaptureRunner(taps, sample_rate=fs, freq_offset=1.0e6, decimation=d, fs_channel=fs_ch,
                                        chunk=P.tune_chunk_size(fs, 1_048_576), n_frames=n, precision_guard=0.0)

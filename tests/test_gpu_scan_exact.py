@@ -556,7 +556,7 @@ def test_mean_power_batch_long_and_short_stretches(G, n_each, skip):
     assert np.all(np.abs(got - want) <= 1e-12 * want), (got, want)
 
 
-RAW = {"s16": (0, 8, np.int16), "u8": (1, 16, np.uint8), "f32": (2, 4, np.float32)}
+RAW, _raw_level_want = M.RAW_LEVEL_FORMATS, M.raw_level_want  # (shared with tests/test_gpu_runner_buffers.py)
 
 
 def _raw_values(fmt: str, n_values: int, seed: int) -> np.ndarray:
@@ -573,18 +573,6 @@ def _raw_values(fmt: str, n_values: int, seed: int) -> np.ndarray:
     if fmt == "u8":
         return (128 + np.rint(ramp * rng.integers(-128, 128, size=n_values))).astype(np.uint8)
     return (ramp * rng.normal(size=n_values)).astype(np.float32)
-
-
-def _raw_level_want(fmt: str, raw: np.ndarray) -> float:
-    """Mean of value^2 over the eight documented stretches: vectors r * max(1024, n_vec // 8) + [0, 1024), cut at n_vec."""
-    _, per_vec, _ = RAW[fmt]
-    n_vec = raw.size // per_vec
-    step = max(1024, n_vec // 8)
-    v = raw[:n_vec * per_vec].astype(np.float64).reshape(n_vec, per_vec) - (128.0 if fmt == "u8" else 0.0)
-    rows = np.concatenate([np.arange(r * step, min(r * step + 1024, n_vec)) for r in range(8)]).astype(np.int64) if n_vec else np.zeros(0, np.int64)
-    rows = rows[rows < n_vec]
-    assert np.unique(rows).size == rows.size
-    return float(np.mean(v[rows] ** 2)) if rows.size else 0.0
 
 
 @pytest.mark.parametrize("fmt", ["s16", "u8", "f32"])
