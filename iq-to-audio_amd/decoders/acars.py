@@ -11,7 +11,7 @@ from __future__ import annotations
 
 import logging
 import math
-from ctypes import c_double, c_int32, c_int64
+from ctypes import c_int32, c_int64
 from dataclasses import asdict, dataclass, field
 
 import numpy as np
@@ -19,7 +19,7 @@ import numpy as np
 from .. import _dev as D
 from .. import _native as N
 from .. import dsp_plan as P
-from .common import SideStage, group_records, search_with_room
+from .common import FrameCore, SideStage, group_records, parse_head, phase_planes, stage_records
 
 LOG = logging.getLogger(__name__)
 
@@ -95,11 +95,7 @@ def parse_message(raw: bytes) -> dict:
 def parse_messages(plan: P.AcarsPlan, records: dict, candidates: int = 0) -> AcarsResult | None:
     """``records``: dict(phase=[k], s=[k], start=[k], nbytes=[k], data=uint8[k, >= nbytes]) in any order (the kept list of
     ``iqa_acars_frames``) -> the run's messages.  Integer logic only; ``None`` where no message survives."""
-    start = np.asarray(records["start"], dtype=np.int64).reshape(-1)
-    phase = np.asarray(records["phase"], dtype=np.int64).reshape(-1)
-    nbytes = np.asarray(records["nbytes"], dtype=np.int64).reshape(-1)
-    data = np.asarray(records["data"], dtype=np.uint8).reshape(start.size, -1) if start.size else np.zeros((0, 0), dtype=np.uint8)
-    res = AcarsResult(candidates=int(candidates), crc_ok=int(start.size))
+    res, start, phase, nbytes, data = parse_head(AcarsResult, records, candidates, "start", "phase", "nbytes")
     for at, raw, hits, _ in group_records(start, nbytes, data, plan.L, tie=phase):
         res.messages.append(AcarsMessage(time_s=at / plan.fs, hits=hits, **parse_message(raw)))
     return res if res.messages else None
@@ -111,39 +107,25 @@ def shift_of(emax: float) -> int:
     return 14 - (ex - 1)
 
 
-class AcarsCore:
-    """Per-stream device state: the run's stored envelope (one float32 device tensor per block, joined by ``finish``) and
-    the absolute position.  ``keep_stages`` also stores q, I, Q and y at ``finish``, for the tests."""
+class AcarsCore(FrameCore):
+    """Per-stream device state (``StreamCore``, no history): the run's stored envelope (one float32 device tensor per block,
+    joined by ``finish``) and the absolute position.  ``keep_stages`` also stores q, I, Q and y at ``finish``, for the tests."""
+
+    bits_entry, frames_entry = "iqa_acars_bits", "iqa_acars_frames"
+    SLOT_BYTES, PHASES, STREAMS = SLOT_BYTES, PHASES, PHASES
+    key, plane_keys, plane_dtype = "phase", ("bits", "nbits"), "uint8"
 
     def __init__(self, plan: P.AcarsPlan, *, keep_stages: bool = False):
-        self.plan = plan
+        super().__init__(plan, plan.W, plan.bit_count, planes=dict(e="float32"))
         self._taps = D.from_numpy(np.ascontiguousarray(plan.taps))
         self.keep_stages = keep_stages
-        self.pos = 0  # absolute index of the next block's first sample
-        self._e: list = []
 
-    def process(self, e) -> None:
+    def _block(self, e, n: int) -> None:
         """One block of the envelope (device float32[n], finite and >= 0).  The tensor is kept, not copied."""
-        n = int(e.numel())
-        if n == 0:
-            return
-        self._e.append(e)
-        self.pos += n
+        self.store.append("e", e)
 
     def joined(self):
-        if len(self._e) > 1:
-            self._e = [D.torch_mod().cat(self._e)]
-        return self._e[0] if self._e else D.empty(0, "float32")
-
-    def reset(self) -> None:
-        """Back to a stream that has seen nothing: position 0, no stored envelope."""
-        self.pos, self._e = 0, []
-
-    def _frames(self, bits, nbits: int, count_of, capacity: int, counts):
-        lst, slots = D.empty(4 * capacity, "int64"), D.empty(SLOT_BYTES * capacity, "uint8")
-        N.call("iqa_acars_frames", N.ptr(bits), c_int64(nbits), count_of, c_int32(self.plan.W), c_double(self.plan.step), N.ptr(lst),
-               N.ptr(slots), c_int64(capacity), N.ptr(counts), N.stream_ptr())
-        return lst, slots
+        return self.store.joined("e")
 
     def finish(self, capacity: int = 64) -> dict:
         """The stages and the kept blocks of the stored run: dict(emax, sh, phase, s, start, nbytes, data, candidates, same,
@@ -169,21 +151,8 @@ class AcarsCore:
         N.call("iqa_acars_detect", N.ptr(e), c_int64(n), c_int32(sh), c_int32(plan.W), c_int32(plan.L), N.ptr(self._taps), c_int32(plan.cr),
                c_int32(plan.sr), N.ptr(stages.get("q")), N.ptr(stages.get("I")), N.ptr(stages.get("Q")), N.ptr(stages.get("y")), N.ptr(same),
                N.stream_ptr())
-        counts_of = [plan.bit_count(p, n) for p in range(PHASES)]
-        nbits = max(counts_of)
-        if nbits == 0:
-            return dict(empty, sh=sh, same=same, **stages)
-        count_of = (c_int64 * PHASES)(*counts_of)
-        bits = D.empty(PHASES * nbits, "uint8")
-        N.call("iqa_acars_bits", N.ptr(same), c_int64(n), c_int32(plan.W), c_double(plan.step), c_int64(nbits), N.ptr(bits), N.stream_ptr())
-        counts = D.zeros(2, "int64")
-        ((lst, slots),), (kept, reached) = search_with_room([lambda room: self._frames(bits, nbits, count_of, room, counts)], counts, capacity)
-        entries = lst[: 4 * kept].cpu().numpy().reshape(-1, 4)
-        data = slots[: SLOT_BYTES * kept].cpu().numpy().reshape(-1, SLOT_BYTES)
-        order = np.lexsort((entries[:, 1], entries[:, 0]))
-        entries, data = entries[order], data[order]
-        return dict(emax=emax, sh=sh, phase=entries[:, 0].copy(), s=entries[:, 1].copy(), start=entries[:, 2].copy(),
-                    nbytes=entries[:, 3].copy(), data=data, candidates=reached, same=same, bits=bits, nbits=nbits, count_of=counts_of, **stages)
+        tail = self.frames_of(same, capacity) if max(self.counts_of(n)) else {}  # (no phase has a bit: nothing more is launched)
+        return dict(empty, sh=sh, same=same, **tail, **stages)
 
     def result(self, fin=None, **context) -> AcarsResult | None:
         """The run's ``AcarsResult`` (``None`` without a message); ``fin``: a ``finish()`` made earlier."""
@@ -210,9 +179,6 @@ class AcarsDecoder(SideStage):
         def host(key):
             return None if fin.get(key) is None else fin[key].cpu().numpy()
 
-        plane = fin["bits"].cpu().numpy().reshape(PHASES, -1) if fin["nbits"] else np.zeros((PHASES, 0), dtype=np.uint8)
-        bits = [plane[p, : fin["count_of"][p]] for p in range(PHASES)]
-        records = [(int(p), int(s), int(at), fin["data"][k, : int(nb)].tobytes())
-                   for k, (p, s, at, nb) in enumerate(zip(fin["phase"], fin["s"], fin["start"], fin["nbytes"]))]
         return dict(e=self.core.joined().cpu().numpy(), emax=np.float32(fin["emax"]), sh=fin["sh"], q=host("q"), I=host("I"), Q=host("Q"),
-                    y=host("y"), same=host("same"), bits=bits, records=records, candidates=fin["candidates"])
+                    y=host("y"), same=host("same"), bits=phase_planes(self.core, fin), records=stage_records(fin, "phase"),
+                    candidates=fin["candidates"])

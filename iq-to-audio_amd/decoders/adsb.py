@@ -18,7 +18,7 @@ import numpy as np
 from .. import _dev as D
 from .. import _native as N
 from .. import dsp_plan as P
-from .common import SideStage, group_records, search_with_room
+from .common import SideStage, StreamCore, group_records, kept_records, parse_head
 
 LOG = logging.getLogger(__name__)
 
@@ -168,11 +168,7 @@ def parse_me(me: int) -> dict:
 def parse_frames(plan: P.AdsbPlan, records: dict, candidates: int = 0) -> AdsbResult | None:
     """``records``: dict(n=[k], nbits=[k], P=[k], data=uint8[k, 14]) in any order (the kept list of ``iqa_adsb_search``) ->
     the run's messages and aircraft.  ``None`` where no message survives."""
-    at = np.asarray(records["n"], dtype=np.int64).reshape(-1)
-    nbits = np.asarray(records["nbits"], dtype=np.int64).reshape(-1)
-    level = np.asarray(records["P"], dtype=np.int64).reshape(-1)
-    data = np.asarray(records["data"], dtype=np.uint8).reshape(at.size, -1) if at.size else np.zeros((0, SLOT_BYTES), dtype=np.uint8)
-    res = AdsbResult(candidates=int(candidates), crc_ok=int(at.size))
+    res, at, nbits, level, data = parse_head(AdsbResult, records, candidates, "n", "nbits", "P")
     last_pos: dict = {}  # (icao, parity) -> the latest position message
     craft: dict = {}
     for n, raw, hits, first in group_records(at, nbits // 8, data, plan.L):
@@ -204,35 +200,23 @@ def parse_frames(plan: P.AdsbPlan, records: dict, candidates: int = 0) -> AdsbRe
     return res if res.messages else None
 
 
-class AdsbCore:
-    """Per-stream device state: the run's stored q plane (one device tensor per block, uint16 values held in int16 storage,
-    joined by ``finish``) and the absolute position."""
+class AdsbCore(StreamCore):
+    """Per-stream device state (``StreamCore``, no history): the run's stored q plane (one device tensor per block, uint16
+    values held in int16 storage, joined by ``finish``) and the absolute position."""
 
     def __init__(self, plan: P.AdsbPlan):
-        self.plan = plan
+        super().__init__(plan, planes=dict(q="int16"))
         self._offsets_host = np.ascontiguousarray(plan.offsets, dtype=np.int32)
         self._offsets = D.from_numpy(self._offsets_host)
-        self.pos = 0  # absolute index of the next block's first sample
-        self._q: list = []
 
-    def process(self, e) -> None:
+    def _block(self, e, n: int) -> None:
         """One block of the envelope (device float32[n], >= 0): quantised into a tensor of the core's own."""
-        n = int(e.numel())
-        if n == 0:
-            return
         q = D.empty(n, "int16")
         N.call("iqa_adsb_quantise", N.ptr(e), c_int64(n), N.ptr(q), N.stream_ptr())
-        self._q.append(q)
-        self.pos += n
+        self.store.append("q", q)
 
     def joined(self):
-        if len(self._q) > 1:
-            self._q = [D.torch_mod().cat(self._q)]
-        return self._q[0] if self._q else D.empty(0, "int16")
-
-    def reset(self) -> None:
-        """Back to a stream that has seen nothing: position 0, no stored plane."""
-        self.pos, self._q = 0, []
+        return self.store.joined("q")
 
     def search(self, q, capacity: int, counts, flags=None):
         """One ``iqa_adsb_search`` over the device plane ``q`` -> (list, slots)."""
@@ -249,12 +233,7 @@ class AdsbCore:
         n = int(q.numel())
         npos = max(n - self.plan.span + 1, 0)
         flags = D.empty(npos, "uint8") if keep_flags else None
-        counts = D.zeros(2, "int64")
-        ((lst, slots),), (kept, passed) = search_with_room([lambda room: self.search(q, room, counts, flags)], counts, capacity)
-        entries = lst[: 3 * kept].cpu().numpy().reshape(-1, 3)
-        data = slots[: SLOT_BYTES * kept].cpu().numpy().reshape(-1, SLOT_BYTES)
-        order = np.argsort(entries[:, 0], kind="stable")
-        entries, data = entries[order], data[order]
+        entries, data, _, passed = kept_records(lambda room, counts: self.search(q, room, counts, flags), capacity, 3, SLOT_BYTES, (0,))
         out = dict(n=entries[:, 0].copy(), nbits=entries[:, 1].copy(), P=entries[:, 2].copy(), data=data, candidates=passed)
         if keep_flags:
             out["flags"] = flags

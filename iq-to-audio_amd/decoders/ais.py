@@ -8,7 +8,7 @@ the level per burst: there is no loop.  Merging, the bit fields and the NMEA sen
 frames and run on plain numpy arrays as well (``parse_frames``)."""
 from __future__ import annotations
 
-from ctypes import c_double, c_int32, c_int64
+from ctypes import c_int32, c_int64
 from dataclasses import dataclass, field
 
 import numpy as np
@@ -16,7 +16,7 @@ import numpy as np
 from .. import _dev as D
 from .. import _native as N
 from .. import dsp_plan as P
-from .common import SideStage, carried_history, group_records, search_with_room
+from .common import FrameCore, SideStage, group_records, parse_head, phase_planes, stage_records
 
 PHASES = P.AIS_PHASES
 MIN_FRAME, MAX_FRAME = 11, 128  # bytes, FCS included
@@ -196,11 +196,7 @@ def parse_frames(plan: P.AisPlan, records: dict, candidates: int = 0, *, frequen
     """``records``: dict(phase=[k], s=[k], start=[k], nbytes=[k], data=uint8[k, >= nbytes]) in any order (the kept-frame list
     of ``iqa_ais_frames``) -> the run's messages; ``frequency`` (Hz) names the channel of the sentences.  Integer logic only;
     ``None`` where no frame survives."""
-    start = np.asarray(records["start"], dtype=np.int64).reshape(-1)
-    phase = np.asarray(records["phase"], dtype=np.int64).reshape(-1)
-    nbytes = np.asarray(records["nbytes"], dtype=np.int64).reshape(-1)
-    data = np.asarray(records["data"], dtype=np.uint8).reshape(start.size, -1) if start.size else np.zeros((0, 0), dtype=np.uint8)
-    res = AisResult(candidates=int(candidates), crc_ok=int(start.size))
+    res, start, phase, nbytes, data = parse_head(AisResult, records, candidates, "start", "phase", "nbytes")
     channel, seq = channel_of(frequency), 0
     for at, raw, hits, _ in group_records(start, nbytes, data, plan.L, tie=phase):
         got = decode_message(raw)
@@ -212,72 +208,38 @@ def parse_frames(plan: P.AisPlan, records: dict, candidates: int = 0, *, frequen
     return res if res.messages else None
 
 
-class AisCore:
-    """Per-stream device state: the carried quantised history (W - 1 values), the absolute position, and the growing store
-    of the filter output (one int32 device tensor per block, joined by ``finish``).  ``keep_stages`` also stores t, for the
-    tests."""
+class AisCore(FrameCore):
+    """Per-stream device state (``StreamCore``): the carried quantised history (W - 1 values), the absolute position, and the
+    growing store of the filter output (one int32 device tensor per block, joined by ``finish``).  ``keep_stages`` also stores
+    t, for the tests."""
+
+    bits_entry, frames_entry = "iqa_ais_symbols", "iqa_ais_frames"
+    SLOT_BYTES, PHASES, STREAMS = SLOT_BYTES, PHASES, PHASES
+    key, plane_keys, plane_dtype = "phase", ("v", "nsym"), "int32"
 
     def __init__(self, plan: P.AisPlan, *, keep_stages: bool = False):
-        self.plan = plan
-        self.hist_len = plan.W - 1
+        super().__init__(plan, plan.W, plan.symbol_count, plan.W - 1, dict(S="int32", t=None))
         self._taps = D.from_numpy(np.ascontiguousarray(plan.taps))
-        self._hist = None  # device int32[hist_len]; None = zeros
-        self.pos = 0  # absolute index of the next block's first sample
         self.keep_stages = keep_stages
-        self._s: list = []
-        self._t: list = []
 
-    def process(self, theta) -> None:
+    def _block(self, theta, n: int):
         """One block of the discriminator output (device float32[n], radians per sample)."""
-        n = int(theta.numel())
-        if n == 0:
-            return
         t, s = D.empty(n, "int32"), D.empty(n, "int32")
         N.call("iqa_ais_filter", N.ptr(theta), c_int64(n), N.ptr(self._hist), c_int32(self.plan.W), N.ptr(self._taps), N.ptr(t), N.ptr(s),
                N.stream_ptr())
-        self._s.append(s)
+        self.store.append("S", s)
         if self.keep_stages:
-            self._t.append(t)
-        self._hist = carried_history(self._hist, t, self.hist_len)
-        self.pos += n
+            self.store.append("t", t)
+        return t
 
     def joined(self) -> dict:
-        torch = D.torch_mod()
-        if len(self._s) > 1:
-            self._s = [torch.cat(self._s)]
-            self._t = [torch.cat(self._t)] if self._t else []
-        return dict(S=self._s[0] if self._s else D.empty(0, "int32"), t=self._t[0] if self._t else None)
-
-    def reset(self) -> None:
-        """Back to a stream that has seen nothing: no history, position 0, no stored plane."""
-        self._hist, self.pos, self._s, self._t = None, 0, [], []
-
-    def _frames(self, v, nsym: int, count_of, capacity: int, counts):
-        lst, slots = D.empty(4 * capacity, "int64"), D.empty(SLOT_BYTES * capacity, "uint8")
-        N.call("iqa_ais_frames", N.ptr(v), c_int64(nsym), count_of, c_int32(self.plan.W), c_double(self.plan.step), N.ptr(lst), N.ptr(slots),
-               c_int64(capacity), N.ptr(counts), N.stream_ptr())
-        return lst, slots
+        return dict(S=self.store.joined("S"), t=self.store.joined("t"))
 
     def finish(self, capacity: int = 256) -> dict:
         """The symbol planes and the kept frames of the stored run: dict(phase, s, start, nbytes, data, candidates, v, nsym,
         count_of), the records as numpy arrays sorted by (phase, s).  A list too short for the kept frames is never used:
         the search is repeated with room for all of them."""
-        plan = self.plan
-        S = self.joined()["S"]
-        n = int(S.numel())
-        counts_of = [plan.symbol_count(p, n) for p in range(PHASES)]
-        nsym = max(counts_of)
-        count_of = (c_int64 * PHASES)(*counts_of)
-        v = D.empty(PHASES * nsym, "int32")
-        N.call("iqa_ais_symbols", N.ptr(S), c_int64(n), c_int32(plan.W), c_double(plan.step), c_int64(nsym), N.ptr(v), N.stream_ptr())
-        counts = D.zeros(2, "int64")
-        ((lst, slots),), (kept, closed) = search_with_room([lambda room: self._frames(v, nsym, count_of, room, counts)], counts, capacity)
-        entries = lst[: 4 * kept].cpu().numpy().reshape(-1, 4)
-        data = slots[: SLOT_BYTES * kept].cpu().numpy().reshape(-1, SLOT_BYTES)
-        order = np.lexsort((entries[:, 1], entries[:, 0]))
-        entries, data = entries[order], data[order]
-        return dict(phase=entries[:, 0].copy(), s=entries[:, 1].copy(), start=entries[:, 2].copy(), nbytes=entries[:, 3].copy(), data=data,
-                    candidates=closed, v=v, nsym=nsym, count_of=counts_of)
+        return self.frames_of(self.store.joined("S"), capacity)
 
     def result(self, fin=None, *, frequency=None, **context) -> AisResult | None:
         """The run's ``AisResult`` (``None`` without a message); ``frequency`` names the channel of the sentences; ``fin``: a
@@ -302,9 +264,5 @@ class AisDecoder(SideStage):
         symbols), ``records`` ([(phase, s, start instant, bytes)] sorted) and ``candidates``."""
         fin = self._finished()
         st = self.core.joined()
-        plane = fin["v"].cpu().numpy().reshape(PHASES, -1) if fin["nsym"] else np.zeros((PHASES, 0), dtype=np.int32)
-        v = [plane[p, : fin["count_of"][p]] for p in range(PHASES)]
-        records = [(int(p), int(s), int(at), fin["data"][k, : int(nb)].tobytes())
-                   for k, (p, s, at, nb) in enumerate(zip(fin["phase"], fin["s"], fin["start"], fin["nbytes"]))]
         return dict(theta=self._inputs_host(), t=None if st["t"] is None else st["t"].cpu().numpy(),
-                    S=st["S"].cpu().numpy(), v=v, records=records, candidates=fin["candidates"])
+                    S=st["S"].cpu().numpy(), v=phase_planes(self.core, fin), records=stage_records(fin, "phase"), candidates=fin["candidates"])

@@ -8,7 +8,7 @@ search: there is no loop.  Merging, address validation and parsing are integer h
 plain numpy arrays as well (``parse_frames``)."""
 from __future__ import annotations
 
-from ctypes import c_double, c_int32, c_int64
+from ctypes import c_int32, c_int64
 from dataclasses import asdict, dataclass, field
 
 import numpy as np
@@ -16,7 +16,7 @@ import numpy as np
 from .. import _dev as D
 from .. import _native as N
 from .. import dsp_plan as P
-from .common import SideStage, carried_history, group_records, search_with_room
+from .common import FrameCore, SideStage, group_records, parse_head, phase_planes, stage_records
 
 FLAG = 0x7E
 CRC_POLY = 0x8408  # CRC-16/X.25, reflected; init 0xFFFF, final xor 0xFFFF
@@ -107,11 +107,7 @@ def parse_frame(raw: bytes):
 def parse_frames(plan: P.AfskPlan, records: dict, candidates: int = 0) -> Ax25Result | None:
     """``records``: dict(variant=[k], s=[k], start=[k], nbytes=[k], data=uint8[k, >= nbytes]) in any order (the kept-frame
     list of ``iqa_afsk_frames``) -> the run's frames.  Integer logic only; ``None`` where no frame survives."""
-    start = np.asarray(records["start"], dtype=np.int64).reshape(-1)
-    variant = np.asarray(records["variant"], dtype=np.int64).reshape(-1)
-    nbytes = np.asarray(records["nbytes"], dtype=np.int64).reshape(-1)
-    data = np.asarray(records["data"], dtype=np.uint8).reshape(start.size, -1) if start.size else np.zeros((0, 0), dtype=np.uint8)
-    res = Ax25Result(candidates=int(candidates), crc_ok=int(start.size))
+    res, start, variant, nbytes, data = parse_head(Ax25Result, records, candidates, "start", "variant", "nbytes")
     for at, raw, hits, _ in group_records(start, nbytes, data, plan.L, tie=variant):
         got = parse_frame(raw)
         if got is None:
@@ -121,77 +117,41 @@ def parse_frames(plan: P.AfskPlan, records: dict, candidates: int = 0) -> Ax25Re
     return res if res.frames else None
 
 
-class AfskCore:
-    """Per-stream device state: the carried quantised history (L - 1 values), the absolute position, and the growing store
-    of the slicer plane (one uint8 device tensor per block, joined by ``finish``).  ``keep_stages`` also stores t and the
-    two energy planes, for the tests."""
+class AfskCore(FrameCore):
+    """Per-stream device state (``StreamCore``): the carried quantised history (L - 1 values), the absolute position, and the
+    growing store of the slicer plane (one uint8 device tensor per block, joined by ``finish``).  ``keep_stages`` also stores t
+    and the two energy planes, for the tests."""
+
+    bits_entry, frames_entry = "iqa_afsk_bits", "iqa_afsk_frames"
+    SLOT_BYTES, PHASES, STREAMS = SLOT_BYTES, P.AFSK_PHASES, VARIANTS
+    key, plane_keys, plane_dtype = "variant", ("bits", "nbits"), "uint8"
 
     def __init__(self, plan: P.AfskPlan, *, keep_stages: bool = False):
-        self.plan = plan
-        self.hist_len = plan.L - 1
+        super().__init__(plan, plan.L, plan.bit_count, plan.L - 1, dict(sign="uint8", t=None, E0=None, E1=None))
         self._taps = D.from_numpy(np.ascontiguousarray(plan.taps))
-        self._hist = None  # device int32[hist_len]; None = zeros
-        self.pos = 0  # absolute index of the next block's first sample
         self.keep_stages = keep_stages
-        self._sign: list = []
-        self._t: list = []
-        self._e: list = []  # per block: (E_1200, E_2200)
 
-    def process(self, theta) -> None:
+    def _block(self, theta, n: int):
         """One block of the discriminator output (device float32[n], radians per sample)."""
-        n = int(theta.numel())
-        if n == 0:
-            return
         t, sign = D.empty(n, "int32"), D.empty(n, "uint8")
         e = (D.empty(n, "int64"), D.empty(n, "int64")) if self.keep_stages else (None, None)
         N.call("iqa_afsk_correlate", N.ptr(theta), c_int64(n), N.ptr(self._hist), c_int32(self.plan.L), N.ptr(self._taps), N.ptr(t),
                N.ptr(sign), N.ptr(e[0]), N.ptr(e[1]), N.stream_ptr())
-        self._sign.append(sign)
+        self.store.append("sign", sign)
         if self.keep_stages:
-            self._t.append(t)
-            self._e.append(e)
-        self._hist = carried_history(self._hist, t, self.hist_len)
-        self.pos += n
+            for name, plane in (("t", t), ("E0", e[0]), ("E1", e[1])):
+                self.store.append(name, plane)
+        return t
 
     def joined(self) -> dict:
-        torch = D.torch_mod()
-        if len(self._sign) > 1:
-            self._sign = [torch.cat(self._sign)]
-            self._t = [torch.cat(self._t)] if self._t else []
-            self._e = [tuple(torch.cat(col) for col in zip(*self._e))] if self._e else []
-        return dict(sign=self._sign[0] if self._sign else D.empty(0, "uint8"), t=self._t[0] if self._t else None,
-                    E=dict(zip(P.AFSK_TONES, self._e[0])) if self._e else None)
-
-    def reset(self) -> None:
-        """Back to a stream that has seen nothing: no history, position 0, no stored planes."""
-        self._hist, self.pos, self._sign, self._t, self._e = None, 0, [], [], []
-
-    def _frames(self, bits, nbits: int, count_of, capacity: int, counts):
-        lst, slots = D.empty(4 * capacity, "int64"), D.empty(SLOT_BYTES * capacity, "uint8")
-        N.call("iqa_afsk_frames", N.ptr(bits), c_int64(nbits), count_of, c_int32(self.plan.L), c_double(self.plan.step), N.ptr(lst),
-               N.ptr(slots), c_int64(capacity), N.ptr(counts), N.stream_ptr())
-        return lst, slots
+        e = (self.store.joined("E0"), self.store.joined("E1"))
+        return dict(sign=self.store.joined("sign"), t=self.store.joined("t"), E=None if e[0] is None else dict(zip(P.AFSK_TONES, e)))
 
     def finish(self, capacity: int = 256) -> dict:
         """The bit streams and the kept frames of the stored run: dict(variant, s, start, nbytes, data, candidates, bits,
         count_of), the records as numpy arrays sorted by (variant, s).  A list too short for the kept frames is never used:
         the search is repeated with room for all of them."""
-        plan = self.plan
-        sign = self.joined()["sign"]
-        n = int(sign.numel())
-        counts_of = [plan.bit_count(p, n) for p in range(P.AFSK_PHASES)]
-        nbits = max(counts_of)
-        count_of = (c_int64 * P.AFSK_PHASES)(*counts_of)
-        bits = D.empty(VARIANTS * nbits, "uint8")
-        N.call("iqa_afsk_bits", N.ptr(sign), c_int64(n), c_int32(plan.L), c_double(plan.step), c_int64(nbits), N.ptr(bits), N.stream_ptr())
-        counts = D.zeros(2, "int64")
-        ((lst, slots),), (kept, closed) = search_with_room([lambda room: self._frames(bits, nbits, count_of, room, counts)], counts, capacity)
-        entries = lst[: 4 * kept].cpu().numpy().reshape(-1, 4)
-        data = slots[: SLOT_BYTES * kept].cpu().numpy().reshape(-1, SLOT_BYTES)
-        order = np.lexsort((entries[:, 1], entries[:, 0]))
-        entries, data = entries[order], data[order]
-        return dict(variant=entries[:, 0].copy(), s=entries[:, 1].copy(), start=entries[:, 2].copy(), nbytes=entries[:, 3].copy(), data=data,
-                    candidates=closed, bits=bits, nbits=nbits, count_of=counts_of)
+        return self.frames_of(self.store.joined("sign"), capacity)
 
     def result(self, fin=None, **context) -> Ax25Result | None:
         """The run's ``Ax25Result`` (``None`` without a frame); ``fin``: a ``finish()`` made earlier."""
@@ -213,10 +173,7 @@ class Ax25Decoder(SideStage):
         as long as its phase has bits) and ``records`` ([(variant, s, start instant, bytes)] sorted)."""
         fin = self._finished()
         st = self.core.joined()
-        plane = fin["bits"].cpu().numpy().reshape(VARIANTS, -1) if fin["nbits"] else np.zeros((VARIANTS, 0), dtype=np.uint8)
-        bits = [plane[v, : fin["count_of"][v % P.AFSK_PHASES]] for v in range(VARIANTS)]
-        records = [(int(v), int(s), int(at), fin["data"][k, : int(nb)].tobytes())
-                   for k, (v, s, at, nb) in enumerate(zip(fin["variant"], fin["s"], fin["start"], fin["nbytes"]))]
         return dict(theta=self._inputs_host(), t=None if st["t"] is None else st["t"].cpu().numpy(),
                     E=None if st["E"] is None else {f: e.cpu().numpy() for f, e in st["E"].items()},
-                    sign=st["sign"].cpu().numpy(), bits=bits, records=records, candidates=fin["candidates"])
+                    sign=st["sign"].cpu().numpy(), bits=phase_planes(self.core, fin), records=stage_records(fin, "variant"),
+                    candidates=fin["candidates"])

@@ -15,7 +15,7 @@ import numpy as np
 from .. import _dev as D
 from .. import _native as N
 from .. import dsp_plan as P
-from .common import SideStage, carried_history, search_with_room
+from .common import SideStage, StreamCore, search_with_room
 
 SYNC_WORD = 0x7CD215D8
 IDLE_WORD = 0x7A89C197
@@ -137,51 +137,33 @@ def parse_batches(plan: P.PocsagPlan, batches: dict) -> PocsagResult | None:
     return res
 
 
-class PocsagCore:
-    """Per-stream device state: the carried quantised history, the absolute position, and the growing store of the
-    integrator planes (one device tensor per block and baud, joined by ``finish``).  ``keep_t`` also stores t."""
+class PocsagCore(StreamCore):
+    """Per-stream device state (``StreamCore``): the carried quantised history, the absolute position, and the growing store
+    of the integrator planes (one device tensor per block and baud, joined by ``finish``).  ``keep_t`` also stores t."""
 
     def __init__(self, plan: P.PocsagPlan, *, keep_t: bool = False):
-        self.plan = plan
-        self.hist_len = plan.hist_len
+        super().__init__(plan, plan.hist_len, {"t": None, **{pb.baud: "int32" for pb in plan.bauds}})
         self._windows = (c_int32 * 3)(*plan.lengths())
-        self._active = [i for i, L in enumerate(plan.lengths()) if L]  # slots of P.POCSAG_BAUDS that run
+        self._active = [i for i, L in enumerate(plan.lengths()) if L]  # slots of P.POCSAG_BAUDS that run, in the order of plan.bauds
         self._offsets_dev = {pb.baud: D.from_numpy(np.ascontiguousarray(pb.offsets)) for pb in plan.bauds}
-        self._hist = None  # device int32[hist_len]; None = zeros
-        self.pos = 0  # absolute index of the next block's first sample
         self.keep_t = keep_t
-        self._t: list = []
-        self._s: list = []  # per block: one int32 tensor per active baud
 
-    def process(self, theta) -> None:
+    def _block(self, theta, n: int):
         """One block of the discriminator output (device float32[n], radians per sample)."""
-        n = int(theta.numel())
-        if n == 0:
-            return
         t = D.empty(n, "int32")
-        planes = [D.empty(n, "int32") for _ in self._active]
         outs = (c_void_p * 3)()
-        for slot, plane in zip(self._active, planes):
+        for slot, pb in zip(self._active, self.plan.bauds):
+            plane = D.empty(n, "int32")
             outs[slot] = plane.data_ptr()
+            self.store.append(pb.baud, plane)
         N.call("iqa_pocsag_integrate", N.ptr(theta), c_int64(n), N.ptr(self._hist), c_int32(self.hist_len), self._windows, N.ptr(t),
                outs, N.stream_ptr())
-        self._s.append(planes)
         if self.keep_t:
-            self._t.append(t)
-        self._hist = carried_history(self._hist, t, self.hist_len)
-        self.pos += n
+            self.store.append("t", t)
+        return t
 
     def joined(self) -> dict:
-        torch = D.torch_mod()
-        if len(self._s) > 1:
-            self._s = [[torch.cat(col) for col in zip(*self._s)]]
-            self._t = [torch.cat(self._t)] if self._t else []
-        planes = self._s[0] if self._s else [D.empty(0, "int32") for _ in self._active]
-        return dict(t=self._t[0] if self._t else None, S={pb.baud: s for pb, s in zip(self.plan.bauds, planes)})
-
-    def reset(self) -> None:
-        """Back to a stream that has seen nothing: no history, position 0, no stored planes."""
-        self._hist, self.pos, self._t, self._s = None, 0, [], []
+        return dict(t=self.store.joined("t"), S={pb.baud: self.store.joined(pb.baud) for pb in self.plan.bauds})
 
     def _search(self, pb, s, score, capacity: int, count):
         lst = D.empty(4 * capacity, "int64")

@@ -16,7 +16,7 @@ import numpy as np
 from .. import _dev as D
 from .. import _native as N
 from .. import dsp_plan as P
-from .common import SideStage, carried_history
+from .common import SideStage, StreamCore
 
 NONE = P.TONES_NONE
 MIN_RUN = 3  # frames of one code that make an event
@@ -104,49 +104,31 @@ def parse_tones(plan: P.TonesPlan, ctcss_codes, dtmf_codes) -> TonesResult | Non
     return res if (res.ctcss or res.dtmf) else None
 
 
-class TonesCore:
-    """Per-stream device state: the carried quantised history (2R - 2 values), the absolute position, and the growing
-    store of ``u`` (one int32 device tensor per block, joined by ``finish``).  ``keep_stages`` also stores t, for the
-    tests."""
+class TonesCore(StreamCore):
+    """Per-stream device state (``StreamCore``): the carried quantised history (2R - 2 values), the absolute position, and
+    the growing store of ``u`` (one int32 device tensor per block, joined by ``finish``).  ``keep_stages`` also stores t, for
+    the tests."""
 
     def __init__(self, plan: P.TonesPlan, *, keep_stages: bool = False):
-        self.plan = plan
-        self.hist_len = 2 * plan.R - 2
+        super().__init__(plan, 2 * plan.R - 2, dict(u="int32", t=None))
         self._ctcss_taps = D.from_numpy(np.ascontiguousarray(plan.ctcss_taps))
         self._dtmf_taps = D.from_numpy(np.ascontiguousarray(plan.dtmf_taps))
-        self._hist = None  # device int32[hist_len]; None = zeros
-        self.pos = 0  # absolute index of the next block's first sample
         self.keep_stages = keep_stages
-        self._u: list = []
-        self._t: list = []
 
-    def process(self, theta) -> None:
+    def _block(self, theta, n: int):
         """One block of the discriminator output (device float32[n], radians per sample)."""
-        n = int(theta.numel())
-        if n == 0:
-            return
         R = self.plan.R
         t, u = D.empty(n, "int32"), D.empty((self.pos + n) // R - self.pos // R, "int32")
         N.call("iqa_tones_decimate", N.ptr(theta), c_int64(n), c_int64(self.pos), N.ptr(self._hist), c_int32(R), N.ptr(t),
                N.ptr(u) if u.numel() else N.ptr(None), N.stream_ptr())
         if u.numel():
-            self._u.append(u)
+            self.store.append("u", u)
         if self.keep_stages:
-            self._t.append(t)
-        self._hist = carried_history(self._hist, t, self.hist_len)
-        self.pos += n
+            self.store.append("t", t)
+        return t
 
     def joined(self) -> dict:
-        torch = D.torch_mod()
-        if len(self._u) > 1:
-            self._u = [torch.cat(self._u)]
-        if len(self._t) > 1:
-            self._t = [torch.cat(self._t)]
-        return dict(u=self._u[0] if self._u else D.empty(0, "int32"), t=self._t[0] if self._t else None)
-
-    def reset(self) -> None:
-        """Back to a stream that has seen nothing: no history, position 0, no stored u."""
-        self._hist, self.pos, self._u, self._t = None, 0, [], []
+        return dict(u=self.store.joined("u"), t=self.store.joined("t"))
 
     def finish(self) -> dict:
         """The banks and the decisions over the stored run, as device tensors: ``E_ctcss`` int64[Fc * 50], ``E_dtmf``

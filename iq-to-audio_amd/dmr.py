@@ -8,11 +8,16 @@ every sliced burst.  The host checks the payload (Reed-Solomon(12,9) or CRC-CCIT
 fields (``parse_bursts``) and follows the calls of every slot (``track_calls``): integer logic.  The constants are written
 from memory of ETSI TS 102 361-1 and of open-source readers of it, not checked against either here.  Nothing is listened to:
 no vocoder, no embedded or short link control.  No CPU path: without a GPU or the built library the device calls raise
-``RuntimeError``."""
+``RuntimeError``.
+
+What is DMR's own lives here: the checks, the device calls, the burst parser, the call tracker, the dataclasses,
+``decode_stream`` and ``channel_of``.  What every protocol layer shares lives in ``protocol_layer.py``: the stored stream under
+``DmrDecoder``, the per-lane loop under ``finish_dmr``, the builder under ``dmr_result``, and ``label`` / ``lines`` / ``to_json`` /
+``from_json`` of the results."""
 from __future__ import annotations
 
 from ctypes import c_int32, c_int64
-from dataclasses import asdict, dataclass, field
+from dataclasses import dataclass, field
 
 import numpy as np
 
@@ -20,6 +25,7 @@ from . import _dev as D
 from . import _native as N
 from . import dsp_plan as P
 from . import identify as I
+from . import protocol_layer as L
 
 PATTERNS = tuple(p for p in I.PATTERNS if p.protocol == "dmr")  # bs, ms: a hit with C > 0 is the voice word, with C < 0 the data word
 KINDS = ("bs voice", "bs data", "ms voice", "ms data")
@@ -185,7 +191,7 @@ def apply_flags(rec, levels, kinds) -> np.ndarray:
 
 
 @dataclass
-class DmrBurst:
+class DmrBurst(L.JsonRecord):
     time_s: float  # where sync symbol 0 ends, in seconds of the stream
     kind: int  # 0 bs voice, 1 bs data, 2 ms voice, 3 ms data
     slot: int | None  # 1 or 2; None for an ms kind or an unread TACT
@@ -211,9 +217,6 @@ class DmrBurst:
         if self.flco is not None:
             return f"{head} {self.type_name} {FLCO.get(self.flco, f'flco {self.flco}')} {self.src} -> {self.dst}{tail}"
         return f"{head} {self.type_name} {self.hex or ''}{tail}".rstrip()
-
-    def to_json(self) -> dict:
-        return asdict(self)
 
 
 def new_counts() -> dict:
@@ -270,7 +273,7 @@ def parse_bursts(rows, levels, info, rec, fs_ch: float, keyed_from: int = 0) -> 
 
 
 @dataclass
-class DmrCall:
+class DmrCall(L.JsonRecord):
     start_s: float
     end_s: float
     slot: int | None
@@ -286,9 +289,6 @@ class DmrCall:
         frames = f"{self.superframes} superframe{'' if self.superframes == 1 else 's'}"
         return (f"DMR cc={'?' if self.cc is None else self.cc} ts={'?' if self.slot is None else self.slot} {who} "
                 f"{self.end_s - self.start_s:.2f} s ({frames}{'' if self.terminated else ', not terminated'})")
-
-    def to_json(self) -> dict:
-        return asdict(self)
 
 
 def track_calls(bursts) -> list:
@@ -332,7 +332,7 @@ def track_calls(bursts) -> list:
 
 
 @dataclass
-class DmrChannel:
+class DmrChannel(L.JsonRecord, L.ChannelLabel):
     offset_hz: float  # the finder's
     freq_hz: float | None
     kinds: dict = field(default_factory=dict)  # bursts per kind name
@@ -346,9 +346,7 @@ class DmrChannel:
     calls: list = field(default_factory=list)  # DmrCall, in order of their start
     bursts: list = field(default_factory=list)  # DmrBurst: the data bursts that are not idle, the failed ones with checked = False
     note: str = ""  # why nothing was decoded
-
-    def label(self) -> str:
-        return f"{self.freq_hz:.0f} Hz" if self.freq_hz is not None else f"{self.offset_hz:+.0f} Hz"
+    NESTED = {"calls": DmrCall, "bursts": DmrBurst}
 
     def lines(self) -> list:
         """One line per call and per checked CSBK, in order of time."""
@@ -356,37 +354,17 @@ class DmrChannel:
         items += [(b.time_s, 1, b.line()) for b in self.bursts if b.data_type == 3 and b.checked]
         return [f"{self.label()}: {line}" for _, _, line in sorted(items)]
 
-    def to_json(self) -> dict:
-        return asdict(self)
-
 
 @dataclass
-class DmrResult:
+class DmrResult(L.JsonRecord, L.ChannelLines):
     channels: list = field(default_factory=list)  # DmrChannel, in the order of the FindResult's channels
     sample_rate: float = 0.0
     center_freq: float | None = None
-
-    def lines(self) -> list:
-        return [line for ch in self.channels for line in ch.lines()]
+    NESTED = {"channels": DmrChannel}
 
     @property
     def calls(self) -> list:
         return [call for ch in self.channels for call in ch.calls]
-
-    def to_json(self) -> dict:
-        return asdict(self)
-
-    @classmethod
-    def from_json(cls, data: dict) -> "DmrResult":
-        data = dict(data)
-        chans = []
-        for ch in data.get("channels", []):
-            ch = dict(ch)
-            ch["calls"] = [DmrCall(**c) for c in ch.get("calls", [])]
-            ch["bursts"] = [DmrBurst(**b) for b in ch.get("bursts", [])]
-            chans.append(DmrChannel(**ch))
-        data["channels"] = chans
-        return cls(**data)
 
 
 # ---- one stream ---------------------------------------------------------------------------------------------------------------
@@ -415,50 +393,19 @@ def channel_of(st: dict, fs_ch: float, keyed_from: int, offset_hz: float, freq_h
     return out
 
 
-class DmrDecoder:
-    """A DMR decoder for one discriminator stream from Python: ``process(theta_block)`` per block (float32, radians per sample
-    at ``fs_ch``), ``finish()`` once (a ``DmrResult`` of one channel), ``stages()`` for the tests, ``reset()``.  ``centre``:
-    section 23's centre of the quantised stream.  ``ValueError`` where ``fs_ch`` does not fit (``plan_dmr``)."""
+class DmrDecoder(L.StoredTheta):
+    """A DMR decoder for one discriminator stream from Python (``protocol_layer.StoredTheta``): ``finish()`` gives a
+    ``DmrResult`` of one channel, ``stages()`` ``decode_stream``'s output with the plane on the host, and ``hits``."""
 
-    def __init__(self, fs_ch: float, centre: int = 0):
-        self.plan = P.plan_dmr(fs_ch)
-        self.centre = int(centre)
-        self.reset()
+    plan_of = staticmethod(P.plan_dmr)
+    planes = ("v",)
 
-    def reset(self) -> None:
-        self._stored: list = []
-        self._st = None
-        self._result = None
-
-    def process(self, theta_block) -> None:
-        theta = D.to_device(theta_block, "float32").reshape(-1)
-        if int(theta.numel()):
-            self._stored.append(theta)
-            self._st = self._result = None
-
-    def _theta(self):
-        if not self._stored:
-            return D.empty(0, "float32")
-        return self._stored[0] if len(self._stored) == 1 else D.torch_mod().cat(self._stored)
-
-    def finish(self) -> DmrResult:
-        if self._result is None:
-            theta = self._theta()
-            if int(theta.numel()) > P.IDENT_MAX_N:
-                raise ValueError(f"a stored stream of {int(theta.numel())} samples is longer than 2^30")
-            v = I.integrate(theta, self.plan.ident, self.centre)
-            _, hits = I.search(v, self.plan.ident, PATTERNS)
-            self._st = decode_stream(theta, self.plan, self.centre, hits, PATTERNS, v)
-            self._st["hits"] = hits
-            self._result = DmrResult(channels=[channel_of(self._st, self.plan.fs_ch, 0, 0.0, None)], sample_rate=self.plan.fs_ch)
-        return self._result
-
-    def stages(self) -> dict:
-        """``decode_stream``'s output with the plane on the host, and ``hits``."""
-        self.finish()
-        st = dict(self._st)
-        st["v"] = st["v"].cpu().numpy()
-        return st
+    def _decode(self, theta) -> tuple:
+        v = I.integrate(theta, self.plan.ident, self.centre)
+        _, hits = I.search(v, self.plan.ident, PATTERNS)
+        st = decode_stream(theta, self.plan, self.centre, hits, PATTERNS, v)
+        st["hits"] = hits
+        return st, DmrResult(channels=[channel_of(st, self.plan.fs_ch, 0, 0.0, None)], sample_rate=self.plan.fs_ch)
 
 
 # ---- the layer of the second pass (describe.py) ---------------------------------------------------------------------------------
@@ -470,34 +417,13 @@ def finish_dmr(lanes, found) -> list:
     """Per lane of the pass (``found``: its dict of ``identify.finish_identify``) the output of ``decode_stream`` with ``plan`` (the
     ``DmrPlan``) and ``note``, or a dict of ``note`` alone where nothing is decoded: the channel is not of the 4800 family, its
     rate does not fit or nothing was searched.  It reuses section 25's hits and plane and runs no second search."""
-    out = []
-    for lane, d in zip(lanes, found):
-        if d["rate"] != 4800:
-            out.append(dict(note="no dmr channel"))
-            continue
-        try:
-            plan = P.plan_dmr(lane.plan.fs_ch)
-        except ValueError:
-            plan = None
-        if plan is None or d["hits"] is None:
-            out.append(dict(note="rate does not fit" if plan is None or d["plan"] is None else "not measured"))
-            continue
-        st = decode_stream(I._stored_theta(lane), plan, lane.centre, d["hits"], I.patterns_for(4800), d["v"])
-        st.update(plan=plan, note="")
-        out.append(st)
-    return out
+    return L.finish_lanes(lanes, found, 4800, P.plan_dmr, "dmr",
+                          lambda theta, plan, centre, hits, v: decode_stream(theta, plan, centre, hits, I.patterns_for(4800), v))
 
 
 def dmr_result(channels, lanes, decoded, sample_rate: float, center_freq: float | None = None) -> DmrResult:
     """The ``DmrResult`` of the pass: ``channels`` the finder's, ``decoded`` the dicts of ``finish_dmr``."""
-    chans = []
-    for ch, lane, st in zip(channels, lanes, decoded):
-        freq = None if center_freq is None else center_freq + ch.offset_hz
-        if "rows" not in st:
-            chans.append(DmrChannel(offset_hz=ch.offset_hz, freq_hz=freq, note=st["note"]))
-        else:
-            chans.append(channel_of(st, lane.plan.fs_ch, lane.keyed_from, ch.offset_hz, freq))
-    return DmrResult(channels=chans, sample_rate=sample_rate, center_freq=center_freq)
+    return L.layer_result(DmrResult, DmrChannel, channel_of, channels, lanes, decoded, sample_rate, center_freq)
 
 
 def stage_keys(describer, j: int, lane, keep: bool) -> dict:

@@ -6,11 +6,15 @@ the sync-1 hits that section 25 keeps (``identify.py``) to the text of its pages
 interleave and checks every word as a BCH(31,21) codeword, at five timing shifts.  The host keeps the best shift of every block
 (``choose_shifts``) and parses the words (``parse_frames``): integer logic on numpy arrays.  The constants are written from
 memory of the FLEX air interface and of multimon-ng's reading of it, not checked against either here.  No CPU path: without
-a GPU or the built library the device calls raise ``RuntimeError``."""
+a GPU or the built library the device calls raise ``RuntimeError``.
+
+What is FLEX's own lives here: the device calls, the shifts, the parser, the dataclasses, ``decode_stream`` and ``channel_of``.
+What every protocol layer shares lives in ``protocol_layer.py``: the stored stream under ``FlexDecoder``, the per-lane loop
+under ``finish_flex``, the builder under ``flex_result``, and ``label`` / ``lines`` / ``to_json`` / ``from_json`` of the results."""
 from __future__ import annotations
 
 from ctypes import c_int32, c_int64
-from dataclasses import asdict, dataclass, field
+from dataclasses import dataclass, field
 
 import numpy as np
 
@@ -18,6 +22,7 @@ from . import _dev as D
 from . import _native as N
 from . import dsp_plan as P
 from . import identify as I
+from . import protocol_layer as L
 
 MARKER = 0xA6C6AAAA
 SYNC_B = 0x5939  # bits 48 .. 63 of the 1600 bit/s grid; not read
@@ -137,7 +142,7 @@ def take_shifts(arr, chosen) -> np.ndarray:
 
 
 @dataclass
-class FlexPage:
+class FlexPage(L.JsonRecord):
     time_s: float  # the frame's marker, in seconds of the stream
     cycle: int
     frame: int
@@ -160,9 +165,6 @@ class FlexPage:
         if self.text is not None:
             head += f' "{self.text}"'
         return head + (" (damaged)" if self.damaged else "")
-
-    def to_json(self) -> dict:
-        return asdict(self)
 
 
 def _chars(info: int) -> list:
@@ -303,7 +305,7 @@ def parse_frames(heads, fixed, status) -> tuple:
 
 
 @dataclass
-class FlexChannel:
+class FlexChannel(L.JsonRecord, L.ChannelLabel):
     offset_hz: float  # the finder's
     freq_hz: float | None
     frames: dict = field(default_factory=dict)  # frames per mode
@@ -317,43 +319,22 @@ class FlexChannel:
     shifts: dict = field(default_factory=dict)  # blocks per chosen shift ("-2" .. "2", in steps)
     pages: list = field(default_factory=list)  # FlexPage, in order of time, phase, address
     note: str = ""  # why nothing was decoded
-
-    def label(self) -> str:
-        return f"{self.freq_hz:.0f} Hz" if self.freq_hz is not None else f"{self.offset_hz:+.0f} Hz"
+    NESTED = {"pages": FlexPage}
 
     def lines(self) -> list:
         return [f"{self.label()}: {page.line()}" for page in self.pages]
 
-    def to_json(self) -> dict:
-        return asdict(self)
-
 
 @dataclass
-class FlexResult:
+class FlexResult(L.JsonRecord, L.ChannelLines):
     channels: list = field(default_factory=list)  # FlexChannel, in the order of the FindResult's channels
     sample_rate: float = 0.0
     center_freq: float | None = None
-
-    def lines(self) -> list:
-        return [line for ch in self.channels for line in ch.lines()]
+    NESTED = {"channels": FlexChannel}
 
     @property
     def pages(self) -> list:
         return [page for ch in self.channels for page in ch.pages]
-
-    def to_json(self) -> dict:
-        return asdict(self)
-
-    @classmethod
-    def from_json(cls, data: dict) -> "FlexResult":
-        data = dict(data)
-        chans = []
-        for ch in data.get("channels", []):
-            ch = dict(ch)
-            ch["pages"] = [FlexPage(**p) for p in ch.get("pages", [])]
-            chans.append(FlexChannel(**ch))
-        data["channels"] = chans
-        return cls(**data)
 
 
 # ---- one stream ---------------------------------------------------------------------------------------------------------------
@@ -435,52 +416,20 @@ def channel_of(st: dict, fs_ch: float, keyed_from: int, offset_hz: float, freq_h
     return out
 
 
-class FlexDecoder:
-    """A FLEX decoder for one discriminator stream from Python: ``process(theta_block)`` per block (float32, radians per sample
-    at ``fs_ch``), ``finish()`` once (a ``FlexResult`` of one channel), ``stages()`` for the tests, ``reset()``.  ``centre``:
-    section 23's centre of the quantised stream.  ``ValueError`` where ``fs_ch`` does not fit (``plan_flex``)."""
+class FlexDecoder(L.StoredTheta):
+    """A FLEX decoder for one discriminator stream from Python (``protocol_layer.StoredTheta``): ``finish()`` gives a
+    ``FlexResult`` of one channel, ``stages()`` ``decode_stream``'s output with the planes on the host, and ``hits``."""
 
-    def __init__(self, fs_ch: float, centre: int = 0):
-        self.plan = P.plan_flex(fs_ch)
-        self.centre = int(centre)
-        self.reset()
+    plan_of = staticmethod(P.plan_flex)
+    planes = ("v16", "v32")
 
-    def reset(self) -> None:
-        self._stored: list = []
-        self._st = None
-        self._result = None
-
-    def process(self, theta_block) -> None:
-        theta = D.to_device(theta_block, "float32").reshape(-1)
-        if int(theta.numel()):
-            self._stored.append(theta)
-            self._st = self._result = None
-
-    def _theta(self):
-        if not self._stored:
-            return D.empty(0, "float32")
-        return self._stored[0] if len(self._stored) == 1 else D.torch_mod().cat(self._stored)
-
-    def finish(self) -> FlexResult:
-        if self._result is None:
-            theta = self._theta()
-            if int(theta.numel()) > P.IDENT_MAX_N:
-                raise ValueError(f"a stored stream of {int(theta.numel())} samples is longer than 2^30")
-            pats = I.patterns_for(1600)
-            v16 = I.integrate(theta, self.plan.ident[0], self.centre)
-            _, hits = I.search(v16, self.plan.ident[0], pats)
-            self._st = decode_stream(theta, self.plan, self.centre, hits, pats, v16)
-            self._st["hits"] = hits
-            self._result = FlexResult(channels=[channel_of(self._st, self.plan.fs_ch, 0, 0.0, None)], sample_rate=self.plan.fs_ch)
-        return self._result
-
-    def stages(self) -> dict:
-        """``decode_stream``'s output with the planes on the host, and ``hits``."""
-        self.finish()
-        st = dict(self._st)
-        for name in ("v16", "v32"):
-            st[name] = None if st[name] is None else st[name].cpu().numpy()
-        return st
+    def _decode(self, theta) -> tuple:
+        pats = I.patterns_for(1600)
+        v16 = I.integrate(theta, self.plan.ident[0], self.centre)
+        _, hits = I.search(v16, self.plan.ident[0], pats)
+        st = decode_stream(theta, self.plan, self.centre, hits, pats, v16)
+        st["hits"] = hits
+        return st, FlexResult(channels=[channel_of(st, self.plan.fs_ch, 0, 0.0, None)], sample_rate=self.plan.fs_ch)
 
 
 # ---- the layer of the second pass (describe.py) ---------------------------------------------------------------------------------
@@ -492,34 +441,13 @@ def finish_flex(lanes, found) -> list:
     """Per lane of the pass (``found``: its dict of ``identify.finish_identify``) the output of ``decode_stream`` with ``plan`` (the
     ``FlexPlan``) and ``note``, or a dict of ``note`` alone where nothing is decoded: the channel is not of the 1600 family, its
     rate does not fit or nothing was searched.  It reuses section 25's hits and plane and runs no second search."""
-    out = []
-    for lane, d in zip(lanes, found):
-        if d["rate"] != 1600:
-            out.append(dict(note="no flex channel"))
-            continue
-        try:
-            plan = P.plan_flex(lane.plan.fs_ch)
-        except ValueError:
-            plan = None
-        if plan is None or d["hits"] is None:
-            out.append(dict(note="rate does not fit" if plan is None or d["plan"] is None else "not measured"))
-            continue
-        st = decode_stream(I._stored_theta(lane), plan, lane.centre, d["hits"], I.patterns_for(1600), d["v"])
-        st.update(plan=plan, note="")
-        out.append(st)
-    return out
+    return L.finish_lanes(lanes, found, 1600, P.plan_flex, "flex",
+                          lambda theta, plan, centre, hits, v: decode_stream(theta, plan, centre, hits, I.patterns_for(1600), v))
 
 
 def flex_result(channels, lanes, decoded, sample_rate: float, center_freq: float | None = None) -> FlexResult:
     """The ``FlexResult`` of the pass: ``channels`` the finder's, ``decoded`` the dicts of ``finish_flex``."""
-    chans = []
-    for ch, lane, st in zip(channels, lanes, decoded):
-        freq = None if center_freq is None else center_freq + ch.offset_hz
-        if "rows" not in st:
-            chans.append(FlexChannel(offset_hz=ch.offset_hz, freq_hz=freq, note=st["note"]))
-        else:
-            chans.append(channel_of(st, lane.plan.fs_ch, lane.keyed_from, ch.offset_hz, freq))
-    return FlexResult(channels=chans, sample_rate=sample_rate, center_freq=center_freq)
+    return L.layer_result(FlexResult, FlexChannel, channel_of, channels, lanes, decoded, sample_rate, center_freq)
 
 
 def stage_keys(describer, j: int, lane, keep: bool) -> dict:

@@ -10,7 +10,7 @@ without a GPU or the built library the device calls raise ``RuntimeError``."""
 from __future__ import annotations
 
 from ctypes import c_int8, c_int32, c_int64
-from dataclasses import asdict, dataclass, field
+from dataclasses import dataclass, field
 
 import numpy as np
 
@@ -18,6 +18,7 @@ from . import _dev as D
 from . import _native as N
 from . import dsp_plan as P
 from .decoders.common import search_with_room
+from .protocol_layer import JsonRecord, checked_theta, join_theta
 
 
 @dataclass(frozen=True)
@@ -202,7 +203,7 @@ def decide(hits, pats, plan: P.IdentPlan) -> dict:
 
 
 @dataclass
-class ChannelProtocol:
+class ChannelProtocol(JsonRecord):
     offset_hz: float  # the finder's
     freq_hz: float | None
     baud: int | None  # section 23's keyed rate; None where the channel is not keyed
@@ -233,27 +234,16 @@ class ChannelProtocol:
         n = self.pairs.get(self.protocol, 0)
         return f"    protocol: {head} ({short}; {n} pair{'' if n == 1 else 's'} on the {1000.0 * mine.grid / self.family:g} ms grid)"
 
-    def to_json(self) -> dict:
-        return asdict(self)
-
 
 @dataclass
-class ProtocolResult:
+class ProtocolResult(JsonRecord):
     channels: list = field(default_factory=list)  # ChannelProtocol, in the order of the FindResult's channels
     sample_rate: float = 0.0
     center_freq: float | None = None
+    NESTED = {"channels": ChannelProtocol}
 
     def lines(self) -> list:
         return [ch.line() for ch in self.channels]
-
-    def to_json(self) -> dict:
-        return asdict(self)
-
-    @classmethod
-    def from_json(cls, data: dict) -> "ProtocolResult":
-        data = dict(data)
-        data["channels"] = [ChannelProtocol(**ch) for ch in data.get("channels", [])]
-        return cls(**data)
 
 
 def family_plan(keyed_label: str | None, baud, fs_ch: float) -> tuple:
@@ -287,9 +277,8 @@ def protocol_of(keyed, hits, plan: P.IdentPlan | None, rate, note: str, keyed_fr
 
 
 def _stored_theta(lane):
-    """A lane's stored discriminator stream as one device tensor: the single block, or the blocks joined.  Made anew by every
-    call and kept by none: the stream can approach 2^30 samples."""
-    return lane.stored[0] if len(lane.stored) == 1 else D.torch_mod().cat(lane.stored)
+    """A lane's stored discriminator stream as one device tensor (``protocol_layer.join_theta``)."""
+    return join_theta(lane.stored)
 
 
 def finish_identify(lanes, keyed, keep: bool, plane_rates=()) -> list:
@@ -303,9 +292,7 @@ def finish_identify(lanes, keyed, keep: bool, plane_rates=()) -> list:
         rate, plan, note = family_plan(k.label, k.baud if k.label is not None else None, lane.plan.fs_ch)
         d = dict(rate=rate, plan=plan, note=note, hits=None)
         if plan is not None and lane.centre is not None and lane.stored:
-            theta = _stored_theta(lane)
-            if int(theta.numel()) > P.IDENT_MAX_N:
-                raise ValueError(f"a stored stream of {int(theta.numel())} samples is longer than 2^30")
+            theta = checked_theta(lane.stored)
             v = integrate(theta, plan, lane.centre)
             score, d["hits"] = search(v, plan, patterns_for(rate))
             if keep or rate in plane_rates:

@@ -6,13 +6,14 @@ from __future__ import annotations
 import logging
 import math
 from ctypes import c_int32, c_int64
-from dataclasses import asdict, dataclass, field
+from dataclasses import dataclass, field
 
 import numpy as np
 
 from . import _dev as D
 from . import _native as N
 from . import dsp_plan as P
+from .protocol_layer import JsonRecord
 
 LOG = logging.getLogger(__name__)
 
@@ -29,7 +30,7 @@ NFM_RATE, WFM_RATE = 96_000.0, 480_000.0  # the channel rates a target of that m
 
 
 @dataclass
-class ChannelKeying:
+class ChannelKeying(JsonRecord):
     offset_hz: float  # the finder's
     freq_hz: float | None
     described: str  # the label of section 22
@@ -63,27 +64,16 @@ class ChannelKeying:
         flags = " ".join(f"--{name}" for name in self.decoders)
         return f"    keying: {head} -> {flags}" + (f" --bw {self.bw:.0f}" if "ais" in self.decoders else "")
 
-    def to_json(self) -> dict:
-        return asdict(self)
-
 
 @dataclass
-class KeyingResult:
+class KeyingResult(JsonRecord):
     channels: list = field(default_factory=list)  # ChannelKeying, in the order of the FindResult's channels
     sample_rate: float = 0.0
     center_freq: float | None = None
+    NESTED = {"channels": ChannelKeying}
 
     def lines(self) -> list:
         return [ch.line() for ch in self.channels]
-
-    def to_json(self) -> dict:
-        return asdict(self)
-
-    @classmethod
-    def from_json(cls, data: dict) -> "KeyingResult":
-        data = dict(data)
-        data["channels"] = [ChannelKeying(**ch) for ch in data.get("channels", [])]
-        return cls(**data)
 
 
 def keying_centre(cr: int, ci: int) -> int:

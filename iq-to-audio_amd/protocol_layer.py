@@ -1,0 +1,134 @@
+"""What the protocol layers behind section 25 share (``flex.py``, ``dmr.py``; DESIGN.md, "Adding a layer to the second pass"):
+the stored discriminator stream of one channel (``join_theta``, ``StoredTheta``), the per-lane loop of a layer's ``finish_*``
+(``finish_lanes``), its result builder (``layer_result``) and the mixins of the result classes (``JsonRecord``,
+``ChannelLabel``, ``ChannelLines``).  A layer's module keeps its plan, its device calls, its parser and its dataclasses.
+Nothing here touches the GPU at import; ``identify.py``, which the layers import, imports this module in turn."""
+from __future__ import annotations
+
+from dataclasses import asdict
+
+from . import _dev as D
+from . import dsp_plan as P
+
+
+def join_theta(stored):
+    """The stored blocks of one discriminator stream (device float32) as one device tensor: the single block, or the blocks
+    joined, or an empty tensor.  Made anew by every call and kept by none: the stream can approach 2^30 samples."""
+    if not stored:
+        return D.empty(0, "float32")
+    return stored[0] if len(stored) == 1 else D.torch_mod().cat(stored)
+
+
+def checked_theta(stored):
+    """``join_theta``, with ``ValueError`` for a stream longer than the sync search indexes (``IDENT_MAX_N``)."""
+    theta = join_theta(stored)
+    if int(theta.numel()) > P.IDENT_MAX_N:
+        raise ValueError(f"a stored stream of {int(theta.numel())} samples is longer than 2^30")
+    return theta
+
+
+class StoredTheta:
+    """A protocol decoder for one discriminator stream from Python: ``process(theta_block)`` per block (float32, radians per
+    sample at ``fs_ch``), ``finish()`` once (the layer's result of one channel), ``stages()`` for the tests, ``reset()``.
+    ``centre``: section 23's centre of the quantised stream.  The subclass names its plan function (``ValueError`` where
+    ``fs_ch`` does not fit), the device planes that ``stages()`` moves to the host, and writes ``_decode(theta)``: (the stages
+    of the stream, its result)."""
+
+    plan_of = None
+    planes = ()
+
+    def __init__(self, fs_ch: float, centre: int = 0):
+        self.plan = type(self).plan_of(fs_ch)
+        self.centre = int(centre)
+        self.reset()
+
+    def reset(self) -> None:
+        self._stored: list = []
+        self._st = None
+        self._result = None
+
+    def process(self, theta_block) -> None:
+        theta = D.to_device(theta_block, "float32").reshape(-1)
+        if int(theta.numel()):
+            self._stored.append(theta)
+            self._st = self._result = None
+
+    def finish(self):
+        if self._result is None:
+            self._st, self._result = self._decode(checked_theta(self._stored))
+        return self._result
+
+    def stages(self) -> dict:
+        """The stages of ``_decode`` with the planes on the host."""
+        self.finish()
+        st = dict(self._st)
+        for name in self.planes:
+            st[name] = None if st[name] is None else st[name].cpu().numpy()
+        return st
+
+
+def finish_lanes(lanes, found, rate: int, plan_of, word: str, decode) -> list:
+    """The ``finish_*`` of a layer: per lane of the pass (``found``: its dict of ``identify.finish_identify``) the output of
+    ``decode(theta, plan, centre, hits, v)`` with ``plan`` (``plan_of`` the lane's rate) and ``note``, or a dict of ``note``
+    alone where nothing is decoded: the channel is not of the family ``rate`` ("no ``word`` channel"), its rate does not fit
+    or nothing was searched.  It reuses section 25's hits and plane and runs no second search."""
+    out = []
+    for lane, d in zip(lanes, found):
+        if d["rate"] != rate:
+            out.append(dict(note=f"no {word} channel"))
+            continue
+        try:
+            plan = plan_of(lane.plan.fs_ch)
+        except ValueError:
+            plan = None
+        if plan is None or d["hits"] is None:
+            out.append(dict(note="rate does not fit" if plan is None or d["plan"] is None else "not measured"))
+            continue
+        st = decode(join_theta(lane.stored), plan, lane.centre, d["hits"], d["v"])
+        st.update(plan=plan, note="")
+        out.append(st)
+    return out
+
+
+def layer_result(result, channel, channel_of, channels, lanes, decoded, sample_rate: float, center_freq: float | None = None):
+    """The ``result`` of the pass (``FlexResult``, ``DmrResult``): ``channels`` the finder's, ``decoded`` the dicts of the layer's
+    ``finish_*``; per channel ``channel_of`` its decoded stream, or a ``channel`` of the note alone."""
+    chans = []
+    for ch, lane, st in zip(channels, lanes, decoded):
+        freq = None if center_freq is None else center_freq + ch.offset_hz
+        if "rows" not in st:
+            chans.append(channel(offset_hz=ch.offset_hz, freq_hz=freq, note=st["note"]))
+        else:
+            chans.append(channel_of(st, lane.plan.fs_ch, lane.keyed_from, ch.offset_hz, freq))
+    return result(channels=chans, sample_rate=sample_rate, center_freq=center_freq)
+
+
+class JsonRecord:
+    """``to_json`` / ``from_json`` of a result dataclass.  ``NESTED`` names the list fields that hold dataclasses (field ->
+    class, itself a ``JsonRecord``); a mixin, not a dataclass: the fields and their order are the class's own."""
+
+    NESTED = {}
+
+    def to_json(self) -> dict:
+        return asdict(self)
+
+    @classmethod
+    def from_json(cls, data: dict):
+        data = dict(data)
+        for name, item in cls.NESTED.items():
+            data[name] = [item.from_json(x) for x in data.get(name, [])]
+        return cls(**data)
+
+
+class ChannelLabel:
+    """``label()`` of a channel dataclass with ``freq_hz`` and ``offset_hz``: its frequency, or its offset where none is known."""
+
+    def label(self) -> str:
+        return f"{self.freq_hz:.0f} Hz" if self.freq_hz is not None else f"{self.offset_hz:+.0f} Hz"
+
+
+class ChannelLines:
+    """``lines()`` of a result whose ``channels`` have ``lines()`` of their own: all of them, in channel order."""
+
+    def lines(self) -> list:
+        return [line for ch in self.channels for line in ch.lines()]
