@@ -935,6 +935,40 @@ int iqa_dmr_slice(const void *plane_dev, int64_t n, const void *hits_dev, int64_
 int iqa_dmr_decode(const void *bits_dev, const void *kinds_dev, int64_t K, void *info_dev, void *rec_dev, void *stream);
 
 /* ------------------------------------------------------------------------- *
+ * NIDs, link control and TSBKs of a P25 phase 1 channel (--find-p25) *
+ * ------------------------------------------------------------------------- */
+
+#define IQA_P25_OFFSETS 864 /* o[i] = rint(i sps), i = 0 .. 863: the symbols of one LDU behind the end of sync symbol 0 */
+#define IQA_P25_WORDS 54    /* uint32 words of a sliced frame: symbol i the frame bits 2 i, 2 i + 1 */
+#define IQA_P25_INFO 9      /* uint32 words of a decoded frame's information */
+#define IQA_P25_RECORD 8    /* int32 values of a decoded frame */
+/* The levels and the bits of K frame sync hits.  plane_dev: int32[n], iqa_ident_integrate's output at 4800 symbols/s (|v| <=
+ * 64 * 65534).  hits_dev: int64[K][2], (m, s): m where sync symbol 0 ends, s the sign of the hit (negative: -1, the same word
+ * with the spectrum inverted; else +1).  offsets (host): the IQA_P25_OFFSETS sample offsets of the symbols 0 .. 863, ascending
+ * in steps of at most IQA_IDENT_MAX_SPS + 1, o[0] = 0.  valid = 0 if m + o[0] < 0, else the number of i with m + o[i] < n.
+ * With x_i = plane[m + o[i]], i = 0 .. 23, P = sum x_i and Q = sum sgn_i x_i (sgn_i the sign of sync symbol i): A = s (12 Q + P)
+ * and Dc = 12 P + Q, 286 times the outer level and the DC; both 0 where valid < 24.  Symbol i < valid reads as d = s (286
+ * plane[m + o[i]] - Dc): its first bit (d < 0), its second (3 |d| >= 2 A); every other bit is 0.  bits_dev: uint32[K][54], the
+ * first sent bit the MSB of word 0.  levels_dev: int64[K][3]: A, Dc, valid.  Every instant is checked against 0 .. n - 1
+ * before it is read.  n <= 2^30, K <= 2^20.  n = 0 or K = 0 returns IQA_OK and touches no pointer. */
+int iqa_p25_slice(const void *plane_dev, int64_t n, const void *hits_dev, int64_t K, const int32_t offsets[IQA_P25_OFFSETS],
+                  void *bits_dev, void *levels_dev, void *stream);
+/* The network identifier of K sliced frames: the data bits 48 .. 111 (data dibit q is frame symbol q + q / 35), the first 63
+ * against the 65 536 codewords of BCH(63,16,23).  nid_dev: int32[K][4]: status (0 clean, 1 corrected at a distance of 1 .. 11,
+ * 2 refused with the raw top 16 bits kept), distance, value (NAC << 4 | DUID; on equal distance the smaller), parity_ok (the 64
+ * bits have even weight).  K <= 2^20.  K = 0 returns IQA_OK and touches no pointer. */
+int iqa_p25_nid(const void *bits_dev, int64_t K, void *nid_dev, void *stream);
+/* What lies behind the NID of K sliced frames, by DUID (duids_dev: uint8[K], the four low bits are read): 0x5 the 24
+ * Hamming(10,6,3) words of an LDU1's link control (class 1), 0xF the twelve Golay(24,12,8) words of a TDULC (class 2), 0x7 the
+ * three rate 1/2 trellis blocks of a TSBK frame (class 3); any other DUID gives zeros (class 0).  info_dev: uint32[K][9]:
+ * classes 1 and 2 the 144 link control bits in words 0 .. 4, class 3 the 96 bits of block b in words 3 b .. 3 b + 2, the first
+ * bit the MSB.  rec_dev: int32[K][8]: the class, then for classes 1 and 2 the corrected words, the unmatched (Hamming) or
+ * refused (Golay, distance over 3: the raw top 12 bits kept) words and the bits changed, for class 3 the three blocks' metrics
+ * (channel bits changed); the rest 0.  The codes are DESIGN.md section 31's.  K <= 2^20.  K = 0 returns IQA_OK and touches no
+ * pointer. */
+int iqa_p25_decode(const void *bits_dev, const void *duids_dev, int64_t K, void *info_dev, void *rec_dev, void *stream);
+
+/* ------------------------------------------------------------------------- *
  * Carrier squelch of a run's targets (--squelch)       *
  * ------------------------------------------------------------------------- */
 

@@ -1105,6 +1105,33 @@ def plan_dmr(fs_ch: float) -> DmrPlan:
     return DmrPlan(fs_ch=ident.fs_ch, sps=ident.sps, offsets=offsets, ident=ident)
 
 
+# ---- P25 frame decoding plan (--find-p25) ----------------------------------
+
+P25_OFFSETS = 864  # o[i], i = 0 .. 863: the symbols of one LDU, the longest frame read
+P25_WORDS = 54  # uint32 words of a sliced frame: symbol i the frame bits 2 i, 2 i + 1
+P25_INFO = 9  # uint32 words of a decoded frame's information
+P25_RECORD = 8  # int32 values of a decoded frame
+
+
+@dataclass(frozen=True)
+class P25Plan:
+    fs_ch: float
+    sps: float  # fs_ch / 4800
+    offsets: tuple  # o[i] = rint(i sps), i = 0 .. 863 (half-even, float64)
+    ident: IdentPlan  # section 25's plan at 4800 symbols/s
+
+    def o(self, i: int) -> int:
+        return self.offsets[i]
+
+
+def plan_p25(fs_ch: float) -> P25Plan:
+    """The sample offsets of the symbols of a P25 frame behind the end of sync symbol 0 at the channel rate ``fs_ch``, and section
+    25's plan at 4800 symbols/s.  ``ValueError`` unless 4 <= sps <= 224 (``plan_ident``'s limits)."""
+    ident = plan_ident(fs_ch, 4800)
+    offsets = tuple(int(np.rint(i * ident.sps)) for i in range(P25_OFFSETS))
+    return P25Plan(fs_ch=ident.fs_ch, sps=ident.sps, offsets=offsets, ident=ident)
+
+
 # ---- carrier squelch plan (--squelch; DESIGN.md section 24) --------------------------------------
 
 GATE_CELL = 256  # IQA_GATE_CELL: samples to a cell, counted on the absolute position
