@@ -29,7 +29,7 @@
 // loaders also emit.  The text above describes the LDS-DMA form, which remains at 14..16 k steps (the multiplying waves
 // issue the DMAs) and for uint8 captures (two loader waves issue them, ring_loader).  Up to 8 k steps a row whose last k
 // step is at most half full (the ..._half kernels, D = 104 among them) runs on v_mfma_i32_16x16x64_i8 instead of 32x32x32:
-// the same tile per wave as four 16x16 blocks, the two off-diagonal ones in one accumulator, an odd last k step as a
+// the same tile per wave as four 16x16 blocks, the two off-diagonal ones in one accumulator, an odd last k step as seven
 // 16x16x32 (ring_main_h16) -- equal cycles per product, but at its power limit the chip holds a higher clock on that shape.
 // The forms measured against these and rejected are recorded in DESIGN.md section 6.
 //
@@ -833,17 +833,27 @@ __device__ __forceinline__ void ring_main(const MfmaArgs &a, const RingCtx &c, c
 // The main loop of a multiplying wave of the half-step kernels (k_channelize_mfma_s16_ring_multi_half: byte planes fed by
 // loader waves, int32 sums, one lane per workgroup): the wave's tile of 32 tap rows x 32 data rows as 16x16 blocks --
 // tap-row halves bi, data-row halves bj -- on v_mfma_i32_16x16x64_i8: a chunk of 64 values (two k steps) per instruction,
-// an odd last k step on v_mfma_i32_16x16x32_i8.  Held at its power limit the chip keeps a higher clock on this shape than on
-// 32x32x32 (probe/kstep_probe.hip `shape`).
+// twelve per chunk; an odd last k step (at most 16 values) on seven v_mfma_i32_16x16x32_i8.  Held at its power limit the chip
+// keeps a higher clock on this shape than on 32x32x32 (probe/kstep_probe.hip `shape`).
 //   * Element r of lane l of block (bi, bj) is tap row 16 bi + 4 (l >> 4) + r against data row 16 bj + (l & 15): output
 //     position 16 (bi + bj) + (l & 15) + 4 (l >> 4) + r of the tile.  Blocks (0, 1) and (1, 0) are the same positions and
 //     share their accumulators: three blocks per sum, 12 adds per tile.  (dsp_plan.plan_mfma(acc32=True) bounds any
 //     partial sum of an output's terms, so no such sum overflows.)
 //   * Tap operand of chunk c, half bi: values 64 c + 16 (l >> 4) .. + 15 of tap row 16 bi + (l & 15) -- in the planner's
 //     fragments (32x32x32 order: lane = row + 32 * (value >> 4) of the k step) that is lane 16 bi + (l & 15) + 32 ((l >> 4) & 1)
-//     of k step 2 c + (l >> 5).  The odd last step: values 8 (l >> 4) .. + 7, half a fragment.  Gathered once per wave.
+//     of k step 2 c + (l >> 5).  Gathered once per wave.
 //   * Data operand: 16 bytes at 64 c + 16 (l >> 4) of row 16 bj + (l & 15) of either plane (RingGeo::PLANE_PITCH keeps these
-//     reads conflict-free); the odd last step 8 bytes.  What a row holds past its 2 D values meets zero taps.
+//     reads conflict-free).  What a row holds past its 2 D values meets zero taps.
+//   * The odd last step holds 16 values, and the K = 32 instruction issues in the cycles of K = 64: one
+//     instruction per product would multiply half of every operand by zero taps.  So two products that add into the same
+//     accumulator share an instruction, concatenated along K -- operand [x | y] . [u ; v]: lane groups l >> 4 = 0, 1 hold
+//     values 8 ((l >> 4) & 1) .. + 7 of tap piece x and of data bytes u, groups 2, 3 those of y and v:
+//         S1[0] = [0 | q1_0] . [lo_0 ; hi_0]         S2[0] = [q1_0 | q2_0] . [lo_0 ; hi_0]
+//         S1[1] = [q1_0 | q1_1] . [hi_1 ; hi_0]      S2[1] = [q1_0 | q1_1] . [lo_1 ; lo_0] + [q2_0 | q2_1] . [hi_1 ; hi_0]
+//         S1[2] = [0 | q1_1] . [lo_1 ; hi_1]         S2[2] = [q1_1 | q2_1] . [lo_1 ; hi_1]
+//     (q1, q2 of tap-row half 0 / 1, hi, lo of data-row half 0 / 1, S[s] the block sum bi + bj = s): seven instructions for
+//     the twelve products, the same integer terms in every sum; six tap operands of 8 bytes gathered once per wave, four
+//     data operands of 8 bytes read per tile.
 template <int KS>
 __device__ __forceinline__ void ring_main_h16(const MfmaArgs &a, const RingCtx &c)
 {
@@ -852,7 +862,8 @@ __device__ __forceinline__ void ring_main_h16(const MfmaArgs &a, const RingCtx &
     constexpr int SLOT = G::SLOT, PP = G::PLANE_PITCH, NC = KS / 2, ODD = KS & 1;
     const int r16 = c.lane & 15, g = c.lane >> 4;
     v4i_t tq[NC ? NC : 1][2][2];  // [chunk][tap-row half][piece q1, q2]
-    long tl[2][2] = {};           // the odd last k step
+    long tf[6] = {};              // the odd last k step: TF_*
+    enum { TF_Z_Q10, TF_Q10_Q11, TF_Z_Q11, TF_Q10_Q20, TF_Q20_Q21, TF_Q11_Q21 };  // [x | y]: q<piece><tap-row half>, Z = zeros
     const v4i_t *fa = a.afrag + c.rt * 128;
 #pragma unroll
     for (int ch = 0; ch < NC; ++ch)
@@ -861,29 +872,42 @@ __device__ __forceinline__ void ring_main_h16(const MfmaArgs &a, const RingCtx &
 #pragma unroll
             for (int pc = 0; pc < 2; ++pc) tq[ch][bi][pc] = fa[((2 * ch + (g >> 1)) * 8 + pc) * 64 + 16 * bi + r16 + 32 * (g & 1)];
     if constexpr (ODD) {
+        long s[2][2];  // [tap-row half][piece]: values 8 (g & 1) .. + 7 of the last k step
 #pragma unroll
         for (int bi = 0; bi < 2; ++bi)
 #pragma unroll
-            for (int pc = 0; pc < 2; ++pc) tl[bi][pc] = reinterpret_cast<const long *>(fa + ((KS - 1) * 8 + pc) * 64 + 16 * bi + r16 + 32 * (g >> 1))[g & 1];
+            for (int pc = 0; pc < 2; ++pc) s[bi][pc] = reinterpret_cast<const long *>(fa + ((KS - 1) * 8 + pc) * 64 + 16 * bi + r16)[g & 1];
+        const bool up = g >> 1;  // lane groups 2, 3: the operand's second piece
+        tf[TF_Z_Q10] = up ? s[0][0] : 0;
+        tf[TF_Q10_Q11] = up ? s[1][0] : s[0][0];
+        tf[TF_Z_Q11] = up ? s[1][0] : 0;
+        tf[TF_Q10_Q20] = up ? s[0][1] : s[0][0];
+        tf[TF_Q20_Q21] = up ? s[1][1] : s[0][1];
+        tf[TF_Q11_Q21] = up ? s[1][1] : s[1][0];
     }
     // have them arrive here: a wait for them inside the round loop would be met in every round
 #pragma unroll
     for (int ch = 0; ch < NC; ++ch)
 #pragma unroll
         for (int bi = 0; bi < 2; ++bi) asm volatile("" ::"v"(tq[ch][bi][0]), "v"(tq[ch][bi][1]));
-    asm volatile("" ::"v"(tl[0][0]), "v"(tl[0][1]), "v"(tl[1][0]), "v"(tl[1][1]));
+    asm volatile("" ::"v"(tf[0]), "v"(tf[1]), "v"(tf[2]), "v"(tf[3]), "v"(tf[4]), "v"(tf[5]));
     const int lane_off = r16 * PP + 16 * g;
-    // The odd step's four 8-byte reads (data-row half, plane) each get an offset register of their own, and the compiler is
-    // not told how they relate: it would pair them into ds_read2st64_b64, whose 16-lane groups and 32 banks make this
-    // pitch a 4-way conflict (measured: 24 extra LDS cycles per instruction against 2 for a plain ds_read_b64)
-    int lane_off_odd[2][2];
+    // The odd step's four 8-byte data operands [u ; v]: lane groups 0, 1 read bytes 8 (g & 1) .. + 7 of the last k step of u,
+    // groups 2, 3 those of v (u, v: a plane and a data-row half each).  Each read gets an offset register of its own, and the
+    // compiler is not told how they relate: it would pair them into ds_read2st64_b64, whose 16-lane groups and 32 banks make
+    // this pitch a 4-way conflict (measured: 24 extra LDS cycles per instruction against 2 for a plain ds_read_b64)
+    enum { DF_L0_H0, DF_L1_L0, DF_H1_H0, DF_L1_H1 };  // [u ; v]: H / L = high / biased low bytes, of data-row half 0 / 1
+    int lane_off_odd[4];
+    {
+        const int up = g >> 1, at = r16 * PP + 32 * (KS - 1) + 8 * (g & 1);
+        const int hi_pl = 0, lo_pl = 32 * PP, bj1 = 16 * PP;
+        lane_off_odd[DF_L0_H0] = at + (up ? hi_pl : lo_pl);
+        lane_off_odd[DF_L1_L0] = at + lo_pl + (up ? 0 : bj1);
+        lane_off_odd[DF_H1_H0] = at + hi_pl + (up ? 0 : bj1);
+        lane_off_odd[DF_L1_H1] = at + bj1 + (up ? hi_pl : lo_pl);
 #pragma unroll
-    for (int pl = 0; pl < 2; ++pl)
-#pragma unroll
-        for (int bj = 0; bj < 2; ++bj) {
-            lane_off_odd[pl][bj] = r16 * PP + 32 * (KS - 1) + 8 * g + 32 * PP * pl + 16 * PP * bj;
-            asm volatile("" : "+v"(lane_off_odd[pl][bj]));
-        }
+        for (int i = 0; i < 4; ++i) asm volatile("" : "+v"(lane_off_odd[i]));
+    }
     const v4i_t zero4 = {0, 0, 0, 0};
     int slot = 0;
     for (int r = 0; r < c.rounds; ++r) {
@@ -893,21 +917,21 @@ __device__ __forceinline__ void ring_main_h16(const MfmaArgs &a, const RingCtx &
             const char *la = c.smem + (slot * 2 + c.cp) * SLOT + lane_off;
             const char *lb = c.smem + (slot * 2 + c.cp) * SLOT;
             v4i_t hh[NC ? NC : 1][2], ll[NC ? NC : 1][2];  // [chunk][data-row half]: high bytes, biased low bytes
-            long ho[2] = {}, lo[2] = {};
+            long df[4] = {};     // the odd last k step: DF_*
             v4i_t a1[3], a2[3];  // S1, S2 of the blocks bi + bj = 0, 1, 2
             auto fetch = [&](int ch) {  // `ch` is a compile-time constant at every call site
+                if (ch < NC) {
 #pragma unroll
-                for (int bj = 0; bj < 2; ++bj) {
-                    if (ch < NC) {
+                    for (int bj = 0; bj < 2; ++bj) {
                         hh[ch][bj] = *reinterpret_cast<const v4i_t *>(la + 16 * PP * bj + 64 * ch);
                         ll[ch][bj] = *reinterpret_cast<const v4i_t *>(la + 32 * PP + 16 * PP * bj + 64 * ch);
-                    } else {
-                        ho[bj] = *reinterpret_cast<const long *>(lb + lane_off_odd[0][bj]);
-                        lo[bj] = *reinterpret_cast<const long *>(lb + lane_off_odd[1][bj]);
                     }
+                } else {
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) df[i] = *reinterpret_cast<const long *>(lb + lane_off_odd[i]);
                 }
             };
-            // the twelve products of a step (q1*hi into S1; q1*lo and q2*hi into S2); an accumulator's uses lie at least two
+            // the twelve products of a chunk (q1*hi into S1; q1*lo and q2*hi into S2); an accumulator's uses lie at least two
             // instructions apart
             auto step = [&](auto mf, const auto &q, const auto &hi, const auto &lw, bool first) {
                 a2[1] = mf(q[0][0], lw[1], first ? zero4 : a2[1]);
@@ -924,14 +948,27 @@ __device__ __forceinline__ void ring_main_h16(const MfmaArgs &a, const RingCtx &
                 a2[2] = mf(q[1][1], hi[1], a2[2]);
             };
             auto mf64 = [](v4i_t x, v4i_t y, v4i_t z) { return __builtin_amdgcn_mfma_i32_16x16x64_i8(x, y, z, 0, 0, 0); };
-            auto mf32 = [](long x, long y, v4i_t z) { return __builtin_amdgcn_mfma_i32_16x16x32_i8(x, y, z, 0, 0, 0); };
+            // The same twelve products of the odd last k step, 16 values each, folded along K into seven instructions of 32: two
+            // products that add into one accumulator are one [x | y] . [u ; v].  a1[0] and a1[2] have one product each and
+            // borrow the operands of a2[0] and a2[2] with the other half of the taps zero.  The order keeps the two uses of
+            // a2[1], and every accumulator's last use in the chunk before, at least two instructions apart.
+            auto step_odd = [&](bool first) {
+                auto mf32 = [](long x, long y, v4i_t z) { return __builtin_amdgcn_mfma_i32_16x16x32_i8(x, y, z, 0, 0, 0); };
+                a1[0] = mf32(tf[TF_Z_Q10], df[DF_L0_H0], first ? zero4 : a1[0]);
+                a2[1] = mf32(tf[TF_Q10_Q11], df[DF_L1_L0], first ? zero4 : a2[1]);
+                a1[1] = mf32(tf[TF_Q10_Q11], df[DF_H1_H0], first ? zero4 : a1[1]);
+                a2[0] = mf32(tf[TF_Q10_Q20], df[DF_L0_H0], first ? zero4 : a2[0]);
+                a2[1] = mf32(tf[TF_Q20_Q21], df[DF_H1_H0], a2[1]);
+                a1[2] = mf32(tf[TF_Z_Q11], df[DF_L1_H1], first ? zero4 : a1[2]);
+                a2[2] = mf32(tf[TF_Q11_Q21], df[DF_L1_H1], first ? zero4 : a2[2]);
+            };
             fetch(0);  // reads run one step ahead of the MFMAs
 #pragma unroll
             for (int ch = 0; ch < NC; ++ch) {
                 if (ch + 1 < NC + ODD) fetch(ch + 1);
                 step(mf64, tq[ch], hh[ch], ll[ch], ch == 0);
             }
-            if constexpr (ODD) step(mf32, tl, ho, lo, NC == 0);
+            if constexpr (ODD) step_odd(NC == 0);
             // diagonal scatter into the window of sums, 256*S1 + S2 in one int32 as in ring_main (inline asm for the same reason)
             // (lanes 16 apart meet on 12 of a half wave's 20 addresses: a 2-way serialisation per add.  Sending the lanes of odd
             // l >> 4 into a second window that the emission adds measured the same)

@@ -9,7 +9,8 @@
 // against the pipe's 1 / 32.   Build: hipcc --offload-arch=gfx950 -O3 kstep_probe.hip -o kstep_probe
 //   kstep_probe shape [seconds] [pairs]: the 32x32x32 tile body against the 16x16x64 one at the same tile per wave (wall
 //     time, in-kernel clock, equal sums) and the bare issue rates of the four int8 forms -- see k_probe_shape
-//   kstep_probe lds: the LDS access patterns of both bodies, one kernel each, for a counters-only profiler run
+//   kstep_probe fold [seconds] [pairs]: the 16x16x64 body against the same with its odd last k step folded along K
+//   kstep_probe lds: the LDS access patterns of the bodies, one kernel each, for a counters-only profiler run
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
@@ -361,7 +362,9 @@ static void run_rt(const v4i *taps, int *sink, int tiles, unsigned long long *cl
 // BODY 0: six v_mfma_i32_32x32x32_i8 steps and one 32x32x16 (plane pitch 15 sixteen-byte units), lane = data row.
 // BODY 1: three v_mfma_i32_16x16x64_i8 chunks and one 16x16x32 for the odd last k step (plane pitch 14 units); the two
 //         off-diagonal 16x16 blocks of the tile land on the same output positions and share one accumulator.
-// Both read the same logical tile (random bytes) and the same tap fragments (the library's afrag layout, random, zero
+// BODY 2: BODY 1 with the odd step's twelve 16x16x32, each half against zero taps, folded along K into seven: products
+//         that add into the same accumulator are concatenated, 43 matrix instructions per tile instead of 48 (`fold`).
+// All read the same logical tile (random bytes) and the same tap fragments (the library's afrag layout, random, zero
 // beyond value 208 as the planner pads them); the windows of sums they leave must be equal -- that also checks the tap
 // gather and the lane maps.  Twelve waves as in the kernel: eight multiply (two per SIMD), four only join the barriers
 // (the loader waves' place).  In-kernel clock: s_memtime ticks per 100 MHz s_memrealtime tick (diagnostic, this probe only).
@@ -466,9 +469,13 @@ __global__ __launch_bounds__(768, 3) void k_probe_shape(const v4i *afrag, int *w
         c1 = __builtin_amdgcn_s_memtime(), r1 = __builtin_amdgcn_s_memrealtime();
     } else {
         constexpr int NC = KS / 2;  // 64-value chunks; KS odd: one 32-value step behind them
-        const int r16 = lane & 15, g = lane >> 4;
+        constexpr bool FOLD = BODY == 2;
+        const int r16 = lane & 15, g = lane >> 4, up = g >> 1;
         v4i tq[NC][2][2];  // [chunk][tap-row half][piece]
-        long tl[2][2];     // the odd last k step
+        long tl[2][2];     // the odd last k step, BODY 1: values 8 g .. + 7 (16 .. 31 are zero taps)
+        long tf[6];        // BODY 2: [x | y] -- lane groups 0, 1 values 8 (g & 1) .. + 7 of x, groups 2, 3 those of y
+        enum { TF_Z_Q10, TF_Q10_Q11, TF_Z_Q11, TF_Q10_Q20, TF_Q20_Q21, TF_Q11_Q21 };  // q<piece><tap-row half>, Z = zeros
+        enum { DF_L0_H0, DF_L1_L0, DF_H1_H0, DF_L1_H1 };  // [u ; v] of data bytes: plane H / L of data-row half 0 / 1
 #pragma unroll
         for (int c = 0; c < NC; ++c)
 #pragma unroll
@@ -479,15 +486,37 @@ __global__ __launch_bounds__(768, 3) void k_probe_shape(const v4i *afrag, int *w
         for (int bi = 0; bi < 2; ++bi)
 #pragma unroll
             for (int pc = 0; pc < 2; ++pc)
-                tl[bi][pc] = reinterpret_cast<const long *>(afrag + ((KS - 1) * 8 + rt * 2 + pc) * 64 + 16 * bi + r16 + 32 * (g >> 1))[g & 1];
+                tl[bi][pc] = reinterpret_cast<const long *>(afrag + ((KS - 1) * 8 + rt * 2 + pc) * 64 + 16 * bi + r16 + 32 * (FOLD ? 0 : up))[g & 1];
+        tf[TF_Z_Q10] = up ? tl[0][0] : 0;
+        tf[TF_Q10_Q11] = up ? tl[1][0] : tl[0][0];
+        tf[TF_Z_Q11] = up ? tl[1][0] : 0;
+        tf[TF_Q10_Q20] = up ? tl[0][1] : tl[0][0];
+        tf[TF_Q20_Q21] = up ? tl[1][1] : tl[0][1];
+        tf[TF_Q11_Q21] = up ? tl[1][1] : tl[1][0];
         const char *la = slot + r16 * PP + 16 * g;
-        const char *lb = slot + r16 * PP + 32 * (KS - 1) + 8 * g;
+        // the odd step's four 8-byte reads, an offset register each that the compiler cannot relate (paired into
+        // ds_read2st64_b64 they are a 4-way conflict at this pitch).  BODY 1: [plane][data-row half]; BODY 2: DF_*
+        int odd_off[4];
+        {
+            const int at = r16 * PP + 32 * (KS - 1), lo_pl = 32 * PP, bj1 = 16 * PP;
+            if (FOLD) {
+                odd_off[DF_L0_H0] = at + 8 * (g & 1) + (up ? 0 : lo_pl);
+                odd_off[DF_L1_L0] = at + 8 * (g & 1) + lo_pl + (up ? 0 : bj1);
+                odd_off[DF_H1_H0] = at + 8 * (g & 1) + (up ? 0 : bj1);
+                odd_off[DF_L1_H1] = at + 8 * (g & 1) + bj1 + (up ? 0 : lo_pl);
+            } else {
+#pragma unroll
+                for (int i = 0; i < 4; ++i) odd_off[i] = at + 8 * g + lo_pl * (i >> 1) + bj1 * (i & 1);
+            }
+#pragma unroll
+            for (int i = 0; i < 4; ++i) asm volatile("" : "+v"(odd_off[i]));
+        }
         const v4i zero4 = {0, 0, 0, 0};
         c0 = __builtin_amdgcn_s_memtime(), r0 = __builtin_amdgcn_s_memrealtime();
         for (int t = 0; t < tiles; ++t) {
             asm volatile("s_barrier" ::: "memory");
             v4i hh[NC][2], ll[NC][2];
-            long ho[2], lo[2];
+            long ho[2], lo[2], df[4];
             v4i a1[3], a2[3];
             auto fetch = [&](int c) {
                 if (c < NC) {
@@ -498,10 +527,8 @@ __global__ __launch_bounds__(768, 3) void k_probe_shape(const v4i *afrag, int *w
                     }
                 } else {
 #pragma unroll
-                    for (int bj = 0; bj < 2; ++bj) {
-                        ho[bj] = *reinterpret_cast<const long *>(lb + 16 * PP * bj);
-                        lo[bj] = *reinterpret_cast<const long *>(lb + 32 * PP + 16 * PP * bj);
-                    }
+                    for (int i = 0; i < 4; ++i) df[i] = *reinterpret_cast<const long *>(slot + odd_off[i]);
+                    ho[0] = df[0], ho[1] = df[1], lo[0] = df[2], lo[1] = df[3];  // (BODY 1's names)
                 }
             };
             // the twelve products of a step; an accumulator's uses lie at least two instructions apart
@@ -527,7 +554,18 @@ __global__ __launch_bounds__(768, 3) void k_probe_shape(const v4i *afrag, int *w
                 if (c + 1 < NC + (KS & 1)) fetch(c + 1);
                 step(mf64, tq[c], hh[c], ll[c], c == 0);
             }
-            if (KS & 1) step(mf32, tl, ho, lo, NC == 0);
+            if constexpr (FOLD) {
+                // the odd step's twelve K = 16 products folded along K: two products of one accumulator per instruction
+                a1[0] = mf32(tf[TF_Z_Q10], df[DF_L0_H0], a1[0]);
+                a2[1] = mf32(tf[TF_Q10_Q11], df[DF_L1_L0], a2[1]);
+                a1[1] = mf32(tf[TF_Q10_Q11], df[DF_H1_H0], a1[1]);
+                a2[0] = mf32(tf[TF_Q10_Q20], df[DF_L0_H0], a2[0]);
+                a2[1] = mf32(tf[TF_Q20_Q21], df[DF_H1_H0], a2[1]);
+                a1[2] = mf32(tf[TF_Z_Q11], df[DF_L1_H1], a1[2]);
+                a2[2] = mf32(tf[TF_Q11_Q21], df[DF_L1_H1], a2[2]);
+            } else if (KS & 1) {
+                step(mf32, tl, ho, lo, NC == 0);
+            }
             const unsigned p = static_cast<unsigned>(reinterpret_cast<size_t>((__attribute__((address_space(3))) const void *)(
                 s_acc + ((t * 64 + cp * 32 + (rt & 1) * 32 + r16 + 4 * g + 1) & 511) + (rt >> 1) * SH_AS)));
 #pragma unroll
@@ -605,6 +643,9 @@ static void run_rate(const v4i *taps, int *sink, unsigned long long *clk)
 //   KIND 1: ds_read_b128, lane l at row l & 31, unit l >> 5, rows P units apart (the 32x32x32 data operand)
 //   KIND 2: ds_read_b64, lane l at row l & 15, 8 (l >> 4) bytes into the row (the 16x16x32 data operand)
 //   KIND 3: ds_add_u32 at position (l & 15) + 4 (l >> 4) (the 16x16 blocks' scatter); KIND 4: at (l & 31) + 4 (l >> 5)
+//   KIND 5..8: ds_read_b64, lane l at row l & 15, 8 ((l >> 4) & 1) bytes into the row, lane groups 0, 1 in one (plane,
+//     data-row half) of a slot of 64 rows and groups 2, 3 in another (the folded odd step's data operands [lo0 ; hi0],
+//     [lo1 ; lo0], [hi1 ; hi0], [lo1 ; hi1]: planes 32 rows apart, halves 16)
 template <int KIND, int P>
 __global__ __launch_bounds__(64) void k_probe_lds(int *sink, int n)
 {
@@ -612,17 +653,23 @@ __global__ __launch_bounds__(64) void k_probe_lds(int *sink, int n)
     const int lane = threadIdx.x;
     for (int i = lane; i < 4096; i += 64) reinterpret_cast<int *>(smem)[i] = i;
     __syncthreads();
+    static_assert(KIND < 5 || 64 * P * 16 <= 16384, "the slot of 64 rows must fit the kernel's LDS");
+    const int up = lane >> 5, at = (lane & 15) * P * 16 + 8 * ((lane >> 4) & 1), lo_pl = 32 * P * 16, bj1 = 16 * P * 16;
     int off;
     if (KIND == 0) off = (lane & 15) * P * 16 + 16 * (lane >> 4);
     else if (KIND == 1) off = (lane & 31) * P * 16 + 16 * (lane >> 5);
     else if (KIND == 2) off = (lane & 15) * P * 16 + 8 * (lane >> 4);
     else if (KIND == 3) off = 4 * ((lane & 15) + 4 * (lane >> 4));
-    else off = 4 * ((lane & 31) + 4 * (lane >> 5));
+    else if (KIND == 4) off = 4 * ((lane & 31) + 4 * (lane >> 5));
+    else if (KIND == 5) off = at + (up ? 0 : lo_pl);
+    else if (KIND == 6) off = at + lo_pl + (up ? 0 : bj1);
+    else if (KIND == 7) off = at + (up ? 0 : bj1);
+    else off = at + bj1 + (up ? 0 : lo_pl);
     const unsigned p = static_cast<unsigned>(reinterpret_cast<size_t>((__attribute__((address_space(3))) const void *)(smem + off)));
     v4i v = {0, 0, 0, 0};
     for (int i = 0; i < n; ++i) {
         if (KIND <= 1) asm volatile("ds_read_b128 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(v) : "v"(p) : "memory");
-        else if (KIND == 2) asm volatile("ds_read_b64 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(*reinterpret_cast<long *>(&v)) : "v"(p) : "memory");
+        else if (KIND == 2 || KIND >= 5) asm volatile("ds_read_b64 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(*reinterpret_cast<long *>(&v)) : "v"(p) : "memory");
         else asm volatile("ds_add_u32 %0, %1\n\ts_waitcnt lgkmcnt(0)" ::"v"(p), "v"(lane) : "memory");
     }
     if (v.x == 0x12345678) sink[0] = v.y;
@@ -650,6 +697,16 @@ static int lds_main()
     run_lds<2, 15>(sink);
     run_lds<3, 0>(sink);
     run_lds<4, 0>(sink);
+    // the odd step's reads at the plane pitch of 7 and of 3 k steps: as they were, and the folded step's four
+    run_lds<2, 6>(sink);
+    run_lds<5, 14>(sink);
+    run_lds<6, 14>(sink);
+    run_lds<7, 14>(sink);
+    run_lds<8, 14>(sink);
+    run_lds<5, 6>(sink);
+    run_lds<6, 6>(sink);
+    run_lds<7, 6>(sink);
+    run_lds<8, 6>(sink);
     return 0;
 }
 
@@ -696,8 +753,8 @@ static ShapeResult run_shape(const v4i *afrag, int *win, unsigned long long *clk
     return r;
 }
 
-// kstep_probe shape [seconds per run] [pairs]
-static int shape_main(double seconds, int pairs)
+// kstep_probe shape [seconds per run] [pairs]; `fold`: the 16x16x64 body against the one with the folded odd step
+static int shape_main(double seconds, int pairs, bool fold)
 {
     const int tiles = 20000;
     std::vector<signed char> ha(SH_KS * 8 * 64 * 16);
@@ -718,11 +775,25 @@ static int shape_main(double seconds, int pairs)
     hipMalloc(&win, 1024 * 4);
     hipMalloc(&sink, 64);
     hipMalloc(&clk, 512 * 8);
+    int bad = 0;
+    if (fold) {
+        const ShapeResult ref = run_shape<0>(afrag, win, clk, tiles, 1e-3);  // (one batch: the 32x32x32 body's sums)
+        for (int p = 0; p < pairs; ++p) {
+            const ShapeResult a = run_shape<1>(afrag, win, clk, tiles, seconds);
+            const ShapeResult b = run_shape<2>(afrag, win, clk, tiles, seconds);
+            int diff = 0, diff_ref = 0;
+            for (int i = 0; i < 1024; ++i) diff += a.win[i] != b.win[i], diff_ref += ref.win[i] != b.win[i];
+            bad += diff + diff_ref;
+            printf("pair %d: 16x16x64 body, odd step of 12 x 16x16x32: %.1f ns per round at %.3f GHz; folded to 7: %.1f ns at %.3f GHz; ratio %.4f; "
+                   "windows differ in %d of 1024 sums, from the 32x32x32 body's in %d (first %d)\n",
+                   p, a.ns_per_round, a.ghz, b.ns_per_round, b.ghz, b.ns_per_round / a.ns_per_round, diff, diff_ref, b.win[7]);
+        }
+        return bad ? 1 : 0;
+    }
     run_rate<0>(afrag, sink, clk);
     run_rate<1>(afrag, sink, clk);
     run_rate<2>(afrag, sink, clk);
     run_rate<3>(afrag, sink, clk);
-    int bad = 0;
     for (int p = 0; p < pairs; ++p) {
         const ShapeResult a = run_shape<0>(afrag, win, clk, tiles, seconds);
         const ShapeResult b = run_shape<1>(afrag, win, clk, tiles, seconds);
@@ -739,7 +810,8 @@ static int shape_main(double seconds, int pairs)
 int main(int argc, char **argv)
 {
     if (argc > 1 && std::string(argv[1]) == "lds") return lds_main();
-    if (argc > 1 && std::string(argv[1]) == "shape") return shape_main(argc > 2 ? atof(argv[2]) : 2.0, argc > 3 ? atoi(argv[3]) : 4);
+    if (argc > 1 && (std::string(argv[1]) == "shape" || std::string(argv[1]) == "fold"))
+        return shape_main(argc > 2 ? atof(argv[2]) : 2.0, argc > 3 ? atoi(argv[3]) : 4, std::string(argv[1]) == "fold");
     const int tiles = argc > 1 ? atoi(argv[1]) : 20000;
     v4i *taps;
     int *sink;
