@@ -31,6 +31,9 @@
 // step is at most half full (the ..._half kernels, D = 104 among them) runs on v_mfma_i32_16x16x64_i8 instead of 32x32x32:
 // the same tile per wave as four 16x16 blocks, the two off-diagonal ones in one accumulator, an odd last k step as seven
 // 16x16x32 (ring_main_h16) -- equal cycles per product, but at its power limit the chip holds a higher clock on that shape.
+// Round 7: in launches of a single lane the loaders of the contiguous slots fetch with non-temporal loads (ring_load16; the
+// stream alone 6.0 -> 6.6 TB/s, probe/stream_probe.hip); the stream's phase against a 16-byte boundary costs nothing, aligned
+// loads with the shift done in registers and a second pass through LDS were slower.
 // The forms measured against these and rejected are recorded in DESIGN.md section 6.
 //
 // Every launch goes through the lane table of mfma_ring_launch_multi (k_channelize_mfma_s16_ring_multi / _multi_half /
@@ -376,18 +379,39 @@ __device__ __forceinline__ void ring_loader(const MfmaArgs &a, const RingCtx &c)
 // A loader wave of the byte-plane kernels (RingGeo::SPLIT): parity cp, half `half`.  Round r: behind the barrier it waits
 // for ITS pieces of the tile of round r + 1 (requested SPLIT_F rounds ago), splits them and writes the planes of slot
 // (r + 1) % 2 -- the slot round r - 1 has just left --, requests the tile of round r + 1 + SPLIT_F into the registers that
-// became free, and (half 0) emits like ring_loader.  Plain loads: the compiler counts vmcnt itself, the emission's store
-// included.  Pieces beyond the tile's last unit (a tile is D / 8 pieces, a wave pair fetches 2 KS) re-fetch the last unit
-// and are not written.
+// became free, and (half 0) emits like ring_loader.  Loads into registers (contiguous slots, launches of a single lane: nt,
+// ring_load16): the compiler counts vmcnt itself, the emission's store included.  Pieces beyond the tile's last unit (a tile
+// is D / 8 pieces, a wave pair fetches 2 KS) re-fetch the last unit and are not written.
 struct __attribute__((packed, aligned(4))) ring_raw16 {  // 16 bytes of the capture: dword-aligned (the stream starts at frame row*D + 1)
     int x, y, z, w;
 };
+typedef int ring_raw16v __attribute__((ext_vector_type(4), aligned(4)));  // the same for __builtin_nontemporal_load
+
+// NT: global_load_dwordx4 nt -- the contiguous slots' stream in launches of a SINGLE lane (the kernel variants ONCE: one
+// workgroup streams each range, every byte is fetched once by the whole launch).  Alone, with config 2's loader geometry,
+// the stream runs at 6.6 TB/s with it against 6.1 without (probe/stream_probe.hip, profiles/r07_stream_probe.txt).  Where
+// several lanes' workgroups stream the same range the later ones are meant to hit in L2, and nt loads cost config 3's pair
+// launches 3 %: those, and the row-staged kernels, keep the default policy.  A variant and
+// not a kernel argument: a uniform branch between the two forms of the requests cost the loaders of 10 - 13 k steps 8 - 190
+// bytes of scratch and every kernel its load schedule (config 2 +14 us, config 4's unit 1.10 -> 1.66 ms).
+template <bool NT>
+__device__ __forceinline__ int4 ring_load16(const char *p)
+{
+    if constexpr (NT) {
+        const ring_raw16v t = __builtin_nontemporal_load(reinterpret_cast<const ring_raw16v *>(p));
+        return make_int4(t.x, t.y, t.z, t.w);
+    } else {
+        const ring_raw16 t = *reinterpret_cast<const ring_raw16 *>(p);
+        return make_int4(t.x, t.y, t.z, t.w);
+    }
+}
 
 // PAIR: the four loader waves (HALF 0..3) share the round's one tile, piece 4 j + HALF each; waves 0 and 1 emit lane 0's and
 // lane 1's outputs (c.cp = the lane; a, c.s_acc, c.tshift are that lane's), every group of their lane.
-template <int KS, bool ACC64, bool ROWS, int HALF, bool PAIR = false, bool H16 = false>
+template <int KS, bool ACC64, bool ROWS, int HALF, bool PAIR = false, bool H16 = false, bool NT = false>
 __device__ __forceinline__ void ring_loader_split(const MfmaArgs &a, const RingCtx &c)
 {
+    static_assert(!NT || (!ROWS && !PAIR), "nt loads: the single-lane kernels over contiguous slots");
     constexpr bool EMITTER = PAIR ? HALF < 2 : HALF == 0;
     // pieces of a tile this wave takes: every second one, or -- from 12 k steps on, where 8 KS registers of data in flight
     // and the emission's float64 state do not fit one wave -- the emitting wave (half 0) the first KS - 2, the other the rest
@@ -440,8 +464,7 @@ __device__ __forceinline__ void ring_loader_split(const MfmaArgs &a, const RingC
                 const unsigned f = rowu[j >> 1] >> (16 * (j & 1));
                 so = static_cast<int>((f >> 6) & 31u) * row_bytes + 16 * static_cast<int>(f & 63u);
             }
-            const ring_raw16 t = *reinterpret_cast<const ring_raw16 *>(src + so);
-            buf[S][j] = make_int4(t.x, t.y, t.z, t.w);
+            buf[S][j] = ring_load16<NT>(src + so);
         }
     };
     auto stage = [&](int slot, auto set) {
@@ -992,7 +1015,7 @@ __device__ __forceinline__ void ring_main_h16(const MfmaArgs &a, const RingCtx &
 // SKIPK (kernels of launches in which some lanes have high-byte-only taps, see ring_main's SKIP): lane pairs -- the pair's
 // first lane (parity 0) skips the q2*hi product at compile time, the second never does (the host pairs a tap-row group's
 // high-byte lane with its residue lane); one lane per workgroup -- every wave asks its lane's flag.
-template <int KS, bool ACC64, bool ROWS, bool U8, bool PAIR = false, bool SKIPK = false, bool HALF = false>
+template <int KS, bool ACC64, bool ROWS, bool U8, bool PAIR = false, bool SKIPK = false, bool HALF = false, bool ONCE = false>
 __device__ __forceinline__ void ring_block(const MfmaArgs &a, long long range_idx)
 {
     using G = RingGeo<KS, ROWS, U8, PAIR, HALF>;
@@ -1041,8 +1064,8 @@ __device__ __forceinline__ void ring_block(const MfmaArgs &a, long long range_id
                     default: ring_loader_split<KS, ACC64, ROWS, 3, true>(a, c); break;
                 }
             } else if constexpr (G::SPLIT) {
-                if ((wave - RG_WAVES) >> 1) ring_loader_split<KS, ACC64, ROWS, 1, false, HALF>(a, c);
-                else ring_loader_split<KS, ACC64, ROWS, 0, false, HALF>(a, c);
+                if ((wave - RG_WAVES) >> 1) ring_loader_split<KS, ACC64, ROWS, 1, false, HALF, ONCE>(a, c);
+                else ring_loader_split<KS, ACC64, ROWS, 0, false, HALF, ONCE>(a, c);
             } else {
                 ring_loader<KS, ACC64>(a, c);
             }
@@ -1123,7 +1146,7 @@ struct RingMultiArgs {
     MfmaLane lane[RG_MAX_LANES];
 };
 
-template <int KS, bool ROWS, bool U8, bool PAIR = false, bool ACC64 = false, bool SKIPK = false, bool HALF = false>
+template <int KS, bool ROWS, bool U8, bool PAIR = false, bool ACC64 = false, bool SKIPK = false, bool HALF = false, bool ONCE = false>
 __device__ __forceinline__ void ring_multi_block(const RingMultiArgs &m)
 {
     const int idx = blockIdx.x >> 3;
@@ -1172,24 +1195,26 @@ __device__ __forceinline__ void ring_multi_block(const RingMultiArgs &m)
         a.pace_slot = static_cast<int>(range_idx) * units + idx % units;
     }
     if (range_idx * a.range >= a.n_out) return;  // (the last ranges of a short launch)
-    ring_block<KS, ACC64, ROWS, U8, PAIR, SKIPK, HALF>(a, range_idx);
+    ring_block<KS, ACC64, ROWS, U8, PAIR, SKIPK, HALF, ONCE>(a, range_idx);
 }
 
 // ACC64: one int64 (S1 << 32) + S2 per output component instead of one int32 256*S1 + S2 -- 16-bit taps without the int32
 // bound, what the "full" precision's lanes (taps + their residue, dsp_plan.plan_mfma(residual=True)) need; contiguous slots only.
-template <int KS, bool ACC64 = false, bool SKIPK = false>
+// ONCE (launches of a single lane, loader waves): the loaders stream the capture with nt loads (ring_load16).
+template <int KS, bool ACC64 = false, bool SKIPK = false, bool ONCE = false>
 __global__ __launch_bounds__((RingGeo<KS, false>::THREADS), (RingGeo<KS, false>::LOADERS ? 3 : 2)) void k_channelize_mfma_s16_ring_multi(RingMultiArgs m)
 {
-    ring_multi_block<KS, false, false, false, ACC64, SKIPK>(m);
+    static_assert(!ONCE || (RingGeo<KS, false>::SPLIT && !ACC64 && !SKIPK), "nt variant: byte-plane kernels, int32 sums, no skipped product");
+    ring_multi_block<KS, false, false, false, ACC64, SKIPK, false, ONCE>(m);
 }
 
 // ... for rows whose last k step is at most half full (rows of 32 (KS - 1) + 1 .. 16 values: D = 104 -> 208 = 6 x 32 + 16),
 // on 16x16x64 matrix tiles (ring_main_h16).
-template <int KS>
+template <int KS, bool ONCE = false>
 __global__ __launch_bounds__((RingGeo<KS, false, false, false, true>::THREADS), 3) void k_channelize_mfma_s16_ring_multi_half(RingMultiArgs m)
 {
     static_assert(RingGeo<KS, false, false, false, true>::SPLIT, "byte-plane kernels only");
-    ring_multi_block<KS, false, false, false, false, false, true>(m);
+    ring_multi_block<KS, false, false, false, false, false, true, ONCE>(m);
 }
 
 // Two lanes per workgroup (RingGeo PAIR): the lanes of the table in pairs of equal tap-row group.
@@ -1235,7 +1260,11 @@ static int ring_launch_kernel(K kernel, const char *name, int threads, const A &
 template <int KS>
 static int ring_launch_multi(const RingMultiArgs &m, unsigned blocks, size_t lds, hipStream_t stream, bool rows, bool u8, bool acc64, bool skipk)
 {
-    static std::atomic<unsigned long long> done[8] = {{0}, {0}, {0}, {0}, {0}, {0}, {0}, {0}};
+    static std::atomic<unsigned long long> done[10] = {{0}, {0}, {0}, {0}, {0}, {0}, {0}, {0}, {0}, {0}};
+    // a single lane: one workgroup streams each range, nobody fetches a byte of the capture twice -- the variants whose
+    // loaders stream it with nt loads (traces show them as <KS, false, false, true> and ..._multi_half<KS, true>)
+    const bool once = m.n_lanes == 1;
+    (void)once;  // (14 - 16 k steps have no such variant)
     if (acc64) {
         if constexpr (KS < RG_MAX_KS) {  // (64-bit sums at 16 k steps do not fit the registers)
             if (!rows && !u8) {
@@ -1262,8 +1291,12 @@ static int ring_launch_multi(const RingMultiArgs &m, unsigned blocks, size_t lds
         const int rem = (2 * m.c.D) & 31;  // values in the row's last k step
         if (rem != 0 && rem <= 16) {  // (planes at a pitch of their own: this family's LDS, not the caller's figure)
             using GH = RingGeo<KS, false, false, false, true>;
+            if (once) return ring_launch_kernel(k_channelize_mfma_s16_ring_multi_half<KS, true>, "k_channelize_mfma_s16_ring_multi", GH::THREADS, m, blocks, GH::LDS_BYTES, stream, done[9]);
             return ring_launch_kernel(k_channelize_mfma_s16_ring_multi_half<KS>, "k_channelize_mfma_s16_ring_multi", GH::THREADS, m, blocks, GH::LDS_BYTES, stream, done[7]);
         }
+    }
+    if constexpr (KS <= RG_LOADERS_MAX_KS) {
+        if (once) return ring_launch_kernel(k_channelize_mfma_s16_ring_multi<KS, false, false, true>, "k_channelize_mfma_s16_ring_multi", RingGeo<KS, false>::THREADS, m, blocks, lds, stream, done[8]);
     }
     return ring_launch_kernel(k_channelize_mfma_s16_ring_multi<KS>, "k_channelize_mfma_s16_ring_multi", RingGeo<KS, false>::THREADS, m, blocks, lds, stream, done[0]);
 }
