@@ -50,13 +50,6 @@ __device__ __forceinline__ unsigned long long ds_isqrt(unsigned long long v)
     return r;
 }
 
-__device__ __forceinline__ long long ds_wave_sum(long long v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, kWave);
-    return v;
-}
-
 __global__ __launch_bounds__(SB_THREADS) void k_describe(DescribeArgs g)
 {
     __shared__ int s_i[DS_IMAGE], s_q[DS_IMAGE];
@@ -127,7 +120,7 @@ __global__ __launch_bounds__(SB_THREADS) void k_describe(DescribeArgs g)
         }
     }
 #pragma unroll
-    for (int k = 0; k < DS_SUMS; ++k) sum[k] = ds_wave_sum(sum[k]);
+    for (int k = 0; k < DS_SUMS; ++k) sum[k] = wave_sum(sum[k]);
     if (tid % kWave == 0) {
 #pragma unroll
         for (int k = 0; k < DS_SUMS; ++k) s_part[tid / kWave][k] = sum[k];

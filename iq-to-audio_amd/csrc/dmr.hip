@@ -26,8 +26,9 @@
 // k_dmr_slice is one wave per hit: its lanes gather the 144 instants (three strided reads at the most), the levels are
 // reduced across the wave, nine lanes pack the words.  k_dmr_decode is a workgroup of 256 per burst: a codeword of the slot
 // type to a thread with a minimum over (distance, value), then the de-interleaved bits in LDS and a thread per column and per
-// row under block-uniform barriers.  Plain C++ stores, no inline assembly, no atomics, no mutable statics.
-#include "common.h"
+// row under block-uniform barriers.  The sync word's signs, the Golay encoder, the minimum, the dibit rule, the packing and the
+// host prologue are protocol.h's.  Plain C++ stores, no inline assembly, no atomics, no mutable statics.
+#include "protocol.h"
 
 namespace iqa {
 
@@ -40,82 +41,32 @@ constexpr int DM_WORDS = IQA_DMR_WORDS;      // 9 words of 32 bits: 24 + 264
 constexpr int DM_REC = IQA_DMR_RECORD;       // 8
 constexpr int DM_ROUNDS = 5;
 constexpr unsigned long long DM_BS_VOICE = 0x755FD7DF75F7ull, DM_MS_VOICE = 0x7F7D5DD57DFDull;
-constexpr unsigned DM_GOLAY_POLY = 0xC75u;
-constexpr long long DM_V_MAX = 64LL * 65534;  // |plane|
 
-static_assert(24 * DM_V_MAX * 2 < (1LL << 40), "24 y - Sigma and 3 |d| stay far inside int64");
+static_assert(24 * PL_V_MAX * 2 < (1LL << 40), "24 y - Sigma and 3 |d| stay far inside int64");
 static_assert(DM_OFFSETS == 2 * DM_WAVE + 16 && 2 * DM_OFFSETS == 32 * DM_WORDS, "144 symbols: three passes of a wave, nine words");
 
 struct DmrOffsets {
     int o[DM_OFFSETS];
 };
 
-// whether symbol i (0 .. 23) of a sync word is a positive level: the dibits 01 (+3) and 00 (+1) have a clear first bit
-__host__ __device__ constexpr bool dm_positive(unsigned long long word, int i) { return ((word >> (2 * (23 - i) + 1)) & 1ull) == 0; }
+static_assert(pl_sync_ups(DM_BS_VOICE) == 12 && pl_sync_ups(DM_MS_VOICE) == 12, "both sync words hold twelve +3 and twelve -3: Sigma / 24 is the DC");
 
-constexpr bool dm_balanced(unsigned long long word)
-{
-    int up = 0;
-    for (int i = 0; i < 24; ++i) {
-        if (((word >> (2 * (23 - i))) & 1ull) == 0) return false;  // only the outer levels: 01 and 11
-        up += dm_positive(word, i) ? 1 : 0;
-    }
-    return up == 12;
-}
-static_assert(dm_balanced(DM_BS_VOICE) && dm_balanced(DM_MS_VOICE), "both sync words hold twelve +3 and twelve -3: Sigma / 24 is the DC");
-
-__host__ __device__ constexpr unsigned dm_parity(unsigned x)
-{
-    x ^= x >> 16;
-    x ^= x >> 8;
-    x ^= x >> 4;
-    x ^= x >> 2;
-    x ^= x >> 1;
-    return x & 1u;
-}
-
-__host__ __device__ constexpr unsigned dm_popcount(unsigned x)
-{
-    unsigned c = 0;
-    for (; x; x &= x - 1) ++c;
-    return c;
-}
-
-// the slot type's codeword of an 8-bit value
-__host__ __device__ constexpr unsigned dm_golay(unsigned data)
-{
-    unsigned r = data << 11;
-    for (int i = 18; i >= 11; --i)
-        if ((r >> i) & 1u) r ^= DM_GOLAY_POLY << (i - 11);
-    const unsigned cw = (data << 12) | ((r & 0x7FFu) << 1);
-    return cw | dm_parity(cw);
-}
-
+// the slot type's codewords of the 8-bit values
 struct DmrGolay {
     unsigned cw[256];
+    constexpr unsigned word(unsigned d) const { return cw[d]; }
 };
 
 constexpr DmrGolay dm_golay_table()
 {
     DmrGolay t{};
-    for (unsigned d = 0; d < 256; ++d) t.cw[d] = dm_golay(d);
+    for (unsigned d = 0; d < 256; ++d) t.cw[d] = pl_golay(d, 8);
     return t;
-}
-
-constexpr unsigned dm_golay_distance(const DmrGolay &t)
-{
-    unsigned best = 20;
-    for (int a = 0; a < 256; ++a)
-        for (int b = a + 1; b < 256; ++b) {
-            const unsigned d = dm_popcount(t.cw[a] ^ t.cw[b]);
-            if (d < best) best = d;
-        }
-    return best;
 }
 
 constexpr DmrGolay DM_GOLAY_HOST = dm_golay_table();
 static_assert(DM_GOLAY_HOST.cw[1] == 0x18EBu && DM_GOLAY_HOST.cw[2] == 0x293Eu && DM_GOLAY_HOST.cw[4] == 0x4A97u, "the slot type's codewords of 1, 2 and 4");
-static_assert(dm_golay_distance(DM_GOLAY_HOST) == 8, "the 256 codewords lie 8 apart at the least: a word within 3 of one is within 3 of no other");
+static_assert(pl_golay_distance(DM_GOLAY_HOST, 256) == 8, "the 256 codewords lie 8 apart at the least: a word within 3 of one is within 3 of no other");
 __device__ const DmrGolay DM_GOLAY = dm_golay_table();
 
 // The parity checks as masks over a word whose bit j is d_j; check e covers the bits of its equation and its parity bit.
@@ -143,7 +94,7 @@ __host__ __device__ constexpr unsigned dm_check(int code, int e)
 __host__ __device__ constexpr unsigned dm_syndrome(int code, unsigned word)
 {
     unsigned syn = 0;
-    for (int e = 0; e < dm_checks(code); ++e) syn |= dm_parity(word & dm_check(code, e)) << e;
+    for (int e = 0; e < dm_checks(code); ++e) syn |= pl_parity(word & dm_check(code, e)) << e;
     return syn;
 }
 
@@ -165,16 +116,13 @@ static_assert(dm_named(DM_H7) == 7 && dm_named(DM_H15) == 15, "every nonzero syn
 static_assert(dm_named(DM_H13) == 13 && dm_position(DM_H13, 0x9u) < 0 && dm_position(DM_H13, 0xBu) < 0,
               "a column's syndromes name 13 bits; (1,0,0,1) and (1,1,0,1) name none");
 
-// bit b of a record of nine words, the first sent bit the MSB of word 0
-__device__ inline unsigned dm_bit(const unsigned *w, int b) { return (w[b >> 5] >> (31 - (b & 31))) & 1u; }
-
 __global__ __launch_bounds__(DM_WAVE) void k_dmr_slice(const int *__restrict__ plane, long long n, const long long *__restrict__ hits,
                                                        DmrOffsets off, unsigned *__restrict__ bits_out, long long *__restrict__ levels_out)
 {
     __shared__ unsigned char s_two[DM_OFFSETS];
     const int lane = threadIdx.x;
     const long long id = blockIdx.x;
-    const long long m = hits[3 * id], s = hits[3 * id + 1] < 0 ? -1 : 1;
+    const PlHit hit = pl_hit(hits + 3 * id);
     const int kind = static_cast<int>(hits[3 * id + 2]) & 3;
     const bool bs = kind < 2;
     // the gather: every instant is checked against [0, n) before it is read
@@ -183,9 +131,8 @@ __global__ __launch_bounds__(DM_WAVE) void k_dmr_slice(const int *__restrict__ p
     for (int p = 0; p < 3; ++p) {
         const int idx = p * DM_WAVE + lane;
         if (idx >= DM_OFFSETS) break;
-        const long long at = m + off.o[idx];
-        const bool inside = at >= 0 && at < n;
-        if (inside) y[p] = plane[at];
+        bool inside;
+        y[p] = pl_read(plane, n, hit.m + off.o[idx], inside);
         if (idx < DM_CACH)
             cach_in = cach_in && inside;
         else
@@ -197,27 +144,19 @@ __global__ __launch_bounds__(DM_WAVE) void k_dmr_slice(const int *__restrict__ p
     const bool sync = i >= 0 && i < 24;
     long long sigma = sync ? y[1] : 0;
     long long amp = 0;
-    if (sync) amp = dm_positive(bs ? DM_BS_VOICE : DM_MS_VOICE, i) ? y[1] : -static_cast<long long>(y[1]);
-    for (int w = DM_WAVE / 2; w >= 1; w >>= 1) {
-        sigma += __shfl_xor(sigma, w, DM_WAVE);
-        amp += __shfl_xor(amp, w, DM_WAVE);
-    }
-    amp *= s;
+    if (sync) amp = pl_sync_positive(bs ? DM_BS_VOICE : DM_MS_VOICE, i) ? y[1] : -static_cast<long long>(y[1]);
+    sigma = wave_sum(sigma);
+    amp = hit.s * wave_sum(amp);
     if (!burst_ok) sigma = amp = 0;
     for (int p = 0; p < 3; ++p) {
         const int idx = p * DM_WAVE + lane;
         if (idx >= DM_OFFSETS) break;
-        const long long d = 24LL * y[p] - sigma, mag = d < 0 ? -d : d;
-        unsigned two = (d < 0 ? 2u : 0u) | (3 * mag >= 2 * amp ? 1u : 0u);
+        unsigned two = pl_dibit(24LL * y[p] - sigma, amp);
         if (!burst_ok || (idx < DM_CACH && !cach_ok)) two = 0;
         s_two[idx] = static_cast<unsigned char>(two);
     }
     __syncthreads();
-    if (lane < DM_WORDS) {
-        unsigned word = 0;
-        for (int k = 0; k < 16; ++k) word |= static_cast<unsigned>(s_two[16 * lane + k]) << (30 - 2 * k);
-        bits_out[DM_WORDS * id + lane] = word;
-    }
+    if (lane < DM_WORDS) bits_out[DM_WORDS * id + lane] = pl_pack_dibits(s_two, lane);
     if (lane == 0) {
         long long *e = levels_out + 3 * id;
         e[0] = sigma;
@@ -243,14 +182,14 @@ __global__ __launch_bounds__(DM_THREADS) void k_dmr_decode(const unsigned *__res
     if (tid < DM_WORDS) s_w[tid] = bits[DM_WORDS * id + tid];
     __syncthreads();
     const unsigned *cach = s_w;
-    auto burst = [&](int b) { return dm_bit(s_w, 24 + b); };
+    auto burst = [&](int b) { return pl_bit(s_w, 24 + b); };
 
     // the TACT: every thread reads the same seven bits
     int tact_status = 4, tact = 0;
     if (bs) {
         constexpr int at[7] = {0, 4, 8, 12, 14, 18, 22};
         unsigned word = 0;
-        for (int j = 0; j < 7; ++j) word |= dm_bit(cach, at[j]) << j;
+        for (int j = 0; j < 7; ++j) word |= pl_bit(cach, at[j]) << j;
         const unsigned syn = dm_syndrome(DM_H7, word);
         tact_status = syn ? 1 : 0;
         if (syn) word ^= 1u << dm_position(DM_H7, syn);
@@ -262,15 +201,11 @@ __global__ __launch_bounds__(DM_THREADS) void k_dmr_decode(const unsigned *__res
     if (data) {
         unsigned word = 0;
         for (int j = 0; j < 10; ++j) word |= burst(98 + j) << (19 - j) | burst(156 + j) << (9 - j);
-        s_key[tid] = (dm_popcount(word ^ DM_GOLAY.cw[tid]) << 8) | static_cast<unsigned>(tid);
-        __syncthreads();
-        for (int w = DM_THREADS / 2; w >= 1; w >>= 1) {
-            if (tid < w && s_key[tid + w] < s_key[tid]) s_key[tid] = s_key[tid + w];
-            __syncthreads();
-        }
-        st_distance = static_cast<int>(s_key[0] >> 8);
+        s_key[tid] = (pl_popcount(word ^ DM_GOLAY.cw[tid]) << 8) | static_cast<unsigned>(tid);
+        const unsigned key = pl_block_min(s_key, tid, DM_THREADS);
+        st_distance = static_cast<int>(key >> 8);
         st_status = st_distance == 0 ? 0 : st_distance <= 3 ? 1 : 2;
-        st_byte = st_status == 2 ? static_cast<int>(word >> 12) : static_cast<int>(s_key[0] & 0xFFu);
+        st_byte = st_status == 2 ? static_cast<int>(word >> 12) : static_cast<int>(key & 0xFFu);
     }
 
     // the payload
@@ -353,23 +288,12 @@ __global__ __launch_bounds__(DM_THREADS) void k_dmr_decode(const unsigned *__res
 
 using namespace iqa;
 
-constexpr int64_t DM_MAX_N = 1LL << 30;  // samples of one stored stream, as section 25's
-constexpr int64_t DM_MAX_K = 1LL << 20;  // bursts of one call: a workgroup each
-
 extern "C" int iqa_dmr_slice(const void *plane_dev, int64_t n, const void *hits_dev, int64_t K, const int32_t offsets[IQA_DMR_OFFSETS],
                              void *bits_dev, void *levels_dev, void *stream)
 {
-    if (n < 0 || K < 0) return fail_inval("negative length");
-    if (n > DM_MAX_N) return fail_inval("n must not exceed 2^30");
-    if (K > DM_MAX_K) return fail_inval("K must not exceed 2^20");
-    if (!offsets) return fail_inval("NULL offsets");
     DmrOffsets off;
-    if (offsets[DM_LEAD] != 0) return fail_inval("offsets[66] (o[0]) must be 0");
-    for (int i = 0; i < DM_OFFSETS; ++i) {
-        if (i && offsets[i] <= offsets[i - 1]) return fail_inval("offsets must ascend");
-        if (i && offsets[i] - offsets[i - 1] > IQA_IDENT_MAX_SPS + 1) return fail_inval("offsets must not step by more than IQA_IDENT_MAX_SPS + 1");
-        off.o[i] = offsets[i];
-    }
+    if (const int rc = pl_check_lengths(n, K)) return rc;
+    if (const int rc = pl_copy_offsets(offsets, DM_OFFSETS, DM_LEAD, "offsets", off.o)) return rc;
     if (n == 0 || K == 0) return IQA_OK;  // (nothing to read: no pointer is touched)
     if (!plane_dev || !hits_dev || !bits_dev || !levels_dev) return fail_inval("NULL device pointer");
     hipLaunchKernelGGL(k_dmr_slice, dim3(static_cast<unsigned>(K)), dim3(DM_WAVE), 0, as_stream(stream), static_cast<const int *>(plane_dev),
@@ -380,8 +304,7 @@ extern "C" int iqa_dmr_slice(const void *plane_dev, int64_t n, const void *hits_
 
 extern "C" int iqa_dmr_decode(const void *bits_dev, const void *kinds_dev, int64_t K, void *info_dev, void *rec_dev, void *stream)
 {
-    if (K < 0) return fail_inval("negative length");
-    if (K > DM_MAX_K) return fail_inval("K must not exceed 2^20");
+    if (const int rc = pl_check_lengths(0, K)) return rc;
     if (K == 0) return IQA_OK;  // (nothing to read: no pointer is touched)
     if (!bits_dev || !kinds_dev || !info_dev || !rec_dev) return fail_inval("NULL device pointer");
     hipLaunchKernelGGL(k_dmr_decode, dim3(static_cast<unsigned>(K)), dim3(DM_THREADS), 0, as_stream(stream),

@@ -201,13 +201,6 @@ struct FindActArgs {
     int nbins, T, S, thr_act;
 };
 
-__device__ __forceinline__ long long fd_wave_sum(long long v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, kWave);
-    return v;
-}
-
 __global__ __launch_bounds__(FD_THREADS) void k_find_activity(FindActArgs g)
 {
     const int lane = threadIdx.x % kWave;
@@ -224,7 +217,7 @@ __global__ __launch_bounds__(FD_THREADS) void k_find_activity(FindActArgs g)
     const int *row = g.slice + static_cast<long long>(s) * g.nbins;
     long long total = 0;
     for (long long k = lo + lane; k <= hi; k += kWave) total += row[k] - Ts * g.fmean[k];
-    total = fd_wave_sum(total);
+    total = wave_sum(total);
     if (lane == 0) g.on[job] = total >= Ts * (hi - lo + 1) * g.thr_act ? 1 : 0;
 }
 

@@ -18,8 +18,9 @@
 //
 // k_flex_words is a workgroup per (frame, shift, block): 256 threads gather the block's 256 u plane values (one strided read
 // each, u = 1 or 2), slice them to a byte of four phase bits and two validity bits in LDS; 32 threads (8 words x 4 phases)
-// then assemble and check their words from LDS.  Plain C++ stores, no inline assembly, no atomics.
-#include "common.h"
+// then assemble and check their words from LDS.  The hit's head, the checked read, the parity and the host prologue are
+// protocol.h's; the bit convention is FLEX's own.  Plain C++ stores, no inline assembly, no atomics.
+#include "protocol.h"
 
 namespace iqa {
 
@@ -34,10 +35,9 @@ constexpr int FX_WORDS = IQA_FLEX_WORDS;          // 88 words of a phase
 constexpr int FX_SYMBOLS = IQA_FLEX_SYMBOLS;      // 2816 data symbols of a frame at u = 1
 constexpr unsigned FX_POLY = 0x769u;              // x^10 + x^9 + x^8 + x^6 + x^5 + x^3 + 1
 constexpr unsigned FX_MARKER = 0xA6C6AAAAu;
-constexpr long long FX_V_MAX = 64LL * 65534;      // |plane|
 
 static_assert(FX_THREADS * 11 == FX_SYMBOLS && FX_BLOCKS * 8 == FX_WORDS, "eleven blocks of 256 bits, eight words each");
-static_assert(32 * FX_V_MAX * 33 < (1LL << 40), "32 y - Sigma and 3 |dd| stay far inside int64");
+static_assert(32 * PL_V_MAX * 33 < (1LL << 40), "32 y - Sigma and 3 |dd| stay far inside int64");
 
 struct FlexHeader {
     int o[FX_HEAD];
@@ -61,16 +61,6 @@ __host__ __device__ constexpr unsigned fx_syndrome(unsigned cw)
     return r & 0x3FFu;
 }
 
-__host__ __device__ constexpr unsigned fx_parity(unsigned x)
-{
-    x ^= x >> 16;
-    x ^= x >> 8;
-    x ^= x >> 4;
-    x ^= x >> 2;
-    x ^= x >> 1;
-    return x & 1u;
-}
-
 constexpr bool fx_singles_distinct()
 {
     for (int a = 1; a < 32; ++a)
@@ -82,14 +72,14 @@ constexpr bool fx_singles_distinct()
 }
 
 // 0x1BA84B3E is 0x7CD215D8 (section 12's sync word, a codeword of g) with its first sent bit as bit 0
-static_assert(fx_rev32(0x1BA84B3Eu) == 0x7CD215D8u && fx_syndrome(fx_rev32(0x1BA84B3Eu)) == 0 && fx_parity(0x1BA84B3Eu) == 0,
+static_assert(fx_rev32(0x1BA84B3Eu) == 0x7CD215D8u && fx_syndrome(fx_rev32(0x1BA84B3Eu)) == 0 && pl_parity(0x1BA84B3Eu) == 0,
               "rev32 of a known codeword has a zero syndrome and even parity");
 static_assert(fx_singles_distinct(), "the 31 single-bit syndromes are distinct and not zero");
 
 // section 12's rule on a word whose first sent bit is bit 0: the fixed word; status 0, 1 or 2
 __host__ __device__ constexpr unsigned fx_correct(unsigned raw, unsigned char &status)
 {
-    const unsigned cw = fx_rev32(raw), syn = fx_syndrome(cw), odd = fx_parity(cw);
+    const unsigned cw = fx_rev32(raw), syn = fx_syndrome(cw), odd = pl_parity(cw);
     status = 2;
     if (syn == 0) {
         status = odd ? 1 : 0;
@@ -110,15 +100,15 @@ __global__ __launch_bounds__(FX_FRAME_THREADS) void k_flex_frames(const int *__r
 {
     const long long id = static_cast<long long>(blockIdx.x) * FX_FRAME_THREADS + threadIdx.x;
     if (id >= K) return;
-    const long long m = hits[2 * id], s = hits[2 * id + 1] < 0 ? -1 : 1;
+    const PlHit hit = pl_hit(hits + 2 * id);
     long long sigma = 0, amp = 0, valid = 1;
     for (int i = 0; i < 32; ++i) {
-        const long long at = m + hd.o[FX_LEAD + i];
-        if (at < 0 || at >= n) {
+        bool inside;
+        const long long x = hit.s * pl_read(plane, n, hit.m + hd.o[FX_LEAD + i], inside);
+        if (!inside) {
             valid = 0;
             break;
         }
-        const long long x = s * plane[at];
         sigma += x;
         amp += ((FX_MARKER >> (31 - i)) & 1u) ? x : -x;
     }
@@ -128,14 +118,8 @@ __global__ __launch_bounds__(FX_FRAME_THREADS) void k_flex_frames(const int *__r
         sigma = amp = 0;
     } else {
         bool inside = true;
-        for (int j = 0; j < 32; ++j) {
-            const long long at = m + hd.o[FX_LEAD + 64 + j];
-            if (at < 0 || at >= n) {
-                inside = false;
-                break;
-            }
-            if (32 * s * plane[at] - sigma > 0) raw |= 1u << j;
-        }
+        for (int j = 0; j < 32 && inside; ++j)
+            if (32 * hit.s * pl_read(plane, n, hit.m + hd.o[FX_LEAD + 64 + j], inside) - sigma > 0) raw |= 1u << j;
         if (inside)
             fixed = fx_correct(raw, status);
         else
@@ -160,17 +144,18 @@ __global__ __launch_bounds__(FX_THREADS) void k_flex_words(const int *__restrict
     const int tid = threadIdx.x;
     const int b = blockIdx.x % FX_BLOCKS, e = (blockIdx.x / FX_BLOCKS) % FX_SHIFTS;
     const long long f = blockIdx.x / (FX_BLOCKS * FX_SHIFTS);
-    const long long m = frames[4 * f], s = frames[4 * f + 1] < 0 ? -1 : 1, sigma = frames[4 * f + 2], amp = frames[4 * f + 3];
+    const PlHit hit = pl_hit(frames + 4 * f);
+    const long long sigma = frames[4 * f + 2], amp = frames[4 * f + 3];
     const long long d = static_cast<long long>(e - 2) * step;
     unsigned bits = 0;
     for (int pair = 0; pair < u; ++pair) {
         const int q = b * FX_THREADS * u + tid * u + pair;  // (< 2816 u: inside offs)
-        const long long at = m + offs[q] + d;
-        if (at < 0 || at >= n) {
+        bool inside;
+        const long long dd = 32 * hit.s * pl_read(plane, n, hit.m + offs[q] + d, inside) - sigma;
+        if (!inside) {
             bits |= 16u << pair;
             continue;
         }
-        const long long dd = 32 * s * plane[at] - sigma;
         if (dd > 0) bits |= 1u << (2 * pair);
         if (levels == 4 && 3 * (dd < 0 ? -dd : dd) < 2 * amp) bits |= 2u << (2 * pair);
     }
@@ -205,23 +190,14 @@ __global__ __launch_bounds__(FX_THREADS) void k_flex_words(const int *__restrict
 
 using namespace iqa;
 
-constexpr int64_t FX_MAX_N = 1LL << 30;       // samples of one stored stream, as section 25's
-constexpr int64_t FX_MAX_FRAMES = 1LL << 20;  // frames of one call: 55 workgroups each stay inside the grid's 2^31
+static_assert(PL_MAX_K * FX_SHIFTS * FX_BLOCKS < (1LL << 31), "55 workgroups to a frame stay inside the grid");
 
 extern "C" int iqa_flex_frames(const void *plane_dev, int64_t n, const void *hits_dev, int64_t K,
                                const int32_t offsets16[IQA_FLEX_HEADER_OFFSETS], void *out_dev, void *stream)
 {
-    if (n < 0 || K < 0) return fail_inval("negative length");
-    if (n > FX_MAX_N) return fail_inval("n must not exceed 2^30");
-    if (K > FX_MAX_FRAMES) return fail_inval("K must not exceed 2^20");
-    if (!offsets16) return fail_inval("NULL offsets");
     FlexHeader hd;
-    if (offsets16[FX_LEAD] != 0) return fail_inval("offsets16[16] (o[0]) must be 0");
-    for (int i = 0; i < FX_HEAD; ++i) {
-        if (i && offsets16[i] <= offsets16[i - 1]) return fail_inval("offsets16 must ascend");
-        if (i && offsets16[i] - offsets16[i - 1] > IQA_IDENT_MAX_SPS + 1) return fail_inval("offsets16 must not step by more than IQA_IDENT_MAX_SPS + 1");
-        hd.o[i] = offsets16[i];
-    }
+    if (const int rc = pl_check_lengths(n, K)) return rc;
+    if (const int rc = pl_copy_offsets(offsets16, FX_HEAD, FX_LEAD, "offsets16", hd.o)) return rc;
     if (n == 0 || K == 0) return IQA_OK;  // (nothing to read: no pointer is touched)
     if (!plane_dev || !hits_dev || !out_dev) return fail_inval("NULL device pointer");
     hipLaunchKernelGGL(k_flex_frames, grid1d(K, FX_FRAME_THREADS), dim3(FX_FRAME_THREADS), 0, as_stream(stream),
@@ -233,9 +209,7 @@ extern "C" int iqa_flex_frames(const void *plane_dev, int64_t n, const void *hit
 extern "C" int iqa_flex_words(const void *plane_dev, int64_t n, const void *frames_dev, int64_t F, int32_t levels, int32_t u,
                               int32_t step, const void *offsets_dev, void *fixed_dev, void *raw_dev, void *status_dev, void *stream)
 {
-    if (n < 0 || F < 0) return fail_inval("negative length");
-    if (n > FX_MAX_N) return fail_inval("n must not exceed 2^30");
-    if (F > FX_MAX_FRAMES) return fail_inval("F must not exceed 2^20");
+    if (const int rc = pl_check_lengths(n, F, 'F')) return rc;
     if (levels != 2 && levels != 4) return fail_inval("levels must be 2 or 4");
     if (u != 1 && u != 2) return fail_inval("u must be 1 or 2");
     if (step < 1 || step > IQA_FLEX_MAX_STEP) return fail_inval("step must be 1 .. IQA_FLEX_MAX_STEP");

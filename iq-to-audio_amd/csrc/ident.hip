@@ -18,7 +18,9 @@
 // a thread makes one full window sum and seven slides.  k_ident_score: a workgroup stages 1024 positions and the longest
 // span of v into LDS, the offsets and the symbols beside them; for a fixed symbol consecutive lanes read consecutive words.
 // k_ident_keep: one thread per position and pattern on the few candidates, reading global memory directly, appending through
-// one atomic counter as k_pocsag_keep does.  Integers only behind the quantiser; plain C++ stores, no inline assembly.
+// one atomic counter as k_pocsag_keep does, pre and post through protocol.h's checked read; the host prologue is protocol.h's
+// too.  Integers only behind the quantiser; plain C++ stores, no inline assembly.
+#include "protocol.h"
 #include "sideband.h"
 
 namespace iqa {
@@ -33,7 +35,7 @@ constexpr int ID_OFFS = IQA_IDENT_OFFSETS;                        // 64: o[-16] 
 constexpr int ID_LEAD = 16;                                       // o[i] sits at index 16 + i
 constexpr int ID_SYMS = IQA_IDENT_MAX_SYMBOLS;                    // 32
 constexpr int ID_PATS = IQA_IDENT_MAX_PATTERNS;                   // 8
-constexpr long long ID_V_MAX = 64LL * 65534;                      // |v|
+constexpr long long ID_V_MAX = PL_V_MAX;                          // |v|
 constexpr int ID_RECORD = IQA_IDENT_RECORD;                       // 6 int64 of a kept hit
 
 // every product of the candidate test stays inside int64
@@ -151,10 +153,11 @@ __global__ __launch_bounds__(ID_THREADS) void k_ident_keep(const int *__restrict
     long long E;
     id_eval([&](int off) { return v[a + off]; }, s_sym, s_o + ID_LEAD, N, C, E);  // (a candidate: a + o[N - 1] < n)
     unsigned pre = 0, post = 0;
+#pragma unroll 1  // (unrolled, the 32 reads of a kept hit are issued at once and take 74 registers, not 23)
     for (int k = 0; k < 16; ++k) {
-        const long long before = a + s_o[k], behind = a + s_o[ID_LEAD + N + k];
-        if (before >= 0 && before < n && v[before] > 0) pre |= 1u << k;
-        if (behind >= 0 && behind < n && v[behind] > 0) post |= 1u << k;
+        bool inside;  // (an instant outside the stream reads as 0: its bit stays clear)
+        if (pl_read(v, n, a + s_o[k], inside) > 0) pre |= 1u << k;
+        if (pl_read(v, n, a + s_o[ID_LEAD + N + k], inside) > 0) post |= 1u << k;
     }
     const unsigned long long at = atomicAdd(count, 1ULL);
     if (at < static_cast<unsigned long long>(capacity)) {
@@ -172,12 +175,9 @@ __global__ __launch_bounds__(ID_THREADS) void k_ident_keep(const int *__restrict
 
 using namespace iqa;
 
-constexpr int64_t ID_MAX_N = 1LL << 30;  // samples of one stored stream: positions and npat * n stay far inside int64 / 2^31 rows
-
 extern "C" int iqa_ident_integrate(const void *theta_dev, int64_t n, int32_t L, int32_t sh, int32_t c, void *v_dev, void *stream)
 {
-    if (n < 0) return fail_inval("negative length");
-    if (n > ID_MAX_N) return fail_inval("n must not exceed 2^30");
+    if (const int rc = pl_check_lengths(n, 0)) return rc;
     if (L < IQA_IDENT_MIN_SPS || L > IQA_IDENT_MAX_SPS) return fail_inval("L must be IQA_IDENT_MIN_SPS .. IQA_IDENT_MAX_SPS");
     if (sh < 0 || sh > 8 || ((static_cast<long long>(L) * 65534) >> sh) > ID_V_MAX) return fail_inval("sh must be 0 .. 8 and keep |v| within 64 * 65534");
     if (c < -ID_T_MAX || c > ID_T_MAX) return fail_inval("the centre must be -32767 .. 32767");
@@ -192,18 +192,13 @@ extern "C" int iqa_ident_search(const void *v_dev, int64_t n, const int32_t offs
                                 const int8_t *symbols, const int32_t *nsym, int32_t half, void *score_dev, void *list_dev,
                                 int64_t capacity, void *count_dev, void *stream)
 {
-    if (n < 0 || capacity < 0) return fail_inval("negative length");
-    if (n > ID_MAX_N) return fail_inval("n must not exceed 2^30");
+    if (capacity < 0) return fail_inval("negative length");
+    if (const int rc = pl_check_lengths(n, 0)) return rc;
     if (!offsets || !symbols || !nsym) return fail_inval("NULL offsets, symbols or symbol counts");
     if (npat < 1 || npat > ID_PATS) return fail_inval("npat must be 1 .. IQA_IDENT_MAX_PATTERNS");
     if (half < 0 || half > IQA_IDENT_MAX_SPS) return fail_inval("half must be 0 .. IQA_IDENT_MAX_SPS");
     IdentTable tb;
-    if (offsets[ID_LEAD] != 0) return fail_inval("offsets[16] (o[0]) must be 0");
-    for (int i = 0; i < ID_OFFS; ++i) {
-        if (i && offsets[i] <= offsets[i - 1]) return fail_inval("offsets must ascend");
-        if (i && offsets[i] - offsets[i - 1] > IQA_IDENT_MAX_SPS + 1) return fail_inval("offsets must not step by more than IQA_IDENT_MAX_SPS + 1");
-        tb.o[i] = offsets[i];
-    }
+    if (const int rc = pl_copy_offsets(offsets, ID_OFFS, ID_LEAD, "offsets", tb.o)) return rc;
     int span = 0;
     tb.npat = npat;
     for (int p = 0; p < ID_PATS; ++p) {

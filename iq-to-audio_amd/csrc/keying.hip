@@ -40,13 +40,6 @@ struct KeyingArgs {
     unsigned inc[KY_BAUDS];
 };
 
-__device__ __forceinline__ int ky_wave_sum(int v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, kWave);
-    return v;
-}
-
 __global__ __launch_bounds__(SB_THREADS) void k_keying(KeyingArgs g)
 {
     __shared__ int s_t[KY_IMAGE];
@@ -118,7 +111,7 @@ __global__ __launch_bounds__(SB_THREADS) void k_keying(KeyingArgs g)
         }
     }
 #pragma unroll
-    for (int k = 0; k < KY_SUMS; ++k) sum[k] = ky_wave_sum(sum[k]);
+    for (int k = 0; k < KY_SUMS; ++k) sum[k] = wave_sum(sum[k]);
     if (tid % kWave == 0) {
 #pragma unroll
         for (int k = 0; k < KY_SUMS; ++k) s_part[tid / kWave][k] = sum[k];

@@ -33,8 +33,9 @@
 // before it is read; P, Q and valid are wave reductions; 54 lanes pack the words from LDS.  k_p25_nid and k_p25_decode are a
 // workgroup of 256 per frame: 256 codewords of the BCH code to a thread (T_hi[t] ^ T_lo[j]: the code is linear), 16 of the Golay
 // code, with a minimum over (distance, data) through LDS; a thread per Hamming word; a thread per trellis block with its
-// survivors in LDS.  Plain C++ stores, no inline assembly, no atomics, no mutable statics.
-#include "common.h"
+// survivors in LDS.  The sync word's signs, the Golay encoder, the minimum, the dibit rule, the packing and the host prologue are
+// protocol.h's.  Plain C++ stores, no inline assembly, no atomics, no mutable statics.
+#include "protocol.h"
 
 namespace iqa {
 
@@ -47,29 +48,15 @@ constexpr int P5_INFO = IQA_P25_INFO;        // 9
 constexpr int P5_REC = IQA_P25_RECORD;       // 8
 constexpr int P5_SYNC_SYMBOLS = 24;
 constexpr unsigned long long P5_SYNC = 0x5575F5FF77FFull;
-constexpr unsigned P5_GOLAY_POLY = 0xC75u;
-constexpr long long P5_V_MAX = 64LL * 65534;  // |plane|
 
 static_assert(2 * P5_OFFSETS == 32 * P5_WORDS && P5_ROUNDS == 14, "864 symbols: fourteen rounds of a wave, 54 words");
-static_assert(286 * P5_V_MAX * 2 * 24 * 3 < (1LL << 50), "286 y - Dc and 3 |d| stay far inside int64");
+static_assert(286 * PL_V_MAX * 2 * 24 * 3 < (1LL << 50), "286 y - Dc and 3 |d| stay far inside int64");
 
 struct P25Offsets {
     int o[P5_OFFSETS];
 };
 
-// whether sync symbol i (0 .. 23) is a positive level: the dibit 01 (+3) has a clear first bit
-__host__ __device__ constexpr bool p5_positive(int i) { return ((P5_SYNC >> (2 * (23 - i) + 1)) & 1ull) == 0; }
-
-constexpr int p5_ups()
-{
-    int up = 0;
-    for (int i = 0; i < P5_SYNC_SYMBOLS; ++i) {
-        if (((P5_SYNC >> (2 * (23 - i))) & 1ull) == 0) return -1;  // only the outer levels: 01 and 11
-        up += p5_positive(i) ? 1 : 0;
-    }
-    return up;
-}
-static_assert(p5_ups() == 11, "the sync word holds eleven +3 and thirteen -3: 12 Q + P = 286 s L and 12 P + Q = 286 DC");
+static_assert(pl_sync_ups(P5_SYNC) == 11, "the sync word holds eleven +3 and thirteen -3: 12 Q + P = 286 s L and 12 P + Q = 286 DC");
 
 // ---- BCH(63,16,23) over GF(64) / x^6 + x + 1 ------------------------------------------------------------------------------------
 
@@ -157,48 +144,23 @@ __device__ const P5Bch P5_BCH = p5_bch_tables();
 
 // ---- Golay(24,12,8) ---------------------------------------------------------------------------------------------------------------
 
-__host__ __device__ constexpr unsigned p5_popcount(unsigned x)
-{
-    unsigned c = 0;
-    for (; x; x &= x - 1) ++c;
-    return c;
-}
-
-constexpr unsigned p5_golay(unsigned data)
-{
-    unsigned r = data << 11;
-    for (int i = 22; i >= 11; --i)
-        if ((r >> i) & 1u) r ^= P5_GOLAY_POLY << (i - 11);
-    const unsigned cw = (data << 12) | ((r & 0x7FFu) << 1);
-    return cw | (p5_popcount(cw) & 1u);
-}
-
+// the codeword of the 12-bit value d is hi[d >> 4] ^ lo[d & 15]
 struct P5Golay {
     unsigned hi[256], lo[16];
+    constexpr unsigned word(unsigned d) const { return hi[d >> 4] ^ lo[d & 15u]; }
 };
 
 constexpr P5Golay p5_golay_tables()
 {
     P5Golay t{};
-    for (unsigned d = 0; d < 256; ++d) t.hi[d] = p5_golay(d << 4);
-    for (unsigned d = 0; d < 16; ++d) t.lo[d] = p5_golay(d);
+    for (unsigned d = 0; d < 256; ++d) t.hi[d] = pl_golay(d << 4, 12);
+    for (unsigned d = 0; d < 16; ++d) t.lo[d] = pl_golay(d, 12);
     return t;
 }
 
-// the smallest weight of a nonzero codeword: the code is linear, so this is the smallest distance between two of the 4096 words
-constexpr unsigned p5_golay_distance(const P5Golay &t)
-{
-    unsigned best = 24;
-    for (unsigned d = 1; d < 4096; ++d) {
-        const unsigned w = p5_popcount(t.hi[d >> 4] ^ t.lo[d & 15u]);
-        if (w < best) best = w;
-    }
-    return best;
-}
-
 constexpr P5Golay P5_GOLAY_HOST = p5_golay_tables();
-static_assert((P5_GOLAY_HOST.hi[0xAB] ^ P5_GOLAY_HOST.lo[0xC]) == p5_golay(0xABC), "the code is linear: a codeword is G_hi ^ G_lo");
-static_assert(p5_golay_distance(P5_GOLAY_HOST) == 8, "the 4096 codewords lie 8 apart at the least: a word within 3 of one is within 3 of no other");
+static_assert((P5_GOLAY_HOST.hi[0xAB] ^ P5_GOLAY_HOST.lo[0xC]) == pl_golay(0xABC, 12), "the code is linear: a codeword is G_hi ^ G_lo");
+static_assert(pl_golay_distance(P5_GOLAY_HOST, 4096) == 8, "the 4096 codewords lie 8 apart at the least: a word within 3 of one is within 3 of no other");
 __device__ const P5Golay P5_GOLAY = p5_golay_tables();
 
 // ---- Hamming(10,6,3) --------------------------------------------------------------------------------------------------------------
@@ -265,13 +227,11 @@ constexpr int P5_FAR = 1000;  // the metric of a state that cannot be reached ye
 
 // ---- the bits of a frame ------------------------------------------------------------------------------------------------------------
 
-// frame bit b of a record of 54 words, the first sent bit the MSB of word 0
-__device__ inline unsigned p5_bit(const unsigned *w, int b) { return (w[b >> 5] >> (31 - (b & 31))) & 1u; }
-// data bit b: the status symbols skipped
+// data bit b of a frame's record: the status symbols skipped
 __device__ inline unsigned p5_data_bit(const unsigned *w, int b)
 {
     const int q = b >> 1;
-    return p5_bit(w, 2 * (q + q / 35) + (b & 1));
+    return pl_bit(w, 2 * (q + q / 35) + (b & 1));
 }
 static_assert(2 * (679 + 679 / 35) + 1 < 32 * P5_WORDS, "data bit 1359, the last that a decoder reads, lies inside the record");
 
@@ -281,8 +241,8 @@ __global__ __launch_bounds__(P5_WAVE) void k_p25_slice(const int *__restrict__ p
     __shared__ unsigned char s_two[P5_ROUNDS * P5_WAVE];
     const int lane = threadIdx.x;
     const long long id = blockIdx.x;
-    const long long m = hits[2 * id], s = hits[2 * id + 1] < 0 ? -1 : 1;
-    const bool front = m >= 0;  // o[0] = 0 and o ascends: no instant lies in front of the plane
+    const PlHit hit = pl_hit(hits + 2 * id);
+    const long long reach = hit.m >= 0 ? n : 0;  // o[0] = 0 and o ascends: a hit in front of the plane reads nothing, one inside it a prefix
     // the gather: every instant is checked against [0, n) before it is read
     int y[P5_ROUNDS];
     int count = 0;
@@ -291,58 +251,34 @@ __global__ __launch_bounds__(P5_WAVE) void k_p25_slice(const int *__restrict__ p
         const int idx = p * P5_WAVE + lane;
         y[p] = 0;
         if (idx < P5_OFFSETS) {
-            const long long at = m + off.o[idx];
-            const bool inside = front && at >= 0 && at < n;
-            if (inside) {
-                y[p] = plane[at];
-                ++count;
-            }
+            bool inside;
+            y[p] = pl_read(plane, reach, hit.m + off.o[idx], inside);
+            count += inside ? 1 : 0;
         }
     }
     long long sum = lane < P5_SYNC_SYMBOLS ? y[0] : 0;
     long long signed_sum = 0;
-    if (lane < P5_SYNC_SYMBOLS) signed_sum = p5_positive(lane) ? y[0] : -static_cast<long long>(y[0]);
-    for (int w = P5_WAVE / 2; w >= 1; w >>= 1) {
-        sum += __shfl_xor(sum, w, P5_WAVE);
-        signed_sum += __shfl_xor(signed_sum, w, P5_WAVE);
-        count += __shfl_xor(count, w, P5_WAVE);
-    }
-    const int valid = count;
+    if (lane < P5_SYNC_SYMBOLS) signed_sum = pl_sync_positive(P5_SYNC, lane) ? y[0] : -static_cast<long long>(y[0]);
+    sum = wave_sum(sum);
+    signed_sum = wave_sum(signed_sum);
+    const int valid = wave_sum(count);
     const bool read = valid >= P5_SYNC_SYMBOLS;
-    const long long amp = read ? s * (12 * signed_sum + sum) : 0, dc = read ? 12 * sum + signed_sum : 0;
+    const long long amp = read ? hit.s * (12 * signed_sum + sum) : 0, dc = read ? 12 * sum + signed_sum : 0;
 #pragma unroll
     for (int p = 0; p < P5_ROUNDS; ++p) {
         const int idx = p * P5_WAVE + lane;
-        const long long d = s * (286LL * y[p] - dc), mag = d < 0 ? -d : d;
-        unsigned two = (d < 0 ? 2u : 0u) | (3 * mag >= 2 * amp ? 1u : 0u);
+        unsigned two = pl_dibit(hit.s * (286LL * y[p] - dc), amp);
         if (!read || idx >= valid) two = 0;
         s_two[idx] = static_cast<unsigned char>(two);
     }
     __syncthreads();
-    if (lane < P5_WORDS) {
-        unsigned word = 0;
-        for (int k = 0; k < 16; ++k) word |= static_cast<unsigned>(s_two[16 * lane + k]) << (30 - 2 * k);
-        bits_out[P5_WORDS * id + lane] = word;
-    }
+    if (lane < P5_WORDS) bits_out[P5_WORDS * id + lane] = pl_pack_dibits(s_two, lane);
     if (lane == 0) {
         long long *e = levels_out + 3 * id;
         e[0] = amp;
         e[1] = dc;
         e[2] = valid;
     }
-}
-
-// the minimum of s_key over the workgroup, left in s_key[0]; every thread has written its entry
-__device__ inline unsigned p5_block_min(unsigned *s_key, int tid)
-{
-    __syncthreads();
-    for (int w = P5_THREADS / 2; w >= 1; w >>= 1) {
-        if (tid < w && s_key[tid + w] < s_key[tid]) s_key[tid] = s_key[tid + w];
-        __syncthreads();
-    }
-    const unsigned key = s_key[0];
-    __syncthreads();  // (the next round overwrites s_key only behind every read of it)
-    return key;
 }
 
 __global__ __launch_bounds__(P5_THREADS) void k_p25_nid(const unsigned *__restrict__ bits, int *__restrict__ nid_out)
@@ -362,7 +298,7 @@ __global__ __launch_bounds__(P5_THREADS) void k_p25_nid(const unsigned *__restri
         best = key < best ? key : best;
     }
     s_key[tid] = best;
-    const unsigned key = p5_block_min(s_key, tid);
+    const unsigned key = pl_block_min(s_key, tid, P5_THREADS);
     if (tid == 0) {
         const int distance = static_cast<int>(key >> 16);
         const int status = distance == 0 ? 0 : distance <= 11 ? 1 : 2;
@@ -398,11 +334,11 @@ __global__ __launch_bounds__(P5_THREADS) void k_p25_decode(const unsigned *__res
             const unsigned mine = word ^ P5_GOLAY.hi[tid];
             unsigned best = 0xFFFFFFFFu;
             for (int j = 0; j < 16; ++j) {
-                const unsigned key = p5_popcount(mine ^ P5_GOLAY.lo[j]) << 12 | static_cast<unsigned>(tid) << 4 | static_cast<unsigned>(j);
+                const unsigned key = pl_popcount(mine ^ P5_GOLAY.lo[j]) << 12 | static_cast<unsigned>(tid) << 4 | static_cast<unsigned>(j);
                 best = key < best ? key : best;
             }
             s_key[tid] = best;
-            const unsigned key = p5_block_min(s_key, tid);
+            const unsigned key = pl_block_min(s_key, tid, P5_THREADS);
             const int distance = static_cast<int>(key >> 12);
             unsigned data = key & 0xFFFu;
             if (distance > 3) {
@@ -447,10 +383,10 @@ __global__ __launch_bounds__(P5_THREADS) void k_p25_decode(const unsigned *__res
                 unsigned surv = 0;
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
-                    int best = m0 + static_cast<int>(p5_popcount(rx ^ p5_branch(0, j))), arg = 0;
-                    const int c1 = m1 + static_cast<int>(p5_popcount(rx ^ p5_branch(1, j)));
-                    const int c2 = m2 + static_cast<int>(p5_popcount(rx ^ p5_branch(2, j)));
-                    const int c3 = m3 + static_cast<int>(p5_popcount(rx ^ p5_branch(3, j)));
+                    int best = m0 + static_cast<int>(pl_popcount(rx ^ p5_branch(0, j))), arg = 0;
+                    const int c1 = m1 + static_cast<int>(pl_popcount(rx ^ p5_branch(1, j)));
+                    const int c2 = m2 + static_cast<int>(pl_popcount(rx ^ p5_branch(2, j)));
+                    const int c3 = m3 + static_cast<int>(pl_popcount(rx ^ p5_branch(3, j)));
                     if (c1 < best) best = c1, arg = 1;
                     if (c2 < best) best = c2, arg = 2;
                     if (c3 < best) best = c3, arg = 3;
@@ -493,23 +429,12 @@ __global__ __launch_bounds__(P5_THREADS) void k_p25_decode(const unsigned *__res
 
 using namespace iqa;
 
-constexpr int64_t P5_MAX_N = 1LL << 30;  // samples of one stored stream, as section 25's
-constexpr int64_t P5_MAX_K = 1LL << 20;  // frames of one call: a workgroup each
-
 extern "C" int iqa_p25_slice(const void *plane_dev, int64_t n, const void *hits_dev, int64_t K, const int32_t offsets[IQA_P25_OFFSETS],
                              void *bits_dev, void *levels_dev, void *stream)
 {
-    if (n < 0 || K < 0) return fail_inval("negative length");
-    if (n > P5_MAX_N) return fail_inval("n must not exceed 2^30");
-    if (K > P5_MAX_K) return fail_inval("K must not exceed 2^20");
-    if (!offsets) return fail_inval("NULL offsets");
     P25Offsets off;
-    if (offsets[0] != 0) return fail_inval("offsets[0] (o[0]) must be 0");
-    for (int i = 0; i < P5_OFFSETS; ++i) {
-        if (i && offsets[i] <= offsets[i - 1]) return fail_inval("offsets must ascend");
-        if (i && offsets[i] - offsets[i - 1] > IQA_IDENT_MAX_SPS + 1) return fail_inval("offsets must not step by more than IQA_IDENT_MAX_SPS + 1");
-        off.o[i] = offsets[i];
-    }
+    if (const int rc = pl_check_lengths(n, K)) return rc;
+    if (const int rc = pl_copy_offsets(offsets, P5_OFFSETS, 0, "offsets", off.o)) return rc;
     if (n == 0 || K == 0) return IQA_OK;  // (nothing to read: no pointer is touched)
     if (!plane_dev || !hits_dev || !bits_dev || !levels_dev) return fail_inval("NULL device pointer");
     hipLaunchKernelGGL(k_p25_slice, dim3(static_cast<unsigned>(K)), dim3(P5_WAVE), 0, as_stream(stream), static_cast<const int *>(plane_dev),
@@ -520,8 +445,7 @@ extern "C" int iqa_p25_slice(const void *plane_dev, int64_t n, const void *hits_
 
 extern "C" int iqa_p25_nid(const void *bits_dev, int64_t K, void *nid_dev, void *stream)
 {
-    if (K < 0) return fail_inval("negative length");
-    if (K > P5_MAX_K) return fail_inval("K must not exceed 2^20");
+    if (const int rc = pl_check_lengths(0, K)) return rc;
     if (K == 0) return IQA_OK;  // (nothing to read: no pointer is touched)
     if (!bits_dev || !nid_dev) return fail_inval("NULL device pointer");
     hipLaunchKernelGGL(k_p25_nid, dim3(static_cast<unsigned>(K)), dim3(P5_THREADS), 0, as_stream(stream), static_cast<const unsigned *>(bits_dev),
@@ -531,8 +455,7 @@ extern "C" int iqa_p25_nid(const void *bits_dev, int64_t K, void *nid_dev, void 
 
 extern "C" int iqa_p25_decode(const void *bits_dev, const void *duids_dev, int64_t K, void *info_dev, void *rec_dev, void *stream)
 {
-    if (K < 0) return fail_inval("negative length");
-    if (K > P5_MAX_K) return fail_inval("K must not exceed 2^20");
+    if (const int rc = pl_check_lengths(0, K)) return rc;
     if (K == 0) return IQA_OK;  // (nothing to read: no pointer is touched)
     if (!bits_dev || !duids_dev || !info_dev || !rec_dev) return fail_inval("NULL device pointer");
     hipLaunchKernelGGL(k_p25_decode, dim3(static_cast<unsigned>(K)), dim3(P5_THREADS), 0, as_stream(stream),

@@ -12,17 +12,15 @@ no vocoder, no embedded or short link control.  No CPU path: without a GPU or th
 
 What is DMR's own lives here: the checks, the device calls, the burst parser, the call tracker, the dataclasses,
 ``decode_stream`` and ``channel_of``.  What every protocol layer shares lives in ``protocol_layer.py``: the stored stream under
-``DmrDecoder``, the per-lane loop under ``finish_dmr``, the builder under ``dmr_result``, and ``label`` / ``lines`` / ``to_json`` /
-``from_json`` of the results."""
+``DmrDecoder``, the device call on host rows under ``slice_bursts`` / ``decode_bursts``, the keep rule under ``burst_hits``, the
+per-lane loop under ``finish_dmr``, the builder under ``dmr_result``, and ``label`` / ``lines`` / ``to_json`` / ``from_json``."""
 from __future__ import annotations
 
-from ctypes import c_int32, c_int64
+from ctypes import c_int64
 from dataclasses import dataclass, field
 
 import numpy as np
 
-from . import _dev as D
-from . import _native as N
 from . import dsp_plan as P
 from . import identify as I
 from . import protocol_layer as L
@@ -125,14 +123,7 @@ def slice_bursts(plane, rows, plan: P.DmrPlan) -> tuple:
     rows = np.ascontiguousarray(np.asarray(rows, dtype=np.int64).reshape(-1, 3))
     if rows.size and not (np.isin(rows[:, 1], (-1, 1)).all() and ((rows[:, 2] >= 0) & (rows[:, 2] <= 3)).all()):
         raise ValueError("iqa_dmr_slice: a hit's sign must be +-1 and its kind 0 .. 3")
-    n, k = int(plane.numel()), rows.shape[0]
-    offsets = (c_int32 * P.DMR_OFFSETS)(*plan.offsets)
-    if n == 0 or k == 0:
-        N.call("iqa_dmr_slice", N.ptr(None), c_int64(n), N.ptr(None), c_int64(k), offsets, N.ptr(None), N.ptr(None), N.stream_ptr())
-        return np.zeros((k, P.DMR_WORDS), dtype=np.uint32), np.zeros((k, 3), dtype=np.int64)
-    bits, levels, rows_dev = D.empty(P.DMR_WORDS * k, "int32"), D.empty(3 * k, "int64"), D.from_numpy(rows)
-    N.call("iqa_dmr_slice", N.ptr(plane), c_int64(n), N.ptr(rows_dev), c_int64(k), offsets, N.ptr(bits), N.ptr(levels), N.stream_ptr())
-    return bits.cpu().numpy().view(np.uint32).reshape(k, P.DMR_WORDS), levels.cpu().numpy().reshape(k, 3)
+    return L.slice_hits("iqa_dmr_slice", plane, rows, plan.offsets, P.DMR_WORDS)
 
 
 def decode_bursts(bits, kinds) -> tuple:
@@ -145,13 +136,8 @@ def decode_bursts(bits, kinds) -> tuple:
     if kinds.size and not ((kinds >= 0) & (kinds <= 3)).all():
         raise ValueError("iqa_dmr_decode: a kind must be 0 .. 3")
     k = bits.shape[0]
-    if k == 0:
-        N.call("iqa_dmr_decode", N.ptr(None), N.ptr(None), c_int64(0), N.ptr(None), N.ptr(None), N.stream_ptr())
-        return np.zeros((0, 3), dtype=np.uint32), np.zeros((0, RECORD), dtype=np.int32)
-    bits_dev, kinds_dev = D.from_numpy(bits.view(np.int32)), D.from_numpy(kinds.astype(np.uint8))
-    info, rec = D.empty(3 * k, "int32"), D.empty(RECORD * k, "int32")
-    N.call("iqa_dmr_decode", N.ptr(bits_dev), N.ptr(kinds_dev), c_int64(k), N.ptr(info), N.ptr(rec), N.stream_ptr())
-    return info.cpu().numpy().view(np.uint32).reshape(k, 3), rec.cpu().numpy().reshape(k, RECORD)
+    return tuple(L.device_rows("iqa_dmr_decode", k, k == 0, bits.view(np.int32), kinds.astype(np.uint8), c_int64(k),
+                               L.Out(3, np.uint32), L.Out(RECORD, np.int32)))
 
 
 # ---- the bursts ---------------------------------------------------------------------------------------------------------------
@@ -167,16 +153,7 @@ def burst_hits(hits, pats, half: int) -> np.ndarray:
             continue
         which = PATTERNS.index(pats[p])
         cand.append((m, -abs(c), which, -1 if c < 0 else 1, 2 * which + (1 if c < 0 else 0)))
-    cand.sort()
-    rows = []
-    for j, (m, neg, which, s, kind) in enumerate(cand):
-        lo = hi = j
-        while lo > 0 and m - cand[lo - 1][0] <= half:
-            lo -= 1
-        while hi + 1 < len(cand) and cand[hi + 1][0] - m <= half:
-            hi += 1
-        if not any((o[1], o[0], o[2]) < (neg, m, which) for o in cand[lo : hi + 1]):
-            rows.append((m, s, kind))
+    rows = [(m, s, kind) for m, _neg, _which, s, kind in L.strongest_hits(cand, half)]
     return np.array(rows, dtype=np.int64).reshape(-1, 3)
 
 

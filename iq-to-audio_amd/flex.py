@@ -19,7 +19,6 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from . import _dev as D
-from . import _native as N
 from . import dsp_plan as P
 from . import identify as I
 from . import protocol_layer as L
@@ -77,15 +76,11 @@ def frames(plane, hits, plan: P.FlexPlan) -> np.ndarray:
     """``iqa_flex_frames`` on a device int32 plane for ``hits`` (int64[K][2]: m, s): int64[K][6] on the host."""
     hits = np.ascontiguousarray(np.asarray(hits, dtype=np.int64).reshape(-1, 2))
     n, k = int(plane.numel()), hits.shape[0]
-    offsets = (c_int32 * P.FLEX_HEADER_OFFSETS)(*plan.header)
+    (out,) = L.device_rows("iqa_flex_frames", k, n == 0 or k == 0, plane, c_int64(n), hits, c_int64(k),
+                           (c_int32 * P.FLEX_HEADER_OFFSETS)(*plan.header), L.Out(RECORD, np.int64))
     if n == 0 or k == 0:
-        N.call("iqa_flex_frames", N.ptr(None), c_int64(n), N.ptr(None), c_int64(k), offsets, N.ptr(None), N.stream_ptr())
-        out = np.zeros((k, RECORD), dtype=np.int64)
-        out[:, 4] = 3
-        return out
-    out, hits_dev = D.empty(RECORD * k, "int64"), D.from_numpy(hits)
-    N.call("iqa_flex_frames", N.ptr(plane), c_int64(n), N.ptr(hits_dev), c_int64(k), offsets, N.ptr(out), N.stream_ptr())
-    return out.cpu().numpy().reshape(k, RECORD)
+        out[:, 4] = 3  # (nothing was read: every instant lies outside)
+    return out
 
 
 def words(plane, recs, levels: int, u: int, plan: P.FlexPlan, offsets=None) -> tuple:
@@ -95,21 +90,15 @@ def words(plane, recs, levels: int, u: int, plan: P.FlexPlan, offsets=None) -> t
     recs = np.ascontiguousarray(np.asarray(recs, dtype=np.int64).reshape(-1, 4))
     n, f = int(plane.numel()), recs.shape[0]
     step = plan.steps[u - 1] if u in (1, 2) else 0
-    if n == 0 or f == 0:
-        N.call("iqa_flex_words", N.ptr(None), c_int64(n), N.ptr(None), c_int64(f), c_int32(levels), c_int32(u), c_int32(step),
-               N.ptr(None), N.ptr(None), N.ptr(None), N.ptr(None), N.stream_ptr())
-        shape = (f,) + WORD_SHAPE
-        return np.zeros(shape, dtype=np.uint32), np.zeros(shape, dtype=np.uint32), np.full(shape, 3, dtype=np.uint8)
     if offsets is None and u in (1, 2):
-        offsets = D.from_numpy(plan.data[u - 1])
-    count = f * P.FLEX_SHIFTS * P.FLEX_PHASES * P.FLEX_WORDS
-    fixed, raw, status = D.empty(count, "int32"), D.empty(count, "int32"), D.empty(count, "uint8")
-    recs_dev = D.from_numpy(recs)
-    N.call("iqa_flex_words", N.ptr(plane), c_int64(n), N.ptr(recs_dev), c_int64(f), c_int32(levels), c_int32(u), c_int32(step),
-           N.ptr(offsets), N.ptr(fixed), N.ptr(raw), N.ptr(status), N.stream_ptr())
-    shape = (f,) + WORD_SHAPE
-    return (fixed.cpu().numpy().view(np.uint32).reshape(shape), raw.cpu().numpy().view(np.uint32).reshape(shape),
-            status.cpu().numpy().reshape(shape))
+        offsets = plan.data[u - 1]  # (a host array: uploaded where anything is read)
+    count = P.FLEX_SHIFTS * P.FLEX_PHASES * P.FLEX_WORDS
+    fixed, raw, status = (a.reshape((f,) + WORD_SHAPE) for a in L.device_rows(
+        "iqa_flex_words", f, n == 0 or f == 0, plane, c_int64(n), recs, c_int64(f), c_int32(levels), c_int32(u), c_int32(step), offsets,
+        L.Out(count, np.uint32), L.Out(count, np.uint32), L.Out(count, np.uint8)))
+    if n == 0 or f == 0:
+        status[...] = 3  # (nothing was read: every instant lies outside)
+    return fixed, raw, status
 
 
 # ---- the shifts ---------------------------------------------------------------------------------------------------------------

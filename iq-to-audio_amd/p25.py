@@ -11,17 +11,16 @@ LDU1, the Golay(24,12,8) words of a TDULC or the three trellis blocks of a TSBK 
 from memory of TIA-102.BAAA and of open-source readers of it, not checked against either here.  Nothing is listened to: no
 vocoder, no HDU body, no LDU2.  No CPU path: without a GPU or the built library the device calls raise ``RuntimeError``.
 
-What every protocol layer shares lives in ``protocol_layer.py``: the stored stream under ``P25Decoder``, the per-lane loop under
+What every protocol layer shares lives in ``protocol_layer.py``: the stored stream under ``P25Decoder``, the device call on host
+rows under ``slice_frames`` / ``decode_nids`` / ``decode_frames``, the keep rule under ``frame_hits``, the per-lane loop under
 ``finish_p25``, the builder under ``p25_result``, and ``label`` / ``lines`` / ``to_json`` / ``from_json`` of the results."""
 from __future__ import annotations
 
-from ctypes import c_int32, c_int64
+from ctypes import c_int64
 from dataclasses import dataclass, field
 
 import numpy as np
 
-from . import _dev as D
-from . import _native as N
 from . import dsp_plan as P
 from . import identify as I
 from . import protocol_layer as L
@@ -203,14 +202,7 @@ def slice_frames(plane, rows, plan: P.P25Plan) -> tuple:
     rows = np.ascontiguousarray(np.asarray(rows, dtype=np.int64).reshape(-1, 2))
     if rows.size and not np.isin(rows[:, 1], (-1, 1)).all():
         raise ValueError("iqa_p25_slice: a hit's sign must be +-1")
-    n, k = int(plane.numel()), rows.shape[0]
-    offsets = (c_int32 * P.P25_OFFSETS)(*plan.offsets)
-    if n == 0 or k == 0:
-        N.call("iqa_p25_slice", N.ptr(None), c_int64(n), N.ptr(None), c_int64(k), offsets, N.ptr(None), N.ptr(None), N.stream_ptr())
-        return np.zeros((k, P.P25_WORDS), dtype=np.uint32), np.zeros((k, 3), dtype=np.int64)
-    bits, levels, rows_dev = D.empty(P.P25_WORDS * k, "int32"), D.empty(3 * k, "int64"), D.from_numpy(rows)
-    N.call("iqa_p25_slice", N.ptr(plane), c_int64(n), N.ptr(rows_dev), c_int64(k), offsets, N.ptr(bits), N.ptr(levels), N.stream_ptr())
-    return bits.cpu().numpy().view(np.uint32).reshape(k, P.P25_WORDS), levels.cpu().numpy().reshape(k, 3)
+    return L.slice_hits("iqa_p25_slice", plane, rows, plan.offsets, P.P25_WORDS)
 
 
 def _bits_of(bits) -> np.ndarray:
@@ -221,12 +213,7 @@ def decode_nids(bits) -> np.ndarray:
     """``iqa_p25_nid`` on ``bits`` (uint32[K][54], host): int32[K][4] (status, distance, value, parity_ok) on the host."""
     bits = _bits_of(bits)
     k = bits.shape[0]
-    if k == 0:
-        N.call("iqa_p25_nid", N.ptr(None), c_int64(0), N.ptr(None), N.stream_ptr())
-        return np.zeros((0, NID_RECORD), dtype=np.int32)
-    bits_dev, nid = D.from_numpy(bits.view(np.int32)), D.empty(NID_RECORD * k, "int32")
-    N.call("iqa_p25_nid", N.ptr(bits_dev), c_int64(k), N.ptr(nid), N.stream_ptr())
-    return nid.cpu().numpy().reshape(k, NID_RECORD)
+    return L.device_rows("iqa_p25_nid", k, k == 0, bits.view(np.int32), c_int64(k), L.Out(NID_RECORD, np.int32))[0]
 
 
 def decode_frames(bits, duids) -> tuple:
@@ -239,13 +226,8 @@ def decode_frames(bits, duids) -> tuple:
     if duids.size and not ((duids >= 0) & (duids <= 15)).all():
         raise ValueError("iqa_p25_decode: a DUID must be 0 .. 15")
     k = bits.shape[0]
-    if k == 0:
-        N.call("iqa_p25_decode", N.ptr(None), N.ptr(None), c_int64(0), N.ptr(None), N.ptr(None), N.stream_ptr())
-        return np.zeros((0, P.P25_INFO), dtype=np.uint32), np.zeros((0, RECORD), dtype=np.int32)
-    bits_dev, duids_dev = D.from_numpy(bits.view(np.int32)), D.from_numpy(duids.astype(np.uint8))
-    info, rec = D.empty(P.P25_INFO * k, "int32"), D.empty(RECORD * k, "int32")
-    N.call("iqa_p25_decode", N.ptr(bits_dev), N.ptr(duids_dev), c_int64(k), N.ptr(info), N.ptr(rec), N.stream_ptr())
-    return info.cpu().numpy().view(np.uint32).reshape(k, P.P25_INFO), rec.cpu().numpy().reshape(k, RECORD)
+    return tuple(L.device_rows("iqa_p25_decode", k, k == 0, bits.view(np.int32), duids.astype(np.uint8), c_int64(k),
+                               L.Out(P.P25_INFO, np.uint32), L.Out(RECORD, np.int32)))
 
 
 # ---- the frames ---------------------------------------------------------------------------------------------------------------
@@ -258,17 +240,8 @@ def frame_hits(hits, pats, half: int) -> np.ndarray:
     cand = []
     for p, m, c, _e, _pre, _post in np.asarray(hits, dtype=np.int64).reshape(-1, P.IDENT_RECORD).tolist():
         if pats[p].protocol == "p25" and c != 0:
-            cand.append((m, -abs(c), -1 if c < 0 else 1))
-    cand.sort()
-    rows = []
-    for j, (m, neg, s) in enumerate(cand):
-        lo = hi = j
-        while lo > 0 and m - cand[lo - 1][0] <= half:
-            lo -= 1
-        while hi + 1 < len(cand) and cand[hi + 1][0] - m <= half:
-            hi += 1
-        if not any((o[1], o[0]) < (neg, m) for o in cand[lo : hi + 1]):
-            rows.append((m, s))
+            cand.append((m, -abs(c), 0, -1 if c < 0 else 1))
+    rows = [(m, s) for m, _neg, _tie, s in L.strongest_hits(cand, half)]
     return np.array(rows, dtype=np.int64).reshape(-1, 2)
 
 

@@ -1,13 +1,19 @@
-"""What the protocol layers behind section 25 share (``flex.py``, ``dmr.py``; DESIGN.md, "Adding a layer to the second pass"):
-the stored discriminator stream of one channel (``join_theta``, ``StoredTheta``), the per-lane loop of a layer's ``finish_*``
-(``finish_lanes``), its result builder (``layer_result``) and the mixins of the result classes (``JsonRecord``,
-``ChannelLabel``, ``ChannelLines``).  A layer's module keeps its plan, its device calls, its parser and its dataclasses.
-Nothing here touches the GPU at import; ``identify.py``, which the layers import, imports this module in turn."""
+"""What the protocol layers behind section 25 share (``flex.py``, ``dmr.py``, ``p25.py``; DESIGN.md, "Adding a layer to the
+second pass"): the stored discriminator stream of one channel (``join_theta``, ``StoredTheta``), the shape of a device call on
+host rows (``device_rows``, ``slice_hits``), the keep rule across a protocol's patterns (``strongest_hits``), the per-lane loop
+of a layer's ``finish_*`` (``finish_lanes``), its result builder (``layer_result``) and the mixins of the result classes
+(``JsonRecord``, ``ChannelLabel``, ``ChannelLines``).  A layer's module keeps its plan, its checks, its parser and its
+dataclasses.  Nothing here touches the GPU at import; ``identify.py``, which the layers import, imports this module in turn."""
 from __future__ import annotations
 
+import ctypes
+from ctypes import c_int32, c_int64
 from dataclasses import asdict
 
+import numpy as np
+
 from . import _dev as D
+from . import _native as N
 from . import dsp_plan as P
 
 
@@ -65,6 +71,53 @@ class StoredTheta:
         for name in self.planes:
             st[name] = None if st[name] is None else st[name].cpu().numpy()
         return st
+
+
+class Out:
+    """An output of ``device_rows``: ``cols`` values of the numpy type ``dtype`` to a row (uint32 travels as int32)."""
+
+    def __init__(self, cols: int, dtype):
+        self.cols, self.dtype = int(cols), np.dtype(dtype)
+
+
+def device_rows(entry: str, k: int, empty: bool, *args) -> list:
+    """Host rows in, one call of ``entry``, host arrays out.  ``args`` are the entry point's, in its order and less the stream: a
+    ctypes value goes as it is, a device tensor as its pointer, a host array is uploaded, an ``Out`` is allocated for ``k`` rows
+    and comes back as a host array [k][cols], in the order of the ``Out``s.  ``empty`` (nothing to read): the same call with
+    every pointer NULL, which runs the entry point's checks and touches no device memory, and zeros come back."""
+    passed = (c_int32, c_int64, ctypes.Array)
+    if empty:
+        N.call(entry, *(a if isinstance(a, passed) else N.ptr(None) for a in args), N.stream_ptr())
+        return [np.zeros((k, a.cols), dtype=a.dtype) for a in args if isinstance(a, Out)]
+    held = [D.empty(k * a.cols, "int32" if a.dtype == np.uint32 else a.dtype.name) if isinstance(a, Out)
+            else D.from_numpy(a) if isinstance(a, np.ndarray) else a for a in args]
+    N.call(entry, *(t if isinstance(t, passed) else N.ptr(t) for t in held), N.stream_ptr())
+    return [t.cpu().numpy().view(a.dtype).reshape(k, a.cols) for a, t in zip(args, held) if isinstance(a, Out)]
+
+
+def slice_hits(entry: str, plane, rows, offsets, words: int) -> tuple:
+    """An ``iqa_*_slice`` on a device int32 plane for the checked ``rows`` (int64[K][..], a hit each) with the plan's ``offsets``:
+    (bits uint32[K][words], levels int64[K][3]) on the host."""
+    n, k = int(plane.numel()), rows.shape[0]
+    return tuple(device_rows(entry, k, n == 0 or k == 0, plane, c_int64(n), rows, c_int64(k), (c_int32 * len(offsets))(*offsets),
+                             Out(words, np.uint32), Out(3, np.int64)))
+
+
+def strongest_hits(cand, half: int) -> list:
+    """Of ``cand`` (tuples that begin m, -|C|, tie) those, in order of m, with no other within +-``half`` that has a larger |C|, or
+    the same |C| at a smaller m, or the same m at a smaller ``tie`` (the pattern's place in the table): section 25's keep rule
+    across the patterns of one protocol."""
+    cand = sorted(cand)
+    kept = []
+    for j, c in enumerate(cand):
+        lo = hi = j
+        while lo > 0 and c[0] - cand[lo - 1][0] <= half:
+            lo -= 1
+        while hi + 1 < len(cand) and cand[hi + 1][0] - c[0] <= half:
+            hi += 1
+        if not any((o[1], o[0], o[2]) < (c[1], c[0], c[2]) for o in cand[lo : hi + 1]):
+            kept.append(c)
+    return kept
 
 
 def finish_lanes(lanes, found, rate: int, plan_of, word: str, decode) -> list:
