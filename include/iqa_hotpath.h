@@ -969,6 +969,48 @@ int iqa_p25_nid(const void *bits_dev, int64_t K, void *nid_dev, void *stream);
 int iqa_p25_decode(const void *bits_dev, const void *duids_dev, int64_t K, void *info_dev, void *rec_dev, void *stream);
 
 /* ------------------------------------------------------------------------- *
+ * FICH and data channels of a YSF (System Fusion) channel (--find-ysf) *
+ * ------------------------------------------------------------------------- */
+
+#define IQA_YSF_OFFSETS 480     /* o[i] = rint(i sps), i = 0 .. 479: the symbols of one frame behind the end of sync symbol 0 */
+#define IQA_YSF_WORDS 30        /* uint32 words of a sliced frame: symbol i the frame bits 2 i, 2 i + 1 */
+#define IQA_YSF_FICH_RECORD 5   /* int32 values of a decoded FICH */
+#define IQA_YSF_INFO 12         /* uint32 words of a frame's decoded data channels: six to a block */
+#define IQA_YSF_RECORD 4        /* int32 values of a frame's decoded data channels */
+/* The levels and the bits of K frame sync hits.  plane_dev: int32[n], iqa_ident_integrate's output at 4800 symbols/s (|v| <=
+ * 64 * 65534).  hits_dev: int64[K][2], (m, s): m where sync symbol 0 ends, s the sign of the hit (negative: -1, the same word
+ * with the spectrum inverted; else +1).  offsets (host): the IQA_YSF_OFFSETS sample offsets of the symbols 0 .. 479, ascending
+ * in steps of at most IQA_IDENT_MAX_SPS + 1, o[0] = 0.  valid = 0 if m + o[0] < 0, else the number of i with m + o[i] < n.
+ * The sync word 0xD471C9634D holds inner levels (s_i in -3, -1, 1, 3; sum s_i = 12, sum s_i^2 = 124), so the levels are the
+ * least squares fit of x_i = plane[m + o[i]], i = 0 .. 19, to Dc + L s s_i: with P = sum x_i and Q = sum s_i x_i,
+ * Dc = 31 P - 3 Q and A = s (15 Q - 9 P), 584 times the DC and the outer level (3 L); both 0 where valid < 20.  Symbol
+ * i < valid reads as d = s (584 plane[m + o[i]] - Dc): its first bit (d < 0), its second (3 |d| >= 2 A); every other bit is
+ * 0.  bits_dev: uint32[K][30], the first sent bit the MSB of word 0.  levels_dev: int64[K][3]: A, Dc, valid.  Every instant
+ * is checked against 0 .. n - 1 before it is read.  n <= 2^30, K <= 2^20.  n = 0 or K = 0 returns IQA_OK and touches no
+ * pointer. */
+int iqa_ysf_slice(const void *plane_dev, int64_t n, const void *hits_dev, int64_t K, const int32_t offsets[IQA_YSF_OFFSETS],
+                  void *bits_dev, void *levels_dev, void *stream);
+/* The frame information channel of K sliced frames: the 100 dibits of the frame bits 40 .. 239, coded dibit i the channel dibit
+ * 20 (i mod 5) + i / 5, through the 16-state Viterbi decoder of the rate 1/2, K = 5 code (g1 = d + d3 + d4, g2 = d + d1 + d2 +
+ * d4, g1 sent first; the trellis starts and ends in state 0; Hamming metric; on equal metrics the predecessor with the smaller
+ * state index d1 d2 d3 d4 survives), then the four Golay(24,12,8) words of the 96 decoded bits against the 4096 codewords: a
+ * word at a distance of 3 or less is corrected (on equal distance the smaller data value), else refused with its raw top 12
+ * bits kept.  fich_dev: uint32[K][2]: the 48 data bits, word 0 the four FICH bytes, the top 16 bits of word 1 their CRC.
+ * rec_dev: int32[K][5]: status (0 clean, 1 corrected, 2 a Golay word refused), the Viterbi metric (channel bits changed), the
+ * Golay words corrected, refused, and the bits changed in the corrected ones.  K <= 2^20.  K = 0 returns IQA_OK and touches
+ * no pointer. */
+int iqa_ysf_fich(const void *bits_dev, int64_t K, void *fich_dev, void *rec_dev, void *stream);
+/* The data channels (DCH) of K sliced frames, by class (classes_dev: uint8[K]); payload block p = 0 .. 4 is the frame bits
+ * 240 + 144 p .. + 143.  Class 1 (header, terminator, data FR): DCH-a the first 72 bits of every block, DCH-b the 72 behind
+ * them, 180 dibits each, coded dibit i the channel dibit 20 (i mod 9) + i / 9, each through iqa_ysf_fich's Viterbi decoder
+ * to 176 bits and 4 tail bits.  Class 2 (V/D mode 1): DCH-a alone.  Class 3 (V/D mode 2): the first 40 bits of every block,
+ * 100 dibits, coded dibit i the channel dibit 20 (i mod 5) + i / 5, to 96 bits and 4 tail bits.  Class 0 and every value over
+ * 3: zeros.  info_dev: uint32[K][12]: DCH-a in words 0 .. 5, DCH-b in words 6 .. 11, the first bit the MSB of the block's
+ * first word, zeros behind the block's bits.  rec_dev: int32[K][4]: the class (0 for a value over 3), the metric of DCH-a, of
+ * DCH-b (channel bits changed; 0 where the block is not read), 0.  K <= 2^20.  K = 0 returns IQA_OK and touches no pointer. */
+int iqa_ysf_decode(const void *bits_dev, const void *classes_dev, int64_t K, void *info_dev, void *rec_dev, void *stream);
+
+/* ------------------------------------------------------------------------- *
  * Carrier squelch of a run's targets (--squelch)       *
  * ------------------------------------------------------------------------- */
 

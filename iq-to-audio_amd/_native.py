@@ -212,6 +212,9 @@ _SIGNATURES = {
     "iqa_p25_slice": (ctypes.c_int, [c_void_p, c_int64, c_void_p, c_int64, ctypes.POINTER(c_int32), c_void_p, c_void_p, c_void_p]),
     "iqa_p25_nid": (ctypes.c_int, [c_void_p, c_int64, c_void_p, c_void_p]),
     "iqa_p25_decode": (ctypes.c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
+    "iqa_ysf_slice": (ctypes.c_int, [c_void_p, c_int64, c_void_p, c_int64, ctypes.POINTER(c_int32), c_void_p, c_void_p, c_void_p]),
+    "iqa_ysf_fich": (ctypes.c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
+    "iqa_ysf_decode": (ctypes.c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
     "iqa_gate_cells": (c_int64, [c_int64, c_int64]),
     "iqa_gate_power": (ctypes.c_int, [c_void_p, c_int64, c_int64, c_int32, c_void_p, c_void_p]),
     "iqa_gate_add_cells": (ctypes.c_int, [c_void_p, c_int64, c_void_p, c_void_p]),

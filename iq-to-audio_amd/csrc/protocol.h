@@ -1,4 +1,4 @@
-// protocol.h -- what the kernels of the second pass's protocol layers share (ident.hip, flex.hip, dmr.hip, p25.hip; DESIGN.md
+// protocol.h -- what the kernels of the second pass's protocol layers share (ident.hip, flex.hip, dmr.hip, p25.hip, ysf.hip; DESIGN.md
 // section 27), for gfx950: the bits of a word record, the sync word's levels, the Golay code over 0xC75, the workgroup minimum,
 // the slicing of a four-level symbol against the levels of its sync word, and the host checks of the entry points.
 //

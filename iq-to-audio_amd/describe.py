@@ -12,7 +12,7 @@ library the calls raise ``RuntimeError``.
 The layers above this one (``find_layers.FIND_LAYERS``, each in the module of its name) ride on the same pass: with ``keying=True``
 it also takes every channel's discriminator and, once the channel holds 1024 gated pairs, its keying rows (``keying.py``); with
 ``identify=True`` it keeps that discriminator output for the sync-word search of ``identify.py``, whose hits ``flex.py`` decodes
-with ``flex=True``, ``dmr.py`` with ``dmr=True`` and ``p25.py`` with ``p25=True``."""
+with ``flex=True``, ``dmr.py`` with ``dmr=True``, ``p25.py`` with ``p25=True`` and ``ysf.py`` with ``ysf=True``."""
 from __future__ import annotations
 
 import math
@@ -29,6 +29,7 @@ from . import flex as X
 from . import identify as I
 from . import keying as KY
 from . import p25 as P5
+from . import ysf as YS
 from .find import _RAW_DTYPE
 from .find_layers import FIND_LAYERS, active_layers
 
@@ -244,7 +245,7 @@ def add_rows(rows: np.ndarray) -> tuple:
     return tuple((int(h) << 32) + int(l) for h, l in zip(high, low))
 
 
-_MODULES = {m.__name__.rpartition(".")[2]: m for m in (KY, I, X, DM, P5)}  # a layer above the first lives in the module of its keyword
+_MODULES = {m.__name__.rpartition(".")[2]: m for m in (KY, I, X, DM, P5, YS)}  # a layer above the first lives in the module of its keyword
 
 
 class _Lane:
@@ -276,7 +277,7 @@ class ChannelDescriber:
     (the eight sums of every channel), ``result()`` (a ``DescribeResult``), ``stages()`` for the tests, ``reset()``.
     ``fin`` is ``ChannelFinder.finish()`` of the same capture and ``channels`` the ``FoundChannel``s made from it.  ``layers``: the
     keywords of ``FIND_LAYERS`` above the first (``keying=True``, ``identify=True``, ``flex=True``), each with the one in front of
-    it, and of ``FIND_ALL_BRANCHES`` (``dmr=True``, ``p25=True``, with ``identify=True``)."""
+    it, and of ``FIND_EVERY_BRANCH`` (``dmr=True``, ``p25=True``, ``ysf=True``, with ``identify=True``)."""
 
     def __init__(self, find_plan: P.FindPlan, fin: dict, channels, fmt: str = "s16", iq_order: str = "iq", *, keep_stages: bool = False,
                  **layers):
@@ -477,6 +478,14 @@ class ChannelDescriber:
 
     def p25_result(self, center_freq: float | None = None) -> P5.P25Result:
         return P5.p25_result(self.channels, self.lanes(), self.finish_p25(), self.find_plan.fs, center_freq)
+
+    def finish_ysf(self) -> list:
+        """Per channel the dict of ``ysf.finish_ysf``."""
+        self._need("ysf")
+        return self._once("ysf", lambda: YS.finish_ysf(self.lanes(), self.finish_identify()))
+
+    def ysf_result(self, center_freq: float | None = None) -> YS.YsfResult:
+        return YS.ysf_result(self.channels, self.lanes(), self.finish_ysf(), self.find_plan.fs, center_freq)
 
     def result(self, center_freq: float | None = None) -> DescribeResult:
         sums = self.finish()

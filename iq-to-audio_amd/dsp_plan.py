@@ -1132,6 +1132,34 @@ def plan_p25(fs_ch: float) -> P25Plan:
     return P25Plan(fs_ch=ident.fs_ch, sps=ident.sps, offsets=offsets, ident=ident)
 
 
+# ---- YSF frame decoding plan (--find-ysf) ----------------------------------
+
+YSF_OFFSETS = 480  # o[i], i = 0 .. 479: the symbols of one frame
+YSF_WORDS = 30  # uint32 words of a sliced frame: symbol i the frame bits 2 i, 2 i + 1
+YSF_FICH_RECORD = 5  # int32 values of a decoded FICH
+YSF_INFO = 12  # uint32 words of a frame's decoded data channels: six to a block
+YSF_RECORD = 4  # int32 values of a frame's decoded data channels
+
+
+@dataclass(frozen=True)
+class YsfPlan:
+    fs_ch: float
+    sps: float  # fs_ch / 4800
+    offsets: tuple  # o[i] = rint(i sps), i = 0 .. 479 (half-even, float64)
+    ident: IdentPlan  # section 25's plan at 4800 symbols/s
+
+    def o(self, i: int) -> int:
+        return self.offsets[i]
+
+
+def plan_ysf(fs_ch: float) -> YsfPlan:
+    """The sample offsets of the symbols of a YSF frame behind the end of sync symbol 0 at the channel rate ``fs_ch``, and section
+    25's plan at 4800 symbols/s.  ``ValueError`` unless 4 <= sps <= 224 (``plan_ident``'s limits)."""
+    ident = plan_ident(fs_ch, 4800)
+    offsets = tuple(int(np.rint(i * ident.sps)) for i in range(YSF_OFFSETS))
+    return YsfPlan(fs_ch=ident.fs_ch, sps=ident.sps, offsets=offsets, ident=ident)
+
+
 # ---- carrier squelch plan (--squelch; DESIGN.md section 24) --------------------------------------
 
 GATE_CELL = 256  # IQA_GATE_CELL: samples to a cell, counted on the absolute position

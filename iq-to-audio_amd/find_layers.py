@@ -1,9 +1,11 @@
 """The layers of the second pass over a capture: what ``--find-describe``, ``--find-decode``, ``--find-identify``,
-``--find-flex``, ``--find-dmr`` and ``--find-p25`` add to the finder's channel list (DESIGN.md sections 22, 23, 25, 26, 29 and 31).
+``--find-flex``, ``--find-dmr``, ``--find-p25`` and ``--find-ysf`` add to the finder's channel list (DESIGN.md sections 22, 23, 25, 26, 29,
+31 and 32).
 
 ``FIND_LAYERS`` lists the chain, in order: every row needs the row in front of it.  ``FIND_BRANCHES`` lists the layers that
-hang off one row of the chain (``needs``) and off nothing else; ``FIND_ALL_BRANCHES`` is that list with the branches added since
-(``p25``; YSF and NXDN will be rows there), and it is the one that is looped over.  ``find_channels``, ``ChannelDescriber`` and the CLI read a
+hang off one row of the chain (``needs``) and off nothing else; ``FIND_ALL_BRANCHES`` is that list with ``p25`` added, and
+``FIND_EVERY_BRANCH`` that one with the branches added since (``ysf``; NXDN will be a row there): it is the one that is looped
+over, and a test that finds its row by name need not be touched by the next.  ``find_channels``, ``ChannelDescriber`` and the CLI read a
 layer's keyword, flag, result and file suffix from its row; a new layer is a row here, a keyword on ``ChannelDescriber`` and
 its own module ("Adding a layer to the second pass").  Nothing heavy is imported here: the CLI reads the tables
 before the GPU is touched."""
@@ -63,6 +65,15 @@ FIND_ALL_BRANCHES = FIND_BRANCHES + (
 )
 
 
+FIND_EVERY_BRANCH = FIND_ALL_BRANCHES + (
+    FindLayer("ysf", "find_ysf", 32, lambda d, fc, fs_ch: d.ysf_result(fc), "ysf", False,
+              "Find, describe, key and identify the channels, and decode the frames of every channel that carries YSF (System "
+              "Fusion) frame sync words: the FICH and the callsigns of the data channels, one line per transmission (source, "
+              "destination, repeater, mode, duration), also written to <capture stem>.ysf.json.  No voice.  Implies "
+              "--find-identify.", needs="identify"),
+)
+
+
 def active_layers(switches: dict) -> tuple:
     """The rows switched on in ``switches`` (name -> bool): the chain's in chain order, then the branches'.  ``ValueError`` for
     the first row of the chain that is on while the row in front of it is not, then for the first branch that is on while the
@@ -70,7 +81,7 @@ def active_layers(switches: dict) -> tuple:
     for below, layer in zip(FIND_LAYERS, FIND_LAYERS[1:]):
         if switches.get(layer.name) and not switches.get(below.name):
             raise ValueError(f"{layer.name}=True needs {below.name}=True")
-    for layer in FIND_ALL_BRANCHES:
+    for layer in FIND_EVERY_BRANCH:
         if switches.get(layer.name) and not switches.get(layer.needs):
             raise ValueError(f"{layer.name}=True needs {layer.needs}=True")
-    return tuple(layer for layer in FIND_LAYERS + FIND_ALL_BRANCHES if switches.get(layer.name))
+    return tuple(layer for layer in FIND_LAYERS + FIND_EVERY_BRANCH if switches.get(layer.name))

@@ -1,4 +1,4 @@
-"""What the protocol layers behind section 25 share (``flex.py``, ``dmr.py``, ``p25.py``; DESIGN.md, "Adding a layer to the
+"""What the protocol layers behind section 25 share (``flex.py``, ``dmr.py``, ``p25.py``, ``ysf.py``; DESIGN.md, "Adding a layer to the
 second pass"): the stored discriminator stream of one channel (``join_theta``, ``StoredTheta``), the shape of a device call on
 host rows (``device_rows``, ``slice_hits``), the keep rule across a protocol's patterns (``strongest_hits``), the per-lane loop
 of a layer's ``finish_*`` (``finish_lanes``), its result builder (``layer_result``) and the mixins of the result classes
