@@ -171,7 +171,9 @@ class _ChannelKernel:
     def fixed_point_error_rms(self, wideband_rms: float) -> float:
         """Expected z error (RMS, fraction of full scale) of this kernel for a capture of the given wideband RMS: tap
         rounding x wideband level plus the level-independent floor of the dropped (low tap byte) x (low data byte)
-        products (0.0 when this channel never runs on the matrix cores)."""
+        products -- for uniform low bytes, never below the plan's zero-input response, and for a quiet capture the bound
+        for low bytes coherent with an in-channel signal (``dsp_plan.dropped_floor``); 0.0 when this channel never runs on
+        the matrix cores."""
         return float(self._ensure_mfma().z_error_rms(wideband_rms)) if self._mfma_ok else 0.0
 
     @staticmethod

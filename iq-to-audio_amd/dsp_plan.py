@@ -114,6 +114,7 @@ class ChannelPlan:
     rot_base: int
     out_scale: complex
     taps_natural: np.ndarray | None = None  # complex128 [L], natural order g[k] (same folding), for the MFMA planner
+    nco_step: int = 0  # NCO advance per input sample, 2^-64 turns: g[k] = h[k] e^{-+j 2 pi nco_step k / 2^64} (the MFMA planner's in-band gain)
 
 
 def plan_channel(
@@ -159,7 +160,7 @@ def plan_channel(
     win[:ntaps] = g[::-1].astype(np.complex64)  # window order: win[i] multiplies x[n0-(L-1)+i]
     return ChannelPlan(
         fmt=fmt, ntaps=ntaps, decimation=int(decimation), taps_window=win, conj_sum=int(conj), rotate=1,
-        rot_step=(w * int(decimation)) % TWO64, rot_base=0, out_scale=c, taps_natural=g.astype(np.complex128),
+        rot_step=(w * int(decimation)) % TWO64, rot_base=0, out_scale=c, taps_natural=g.astype(np.complex128), nco_step=w,
     )
 
 
@@ -198,9 +199,26 @@ class MfmaPlan:
     groups: list
     passes: list
     err_norm: float = 0.0  # sqrt(sum_k |T_k u - g_k|^2) per unit of full scale: the z error for a white input of unit RMS
-    #: RMS of the part of the z error that does NOT scale with the input: the q2*lo' products the int16 kernels drop
-    #: (low tap byte x low data byte), for data whose low bytes are uniform (any capture well above 8 bits)
+    #: The part of the z error that does NOT scale with the input: the q2*lo' products the int16 kernels drop (low tap
+    #: byte x low data byte; uint8 captures drop nothing: all three are 0).  Three figures, fractions of full scale:
+    #: ``floor_rms`` -- its RMS for data whose low bytes are uniform and independent of the taps (noise of some tens of LSB
+    #: and more: measured 1.0x at 300 and 3000 LSB, 1.4x at 30 LSB).
     floor_rms: float = 0.0
+    #: ``zero_rms`` -- |z| of the zero-input response, EXACT: an all-zero capture has lo' = -128 everywhere, so the kernels
+    #: emit the constant 128 * unit * sum(q2) per output component (summed over the plan's groups) where the filter gives
+    #: 0.  It is what any stretch of a capture costs whose values stand still within one byte -- silence, a DC offset, the
+    #: quiet half of a keyed signal, a clean carrier whose phase turns slowly against the filter length -- at ANY level
+    #: estimate, so ``z_error_rms`` and the precision guard always apply it.  sum(q2) is the DC gain of the low tap bytes:
+    #: where |T| < 128 (the tails of a Kaiser design) q2 IS the tap, so at offset 0 it is ~18x ``floor_rms``; away from
+    #: offset 0 the NCO turns the taps and it is of the order of ``floor_rms`` or below.
+    zero_rms: float = 0.0
+    #: ``coherent_rms`` -- the bound for a QUIET capture (see ``QUIET_WIDEBAND``) whose content is a clean signal in the
+    #: channel: for |v| < 128 the low byte is lo' = v - 128 sgn(v), i.e. the signal itself minus a square wave of 128 LSB
+    #: in step with it, whose fundamental (4/pi * 128) the low tap bytes pass with their gain at the channel centre:
+    #: (4/pi) * 128 * |sum_k unit * g2[k] e^{+-j 2 pi nco_step k}|, g2 the complex low-byte taps.  A constant-envelope
+    #: signal of A LSB measures |1 - A / 163| of it (D = 104, +1 MHz: 1.10e-5 at 46 LSB, 6.4e-6 at 100 against 1.16e-5 and
+    #: 6.2e-6 predicted).
+    coherent_rms: float = 0.0
 
     # single-pass conveniences (tests, and the common ceil(L/D) <= 64, D <= 256 case)
     @property
@@ -223,9 +241,36 @@ class MfmaPlan:
     def c_im(self):
         return sum(p.c_im for p in self.passes if p.group == 0)
 
+    def floors(self) -> tuple:
+        """(floor_rms, zero_rms, coherent_rms): the operands of ``dropped_floor``."""
+        return float(self.floor_rms), float(self.zero_rms), float(self.coherent_rms)
+
     def z_error_rms(self, wideband_rms: float) -> float:
-        """Expected RMS error of z for a capture of the given wideband RMS (fraction of full scale)."""
-        return math.hypot(self.err_norm * wideband_rms, self.floor_rms)
+        """Expected RMS error of z for a capture of the given wideband RMS (fraction of full scale): tap rounding x level
+        and the level-independent floor of the dropped products (``dropped_floor``)."""
+        return math.hypot(self.err_norm * wideband_rms, dropped_floor(self.floors(), wideband_rms))
+
+
+#: Wideband RMS (fraction of the KERNEL's full scale) below which a capture counts as quiet: 128 LSB of an int16.  A
+#: constant-envelope signal of that level is the largest whose I and Q never leave the two bytes around zero, which is
+#: what makes lo' = v - 128 sgn(v) coherent with it.  Exact-model sweep (tests/test_guard_model_host.py; D = 104, clean NFM,
+#: 1 LSB of noise; audio RMS error of "fast" against the float64 chain, bar 1e-4), at offset 0 / +1 MHz:
+#:   46 LSB 2.2e-4 / 1.7e-4, 64 LSB 1.3e-4 / 1.0e-4, 80 LSB 9.3e-5, 100 LSB 6.2e-5 / 4.6e-5, 128 LSB 3.7e-5 / 2.5e-5,
+#:   160 LSB 2.5e-5 / 1.5e-5, 200 LSB 2.7e-5 / 1.7e-5.
+#: D = 521 at +2.2 MHz (the plan of the sweep whose zero-input response is smallest, so that nothing else catches it):
+#:   64 LSB 1.5e-4, 80 LSB 1.1e-4, 100 LSB 8.1e-5, 128 LSB 5.8e-5, 160 LSB 4.4e-5, 200 LSB 3.7e-5.
+#: The bar is crossed between 64 and 100 LSB; at 128 LSB and above "fast" keeps it with a margin of 1.7 and more.
+QUIET_WIDEBAND = 2.0**-8
+
+
+def dropped_floor(floors, kernel_wideband_rms: float) -> float:
+    """The level-independent part of the int16 kernels' z error, in units of the kernel's full scale, for a capture of
+    wideband RMS ``kernel_wideband_rms`` (same units).  ``floors``: ``MfmaPlan.floors()``.  The uniform-low-byte RMS and
+    the zero-input response hold at every level (a level estimate says nothing about the quiet stretches of a capture);
+    the coherent bound joins them below ``QUIET_WIDEBAND``."""
+    floor_rms, zero_rms, coherent_rms = floors
+    worst = max(floor_rms, zero_rms)
+    return max(worst, coherent_rms) if kernel_wideband_rms < QUIET_WIDEBAND else worst
 
 
 def mfma_supported(plan: ChannelPlan) -> bool:
@@ -315,6 +360,11 @@ def plan_mfma(plan: ChannelPlan, acc32: bool = False, max_ksteps: int | None = N
     n_groups = max(1, -(-(-(-plan.ntaps // D)) // MFMA_Q))
     groups, passes = [], []
     err_sq = floor_sq = 0.0
+    zero_re = zero_im = 0.0  # the zero-input response: 128 * unit * sum(q2) per output component, over every group
+    inband = np.zeros(2, dtype=np.complex128)  # sum_k unit * g2[k] e^{+-j 2 pi nco_step k}: the low tap bytes' gain at the channel centre
+    with np.errstate(over="ignore"):
+        nco_turns = ((np.uint64(plan.nco_step % TWO64) * np.arange(plan.ntaps, dtype=np.uint64)) >> np.uint64(11)).astype(np.float64) * 2.0**-53
+    nco = np.exp(2j * np.pi * nco_turns)
     ksteps = -(-2 * D // 32)
     n_chunks = -(-ksteps // (max_ksteps or MFMA_MAX_KSTEPS_PER_PASS))  # k-step ranges: one pass each
     bounds = [round(i * ksteps / n_chunks) for i in range(n_chunks + 1)]
@@ -338,6 +388,10 @@ def plan_mfma(plan: ChannelPlan, acc32: bool = False, max_ksteps: int | None = N
             left = left - t * unit
             if s16:
                 floor_sq += unit * unit * _LOW_BYTE_VAR * float((q2.astype(np.float64) ** 2).sum())
+                zero_re += 128.0 * unit * float(q2[:MFMA_Q].sum(dtype=np.int64))
+                zero_im += 128.0 * unit * float(q2[MFMA_Q:].sum(dtype=np.int64))
+                g2 = (q2[:MFMA_Q, 0 : 2 * D : 2] - 1j * q2[:MFMA_Q, 1 : 2 * D : 2])[ok] * unit  # (the layout of ``a`` above)
+                inband += [np.sum(g2 * nco[kc[ok]]), np.sum(g2 * np.conj(nco[kc[ok]]))]
             frag = np.empty((ksteps, 4, 2, 64, 16), dtype=np.int8)
             frag[:, :, 0] = q1.reshape(-1)[flat]
             frag[:, :, 1] = q2.reshape(-1)[flat]
@@ -350,7 +404,10 @@ def plan_mfma(plan: ChannelPlan, acc32: bool = False, max_ksteps: int | None = N
                 passes.append(MfmaPass(len(groups) - 1, k0, k1 - k0, bias * float(sl[:MFMA_Q].sum(dtype=np.int64)),
                                        bias * float(sl[MFMA_Q:].sum(dtype=np.int64))))
         err_sq += 0.5 * float((left**2).sum())  # every complex tap sits in the matrix twice (re and im rows)
-    return MfmaPlan(ksteps, groups, passes, math.sqrt(err_sq) / INGEST_SCALE[plan.fmt], math.sqrt(floor_sq))
+    # (which of the two turns is the channel's depends on the sample order's conjugation: the other one finds no gain)
+    coherent = 4.0 / math.pi * 128.0 * float(np.abs(inband).max())
+    return MfmaPlan(ksteps, groups, passes, math.sqrt(err_sq) / INGEST_SCALE[plan.fmt], math.sqrt(floor_sq),
+                    math.hypot(zero_re, zero_im), coherent)
 
 
 def mfma_interior(consumed: int, n_frames: int, m_first: int, n_out: int, decimation: int, ksteps: int,

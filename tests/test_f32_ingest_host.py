@@ -51,10 +51,11 @@ def test_f32_ingest_zero_length_is_a_no_op():
 
 
 class _Kernel(SimpleNamespace):
-    """A planned kernel as ``pick_precision`` sees it: its precision, and (tap-rounding norm, floor) of its plan."""
+    """A planned kernel as ``pick_precision`` sees it: its precision, and (tap-rounding norm, floors) of its plan -- the
+    uniform-low-byte floor alone (zero-input response and coherent bound 0: ``floor`` is the whole level-independent part)."""
 
     def _ensure_mfma(self):
-        return SimpleNamespace(err_norm=self.norm, floor_rms=self.floor)
+        return SimpleNamespace(err_norm=self.norm, floor_rms=self.floor, zero_rms=0.0, coherent_rms=0.0)
 
 
 def test_precision_guard_scales_the_floor_by_the_planes_headroom():

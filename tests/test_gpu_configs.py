@@ -684,6 +684,60 @@ def test_precision_guard_routes_a_very_weak_nfm_channel_to_a_finer_precision(A, 
         assert err < 1e-4, (off, err)
 
 
+def quiet_nfm_capture(amplitude_lsb, n, fs=10e6):
+    """A clean NFM signal of ``amplitude_lsb`` LSB at +1.0 MHz alone in the capture, one LSB of noise: int16 frames."""
+    t = np.arange(n, dtype=np.float64) / fs
+    z = amplitude_lsb * np.exp(1j * (2 * np.pi * 1.0e6 * t + 3.0 * (1.0 - np.cos(2 * np.pi * 1000.0 * t))))
+    iq = np.column_stack((z.real, z.imag)) + np.random.default_rng(64).normal(scale=1.0, size=(n, 2))
+    return np.rint(iq).astype(np.int16)
+
+
+@pytest.mark.parametrize("container", ["cs16", "cf32"])
+@pytest.mark.parametrize("amplitude_lsb,stays_fast", [(64, False), (200, True)])
+def test_precision_guard_on_a_quiet_capture(A, tmp_path, amplitude_lsb, stays_fast, container):
+    """A low-gain recording: the capture's only content is a clean NFM signal a few dozen LSB tall.  The channel is as
+    loud as the capture, so the tap-rounding term of the guard is nowhere near -- but below 128 LSB the low data bytes are
+    coherent with the signal, and the products the int16 kernels drop put "fast" 1.0e-4 off the float64 chain at 64 LSB
+    (exact model, tests/test_guard_model_host.py).  The guard must move that target off "fast" and keep the 1e-4 bar; the same
+    signal at 200 LSB must stay "fast" and keep it too (the fix does not escalate everything).  As int16 and as float32
+    on the integer path; the shortest capture whose one block still has ``mfma_min_outputs`` (lowered to 4096) interior
+    outputs, so that the matrix-core kernel runs."""
+    from iq_to_audio_amd import dsp_plan as P
+    from iq_to_audio_amd import processing as PR
+
+    fs, fc, d, ks, min_out = 10e6, 1.0e9, 104, 7, 4096
+
+    def interior(frames):  # (_ChannelKernel._interior of a first block: the contiguous ring slots fetch 512 ks frames per tile)
+        m_a, m_b = P.mfma_interior(0, frames, 0, -(-frames // d), d, ks)
+        return min(m_b, (frames - 512 * ks - 1) // d + 2) - m_a
+
+    n = (min_out + 64 - 2) * d + 512 * ks + 1
+    assert interior(n) == min_out and interior(n - 1) == min_out - 1
+    raw = quiet_nfm_capture(amplitude_lsb, n, fs)
+    path = tmp_path / f"quiet_1000000000Hz.{container}"
+    path.write_bytes((raw if container == "cs16" else (raw.astype(np.float32) / 32768.0).astype(np.float32)).tobytes())
+    cfg = A.ProcessingConfig(in_path=path, target_freq=fc + 1.0e6, demod_mode="nfm", input_sample_rate=fs, output_path=tmp_path / "q.wav")
+    keep = PR._ChannelKernel.mfma_min_outputs
+    try:
+        PR._ChannelKernel.mfma_min_outputs = min_out
+        multi = A.MultiChannelPipeline([cfg])
+        multi.owners[0].keep_channel_audio = True
+        res = multi.run()
+    finally:
+        PR._ChannelKernel.mfma_min_outputs = keep
+    o = multi.owners[0]
+    if container == "cf32":
+        assert multi.integer_blocks >= 1  # the block ran as int16
+    assert o.channelizer_kernel == "k_channelize_mfma_s16_ring", o.channelizer_kernel
+    want = O.run_chain(raw, sample_rate=fs, freq_offset=1.0e6, keep_decimated=False)
+    got = o.audio_fs_channel.cpu().numpy()
+    assert got.size == want.audio.size and res[0].mix_sign == want.mix_sign
+    err = rms(got - want.audio)
+    print(f"quiet capture, {amplitude_lsb} LSB as {container}: precision {o.channelizer_precision}, audio rms err {err:.2e}")
+    assert (o.channelizer_precision == "fast") == stays_fast, o.channelizer_precision
+    assert err < 1e-4, (amplitude_lsb, container, o.channelizer_precision, err)
+
+
 def test_channelizer_precision_ladder_against_the_oracle(A):
     """Channelizer(precision=...): "fast" (ring, one int32 sum, ~14-bit taps), "fine" (the same kernels, each tap-row
     group as two lanes: high-byte-only taps + their residue), "full" (per-lane kernel, 16-bit taps + residue as chained

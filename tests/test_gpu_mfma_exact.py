@@ -69,8 +69,14 @@ def random_plan(L: int, d: int, fmt: str, acc32: bool, residual: bool, max_ks, s
     return P.plan_mfma(plan, acc32=acc32, max_ksteps=max_ks, residual=residual)
 
 
-def capture(fmt: str, n_frames: int, seed: int) -> np.ndarray:
-    """Uniform full-range interleaved values, the extremes included."""
+def capture(fmt: str, n_frames: int, seed: int, data=None) -> np.ndarray:
+    """Uniform full-range interleaved values, the extremes included.  ``data(fmt, n_frames)``: the 2 n_frames values to
+    use instead (tests/test_gpu_mfma_data_classes.py), which must be legal for the format."""
+    if data is not None:
+        lo, hi, dt = (-32768, 32767, np.int16) if fmt == "s16" else (0, 255, np.uint8)
+        v = np.asarray(data(fmt, n_frames))
+        assert v.shape == (2 * n_frames,) and v.dtype.kind in "iu" and v.min() >= lo and v.max() <= hi
+        return v.astype(dt)
     rng = np.random.default_rng(seed)
     if fmt == "s16":
         v = rng.integers(-32768, 32768, 2 * n_frames, dtype=np.int64)
@@ -275,9 +281,10 @@ def _rot(rng):
     return int(rng.integers(0, 2**63)) * 2 + int(rng.integers(0, 2)), int(rng.integers(0, 2**63)) * 2
 
 
-def setup_capture(fmt, d, mode, k_first, k_count, q_min, q_max, m_first, n_out, opb, seed, consumed=None, extra=0):
+def setup_capture(fmt, d, mode, k_first, k_count, q_min, q_max, m_first, n_out, opb, seed, consumed=None, extra=0, data=None):
     """Device capture that holds exactly what the launch may read (+ ``extra`` frames), with random values behind it
-    that a read past the bound would pick up.  Returns (raw numpy, x_dev, n_frames, consumed)."""
+    that a read past the bound would pick up.  ``data(fmt, n_frames)``: the values of the readable part (default: uniform
+    full range, see ``capture``).  Returns (raw numpy, x_dev, n_frames, consumed)."""
     from iq_to_audio_amd import _dev as D
 
     if consumed is None:
@@ -286,6 +293,8 @@ def setup_capture(fmt, d, mode, k_first, k_count, q_min, q_max, m_first, n_out, 
     if mode == 1:  # the header's form of the contiguous bound
         n_frames = max(n_frames, (m_first + n_out - 2) * d + 512 * (-(-2 * d // 32)) - consumed + 1)
     raw = capture(fmt, n_frames + 4096, seed)
+    if data is not None:
+        raw[: 2 * n_frames] = capture(fmt, n_frames, seed, data=data)
     x_dev = D.to_device(raw, "int16" if fmt == "s16" else "uint8")
     assert_read_bounds(mode, d, k_first, k_count, q_min, q_max, m_first, n_out, opb, consumed, n_frames)
     return raw[: 2 * n_frames], x_dev, n_frames, consumed
