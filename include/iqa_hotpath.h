@@ -1011,6 +1011,45 @@ int iqa_ysf_fich(const void *bits_dev, int64_t K, void *fich_dev, void *rec_dev,
 int iqa_ysf_decode(const void *bits_dev, const void *classes_dev, int64_t K, void *info_dev, void *rec_dev, void *stream);
 
 /* ------------------------------------------------------------------------- *
+ * LICH, SACCH, FACCH1 and CAC of an NXDN channel (--find-nxdn) *
+ * ------------------------------------------------------------------------- */
+
+#define IQA_NXDN_OFFSETS 192    /* o[i] = rint(i sps), i = 0 .. 191: the symbols of one frame behind the end of sync symbol 0 */
+#define IQA_NXDN_WORDS 12       /* uint32 words of a sliced frame: symbol i the frame bits 2 i, 2 i + 1 */
+#define IQA_NXDN_INFO 14        /* uint32 words of a frame's decoded blocks: SACCH 0 .. 1, FACCH1-a 2 .. 4, FACCH1-b 5 .. 7, CAC 8 .. 13 */
+#define IQA_NXDN_RECORD 4       /* int32 values of a frame's decoded blocks */
+#define IQA_NXDN_SACCH 1        /* the bits of a frame's class mask */
+#define IQA_NXDN_FACCH1_A 2
+#define IQA_NXDN_FACCH1_B 4
+#define IQA_NXDN_CAC 8
+/* The levels and the descrambled bits of K frame sync hits.  plane_dev: int32[n], iqa_ident_integrate's output at 4800 or 2400
+ * symbols/s (|v| <= 64 * 65534).  hits_dev: int64[K][2], (m, s): m where sync symbol 0 ends, s the sign of the hit (negative:
+ * -1, the same word with the spectrum inverted; else +1).  offsets (host): the IQA_NXDN_OFFSETS sample offsets of the symbols
+ * 0 .. 191, ascending in steps of at most IQA_IDENT_MAX_SPS + 1, o[0] = 0.  valid = 0 if m + o[0] < 0, else the number of i
+ * with m + o[i] < n.  The frame sync word 0xCDF59 holds inner levels (s_i in -3, -1, 1, 3; sum s_i = 0, sum s_i^2 = 74), so
+ * the levels are the least squares fit of x_i = plane[m + o[i]], i = 0 .. 9: with P = sum x_i and Q = sum s_i x_i, Dc = 37 P
+ * and A = s 15 Q, 370 times the DC and the outer level; both 0 where valid < 10.  Symbol i < valid reads as
+ * d = s (370 plane[m + o[i]] - Dc): its first bit (d < 0), its second (3 |d| >= 2 A); from symbol 10 on the first bit is
+ * inverted where the scrambler's bit is 1 (one bit per symbol, 0 0 1 0 0 1 1 1 0 and then b[k] = b[k - 5] ^ b[k - 9]); every
+ * other bit is 0.  bits_dev: uint32[K][12], the first sent bit the MSB of word 0.  levels_dev: int64[K][3]: A, Dc, valid.
+ * Every instant is checked against 0 .. n - 1 before it is read.  n <= 2^30, K <= 2^20.  n = 0 or K = 0 returns IQA_OK and
+ * touches no pointer. */
+int iqa_nxdn_slice(const void *plane_dev, int64_t n, const void *hits_dev, int64_t K, const int32_t offsets[IQA_NXDN_OFFSETS],
+                   void *bits_dev, void *levels_dev, void *stream);
+/* The blocks of K sliced frames, by class mask (classes_dev: uint8[K]): IQA_NXDN_SACCH the frame bits 36 .. 95 (36 steps,
+ * coded bit j punctured where j mod 6 = 5, interleave 12 x 5), IQA_NXDN_FACCH1_A the bits 96 .. 239 and IQA_NXDN_FACCH1_B the
+ * bits 240 .. 383 (96 steps, j mod 4 = 1, 9 x 16), IQA_NXDN_CAC alone the bits 36 .. 335 (175 steps, j mod 14 = 3 or 11,
+ * 12 x 25); the p-th coded bit that is sent travels as channel bit C (p mod D) + p / D of its block.  Each block goes through
+ * the 16-state Viterbi decoder of iqa_ysf_fich's code (g1 of step t the coded bit 2 t, g2 the bit 2 t + 1; the trellis starts
+ * and ends in state 0; Hamming metric, a punctured bit counts 0 on every branch; on equal metrics the predecessor with the
+ * smaller state index survives).  A mask over 15, or IQA_NXDN_CAC with another bit, reads nothing and is recorded as 0.
+ * info_dev: uint32[K][14]: SACCH words 0 .. 1, FACCH1-a 2 .. 4, FACCH1-b 5 .. 7, CAC 8 .. 13, the first decoded bit the MSB of
+ * the block's first word, zeros behind the block's bits and where nothing is read.  rec_dev: int32[K][4]: the mask, the metric
+ * of the SACCH or the CAC, of FACCH1-a, of FACCH1-b (channel bits changed; 0 where the block is not read).  K <= 2^20.  K = 0
+ * returns IQA_OK and touches no pointer. */
+int iqa_nxdn_decode(const void *bits_dev, const void *classes_dev, int64_t K, void *info_dev, void *rec_dev, void *stream);
+
+/* ------------------------------------------------------------------------- *
  * Carrier squelch of a run's targets (--squelch)       *
  * ------------------------------------------------------------------------- */
 

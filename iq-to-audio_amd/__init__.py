@@ -27,12 +27,14 @@ from . import _native as native  # noqa: F401
 from .decoders import Decoder, DecoderStats, create_decoder  # noqa: F401
 from .describe import ChannelDescriber, ChannelDescription, DescribeResult  # noqa: F401
 from .dsp_plan import KEYING_BAUDS, GatePlan, IdentPlan, plan_dmr, plan_flex, plan_gate, plan_ident, plan_keying, plan_p25, plan_ysf  # noqa: F401
+from .dsp_plan import NxdnPlan, plan_nxdn  # noqa: F401
 from .find import ChannelFinder, FindResult, FoundChannel, find_channels  # noqa: F401
 from .keying import ChannelKeying, KeyingResult  # noqa: F401
 from .identify import ChannelProtocol, ProtocolResult  # noqa: F401
 from .dmr import DmrBurst, DmrCall, DmrDecoder, DmrResult  # noqa: F401
 from .p25 import P25Call, P25Decoder, P25Frame, P25Result, P25Tsbk  # noqa: F401
 from .ysf import YsfChannel, YsfDecoder, YsfFrame, YsfResult, YsfTransmission  # noqa: F401
+from .nxdn import NxdnCall, NxdnChannel, NxdnControl, NxdnDecoder, NxdnFrame, NxdnResult  # noqa: F401
 from .flex import FlexDecoder, FlexPage, FlexResult  # noqa: F401
 from .gate import CarrierGate, CarrierSquelch, GateResult, Transmission  # noqa: F401
 from .processing import (  # noqa: F401

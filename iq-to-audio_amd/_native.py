@@ -215,6 +215,8 @@ _SIGNATURES = {
     "iqa_ysf_slice": (ctypes.c_int, [c_void_p, c_int64, c_void_p, c_int64, ctypes.POINTER(c_int32), c_void_p, c_void_p, c_void_p]),
     "iqa_ysf_fich": (ctypes.c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
     "iqa_ysf_decode": (ctypes.c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
+    "iqa_nxdn_slice": (ctypes.c_int, [c_void_p, c_int64, c_void_p, c_int64, ctypes.POINTER(c_int32), c_void_p, c_void_p, c_void_p]),
+    "iqa_nxdn_decode": (ctypes.c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
     "iqa_gate_cells": (c_int64, [c_int64, c_int64]),
     "iqa_gate_power": (ctypes.c_int, [c_void_p, c_int64, c_int64, c_int32, c_void_p, c_void_p]),
     "iqa_gate_add_cells": (ctypes.c_int, [c_void_p, c_int64, c_void_p, c_void_p]),

@@ -1,5 +1,5 @@
-// protocol.h -- what the kernels of the second pass's protocol layers share (ident.hip, flex.hip, dmr.hip, p25.hip, ysf.hip; DESIGN.md
-// section 27), for gfx950: the bits of a word record, the sync word's levels, the Golay code over 0xC75, the workgroup minimum,
+// protocol.h -- what the kernels of the second pass's protocol layers share (ident.hip, flex.hip, dmr.hip, p25.hip, ysf.hip, nxdn.hip;
+// DESIGN.md section 27), for gfx950: the bits of a word record, the sync word's levels, the Golay code over 0xC75, the workgroup minimum,
 // the slicing of a four-level symbol against the levels of its sync word, and the host checks of the entry points.
 //
 // Words and codes.  A record is u32 words with the first sent bit the MSB of word 0 (pl_bit).  A 24-symbol sync word is 48 bits,

@@ -1217,6 +1217,38 @@ def plan_ysf(fs_ch: float) -> YsfPlan:
     return YsfPlan(fs_ch=ident.fs_ch, sps=ident.sps, offsets=offsets, ident=ident)
 
 
+# ---- NXDN frame decoding plan (--find-nxdn) --------------------------------
+
+NXDN_OFFSETS = 192  # o[i], i = 0 .. 191: the symbols of one frame
+NXDN_WORDS = 12  # uint32 words of a sliced frame: symbol i the frame bits 2 i, 2 i + 1
+NXDN_INFO = 14  # uint32 words of a frame's decoded blocks: SACCH 0 .. 1, FACCH1-a 2 .. 4, FACCH1-b 5 .. 7, CAC 8 .. 13
+NXDN_RECORD = 4  # int32 values of a frame's decoded blocks
+NXDN_RATES = (4800, 2400)  # symbols/s
+
+
+@dataclass(frozen=True)
+class NxdnPlan:
+    fs_ch: float
+    rate: int  # 4800 or 2400 symbols/s
+    sps: float  # fs_ch / rate
+    offsets: tuple  # o[i] = rint(i sps), i = 0 .. 191 (half-even, float64)
+    ident: IdentPlan  # section 25's plan at ``rate``
+
+    def o(self, i: int) -> int:
+        return self.offsets[i]
+
+
+def plan_nxdn(fs_ch: float, rate: int = 4800) -> NxdnPlan:
+    """The sample offsets of the symbols of an NXDN frame behind the end of sync symbol 0 at the channel rate ``fs_ch`` and
+    ``rate`` symbols/s (4800 or 2400), and section 25's plan at that rate.  ``ValueError`` for another rate and unless
+    4 <= sps <= 224 (``plan_ident``'s limits)."""
+    if rate not in NXDN_RATES:
+        raise ValueError(f"NXDN is sent at 4800 or 2400 symbols/s, not {rate}")
+    ident = plan_ident(fs_ch, int(rate))
+    offsets = tuple(int(np.rint(i * ident.sps)) for i in range(NXDN_OFFSETS))
+    return NxdnPlan(fs_ch=ident.fs_ch, rate=int(rate), sps=ident.sps, offsets=offsets, ident=ident)
+
+
 # ---- carrier squelch plan (--squelch; DESIGN.md section 24) --------------------------------------
 
 GATE_CELL = 256  # IQA_GATE_CELL: samples to a cell, counted on the absolute position

@@ -267,9 +267,10 @@ def find_channels(path, *, center_freq: float | None = None, input_format: str |
     channels among them (section 26); ``dmr=True`` (``find_layers.FIND_EVERY_BRANCH``: with ``identify=True``, and without ``flex``
     if so wished) decodes the data bursts of the channels that carry DMR sync words (section 29), ``p25=True`` likewise the
     NIDs, link control and TSBKs of those that carry P25 frame sync words (section 31), ``ysf=True`` the FICH and the callsigns
-    of those that carry YSF frame sync words (section 32).  Returns the ``FindResult``
+    of those that carry YSF frame sync words (section 32), ``nxdn=True`` the LICH, the calls and the control messages of those
+    that carry NXDN frame sync words at either symbol rate (section 34).  Returns the ``FindResult``
     alone without a layer, else a tuple of it and every layer's result in that order: ``DescribeResult``, ``KeyingResult``,
-    ``ProtocolResult``, ``FlexResult``, ``DmrResult``, ``P25Result``, ``YsfResult``."""
+    ``ProtocolResult``, ``FlexResult``, ``DmrResult``, ``P25Result``, ``YsfResult``, ``NxdnResult``."""
     layers = active_layers({layer.name: options.pop(layer.name, False) for layer in FIND_LAYERS + FIND_EVERY_BRANCH})
     path = Path(path)
     info = iqio.probe_capture(path, input_format=input_format, input_container=input_container, input_sample_rate=input_sample_rate)

@@ -1,10 +1,10 @@
 """The layers of the second pass over a capture: what ``--find-describe``, ``--find-decode``, ``--find-identify``,
-``--find-flex``, ``--find-dmr``, ``--find-p25`` and ``--find-ysf`` add to the finder's channel list (DESIGN.md sections 22, 23, 25, 26, 29,
-31 and 32).
+``--find-flex``, ``--find-dmr``, ``--find-p25``, ``--find-ysf`` and ``--find-nxdn`` add to the finder's channel list (DESIGN.md sections
+22, 23, 25, 26, 29, 31, 32 and 34).
 
 ``FIND_LAYERS`` lists the chain, in order: every row needs the row in front of it.  ``FIND_BRANCHES`` lists the layers that
 hang off one row of the chain (``needs``) and off nothing else; ``FIND_ALL_BRANCHES`` is that list with ``p25`` added, and
-``FIND_EVERY_BRANCH`` that one with the branches added since (``ysf``; NXDN will be a row there): it is the one that is looped
+``FIND_EVERY_BRANCH`` that one with the branches added since (``ysf``, ``nxdn``; the next is a row there): it is the one that is looped
 over, and a test that finds its row by name need not be touched by the next.  ``find_channels``, ``ChannelDescriber`` and the CLI read a
 layer's keyword, flag, result and file suffix from its row; a new layer is a row here, a keyword on ``ChannelDescriber`` and
 its own module ("Adding a layer to the second pass").  Nothing heavy is imported here: the CLI reads the tables
@@ -71,6 +71,11 @@ FIND_EVERY_BRANCH = FIND_ALL_BRANCHES + (
               "Fusion) frame sync words: the FICH and the callsigns of the data channels, one line per transmission (source, "
               "destination, repeater, mode, duration), also written to <capture stem>.ysf.json.  No voice.  Implies "
               "--find-identify.", needs="identify"),
+    FindLayer("nxdn", "find_nxdn", 34, lambda d, fc, fs_ch: d.nxdn_result(fc), "nxdn", False,
+              "Find, describe, key and identify the channels, and decode the frames of every channel that carries NXDN frame "
+              "sync words at 4800 or 2400 symbols/s: the LICH, the SACCH, the FACCH1s and the outbound CAC, one line per call "
+              "(RAN, source, destination, call type, cipher, duration) and per distinct control message, also written to "
+              "<capture stem>.nxdn.json.  No voice.  Implies --find-identify.", needs="identify"),
 )
 
 
