@@ -26,16 +26,14 @@
 //     info: u32[14]: SACCH words 0 .. 1, FACCH1-a 2 .. 4, FACCH1-b 5 .. 7, CAC 8 .. 13, a block's first bit the MSB of its first
 //     word, zeros elsewhere; rec: int32[4] = the mask, the metric of the SACCH or the CAC, of FACCH1-a, of FACCH1-b
 //
-// k_nxdn_slice is one wave per hit: its lanes gather the 192 instants in three strided rounds, each checked against [0, n) before
-// it is read; P, Q and valid are wave reductions; 12 lanes pack the words from LDS.  The decoder (n_viterbi) is ysf.hip's
-// layout with an erasure mask: one trellis in sixteen lanes, a state to a lane, add-compare-select reading the two
-// predecessors' metrics by a shuffle inside the sixteen, a step's survivor bit bit t mod 32 of register t / 32 of its lane, the
-// traceback reading the bit of the state it stands in by the same shuffle.  k_nxdn_decode is a wave to a frame: the lanes
-// 0 .. 15 run the SACCH or the CAC, 16 .. 31 and 32 .. 47 the two FACCH1s, 48 .. 63 nothing (0 steps).  The mask is the same in
-// the whole wave, so the wave takes one of three sizes of the decoder: six survivor words with a CAC, three with a FACCH1, two
-// for a SACCH alone.  Every shuffle stands outside the conditions on lanes, and no lane leaves before the barrier.  LDS holds
-// only the frame's words, written before the one barrier and read after it.  Plain C++ stores, no inline assembly, no atomics,
-// no mutable statics.
+// k_nxdn_slice is protocol.h's pl_slice_frame on NxdnSlice, one wave per hit: three whole rounds, the scrambler bit of a symbol
+// from a constexpr table, 12 lanes pack the words.  The code, its decoder of one trellis in sixteen lanes (pl_viterbi16, with
+// erasures: nx_fetch says which bits of a step were sent) and the rule for a frame past K (pl_frame) are protocol.h's as well.
+// k_nxdn_decode is a wave to a frame: the lanes 0 .. 15 run the SACCH or the CAC, 16 .. 31 and 32 .. 47 the two FACCH1s,
+// 48 .. 63 nothing (0 steps).  The mask is the same in the whole wave, so the wave takes one of three sizes of the decoder: six
+// survivor words with a CAC, three with a FACCH1, two for a SACCH alone.  No lane leaves before the barrier.  LDS holds only the
+// frame's words, written before the one barrier and read after it.  Plain C++ stores, no inline assembly, no atomics, no mutable
+// statics.
 #include "protocol.h"
 
 namespace iqa {
@@ -48,9 +46,6 @@ constexpr int NX_INFO = IQA_NXDN_INFO;        // 14
 constexpr int NX_REC = IQA_NXDN_RECORD;       // 4
 constexpr int NX_SYNC_SYMBOLS = 10;
 constexpr unsigned NX_SYNC = 0xCDF59u;
-constexpr long long NX_SCALE = 370;
-constexpr int NX_GROUP = 16;  // lanes of a trellis: its states
-constexpr int NX_FAR = 1000;  // the metric of a state that cannot be reached yet: above every real one (300 at the most)
 constexpr int NX_SCRAMBLED = NX_OFFSETS - NX_SYNC_SYMBOLS;  // 182 scrambler bits
 
 static_assert(NX_ROUNDS * NX_WAVE == NX_OFFSETS && 2 * NX_OFFSETS == 32 * NX_WORDS, "192 symbols: three rounds of a wave, 12 words");
@@ -59,26 +54,6 @@ static_assert(NX_INFO == 2 + 3 + 3 + 6 && NX_REC == 4, "two words to the SACCH, 
 struct NxdnOffsets {
     int o[NX_OFFSETS];
 };
-
-// the level of sync symbol i: the dibits 01 +3, 00 +1, 10 -1, 11 -3
-__host__ __device__ constexpr int nx_sync_level(int i)
-{
-    const unsigned two = (NX_SYNC >> (2 * (NX_SYNC_SYMBOLS - 1 - i))) & 3u;
-    return two == 1u ? 3 : two == 0u ? 1 : two == 2u ? -1 : -3;
-}
-
-constexpr int nx_sync_sum(int power)
-{
-    int sum = 0;
-    for (int i = 0; i < NX_SYNC_SYMBOLS; ++i) {
-        const int s = nx_sync_level(i);
-        sum += power == 2 ? s * s : power == 1 ? s : s < 0 ? -s : s;
-    }
-    return sum;
-}
-static_assert(nx_sync_sum(1) == 0 && nx_sync_sum(2) == 74, "sum s_i = 0 and sum s_i^2 = 74: the fit is DC = P / 10, L = s Q / 74");
-static_assert(NX_SCALE == 37 * NX_SYNC_SYMBOLS && NX_SCALE * 3 == 15 * 74, "at the scale 370: Dc = 37 P, A = s 15 Q");
-static_assert(15LL * nx_sync_sum(0) * PL_V_MAX * 3 < (1LL << 50) && NX_SCALE * PL_V_MAX * 2 * 3 < (1LL << 50), "15 Q, 370 x - Dc and 3 |d| stay far inside int64");
 
 // ---- the scrambler ------------------------------------------------------------------------------------------------------------------
 
@@ -117,27 +92,31 @@ static_assert(NX_SCRAMBLE_HOST.mask[0] == 0x00000082u && NX_SCRAMBLE_HOST.mask[1
               "the scrambler as a mask over the 48 bytes of a frame");
 __device__ const NxScramble NX_SCRAMBLE = nx_scramble();
 
-// ---- the convolutional code, its puncturing and its interleave -------------------------------------------------------------------------
+// ---- the slicer -----------------------------------------------------------------------------------------------------------------------
 
-// the dibit g1 << 1 | g2 that the input d sends from the state d1 << 3 | d2 << 2 | d3 << 1 | d4
-__host__ __device__ constexpr unsigned nx_branch(unsigned state, unsigned d)
-{
-    const unsigned d1 = (state >> 3) & 1u, d2 = (state >> 2) & 1u, d3 = (state >> 1) & 1u, d4 = state & 1u;
-    return (d ^ d3 ^ d4) << 1 | (d ^ d1 ^ d2 ^ d4);
-}
+// protocol.h's slicer on the levels of the sync word: Dc = 37 P, A = s 15 Q at the scale 370; the scrambler inverts a symbol's sign
+struct NxdnSlice {
+    static constexpr int OFFSETS = NX_OFFSETS, WORDS = NX_WORDS, SYNC_SYMBOLS = NX_SYNC_SYMBOLS, OUTER = 3;
+    static constexpr long long SCALE = 370, A_Q = 15, A_P = 0, D_P = 37, D_Q = 0;
+    __host__ __device__ static constexpr int weight(int i) { return pl_sync_level(NX_SYNC, NX_SYNC_SYMBOLS, i); }
+    __device__ static unsigned flip(int i) { return ((NX_SCRAMBLE.sym[i >> 5] >> (i & 31)) & 1u) << 1; }
+};
 
-// the ten sent bits of the input 1, 0, 0, 0, 0
-constexpr unsigned nx_impulse()
+constexpr int nx_sync_sum(int power)
 {
-    unsigned state = 0, sent = 0;
-    for (int t = 0; t < 5; ++t) {
-        const unsigned d = t == 0 ? 1u : 0u;
-        sent = sent << 2 | nx_branch(state, d);
-        state = d << 3 | state >> 1;
+    int sum = 0;
+    for (int i = 0; i < NX_SYNC_SYMBOLS; ++i) {
+        const int s = NxdnSlice::weight(i);
+        sum += power == 2 ? s * s : power == 1 ? s : s < 0 ? -s : s;
     }
-    return sent;
+    return sum;
 }
-static_assert(nx_impulse() == 0x35Bu, "the input 1 0 0 0 0 sends 11 01 01 10 11");
+static_assert(nx_sync_sum(1) == 0 && nx_sync_sum(2) == 74, "sum s_i = 0 and sum s_i^2 = 74: the fit is DC = P / 10, L = s Q / 74");
+static_assert(NxdnSlice::SCALE == NxdnSlice::D_P * NX_SYNC_SYMBOLS && NxdnSlice::SCALE * 3 == NxdnSlice::A_Q * 74, "at the scale 370: Dc = 37 P, A = s 15 Q");
+static_assert(NxdnSlice::A_Q * nx_sync_sum(0) * PL_V_MAX * 3 < (1LL << 50) && NxdnSlice::SCALE * PL_V_MAX * 2 * 3 < (1LL << 50),
+              "15 Q, 370 x - Dc and 3 |d| stay far inside int64");
+
+// ---- the convolutional code, its puncturing and its interleave -------------------------------------------------------------------------
 
 // A block's coder: STEPS trellis steps; of every PERIOD coded bits those at Q0 and Q1 are not sent (Q1 = PERIOD: one alone);
 // the p-th sent bit is channel bit C (p mod D) + p / D of the D C bits from frame bit FIRST on.
@@ -195,104 +174,20 @@ __device__ __forceinline__ unsigned nx_fetch(const unsigned *w, int first, int t
     return out;
 }
 
-// The decoder of one block in the sixteen lanes that the caller's lane belongs to: ``steps`` trellis steps (the same in all
-// sixteen; 0: nothing is read), step t from ``fetch(t)`` (nx_fetch's form).  out: decoded bit t is bit 31 - t mod 32 of word
-// t / 32 (the four tail bits are 0: the path ends in state 0), zeros behind.  Returns the metric of the surviving path.  Every
-// lane of the wave calls it.
-template <int NW, class Fetch>
-__device__ __forceinline__ int n_viterbi(int steps, Fetch fetch, unsigned (&out)[NW])
-{
-    const unsigned state = threadIdx.x & (NX_GROUP - 1), input = state >> 3;
-    const int from = static_cast<int>((state & 7u) << 1);  // the smaller predecessor; the other is from + 1
-    const unsigned sent0 = nx_branch(from, input), sent1 = nx_branch(from + 1, input);
-    int metric = state == 0 ? 0 : NX_FAR;
-    unsigned surv[NW];
-#pragma unroll
-    for (int w = 0; w < NW; ++w) {
-        unsigned word = 0;
-#pragma unroll 1
-        for (int b = 0; b < 32; ++b) {
-            const int t = 32 * w + b;
-            const bool live = t < steps;
-            const unsigned got = live ? fetch(t) : 0u;
-            const unsigned rx = got & 3u, keep = got >> 2;  // (a punctured bit adds 0 to both branches)
-            const int m0 = __shfl(metric, from, NX_GROUP) + static_cast<int>(pl_popcount((rx ^ sent0) & keep));
-            const int m1 = __shfl(metric, from + 1, NX_GROUP) + static_cast<int>(pl_popcount((rx ^ sent1) & keep));
-            const bool second = m1 < m0;  // (equal: the smaller state index survives)
-            metric = live ? (second ? m1 : m0) : metric;
-            word |= (live && second ? 1u : 0u) << b;
-        }
-        surv[w] = word;
-    }
-    const int total = __shfl(metric, 0, NX_GROUP);
-    unsigned at = 0;  // the state the path stands in behind step t: the same in all sixteen lanes
-#pragma unroll
-    for (int w = NW - 1; w >= 0; --w) {
-        unsigned word = 0;
-#pragma unroll 1
-        for (int b = 31; b >= 0; --b) {
-            const bool live = 32 * w + b < steps;
-            const unsigned bit = (static_cast<unsigned>(__shfl(static_cast<int>(surv[w]), static_cast<int>(at), NX_GROUP)) >> b) & 1u;
-            word |= (live ? at >> 3 : 0u) << (31 - b);
-            at = live ? ((at & 7u) << 1 | bit) : at;
-        }
-        out[w] = word;
-    }
-    return steps > 0 ? total : 0;
-}
-
 __global__ __launch_bounds__(NX_WAVE) void k_nxdn_slice(const int *__restrict__ plane, long long n, const long long *__restrict__ hits,
                                                         NxdnOffsets off, unsigned *__restrict__ bits_out, long long *__restrict__ levels_out)
 {
-    __shared__ unsigned char s_two[NX_OFFSETS];
-    const int lane = threadIdx.x;
-    const long long id = blockIdx.x;
-    const PlHit hit = pl_hit(hits + 2 * id);
-    const long long reach = hit.m >= 0 ? n : 0;  // o[0] = 0 and o ascends: a hit in front of the plane reads nothing, one inside it a prefix
-    // the gather: every instant is checked against [0, n) before it is read
-    int y[NX_ROUNDS];
-    int count = 0;
-#pragma unroll
-    for (int p = 0; p < NX_ROUNDS; ++p) {
-        bool inside;
-        y[p] = pl_read(plane, reach, hit.m + off.o[p * NX_WAVE + lane], inside);
-        count += inside ? 1 : 0;
-    }
-    long long sum = lane < NX_SYNC_SYMBOLS ? y[0] : 0;
-    long long weighted = lane < NX_SYNC_SYMBOLS ? static_cast<long long>(nx_sync_level(lane)) * y[0] : 0;
-    sum = wave_sum(sum);
-    weighted = wave_sum(weighted);
-    const int valid = wave_sum(count);
-    const bool read = valid >= NX_SYNC_SYMBOLS;
-    const long long amp = read ? hit.s * 15 * weighted : 0, dc = read ? 37 * sum : 0;
-#pragma unroll
-    for (int p = 0; p < NX_ROUNDS; ++p) {
-        const int idx = p * NX_WAVE + lane;
-        unsigned two = pl_dibit(hit.s * (NX_SCALE * y[p] - dc), amp);
-        two ^= ((NX_SCRAMBLE.sym[idx >> 5] >> (idx & 31)) & 1u) << 1;  // (the scrambler inverts the symbol's sign)
-        if (!read || idx >= valid) two = 0;
-        s_two[idx] = static_cast<unsigned char>(two);
-    }
-    __syncthreads();
-    if (lane < NX_WORDS) bits_out[NX_WORDS * id + lane] = pl_pack_dibits(s_two, lane);
-    if (lane == 0) {
-        long long *e = levels_out + 3 * id;
-        e[0] = amp;
-        e[1] = dc;
-        e[2] = valid;
-    }
+    pl_slice_frame<NxdnSlice>(plane, n, hits, off.o, bits_out, levels_out);
 }
 
 // a frame to a wave: the lanes 0 .. 15 take the SACCH or the CAC, 16 .. 31 FACCH1-a, 32 .. 47 FACCH1-b, 48 .. 63 nothing
 __global__ __launch_bounds__(NX_WAVE) void k_nxdn_decode(const unsigned *__restrict__ bits, const unsigned char *__restrict__ classes, long long count,
                                                          unsigned *__restrict__ info_out, int *__restrict__ rec_out)
 {
-    __shared__ unsigned s_w[NX_GROUP];
-    const int lane = threadIdx.x, group = lane / NX_GROUP, sub = lane % NX_GROUP;
-    const long long want = blockIdx.x;
-    const bool mine = want < count;
-    const long long id = mine ? want : count - 1;  // (a frame past the last reads the last and writes nothing)
-    if (lane < NX_GROUP) s_w[lane] = lane < NX_WORDS ? bits[NX_WORDS * id + lane] : 0u;
+    __shared__ unsigned s_w[PL_GROUP];
+    const int lane = threadIdx.x, group = lane / PL_GROUP, sub = lane % PL_GROUP;
+    const auto [mine, id] = pl_frame(blockIdx.x, count);
+    if (lane < PL_GROUP) s_w[lane] = lane < NX_WORDS ? bits[NX_WORDS * id + lane] : 0u;
     __syncthreads();
     const unsigned *w = s_w;
     const int given = classes[id];
@@ -301,7 +196,7 @@ __global__ __launch_bounds__(NX_WAVE) void k_nxdn_decode(const unsigned *__restr
     unsigned out[6] = {0u, 0u, 0u, 0u, 0u, 0u};
     int metric;
     if (cac) {
-        metric = n_viterbi<6>(group == 0 ? NxCac::STEPS : 0, [w](int t) { return nx_fetch<NxCac>(w, NX_CAC_FIRST, t); }, out);
+        metric = pl_viterbi16<6, true>(group == 0 ? NxCac::STEPS : 0, [w](int t) { return nx_fetch<NxCac>(w, NX_CAC_FIRST, t); }, out);
     } else {
         const int steps = group == 0 ? (cls & IQA_NXDN_SACCH ? NxSacch::STEPS : 0)
                                      : group == 1 ? (cls & IQA_NXDN_FACCH1_A ? NxFacch1::STEPS : 0)
@@ -309,7 +204,7 @@ __global__ __launch_bounds__(NX_WAVE) void k_nxdn_decode(const unsigned *__restr
         const int first = group == 2 ? NX_FACCH1_B_FIRST : NX_FACCH1_A_FIRST;
         if (cls & (IQA_NXDN_FACCH1_A | IQA_NXDN_FACCH1_B)) {
             unsigned three[3];
-            metric = n_viterbi<3>(steps, [=](int t) {
+            metric = pl_viterbi16<3, true>(steps, [=](int t) {
                 const unsigned sacch = nx_fetch<NxSacch>(w, NX_SACCH_FIRST, t < NxSacch::STEPS ? t : 0);
                 const unsigned facch = nx_fetch<NxFacch1>(w, first, t);
                 return group == 0 ? sacch : facch;
@@ -317,11 +212,11 @@ __global__ __launch_bounds__(NX_WAVE) void k_nxdn_decode(const unsigned *__restr
             out[0] = three[0], out[1] = three[1], out[2] = three[2];
         } else {
             unsigned two[2];
-            metric = n_viterbi<2>(steps, [w](int t) { return nx_fetch<NxSacch>(w, NX_SACCH_FIRST, t); }, two);
+            metric = pl_viterbi16<2, true>(steps, [w](int t) { return nx_fetch<NxSacch>(w, NX_SACCH_FIRST, t); }, two);
             out[0] = two[0], out[1] = two[1];
         }
     }
-    const int metric_0 = __shfl(metric, 0), metric_a = __shfl(metric, NX_GROUP), metric_b = __shfl(metric, 2 * NX_GROUP);
+    const int metric_0 = __shfl(metric, 0), metric_a = __shfl(metric, PL_GROUP), metric_b = __shfl(metric, 2 * PL_GROUP);
     if (mine) {
         unsigned *e = info_out + NX_INFO * id;
         if (group == 0 && sub < 8) {

@@ -29,12 +29,11 @@
 //   info: u32[9]: classes 1, 2 the 144 bits in words 0 .. 4; class 3 the 96 bits of block b in words 3 b .. 3 b + 2
 //   rec: int32[8] = class, then (corrected words, refused or unmatched words, bits changed) or the three block metrics; 0s
 //
-// k_p25_slice is one wave per hit: its lanes gather the 864 instants in fourteen strided rounds, each checked against [0, n)
-// before it is read; P, Q and valid are wave reductions; 54 lanes pack the words from LDS.  k_p25_nid and k_p25_decode are a
-// workgroup of 256 per frame: 256 codewords of the BCH code to a thread (T_hi[t] ^ T_lo[j]: the code is linear), 16 of the Golay
-// code, with a minimum over (distance, data) through LDS; a thread per Hamming word; a thread per trellis block with its
-// survivors in LDS.  The sync word's signs, the Golay encoder, the minimum, the dibit rule, the packing and the host prologue are
-// protocol.h's.  Plain C++ stores, no inline assembly, no atomics, no mutable statics.
+// k_p25_slice is protocol.h's pl_slice_frame on P25Slice, one wave per hit: fourteen strided rounds, 54 lanes pack the words.
+// k_p25_nid and k_p25_decode are a workgroup of 256 per frame: 256 codewords of the BCH code to a thread (T_hi[t] ^ T_lo[j]: the
+// code is linear), 16 of the Golay code, with a minimum over (distance, data) through LDS; a thread per Hamming word; a thread
+// per trellis block with its survivors in LDS.  The sync word's signs, the Golay encoder, the minimum and the host prologue are
+// protocol.h's too.  Plain C++ stores, no inline assembly, no atomics, no mutable statics.
 #include "protocol.h"
 
 namespace iqa {
@@ -49,13 +48,20 @@ constexpr int P5_REC = IQA_P25_RECORD;       // 8
 constexpr int P5_SYNC_SYMBOLS = 24;
 constexpr unsigned long long P5_SYNC = 0x5575F5FF77FFull;
 
-static_assert(2 * P5_OFFSETS == 32 * P5_WORDS && P5_ROUNDS == 14, "864 symbols: fourteen rounds of a wave, 54 words");
-static_assert(286 * PL_V_MAX * 2 * 24 * 3 < (1LL << 50), "286 y - Dc and 3 |d| stay far inside int64");
-
 struct P25Offsets {
     int o[P5_OFFSETS];
 };
 
+// protocol.h's slicer on the signs of the all-outer sync word: A = s (12 Q + P), Dc = 12 P + Q at the scale 286
+struct P25Slice {
+    static constexpr int OFFSETS = P5_OFFSETS, WORDS = P5_WORDS, SYNC_SYMBOLS = P5_SYNC_SYMBOLS, OUTER = 1;
+    static constexpr long long SCALE = 286, A_Q = 12, A_P = 1, D_P = 12, D_Q = 1;
+    __host__ __device__ static constexpr int weight(int i) { return pl_sync_positive(P5_SYNC, i) ? 1 : -1; }
+    __device__ static constexpr unsigned flip(int) { return 0u; }
+};
+
+static_assert(2 * P5_OFFSETS == 32 * P5_WORDS && P5_ROUNDS == 14, "864 symbols: fourteen rounds of a wave, 54 words");
+static_assert(P25Slice::SCALE * PL_V_MAX * 2 * P5_SYNC_SYMBOLS * 3 < (1LL << 50), "286 y - Dc and 3 |d| stay far inside int64");
 static_assert(pl_sync_ups(P5_SYNC) == 11, "the sync word holds eleven +3 and thirteen -3: 12 Q + P = 286 s L and 12 P + Q = 286 DC");
 
 // ---- BCH(63,16,23) over GF(64) / x^6 + x + 1 ------------------------------------------------------------------------------------
@@ -238,47 +244,7 @@ static_assert(2 * (679 + 679 / 35) + 1 < 32 * P5_WORDS, "data bit 1359, the last
 __global__ __launch_bounds__(P5_WAVE) void k_p25_slice(const int *__restrict__ plane, long long n, const long long *__restrict__ hits,
                                                        P25Offsets off, unsigned *__restrict__ bits_out, long long *__restrict__ levels_out)
 {
-    __shared__ unsigned char s_two[P5_ROUNDS * P5_WAVE];
-    const int lane = threadIdx.x;
-    const long long id = blockIdx.x;
-    const PlHit hit = pl_hit(hits + 2 * id);
-    const long long reach = hit.m >= 0 ? n : 0;  // o[0] = 0 and o ascends: a hit in front of the plane reads nothing, one inside it a prefix
-    // the gather: every instant is checked against [0, n) before it is read
-    int y[P5_ROUNDS];
-    int count = 0;
-#pragma unroll
-    for (int p = 0; p < P5_ROUNDS; ++p) {
-        const int idx = p * P5_WAVE + lane;
-        y[p] = 0;
-        if (idx < P5_OFFSETS) {
-            bool inside;
-            y[p] = pl_read(plane, reach, hit.m + off.o[idx], inside);
-            count += inside ? 1 : 0;
-        }
-    }
-    long long sum = lane < P5_SYNC_SYMBOLS ? y[0] : 0;
-    long long signed_sum = 0;
-    if (lane < P5_SYNC_SYMBOLS) signed_sum = pl_sync_positive(P5_SYNC, lane) ? y[0] : -static_cast<long long>(y[0]);
-    sum = wave_sum(sum);
-    signed_sum = wave_sum(signed_sum);
-    const int valid = wave_sum(count);
-    const bool read = valid >= P5_SYNC_SYMBOLS;
-    const long long amp = read ? hit.s * (12 * signed_sum + sum) : 0, dc = read ? 12 * sum + signed_sum : 0;
-#pragma unroll
-    for (int p = 0; p < P5_ROUNDS; ++p) {
-        const int idx = p * P5_WAVE + lane;
-        unsigned two = pl_dibit(hit.s * (286LL * y[p] - dc), amp);
-        if (!read || idx >= valid) two = 0;
-        s_two[idx] = static_cast<unsigned char>(two);
-    }
-    __syncthreads();
-    if (lane < P5_WORDS) bits_out[P5_WORDS * id + lane] = pl_pack_dibits(s_two, lane);
-    if (lane == 0) {
-        long long *e = levels_out + 3 * id;
-        e[0] = amp;
-        e[1] = dc;
-        e[2] = valid;
-    }
+    pl_slice_frame<P25Slice>(plane, n, hits, off.o, bits_out, levels_out);
 }
 
 __global__ __launch_bounds__(P5_THREADS) void k_p25_nid(const unsigned *__restrict__ bits, int *__restrict__ nid_out)

@@ -29,16 +29,12 @@
 //     info: u32[12]: DCH-a in words 0 .. 5, DCH-b in 6 .. 11, the block's first bit the MSB of its first word; rec: int32[4] =
 //     the class, the metric of DCH-a, of DCH-b, 0
 //
-// k_ysf_slice is one wave per hit: its lanes gather the 480 instants in eight strided rounds, each checked against [0, n)
-// before it is read; P, Q and valid are wave reductions; 30 lanes pack the words from LDS.  The decoder (y_viterbi) holds one
-// trellis in sixteen lanes, a state to a lane, so a wave holds four: add-compare-select reads the two predecessors' metrics by
-// a shuffle inside the sixteen, a step's survivor bit is bit t mod 32 of register t / 32 of its lane (six registers for 180
-// steps), and the traceback reads the bit of the state it stands in by the same shuffle.  Lanes of one trellis share their step
-// count, and every shuffle stands outside the conditions, so no lane reads from one that is switched off.  k_ysf_fich is a wave
-// for four frames, k_ysf_decode a wave for the two blocks of two frames; a frame past K reads frame K - 1 and writes nothing,
-// and no lane leaves before the barrier.  The Golay search is sixteen lanes by 256 codewords, the minimum over (distance, data)
-// by shuffles.  LDS holds only the frames' words, written before the one barrier and read after it.  Plain C++ stores, no inline
-// assembly, no atomics, no mutable statics.
+// k_ysf_slice is protocol.h's pl_slice_frame on YsfSlice, one wave per hit: eight strided rounds, 30 lanes pack the words.  The
+// code, its decoder of one trellis in sixteen lanes (pl_viterbi16, without erasures; four survivor words for 100 steps, six for
+// 180) and the rule for a frame past K (pl_frame) are protocol.h's as well.  k_ysf_fich is a wave for four frames, k_ysf_decode a
+// wave for the two blocks of two frames; no lane leaves before the barrier.  The Golay search is sixteen lanes by 256 codewords,
+// the minimum over (distance, data) by shuffles.  LDS holds only the frames' words, written before the one barrier and read after
+// it.  Plain C++ stores, no inline assembly, no atomics, no mutable statics.
 #include "protocol.h"
 
 namespace iqa {
@@ -52,9 +48,6 @@ constexpr int Y_INFO = IQA_YSF_INFO;        // 12
 constexpr int Y_REC = IQA_YSF_RECORD;       // 4
 constexpr int Y_SYNC_SYMBOLS = 20;
 constexpr unsigned long long Y_SYNC = 0xD471C9634Dull;
-constexpr long long Y_SCALE = 584;
-constexpr int Y_GROUP = 16;   // lanes of a trellis: its states
-constexpr int Y_FAR = 1000;   // the metric of a state that cannot be reached yet: above every real one (360 at the most)
 constexpr int Y_FICH_STEPS = 100, Y_DCH_STEPS = 180, Y_DCH2_STEPS = 100;
 constexpr int Y_FICH_FIRST = 40, Y_PAYLOAD_FIRST = 240, Y_PAYLOAD_BLOCK = 144;
 
@@ -65,22 +58,25 @@ struct YsfOffsets {
     int o[Y_OFFSETS];
 };
 
-// the level of sync symbol i: the dibits 01 +3, 00 +1, 10 -1, 11 -3
-__host__ __device__ constexpr int y_sync_level(int i)
-{
-    const unsigned two = static_cast<unsigned>(Y_SYNC >> (2 * (Y_SYNC_SYMBOLS - 1 - i))) & 3u;
-    return two == 1u ? 3 : two == 0u ? 1 : two == 2u ? -1 : -3;
-}
+// protocol.h's slicer on the levels of the sync word: Dc = 31 P - 3 Q, A = s (15 Q - 9 P) at the scale 584
+struct YsfSlice {
+    static constexpr int OFFSETS = Y_OFFSETS, WORDS = Y_WORDS, SYNC_SYMBOLS = Y_SYNC_SYMBOLS, OUTER = 3;
+    static constexpr long long SCALE = 584, A_Q = 15, A_P = -9, D_P = 31, D_Q = -3;
+    __host__ __device__ static constexpr int weight(int i) { return pl_sync_level(Y_SYNC, Y_SYNC_SYMBOLS, i); }
+    __device__ static constexpr unsigned flip(int) { return 0u; }
+};
 
 constexpr int y_sync_sum(bool squares)
 {
     int sum = 0;
-    for (int i = 0; i < Y_SYNC_SYMBOLS; ++i) sum += squares ? y_sync_level(i) * y_sync_level(i) : y_sync_level(i);
+    for (int i = 0; i < Y_SYNC_SYMBOLS; ++i) sum += squares ? YsfSlice::weight(i) * YsfSlice::weight(i) : YsfSlice::weight(i);
     return sum;
 }
 static_assert(y_sync_sum(false) == 12 && y_sync_sum(true) == 124, "sum s_i = 12 and sum s_i^2 = 124: Dc = 31 P - 3 Q, A = s (15 Q - 9 P)");
-static_assert(20 * 124 - 12 * 12 == 4 * Y_SCALE && 124 == 4 * 31 && 12 == 4 * 3 && 20 * 3 == 4 * 15 && 12 * 3 == 4 * 9, "the fit, less its factor 4");
-static_assert((15 * 124 + 9 * 20) * PL_V_MAX * 3 < (1LL << 50) && Y_SCALE * PL_V_MAX * 2 * 3 < (1LL << 50), "15 Q - 9 P, 584 y - Dc and 3 |d| stay far inside int64");
+static_assert(20 * 124 - 12 * 12 == 4 * YsfSlice::SCALE && 124 == 4 * YsfSlice::D_P && 12 == -4 * YsfSlice::D_Q && 20 * 3 == 4 * YsfSlice::A_Q &&
+              12 * 3 == -4 * YsfSlice::A_P, "the fit, less its factor 4");
+static_assert((YsfSlice::A_Q * 124 - YsfSlice::A_P * 20) * PL_V_MAX * 3 < (1LL << 50) && YsfSlice::SCALE * PL_V_MAX * 2 * 3 < (1LL << 50),
+              "15 Q - 9 P, 584 y - Dc and 3 |d| stay far inside int64");
 
 // ---- Golay(24,12,8) ---------------------------------------------------------------------------------------------------------------
 
@@ -105,26 +101,6 @@ __device__ const YGolay Y_GOLAY = y_golay_tables();
 
 // ---- the convolutional code ---------------------------------------------------------------------------------------------------------
 
-// the dibit g1 << 1 | g2 that the input d sends from the state d1 << 3 | d2 << 2 | d3 << 1 | d4
-__host__ __device__ constexpr unsigned y_branch(unsigned state, unsigned d)
-{
-    const unsigned d1 = (state >> 3) & 1u, d2 = (state >> 2) & 1u, d3 = (state >> 1) & 1u, d4 = state & 1u;
-    return (d ^ d3 ^ d4) << 1 | (d ^ d1 ^ d2 ^ d4);
-}
-
-// the ten sent bits of the input 1, 0, 0, 0, 0
-constexpr unsigned y_impulse()
-{
-    unsigned state = 0, sent = 0;
-    for (int t = 0; t < 5; ++t) {
-        const unsigned d = t == 0 ? 1u : 0u;
-        sent = sent << 2 | y_branch(state, d);
-        state = d << 3 | state >> 1;
-    }
-    return sent;
-}
-static_assert(y_impulse() == 0x35Bu, "the input 1 0 0 0 0 sends 11 01 01 10 11");
-
 // the channel dibit of a block of 20 R dibits that is dibit i of the coded stream
 __host__ __device__ constexpr int y_deinterleave(int i, int rows) { return 20 * (i % rows) + i / rows; }
 
@@ -140,124 +116,28 @@ constexpr bool y_permutes(int rows)
 }
 static_assert(y_permutes(5) && y_permutes(9), "the de-interleaver is a permutation of 0 .. 99 and of 0 .. 179");
 
-// The decoder of one block in the sixteen lanes that the caller's lane belongs to: ``steps`` dibits (the same in all sixteen;
-// 0: nothing is read), dibit t from ``fetch(t)``.  out: decoded bit t is bit 31 - t mod 32 of word t / 32 (the four tail bits
-// are 0: the path ends in state 0), zeros behind.  Returns the metric of the surviving path.  Every lane of the wave calls it.
-template <int NW, class Fetch>
-__device__ __forceinline__ int y_viterbi(int steps, Fetch fetch, unsigned (&out)[NW])
-{
-    const unsigned state = threadIdx.x & (Y_GROUP - 1), input = state >> 3;
-    const int from = static_cast<int>((state & 7u) << 1);  // the smaller predecessor; the other is from + 1
-    const unsigned sent0 = y_branch(from, input), sent1 = y_branch(from + 1, input);
-    int metric = state == 0 ? 0 : Y_FAR;
-    unsigned surv[NW];
-#pragma unroll
-    for (int w = 0; w < NW; ++w) {
-        unsigned word = 0;
-#pragma unroll 1
-        for (int b = 0; b < 32; ++b) {
-            const int t = 32 * w + b;
-            const bool live = t < steps;
-            const unsigned rx = live ? fetch(t) : 0u;
-            const int m0 = __shfl(metric, from, Y_GROUP) + static_cast<int>(pl_popcount(rx ^ sent0));
-            const int m1 = __shfl(metric, from + 1, Y_GROUP) + static_cast<int>(pl_popcount(rx ^ sent1));
-            const bool second = m1 < m0;  // (equal: the smaller state index survives)
-            metric = live ? (second ? m1 : m0) : metric;
-            word |= (live && second ? 1u : 0u) << b;
-        }
-        surv[w] = word;
-    }
-    const int total = __shfl(metric, 0, Y_GROUP);
-    unsigned at = 0;  // the state the path stands in behind step t: the same in all sixteen lanes
-#pragma unroll
-    for (int w = NW - 1; w >= 0; --w) {
-        unsigned word = 0;
-#pragma unroll 1
-        for (int b = 31; b >= 0; --b) {
-            const bool live = 32 * w + b < steps;
-            const unsigned bit = (static_cast<unsigned>(__shfl(static_cast<int>(surv[w]), static_cast<int>(at), Y_GROUP)) >> b) & 1u;
-            word |= (live ? at >> 3 : 0u) << (31 - b);
-            at = live ? ((at & 7u) << 1 | bit) : at;
-        }
-        out[w] = word;
-    }
-    return steps > 0 ? total : 0;
-}
-
-// the minimum of key over the sixteen lanes of a trellis
-__device__ __forceinline__ unsigned y_group_min(unsigned key)
-{
-#pragma unroll
-    for (int w = Y_GROUP / 2; w >= 1; w >>= 1) {
-        const unsigned other = static_cast<unsigned>(__shfl_xor(static_cast<int>(key), w, Y_GROUP));
-        key = other < key ? other : key;
-    }
-    return key;
-}
-
 // the dibit at the frame bits b, b + 1 (b even) of a frame's words
 __device__ __forceinline__ unsigned y_dibit(const unsigned *w, int b) { return (w[b >> 5] >> (30 - (b & 31))) & 3u; }
 
 __global__ __launch_bounds__(Y_WAVE) void k_ysf_slice(const int *__restrict__ plane, long long n, const long long *__restrict__ hits,
                                                       YsfOffsets off, unsigned *__restrict__ bits_out, long long *__restrict__ levels_out)
 {
-    __shared__ unsigned char s_two[Y_ROUNDS * Y_WAVE];
-    const int lane = threadIdx.x;
-    const long long id = blockIdx.x;
-    const PlHit hit = pl_hit(hits + 2 * id);
-    const long long reach = hit.m >= 0 ? n : 0;  // o[0] = 0 and o ascends: a hit in front of the plane reads nothing, one inside it a prefix
-    // the gather: every instant is checked against [0, n) before it is read
-    int y[Y_ROUNDS];
-    int count = 0;
-#pragma unroll
-    for (int p = 0; p < Y_ROUNDS; ++p) {
-        const int idx = p * Y_WAVE + lane;
-        y[p] = 0;
-        if (idx < Y_OFFSETS) {
-            bool inside;
-            y[p] = pl_read(plane, reach, hit.m + off.o[idx], inside);
-            count += inside ? 1 : 0;
-        }
-    }
-    long long sum = lane < Y_SYNC_SYMBOLS ? y[0] : 0;
-    long long weighted = lane < Y_SYNC_SYMBOLS ? static_cast<long long>(y_sync_level(lane)) * y[0] : 0;
-    sum = wave_sum(sum);
-    weighted = wave_sum(weighted);
-    const int valid = wave_sum(count);
-    const bool read = valid >= Y_SYNC_SYMBOLS;
-    const long long amp = read ? hit.s * (15 * weighted - 9 * sum) : 0, dc = read ? 31 * sum - 3 * weighted : 0;
-#pragma unroll
-    for (int p = 0; p < Y_ROUNDS; ++p) {
-        const int idx = p * Y_WAVE + lane;
-        unsigned two = pl_dibit(hit.s * (Y_SCALE * y[p] - dc), amp);
-        if (!read || idx >= valid) two = 0;
-        s_two[idx] = static_cast<unsigned char>(two);
-    }
-    __syncthreads();
-    if (lane < Y_WORDS) bits_out[Y_WORDS * id + lane] = pl_pack_dibits(s_two, lane);
-    if (lane == 0) {
-        long long *e = levels_out + 3 * id;
-        e[0] = amp;
-        e[1] = dc;
-        e[2] = valid;
-    }
+    pl_slice_frame<YsfSlice>(plane, n, hits, off.o, bits_out, levels_out);
 }
 
 // four frames to a wave, one to every sixteen lanes
 __global__ __launch_bounds__(Y_WAVE) void k_ysf_fich(const unsigned *__restrict__ bits, long long count, unsigned *__restrict__ fich_out,
                                                      int *__restrict__ rec_out)
 {
-    __shared__ unsigned s_w[Y_WAVE / Y_GROUP][Y_WORDS + 2];
-    const int lane = threadIdx.x, group = lane / Y_GROUP, sub = lane % Y_GROUP;
-    const long long want = 4LL * blockIdx.x + group;
-    const bool mine = want < count;
-    const long long id = mine ? want : count - 1;  // (a frame past the last reads the last and writes nothing)
+    __shared__ unsigned s_w[Y_WAVE / PL_GROUP][Y_WORDS + 2];
+    const int lane = threadIdx.x, group = lane / PL_GROUP, sub = lane % PL_GROUP;
+    const auto [mine, id] = pl_frame(4LL * blockIdx.x + group, count);
     s_w[group][sub] = bits[Y_WORDS * id + sub];
-    s_w[group][sub + Y_GROUP] = sub + Y_GROUP < Y_WORDS ? bits[Y_WORDS * id + sub + Y_GROUP] : 0u;
+    s_w[group][sub + PL_GROUP] = sub + PL_GROUP < Y_WORDS ? bits[Y_WORDS * id + sub + PL_GROUP] : 0u;
     __syncthreads();
     const unsigned *w = s_w[group];
     unsigned out[4];
-    const int metric = y_viterbi<4>(Y_FICH_STEPS, [w](int t) { return y_dibit(w, Y_FICH_FIRST + 2 * y_deinterleave(t, 5)); }, out);
+    const int metric = pl_viterbi16<4, false>(Y_FICH_STEPS, [w](int t) { return y_dibit(w, Y_FICH_FIRST + 2 * y_deinterleave(t, 5)); }, out);
     const unsigned words[4] = {out[0] >> 8, (out[0] & 0xFFu) << 16 | out[1] >> 16, (out[1] & 0xFFFFu) << 8 | out[2] >> 24, out[2] & 0xFFFFFFu};
     unsigned data[4];
     int corrected = 0, refused = 0, changed = 0;
@@ -272,7 +152,7 @@ __global__ __launch_bounds__(Y_WAVE) void k_ysf_fich(const unsigned *__restrict_
                 best = key < best ? key : best;
             }
         }
-        const unsigned key = y_group_min(best);
+        const unsigned key = pl_group_min16(best);
         const int distance = static_cast<int>(key >> 12);
         data[j] = key & 0xFFFu;
         if (distance > 3) {
@@ -299,12 +179,10 @@ __global__ __launch_bounds__(Y_WAVE) void k_ysf_fich(const unsigned *__restrict_
 __global__ __launch_bounds__(Y_WAVE) void k_ysf_decode(const unsigned *__restrict__ bits, const unsigned char *__restrict__ classes, long long count,
                                                        unsigned *__restrict__ info_out, int *__restrict__ rec_out)
 {
-    __shared__ unsigned s_w[2][2 * Y_GROUP];
-    const int lane = threadIdx.x, slot = lane / (2 * Y_GROUP), block = (lane / Y_GROUP) & 1, sub = lane % Y_GROUP;
-    const long long want = 2LL * blockIdx.x + slot;
-    const bool mine = want < count;
-    const long long id = mine ? want : count - 1;  // (a frame past the last reads the last and writes nothing)
-    const int at = lane % (2 * Y_GROUP);
+    __shared__ unsigned s_w[2][2 * PL_GROUP];
+    const int lane = threadIdx.x, slot = lane / (2 * PL_GROUP), block = (lane / PL_GROUP) & 1, sub = lane % PL_GROUP;
+    const auto [mine, id] = pl_frame(2LL * blockIdx.x + slot, count);
+    const int at = lane % (2 * PL_GROUP);
     s_w[slot][at] = at < Y_WORDS ? bits[Y_WORDS * id + at] : 0u;
     __syncthreads();
     const unsigned *w = s_w[slot];
@@ -313,11 +191,11 @@ __global__ __launch_bounds__(Y_WAVE) void k_ysf_decode(const unsigned *__restric
     const int steps = cls == 1 || (cls == 2 && block == 0) ? Y_DCH_STEPS : cls == 3 && block == 0 ? Y_DCH2_STEPS : 0;
     const int rows = cls == 3 ? 5 : 9, part = cls == 3 ? 40 : 72, first = Y_PAYLOAD_FIRST + 72 * block;
     unsigned out[6];
-    const int metric = y_viterbi<6>(steps, [=](int t) {
+    const int metric = pl_viterbi16<6, false>(steps, [=](int t) {
         const int b = 2 * y_deinterleave(t, rows);  // the bit of the data channel; it lies in payload block b / part
         return y_dibit(w, first + Y_PAYLOAD_BLOCK * (b / part) + b % part);
     }, out);
-    const int metric_a = __shfl(metric, 0, 2 * Y_GROUP), metric_b = __shfl(metric, Y_GROUP, 2 * Y_GROUP);
+    const int metric_a = __shfl(metric, 0, 2 * PL_GROUP), metric_b = __shfl(metric, PL_GROUP, 2 * PL_GROUP);
     if (mine) {
         unsigned word = 0;
 #pragma unroll

@@ -376,13 +376,8 @@ class DmrDecoder(L.StoredTheta):
 
     plan_of = staticmethod(P.plan_dmr)
     planes = ("v",)
-
-    def _decode(self, theta) -> tuple:
-        v = I.integrate(theta, self.plan.ident, self.centre)
-        _, hits = I.search(v, self.plan.ident, PATTERNS)
-        st = decode_stream(theta, self.plan, self.centre, hits, PATTERNS, v)
-        st["hits"] = hits
-        return st, DmrResult(channels=[channel_of(st, self.plan.fs_ch, 0, 0.0, None)], sample_rate=self.plan.fs_ch)
+    patterns, result = PATTERNS, DmrResult
+    decode_stream, channel_of = staticmethod(decode_stream), staticmethod(channel_of)
 
 
 # ---- the layer of the second pass (describe.py) ---------------------------------------------------------------------------------
@@ -406,8 +401,4 @@ def dmr_result(channels, lanes, decoded, sample_rate: float, center_freq: float 
 def stage_keys(describer, j: int, lane, keep: bool) -> dict:
     """This layer's keys of ``ChannelDescriber.stages()`` for channel ``j``: ``dmr_rows`` ((m, s, kind) per burst, None where the
     channel is no DMR channel) and, with ``keep``, ``dmr_plan``, ``dmr_bits``, ``dmr_levels``, ``dmr_info`` and ``dmr_rec``."""
-    x = describer.finish_dmr()[j]
-    d = dict(dmr_rows=x.get("rows"))
-    if keep and "rows" in x:
-        d.update(dmr_plan=x["plan"], dmr_bits=x["bits"], dmr_levels=x["levels"], dmr_info=x["info"], dmr_rec=x["rec"])
-    return d
+    return L.layer_stage_keys("dmr", describer.finish_dmr()[j], ("bits", "levels", "info", "rec"), keep)

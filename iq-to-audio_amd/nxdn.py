@@ -155,22 +155,15 @@ def layer3_fields(data, whole: bool = True) -> dict:
 def slice_frames(plane, rows, plan: P.NxdnPlan) -> tuple:
     """``iqa_nxdn_slice`` on a device int32 plane for ``rows`` (int64[K][2]: m, s): (bits uint32[K][12], descrambled, levels
     int64[K][3]: A, Dc, valid) on the host.  ``ValueError`` for a sign other than +-1, before anything is launched."""
-    rows = np.ascontiguousarray(np.asarray(rows, dtype=np.int64).reshape(-1, 2))
-    if rows.size and not np.isin(rows[:, 1], (-1, 1)).all():
-        raise ValueError("iqa_nxdn_slice: a hit's sign must be +-1")
-    return L.slice_hits("iqa_nxdn_slice", plane, rows, plan.offsets, P.NXDN_WORDS)
+    return L.slice_frames("iqa_nxdn_slice", plane, rows, plan.offsets, P.NXDN_WORDS)
 
 
 def decode_frames(bits, classes) -> tuple:
     """``iqa_nxdn_decode`` on ``bits`` (uint32[K][12], host) with the class masks ``classes`` (K values: 0, CAC alone, or any
     of SACCH | FACCH1_A | FACCH1_B): (info uint32[K][14], rec int32[K][4]) on the host.  ``ValueError`` for another value, before
     anything is launched."""
-    bits = np.ascontiguousarray(np.asarray(bits, dtype=np.uint32).reshape(-1, P.NXDN_WORDS))
-    classes = np.asarray(classes, dtype=np.int64).reshape(-1)
-    if classes.shape[0] != bits.shape[0]:
-        raise ValueError("iqa_nxdn_decode: one class mask to a frame")
-    if classes.size and not ((classes >= 0) & ((classes < CAC) | (classes == CAC))).all():
-        raise ValueError("iqa_nxdn_decode: a class mask must be 0 .. 7 or 8")
+    bits = L.word_rows(bits, P.NXDN_WORDS)
+    classes = L.frame_classes("iqa_nxdn_decode", bits, classes, "class mask", CAC, "0 .. 7 or 8")
     k = bits.shape[0]
     return tuple(L.device_rows("iqa_nxdn_decode", k, k == 0, bits.view(np.int32), classes.astype(np.uint8), c_int64(k),
                                L.Out(P.NXDN_INFO, np.uint32), L.Out(RECORD, np.int32)))
@@ -183,12 +176,7 @@ def frame_hits(hits, pats, half: int) -> np.ndarray:
     """int64[K][2], (m, s) in order of m: of the kept hits (int64[K][6] of section 25, ``pats`` the patterns searched for) every
     hit of the ``nxdn`` pattern, less those with another within +-``half`` that has a larger |C|, or the same |C| at a smaller
     m (section 29's keep rule)."""
-    cand = []
-    for p, m, c, _e, _pre, _post in np.asarray(hits, dtype=np.int64).reshape(-1, P.IDENT_RECORD).tolist():
-        if pats[p].protocol == "nxdn" and c != 0:
-            cand.append((m, -abs(c), 0, -1 if c < 0 else 1))
-    rows = [(m, s) for m, _neg, _tie, s in L.strongest_hits(cand, half)]
-    return np.array(rows, dtype=np.int64).reshape(-1, 2)
+    return L.sync_hits(hits, pats, "nxdn", half)
 
 
 def decoder_classes(bits, levels) -> np.ndarray:
@@ -475,8 +463,7 @@ def channel_of(st: dict, fs_ch: float, keyed_from: int, offset_hz: float, freq_h
     out = NxdnChannel(offset_hz=offset_hz, freq_hz=freq_hz, rate=st["rate"], **counts)
     for f in frames:
         out.frames[f.kind()] = out.frames.get(f.kind(), 0) + 1
-    signs = st["rows"][:, 1]
-    out.inverted = bool(2 * int((signs < 0).sum()) > signs.size)
+    out.inverted = L.mostly_inverted(st["rows"])
     out.calls = track_calls(frames)
     out.control = fold_control(frames)
     return out
@@ -488,19 +475,14 @@ class NxdnDecoder(L.StoredTheta):
     host, and ``hits``."""
 
     planes = ("v",)
+    patterns, result = NXDN_PATTERNS, NxdnResult
+    decode_stream, channel_of = staticmethod(decode_stream), staticmethod(channel_of)
 
     def __init__(self, fs_ch: float, centre: int = 0, rate: int = 4800):
         self.rate = int(rate)
         self.plan = P.plan_nxdn(fs_ch, self.rate)
         self.centre = int(centre)
         self.reset()
-
-    def _decode(self, theta) -> tuple:
-        v = I.integrate(theta, self.plan.ident, self.centre)
-        _, hits = I.search(v, self.plan.ident, NXDN_PATTERNS)
-        st = decode_stream(theta, self.plan, self.centre, hits, NXDN_PATTERNS, v)
-        st["hits"] = hits
-        return st, NxdnResult(channels=[channel_of(st, self.plan.fs_ch, 0, 0.0, None)], sample_rate=self.plan.fs_ch)
 
 
 # ---- the layer of the second pass (describe.py) ---------------------------------------------------------------------------------
@@ -531,8 +513,4 @@ def stage_keys(describer, j: int, lane, keep: bool) -> dict:
     """This layer's keys of ``ChannelDescriber.stages()`` for channel ``j``: ``nxdn_rows`` ((m, s) per frame, None where the channel
     is no NXDN channel) and, with ``keep``, ``nxdn_plan``, ``nxdn_bits``, ``nxdn_levels``, ``nxdn_classes``, ``nxdn_info`` and
     ``nxdn_rec``."""
-    x = describer.finish_nxdn()[j]
-    d = dict(nxdn_rows=x.get("rows"))
-    if keep and "rows" in x:
-        d.update(nxdn_plan=x["plan"], **{f"nxdn_{name}": x[name] for name in ("bits", "levels", "classes", "info", "rec")})
-    return d
+    return L.layer_stage_keys("nxdn", describer.finish_nxdn()[j], ("bits", "levels", "classes", "info", "rec"), keep)

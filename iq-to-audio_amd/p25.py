@@ -199,19 +199,12 @@ def tsbk_text(opcode: int, mfid: int, args: int, idens: dict) -> str:
 def slice_frames(plane, rows, plan: P.P25Plan) -> tuple:
     """``iqa_p25_slice`` on a device int32 plane for ``rows`` (int64[K][2]: m, s): (bits uint32[K][54], levels int64[K][3]: A, Dc,
     valid) on the host.  ``ValueError`` for a sign other than +-1, before anything is launched."""
-    rows = np.ascontiguousarray(np.asarray(rows, dtype=np.int64).reshape(-1, 2))
-    if rows.size and not np.isin(rows[:, 1], (-1, 1)).all():
-        raise ValueError("iqa_p25_slice: a hit's sign must be +-1")
-    return L.slice_hits("iqa_p25_slice", plane, rows, plan.offsets, P.P25_WORDS)
-
-
-def _bits_of(bits) -> np.ndarray:
-    return np.ascontiguousarray(np.asarray(bits, dtype=np.uint32).reshape(-1, P.P25_WORDS))
+    return L.slice_frames("iqa_p25_slice", plane, rows, plan.offsets, P.P25_WORDS)
 
 
 def decode_nids(bits) -> np.ndarray:
     """``iqa_p25_nid`` on ``bits`` (uint32[K][54], host): int32[K][4] (status, distance, value, parity_ok) on the host."""
-    bits = _bits_of(bits)
+    bits = L.word_rows(bits, P.P25_WORDS)
     k = bits.shape[0]
     return L.device_rows("iqa_p25_nid", k, k == 0, bits.view(np.int32), c_int64(k), L.Out(NID_RECORD, np.int32))[0]
 
@@ -219,12 +212,8 @@ def decode_nids(bits) -> np.ndarray:
 def decode_frames(bits, duids) -> tuple:
     """``iqa_p25_decode`` on ``bits`` (uint32[K][54], host) of the ``duids`` (K values 0 .. 15): (info uint32[K][9], rec
     int32[K][8]) on the host.  ``ValueError`` for a DUID over 15, before anything is launched."""
-    bits = _bits_of(bits)
-    duids = np.asarray(duids, dtype=np.int64).reshape(-1)
-    if duids.shape[0] != bits.shape[0]:
-        raise ValueError("iqa_p25_decode: one DUID to a frame")
-    if duids.size and not ((duids >= 0) & (duids <= 15)).all():
-        raise ValueError("iqa_p25_decode: a DUID must be 0 .. 15")
+    bits = L.word_rows(bits, P.P25_WORDS)
+    duids = L.frame_classes("iqa_p25_decode", bits, duids, "DUID", 15, "0 .. 15")
     k = bits.shape[0]
     return tuple(L.device_rows("iqa_p25_decode", k, k == 0, bits.view(np.int32), duids.astype(np.uint8), c_int64(k),
                                L.Out(P.P25_INFO, np.uint32), L.Out(RECORD, np.int32)))
@@ -237,12 +226,7 @@ def frame_hits(hits, pats, half: int) -> np.ndarray:
     """int64[K][2], (m, s) in order of m: of the kept hits (int64[K][6] of section 25, ``pats`` the patterns searched for) every
     hit of the ``p25`` pattern, less those with another within +-``half`` that has a larger |C|, or the same |C| at a smaller
     m (section 29's keep rule)."""
-    cand = []
-    for p, m, c, _e, _pre, _post in np.asarray(hits, dtype=np.int64).reshape(-1, P.IDENT_RECORD).tolist():
-        if pats[p].protocol == "p25" and c != 0:
-            cand.append((m, -abs(c), 0, -1 if c < 0 else 1))
-    rows = [(m, s) for m, _neg, _tie, s in L.strongest_hits(cand, half)]
-    return np.array(rows, dtype=np.int64).reshape(-1, 2)
+    return L.sync_hits(hits, pats, "p25", half)
 
 
 def apply_flags(nid, levels) -> np.ndarray:
@@ -499,8 +483,7 @@ def channel_of(st: dict, fs_ch: float, keyed_from: int, offset_hz: float, freq_h
     for f in frames:
         out.nacs[f"0x{f.nac:03x}"] = out.nacs.get(f"0x{f.nac:03x}", 0) + 1
         out.frames[f.name] = out.frames.get(f.name, 0) + 1
-    signs = st["rows"][:, 1]
-    out.inverted = bool(2 * int((signs < 0).sum()) > signs.size)
+    out.inverted = L.mostly_inverted(st["rows"])
     out.calls, out.tsbks = track_calls(frames), collapse_tsbks(frames)
     return out
 
@@ -511,13 +494,8 @@ class P25Decoder(L.StoredTheta):
 
     plan_of = staticmethod(P.plan_p25)
     planes = ("v",)
-
-    def _decode(self, theta) -> tuple:
-        v = I.integrate(theta, self.plan.ident, self.centre)
-        _, hits = I.search(v, self.plan.ident, P25_PATTERNS)
-        st = decode_stream(theta, self.plan, self.centre, hits, P25_PATTERNS, v)
-        st["hits"] = hits
-        return st, P25Result(channels=[channel_of(st, self.plan.fs_ch, 0, 0.0, None)], sample_rate=self.plan.fs_ch)
+    patterns, result = P25_PATTERNS, P25Result
+    decode_stream, channel_of = staticmethod(decode_stream), staticmethod(channel_of)
 
 
 # ---- the layer of the second pass (describe.py) ---------------------------------------------------------------------------------
@@ -541,8 +519,4 @@ def p25_result(channels, lanes, decoded, sample_rate: float, center_freq: float 
 def stage_keys(describer, j: int, lane, keep: bool) -> dict:
     """This layer's keys of ``ChannelDescriber.stages()`` for channel ``j``: ``p25_rows`` ((m, s) per frame, None where the channel
     is no P25 channel) and, with ``keep``, ``p25_plan``, ``p25_bits``, ``p25_levels``, ``p25_nid``, ``p25_info`` and ``p25_rec``."""
-    x = describer.finish_p25()[j]
-    d = dict(p25_rows=x.get("rows"))
-    if keep and "rows" in x:
-        d.update(p25_plan=x["plan"], p25_bits=x["bits"], p25_levels=x["levels"], p25_nid=x["nid"], p25_info=x["info"], p25_rec=x["rec"])
-    return d
+    return L.layer_stage_keys("p25", describer.finish_p25()[j], ("bits", "levels", "nid", "info", "rec"), keep)

@@ -1,9 +1,10 @@
-"""What the protocol layers behind section 25 share (``flex.py``, ``dmr.py``, ``p25.py``, ``ysf.py``; DESIGN.md, "Adding a layer to the
-second pass"): the stored discriminator stream of one channel (``join_theta``, ``StoredTheta``), the shape of a device call on
-host rows (``device_rows``, ``slice_hits``), the keep rule across a protocol's patterns (``strongest_hits``), the per-lane loop
-of a layer's ``finish_*`` (``finish_lanes``), its result builder (``layer_result``) and the mixins of the result classes
-(``JsonRecord``, ``ChannelLabel``, ``ChannelLines``).  A layer's module keeps its plan, its checks, its parser and its
-dataclasses.  Nothing here touches the GPU at import; ``identify.py``, which the layers import, imports this module in turn."""
+"""What the protocol layers behind section 25 share (``flex.py``, ``dmr.py``, ``p25.py``, ``ysf.py``, ``nxdn.py``; DESIGN.md, "Adding a
+layer to the second pass"): the stored discriminator stream of one channel and its decoder (``join_theta``, ``StoredTheta``),
+the shape of a device call on host rows (``device_rows``, ``slice_hits``) and the checks in front of one (``slice_frames``,
+``word_rows``, ``frame_classes``), the keep rule across a protocol's patterns (``strongest_hits``, ``sync_hits``), the per-lane
+loop of a layer's ``finish_*`` (``finish_lanes``), its result builder (``layer_result``), ``mostly_inverted``, its keys of
+``stages()`` (``layer_stage_keys``) and the mixins of the result classes (``JsonRecord``, ``ChannelLabel``, ``ChannelLines``).  A
+layer's module keeps its plan, its checks, its parser and its dataclasses.  Nothing here touches the GPU at import; ``identify.py``, which the layers import, imports this module in turn."""
 from __future__ import annotations
 
 import ctypes
@@ -37,11 +38,14 @@ class StoredTheta:
     """A protocol decoder for one discriminator stream from Python: ``process(theta_block)`` per block (float32, radians per
     sample at ``fs_ch``), ``finish()`` once (the layer's result of one channel), ``stages()`` for the tests, ``reset()``.
     ``centre``: section 23's centre of the quantised stream.  The subclass names its plan function (``ValueError`` where
-    ``fs_ch`` does not fit), the device planes that ``stages()`` moves to the host, and writes ``_decode(theta)``: (the stages
-    of the stream, its result)."""
+    ``fs_ch`` does not fit), the device planes that ``stages()`` moves to the host, and either what ``_decode`` runs (the
+    ``patterns`` searched for on the plan's one integrated plane, the module's ``decode_stream`` and ``channel_of`` as
+    staticmethods, its ``result`` class) or a ``_decode(theta)`` of its own: (the stages of the stream, its result)."""
 
     plan_of = None
     planes = ()
+    patterns = ()
+    decode_stream = channel_of = result = None
 
     def __init__(self, fs_ch: float, centre: int = 0):
         self.plan = type(self).plan_of(fs_ch)
@@ -63,6 +67,15 @@ class StoredTheta:
         if self._result is None:
             self._st, self._result = self._decode(checked_theta(self._stored))
         return self._result
+
+    def _decode(self, theta) -> tuple:
+        from . import identify as I  # (identify imports this module)
+
+        v = I.integrate(theta, self.plan.ident, self.centre)
+        _, hits = I.search(v, self.plan.ident, self.patterns)
+        st = self.decode_stream(theta, self.plan, self.centre, hits, self.patterns, v)
+        st["hits"] = hits
+        return st, self.result(channels=[self.channel_of(st, self.plan.fs_ch, 0, 0.0, None)], sample_rate=self.plan.fs_ch)
 
     def stages(self) -> dict:
         """The stages of ``_decode`` with the planes on the host."""
@@ -101,6 +114,58 @@ def slice_hits(entry: str, plane, rows, offsets, words: int) -> tuple:
     n, k = int(plane.numel()), rows.shape[0]
     return tuple(device_rows(entry, k, n == 0 or k == 0, plane, c_int64(n), rows, c_int64(k), (c_int32 * len(offsets))(*offsets),
                              Out(words, np.uint32), Out(3, np.int64)))
+
+
+def slice_frames(entry: str, plane, rows, offsets, words: int) -> tuple:
+    """``slice_hits`` for ``rows`` of (m, s) (int64[K][2]), with ``ValueError`` for a sign other than +-1 before anything is
+    launched: the ``slice_frames`` of a layer whose hits carry no kind."""
+    rows = np.ascontiguousarray(np.asarray(rows, dtype=np.int64).reshape(-1, 2))
+    if rows.size and not np.isin(rows[:, 1], (-1, 1)).all():
+        raise ValueError(f"{entry}: a hit's sign must be +-1")
+    return slice_hits(entry, plane, rows, offsets, words)
+
+
+def word_rows(bits, words: int) -> np.ndarray:
+    """``bits`` as contiguous uint32[K][words]: the sliced frames that a decode entry point takes."""
+    return np.ascontiguousarray(np.asarray(bits, dtype=np.uint32).reshape(-1, words))
+
+
+def frame_classes(entry: str, bits, classes, noun: str, top: int, span: str) -> np.ndarray:
+    """The ``classes`` that pick the decoders of the frames ``bits`` (``word_rows``' form) as int64[K], checked before anything is
+    launched: ``ValueError`` unless there is one ``noun`` to a frame and each is 0 .. ``top`` (``span`` in the message)."""
+    classes = np.asarray(classes, dtype=np.int64).reshape(-1)
+    if classes.shape[0] != bits.shape[0]:
+        raise ValueError(f"{entry}: one {noun} to a frame")
+    if classes.size and not ((classes >= 0) & (classes <= top)).all():
+        raise ValueError(f"{entry}: a {noun} must be {span}")
+    return classes
+
+
+def sync_hits(hits, pats, protocol: str, half: int) -> np.ndarray:
+    """int64[K][2], (m, s) in order of m: of the kept hits (int64[K][6] of section 25, ``pats`` the patterns searched for) every
+    hit of the one pattern of ``protocol``, less those with another within +-``half`` that has a larger |C|, or the same |C| at a
+    smaller m (section 29's keep rule): the ``frame_hits`` of a layer with one sync word."""
+    cand = []
+    for p, m, c, _e, _pre, _post in np.asarray(hits, dtype=np.int64).reshape(-1, P.IDENT_RECORD).tolist():
+        if pats[p].protocol == protocol and c != 0:
+            cand.append((m, -abs(c), 0, -1 if c < 0 else 1))
+    rows = [(m, s) for m, _neg, _tie, s in strongest_hits(cand, half)]
+    return np.array(rows, dtype=np.int64).reshape(-1, 2)
+
+
+def mostly_inverted(rows) -> bool:
+    """Whether most of the hits ``rows`` (m, s, ..) are negative: the channel's spectrum is inverted."""
+    signs = rows[:, 1]
+    return bool(2 * int((signs < 0).sum()) > signs.size)
+
+
+def layer_stage_keys(prefix: str, x: dict, names, keep: bool) -> dict:
+    """A layer's keys of ``ChannelDescriber.stages()`` from ``x``, its ``finish_*`` dict of one channel: ``<prefix>_rows`` (None
+    where nothing was decoded) and, with ``keep``, ``<prefix>_plan`` and ``<prefix>_<name>`` for every one of ``names``."""
+    d = {f"{prefix}_rows": x.get("rows")}
+    if keep and "rows" in x:
+        d.update({f"{prefix}_plan": x["plan"]}, **{f"{prefix}_{name}": x[name] for name in names})
+    return d
 
 
 def strongest_hits(cand, half: int) -> list:

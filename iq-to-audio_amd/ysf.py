@@ -129,19 +129,12 @@ def block_fields(cls: int, fi: int, fn: int, second: bool) -> tuple:
 def slice_frames(plane, rows, plan: P.YsfPlan) -> tuple:
     """``iqa_ysf_slice`` on a device int32 plane for ``rows`` (int64[K][2]: m, s): (bits uint32[K][30], levels int64[K][3]: A, Dc,
     valid) on the host.  ``ValueError`` for a sign other than +-1, before anything is launched."""
-    rows = np.ascontiguousarray(np.asarray(rows, dtype=np.int64).reshape(-1, 2))
-    if rows.size and not np.isin(rows[:, 1], (-1, 1)).all():
-        raise ValueError("iqa_ysf_slice: a hit's sign must be +-1")
-    return L.slice_hits("iqa_ysf_slice", plane, rows, plan.offsets, P.YSF_WORDS)
-
-
-def _bits_of(bits) -> np.ndarray:
-    return np.ascontiguousarray(np.asarray(bits, dtype=np.uint32).reshape(-1, P.YSF_WORDS))
+    return L.slice_frames("iqa_ysf_slice", plane, rows, plan.offsets, P.YSF_WORDS)
 
 
 def decode_fich(bits) -> tuple:
     """``iqa_ysf_fich`` on ``bits`` (uint32[K][30], host): (fich uint32[K][2], rec int32[K][5]) on the host."""
-    bits = _bits_of(bits)
+    bits = L.word_rows(bits, P.YSF_WORDS)
     k = bits.shape[0]
     return tuple(L.device_rows("iqa_ysf_fich", k, k == 0, bits.view(np.int32), c_int64(k), L.Out(2, np.uint32), L.Out(FICH_RECORD, np.int32)))
 
@@ -149,12 +142,8 @@ def decode_fich(bits) -> tuple:
 def decode_frames(bits, classes) -> tuple:
     """``iqa_ysf_decode`` on ``bits`` (uint32[K][30], host) of the ``classes`` (K values 0 .. 3): (info uint32[K][12], rec
     int32[K][4]) on the host.  ``ValueError`` for a class over 3, before anything is launched."""
-    bits = _bits_of(bits)
-    classes = np.asarray(classes, dtype=np.int64).reshape(-1)
-    if classes.shape[0] != bits.shape[0]:
-        raise ValueError("iqa_ysf_decode: one class to a frame")
-    if classes.size and not ((classes >= 0) & (classes <= 3)).all():
-        raise ValueError("iqa_ysf_decode: a class must be 0 .. 3")
+    bits = L.word_rows(bits, P.YSF_WORDS)
+    classes = L.frame_classes("iqa_ysf_decode", bits, classes, "class", 3, "0 .. 3")
     k = bits.shape[0]
     return tuple(L.device_rows("iqa_ysf_decode", k, k == 0, bits.view(np.int32), classes.astype(np.uint8), c_int64(k),
                                L.Out(P.YSF_INFO, np.uint32), L.Out(RECORD, np.int32)))
@@ -167,12 +156,7 @@ def frame_hits(hits, pats, half: int) -> np.ndarray:
     """int64[K][2], (m, s) in order of m: of the kept hits (int64[K][6] of section 25, ``pats`` the patterns searched for) every
     hit of the ``ysf`` pattern, less those with another within +-``half`` that has a larger |C|, or the same |C| at a smaller
     m (section 29's keep rule)."""
-    cand = []
-    for p, m, c, _e, _pre, _post in np.asarray(hits, dtype=np.int64).reshape(-1, P.IDENT_RECORD).tolist():
-        if pats[p].protocol == "ysf" and c != 0:
-            cand.append((m, -abs(c), 0, -1 if c < 0 else 1))
-    rows = [(m, s) for m, _neg, _tie, s in L.strongest_hits(cand, half)]
-    return np.array(rows, dtype=np.int64).reshape(-1, 2)
+    return L.sync_hits(hits, pats, "ysf", half)
 
 
 def apply_flags(rec, levels) -> np.ndarray:
@@ -393,8 +377,7 @@ def channel_of(st: dict, fs_ch: float, keyed_from: int, offset_hz: float, freq_h
     out = YsfChannel(offset_hz=offset_hz, freq_hz=freq_hz, **counts)
     for f in frames:
         out.frames[frame_kind(f)] = out.frames.get(frame_kind(f), 0) + 1
-    signs = st["rows"][:, 1]
-    out.inverted = bool(2 * int((signs < 0).sum()) > signs.size)
+    out.inverted = L.mostly_inverted(st["rows"])
     out.transmissions = track_transmissions(frames)
     return out
 
@@ -405,13 +388,8 @@ class YsfDecoder(L.StoredTheta):
 
     plan_of = staticmethod(P.plan_ysf)
     planes = ("v",)
-
-    def _decode(self, theta) -> tuple:
-        v = I.integrate(theta, self.plan.ident, self.centre)
-        _, hits = I.search(v, self.plan.ident, YSF_PATTERNS)
-        st = decode_stream(theta, self.plan, self.centre, hits, YSF_PATTERNS, v)
-        st["hits"] = hits
-        return st, YsfResult(channels=[channel_of(st, self.plan.fs_ch, 0, 0.0, None)], sample_rate=self.plan.fs_ch)
+    patterns, result = YSF_PATTERNS, YsfResult
+    decode_stream, channel_of = staticmethod(decode_stream), staticmethod(channel_of)
 
 
 # ---- the layer of the second pass (describe.py) ---------------------------------------------------------------------------------
@@ -436,8 +414,4 @@ def stage_keys(describer, j: int, lane, keep: bool) -> dict:
     """This layer's keys of ``ChannelDescriber.stages()`` for channel ``j``: ``ysf_rows`` ((m, s) per frame, None where the channel
     is no YSF channel) and, with ``keep``, ``ysf_plan``, ``ysf_bits``, ``ysf_levels``, ``ysf_fich``, ``ysf_frec``, ``ysf_classes``,
     ``ysf_info`` and ``ysf_rec``."""
-    x = describer.finish_ysf()[j]
-    d = dict(ysf_rows=x.get("rows"))
-    if keep and "rows" in x:
-        d.update(ysf_plan=x["plan"], **{f"ysf_{name}": x[name] for name in ("bits", "levels", "fich", "frec", "classes", "info", "rec")})
-    return d
+    return L.layer_stage_keys("ysf", describer.finish_ysf()[j], ("bits", "levels", "fich", "frec", "classes", "info", "rec"), keep)
