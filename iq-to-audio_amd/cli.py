@@ -30,7 +30,7 @@ from pathlib import Path
 from .benchmark import run_benchmark
 from . import dsp_plan as P
 from .decoders.side import SIDE_DECODERS
-from .find_layers import FIND_EVERY_BRANCH, FIND_LAYERS
+from .find_layers import ALL_LAYERS, FIND_BRANCHES, FIND_LAYERS
 from .gate import CarrierSquelch
 from .processing import MultiChannelPipeline, ProcessingCancelled, ProcessingConfig, ProcessingPipeline
 from .squelch import AudioPostOptions, SquelchConfig, gather_audio_targets, process_audio_batch
@@ -155,7 +155,7 @@ def build_parser() -> argparse.ArgumentParser:
                    help="Round the --find-top targets to the nearest multiple of HZ (default 1).")
     p.add_argument("--find-threshold", dest="find_threshold", type=float, metavar="DB",
                    help="dB a channel's mean spectrum must stand over its local floor (default 6).")
-    for layer in FIND_LAYERS + FIND_EVERY_BRANCH:
+    for layer in ALL_LAYERS:
         p.add_argument(layer.option, dest=layer.flag, action="store_true", help=layer.help)
     p.add_argument("--find-auto", dest="find_auto", action="store_true",
                    help="With --find-top N: take the N strongest channels whose label is known and run each with its own "
@@ -224,7 +224,7 @@ def run_audio_post(args) -> int:
 
 def check_find_args(parser, args) -> bool:
     """``parser.error`` for every misuse of the ``--find-*`` flags; whether channels are to be found."""
-    layers = [(layer.option, getattr(args, layer.flag) or None) for layer in FIND_LAYERS + FIND_EVERY_BRANCH]
+    layers = [(layer.option, getattr(args, layer.flag) or None) for layer in ALL_LAYERS]
     given = [flag for flag, value in (("--find-channels", args.find_channels or None), ("--find-top", args.find_top),
                                       ("--find-grid", args.find_grid), ("--find-threshold", args.find_threshold), layers[0],
                                       ("--find-auto", args.find_auto or None), *layers[1:])
@@ -234,7 +234,7 @@ def check_find_args(parser, args) -> bool:
     # a branch's flag sets the flag of the row it hangs off; a layer's flag sets the flags of the layers in front of it, down to
     # the second: the first is derived (run_find)
     by_name = {layer.name: layer for layer in FIND_LAYERS}
-    for layer in FIND_EVERY_BRANCH:
+    for layer in FIND_BRANCHES:
         if getattr(args, layer.flag):
             setattr(args, by_name[layer.needs].flag, True)
     for below, layer in reversed(list(zip(FIND_LAYERS[1:], FIND_LAYERS[2:]))):
@@ -256,7 +256,7 @@ def check_find_args(parser, args) -> bool:
     for e in SIDE_DECODERS:
         if args.find_auto and getattr(args, e.name):
             parser.error(f"--find-auto cannot be combined with --{e.name}.")
-    if not args.find_channels and not any(getattr(args, layer.flag) for layer in FIND_LAYERS + FIND_EVERY_BRANCH) and args.find_top is None:
+    if not args.find_channels and not any(getattr(args, layer.flag) for layer in ALL_LAYERS) and args.find_top is None:
         parser.error("--find-threshold needs --find-channels or --find-top.")
     if args.input_path is None:
         parser.error(f"{given[0]} needs --in.")
@@ -290,16 +290,16 @@ def check_squelch_args(parser, args, finding: bool) -> CarrierSquelch | None:
 
 
 def run_find(args, codec, container):
-    """``--find-channels``, ``--find-top`` and the flags of ``FIND_LAYERS`` and ``FIND_EVERY_BRANCH``: print and store the capture's
+    """``--find-channels``, ``--find-top`` and the flags of ``find_layers.ALL_LAYERS`` (the chain, then the branches): print and store the capture's
     channels and, where asked for, what every layer of the second pass says about them.  Returns (exit code or ``None`` to go on, the targets of the
     run that follows: frequencies, or with ``--find-auto`` (frequency, demod, bw) each, and with ``--find-decode`` beside it
     (frequency, demod, bw, side decoders))."""
     from .find import find_channels, select_targets
 
     options = {} if args.find_threshold is None else {"threshold_db": args.find_threshold}
-    wanted = [getattr(args, layer.flag) for layer in FIND_LAYERS + FIND_EVERY_BRANCH]
+    wanted = [getattr(args, layer.flag) for layer in ALL_LAYERS]
     wanted[0] = args.find_auto or any(wanted)  # (a higher flag leaves the first unset, and --find-auto needs the descriptions)
-    layers = [layer for layer, on in zip(FIND_LAYERS + FIND_EVERY_BRANCH, wanted) if on]
+    layers = [layer for layer, on in zip(ALL_LAYERS, wanted) if on]
     options.update({layer.name: True for layer in layers})
     try:
         found = find_channels(args.input_path, center_freq=args.center_freq, input_format=codec, input_container=container,

@@ -9,31 +9,27 @@ float64 from those integers and from the finder's planes; the label and the sugg
 quantiser everything is integer: the sums do not depend on how the stream is cut.  No CPU path: without a GPU or the built
 library the calls raise ``RuntimeError``.
 
-The layers above this one (``find_layers.FIND_LAYERS``, each in the module of its name) ride on the same pass: with ``keying=True``
+The layers above this one (``find_layers.ALL_LAYERS``, each in the module of its name) ride on the same pass: with ``keying=True``
 it also takes every channel's discriminator and, once the channel holds 1024 gated pairs, its keying rows (``keying.py``); with
-``identify=True`` it keeps that discriminator output for the sync-word search of ``identify.py``, whose hits ``flex.py`` decodes
-with ``flex=True``, ``dmr.py`` with ``dmr=True``, ``p25.py`` with ``p25=True``, ``ysf.py`` with ``ysf=True`` and ``nxdn.py`` with
-``nxdn=True``."""
+``identify=True`` it keeps that discriminator output for the sync-word search of ``identify.py``, whose hits the protocol layers
+decode, each with its keyword (``flex=True``, ``dmr=True``, ...): a module with a ``LAYER`` (``protocol_layer.ProtocolLayer``), which
+``finish_layer`` and ``layer_result`` run by name."""
 from __future__ import annotations
 
 import math
 from ctypes import c_int32, c_int64
 from dataclasses import asdict, dataclass, field
+from importlib import import_module
 
 import numpy as np
 
 from . import _dev as D
 from . import _native as N
 from . import dsp_plan as P
-from . import dmr as DM
-from . import flex as X
 from . import identify as I
 from . import keying as KY
-from . import nxdn as NX
-from . import p25 as P5
-from . import ysf as YS
 from .find import _RAW_DTYPE
-from .find_layers import FIND_LAYERS, active_layers
+from .find_layers import ALL_LAYERS, active_layers
 
 SUMS = ("N", "NP", "S1", "S2", "E", "CR", "CI", "A")
 LABELS = ("nfm", "am", "ssb", "wfm", "carrier", "unknown")
@@ -247,7 +243,7 @@ def add_rows(rows: np.ndarray) -> tuple:
     return tuple((int(h) << 32) + int(l) for h, l in zip(high, low))
 
 
-_MODULES = {m.__name__.rpartition(".")[2]: m for m in (KY, I, X, DM, P5, YS, NX)}  # a layer above the first lives in the module of its keyword
+_MODULES = {layer.name: import_module(f"{__package__}.{layer.name}") for layer in ALL_LAYERS[1:]}  # a layer above the first lives in the module of its keyword
 
 
 class _Lane:
@@ -279,7 +275,8 @@ class ChannelDescriber:
     (the eight sums of every channel), ``result()`` (a ``DescribeResult``), ``stages()`` for the tests, ``reset()``.
     ``fin`` is ``ChannelFinder.finish()`` of the same capture and ``channels`` the ``FoundChannel``s made from it.  ``layers``: the
     keywords of ``FIND_LAYERS`` above the first (``keying=True``, ``identify=True``, ``flex=True``), each with the one in front of
-    it, and of ``FIND_EVERY_BRANCH`` (``dmr=True``, ``p25=True``, ``ysf=True``, ``nxdn=True``, with ``identify=True``)."""
+    it, and of ``FIND_BRANCHES`` (``dmr=True``, ``p25=True``, ``ysf=True``, ``nxdn=True``, with ``identify=True``).  Every protocol
+    layer has its ``finish_<name>()`` and ``<name>_result(center_freq)``, installed below the class from the table."""
 
     def __init__(self, find_plan: P.FindPlan, fin: dict, channels, fmt: str = "s16", iq_order: str = "iq", *, keep_stages: bool = False,
                  **layers):
@@ -290,7 +287,7 @@ class ChannelDescriber:
         for name in layers:
             if name not in _MODULES:
                 raise TypeError(f"ChannelDescriber() got an unexpected keyword argument '{name}'")
-        self._names = tuple(layer.name for layer in active_layers({FIND_LAYERS[0].name: True, **layers}))  # this layer, then the others
+        self._names = tuple(layer.name for layer in active_layers({ALL_LAYERS[0].name: True, **layers}))  # this layer, then the others
         self.find_plan, self.fin, self.channels = find_plan, fin, list(channels)
         self.fmt, self.iq_order, self._keep, self._keying = fmt, iq_order, keep_stages, "keying" in self._names
         by_lo = {int(rec[0]): j for j, rec in enumerate(np.asarray(fin["runs"]).reshape(-1, 8))}
@@ -457,45 +454,14 @@ class ChannelDescriber:
     def protocol_result(self, center_freq: float | None = None) -> I.ProtocolResult:
         return I.ProtocolResult(channels=self.protocols(center_freq), sample_rate=self.find_plan.fs, center_freq=center_freq)
 
-    def finish_flex(self) -> list:
-        """Per channel the dict of ``flex.finish_flex``."""
-        self._need("flex")
-        return self._once("flex", lambda: X.finish_flex(self.lanes(), self.finish_identify()))
+    def finish_layer(self, name: str) -> list:
+        """Per channel the dict of the ``LAYER.finish`` of the protocol layer ``name`` (``flex``, ``dmr``, ...)."""
+        self._need(name)
+        return self._once(name, lambda: _MODULES[name].LAYER.finish(self.lanes(), self.finish_identify()))
 
-    def flex_result(self, center_freq: float | None = None) -> X.FlexResult:
-        return X.flex_result(self.channels, self.lanes(), self.finish_flex(), self.find_plan.fs, center_freq)
-
-    def finish_dmr(self) -> list:
-        """Per channel the dict of ``dmr.finish_dmr``."""
-        self._need("dmr")
-        return self._once("dmr", lambda: DM.finish_dmr(self.lanes(), self.finish_identify()))
-
-    def dmr_result(self, center_freq: float | None = None) -> DM.DmrResult:
-        return DM.dmr_result(self.channels, self.lanes(), self.finish_dmr(), self.find_plan.fs, center_freq)
-
-    def finish_p25(self) -> list:
-        """Per channel the dict of ``p25.finish_p25``."""
-        self._need("p25")
-        return self._once("p25", lambda: P5.finish_p25(self.lanes(), self.finish_identify()))
-
-    def p25_result(self, center_freq: float | None = None) -> P5.P25Result:
-        return P5.p25_result(self.channels, self.lanes(), self.finish_p25(), self.find_plan.fs, center_freq)
-
-    def finish_ysf(self) -> list:
-        """Per channel the dict of ``ysf.finish_ysf``."""
-        self._need("ysf")
-        return self._once("ysf", lambda: YS.finish_ysf(self.lanes(), self.finish_identify()))
-
-    def ysf_result(self, center_freq: float | None = None) -> YS.YsfResult:
-        return YS.ysf_result(self.channels, self.lanes(), self.finish_ysf(), self.find_plan.fs, center_freq)
-
-    def finish_nxdn(self) -> list:
-        """Per channel the dict of ``nxdn.finish_nxdn``."""
-        self._need("nxdn")
-        return self._once("nxdn", lambda: NX.finish_nxdn(self.lanes(), self.finish_identify()))
-
-    def nxdn_result(self, center_freq: float | None = None) -> NX.NxdnResult:
-        return NX.nxdn_result(self.channels, self.lanes(), self.finish_nxdn(), self.find_plan.fs, center_freq)
+    def layer_result(self, name: str, center_freq: float | None = None):
+        """The result object of the protocol layer ``name`` (``FlexResult``, ``DmrResult``, ...)."""
+        return _MODULES[name].LAYER.result_of(self.channels, self.lanes(), self.finish_layer(name), self.find_plan.fs, center_freq)
 
     def result(self, center_freq: float | None = None) -> DescribeResult:
         sums = self.finish()
@@ -520,3 +486,25 @@ class ChannelDescriber:
                 d["rows"] = torch.cat(lane.rows).cpu().numpy().reshape(-1, len(SUMS)) if lane.rows else np.zeros((0, 8), dtype=np.int64)
             out.append(d)
         return out
+
+
+def _install(layer) -> None:
+    """``finish_<name>`` and ``<name>_result`` of ``ChannelDescriber`` for the protocol layer of the table's row ``layer``."""
+    name = layer.name
+
+    def finish(self) -> list:
+        return self.finish_layer(name)
+
+    def result(self, center_freq: float | None = None):
+        return self.layer_result(name, center_freq)
+
+    finish.__doc__ = f"Per channel the dict of ``{name}.finish_{name}`` (DESIGN.md section {layer.section})."
+    result.__doc__ = f"The ``{_MODULES[name].LAYER.result.__name__}`` of the pass (DESIGN.md section {layer.section})."
+    finish.__name__, result.__name__ = f"finish_{name}", f"{name}_result"
+    setattr(ChannelDescriber, finish.__name__, finish)
+    setattr(ChannelDescriber, result.__name__, result)
+
+
+for _layer in ALL_LAYERS[1:]:
+    if hasattr(_MODULES[_layer.name], "LAYER"):
+        _install(_layer)

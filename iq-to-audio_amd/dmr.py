@@ -45,7 +45,7 @@ INFO_INDEX = tuple(range(4, 12)) + tuple(1 + 15 * r + c for r in range(1, 9) for
 GF_POLY = 0x11D
 RS_GENERATOR = (1, 14, 56, 64)  # x^3 + 14 x^2 + 56 x + 64: the roots alpha, alpha^2, alpha^3
 RS_MASK = {1: 0x96, 2: 0x99}  # on bytes 9 .. 11, by data type
-CRC_POLY = 0x1021
+CRC_POLY = L.CRC_POLY
 CRC_MASK = {3: 0xA5A5, 6: 0xCCCC}
 DATA_TYPES = ("pi header", "voice lc header", "terminator lc", "csbk", "mbc header", "mbc continuation", "data header",
               "rate 1/2 data", "rate 3/4 data", "idle", "rate 1 data")
@@ -58,22 +58,8 @@ RECORD = P.DMR_RECORD  # TACT status, TACT nibble, slot-type status, distance, b
 # ---- the checks and the fields (host, integers) ---------------------------------------------------------------------------------
 
 
-def _gf_tables() -> tuple:
-    exp, log, x = [0] * 510, [0] * 256, 1
-    for i in range(255):
-        exp[i], log[x] = x, i
-        x <<= 1
-        if x & 0x100:
-            x ^= GF_POLY
-    exp[255:510] = exp[0:255]
-    return tuple(exp), tuple(log)
-
-
-_EXP, _LOG = _gf_tables()
-
-
-def gf_mul(a: int, b: int) -> int:
-    return 0 if a == 0 or b == 0 else _EXP[_LOG[a] + _LOG[b]]
+_EXP, _LOG, gf_mul = L.gf_tables(GF_POLY, 8)
+info_bytes, crc_ccitt = L.info_bytes, L.crc_ccitt  # twelve bytes of three information words; CRC_POLY from 0
 
 
 def rs_remainder(data) -> tuple:
@@ -93,25 +79,11 @@ def check_lc(info, data_type: int) -> bool:
     return rs_remainder(body[:9]) == tuple(body[9:12])
 
 
-def crc_ccitt(data) -> int:
-    crc = 0
-    for byte in data:
-        crc ^= int(byte) << 8
-        for _ in range(8):
-            crc = ((crc << 1) ^ CRC_POLY) & 0xFFFF if crc & 0x8000 else (crc << 1) & 0xFFFF
-    return crc
-
-
 def check_csbk(info, data_type: int) -> bool:
     """Whether the complemented CRC-CCITT of bytes 0 .. 9 of a CSBK (type 3) or a data header (type 6) equals bytes 10 .. 11
     unmasked."""
     info = [int(b) for b in info]
     return (crc_ccitt(info[:10]) ^ 0xFFFF) == ((info[10] << 8 | info[11]) ^ CRC_MASK[data_type])
-
-
-def info_bytes(words) -> list:
-    """The twelve bytes of three information words (the first bit the MSB of word 0)."""
-    return [(int(w) >> s) & 0xFF for w in words for s in (24, 16, 8, 0)]
 
 
 # ---- the device calls ---------------------------------------------------------------------------------------------------------
@@ -370,35 +342,18 @@ def channel_of(st: dict, fs_ch: float, keyed_from: int, offset_hz: float, freq_h
     return out
 
 
+# ---- the layer of the second pass (describe.py) ---------------------------------------------------------------------------------
+
+#: ``finish_dmr`` reads the 4800 family's plane; ``stages()`` shows ``dmr_rows`` ((m, s, kind) per burst, None where the channel is no
+#: DMR channel) and, with ``keep_stages``, ``dmr_plan`` and these
+LAYER = L.ProtocolLayer("dmr", (4800,), lambda fs_ch, rate: P.plan_dmr(fs_ch), "dmr", decode_stream, channel_of, DmrChannel, DmrResult,
+                        keys=("bits", "levels", "info", "rec"))
+PLANE_RATES, finish_dmr, dmr_result, stage_keys = LAYER.rates, LAYER.finish, LAYER.result_of, LAYER.stage_keys
+
+
 class DmrDecoder(L.StoredTheta):
     """A DMR decoder for one discriminator stream from Python (``protocol_layer.StoredTheta``): ``finish()`` gives a
     ``DmrResult`` of one channel, ``stages()`` ``decode_stream``'s output with the plane on the host, and ``hits``."""
 
     plan_of = staticmethod(P.plan_dmr)
-    planes = ("v",)
-    patterns, result = PATTERNS, DmrResult
-    decode_stream, channel_of = staticmethod(decode_stream), staticmethod(channel_of)
-
-
-# ---- the layer of the second pass (describe.py) ---------------------------------------------------------------------------------
-
-PLANE_RATES = (4800,)  # the families whose integrated plane ``finish_dmr`` reads from section 25's dicts (``v``)
-
-
-def finish_dmr(lanes, found) -> list:
-    """Per lane of the pass (``found``: its dict of ``identify.finish_identify``) the output of ``decode_stream`` with ``plan`` (the
-    ``DmrPlan``) and ``note``, or a dict of ``note`` alone where nothing is decoded: the channel is not of the 4800 family, its
-    rate does not fit or nothing was searched.  It reuses section 25's hits and plane and runs no second search."""
-    return L.finish_lanes(lanes, found, 4800, P.plan_dmr, "dmr",
-                          lambda theta, plan, centre, hits, v: decode_stream(theta, plan, centre, hits, I.patterns_for(4800), v))
-
-
-def dmr_result(channels, lanes, decoded, sample_rate: float, center_freq: float | None = None) -> DmrResult:
-    """The ``DmrResult`` of the pass: ``channels`` the finder's, ``decoded`` the dicts of ``finish_dmr``."""
-    return L.layer_result(DmrResult, DmrChannel, channel_of, channels, lanes, decoded, sample_rate, center_freq)
-
-
-def stage_keys(describer, j: int, lane, keep: bool) -> dict:
-    """This layer's keys of ``ChannelDescriber.stages()`` for channel ``j``: ``dmr_rows`` ((m, s, kind) per burst, None where the
-    channel is no DMR channel) and, with ``keep``, ``dmr_plan``, ``dmr_bits``, ``dmr_levels``, ``dmr_info`` and ``dmr_rec``."""
-    return L.layer_stage_keys("dmr", describer.finish_dmr()[j], ("bits", "levels", "info", "rec"), keep)
+    patterns, layer = PATTERNS, LAYER

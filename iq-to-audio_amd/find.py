@@ -27,7 +27,7 @@ from . import _native as N
 from . import dsp_plan as P
 from . import iqio
 from .decoders.common import search_with_room
-from .find_layers import FIND_EVERY_BRANCH, FIND_LAYERS, active_layers
+from .find_layers import ALL_LAYERS, active_layers
 
 LOG = logging.getLogger(__name__)
 
@@ -260,18 +260,19 @@ def find_channels(path, *, center_freq: float | None = None, input_format: str |
                   fs_ch: float | None = None, **options):
     """The occupied channels of the capture at ``path``.  The centre frequency is taken from the file name where it is not
     given; without one the channels carry offsets only.  ``options``: the keywords of ``dsp_plan.plan_find`` and the layers of a
-    second pass over the mapped file (``find_layers.FIND_LAYERS``, each with the one in front of it): ``describe=True`` measures
+    second pass over the mapped file (``find_layers.ALL_LAYERS``: the chain, each with the one in front of it, then the
+    branches): ``describe=True`` measures
     every channel (``describe.ChannelDescriber``), ``keying=True`` also its keying and its side decoders
     (section 23; ``fs_ch``: an explicit channel rate of the targets that follow), ``identify=True`` searches the keyed channels of
     the usual digital rates for their frame synchronisation words (section 25), ``flex=True`` decodes the pages of the FLEX
-    channels among them (section 26); ``dmr=True`` (``find_layers.FIND_EVERY_BRANCH``: with ``identify=True``, and without ``flex``
+    channels among them (section 26); ``dmr=True`` (``find_layers.FIND_BRANCHES``: with ``identify=True``, and without ``flex``
     if so wished) decodes the data bursts of the channels that carry DMR sync words (section 29), ``p25=True`` likewise the
     NIDs, link control and TSBKs of those that carry P25 frame sync words (section 31), ``ysf=True`` the FICH and the callsigns
     of those that carry YSF frame sync words (section 32), ``nxdn=True`` the LICH, the calls and the control messages of those
     that carry NXDN frame sync words at either symbol rate (section 34).  Returns the ``FindResult``
     alone without a layer, else a tuple of it and every layer's result in that order: ``DescribeResult``, ``KeyingResult``,
     ``ProtocolResult``, ``FlexResult``, ``DmrResult``, ``P25Result``, ``YsfResult``, ``NxdnResult``."""
-    layers = active_layers({layer.name: options.pop(layer.name, False) for layer in FIND_LAYERS + FIND_EVERY_BRANCH})
+    layers = active_layers({layer.name: options.pop(layer.name, False) for layer in ALL_LAYERS})
     path = Path(path)
     info = iqio.probe_capture(path, input_format=input_format, input_container=input_container, input_sample_rate=input_sample_rate)
     if not info.sample_rate:

@@ -3,12 +3,11 @@
 22, 23, 25, 26, 29, 31, 32 and 34).
 
 ``FIND_LAYERS`` lists the chain, in order: every row needs the row in front of it.  ``FIND_BRANCHES`` lists the layers that
-hang off one row of the chain (``needs``) and off nothing else; ``FIND_ALL_BRANCHES`` is that list with ``p25`` added, and
-``FIND_EVERY_BRANCH`` that one with the branches added since (``ysf``, ``nxdn``; the next is a row there): it is the one that is looped
-over, and a test that finds its row by name need not be touched by the next.  ``find_channels``, ``ChannelDescriber`` and the CLI read a
-layer's keyword, flag, result and file suffix from its row; a new layer is a row here, a keyword on ``ChannelDescriber`` and
-its own module ("Adding a layer to the second pass").  Nothing heavy is imported here: the CLI reads the tables
-before the GPU is touched."""
+hang off one row of the chain (``needs``) and off nothing else, in the order of their results, printed lines and files; the
+next branch is a row at its end.  ``ALL_LAYERS`` is the chain, then the branches: the one that is looped over.  ``find_channels``,
+``ChannelDescriber`` and the CLI read a layer's keyword, flag, result and file suffix from its row; a new protocol layer is a row
+here and its own module with its ``LAYER`` ("Adding a layer to the second pass").  Nothing heavy is imported here:
+the CLI reads the tables before the GPU is touched."""
 from __future__ import annotations
 
 from dataclasses import dataclass
@@ -31,6 +30,11 @@ class FindLayer:
         return "--" + self.flag.replace("_", "-")
 
 
+def _protocol(name: str) -> Callable:
+    """The ``result`` of a protocol layer's row: the describer's generic path, by the row's name."""
+    return lambda d, fc, fs_ch: d.layer_result(name, fc)
+
+
 FIND_LAYERS = (
     FindLayer("describe", "find_describe", 22, lambda d, fc, fs_ch: d.result(fc), "describe", True,
               "Find the channels, then measure each one in a second pass: a label (nfm, am, ssb, wfm, carrier, unknown) "
@@ -43,40 +47,34 @@ FIND_LAYERS = (
               "Find, describe and key the channels, and name the protocol of every channel keyed at 1600, 2400, 3200 or "
               "4800 baud by its frame synchronisation words: DMR, P25, YSF, NXDN or FLEX with its mode.  Implies "
               "--find-decode."),
-    FindLayer("flex", "find_flex", 26, lambda d, fc, fs_ch: d.flex_result(fc), "flex", False,
+    FindLayer("flex", "find_flex", 26, _protocol("flex"), "flex", False,
               "Find, describe, key and identify the channels, and decode the pages of every FLEX channel: capcode, type "
               "and text, one line per page, also written to <capture stem>.flex.json.  Implies --find-identify."),
 )
 
 
 FIND_BRANCHES = (
-    FindLayer("dmr", "find_dmr", 29, lambda d, fc, fs_ch: d.dmr_result(fc), "dmr", False,
+    FindLayer("dmr", "find_dmr", 29, _protocol("dmr"), "dmr", False,
               "Find, describe, key and identify the channels, and decode the data bursts of every channel that carries DMR "
               "sync words: colour code, slot, link control and CSBKs, one line per call and per CSBK, also written to "
               "<capture stem>.dmr.json.  Implies --find-identify.", needs="identify"),
-)
-
-
-FIND_ALL_BRANCHES = FIND_BRANCHES + (
-    FindLayer("p25", "find_p25", 31, lambda d, fc, fs_ch: d.p25_result(fc), "p25", False,
+    FindLayer("p25", "find_p25", 31, _protocol("p25"), "p25", False,
               "Find, describe, key and identify the channels, and decode the frames of every channel that carries P25 phase 1 "
               "frame sync words: NAC, link control and trunking blocks, one line per call and per distinct TSBK, also "
               "written to <capture stem>.p25.json.  Implies --find-identify.", needs="identify"),
-)
-
-
-FIND_EVERY_BRANCH = FIND_ALL_BRANCHES + (
-    FindLayer("ysf", "find_ysf", 32, lambda d, fc, fs_ch: d.ysf_result(fc), "ysf", False,
+    FindLayer("ysf", "find_ysf", 32, _protocol("ysf"), "ysf", False,
               "Find, describe, key and identify the channels, and decode the frames of every channel that carries YSF (System "
               "Fusion) frame sync words: the FICH and the callsigns of the data channels, one line per transmission (source, "
               "destination, repeater, mode, duration), also written to <capture stem>.ysf.json.  No voice.  Implies "
               "--find-identify.", needs="identify"),
-    FindLayer("nxdn", "find_nxdn", 34, lambda d, fc, fs_ch: d.nxdn_result(fc), "nxdn", False,
+    FindLayer("nxdn", "find_nxdn", 34, _protocol("nxdn"), "nxdn", False,
               "Find, describe, key and identify the channels, and decode the frames of every channel that carries NXDN frame "
               "sync words at 4800 or 2400 symbols/s: the LICH, the SACCH, the FACCH1s and the outbound CAC, one line per call "
               "(RAN, source, destination, call type, cipher, duration) and per distinct control message, also written to "
               "<capture stem>.nxdn.json.  No voice.  Implies --find-identify.", needs="identify"),
 )
+
+ALL_LAYERS = FIND_LAYERS + FIND_BRANCHES
 
 
 def active_layers(switches: dict) -> tuple:
@@ -86,7 +84,7 @@ def active_layers(switches: dict) -> tuple:
     for below, layer in zip(FIND_LAYERS, FIND_LAYERS[1:]):
         if switches.get(layer.name) and not switches.get(below.name):
             raise ValueError(f"{layer.name}=True needs {below.name}=True")
-    for layer in FIND_EVERY_BRANCH:
+    for layer in FIND_BRANCHES:
         if switches.get(layer.name) and not switches.get(layer.needs):
             raise ValueError(f"{layer.name}=True needs {layer.needs}=True")
-    return tuple(layer for layer in FIND_LAYERS + FIND_EVERY_BRANCH if switches.get(layer.name))
+    return tuple(layer for layer in ALL_LAYERS if switches.get(layer.name))

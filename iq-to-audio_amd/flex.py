@@ -405,6 +405,27 @@ def channel_of(st: dict, fs_ch: float, keyed_from: int, offset_hz: float, freq_h
     return out
 
 
+# ---- the layer of the second pass (describe.py) ---------------------------------------------------------------------------------
+
+
+def _stage_keys(x: dict, keep: bool) -> dict:
+    """The keys of ``ChannelDescriber.stages()`` from ``x``, ``finish_flex``'s dict of one channel: ``flex_frames`` ((m, s, mode) per
+    decoded frame, None where the channel is no FLEX channel) and, with ``keep``, ``flex_words``, ``flex_raw``, ``flex_status``
+    ([F][5][4][88]), ``flex_chosen``, ``flex_rec16``, ``flex_rec32``, ``flex_ok``, ``flex_v32`` and ``flex_plan``."""
+    d = dict(flex_frames=x.get("rows"))
+    if keep and "rows" in x:
+        d.update(flex_plan=x["plan"], flex_rec16=x["rec16"], flex_rec32=x["rec32"], flex_ok=x["ok"], flex_words=x["fixed"],
+                 flex_raw=x["raw"], flex_status=x["status"], flex_chosen=x["chosen"],
+                 flex_v32=None if x["v32"] is None else x["v32"].cpu().numpy())
+    return d
+
+
+#: ``finish_flex`` reads the 1600 family's plane (``v``, its ``v16``)
+LAYER = L.ProtocolLayer("flex", (1600,), lambda fs_ch, rate: P.plan_flex(fs_ch), "flex", decode_stream, channel_of, FlexChannel, FlexResult,
+                        keys_of=_stage_keys)
+PLANE_RATES, finish_flex, flex_result, stage_keys = LAYER.rates, LAYER.finish, LAYER.result_of, LAYER.stage_keys
+
+
 class FlexDecoder(L.StoredTheta):
     """A FLEX decoder for one discriminator stream from Python (``protocol_layer.StoredTheta``): ``finish()`` gives a
     ``FlexResult`` of one channel, ``stages()`` ``decode_stream``'s output with the planes on the host, and ``hits``."""
@@ -419,34 +440,3 @@ class FlexDecoder(L.StoredTheta):
         st = decode_stream(theta, self.plan, self.centre, hits, pats, v16)
         st["hits"] = hits
         return st, FlexResult(channels=[channel_of(st, self.plan.fs_ch, 0, 0.0, None)], sample_rate=self.plan.fs_ch)
-
-
-# ---- the layer of the second pass (describe.py) ---------------------------------------------------------------------------------
-
-PLANE_RATES = (1600,)  # the families whose integrated plane ``finish_flex`` reads from section 25's dicts (``v``)
-
-
-def finish_flex(lanes, found) -> list:
-    """Per lane of the pass (``found``: its dict of ``identify.finish_identify``) the output of ``decode_stream`` with ``plan`` (the
-    ``FlexPlan``) and ``note``, or a dict of ``note`` alone where nothing is decoded: the channel is not of the 1600 family, its
-    rate does not fit or nothing was searched.  It reuses section 25's hits and plane and runs no second search."""
-    return L.finish_lanes(lanes, found, 1600, P.plan_flex, "flex",
-                          lambda theta, plan, centre, hits, v: decode_stream(theta, plan, centre, hits, I.patterns_for(1600), v))
-
-
-def flex_result(channels, lanes, decoded, sample_rate: float, center_freq: float | None = None) -> FlexResult:
-    """The ``FlexResult`` of the pass: ``channels`` the finder's, ``decoded`` the dicts of ``finish_flex``."""
-    return L.layer_result(FlexResult, FlexChannel, channel_of, channels, lanes, decoded, sample_rate, center_freq)
-
-
-def stage_keys(describer, j: int, lane, keep: bool) -> dict:
-    """This layer's keys of ``ChannelDescriber.stages()`` for channel ``j``: ``flex_frames`` ((m, s, mode) per decoded frame, None
-    where the channel is no FLEX channel) and, with ``keep``, ``flex_words``, ``flex_raw``, ``flex_status`` ([F][5][4][88]),
-    ``flex_chosen``, ``flex_rec16``, ``flex_rec32``, ``flex_ok``, ``flex_v32`` and ``flex_plan``."""
-    x = describer.finish_flex()[j]
-    d = dict(flex_frames=x.get("rows"))
-    if keep and "rows" in x:
-        d.update(flex_plan=x["plan"], flex_rec16=x["rec16"], flex_rec32=x["rec32"], flex_ok=x["ok"], flex_words=x["fixed"],
-                 flex_raw=x["raw"], flex_status=x["status"], flex_chosen=x["chosen"],
-                 flex_v32=None if x["v32"] is None else x["v32"].cpu().numpy())
-    return d

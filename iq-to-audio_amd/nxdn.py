@@ -469,48 +469,24 @@ def channel_of(st: dict, fs_ch: float, keyed_from: int, offset_hz: float, freq_h
     return out
 
 
+# ---- the layer of the second pass (describe.py) ---------------------------------------------------------------------------------
+
+#: ``finish_nxdn`` reads the planes of both NXDN families; ``stages()`` shows ``nxdn_rows`` ((m, s) per frame, None where the channel
+#: is no NXDN channel) and, with ``keep_stages``, ``nxdn_plan`` and these
+LAYER = L.ProtocolLayer("nxdn", (4800, 2400), P.plan_nxdn, "nxdn", decode_stream, channel_of, NxdnChannel, NxdnResult,
+                        keys=("bits", "levels", "classes", "info", "rec"))
+PLANE_RATES, finish_nxdn, nxdn_result, stage_keys = LAYER.rates, LAYER.finish, LAYER.result_of, LAYER.stage_keys
+
+
 class NxdnDecoder(L.StoredTheta):
     """An NXDN decoder for one discriminator stream from Python (``protocol_layer.StoredTheta``) at ``rate`` symbols/s (4800 or
     2400): ``finish()`` gives an ``NxdnResult`` of one channel, ``stages()`` ``decode_stream``'s output with the plane on the
     host, and ``hits``."""
 
-    planes = ("v",)
-    patterns, result = NXDN_PATTERNS, NxdnResult
-    decode_stream, channel_of = staticmethod(decode_stream), staticmethod(channel_of)
+    patterns, layer = NXDN_PATTERNS, LAYER
 
     def __init__(self, fs_ch: float, centre: int = 0, rate: int = 4800):
         self.rate = int(rate)
         self.plan = P.plan_nxdn(fs_ch, self.rate)
         self.centre = int(centre)
         self.reset()
-
-
-# ---- the layer of the second pass (describe.py) ---------------------------------------------------------------------------------
-
-PLANE_RATES = (4800, 2400)  # the families whose integrated plane ``finish_nxdn`` reads from section 25's dicts (``v``)
-
-
-def finish_nxdn(lanes, found) -> list:
-    """Per lane of the pass (``found``: its dict of ``identify.finish_identify``) the output of ``decode_stream`` with ``plan`` (the
-    ``NxdnPlan``) and ``note``, or a dict of ``note`` alone where nothing is decoded: the channel is of neither NXDN family, its
-    rate does not fit or nothing was searched.  ``protocol_layer.finish_lanes`` once per symbol rate, merged by lane: a lane
-    belongs to one family at the most.  It reuses section 25's hits and plane and runs no second search."""
-    out = None
-    for rate in PLANE_RATES:
-        pats = I.patterns_for(rate)
-        got = L.finish_lanes(lanes, found, rate, lambda fs_ch, rate=rate: P.plan_nxdn(fs_ch, rate), "nxdn",
-                             lambda theta, plan, centre, hits, v, pats=pats: decode_stream(theta, plan, centre, hits, pats, v))
-        out = got if out is None else [b if d["rate"] == rate else a for a, b, d in zip(out, got, found)]
-    return out
-
-
-def nxdn_result(channels, lanes, decoded, sample_rate: float, center_freq: float | None = None) -> NxdnResult:
-    """The ``NxdnResult`` of the pass: ``channels`` the finder's, ``decoded`` the dicts of ``finish_nxdn``."""
-    return L.layer_result(NxdnResult, NxdnChannel, channel_of, channels, lanes, decoded, sample_rate, center_freq)
-
-
-def stage_keys(describer, j: int, lane, keep: bool) -> dict:
-    """This layer's keys of ``ChannelDescriber.stages()`` for channel ``j``: ``nxdn_rows`` ((m, s) per frame, None where the channel
-    is no NXDN channel) and, with ``keep``, ``nxdn_plan``, ``nxdn_bits``, ``nxdn_levels``, ``nxdn_classes``, ``nxdn_info`` and
-    ``nxdn_rec``."""
-    return L.layer_stage_keys("nxdn", describer.finish_nxdn()[j], ("bits", "levels", "classes", "info", "rec"), keep)

@@ -38,7 +38,7 @@ TRELLIS_POINTS = ((0, 15, 12, 3), (4, 11, 8, 7), (13, 2, 1, 14), (9, 6, 5, 10)) 
 INTERLEAVE = tuple(x for r in range(4) for k in range(13 if r == 0 else 12) for x in (8 * k + 2 * r, 8 * k + 2 * r + 1))
 GF_POLY = 0x43  # x^6 + x + 1
 RS_ROOTS = 12  # alpha^1 .. alpha^12
-CRC_POLY = 0x1021
+CRC_POLY = L.CRC_POLY
 DUIDS = {0x0: "hdu", 0x5: "ldu1", 0xA: "ldu2", 0x3: "tdu", 0xF: "tdulc", 0x7: "tsbk", 0xC: "pdu"}
 LCO = {0: "group", 3: "unit"}
 HANG_S = 0.360  # a call with no frame for longer closes at its last frame
@@ -62,22 +62,8 @@ NEED_TSBK = tuple(symbol_of((TSBK_FIRST + TSBK_BITS * (b + 1) - 1) // 2) + 1 for
 # ---- the checks and the fields (host, integers) ---------------------------------------------------------------------------------
 
 
-def _gf_tables() -> tuple:
-    exp, log, x = [0] * 126, [0] * 64, 1
-    for i in range(63):
-        exp[i], log[x] = x, i
-        x <<= 1
-        if x & 0x40:
-            x ^= GF_POLY
-    exp[63:126] = exp[0:63]
-    return tuple(exp), tuple(log)
-
-
-_EXP, _LOG = _gf_tables()
-
-
-def gf_mul(a: int, b: int) -> int:
-    return 0 if a == 0 or b == 0 else _EXP[_LOG[a] + _LOG[b]]
+_EXP, _LOG, gf_mul = L.gf_tables(GF_POLY, 6)
+info_bytes, crc_ccitt = L.info_bytes, L.crc_ccitt  # the bytes of information words; CRC_POLY from 0
 
 
 def check_lc(hexbits) -> bool:
@@ -92,34 +78,10 @@ def check_lc(hexbits) -> bool:
     return True
 
 
-def _crc_table() -> tuple:
-    table = []
-    for byte in range(256):
-        crc = byte << 8
-        for _ in range(8):
-            crc = ((crc << 1) ^ CRC_POLY) & 0xFFFF if crc & 0x8000 else (crc << 1) & 0xFFFF
-        table.append(crc)
-    return tuple(table)
-
-
-_CRC = _crc_table()
-
-
-def crc_ccitt(data) -> int:
-    crc = 0
-    for byte in data:
-        crc = ((crc << 8) & 0xFFFF) ^ _CRC[(crc >> 8) ^ int(byte)]
-    return crc
-
-
 def check_tsbk(by) -> bool:
     """Whether the complemented CRC-CCITT of bytes 0 .. 9 of a block equals bytes 10 .. 11."""
     by = [int(b) for b in by]
     return (crc_ccitt(by[:10]) ^ 0xFFFF) == (by[10] << 8 | by[11])
-
-
-def info_bytes(words) -> list:
-    return [(int(w) >> s) & 0xFF for w in words for s in (24, 16, 8, 0)]
 
 
 def info_hexbits(words) -> list:
@@ -488,35 +450,18 @@ def channel_of(st: dict, fs_ch: float, keyed_from: int, offset_hz: float, freq_h
     return out
 
 
+# ---- the layer of the second pass (describe.py) ---------------------------------------------------------------------------------
+
+#: ``finish_p25`` reads the 4800 family's plane; ``stages()`` shows ``p25_rows`` ((m, s) per frame, None where the channel is no P25
+#: channel) and, with ``keep_stages``, ``p25_plan`` and these
+LAYER = L.ProtocolLayer("p25", (4800,), lambda fs_ch, rate: P.plan_p25(fs_ch), "p25", decode_stream, channel_of, P25Channel, P25Result,
+                        keys=("bits", "levels", "nid", "info", "rec"))
+PLANE_RATES, finish_p25, p25_result, stage_keys = LAYER.rates, LAYER.finish, LAYER.result_of, LAYER.stage_keys
+
+
 class P25Decoder(L.StoredTheta):
     """A P25 decoder for one discriminator stream from Python (``protocol_layer.StoredTheta``): ``finish()`` gives a
     ``P25Result`` of one channel, ``stages()`` ``decode_stream``'s output with the plane on the host, and ``hits``."""
 
     plan_of = staticmethod(P.plan_p25)
-    planes = ("v",)
-    patterns, result = P25_PATTERNS, P25Result
-    decode_stream, channel_of = staticmethod(decode_stream), staticmethod(channel_of)
-
-
-# ---- the layer of the second pass (describe.py) ---------------------------------------------------------------------------------
-
-PLANE_RATES = (4800,)  # the families whose integrated plane ``finish_p25`` reads from section 25's dicts (``v``)
-
-
-def finish_p25(lanes, found) -> list:
-    """Per lane of the pass (``found``: its dict of ``identify.finish_identify``) the output of ``decode_stream`` with ``plan`` (the
-    ``P25Plan``) and ``note``, or a dict of ``note`` alone where nothing is decoded: the channel is not of the 4800 family, its
-    rate does not fit or nothing was searched.  It reuses section 25's hits and plane and runs no second search."""
-    return L.finish_lanes(lanes, found, 4800, P.plan_p25, "p25",
-                          lambda theta, plan, centre, hits, v: decode_stream(theta, plan, centre, hits, I.patterns_for(4800), v))
-
-
-def p25_result(channels, lanes, decoded, sample_rate: float, center_freq: float | None = None) -> P25Result:
-    """The ``P25Result`` of the pass: ``channels`` the finder's, ``decoded`` the dicts of ``finish_p25``."""
-    return L.layer_result(P25Result, P25Channel, channel_of, channels, lanes, decoded, sample_rate, center_freq)
-
-
-def stage_keys(describer, j: int, lane, keep: bool) -> dict:
-    """This layer's keys of ``ChannelDescriber.stages()`` for channel ``j``: ``p25_rows`` ((m, s) per frame, None where the channel
-    is no P25 channel) and, with ``keep``, ``p25_plan``, ``p25_bits``, ``p25_levels``, ``p25_nid``, ``p25_info`` and ``p25_rec``."""
-    return L.layer_stage_keys("p25", describer.finish_p25()[j], ("bits", "levels", "nid", "info", "rec"), keep)
+    patterns, layer = P25_PATTERNS, LAYER

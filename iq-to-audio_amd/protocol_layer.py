@@ -3,13 +3,17 @@ layer to the second pass"): the stored discriminator stream of one channel and i
 the shape of a device call on host rows (``device_rows``, ``slice_hits``) and the checks in front of one (``slice_frames``,
 ``word_rows``, ``frame_classes``), the keep rule across a protocol's patterns (``strongest_hits``, ``sync_hits``), the per-lane
 loop of a layer's ``finish_*`` (``finish_lanes``), its result builder (``layer_result``), ``mostly_inverted``, its keys of
-``stages()`` (``layer_stage_keys``) and the mixins of the result classes (``JsonRecord``, ``ChannelLabel``, ``ChannelLines``).  A
-layer's module keeps its plan, its checks, its parser and its dataclasses.  Nothing here touches the GPU at import; ``identify.py``, which the layers import, imports this module in turn."""
+``stages()`` (``layer_stage_keys``), the declaration that ties these to one layer (``ProtocolLayer``: a module's ``LAYER``, with
+``finish``, ``result_of`` and ``stage_keys``), the checks that more than one layer runs (``info_bytes``, ``crc_ccitt``,
+``gf_tables``) and the mixins of the result classes (``JsonRecord``, ``ChannelLabel``, ``ChannelLines``).  A layer's module keeps
+its plan, its own checks, its parser and its dataclasses.  Nothing here touches the GPU at import; ``identify.py``, which the
+layers import, imports this module in turn."""
 from __future__ import annotations
 
 import ctypes
 from ctypes import c_int32, c_int64
-from dataclasses import asdict
+from dataclasses import asdict, dataclass
+from typing import Callable
 
 import numpy as np
 
@@ -39,13 +43,13 @@ class StoredTheta:
     sample at ``fs_ch``), ``finish()`` once (the layer's result of one channel), ``stages()`` for the tests, ``reset()``.
     ``centre``: section 23's centre of the quantised stream.  The subclass names its plan function (``ValueError`` where
     ``fs_ch`` does not fit), the device planes that ``stages()`` moves to the host, and either what ``_decode`` runs (the
-    ``patterns`` searched for on the plan's one integrated plane, the module's ``decode_stream`` and ``channel_of`` as
-    staticmethods, its ``result`` class) or a ``_decode(theta)`` of its own: (the stages of the stream, its result)."""
+    ``patterns`` searched for on the plan's one integrated plane and the module's ``LAYER``, for its ``decode_stream``,
+    ``channel_of`` and ``result``) or a ``_decode(theta)`` of its own: (the stages of the stream, its result)."""
 
     plan_of = None
-    planes = ()
+    planes = ("v",)
     patterns = ()
-    decode_stream = channel_of = result = None
+    layer = None
 
     def __init__(self, fs_ch: float, centre: int = 0):
         self.plan = type(self).plan_of(fs_ch)
@@ -73,9 +77,9 @@ class StoredTheta:
 
         v = I.integrate(theta, self.plan.ident, self.centre)
         _, hits = I.search(v, self.plan.ident, self.patterns)
-        st = self.decode_stream(theta, self.plan, self.centre, hits, self.patterns, v)
+        st = self.layer.decode_stream(theta, self.plan, self.centre, hits, self.patterns, v)
         st["hits"] = hits
-        return st, self.result(channels=[self.channel_of(st, self.plan.fs_ch, 0, 0.0, None)], sample_rate=self.plan.fs_ch)
+        return st, self.layer.result(channels=[self.layer.channel_of(st, self.plan.fs_ch, 0, 0.0, None)], sample_rate=self.plan.fs_ch)
 
     def stages(self) -> dict:
         """The stages of ``_decode`` with the planes on the host."""
@@ -219,6 +223,97 @@ def layer_result(result, channel, channel_of, channels, lanes, decoded, sample_r
         else:
             chans.append(channel_of(st, lane.plan.fs_ch, lane.keyed_from, ch.offset_hz, freq))
     return result(channels=chans, sample_rate=sample_rate, center_freq=center_freq)
+
+
+@dataclass(frozen=True)
+class ProtocolLayer:
+    """A protocol layer of the second pass, declared once in its module as ``LAYER``; ``ChannelDescriber`` finds it by ``name``,
+    the module's name and the keyword of its row in ``find_layers``."""
+
+    name: str
+    rates: tuple  # the families whose channels it decodes, whose integrated plane it reads from section 25's dicts (``v``)
+    plan_of: Callable  # (fs_ch, rate) -> the layer's plan; ``ValueError`` where ``fs_ch`` does not fit
+    word: str  # the note of a channel of another family is "no ``word`` channel"
+    decode_stream: Callable  # (theta, plan, centre, hits, pats, v) -> the stages of one stream
+    channel_of: Callable  # (stages, fs_ch, keyed_from, offset_hz, freq_hz) -> the channel dataclass
+    channel: type
+    result: type
+    keys: tuple = ()  # the stages that ``stages()`` shows with ``keep_stages``, as ``<name>_<key>`` beside ``<name>_rows`` and ``<name>_plan``
+    keys_of: Callable | None = None  # (the lane's dict of ``finish``, keep) -> its keys of ``stages()``, where ``keys`` will not do
+
+    def finish(self, lanes, found) -> list:
+        """Per lane of the pass (``found``: its dict of ``identify.finish_identify``) the output of ``decode_stream`` with ``plan`` and
+        ``note``, or a dict of ``note`` alone where nothing is decoded: the channel is of none of ``rates``, its rate does not fit
+        or nothing was searched.  ``finish_lanes`` once per symbol rate, merged by lane: a lane belongs to one family at the most."""
+        from . import identify as I  # (identify imports this module)
+
+        out = None
+        for rate in self.rates:
+            pats = I.patterns_for(rate)
+            got = finish_lanes(lanes, found, rate, lambda fs_ch, rate=rate: self.plan_of(fs_ch, rate), self.word,
+                               lambda theta, plan, centre, hits, v, pats=pats: self.decode_stream(theta, plan, centre, hits, pats, v))
+            out = got if out is None else [b if d["rate"] == rate else a for a, b, d in zip(out, got, found)]
+        return out
+
+    def result_of(self, channels, lanes, decoded, sample_rate: float, center_freq: float | None = None):
+        """The ``result`` of the pass: ``channels`` the finder's, ``decoded`` the dicts of ``finish``."""
+        return layer_result(self.result, self.channel, self.channel_of, channels, lanes, decoded, sample_rate, center_freq)
+
+    def stage_keys(self, describer, j: int, lane, keep: bool) -> dict:
+        """This layer's keys of ``ChannelDescriber.stages()`` for channel ``j``."""
+        x = describer.finish_layer(self.name)[j]
+        return layer_stage_keys(self.name, x, self.keys, keep) if self.keys_of is None else self.keys_of(x, keep)
+
+
+# ---- the checks that more than one layer runs (host, integers) --------------------------------------------------------------------
+
+
+def info_bytes(words) -> list:
+    """The bytes of 32-bit information words (the first bit the MSB of word 0)."""
+    return [(int(w) >> s) & 0xFF for w in words for s in (24, 16, 8, 0)]
+
+
+CRC_POLY = 0x1021
+
+
+def _crc_table() -> tuple:
+    table = []
+    for byte in range(256):
+        crc = byte << 8
+        for _ in range(8):
+            crc = ((crc << 1) ^ CRC_POLY) & 0xFFFF if crc & 0x8000 else (crc << 1) & 0xFFFF
+        table.append(crc)
+    return tuple(table)
+
+
+_CRC = _crc_table()
+
+
+def crc_ccitt(data) -> int:
+    """CRC-CCITT of the bytes ``data``: polynomial 0x1021 from 0, MSB first, not complemented."""
+    crc = 0
+    for byte in data:
+        crc = ((crc << 8) & 0xFFFF) ^ _CRC[(crc >> 8) ^ int(byte)]
+    return crc
+
+
+def gf_tables(poly: int, bits: int) -> tuple:
+    """(exp, log, gf_mul) of GF(2^``bits``) modulo ``poly``: alpha^i for i < 2 (2^bits - 1), so that a sum of two logarithms needs
+    no reduction, the logarithms, and the product by them."""
+    size = (1 << bits) - 1
+    exp, log, x = [0] * (2 * size), [0] * (size + 1), 1
+    for i in range(size):
+        exp[i], log[x] = x, i
+        x <<= 1
+        if x >> bits:
+            x ^= poly
+    exp[size:] = exp[:size]
+    exp, log = tuple(exp), tuple(log)
+
+    def gf_mul(a: int, b: int) -> int:
+        return 0 if a == 0 or b == 0 else exp[log[a] + log[b]]
+
+    return exp, log, gf_mul
 
 
 class JsonRecord:

@@ -24,7 +24,6 @@ import numpy as np
 from . import dsp_plan as P
 from . import identify as I
 from . import protocol_layer as L
-from .p25 import crc_ccitt
 
 YSF_PATTERNS = tuple(p for p in I.PATTERNS if p.protocol == "ysf")  # one word; a hit with C < 0 is the same word, spectrum inverted
 SYNC = YSF_PATTERNS[0].word
@@ -32,7 +31,7 @@ SYNC_SYMBOLS = 20
 LEVEL_SCALE = 584  # A and Dc are 584 times the outer level and the DC
 GOLAY_POLY = 0xC75
 GOLAY_MAX_DISTANCE = 3
-CRC_POLY = 0x1021
+CRC_POLY = L.CRC_POLY
 INTERLEAVE_ROWS = {100: 5, 180: 9}  # coded dibit i of a block of 20 R dibits travels as dibit 20 (i mod R) + i // R
 PN9_FIRST = (1, 0, 0, 1, 0, 0, 1, 1, 1)  # the whitening stream: b[n] = b[n - 5] ^ b[n - 9] behind these, MSB first
 HANG_S = 0.360  # a transmission with no frame for longer closes at its last frame
@@ -60,6 +59,7 @@ def pn9(count: int) -> bytes:
 
 
 _PN9 = pn9(20)
+info_bytes, crc_ccitt = L.info_bytes, L.crc_ccitt  # the bytes of information words; CRC_POLY from 0
 
 
 def dewhiten(data) -> bytes:
@@ -70,10 +70,6 @@ def dewhiten(data) -> bytes:
 def crc16(data) -> int:
     """The CRC of the FICH and of every DCH: CRC-CCITT from 0, complemented."""
     return crc_ccitt(data) ^ 0xFFFF
-
-
-def info_bytes(words) -> list:
-    return [(int(w) >> s) & 0xFF for w in words for s in (24, 16, 8, 0)]
 
 
 def check_fich(words) -> bool:
@@ -382,36 +378,18 @@ def channel_of(st: dict, fs_ch: float, keyed_from: int, offset_hz: float, freq_h
     return out
 
 
+# ---- the layer of the second pass (describe.py) ---------------------------------------------------------------------------------
+
+#: ``finish_ysf`` reads the 4800 family's plane; ``stages()`` shows ``ysf_rows`` ((m, s) per frame, None where the channel is no YSF
+#: channel) and, with ``keep_stages``, ``ysf_plan`` and these
+LAYER = L.ProtocolLayer("ysf", (4800,), lambda fs_ch, rate: P.plan_ysf(fs_ch), "ysf", decode_stream, channel_of, YsfChannel, YsfResult,
+                        keys=("bits", "levels", "fich", "frec", "classes", "info", "rec"))
+PLANE_RATES, finish_ysf, ysf_result, stage_keys = LAYER.rates, LAYER.finish, LAYER.result_of, LAYER.stage_keys
+
+
 class YsfDecoder(L.StoredTheta):
     """A YSF decoder for one discriminator stream from Python (``protocol_layer.StoredTheta``): ``finish()`` gives a
     ``YsfResult`` of one channel, ``stages()`` ``decode_stream``'s output with the plane on the host, and ``hits``."""
 
     plan_of = staticmethod(P.plan_ysf)
-    planes = ("v",)
-    patterns, result = YSF_PATTERNS, YsfResult
-    decode_stream, channel_of = staticmethod(decode_stream), staticmethod(channel_of)
-
-
-# ---- the layer of the second pass (describe.py) ---------------------------------------------------------------------------------
-
-PLANE_RATES = (4800,)  # the families whose integrated plane ``finish_ysf`` reads from section 25's dicts (``v``)
-
-
-def finish_ysf(lanes, found) -> list:
-    """Per lane of the pass (``found``: its dict of ``identify.finish_identify``) the output of ``decode_stream`` with ``plan`` (the
-    ``YsfPlan``) and ``note``, or a dict of ``note`` alone where nothing is decoded: the channel is not of the 4800 family, its
-    rate does not fit or nothing was searched.  It reuses section 25's hits and plane and runs no second search."""
-    return L.finish_lanes(lanes, found, 4800, P.plan_ysf, "ysf",
-                          lambda theta, plan, centre, hits, v: decode_stream(theta, plan, centre, hits, I.patterns_for(4800), v))
-
-
-def ysf_result(channels, lanes, decoded, sample_rate: float, center_freq: float | None = None) -> YsfResult:
-    """The ``YsfResult`` of the pass: ``channels`` the finder's, ``decoded`` the dicts of ``finish_ysf``."""
-    return L.layer_result(YsfResult, YsfChannel, channel_of, channels, lanes, decoded, sample_rate, center_freq)
-
-
-def stage_keys(describer, j: int, lane, keep: bool) -> dict:
-    """This layer's keys of ``ChannelDescriber.stages()`` for channel ``j``: ``ysf_rows`` ((m, s) per frame, None where the channel
-    is no YSF channel) and, with ``keep``, ``ysf_plan``, ``ysf_bits``, ``ysf_levels``, ``ysf_fich``, ``ysf_frec``, ``ysf_classes``,
-    ``ysf_info`` and ``ysf_rec``."""
-    return L.layer_stage_keys("ysf", describer.finish_ysf()[j], ("bits", "levels", "fich", "frec", "classes", "info", "rec"), keep)
+    patterns, layer = YSF_PATTERNS, LAYER

@@ -1,141 +1,37 @@
-"""Cost of the DMR burst decoding (--find-dmr) on the device-resident capture of profiles/find_timing.py
-(60 s at 10 MS/s int16, the capture and the method of profiles/flex_timing.py) with a DMR base channel added: the test script of
-tests/dmr_model.py (idle bursts, a header, three superframes, a terminator, a CSBK) in a loop of 48 slots, at -3.6 MHz, written
-into the capture on the device.  The finder runs once; its channels then go through ``ChannelDescriber`` in the blocks
-``find_channels`` uses, with ``identify`` alone (the yardstick) and with ``dmr`` beside it, alternating in one process.  By device
-events behind one warm-up each: the whole second pass with its results (median of REPEATS).  Then the two entry points on their
-own, on the DMR lane's plane: median of REPEATS each.  Prints one JSON line (kept as profiles/dmr_timing.json).  Kernel
-resources: ``make -C iq-to-audio_amd/csrc asm F=dmr``."""
+"""Cost of the DMR burst decoding (--find-dmr) by the method of profiles/layer_timing.py, with a DMR base
+channel at -3.6 MHz: the test script of tests/dmr_model.py (idle bursts, a header, three superframes, a terminator, a CSBK) in a
+loop of 48 slots.  The whole second pass with ``identify`` alone and with ``dmr`` beside it, then the two entry points on their
+own.  Prints one JSON line (kept as profiles/dmr_timing.json).  Kernel resources: ``make -C iq-to-audio_amd/csrc asm F=dmr``."""
 from __future__ import annotations
 
-import importlib.util
-import json
-import math
-import sys
-import time
-from pathlib import Path
+import layer_timing as T
+from iq_to_audio_amd import dmr as X
 
-ROOT = Path(__file__).resolve().parent.parent
-sys.path.insert(0, str(ROOT))
-
-import torch  # noqa: E402
-
-from iq_to_audio_amd import describe as DS  # noqa: E402
-from iq_to_audio_amd import dmr as X  # noqa: E402
-from iq_to_audio_amd import dsp_plan as P  # noqa: E402
-from iq_to_audio_amd import find as FD  # noqa: E402
-
-
-def _load(name, folder):
-    spec = importlib.util.spec_from_file_location(name, ROOT / folder / f"{name}.py")
-    mod = importlib.util.module_from_spec(spec)
-    sys.modules[name] = mod
-    spec.loader.exec_module(mod)
-    return mod
-
-
-FT = _load("find_timing", "profiles")
-DM = _load("dmr_model", "tests")
-
-REPEATS = FT.REPEATS
+DM = T.load("dmr_model", "tests")
 FC = 145.0e6
-DMR_OFFSET, DMR_AMP, LOOP_SLOTS = -3.6e6, 0.01, 48  # (the amplitude of profiles/flex_timing.py's added channel)
+LOOP_SLOTS = 48
 
 
 def add_dmr(capture) -> int:
-    """Adds the DMR channel to the device capture in place, a second at a time: the script's symbols in a loop, every symbol one
-    entry of a level table.  Returns the slots sent."""
+    """The script's symbols in a loop, every symbol one entry of the level table.  Returns the slots sent."""
     table = DM.base_station(list(DM.SCRIPT) + [None] * (LOOP_SLOTS - len(DM.SCRIPT)))
     assert len(table) == 144 * LOOP_SLOTS
-    levels = torch.tensor(table, dtype=torch.float64, device="cuda")
-    fs, n = FT.FS, int(capture.numel()) // 2
-    phase = 0.0
-    for a in range(0, n, int(fs)):
-        b = min(n, a + int(fs))
-        k = torch.arange(a, b, dtype=torch.int64, device="cuda")
-        symbol = torch.div(k * 4800, int(fs), rounding_mode="floor") % len(table)
-        turns = torch.cumsum(levels[symbol] * (DM.DEV / fs), 0) + phase
-        phase = float(turns[-1]) % 1.0
-        angle = 2.0 * math.pi * ((turns + (k.to(torch.float64) * (DMR_OFFSET / fs))) % 1.0)
-        z = torch.stack([torch.cos(angle), torch.sin(angle)], dim=1) * (DMR_AMP * 32768.0)
-        capture[2 * a : 2 * b] += torch.round(z).to(torch.int16).reshape(-1)
-    return int(n * 4800 // (int(fs) * 144))
+    T.add_channel(capture, table, 4800, DM.DEV)
+    return int(capture.numel() // 2 * 4800 // (int(T.FT.FS) * 144))
 
 
-def second_pass(capture, plan, fin, channels, dmr: bool):
-    """One whole second pass -> (device ms by events, wall ms, the describer)."""
-    describer = DS.ChannelDescriber(plan, fin, channels, "s16", "iq", keying=True, identify=True, dmr=dmr)
-    n = plan.n_samples
-    e = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    e[0].record()
-    for a in range(0, n, FD.BLOCK_FRAMES):
-        describer.process(capture[2 * a : 2 * min(n, a + FD.BLOCK_FRAMES)])
-    describer.keying_result(FC)
-    describer.protocol_result(FC)
-    if dmr:
-        describer.dmr_result(FC)
-    e[1].record()
-    torch.cuda.synchronize()
-    return e[0].elapsed_time(e[1]), (time.perf_counter() - t0) * 1e3, describer
+def summary(ch) -> dict:
+    return dict(offset_hz=ch.offset_hz, note=ch.note, kinds=ch.kinds, no_level=ch.no_level, cut=ch.cut, slot_refused=ch.slot_refused,
+                bptc_failed=ch.bptc_failed, check_failed=ch.check_failed, tact_fixed=ch.tact_fixed, idle=ch.idle,
+                calls=len(ch.calls), terminated=sum(c.terminated for c in ch.calls), bursts=len(ch.bursts))
 
 
-def timed(fn) -> float:
-    """Device ms of one call of ``fn`` by events."""
-    e = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
-    torch.cuda.synchronize()
-    e[0].record()
-    fn()
-    e[1].record()
-    torch.cuda.synchronize()
-    return e[0].elapsed_time(e[1])
-
-
-def main():
-    torch.cuda.set_device(0)
-    capture = FT.make_capture()
-    sent = add_dmr(capture)
-    n = int(capture.numel()) // 2
-    plan = P.plan_find(FT.FS, n)
-    out = dict(capture=f"{FT.SECS:.0f} s @ {FT.FS / 1e6:.0f} MS/s cs16, device-resident, with a DMR base channel at {DMR_OFFSET:+.0f} Hz",
-               device=torch.cuda.get_device_name(0), repeats=REPEATS, slots_sent=sent)
-    finder = FD.ChannelFinder(plan, "s16")
-    for a in range(0, n, FD.BLOCK_FRAMES):
-        finder.process(capture[2 * a : 2 * min(n, a + FD.BLOCK_FRAMES)])
-    fin, found = finder.finish(), finder.result(FC)
-    runs = {False: [], True: []}
-    for dmr in (False, True):
-        second_pass(capture, plan, fin, found.channels, dmr)  # warm-up: tap fragments, code objects, pools
-    last = None
-    for _ in range(REPEATS):  # alternating
-        for dmr in (False, True):
-            r = second_pass(capture, plan, fin, found.channels, dmr)
-            runs[dmr].append(r)
-            last = r[2] if dmr else last
-    for dmr, tag in ((False, "identify"), (True, "dmr")):
-        out[f"{tag}_device_ms"], out[f"{tag}_wall_ms"] = FT.med([r[0] for r in runs[dmr]]), FT.med([r[1] for r in runs[dmr]])
-    out["keying"] = [line.strip() for line in last.keying_result(FC).lines()]
-    out["protocols"] = [line.strip() for line in last.protocol_result(FC).lines()]
-    result = last.dmr_result(FC)
-    out["channels"] = [dict(offset_hz=ch.offset_hz, note=ch.note, kinds=ch.kinds, no_level=ch.no_level, cut=ch.cut, slot_refused=ch.slot_refused,
-                            bptc_failed=ch.bptc_failed, check_failed=ch.check_failed, tact_fixed=ch.tact_fixed, idle=ch.idle,
-                            calls=len(ch.calls), terminated=sum(c.terminated for c in ch.calls), bursts=len(ch.bursts)) for ch in result.channels]
-    out["first_lines"] = result.lines()[:3]
-    entries = []
-    for ch, lane, st in zip(found.channels, last.lanes(), last.finish_dmr()):
-        if "rows" not in st or not len(st["rows"]):
-            continue
-        dplan, rows = st["plan"], st["rows"]
-        entry = dict(offset_hz=ch.offset_hz, fs_ch=lane.plan.fs_ch, sps=dplan.sps, samples=int(st["v"].numel()), bursts=len(rows))
-        X.slice_bursts(st["v"], rows, dplan)  # warm-up
-        entry["slice_ms"] = FT.med([timed(lambda: X.slice_bursts(st["v"], rows, dplan)) for _ in range(REPEATS)])
-        X.decode_bursts(st["bits"], rows[:, 2])  # warm-up
-        entry["decode_ms"] = FT.med([timed(lambda: X.decode_bursts(st["bits"], rows[:, 2])) for _ in range(REPEATS)])
-        entries.append(entry)
-    out["entry_points"] = entries
-    print(json.dumps(out))
+def entry_points(st, entry) -> dict:
+    entry.update(samples=int(st["v"].numel()), bursts=len(st["rows"]))
+    entry["slice_ms"] = T.entry_ms(lambda: X.slice_bursts(st["v"], st["rows"], st["plan"]))
+    entry["decode_ms"] = T.entry_ms(lambda: X.decode_bursts(st["bits"], st["rows"][:, 2]))
+    return entry
 
 
 if __name__ == "__main__":
-    main()
+    T.run("dmr", FC, "a DMR base channel", add_dmr, "slots_sent", summary, 3, entry_points)

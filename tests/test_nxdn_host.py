@@ -321,9 +321,9 @@ def test_result_round_trips_through_json():
 
 
 def test_the_row_of_the_layer_table():
-    assert FL.FIND_EVERY_BRANCH[: len(FL.FIND_ALL_BRANCHES)] == FL.FIND_ALL_BRANCHES  # still a prefix: the rows before this one stay where they were
-    (row,) = [l for l in FL.FIND_EVERY_BRANCH if l.name == "nxdn"]
-    assert FL.FIND_EVERY_BRANCH.index(row) > [l.name for l in FL.FIND_EVERY_BRANCH].index("ysf")
+    assert [l.name for l in FL.FIND_BRANCHES[:2]] == ["dmr", "p25"]  # still a prefix: the rows before this one stay where they were
+    (row,) = [l for l in FL.FIND_BRANCHES if l.name == "nxdn"]
+    assert FL.FIND_BRANCHES.index(row) == 3 > [l.name for l in FL.FIND_BRANCHES].index("ysf")
     assert (row.flag, row.section, row.suffix, row.inline, row.needs, row.option) == ("find_nxdn", 34, "nxdn", False, "identify", "--find-nxdn")
     on = dict(describe=True, keying=True, identify=True)
     assert [l.name for l in FL.active_layers({**on, "nxdn": True})] == ["describe", "keying", "identify", "nxdn"]
@@ -365,7 +365,7 @@ def test_cli_flags(capsys):
     assert "--find-nxdn cannot be combined with --ft." in _usage_error(base + ["--find-nxdn", "--ft", "433200000"], capsys)
     assert "--find-nxdn needs --in." in _usage_error(["--find-nxdn"], capsys)
     text = "".join(cli.build_parser().format_help().split())
-    (row,) = [l for l in FL.FIND_EVERY_BRANCH if l.name == "nxdn"]
+    (row,) = [l for l in FL.FIND_BRANCHES if l.name == "nxdn"]
     assert "--find-nxdn" in text and "".join(row.help.split()) in text
 
 

@@ -389,8 +389,9 @@ def test_result_round_trips_through_json():
 
 
 def test_the_branches_of_the_layer_table():
-    assert FL.FIND_ALL_BRANCHES[: len(FL.FIND_BRANCHES)] == FL.FIND_BRANCHES and [l.name for l in FL.FIND_ALL_BRANCHES] == ["dmr", "p25"]
-    row = FL.FIND_ALL_BRANCHES[-1]
+    assert [l.name for l in FL.FIND_BRANCHES[:2]] == ["dmr", "p25"]  # the rows before this one stay where they were
+    (row,) = [l for l in FL.FIND_BRANCHES if l.name == "p25"]
+    assert FL.FIND_BRANCHES.index(row) == 1
     assert (row.name, row.flag, row.section, row.suffix, row.inline, row.needs, row.option) == ("p25", "find_p25", 31, "p25", False, "identify", "--find-p25")
     on = dict(describe=True, keying=True, identify=True)
     assert [l.name for l in FL.active_layers({**on, "p25": True})] == ["describe", "keying", "identify", "p25"]
@@ -433,7 +434,8 @@ def test_cli_flags(capsys):
     assert "--find-p25 needs --in." in _usage_error(["--find-p25"], capsys)
     assert "--find-auto needs --find-top." in _usage_error(base + ["--find-p25", "--find-auto"], capsys)
     text = "".join(cli.build_parser().format_help().split())
-    assert "--find-p25" in text and "".join(FL.FIND_ALL_BRANCHES[-1].help.split()) in text
+    (row,) = [l for l in FL.FIND_BRANCHES if l.name == "p25"]
+    assert "--find-p25" in text and "".join(row.help.split()) in text
 
 
 def test_package_surface():

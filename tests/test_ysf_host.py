@@ -361,9 +361,9 @@ def test_result_round_trips_through_json():
 
 
 def test_the_branches_of_the_layer_table():
-    assert FL.FIND_EVERY_BRANCH[: len(FL.FIND_ALL_BRANCHES)] == FL.FIND_ALL_BRANCHES  # a prefix: the rows before this one stay where they were
-    (row,) = [l for l in FL.FIND_EVERY_BRANCH if l.name == "ysf"]
-    assert FL.FIND_EVERY_BRANCH.index(row) >= len(FL.FIND_ALL_BRANCHES)
+    assert [l.name for l in FL.FIND_BRANCHES[:2]] == ["dmr", "p25"]  # a prefix: the rows before this one stay where they were
+    (row,) = [l for l in FL.FIND_BRANCHES if l.name == "ysf"]
+    assert FL.FIND_BRANCHES.index(row) == 2
     assert (row.flag, row.section, row.suffix, row.inline, row.needs, row.option) == ("find_ysf", 32, "ysf", False, "identify", "--find-ysf")
     on = dict(describe=True, keying=True, identify=True)
     assert [l.name for l in FL.active_layers({**on, "ysf": True})] == ["describe", "keying", "identify", "ysf"]
@@ -409,7 +409,7 @@ def test_cli_flags(capsys):
     assert "--find-ysf needs --in." in _usage_error(["--find-ysf"], capsys)
     assert "--find-auto needs --find-top." in _usage_error(base + ["--find-ysf", "--find-auto"], capsys)
     text = "".join(cli.build_parser().format_help().split())
-    (row,) = [l for l in FL.FIND_EVERY_BRANCH if l.name == "ysf"]
+    (row,) = [l for l in FL.FIND_BRANCHES if l.name == "ysf"]
     assert "--find-ysf" in text and "".join(row.help.split()) in text
 
 
