@@ -205,7 +205,12 @@ typedef struct {
                                  * slots only, no raw_partials.  See iqa_mfma_ring_lanes.
                                  * bit 1: this lane's LOW tap byte is zero throughout (piece 1 of every fragment: the first
                                  * lane of a tap-row group under dsp_plan.plan_mfma(residual=True)): the kernel skips the
-                                 * q2*hi product of every k step (two matrix instructions per k step instead of three). */
+                                 * q2*hi product of every k step (two matrix instructions per k step instead of three).
+                                 * bits 8..13: rot -- afrag_dev holds dsp_plan's afrag_rot: the tap rows of either component
+                                 * rotated by rot slots so that slots 0..15 are rows whose HIGH tap byte is zero throughout
+                                 * (the edge rows of a Kaiser design), whose q1 products the kernel then does not issue.  A
+                                 * multiple of 4, at most 32, in a single-lane launch where iqa_mfma_ring_zero_rows() != 0;
+                                 * refused elsewhere.  0: not rotated.  Same sums bit for bit. */
 } iqa_mfma_lane;
 int iqa_channelize_mfma_multi(int32_t fmt, int32_t decimation, int32_t k_first, int32_t k_count,
                               int32_t outputs_per_block, const iqa_mfma_lane *lanes, int32_t n_lanes,
@@ -232,6 +237,11 @@ int32_t iqa_mfma_ring_pairs(int32_t fmt, int32_t decimation, int32_t k_first, in
  * their pairs 9..14 k steps).  The "full" precision of the host pipeline puts a filter's tap-row groups AND the residue of
  * their quantisation into such a launch as lanes (ref: the per---ft loop of the reference CLI, cli.py:683-710). */
 int32_t iqa_mfma_ring_lanes(int32_t fmt, int32_t decimation, int32_t k_first, int32_t k_count, int32_t acc32);
+/* != 0: a single-lane iqa_channelize_mfma_multi launch over these k steps takes rotated tap fragments (iqa_mfma_lane.reserved
+ * bits 8..13): int16 captures, int32 sums, contiguous slots, at most 8 k steps, 1..16 values in the row's last k step. */
+int32_t iqa_mfma_ring_zero_rows(int32_t fmt, int32_t decimation, int32_t k_first, int32_t k_count, int32_t acc32);
+/* The kernel family the calling thread's last iqa_channelize_mfma_multi launch took (diagnostics and tests; a static string). */
+const char *iqa_mfma_ring_last_kernel(void);
 /* z[m_first + i] = finish(sum_k partials_dev[k][i]): the float32 conversion, conjugation, rotation and scaling of the
  * kernels' own emission (p supplies conj_sum, rotate, rot_step, rot_base, out_scale).  1..16 buffers of double2[n_out]
  * (a filter's tap-row groups -- and, with residual quantisation, each group's second lane: dsp_plan.plan_mfma(residual=True)),

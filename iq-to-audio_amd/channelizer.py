@@ -66,6 +66,11 @@ def _launch_lanes(lanes: list, pairs: bool, outputs_per_block: int, raw_dev, n_f
         lane.conj_sum, lane.rotate = k.params.conj_sum, k.params.rotate
         lane.q_group, lane.finalize, lane.raw_partials = group.q, int(partial_out is None), int(raw_partials)
         lane.reserved = (0 if k.acc32 else 1) | (2 if group.high_only else 0)  # (bit 0: 64-bit sums; bit 1: q2 == 0)
+        # a launch of one lane over all k steps: the rotated fragments, their rot in bits 8..13 (skips the zero high tap bytes)
+        rot_dev = k.afrag_rot_dev[ps.group] if len(lanes) == 1 and not pairs and ps.k_first == 0 and ps.k_count == k.mfma.ksteps else None
+        if rot_dev is not None:
+            lane.afrag_dev = rot_dev.data_ptr()
+            lane.reserved |= group.rot << 8
         k.last_kernel = f"k_channelize_mfma_{fmt}_ring"
     N.call("iqa_channelize_mfma_pairs" if pairs else "iqa_channelize_mfma_multi", c_int32(P.FMT_CODE[fmt]),
            c_int32(k0.plan.decimation), c_int32(ps0.k_first), c_int32(ps0.k_count), c_int32(outputs_per_block), table,
@@ -84,6 +89,8 @@ class _ChannelKernel:
 
     #: set to False to force the float32 VALU kernel everywhere (tests compare the two)
     use_mfma = True
+    #: set to False to launch single lanes on the unrotated fragments (tests compare the two; read when the plan is made)
+    use_zero_rows = True
     #: data path of the MFMA kernel: "ring" (channelize_ring.hip: persistent blocks stream their contiguous run of the
     #: capture through an LDS-DMA ring, tap fragments in registers; falls back to "plain" where it does not apply:
     #: D % 4 != 0, D > 256, multi-range passes) or "plain" (channelize_mfma.hip: per-lane row loads into VGPRs)
@@ -155,6 +162,13 @@ class _ChannelKernel:
                 mp = P.plan_mfma(self.plan, acc32=ring and self.acc32,
                                  max_ksteps=self.RING_ROWS_KSTEPS if self._ring_mode == 2 else None, residual=self.residual)
                 self.afrag_dev = [D.from_numpy(g.afrag.reshape(-1).view(np.uint8)) for g in mp.groups]
+                # rotated fragments (dsp_plan.zero_high_rotation) where a single-lane launch of this kernel takes them
+                # (all k steps in one pass, a rot the kernel's lane groups can follow): None otherwise
+                self.afrag_rot_dev = [
+                    D.from_numpy(g.afrag_rot.reshape(-1).view(np.uint8))
+                    if ring and self.use_zero_rows and g.rot and g.rot % 4 == 0 and g.rot <= 32 and N.lib().iqa_mfma_ring_zero_rows(
+                        P.FMT_CODE[self.plan.fmt], self.plan.decimation, 0, mp.ksteps, int(bool(self.acc32))) else None
+                    for g in mp.groups]
                 # every pass with its variant: None = a lane of the ring kernels, else the per-lane ("plain") kernel's parameters
                 self._passes = [(ps, None if ring else N.MfmaParams(
                     reserved=0, unit=mp.groups[ps.group].unit, c_re=ps.c_re, c_im=ps.c_im, q_group=mp.groups[ps.group].q,

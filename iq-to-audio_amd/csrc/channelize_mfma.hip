@@ -447,6 +447,7 @@ static int channelize_mfma_lanes(int32_t fmt, int32_t decimation, int32_t k_firs
         if (s.raw_partials && !l.raw_partials) return fail_inval("raw partials need finalize == 0 and no partial_in");
         if (s.raw_partials && acc64) return fail_inval("raw partials are int32 sums: not with 64-bit sums");
         l.high_taps_only = (s.reserved & 2) != 0 ? 1 : 0;
+        l.zrot = (s.reserved >> 8) & 63;  // (mfma_ring_launch_multi refuses it where no kernel takes rotated fragments)
     }
     return mfma_ring_launch_multi(a, packed, n_lanes, lds, as_stream(stream), ring_mode == 2, u8, pairs, acc64);
 }
@@ -479,6 +480,15 @@ extern "C" int32_t iqa_mfma_ring_lanes(int32_t fmt, int32_t decimation, int32_t 
     if (mode == 0 || (acc64 && mode != 1)) return 0;
     return 1 | (mfma_ring_pairs_supported(decimation, k_first, ks, u8, acc64) ? 2 : 0);
 }
+
+extern "C" int32_t iqa_mfma_ring_zero_rows(int32_t fmt, int32_t decimation, int32_t k_first, int32_t k_count, int32_t acc32)
+{
+    if (decimation < 1 || fmt != IQA_FMT_S16) return 0;
+    const int ks_all = (2 * decimation + 31) / 32;
+    return mfma_ring_zedge_supported(decimation, k_first, k_count > 0 ? k_count : ks_all - k_first, false, false, acc32 == 0) ? 1 : 0;
+}
+
+extern "C" const char *iqa_mfma_ring_last_kernel(void) { return mfma_ring_last_kernel(); }
 
 extern "C" int32_t iqa_mfma_ring_pairs(int32_t fmt, int32_t decimation, int32_t k_first, int32_t k_count)
 {

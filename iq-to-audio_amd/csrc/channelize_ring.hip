@@ -34,6 +34,8 @@
 // Round 7: in launches of a single lane the loaders of the contiguous slots fetch with non-temporal loads (ring_load16; the
 // stream alone 6.0 -> 6.6 TB/s, probe/stream_probe.hip); the stream's phase against a 16-byte boundary costs nothing, aligned
 // loads with the shift done in registers and a second pass through LDS were slower.
+// Round 8: single-lane launches of the ..._half kernels whose lane carries rotated fragments (zrot) do not multiply the
+// all-zero high tap bytes of the filter's edge rows (ring_main_h16_light; 15 % less matrix-pipe time, 0.7 % at the step).
 // The forms measured against these and rejected are recorded in DESIGN.md section 6.
 //
 // Every launch goes through the lane table of mfma_ring_launch_multi (k_channelize_mfma_s16_ring_multi / _multi_half /
@@ -877,9 +879,24 @@ __device__ __forceinline__ void ring_main(const MfmaArgs &a, const RingCtx &c, c
 //     (q1, q2 of tap-row half 0 / 1, hi, lo of data-row half 0 / 1, S[s] the block sum bi + bj = s): seven instructions for
 //     the twelve products, the same integer terms in every sum; six tap operands of 8 bytes gathered once per wave, four
 //     data operands of 8 bytes read per tile.
+//   * ZEDGE (launches whose lane carries zrot != 0, dsp_plan's afrag_rot): the first and last tap rows of a Kaiser design
+//     are tiny, their high tap byte q1 is zero throughout, and of such a row's three products only q2 * hi is left.  The
+//     planner has rotated the rows of either component by zrot slots (slot s holds tap row (s - zrot) mod 64) so that
+//     slots 0..15 are such rows: the waves of even rt run ring_main_h16_light on them, the waves of odd rt this body,
+//     their rows moved by the rotation.
 template <int KS>
+__device__ __forceinline__ void ring_main_h16_light(const MfmaArgs &a, const RingCtx &c);
+
+template <int KS, bool ZEDGE = false>
 __device__ __forceinline__ void ring_main_h16(const MfmaArgs &a, const RingCtx &c)
 {
+    if constexpr (ZEDGE) {
+        if (!(c.rt & 1)) {  // (wave-uniform, like loader against multiplier)
+            ring_main_h16_light<KS>(a, c);
+            return;
+        }
+    }
+    const int zrot = ZEDGE ? a.zrot : 0;  // (odd rt: slots 32.. of a component, behind the wrap: tap rows 32 - zrot ..)
     using G = RingGeo<KS, false, false, false, true>;
     static_assert(G::SPLIT && G::R == 2, "byte planes, two slots per parity");
     constexpr int SLOT = G::SLOT, PP = G::PLANE_PITCH, NC = KS / 2, ODD = KS & 1;
@@ -995,7 +1012,7 @@ __device__ __forceinline__ void ring_main_h16(const MfmaArgs &a, const RingCtx &
             // diagonal scatter into the window of sums, 256*S1 + S2 in one int32 as in ring_main (inline asm for the same reason)
             // (lanes 16 apart meet on 12 of a half wave's 20 addresses: a 2-way serialisation per add.  Sending the lanes of odd
             // l >> 4 into a second window that the emission adds measured the same)
-            const unsigned p = lds_addr(c.s_acc + ((t * 32 + 32 * (c.rt & 1) + r16 + 4 * g + 1) & (RG_W - 1)) + (c.rt >> 1) * RG_AS);
+            const unsigned p = lds_addr(c.s_acc + ((t * 32 + 32 * (c.rt & 1) - zrot + r16 + 4 * g + 1) & (RG_W - 1)) + (c.rt >> 1) * RG_AS);
 #pragma unroll
             for (int s = 0; s < 3; ++s)
 #pragma unroll
@@ -1010,12 +1027,133 @@ __device__ __forceinline__ void ring_main_h16(const MfmaArgs &a, const RingCtx &
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
 }
 
+// The light wave of a ZEDGE launch (even rt): slots 0..31 of a component, of which 0..15 (tap-row half 0) have q1 = 0.
+//   * Per chunk eight instructions instead of twelve:
+//         Z[bj] = q2_0 . hi_bj                      (half 0: S2 alone; no S1 accumulator, no q1 fragments)
+//         S1[bj] = q1_1 . hi_bj        S2[bj] = q1_1 . lo_bj + q2_1 . hi_bj        (half 1)
+//     and on the folded odd step six instead of seven, from two of the four 8-byte reads:
+//         Z[bj] = [0 | q2_0] . [lo_bj ; hi_bj]    S1[bj] = [0 | q1_1] . [lo_bj ; hi_bj]    S2[bj] = [q1_1 | q2_1] . [lo_bj ; hi_bj]
+//   * Half 0's rows are two runs -- the filter's last rows, then its first: slots 4 g .. + 3 of a lane group hold tap rows
+//     64 - zrot + 4 g .. while 4 g < zrot and 4 g - zrot .. behind (zrot a multiple of 4, at most 32: the launcher checks) --
+//     so the scatter base differs per lane group; it is computed once per wave.  Half 1 may wrap the same way.  The halves
+//     share no output positions (the (0, 1) / (1, 0) sharing of the heavy body needs consecutive rows): 16 adds per tile.
+//   * Z goes to the add through a VALU instruction the compiler sees (+ an opaque zero): the compiler places the wait
+//     states a matrix result needs in front of its own instructions, not in front of inline asm -- fed directly, the adds
+//     sent stale registers (probe/kstep_probe.hip `zedge`).
+template <int KS>
+__device__ __forceinline__ void ring_main_h16_light(const MfmaArgs &a, const RingCtx &c)
+{
+    using G = RingGeo<KS, false, false, false, true>;
+    constexpr int SLOT = G::SLOT, PP = G::PLANE_PITCH, NC = KS / 2, ODD = KS & 1;
+    const int r16 = c.lane & 15, g = c.lane >> 4;
+    v4i_t t20[NC ? NC : 1], t1[NC ? NC : 1][2];  // q2 of tap-row half 0; q1, q2 of half 1
+    long tf[3] = {};
+    enum { TF_Z_Q20, TF_Z_Q11, TF_Q11_Q21 };  // [x | y] as in ring_main_h16
+    const v4i_t *fa = a.afrag + c.rt * 128;
+#pragma unroll
+    for (int ch = 0; ch < NC; ++ch) {
+        const v4i_t *f = fa + (2 * ch + (g >> 1)) * 8 * 64 + r16 + 32 * (g & 1);
+        t20[ch] = f[64], t1[ch][0] = f[16], t1[ch][1] = f[64 + 16];
+    }
+    if constexpr (ODD) {
+        const v4i_t *f = fa + (KS - 1) * 8 * 64 + r16;
+        const long q20 = reinterpret_cast<const long *>(f + 64)[g & 1], q11 = reinterpret_cast<const long *>(f + 16)[g & 1];
+        const long q21 = reinterpret_cast<const long *>(f + 64 + 16)[g & 1];
+        const bool up = g >> 1;
+        tf[TF_Z_Q20] = up ? q20 : 0;
+        tf[TF_Z_Q11] = up ? q11 : 0;
+        tf[TF_Q11_Q21] = up ? q21 : q11;
+    }
+#pragma unroll
+    for (int ch = 0; ch < NC; ++ch) asm volatile("" ::"v"(t20[ch]), "v"(t1[ch][0]), "v"(t1[ch][1]));
+    asm volatile("" ::"v"(tf[0]), "v"(tf[1]), "v"(tf[2]));
+    const int lane_off = r16 * PP + 16 * g;
+    int lane_off_odd[2], vzero = 0;  // [lo_0 ; hi_0], [lo_1 ; hi_1]: an offset register each, as in ring_main_h16
+    {
+        const int at = r16 * PP + 32 * (KS - 1) + 8 * (g & 1) + ((g >> 1) ? 0 : 32 * PP);
+        lane_off_odd[0] = at;
+        lane_off_odd[1] = at + 16 * PP;
+        asm volatile("" : "+v"(lane_off_odd[0]), "+v"(lane_off_odd[1]), "+v"(vzero));
+    }
+    // first tap row of this lane group's four slots of either half, + the data row + 1
+    const int s0 = 4 * g, s1 = 16 + 4 * g;
+    const int base0 = s0 - a.zrot + (s0 < a.zrot ? MF_Q : 0) + r16 + 1, base1 = s1 - a.zrot + (s1 < a.zrot ? MF_Q : 0) + r16 + 1;
+    int *const win = c.s_acc + (c.rt >> 1) * RG_AS;
+    const v4i_t zero4 = {0, 0, 0, 0};
+    int slot = 0;
+    for (int r = 0; r < c.rounds; ++r) {
+        asm volatile("s_barrier" ::: "memory");
+        const int t = 2 * r + c.cp;
+        if (t < c.tiles) {
+            const char *la = c.smem + (slot * 2 + c.cp) * SLOT + lane_off;
+            const char *lb = c.smem + (slot * 2 + c.cp) * SLOT;
+            v4i_t hh[NC ? NC : 1][2], ll[NC ? NC : 1][2];
+            long df[2] = {};
+            v4i_t z[2], a1[2], a2[2];  // per data-row half bj: S2 of tap-row half 0; S1, S2 of half 1
+            auto fetch = [&](int ch) {  // `ch` is a compile-time constant at every call site
+                if (ch < NC) {
+#pragma unroll
+                    for (int bj = 0; bj < 2; ++bj) {
+                        hh[ch][bj] = *reinterpret_cast<const v4i_t *>(la + 16 * PP * bj + 64 * ch);
+                        ll[ch][bj] = *reinterpret_cast<const v4i_t *>(la + 32 * PP + 16 * PP * bj + 64 * ch);
+                    }
+                } else {
+                    df[0] = *reinterpret_cast<const long *>(lb + lane_off_odd[0]);
+                    df[1] = *reinterpret_cast<const long *>(lb + lane_off_odd[1]);
+                }
+            };
+            auto mf64 = [](v4i_t x, v4i_t y, v4i_t zz) { return __builtin_amdgcn_mfma_i32_16x16x64_i8(x, y, zz, 0, 0, 0); };
+            auto mf32 = [](long x, long y, v4i_t zz) { return __builtin_amdgcn_mfma_i32_16x16x32_i8(x, y, zz, 0, 0, 0); };
+            fetch(0);
+#pragma unroll
+            for (int ch = 0; ch < NC; ++ch) {
+                if (ch + 1 < NC + ODD) fetch(ch + 1);
+                const bool first = ch == 0;  // (an accumulator's uses lie at least two instructions apart)
+                z[0] = mf64(t20[ch], hh[ch][0], first ? zero4 : z[0]);
+                a1[0] = mf64(t1[ch][0], hh[ch][0], first ? zero4 : a1[0]);
+                a2[0] = mf64(t1[ch][0], ll[ch][0], first ? zero4 : a2[0]);
+                z[1] = mf64(t20[ch], hh[ch][1], first ? zero4 : z[1]);
+                a1[1] = mf64(t1[ch][0], hh[ch][1], first ? zero4 : a1[1]);
+                a2[1] = mf64(t1[ch][0], ll[ch][1], first ? zero4 : a2[1]);
+                a2[0] = mf64(t1[ch][1], hh[ch][0], a2[0]);
+                a2[1] = mf64(t1[ch][1], hh[ch][1], a2[1]);
+            }
+            if constexpr (ODD) {
+#pragma unroll
+                for (int bj = 0; bj < 2; ++bj) {
+                    z[bj] = mf32(tf[TF_Z_Q20], df[bj], NC == 0 ? zero4 : z[bj]);
+                    a1[bj] = mf32(tf[TF_Z_Q11], df[bj], NC == 0 ? zero4 : a1[bj]);
+                    a2[bj] = mf32(tf[TF_Q11_Q21], df[bj], NC == 0 ? zero4 : a2[bj]);
+                }
+            }
+            // diagonal scatter, ds_add_u32 in inline asm as in ring_main_h16: half 0 sends S2 alone
+            const unsigned p0 = lds_addr(win + ((t * 32 + base0) & (RG_W - 1))), p1 = lds_addr(win + ((t * 32 + base1) & (RG_W - 1)));
+#pragma unroll
+            for (int bj = 0; bj < 2; ++bj)
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const int comb = z[bj][q] + vzero;
+                    asm volatile("ds_add_u32 %0, %1 offset:%2" ::"v"(p0), "v"(comb), "n"(4 * (16 * bj + q)));
+                }
+#pragma unroll
+            for (int bj = 0; bj < 2; ++bj)
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const int comb = (a1[bj][q] << 8) + a2[bj][q];
+                    asm volatile("ds_add_u32 %0, %1 offset:%2" ::"v"(p1), "v"(comb), "n"(4 * (16 * bj + q)));
+                }
+        }
+        slot ^= 1;
+    }
+    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
+}
+
 // One block = one contiguous range of outputs of any length (the host gives every CU one range): a persistent
 // stream through the ring, sums in a 512-position sliding window, outputs emitted two rounds behind the matrix work.
 // SKIPK (kernels of launches in which some lanes have high-byte-only taps, see ring_main's SKIP): lane pairs -- the pair's
 // first lane (parity 0) skips the q2*hi product at compile time, the second never does (the host pairs a tap-row group's
 // high-byte lane with its residue lane); one lane per workgroup -- every wave asks its lane's flag.
-template <int KS, bool ACC64, bool ROWS, bool U8, bool PAIR = false, bool SKIPK = false, bool HALF = false, bool ONCE = false>
+template <int KS, bool ACC64, bool ROWS, bool U8, bool PAIR = false, bool SKIPK = false, bool HALF = false, bool ONCE = false, bool ZEDGE = false>
 __device__ __forceinline__ void ring_block(const MfmaArgs &a, long long range_idx)
 {
     using G = RingGeo<KS, ROWS, U8, PAIR, HALF>;
@@ -1028,6 +1166,11 @@ __device__ __forceinline__ void ring_block(const MfmaArgs &a, long long range_id
     c.lane = tid & 63;
     c.rt = wave & 3;
     c.cp = wave >= RG_WAVES ? (wave - RG_WAVES) & 1 : (wave >> 2) & 1;  // (loader waves: their parity, or the lane of a pair they emit)
+    // ZEDGE: the multiplying waves of parity 1 take rt ^ 1, so that every SIMD hosts one light (even rt) and one heavy wave:
+    // 8 + 12 instead of 12 + 12 matrix instructions per chunk on each.  Waves w and w + 4 share a SIMD -- read back from
+    // HW_ID by probe/kstep_probe.hip `zedge` (SIMD_ID of waves 0..11: 2 1 3 0 2 1 3 0 2 1 3 0 on one box, 1 3 0 2 ... on another)
+    if constexpr (ZEDGE)
+        if (wave < RG_WAVES) c.rt ^= c.cp;
     c.col = c.lane & 31;
     c.h = c.lane >> 5;
 
@@ -1079,7 +1222,7 @@ __device__ __forceinline__ void ring_block(const MfmaArgs &a, long long range_id
         static_assert(!ROWS && !U8 && !PAIR && !ACC64 && !SKIPK, "16x16x64 tiles: single lanes over contiguous byte-plane slots, int32 sums");
         __syncthreads();
         c.stream0 = stream;
-        ring_main_h16<KS>(a, c);
+        ring_main_h16<KS, ZEDGE>(a, c);
     } else {
     // tap fragments of this wave's row tile: registers for the whole block
     v4i_t fq[KS][2];
@@ -1146,7 +1289,7 @@ struct RingMultiArgs {
     MfmaLane lane[RG_MAX_LANES];
 };
 
-template <int KS, bool ROWS, bool U8, bool PAIR = false, bool ACC64 = false, bool SKIPK = false, bool HALF = false, bool ONCE = false>
+template <int KS, bool ROWS, bool U8, bool PAIR = false, bool ACC64 = false, bool SKIPK = false, bool HALF = false, bool ONCE = false, bool ZEDGE = false>
 __device__ __forceinline__ void ring_multi_block(const RingMultiArgs &m)
 {
     const int idx = blockIdx.x >> 3;
@@ -1179,6 +1322,7 @@ __device__ __forceinline__ void ring_multi_block(const RingMultiArgs &m)
     a.rotate = l.rotate;
     a.raw_partials = l.raw_partials;
     a.high_taps_only = l.high_taps_only;
+    a.zrot = l.zrot;
     if constexpr (PAIR) {
         // the pair's first lane has the larger (or the same) tap-row group: ITS stream is staged, the second lane's own
         // tiles arrive 2 rounds per group of difference later; a pair without a second lane (afrag NULL) idles that half
@@ -1195,7 +1339,7 @@ __device__ __forceinline__ void ring_multi_block(const RingMultiArgs &m)
         a.pace_slot = static_cast<int>(range_idx) * units + idx % units;
     }
     if (range_idx * a.range >= a.n_out) return;  // (the last ranges of a short launch)
-    ring_block<KS, ACC64, ROWS, U8, PAIR, SKIPK, HALF, ONCE>(a, range_idx);
+    ring_block<KS, ACC64, ROWS, U8, PAIR, SKIPK, HALF, ONCE, ZEDGE>(a, range_idx);
 }
 
 // ACC64: one int64 (S1 << 32) + S2 per output component instead of one int32 256*S1 + S2 -- 16-bit taps without the int32
@@ -1209,12 +1353,14 @@ __global__ __launch_bounds__((RingGeo<KS, false>::THREADS), (RingGeo<KS, false>:
 }
 
 // ... for rows whose last k step is at most half full (rows of 32 (KS - 1) + 1 .. 16 values: D = 104 -> 208 = 6 x 32 + 16),
-// on 16x16x64 matrix tiles (ring_main_h16).
-template <int KS, bool ONCE = false>
+// on 16x16x64 matrix tiles (ring_main_h16).  ZEDGE (single-lane launches whose lane carries zrot != 0): the all-zero high
+// tap bytes of the filter's edge rows are not multiplied (ring_main_h16_light).
+template <int KS, bool ONCE = false, bool ZEDGE = false>
 __global__ __launch_bounds__((RingGeo<KS, false, false, false, true>::THREADS), 3) void k_channelize_mfma_s16_ring_multi_half(RingMultiArgs m)
 {
     static_assert(RingGeo<KS, false, false, false, true>::SPLIT, "byte-plane kernels only");
-    ring_multi_block<KS, false, false, false, false, false, true, ONCE>(m);
+    static_assert(!ZEDGE || ONCE, "rotated fragments: single-lane launches");
+    ring_multi_block<KS, false, false, false, false, false, true, ONCE, ZEDGE>(m);
 }
 
 // Two lanes per workgroup (RingGeo PAIR): the lanes of the table in pairs of equal tap-row group.
@@ -1257,10 +1403,14 @@ static int ring_launch_kernel(K kernel, const char *name, int threads, const A &
     return check_launch(name);
 }
 
+// the kernel family the calling thread's last multi-lane launch took (mfma_ring_last_kernel: tests ask which body ran)
+static thread_local const char *g_ring_last_kernel = "";
+
 template <int KS>
 static int ring_launch_multi(const RingMultiArgs &m, unsigned blocks, size_t lds, hipStream_t stream, bool rows, bool u8, bool acc64, bool skipk)
 {
-    static std::atomic<unsigned long long> done[10] = {{0}, {0}, {0}, {0}, {0}, {0}, {0}, {0}, {0}, {0}};
+    g_ring_last_kernel = "another ring kernel";
+    static std::atomic<unsigned long long> done[11] = {{0}, {0}, {0}, {0}, {0}, {0}, {0}, {0}, {0}, {0}, {0}};
     // a single lane: one workgroup streams each range, nobody fetches a byte of the capture twice -- the variants whose
     // loaders stream it with nt loads (traces show them as <KS, false, false, true> and ..._multi_half<KS, true>)
     const bool once = m.n_lanes == 1;
@@ -1291,6 +1441,12 @@ static int ring_launch_multi(const RingMultiArgs &m, unsigned blocks, size_t lds
         const int rem = (2 * m.c.D) & 31;  // values in the row's last k step
         if (rem != 0 && rem <= 16) {  // (planes at a pitch of their own: this family's LDS, not the caller's figure)
             using GH = RingGeo<KS, false, false, false, true>;
+            // rotated fragments (mfma_ring_zedge_supported): the variant that skips the zero high tap bytes of slots 0..15
+            if (once && m.lane[0].zrot) {
+                g_ring_last_kernel = "k_channelize_mfma_s16_ring_multi_half<KS, ONCE, ZEDGE>";
+                return ring_launch_kernel(k_channelize_mfma_s16_ring_multi_half<KS, true, true>, "k_channelize_mfma_s16_ring_multi", GH::THREADS, m, blocks, GH::LDS_BYTES, stream, done[10]);
+            }
+            g_ring_last_kernel = once ? "k_channelize_mfma_s16_ring_multi_half<KS, ONCE>" : "k_channelize_mfma_s16_ring_multi_half<KS>";
             if (once) return ring_launch_kernel(k_channelize_mfma_s16_ring_multi_half<KS, true>, "k_channelize_mfma_s16_ring_multi", GH::THREADS, m, blocks, GH::LDS_BYTES, stream, done[9]);
             return ring_launch_kernel(k_channelize_mfma_s16_ring_multi_half<KS>, "k_channelize_mfma_s16_ring_multi", GH::THREADS, m, blocks, GH::LDS_BYTES, stream, done[7]);
         }
@@ -1449,6 +1605,13 @@ int mfma_ring_launch_multi(const MfmaArgs &a, const MfmaLane *lanes, int n_lanes
     // so it is taken only when every first lane is high-byte-only and no second lane is (what the host's pairing of a
     // tap-row group's two lanes gives); otherwise nothing is skipped.  One lane per workgroup: the variant that asks the
     // lane's flag, when any lane has it.
+    // rotated fragments are for the one kernel that knows the rotation; any other would multiply the wrong rows
+    for (int i = 0; i < n_lanes; ++i)
+        if (lanes[i].zrot != 0 && !(n_lanes == 1 && !pairs && !lanes[i].high_taps_only && (lanes[i].zrot & 3) == 0 && lanes[i].zrot <= 32 &&
+                                    mfma_ring_zedge_supported(a.D, a.k_first, a.ksteps, rows, u8, acc64))) {
+            set_error("lane %d: rotated tap fragments (rot %d) need a single-lane launch of the half-step kernels (iqa_mfma_ring_zero_rows) and a rot of 4, 8 .. 32", i, lanes[i].zrot);
+            return IQA_EINVAL;
+        }
     bool skipk = false;
     if (!u8) {
         if (pairs) {
@@ -1476,6 +1639,15 @@ int mfma_ring_launch_multi(const MfmaArgs &a, const MfmaLane *lanes, int n_lanes
     return with_ks<1, RG_MAX_KS>(a.ksteps, [&](auto k) {
         return ring_launch_multi<decltype(k)::value>(m, blocks, lds, stream, rows, u8, acc64, skipk);
     });
+}
+
+const char *mfma_ring_last_kernel() { return g_ring_last_kernel; }
+
+// A single-lane launch over these k steps takes k_channelize_mfma_s16_ring_multi_half (whose ZEDGE variant reads rotated fragments)
+bool mfma_ring_zedge_supported(int decimation, int k_first, int k_count, bool rows, bool u8, bool acc64)
+{
+    const int rem = (2 * decimation) & 31;
+    return !rows && !u8 && !acc64 && mfma_ring_mode(decimation, k_first, k_count, acc64, u8) == 1 && k_count <= 8 && rem != 0 && rem <= 16;
 }
 
 }  // namespace iqa

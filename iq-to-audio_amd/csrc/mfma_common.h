@@ -46,6 +46,9 @@ struct MfmaArgs {
     unsigned int *pace;
     unsigned int pace_token;
     int pace_slot, pace_units;
+    // half-step ring kernels, single-lane launches: the tap rows of either component are rotated by zrot slots (slot s holds
+    // tap row (s - zrot) mod 64) so that slots 0..15 are rows whose high tap byte is zero (dsp_plan's afrag_rot); 0: not rotated
+    int zrot;
 };
 
 // The last steps of every matrix-core emission, written with explicit roundings so that the kernels that share them
@@ -120,9 +123,12 @@ struct MfmaLane {
     double rot64_re, rot64_im;
     float sc_re, sc_im;
     int col_shift, finalize, conj_sum, rotate, raw_partials, high_taps_only;
+    int zrot;  // MfmaArgs::zrot
 };
 int mfma_ring_launch_multi(const MfmaArgs &common, const MfmaLane *lanes, int n_lanes, size_t lds_bytes, hipStream_t stream, bool rows,
                            bool u8, bool pairs, bool acc64);
+bool mfma_ring_zedge_supported(int decimation, int k_first, int k_count, bool rows, bool u8, bool acc64);  // a single-lane launch takes rotated fragments
+const char *mfma_ring_last_kernel();  // the kernel family of the calling thread's last multi-lane launch
 bool mfma_ring_pairs_supported(int decimation, int k_first, int k_count, bool u8, bool acc64 = false);  // two lanes per workgroup (contiguous slots, no loader waves)
 
 }  // namespace iqa

@@ -10,6 +10,8 @@
 //   kstep_probe shape [seconds] [pairs]: the 32x32x32 tile body against the 16x16x64 one at the same tile per wave (wall
 //     time, in-kernel clock, equal sums) and the bare issue rates of the four int8 forms -- see k_probe_shape
 //   kstep_probe fold [seconds] [pairs]: the 16x16x64 body against the same with its odd last k step folded along K
+//   kstep_probe zedge [seconds] [pairs]: the folded body against the same with the all-zero high tap bytes of a Kaiser
+//     filter's edge rows skipped (light and heavy waves paired per SIMD), and against the pairing alone -- see sh_zedge_wave
 //   kstep_probe lds: the LDS access patterns of the bodies, one kernel each, for a counters-only profiler run
 #include <hip/hip_runtime.h>
 
@@ -386,8 +388,200 @@ __device__ __forceinline__ unsigned sh_hash(unsigned x)
     return x;
 }
 
+// ---- `zedge`: BODY 2 with the all-zero high tap bytes of a Kaiser filter's edge rows skipped --------------------------
+// The first and last tap rows of a Kaiser design are tiny: with T = 256 q1 + q2 their q1 is zero, and of a row's three
+// products only q2 * hi is left.  Config 2's plan has 22 such rows per component, cyclically contiguous (q - 1 = 52..63,
+// 0..9); rotated by `rot` = 12 slots (slot s of a component holds tap row (s - rot) mod 64) the first 16-row block of either
+// component is free of q1.  A wave of even rt (LIGHT) then runs, per 64-value chunk,
+//         Z[bj] = q2_0 . hi_bj                          (block 0: the zero-q1 rows, S2 alone, no S1)
+//         S1[bj] = q1_1 . hi_bj      S2[bj] = q1_1 . lo_bj + q2_1 . hi_bj      (block 1, as before)
+// eight instructions instead of twelve, and on the folded odd step six instead of seven, from two of the four 8-byte reads:
+//         Z[bj] = [0 | q2_0] . [lo_bj ; hi_bj]    S1[bj] = [0 | q1_1] . [lo_bj ; hi_bj]    S2[bj] = [q1_1 | q2_1] . [lo_bj ; hi_bj]
+// 30 matrix instructions per tile against 43.  Block 0's rows are two runs (the filter's last rows, then its first), so
+// its scatter base differs per lane group (rot a multiple of 4, at most 16) and it shares no positions with block 1: 16
+// adds per tile for a light wave, 12 for a heavy one (odd rt: BODY 2's tile, its rows moved by the rotation).
+// PAIRING: the waves of parity 1 take rt ^ 1, so that every SIMD (wave index mod 4, read back from HW_ID below) hosts one
+// light and one heavy wave.  BODY 3: both; BODY 4: the pairing alone, every wave heavy, rot = 0.
+template <bool LIGHT>
+__device__ __forceinline__ void sh_zedge_wave(const v4i *afrag, const char *slot, int *s_acc, int rt, int cp, int lane, int tiles, int rot,
+                                              unsigned long long (&clk)[4])
+{
+    constexpr int KS = SH_KS, NC = KS / 2, PP = 32 * SH_KS;
+    const int r16 = lane & 15, g = lane >> 4, up = g >> 1;
+    const v4i *fa = afrag + rt * 128;
+    auto frag = [&](int c, int bi, int pc) { return fa[((2 * c + (g >> 1)) * 8 + pc) * 64 + 16 * bi + r16 + 32 * (g & 1)]; };
+    auto last = [&](int bi, int pc) { return reinterpret_cast<const long *>(fa + ((KS - 1) * 8 + pc) * 64 + 16 * bi + r16)[g & 1]; };
+    const char *la = slot + r16 * PP + 16 * g;
+    const int at = r16 * PP + 32 * (KS - 1) + 8 * (g & 1), lo_pl = 32 * PP, bj1 = 16 * PP;
+    const v4i zero4 = {0, 0, 0, 0};
+    auto mf64 = [](v4i x, v4i y, v4i z) { return __builtin_amdgcn_mfma_i32_16x16x64_i8(x, y, z, 0, 0, 0); };
+    auto mf32 = [](long x, long y, v4i z) { return __builtin_amdgcn_mfma_i32_16x16x32_i8(x, y, z, 0, 0, 0); };
+    auto win = [&](int at_pos) {
+        return static_cast<unsigned>(reinterpret_cast<size_t>((__attribute__((address_space(3))) const void *)(s_acc + (at_pos & 511) + (rt >> 1) * SH_AS)));
+    };
+    if constexpr (LIGHT) {
+        v4i t20[NC], t1[NC][2];  // q2 of tap-row half 0; q1, q2 of half 1
+        long tf[3];
+        enum { TF_Z_Q20, TF_Z_Q11, TF_Q11_Q21 };
+#pragma unroll
+        for (int c = 0; c < NC; ++c) t20[c] = frag(c, 0, 1), t1[c][0] = frag(c, 1, 0), t1[c][1] = frag(c, 1, 1);
+        {
+            const long q20 = last(0, 1), q11 = last(1, 0), q21 = last(1, 1);
+            tf[TF_Z_Q20] = up ? q20 : 0;
+            tf[TF_Z_Q11] = up ? q11 : 0;
+            tf[TF_Q11_Q21] = up ? q21 : q11;
+        }
+        int odd_off[2] = {at + (up ? 0 : lo_pl), at + bj1 + (up ? 0 : lo_pl)};  // [lo_0 ; hi_0], [lo_1 ; hi_1]
+        int vzero = 0;  // (a zero the compiler cannot see through)
+        asm volatile("" : "+v"(odd_off[0]), "+v"(odd_off[1]), "+v"(vzero));
+        // block 0's rows: slots 4 g .. + 3 are tap rows 64 - rot + 4 g .. of the component while 4 g < rot, 4 g - rot .. behind
+        const int base0 = cp * 32 + r16 + 4 * g + (4 * g < rot ? 64 - rot : -rot) + 1, base1 = cp * 32 + r16 + 4 * g + 16 - rot + 1;
+        clk[0] = __builtin_amdgcn_s_memtime(), clk[1] = __builtin_amdgcn_s_memrealtime();
+        for (int t = 0; t < tiles; ++t) {
+            asm volatile("s_barrier" ::: "memory");
+            v4i hh[NC][2], ll[NC][2];
+            long df[2];
+            v4i z[2], a1[2], a2[2];
+            auto fetch = [&](int c) {
+                if (c < NC) {
+#pragma unroll
+                    for (int bj = 0; bj < 2; ++bj) {
+                        hh[c][bj] = *reinterpret_cast<const v4i *>(la + 16 * PP * bj + 64 * c);
+                        ll[c][bj] = *reinterpret_cast<const v4i *>(la + 32 * PP + 16 * PP * bj + 64 * c);
+                    }
+                } else {
+                    df[0] = *reinterpret_cast<const long *>(slot + odd_off[0]);
+                    df[1] = *reinterpret_cast<const long *>(slot + odd_off[1]);
+                }
+            };
+            fetch(0);
+#pragma unroll
+            for (int c = 0; c < NC; ++c) {
+                fetch(c + 1);
+                const bool first = c == 0;
+                z[0] = mf64(t20[c], hh[c][0], first ? zero4 : z[0]);
+                a1[0] = mf64(t1[c][0], hh[c][0], first ? zero4 : a1[0]);
+                a2[0] = mf64(t1[c][0], ll[c][0], first ? zero4 : a2[0]);
+                z[1] = mf64(t20[c], hh[c][1], first ? zero4 : z[1]);
+                a1[1] = mf64(t1[c][0], hh[c][1], first ? zero4 : a1[1]);
+                a2[1] = mf64(t1[c][0], ll[c][1], first ? zero4 : a2[1]);
+                a2[0] = mf64(t1[c][1], hh[c][0], a2[0]);
+                a2[1] = mf64(t1[c][1], hh[c][1], a2[1]);
+            }
+#pragma unroll
+            for (int bj = 0; bj < 2; ++bj) {
+                z[bj] = mf32(tf[TF_Z_Q20], df[bj], z[bj]);
+                a1[bj] = mf32(tf[TF_Z_Q11], df[bj], a1[bj]);
+                a2[bj] = mf32(tf[TF_Q11_Q21], df[bj], a2[bj]);
+            }
+            const unsigned p0 = win(t * 64 + base0), p1 = win(t * 64 + base1);
+#pragma unroll
+            for (int bj = 0; bj < 2; ++bj)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    // through a VALU instruction the compiler sees: it places the wait states a matrix result needs in front of
+                    // its own instructions, not in front of inline asm (fed directly, these adds sent stale registers)
+                    const int comb = z[bj][r] + vzero;
+                    asm volatile("ds_add_u32 %0, %1 offset:%2" ::"v"(p0), "v"(comb), "n"(4 * (16 * bj + r)));
+                }
+#pragma unroll
+            for (int bj = 0; bj < 2; ++bj)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int comb = (a1[bj][r] << 8) + a2[bj][r];
+                    asm volatile("ds_add_u32 %0, %1 offset:%2" ::"v"(p1), "v"(comb), "n"(4 * (16 * bj + r)));
+                }
+        }
+    } else {
+        v4i tq[NC][2][2];
+        long tl[2][2], tf[6];
+        enum { TF_Z_Q10, TF_Q10_Q11, TF_Z_Q11, TF_Q10_Q20, TF_Q20_Q21, TF_Q11_Q21 };
+        enum { DF_L0_H0, DF_L1_L0, DF_H1_H0, DF_L1_H1 };
+#pragma unroll
+        for (int c = 0; c < NC; ++c)
+#pragma unroll
+            for (int bi = 0; bi < 2; ++bi)
+#pragma unroll
+                for (int pc = 0; pc < 2; ++pc) tq[c][bi][pc] = frag(c, bi, pc);
+#pragma unroll
+        for (int bi = 0; bi < 2; ++bi)
+#pragma unroll
+            for (int pc = 0; pc < 2; ++pc) tl[bi][pc] = last(bi, pc);
+        tf[TF_Z_Q10] = up ? tl[0][0] : 0;
+        tf[TF_Q10_Q11] = up ? tl[1][0] : tl[0][0];
+        tf[TF_Z_Q11] = up ? tl[1][0] : 0;
+        tf[TF_Q10_Q20] = up ? tl[0][1] : tl[0][0];
+        tf[TF_Q20_Q21] = up ? tl[1][1] : tl[0][1];
+        tf[TF_Q11_Q21] = up ? tl[1][1] : tl[1][0];
+        int odd_off[4];
+        odd_off[DF_L0_H0] = at + (up ? 0 : lo_pl);
+        odd_off[DF_L1_L0] = at + lo_pl + (up ? 0 : bj1);
+        odd_off[DF_H1_H0] = at + (up ? 0 : bj1);
+        odd_off[DF_L1_H1] = at + bj1 + (up ? 0 : lo_pl);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) asm volatile("" : "+v"(odd_off[i]));
+        const int base = cp * 32 + (rt & 1) * 32 - rot + r16 + 4 * g + 1;  // (odd rt whenever rot != 0)
+        clk[0] = __builtin_amdgcn_s_memtime(), clk[1] = __builtin_amdgcn_s_memrealtime();
+        for (int t = 0; t < tiles; ++t) {
+            asm volatile("s_barrier" ::: "memory");
+            v4i hh[NC][2], ll[NC][2];
+            long df[4];
+            v4i a1[3], a2[3];
+            auto fetch = [&](int c) {
+                if (c < NC) {
+#pragma unroll
+                    for (int bj = 0; bj < 2; ++bj) {
+                        hh[c][bj] = *reinterpret_cast<const v4i *>(la + 16 * PP * bj + 64 * c);
+                        ll[c][bj] = *reinterpret_cast<const v4i *>(la + 32 * PP + 16 * PP * bj + 64 * c);
+                    }
+                } else {
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) df[i] = *reinterpret_cast<const long *>(slot + odd_off[i]);
+                }
+            };
+            fetch(0);
+#pragma unroll
+            for (int c = 0; c < NC; ++c) {
+                fetch(c + 1);
+                const bool first = c == 0;
+                const auto &q = tq[c];
+                const auto &hi = hh[c];
+                const auto &lw = ll[c];
+                a2[1] = mf64(q[0][0], lw[1], first ? zero4 : a2[1]);
+                a1[0] = mf64(q[0][0], hi[0], first ? zero4 : a1[0]);
+                a2[0] = mf64(q[0][0], lw[0], first ? zero4 : a2[0]);
+                a2[1] = mf64(q[1][0], lw[0], a2[1]);
+                a1[1] = mf64(q[0][0], hi[1], first ? zero4 : a1[1]);
+                a1[2] = mf64(q[1][0], hi[1], first ? zero4 : a1[2]);
+                a2[1] = mf64(q[0][1], hi[1], a2[1]);
+                a2[2] = mf64(q[1][0], lw[1], first ? zero4 : a2[2]);
+                a1[1] = mf64(q[1][0], hi[0], a1[1]);
+                a2[1] = mf64(q[1][1], hi[0], a2[1]);
+                a2[0] = mf64(q[0][1], hi[0], a2[0]);
+                a2[2] = mf64(q[1][1], hi[1], a2[2]);
+            }
+            a1[0] = mf32(tf[TF_Z_Q10], df[DF_L0_H0], a1[0]);
+            a2[1] = mf32(tf[TF_Q10_Q11], df[DF_L1_L0], a2[1]);
+            a1[1] = mf32(tf[TF_Q10_Q11], df[DF_H1_H0], a1[1]);
+            a2[0] = mf32(tf[TF_Q10_Q20], df[DF_L0_H0], a2[0]);
+            a2[1] = mf32(tf[TF_Q20_Q21], df[DF_H1_H0], a2[1]);
+            a1[2] = mf32(tf[TF_Z_Q11], df[DF_L1_H1], a1[2]);
+            a2[2] = mf32(tf[TF_Q11_Q21], df[DF_L1_H1], a2[2]);
+            const unsigned p = win(t * 64 + base);
+#pragma unroll
+            for (int s = 0; s < 3; ++s)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int comb = (a1[s][r] << 8) + a2[s][r];
+                    asm volatile("ds_add_u32 %0, %1 offset:%2" ::"v"(p), "v"(comb), "n"(4 * (16 * s + r)));
+                }
+        }
+    }
+    clk[2] = __builtin_amdgcn_s_memtime(), clk[3] = __builtin_amdgcn_s_memrealtime();
+}
+
 template <int BODY>
-__global__ __launch_bounds__(768, 3) void k_probe_shape(const v4i *afrag, int *win_out, int tiles, unsigned long long *clk)
+__global__ __launch_bounds__(768, 3) void k_probe_shape(const v4i *afrag, int *win_out, int tiles, unsigned long long *clk, int rot = 0)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     using G = ShapeGeo<BODY>;
@@ -401,11 +595,16 @@ __global__ __launch_bounds__(768, 3) void k_probe_shape(const v4i *afrag, int *w
     }
     for (int i = tid; i < 2 * SH_AS; i += 768) s_acc[i] = 0;
     __syncthreads();
-    const int rt = wave & 3, cp = (wave >> 2) & 1, h = lane >> 5, col = lane & 31;
+    const int cp = (wave >> 2) & 1, rt = BODY >= 3 ? (wave & 3) ^ cp : wave & 3, h = lane >> 5, col = lane & 31;
     const char *slot = smem + cp * G::SLOT;
     unsigned long long c0 = 0, r0 = 0, c1 = 0, r1 = 0;
     if (wave >= 8) {  // the loader waves' place: barriers only
         for (int t = 0; t < tiles; ++t) asm volatile("s_barrier" ::: "memory");
+    } else if constexpr (BODY >= 3) {
+        unsigned long long ck[4];
+        if (BODY == 3 && !(rt & 1)) sh_zedge_wave<true>(afrag, slot, s_acc, rt, cp, lane, tiles, rot, ck);
+        else sh_zedge_wave<false>(afrag, slot, s_acc, rt, cp, lane, tiles, rot, ck);
+        c0 = ck[0], r0 = ck[1], c1 = ck[2], r1 = ck[3];
     } else if constexpr (BODY == 0) {
         v4i fq[KS][2];
 #pragma unroll
@@ -582,6 +781,8 @@ __global__ __launch_bounds__(768, 3) void k_probe_shape(const v4i *afrag, int *w
         clk[2 * blockIdx.x] = c1 - c0;
         clk[2 * blockIdx.x + 1] = r1 - r0;
     }
+    // where the waves run: SIMD_ID of HW_ID (bits 5:4), one entry per wave of workgroup 0, behind the clocks
+    if (BODY >= 3 && lane == 0 && blockIdx.x == 0) clk[512 + wave] = __builtin_amdgcn_s_getreg(4 | (4 << 6) | (1 << 11));
     // the window this block leaves, folded over the guard's aliases: equal for the two bodies
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __syncthreads();
@@ -713,11 +914,12 @@ static int lds_main()
 struct ShapeResult {
     double ns_per_round, ghz;
     std::vector<int> win;
+    std::vector<unsigned long long> simd;
 };
 
 // `seconds` of back-to-back launches; the time and the in-kernel clock (median over workgroups) of the last batch
 template <int BODY>
-static ShapeResult run_shape(const v4i *afrag, int *win, unsigned long long *clk, int tiles, double seconds)
+static ShapeResult run_shape(const v4i *afrag, int *win, unsigned long long *clk, int tiles, double seconds, int rot = 0)
 {
     using G = ShapeGeo<BODY>;
     hipFuncSetAttribute(reinterpret_cast<const void *>(k_probe_shape<BODY>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
@@ -729,7 +931,7 @@ static ShapeResult run_shape(const v4i *afrag, int *win, unsigned long long *clk
     float ms = 0;
     while (total_ms < seconds * 1e3) {
         hipEventRecord(e0);
-        for (int i = 0; i < BATCH; ++i) hipLaunchKernelGGL((k_probe_shape<BODY>), dim3(256), dim3(768), G::LDS, 0, afrag, win, tiles, clk);
+        for (int i = 0; i < BATCH; ++i) hipLaunchKernelGGL((k_probe_shape<BODY>), dim3(256), dim3(768), G::LDS, 0, afrag, win, tiles, clk, rot);
         hipEventRecord(e1);
         if (hipEventSynchronize(e1) != hipSuccess) {
             printf("launch failed: %s\n", hipGetErrorString(hipGetLastError()));
@@ -748,9 +950,77 @@ static ShapeResult run_shape(const v4i *afrag, int *win, unsigned long long *clk
     r.ghz = ghz[128];
     r.win.resize(1024);
     hipMemcpy(r.win.data(), win, 1024 * 4, hipMemcpyDeviceToHost);
+    if (BODY >= 3) {  // (zedge_main's clock buffer has the room)
+        unsigned long long simd[12];
+        hipMemcpy(simd, clk + 512, sizeof simd, hipMemcpyDeviceToHost);
+        r.simd.assign(simd, simd + 12);
+    }
     hipEventDestroy(e0);
     hipEventDestroy(e1);
     return r;
+}
+
+// kstep_probe zedge [seconds per run] [pairs]: the folded 16x16x64 body (BODY 2) against the same with the zero-q1 edge rows
+// skipped and a light and a heavy wave on every SIMD (BODY 3), and against the pairing alone (BODY 4).  Taps: random bytes,
+// q1 zero in config 2's zero-q1 rows (q - 1 = 52..63 and 0..9 of either component); BODY 3 reads them rotated by 12 slots
+// and scatters every row to the position it had, so the three windows of sums must be equal.  Under a counters-only
+// profiler run (`kstep_probe zedge 0.01 1`) each body is a kernel name of its own.
+static int zedge_main(double seconds, int pairs)
+{
+    const int tiles = 20000, rot = 12;
+    std::vector<signed char> q(2 * 128 * 224), ha(SH_KS * 8 * 64 * 16), hr(ha.size());
+    unsigned seed = 12345u;
+    for (int pc = 0; pc < 2; ++pc)
+        for (int row = 0; row < 128; ++row)
+            for (int k = 0; k < 224; ++k) {
+                seed = seed * 1664525u + 1013904223u;
+                const int qm = row & 63;
+                const bool zero_q1 = qm >= 52 || qm < 10;
+                q[(pc * 128 + row) * 224 + k] = (k < 208 && !(pc == 0 && zero_q1)) ? static_cast<signed char>(seed >> 24) : 0;
+            }
+    for (int ks = 0; ks < SH_KS; ++ks)
+        for (int rp = 0; rp < 8; ++rp)
+            for (int l = 0; l < 64; ++l)
+                for (int j = 0; j < 16; ++j) {
+                    const int k = 32 * ks + 16 * (l >> 5) + j, pc = rp & 1, comp = rp >> 2, slot = 32 * ((rp >> 1) & 1) + (l & 31);
+                    const size_t at = ((ks * 8 + rp) * 64 + l) * 16 + j;
+                    ha[at] = q[(pc * 128 + comp * 64 + slot) * 224 + k];
+                    hr[at] = q[(pc * 128 + comp * 64 + ((slot - rot + 64) & 63)) * 224 + k];
+                }
+    v4i *afrag, *afrag_rot;
+    int *win;
+    unsigned long long *clk;
+    hipMalloc(&afrag, ha.size());
+    hipMalloc(&afrag_rot, hr.size());
+    hipMemcpy(afrag, ha.data(), ha.size(), hipMemcpyHostToDevice);
+    hipMemcpy(afrag_rot, hr.data(), hr.size(), hipMemcpyHostToDevice);
+    hipMalloc(&win, 1024 * 4);
+    hipMalloc(&clk, (512 + 16) * 8);
+    hipMemset(clk, 0, (512 + 16) * 8);
+    int bad = 0, slower = 0;
+    const ShapeResult ref = run_shape<0>(afrag, win, clk, tiles, 1e-3);  // (one batch: the 32x32x32 body's sums)
+    for (int p = 0; p < pairs; ++p) {
+        const ShapeResult a = run_shape<2>(afrag, win, clk, tiles, seconds);
+        const ShapeResult b = run_shape<3>(afrag_rot, win, clk, tiles, seconds, rot);
+        const ShapeResult c = run_shape<4>(afrag, win, clk, tiles, seconds);
+        int diff = 0, diff_pair = 0, diff_ref = 0, nonzero = 0;
+        for (int i = 0; i < 1024; ++i) diff += a.win[i] != b.win[i], diff_pair += a.win[i] != c.win[i], diff_ref += ref.win[i] != a.win[i], nonzero += a.win[i] != 0;
+        bad += diff + diff_pair + diff_ref + (nonzero < 512);
+        slower += !(b.ns_per_round < a.ns_per_round);
+        printf("pair %d: shipped body %.1f ns per round at %.3f GHz; zero-q1 blocks skipped + light/heavy pairing: %.1f ns at %.3f GHz, ratio %.4f; pairing "
+               "alone: %.1f ns at %.3f GHz, ratio %.4f; windows differ in %d / %d of 1024 sums, the shipped body's from the 32x32x32 body's in %d (%d nonzero, first %d)\n",
+               p, a.ns_per_round, a.ghz, b.ns_per_round, b.ghz, b.ns_per_round / a.ns_per_round, c.ns_per_round, c.ghz, c.ns_per_round / a.ns_per_round, diff,
+               diff_pair, diff_ref, nonzero, a.win[7]);
+        if (p == 0) {
+            printf("SIMD of waves 0..11 of workgroup 0 (HW_ID): with skipping");
+            for (int w = 0; w < 12; ++w) printf(" %llu", b.simd[w]);
+            printf("; pairing alone");
+            for (int w = 0; w < 12; ++w) printf(" %llu", c.simd[w]);
+            printf("\n");
+        }
+    }
+    printf("gate (wall per round lower in every pair): %s; sums %s\n", slower ? "NOT met" : "met", bad ? "DIFFER" : "equal");
+    return bad ? 1 : 0;
 }
 
 // kstep_probe shape [seconds per run] [pairs]; `fold`: the 16x16x64 body against the one with the folded odd step
@@ -810,6 +1080,7 @@ static int shape_main(double seconds, int pairs, bool fold)
 int main(int argc, char **argv)
 {
     if (argc > 1 && std::string(argv[1]) == "lds") return lds_main();
+    if (argc > 1 && std::string(argv[1]) == "zedge") return zedge_main(argc > 2 ? atof(argv[2]) : 2.0, argc > 3 ? atoi(argv[3]) : 5);
     if (argc > 1 && (std::string(argv[1]) == "shape" || std::string(argv[1]) == "fold"))
         return shape_main(argc > 2 ? atof(argv[2]) : 2.0, argc > 3 ? atoi(argv[3]) : 4, std::string(argv[1]) == "fold");
     const int tiles = argc > 1 ? atoi(argv[1]) : 20000;

@@ -180,6 +180,11 @@ class MfmaGroup:
     q: int = 0  # tap-row group (the data rows a lane of this group streams start 64*q rows earlier)
     residual: bool = False  # the taps of this group are the quantisation residue of the group in front of it
     high_only: bool = False  # every low tap byte q2 is zero: the ring kernels skip the q2*hi product (two MFMAs per k step)
+    #: ``rot`` != 0 (int32-sum groups of int16 plans, ``zero_high_rotation``): ``afrag_rot`` holds the same fragments with the
+    #: rows of either component rotated by ``rot`` slots -- slot s holds tap row (s - rot) mod 64 -- so that slots 0..15 are
+    #: rows whose high tap byte q1 is zero throughout; the half-step ring kernel then skips their q1 products.
+    rot: int = 0
+    afrag_rot: np.ndarray | None = None
 
 
 @dataclass
@@ -327,6 +332,45 @@ def _quantise_rows(a: np.ndarray, acc32: bool, high_byte_only: bool, col_ranges=
     return unit, t, q1, q2
 
 
+def zero_high_runs(q1: np.ndarray) -> list:
+    """Per component (re, im) of a 128-row high-byte matrix: (first row, length) of the largest CYCLIC run of rows whose q1
+    is zero throughout (rows past the filter's end are such rows); (0, 64) if all are, (0, 0) if none is."""
+    runs = []
+    for comp in range(2):
+        z = ~np.any(q1[comp * MFMA_Q : (comp + 1) * MFMA_Q], axis=1)
+        if z.all():
+            runs.append((0, MFMA_Q))
+            continue
+        best, start, length = (0, 0), 0, 0
+        for i in range(2 * MFMA_Q):  # twice around: a run that wraps is met whole
+            if z[i % MFMA_Q]:
+                if length == 0:
+                    start = i % MFMA_Q
+                length += 1
+                if length > best[1]:
+                    best = (start, length)
+            else:
+                length = 0
+        runs.append(best)
+    return runs
+
+
+def zero_high_rotation(q1: np.ndarray) -> int:
+    """The slot shift that puts the first 16 rows of the largest cyclic zero-q1 run into slots 0..15 of either component
+    (slot s holds tap row (s - rot) mod 64); 0 = not rotated: the run is shorter than 16 rows in a component, the two
+    components' runs differ, or the run starts at row 0 already."""
+    (s_re, n_re), (s_im, n_im) = zero_high_runs(q1)
+    if min(n_re, n_im) < 16 or (s_re, n_re) != (s_im, n_im):
+        return 0
+    return (MFMA_Q - s_re) % MFMA_Q
+
+
+def rotate_rows(x: np.ndarray, rot: int) -> np.ndarray:
+    """Rows of a [128, ...] tap matrix with either component rotated by ``rot`` slots: out[comp*64 + s] = x[comp*64 + (s - rot) % 64]."""
+    s = (np.arange(MFMA_Q) - rot) % MFMA_Q
+    return x[np.concatenate([s, MFMA_Q + s])]
+
+
 def plan_mfma(plan: ChannelPlan, acc32: bool = False, max_ksteps: int | None = None, residual: bool = False) -> MfmaPlan:
     """Quantise the (already NCO-rotated, scaled) taps to 16-bit fixed point and lay them out as
     the A operand of v_mfma_i32_32x32x32_i8.
@@ -396,6 +440,13 @@ def plan_mfma(plan: ChannelPlan, acc32: bool = False, max_ksteps: int | None = N
             frag[:, :, 0] = q1.reshape(-1)[flat]
             frag[:, :, 1] = q2.reshape(-1)[flat]
             groups.append(MfmaGroup(frag, unit, t, q=gi, residual=part == 1, high_only=bool(s16 and not np.any(q2))))
+            if acc32 and s16 and not residual:  # (the "fine" groups are not covered)
+                rot = zero_high_rotation(q1)
+                if rot:
+                    frag_rot = np.empty_like(frag)
+                    frag_rot[:, :, 0] = rotate_rows(q1, rot).reshape(-1)[flat]
+                    frag_rot[:, :, 1] = rotate_rows(q2, rot).reshape(-1)[flat]
+                    groups[-1].rot, groups[-1].afrag_rot = rot, frag_rot
             for ci in range(n_chunks):
                 k0, k1 = bounds[ci], bounds[ci + 1]
                 sl = t[:, 32 * k0 : 32 * k1]
